@@ -10,6 +10,12 @@ Workload (config.workload): the configuration BASELINE.json's metric is quoted o
 horizon N = 20, batch 8192 per GPU, each instance linearised about its own perturbed hover trajectory
 (reference formulation n = 332, m = 560).  Weak scaling: every rank solves its
 own 8192 instances (seed 2024 + rank); no collective on the data path, one gather of the solutions at the end.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the roofline of the
+timed kernels).  --full adds the legs beside the headline, each with runs of its own after the timed region: the other
+BASELINE configurations, the device SQP iteration, the dispatch hint, the reduced form, the PCIe-inclusive steps, the CPU
+baseline and oracle parity.  --dump-outputs DIR writes what the last timed step returned (x, y, status, iters) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -169,6 +175,25 @@ def sqp_iteration_device(workload, N, batch, seed, dev, reps=5):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """write each (batch, ...) host array as <path>/<name>.npy in float64: whole when all of them fit in `limit` bytes, else the same fixed,
+    seeded sample of instances (rows, in batch order) from every array, with the sampled row indices in <path>/instance.npy"""
+    arrays = {k: np.asarray(a, dtype=np.float64) for k, a in arrays.items()}
+    batch = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // batch for a in arrays.values())
+    if row_bytes * batch > limit:
+        rows = np.sort(np.random.default_rng(seed).choice(batch, limit // (row_bytes + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["instance"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def algorithmic_bytes_per_solve(nnzP_triu, nnzA, n, m, warm=False):
     """compulsory traffic with the iteration resident on-chip."""
     b = 8 * (nnzP_triu + nnzA + n + 2 * m) + 8 * (n + m) + 16
@@ -187,13 +212,20 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="QP instances per GPU")
     ap.add_argument("--cpu-sample", type=int, default=None, help="QPs timed on the host for cpu_baseline (rank 0, N=1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="timed region only: skip the in-order, PCIe-inclusive and CPU-baseline legs (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip its legs all the same (a plain run never runs them)")
+    ap.add_argument("--full", action="store_true", help="after the headline, the legs beside it: other configurations, SQP iteration, dispatch hint, reduced form, "
+                                                        "PCIe-inclusive steps, CPU baseline and oracle parity (rank 0, one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write x, y, status, iters of the last timed step as DIR/<name>.npy (float64; rank 0's shard; "
+                                                                       "a fixed, seeded sample of instances beyond 64 MB)")
     # diagnostics (not used by the driver): force a kernel family / an exact ADMM iteration count
     ap.add_argument("--variant", default=None, choices=["stream", "res1", "res2", "res4", "res8", "gres4", "gres2", "oc4", "oc8"])
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal of the N > 1 flow on a one-GPU box: all ranks use cuda:0, collectives over gloo")
     ap.add_argument("--reduced", action="store_true", help="opt-in reduced form (mpcqp_create_reduced): the parameter rows dp = 0 named as fixed; not the headline configuration")
     ap.add_argument("--force-iters", type=int, default=None, help="run exactly this many ADMM iterations (eps = 0, no adaptive rho)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
 
     if args.variant:
         os.environ["MPCQP_VARIANT"] = args.variant
@@ -270,6 +302,9 @@ def main():
     kernel_ms = [e0.elapsed_time(e1) for e0, e1 in evs]
     kernel_ms_last_lib = qp.last_kernel_ms()         # the library's own events around the solve kernels alone, last step
     setup_ms_last, iter_ms_last = qp.last_phase_ms()  # ... and split by the reference's two calls (on-chip mode: set-up kernel / iteration kernel)
+    if args.dump_outputs and rank == 0:
+        # what mpcqp_get handed the caller in the last timed step, before any leg of --full re-solves into the same buffers
+        dump_outputs(args.dump_outputs, {"x": ox.cpu().numpy(), "y": oy.cpu().numpy(), "status": ost.cpu().numpy(), "iters": oit.cpu().numpy()})
 
     iters = oit.cpu().numpy(); status = ost.cpu().numpy()
     solved_local = int((status == 1).sum())
@@ -335,7 +370,7 @@ def main():
         if collective is not None:
             out["collective"] = collective
         out["lib_sha16"] = lib_sha16()
-        if world == 1 and not args.force_iters and not args.no_extras and not args.reduced and (args.workload, N, batch) == ("quadrotor", 20, 8192):
+        if world == 1 and not args.force_iters and extras and not args.reduced and (args.workload, N, batch) == ("quadrotor", 20, 8192):
             # the other BASELINE configurations that fit one GPU, one warmed step each, and the complete SQP iteration -- under the driver's
             # clock, outside the timed region of `value`
             try:
@@ -348,7 +383,7 @@ def main():
                 out["sqp_iteration_device"] = sqp_iteration_device("quadrotor", 20, 8192, 2024, dev)
             except Exception as e:
                 out["sqp_iteration_device"] = {"error": repr(e)}
-        if world == 1 and not args.force_iters and not args.no_extras and not args.reduced:
+        if world == 1 and not args.force_iters and extras and not args.reduced:
             # the same step with the library's default dispatch hint on: instances ordered longest-first by the previous solve's
             # ADMM iteration counts.  On this repeated batch the prediction is exact, so this is the hint's upper bound.
             qp.set_dispatch_hint(True)
@@ -415,7 +450,7 @@ def main():
             assert np.array_equal(res["x"], hx) and np.array_equal(res["iters"], hit)       # same results as the unpipelined step
             out["pcie_inclusive_pipelined"] = {"value": batch / best[0], "unit": "QP solves/s", "ms_per_step": best[0] * 1e3, "chunks": best[1],
                                                "note": "mpcqp_solve_host: pinned host buffers; slices of the batch are copied in on one stream while earlier slices are solved and copied out on others"}
-        if world == 1 and not args.no_cpu_baseline and not args.force_iters and not args.no_extras:
+        if world == 1 and not args.no_cpu_baseline and not args.force_iters and extras:
             # the oracle (CPU port of the same algorithm) on this box's host cores, bounded sample of the same workload
             from oracle import oracle as orc
             cores = int(os.environ.get("MPCQP_CPU_THREADS", "0")) or host_cores()

@@ -3,7 +3,7 @@
 # usage: bash tools/final_measure.sh [quick]
 set -o pipefail
 out=gpurun_out/final; mkdir -p $out; export TMPDIR=/tmp
-python bench.py > $out/bench.json 2> $out/bench.err || exit 1
+python bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
 tail -c 600 $out/bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats -- python3 bench.py --steps 10 --warmup 2 --no-extras --no-cpu-baseline > $out/kstats.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 bench.py --steps 3 --warmup 2 --no-extras --no-cpu-baseline > $out/pmc_fetch.log 2>&1 || exit 1

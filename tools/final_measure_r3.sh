@@ -5,7 +5,7 @@
 # usage: bash tools/final_measure_r3.sh
 set -o pipefail
 out=gpurun_out/final3; mkdir -p $out; export TMPDIR=/tmp
-python bench.py > $out/bench.json 2> $out/bench.err || exit 1
+python bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
 tail -c 400 $out/bench.json; echo
 for cfg in "q20 --workload quadrotor" "q50 --workload quadrotor --horizon 50 --batch 8192" "cp100 --workload cartpole"; do
   set -- $cfg; tag=$1; shift

@@ -9,7 +9,7 @@ out=gpurun_out/final4; mkdir -p $out; export TMPDIR=/tmp
 part=${1:-1}
 WL=("q20 --workload quadrotor" "q50 --workload quadrotor --horizon 50 --batch 8192" "cp100 --workload cartpole")
 if [ "$part" = "1" ]; then
-  python bench.py > $out/bench.json 2> $out/bench.err || exit 1
+  python bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
   tail -c 300 $out/bench.json; echo
   for cfg in "${WL[@]}"; do
     set -- $cfg; tag=$1; shift
