@@ -11,11 +11,122 @@ def toy_local_system(mdl, arg, x=None):
                             np.asarray(arg["lbg"], float).reshape(1, -1), np.asarray(arg["ubg"], float).reshape(1, -1))
 
 
-def oracle_solve(ls, settings=None, nthreads=1, **kw):
+def oracle_solve(ls, settings=None, nthreads=1, x0=None, y0=None, rho0=None, **kw):
+    """settings: an oracle Settings object, or keyword settings; x0 / y0: warm start; rho0: per-instance starting rho"""
     from oracle import oracle as orc
     pat = orc.Pattern(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai)
     s = settings or orc.default_settings(**kw)
-    return pat.solve(ls.P, ls.q, ls.A, ls.l, ls.u, s, nthreads=nthreads)
+    return pat.solve(ls.P, ls.q, ls.A, ls.l, ls.u, s, nthreads=nthreads, x0=x0, y0=y0, rho0=rho0)
+
+
+# Settings under which the workloads change rho often enough to reach the iteration kernel's in-place re-factorisation (the last launch
+# pair of a solve in the two-kernel on-chip form): id -> (workload, N, batch, settings, the MPCQP_RESUME_ROUNDS values it is used at, whether at
+# least half of the batch reaches the last pair at each of them -- otherwise only some do).  tests/test_rho_recipes.py holds the oracle's update
+# counts to what tests/test_gpu_rho_resume.py relies on.
+_Q_RHO = dict(adaptive_rho_interval=20, rho=10.0, adaptive_rho_tolerance=1.5, eps_abs=1e-7, eps_rel=1e-7)
+RHO_RECIPES = {
+    "q20": ("quadrotor", 20, 24, _Q_RHO, (0, 1), True),
+    "q50": ("quadrotor", 50, 12, _Q_RHO, (0, 1), True),
+    "cp30": ("cartpole", 30, 24, dict(adaptive_rho_tolerance=1.5, eps_abs=1e-6, eps_rel=1e-6), (0,), True),
+    "cp100": ("cartpole", 100, 12, dict(rho=1e-3), (0,), True),
+    "di60": ("double_integrator", 60, 24, dict(adaptive_rho_tolerance=1.5, eps_abs=1e-6, eps_rel=1e-6), (0, 1), False),
+}
+
+
+def rho_recipe(rid, batch=None):
+    """-> (model, LocalSystem, meta, settings dict) of one RHO_RECIPES entry (default seeds; batch overrides the recipe's)"""
+    name, N, B, settings = RHO_RECIPES[rid][:4]
+    mdl, ls, meta = models.make_workload(name, batch or B, N=N)
+    return mdl, ls, meta, dict(settings)
+
+
+def oracle_rho_updates(ls, nthreads=8, rho0=None, x0=None, y0=None, steps=False, **settings):
+    """Number of rho changes per instance, from oracle prefix runs: max_iter = k * interval + 1 for k = 1, 2, ... shows the rho in force after the
+    adaptive-rho step of iteration k * interval; a change counts while the instance is still running: its full run goes beyond that iteration, or ends
+    there on the iteration limit without having passed a termination check in that iteration (the update is then the last thing the run did).
+    steps=True: -> (counts, changed [B, K] bool, interval) with changed[b, k - 1] = instance b changed rho at iteration k * interval."""
+    start = {k: v for k, v in dict(rho0=rho0, x0=x0, y0=y0).items() if v is not None}
+    from oracle import oracle as orc
+    full = oracle_solve(ls, nthreads=nthreads, **start, **settings)
+    s = orc.default_settings(**settings)
+    interval = s.adaptive_rho_interval or 4 * s.check_termination
+    prev = np.full(ls.batch, s.rho) if rho0 is None else np.where(np.asarray(rho0, float) > 0, rho0, s.rho)
+    prev = np.broadcast_to(prev, (ls.batch,)).copy()
+    K = int(full["iters"].max()) // interval if s.adaptive_rho and interval > 0 else 0
+    changed = np.zeros((ls.batch, K), bool)
+    for k in range(1, K + 1):
+        r = oracle_solve(ls, nthreads=nthreads, **start, **dict(settings, max_iter=min(k * interval + 1, s.max_iter)))
+        # (the loop leaves on a termination check before the rho step: statuses 1, 3, 5 of a check made in this iteration)
+        left = np.isin(full["status"], (1, 3, 5)) if s.check_termination and k * interval % s.check_termination == 0 else np.zeros(ls.batch, bool)
+        running = (full["iters"] > k * interval) | ((full["iters"] == k * interval) & (s.max_iter == k * interval) & ~left)
+        changed[:, k - 1] = running & (r["rho"] != prev)
+        prev = np.where(running, r["rho"], prev)
+    assert np.array_equal(prev, full["rho"]), "prefix runs do not end at the full run's rho"
+    counts = changed.sum(axis=1)
+    return (counts, changed, interval) if steps else counts
+
+
+def oracle_stable_mask(ls, draws=3, nthreads=8, rho0=None, x0=None, y0=None, **settings):
+    """Instances whose decisions (iteration count, every rho update) do not hang on rounding: iters and rho of the oracle stay the same when
+    P, A, q are multiplied entry by entry by 1 + 1e-12 * N(0, 1), `draws` times.  Only these can be asked for equal iteration counts of two
+    implementations that round differently."""
+    start = {k: v for k, v in dict(rho0=rho0, x0=x0, y0=y0).items() if v is not None}
+    ref = oracle_solve(ls, nthreads=nthreads, **start, **settings)
+    rng = np.random.default_rng(99)
+    ok = np.ones(ls.batch, bool)
+    for _ in range(draws):
+        P, A, q = (a * (1.0 + 1e-12 * rng.standard_normal(a.shape)) for a in (ls.P, ls.A, ls.q))
+        r = oracle_solve(models.LocalSystem(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai, P, q, A, ls.l, ls.u), nthreads=nthreads, **start, **settings)
+        # (rho "the same": to 1e-6 -- a decision that falls the other way moves it by adaptive_rho_tolerance or more, a value that moves by more than the
+        # parity bar under this perturbation cannot be held to it)
+        ok &= (r["iters"] == ref["iters"]) & (np.abs(r["rho"] - ref["rho"]) <= 1e-6 * np.abs(ref["rho"])) & (r["status"] == ref["status"])
+    return ok
+
+
+def take(ls, idx):
+    """the instances idx of a batch, as a batch of their own"""
+    pick = lambda a: a if a.ndim == 1 else np.ascontiguousarray(a[idx])
+    return models.LocalSystem(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai, pick(ls.P), pick(ls.q), pick(ls.A), pick(ls.l), pick(ls.u), ls.np)
+
+
+# Iteration limits on a rho update, as (MPCQP_RESUME_ROUNDS, which update of an instance: 0 = first, 1 = second, whether the update parks the instance).  The
+# launches of a solve are rounds + 1 iteration kernels <RF=0>, each of which parks an instance on its next update, and a last one <RF=1> that re-factorises in
+# place: update number j (from 1) parks iff j <= rounds + 1.  Parked on the limit, the instance is picked up by a launch that has no iteration left to do (one
+# at limit + 1) and ends in the kernel's tail with the state read back from the slab; in place on the limit, <RF=1> re-factorises in its last iteration.
+UPDATE_LIMIT_CASES = [(0, 0, True), (1, 1, True), (0, 1, False)]
+
+
+def update_limits(ls, settings, which):
+    """(k * interval, k * interval + 1) for the k of the first (which = 0) or second (1) rho update of the first instance that has that many: iteration limits at
+    which an update and the limit fall in the same step, and at which one iteration is left after the update"""
+    counts, changed, interval = oracle_rho_updates(ls, steps=True, **settings)
+    b = int(np.argmax(counts > which))
+    assert counts[b] > which
+    k = int(np.flatnonzero(changed[b])[which]) + 1
+    return k * interval, k * interval + 1
+
+
+def split_rho(batch):
+    """per-instance starting rho: the first half of the batch at 0.1, the second at 10"""
+    return np.r_[np.full(batch // 2, 0.1), np.full(batch - batch // 2, 10.0)]
+
+
+def warm_point(ls, settings):
+    """-> (x0, y0, settings with warm_start = 1): the oracle's solution of the batch with q perturbed by 5 %"""
+    rng = np.random.default_rng(5)
+    near = models.LocalSystem(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai, ls.P, ls.q * (1.0 + 0.05 * rng.standard_normal(ls.q.shape)), ls.A, ls.l, ls.u)
+    w = oracle_solve(near, nthreads=8, **settings)
+    return w["x"], w["y"], dict(settings, warm_start=1)
+
+
+BIG_BATCH = 700          # more instances than an MI355X has compute units: the eight-wave instances run one workgroup per CU and queue the rest
+
+
+def big_batch_sample(rid, batch=BIG_BATCH):
+    """-> (the oracle's sample of a recipe at BIG_BATCH as a batch of its own, its indices, settings): 64 instances, 32 for the slow cart-pole N=100"""
+    _, ls, _, settings = rho_recipe(rid, batch)
+    idx = np.arange(0, batch, 11)[:64] if rid != "cp100" else np.arange(0, batch, 22)[:32]
+    return take(ls, idx), idx, settings
 
 
 def random_qp(n, m, seed, density=0.3, infeasible=None):

@@ -104,10 +104,28 @@ def test_random_stage_patterns_onchip_families(built, monkeypatch):
     only take block-tridiagonal + arrow patterns and so never see the random patterns above: a 20-pattern slice of tools/fuzz_oc.py per family
     (random nx / nu / N / weights / dynamics / iterate), a cold solve and a kept-workspace solve (new q, shifted bounds) each, under the
     reference's settings (src/sqp_solver/SQPOptimizationSolver.cpp:81-85)."""
+    monkeypatch.delenv("MPCQP_RESUME_ROUNDS", raising=False)
+    _onchip_gate(monkeypatch, {})
+
+
+@pytest.mark.parametrize("reach,settings", [(False, dict(adaptive_rho_tolerance=1.5)), (True, dict(adaptive_rho_tolerance=1.5, adaptive_rho_interval=25, rho=1e-3))],
+                         ids=["tolerance-1.5", "tolerance-1.5-interval-25-rho-1e-3"])
+def test_random_stage_patterns_onchip_in_place_refactorisation(built, monkeypatch, reach, settings):
+    """The same patterns, seeds and assertions with MPCQP_RESUME_ROUNDS=0 and adaptive_rho_tolerance = 1.5: an instance's second rho update already
+    re-factorises in place in the iteration kernel <RF=1> (kernel_oc_split.hpp), so the random patterns (phantom slots, hubs sharing a block) go through
+    it too.  How many cold solves have two or more updates is counted on the oracle (tests/support/problems.py oracle_rho_updates) and printed: with the
+    tolerance alone 0 of 55 (four waves) and 2 of 36 (eight waves) -- these problems are solved before a second update -- so a second leg also starts
+    from rho = 1e-3 and looks every 25 iterations, and there every family must have some."""
+    monkeypatch.setenv("MPCQP_RESUME_ROUNDS", "0")
+    _onchip_gate(monkeypatch, settings, launch_pairs=1, reach=reach)
+
+
+def _onchip_gate(monkeypatch, settings, launch_pairs=2, reach=False):
     from optimal_control_problem_amd import _lib
     from optimal_control_problem_amd.batch_qp import BatchQP
     from oracle import oracle as orc
-    stats = {f: dict(solves=0, soft=0, cases=0, dissected=0) for f, _ in OC_FAMILIES}
+    from tests.support.problems import oracle_rho_updates
+    stats = {f: dict(solves=0, soft=0, cases=0, dissected=0, cold=0, inplace=0) for f, _ in OC_FAMILIES}
     worst = 0.0
     for fam, code in OC_FAMILIES:
         monkeypatch.setenv("MPCQP_VARIANT", fam)
@@ -116,16 +134,18 @@ def test_random_stage_patterns_onchip_families(built, monkeypatch):
             ls, dims, rng = random_stage_ocp(c, fam); c += 1
             B = ls.batch
             try:
-                qp = BatchQP(ls.n, ls.m, B, ls.Pp, ls.Pi, ls.Ap, ls.Ai)
+                qp = BatchQP(ls.n, ls.m, B, ls.Pp, ls.Pi, ls.Ap, ls.Ai, **settings)
             except _lib.MpcqpError as e:
                 if e.code == _lib.ERR_LIMIT:      # outside the instance's limits (chain length, LDS): not a case
                     continue
                 raise
-            assert qp.plan_info()["variant"] == code
+            assert qp.plan_info()["variant"] == code and qp.oc_info()["launch_pairs_for_rho_updates"] == launch_pairs
             stats[fam]["cases"] += 1
+            if settings:
+                stats[fam]["cold"] += B; stats[fam]["inplace"] += int((oracle_rho_updates(ls, nthreads=1, **settings) >= 2).sum())
             stats[fam]["dissected"] += qp.oc_info()["chain_pairs"] > 1       # (separators of the stage chain in the hub block: several twisted pairs of chains)
             qp.keep_workspace(True)
-            st = orc.State(orc.Pattern(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai), B, orc.default_settings())
+            st = orc.State(orc.Pattern(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai), B, orc.default_settings(**settings))
             q2 = ls.q * 1.2 + 0.05 * rng.normal(size=ls.q.shape); sh = 0.02 * rng.normal(size=ls.l.shape)
             for leg in ("cold", "kept"):
                 if leg == "cold":
@@ -157,7 +177,10 @@ def test_random_stage_patterns_onchip_families(built, monkeypatch):
             qp.close()
     report = {f: "%d of %d solves, %d patterns (%d in the dissected order)" % (s["soft"], s["solves"], s["cases"], s["dissected"]) for f, s in stats.items()}
     print("on-chip families, tolerance-level instances:", report, "worst residual ratio gpu / oracle among them: %.2f" % worst)
+    if settings:
+        print("cold solves with two or more rho updates (the second re-factorises in place):", {f: "%d of %d" % (s["inplace"], s["cold"]) for f, s in stats.items()})
     for fam, s in stats.items():
+        assert not reach or s["inplace"] > 0, (fam, report)
         assert s["cases"] == OC_NPAT, (fam, report)
         assert 0 < s["dissected"] < s["cases"], (fam, report)        # both orders are in the gate
         assert s["soft"] <= 0.03 * s["solves"], (fam, report)
