@@ -1,16 +1,7 @@
 // kernel_table.hpp -- where mpcqp.hip finds the kernel instances that other translation units instantiate (k_*.hip); nullptr = no such instance
 #pragma once
 #define MPCQP_HIDDEN __attribute__((visibility("hidden")))
-// register-resident blocks per wave of the four-wave on-chip instance: inverse diagonal blocks (positions per wave) and hub blocks
-constexpr int OC_NG = 5, OC_NH = 3;
-// Long chains (more than 20 chain blocks: quadrotor N > 20, cart-pole N > 60): eight waves per QP, one workgroup per CU -- the whole LDS and
-// 8 x 256 VGPRs for one factor.  Two instances: up to 32 chain blocks with every hub block in registers (cart-pole N = 100: 62 KB of chain
-// blocks + 36 KB of vectors in LDS), and up to 56 with seven positions per wave, G_p and every hub block (both orientations) in registers --
-// 168 resident VGPRs -- and only the chain blocks and the hub's inverse in LDS (quadrotor N = 50: 50 blocks = 100 KB + 57 KB of vectors and
-// tables = 159,880 B).  (Measured against <NG 7, NH 5> with z, y in the slab, 157,832 B and 136 resident VGPRs: 35.5 against 35.9 ms and an
-// eighth less HBM traffic -- the slab vectors cost more than the extra spills.)
-struct Oc8Inst { int ng, nh; bool zyg; };
-constexpr Oc8Inst OC8_INST[2] = {{4, 4, false}, {7, 7, false}};
+#include "select.hpp"      // OC_NG, OC_NH, OC8_INST: the shapes of the on-chip instances are part of the selection policy
 
 // (the instances with and without the kept-workspace entry are separate translation units: _r1 / _r0)
 // mpcqp_res_kernel<NW, MINW, false, REUSE>: factor in LDS

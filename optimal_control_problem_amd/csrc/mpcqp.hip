@@ -5,17 +5,19 @@
 // 183-224), i.e. OSQP's osqp_setup + osqp_solve (external to the reference, see oracle/osqp_oracle.h).
 //
 // One launch does the whole sequence for every QP of the batch (grid = batch, one workgroup per QP).  Kernel families
-// (mpcqp_create picks one per sparsity and batch size from measured rules):
-//   * mpcqp_res_kernel<NW, MINW, GB, REUSE, ZYG> -- NW wavefronts per QP (1 or 4), W-fused block LDL' of
+// (select_kernel, select.hpp, picks one per sparsity and batch size from measured rules):
+//   * mpcqp_res_kernel<NW, MINW, GB, REUSE, ZYG, NG, NH, TL> -- NW wavefronts per QP (1, 2, 4 or 8), W-fused block LDL' of
 //     M = P + sigma I + A' diag(rho) A in 16x16 blocks, solve driven by a host-built schedule of arithmetic-progression
 //     segments (plan.hpp).  GB = false: the factor lives in LDS (small / mid-size problems, and any batch that fits one
 //     resident round); GB = true: the factor stays in the per-QP HBM slab and LDS holds only vectors, temp tiles and the
-//     schedule, so that 3-4 workgroups share a CU (the default for the 12-state quadrotor sizes; HBM-roofline-bound).
+//     schedule, so that 3-4 workgroups share a CU (two or four waves; long horizons that no on-chip instance takes; HBM-roofline-bound).
 //     MINW selects the register budget (128 / 168 / 256 VGPRs), REUSE the kept-workspace entry (mpcqp_update_vectors),
 //     ZYG keeps z and y in the slab too (long horizons).
-//     OCG / OCH > 0: the on-chip mode of the global-block kernel (kernel_onchip.hpp) -- after each factorisation the factor is
-//     brought on chip (chain blocks in LDS, inverse diagonal blocks and some hub blocks in registers; two workgroups per CU) and the
-//     triangular solves run on the matrix cores, register to register along each chain.  The default for the 12-state quadrotor, N = 20.
+//     NG / NH > 0: the on-chip mode of the global-block kernel (kernel_onchip.hpp) -- after each factorisation the factor is
+//     brought on chip (chain blocks in LDS, inverse diagonal blocks and some hub blocks in registers; four waves at two workgroups per CU,
+//     eight waves at one) and the triangular solves run on the matrix cores, register to register along each chain.
+//   * mpcqp_oc_setup_kernel + mpcqp_oc_admm_kernel (kernel_oc_split.hpp) -- the on-chip mode as two kernels, set-up and iteration: the
+//     default form of the on-chip mode, and with it of the 12-state quadrotor, N = 20.
 //   * mpcqp_admm_kernel<PD> -- the first-generation streaming kernel, one QP per wavefront, block Cholesky streamed from
 //     the slab; fallback when even the vectors exceed LDS, and a cross-check in the variant tests.
 // Common to all: ADMM iterates in LDS; scaled A in two ELL orientations and scaled P in the slab, streamed with coalesced
@@ -31,10 +33,10 @@
 #include "kernels_util.hpp"
 #include "reduced.hpp"
 
+static_assert(SEL_ERR_ARG == MPCQP_ERR_ARG && SEL_ERR_LIMIT == MPCQP_ERR_LIMIT, "select.hpp reports its refusals in the codes of include/mpcqp.h");
+
 // ------------------------------------------------------------------------------------------ host side
 static thread_local std::string g_last_error;
-static thread_local const char *g_force_variant = nullptr;      // mpcqp_create_tuned: the family the next mpcqp_create on this thread must take ("" = the rule's choice)
-static const char *variant_request() { return g_force_variant ? (g_force_variant[0] ? g_force_variant : nullptr) : getenv("MPCQP_VARIANT"); }
 static int fail(int code, const std::string &msg) { g_last_error = msg; return code; }
 int mpcqp_set_error(int code, const std::string &msg) { return fail(code, msg); }
 int mpcqp_pick_device(int requested, int *device) {
@@ -57,30 +59,11 @@ struct mpcqp_handle {
   int n = 0, m = 0, batch = 0, device = 0;
   hipEvent_t ev_guard = nullptr;              // mpcqp_order_after_last_solve
   mpcqp_settings st;
-  Plan plan; WsLayout wl; long lds = 0;
-  int variant = 0;              // 0 = streaming (1 wave / QP), NW > 0 = LDS-resident factor with NW waves / QP
-  bool wide = false;            // resident kernel instance that may use the whole register file (one QP per CU)
-  bool gblocks = false;         // multi-wave LDL' kernel with the factor blocks streamed from the HBM slab
-  bool zyg = false;             // ... with z, y in the slab instead of LDS (lifts workgroups per CU for long horizons)
-  bool occ3 = false;            // ... its 168-VGPR instance (exactly 3 workgroups per CU fit in LDS), 8 blocks in flight
-  bool res1x = false;           // one-wave kernel, 128-VGPR instance: more than eight QPs per CU when the LDS footprint allows (double integrator N=10: 12.1 -> 13.8 M QP/s)
-  int res3 = 0;                 // LDS-resident 4-wave kernel: 3 or 4 workgroups per CU (168- / 128-VGPR instances) when the LDS footprint allows, else 0
-  bool stream_pd8 = false;      // streaming kernel instance (read from the environment once, at create)
-  bool occ4 = false;            // ... its 128-VGPR instance (>= 3 workgroups per CU fit in LDS)
-  bool oc = false;              // on-chip mode of the global-block kernel (kernel_onchip.hpp): two workgroups per CU, factor in LDS + registers
-  int oc8 = 0;                  // ... its eight-wave instances for long chains (one workgroup per CU): 1 = <NG 4, NH 4>, 2 = <NG 7, NH 7>
-  int resume_rounds = 1;        // two-kernel form: {re-factorisation, iteration} pairs queued behind a solve before the last pair (MPCQP_RESUME_ROUNDS)
-  // two-kernel form: the set-up kernel's own launch shape.  Nothing of the factor is resident while it runs, so it does not need the iteration kernel's LDS
-  // (the block slots) or its eight waves: four-wave workgroups (oc_ldl's chain waves and helpers are four in any case) with an LDS request of their own let
-  // two or three QPs share a CU where the iteration kernel has one
-  int setup_nw = 0; long lds_setup = 0; DevRes dres_setup; DevOc doc_setup;
-  int *qctr = nullptr; int qslots = 0;        // two-kernel on-chip mode: ticket counters of the resident iteration workgroups (16 per solve in flight), and how many workgroups the GPU holds at once
-  bool split = false;           // ... as two kernels, set-up and iteration (kernel_oc_split.hpp): the default; MPCQP_OC_MONO=1 and the tile experiment keep the single kernel
-  OcPlan ocplan; DevOc doc;
-  TilePlan tplan; bool tiles = false;   // on-chip kernels: dense tiles of A for the two sweeps of the iteration (plan.hpp build_tile_plan)
-  bool vtiles = false;                  // ... in the two-kernel form, on the vector ALUs (kernel_oc_split.hpp; MPCQP_VTILES=1)
-  ResPlan rplan; DevRes dres;
-  DevPlan dp; DevIO io;
+  Knobs knobs;                                // the MPCQP_* switches as they stood when the handle was created
+  Selection sel;                              // what select_kernel decided: family, instance, plans, LDS (sel.waves = -1: a reduced handle, `inner` runs)
+  DevPlan dp; DevRes dres; DevOc doc; DevIO io;
+  DevRes dres_setup; DevOc doc_setup;         // two-kernel on-chip form: the set-up kernel's copies of the arguments, with its own launch shape (sel.setup)
+  int *qctr = nullptr; int qslots = 0;        // ... ticket counters of the resident iteration workgroups (16 per solve in flight), and how many workgroups the GPU holds at once
   std::vector<void *> dev_allocs;
   double *ws = nullptr;
   double *dP = nullptr, *dq = nullptr, *dA = nullptr, *dl = nullptr, *du = nullptr;  // owned copies (host-memory updates)
@@ -138,35 +121,32 @@ static int dalloc(mpcqp_handle *h, T **p, size_t count) {
   return MPCQP_OK;
 }
 
-constexpr long OC_LDS_MAX = 80 * 1024;      // four-wave on-chip instances: two workgroups per CU
-constexpr long OC8_LDS_MAX = 160 * 1024;    // eight-wave ones: one (kernel_table.hpp OC8_INST)
-constexpr int OC8_MAX_CHAIN = 64;           // (oc_ldl keeps the chain's block ids one per lane)
-
 // the kernel instance a handle runs (instantiated in the k_*.hip units, kernel_table.hpp): waves per QP, register budget, factor location, and --
 // as its own instance so that the full-setup kernels carry no code for it -- the kept-workspace entry (mpcqp_update_vectors)
 static const void *res_kernel_of(const mpcqp_handle *h, bool reuse) {
+  const Selection &s = h->sel;
   auto lds = [&](int nw, int minw) { return reuse ? mpcqp_kernel_res_lds_r1(nw, minw) : mpcqp_kernel_res_lds_r0(nw, minw); };
   auto gb = [&](int nw, int minw, bool zyg) { return reuse ? mpcqp_kernel_res_gb_r1(nw, minw, zyg) : mpcqp_kernel_res_gb_r0(nw, minw, zyg); };
-  auto mono = [&](int nw, int ng, int nh) { return reuse ? mpcqp_kernel_oc_mono_r1(nw, ng, nh, h->tiles) : mpcqp_kernel_oc_mono_r0(nw, ng, nh, h->tiles); };
-  if (h->oc && h->oc8) return mono(8, OC8_INST[h->oc8 - 1].ng, OC8_INST[h->oc8 - 1].nh);      // (nullptr without an arrow head: such handles run the two-kernel form)
-  if (h->oc) return mono(4, OC_NG, h->ocplan.has_hub ? OC_NH : 0);
-  if (h->gblocks && h->variant == 2) return gb(2, 3, false);
-  if (h->gblocks && h->zyg) return gb(4, h->occ3 ? 3 : 2, true);
-  if (h->gblocks && h->occ3) return gb(4, 3, false);
-  if (h->gblocks) return gb(4, h->occ4 ? 4 : 2, false);
-  if (h->variant == 1) return lds(1, h->res1x ? 4 : 2);
-  if (h->variant == 8) return lds(8, 2);
-  if (h->variant == 2) return lds(2, 3);
-  if (h->res3 == 4) return lds(4, 4);
-  if (h->res3 == 3) return lds(4, 3);
-  return lds(4, h->wide ? 1 : 2);
+  auto mono = [&](int nw) { return reuse ? mpcqp_kernel_oc_mono_r1(nw, s.oc_ng(), s.oc_nh(), s.tiles) : mpcqp_kernel_oc_mono_r0(nw, s.oc_ng(), s.oc_nh(), s.tiles); };
+  if (s.oc) return mono(s.oc8 ? 8 : 4);      // (eight waves: nullptr without an arrow head, such handles run the two-kernel form)
+  if (s.gblocks && s.waves == 2) return gb(2, 3, false);
+  if (s.gblocks && s.zyg) return gb(4, s.occ3 ? 3 : 2, true);
+  if (s.gblocks && s.occ3) return gb(4, 3, false);
+  if (s.gblocks) return gb(4, s.occ4 ? 4 : 2, false);
+  if (s.waves == 1) return lds(1, s.res1x ? 4 : 2);
+  if (s.waves == 8) return lds(8, 2);
+  if (s.waves == 2) return lds(2, 3);
+  if (s.res3 == 4) return lds(4, 4);
+  if (s.res3 == 3) return lds(4, 3);
+  return lds(4, s.wide ? 1 : 2);
 }
 // the two kernels of the on-chip mode (kernel_oc_split.hpp): CuCaQP::initSolver and CuCaQP::solve
-static const void *oc_setup_of(const mpcqp_handle *h, bool reuse) { return mpcqp_kernel_oc_setup(h->setup_nw, h->ocplan.has_hub != 0, reuse); }
+static const void *oc_setup_of(const mpcqp_handle *h, bool reuse) { return mpcqp_kernel_oc_setup(h->sel.setup.nw, h->sel.ocplan.has_hub != 0, reuse); }
 static const void *oc_admm_of(const mpcqp_handle *h, bool rf = false) {
-  const int nw = h->oc8 ? 8 : 4, ng = h->oc8 ? OC8_INST[h->oc8 - 1].ng : OC_NG, nh = !h->ocplan.has_hub ? 0 : h->oc8 ? OC8_INST[h->oc8 - 1].nh : OC_NH;
-  if (!h->oc8 && h->ocplan.pairs.size() > 1) return mpcqp_kernel_oc_admm_p4(rf ? 1 : 0);      // (four waves, two twisted pairs: its own instances)
-  if (h->vtiles && !rf) return mpcqp_kernel_oc_admm_tl(nw, ng, nh);      // (the last launch of a solve, rf, runs the ELL sweeps: the set-up writes both forms)
+  const Selection &s = h->sel;
+  const int nw = s.oc8 ? 8 : 4, ng = s.oc_ng(), nh = s.oc_nh();
+  if (!s.oc8 && s.ocplan.pairs.size() > 1) return mpcqp_kernel_oc_admm_p4(rf ? 1 : 0);      // (four waves, two twisted pairs: its own instances)
+  if (s.vtiles && !rf) return mpcqp_kernel_oc_admm_tl(nw, ng, nh);      // (the last launch of a solve, rf, runs the ELL sweeps: the set-up writes both forms)
   return rf ? mpcqp_kernel_oc_admm_rf(nw, ng, nh) : mpcqp_kernel_oc_admm(nw, ng, nh);
 }
 // One solve of the two-kernel on-chip mode on stream s: set-up, iteration; then, for instances whose adaptive-rho step asked for a new factor
@@ -177,15 +157,17 @@ static const void *oc_admm_of(const mpcqp_handle *h, bool rf = false) {
 // workgroups per CU the touch only competes with them (quadrotor N=20 x 8192 iteration kernel 5.25 -> 5.15 ms without it, N=15 3.98 -> 3.82, N=10 3.02 -> 2.94;
 // cart-pole N=50 and double integrator N=60 unchanged; MPCQP_TOUCH4 turns it on).  The single-kernel form keeps it.
 static int no_touch_of(const mpcqp_handle *h) {
-  if (getenv("MPCQP_NO_TOUCH")) return 1;
-  if (h->oc8) return getenv("MPCQP_TOUCH8") ? 0 : 1;
-  if (h->split) return getenv("MPCQP_TOUCH4") ? 0 : 1;
+  if (h->knobs.no_touch) return 1;
+  if (h->sel.oc8) return h->knobs.touch8 ? 0 : 1;
+  if (h->sel.split) return h->knobs.touch4 ? 0 : 1;
   return 0;
 }
 static int launch_oc_split(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipStream_t s, hipEvent_t after_setup, int qslot) {
-  const dim3 grid(count), block(h->variant * WAVE), block_s(h->setup_nw * WAVE);
+  const Selection &sl = h->sel;
+  const dim3 grid(count), block(sl.waves * WAVE), block_s(sl.setup.nw * WAVE);
+  const size_t lds = (size_t)sl.lds, lds_setup = (size_t)sl.setup.lds;
   // the iteration kernel as resident workgroups that draw instances from one counter (kernel_oc_split.hpp) when the batch is more than the GPU holds at once
-  const bool queued = h->oc8 != 0;      // (the eight-wave instances are compiled as resident workgroups; the four-wave ones are not)
+  const bool queued = sl.oc8 != 0;      // (the eight-wave instances are compiled as resident workgroups; the four-wave ones are not)
   int *qc = queued ? h->qctr + 16 * qslot : nullptr;
   if (queued) HIPCHK(hipMemsetAsync(qc, 0, 16 * sizeof(int), s));
   const dim3 grid_it(queued ? std::min(h->qslots, count) : count);
@@ -200,19 +182,232 @@ static int launch_oc_split(mpcqp_handle *h, DevIO &io, int count, bool reuse, hi
   void *argr[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&docr};
   void *sargs[] = {(void *)&h->dp, (void *)&h->dres_setup, (void *)&h->st, (void *)&io, (void *)&docs0};
   void *sargr[] = {(void *)&h->dp, (void *)&h->dres_setup, (void *)&h->st, (void *)&io, (void *)&docsr};
-  HIPCHK(hipLaunchKernel(oc_setup_of(h, reuse), grid, block_s, sargs, (size_t)h->lds_setup, s));
+  HIPCHK(hipLaunchKernel(oc_setup_of(h, reuse), grid, block_s, sargs, lds_setup, s));
   if (after_setup) HIPCHK(hipEventRecord(after_setup, s));
   const bool rho_updates = h->st.adaptive_rho != 0;
   args[3] = io_of();
-  HIPCHK(hipLaunchKernel(oc_admm_of(h, !rho_updates), grid_it, block, args, (size_t)h->lds, s));     // (without adaptive rho nothing ever leaves: either instance serves)
+  HIPCHK(hipLaunchKernel(oc_admm_of(h, !rho_updates), grid_it, block, args, lds, s));     // (without adaptive rho nothing ever leaves: either instance serves)
   if (!rho_updates) return MPCQP_OK;
-  for (int r = 0; r <= h->resume_rounds; r++) {
-    HIPCHK(hipLaunchKernel(oc_setup_of(h, false), grid, block_s, sargr, (size_t)h->lds_setup, s));
+  for (int r = 0; r <= sl.resume_rounds; r++) {
+    HIPCHK(hipLaunchKernel(oc_setup_of(h, false), grid, block_s, sargr, lds_setup, s));
     argr[3] = io_of();
-    HIPCHK(hipLaunchKernel(oc_admm_of(h, r == h->resume_rounds), grid_it, block, argr, (size_t)h->lds, s));
+    HIPCHK(hipLaunchKernel(oc_admm_of(h, r == sl.resume_rounds), grid_it, block, argr, lds, s));
   }
   return MPCQP_OK;
 }
+// `count` instances on stream s through the handle's kernel(s), then the check of what they wrote; every per-instance pointer of io is at the first of them
+// (the kernels index by blockIdx).  Events, where given: after the set-up kernel of the two-kernel form, after the last kernel of the solve.
+static int launch_batch(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipStream_t s, hipEvent_t after_setup, hipEvent_t after_kernel, int qslot) {
+  const Selection &sl = h->sel;
+  if (sl.waves > 0 && sl.split) {     // CuCaQP::initSolver, then CuCaQP::solve
+    int rc = launch_oc_split(h, io, count, reuse, s, after_setup, qslot);
+    if (rc) return rc;
+  }
+  else if (sl.waves > 0) {
+    void *args[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&h->doc};
+    HIPCHK(hipLaunchKernel(res_kernel_of(h, reuse), dim3(count), dim3(sl.waves * WAVE), args, (size_t)sl.lds, s));
+  }
+  else if (sl.stream_pd8) hipLaunchKernelGGL(mpcqp_admm_kernel<8>, dim3(count), dim3(WAVE), (size_t)sl.lds, s, h->dp, h->st, io);
+  else hipLaunchKernelGGL(mpcqp_admm_kernel<4>, dim3(count), dim3(WAVE), (size_t)sl.lds, s, h->dp, h->st, io);
+  HIPCHK(hipGetLastError());
+  if (after_kernel) HIPCHK(hipEventRecord(after_kernel, s));
+  if (h->m > 0) {
+    hipLaunchKernelGGL(mpcqp_validate_kernel, dim3((count + 3) / 4), dim3(256), 0, s, count, h->n, h->m, io.l, io.sl, io.u, io.su, io.x, io.y, io.z,
+                       io.status, io.iters, io.info);
+    HIPCHK(hipGetLastError());
+  }
+  return MPCQP_OK;
+}
+// the handle's inputs as they stand + its own outputs, workspace and solve-time switches: what every launch starts from
+static DevIO io_of_handle(const mpcqp_handle *h) {
+  DevIO io = h->io;
+  io.x = h->ox; io.y = h->oy; io.z = h->oz; io.status = h->ostatus; io.iters = h->oiters; io.info = h->oinfo; io.ws = h->ws; io.no_remap = h->knobs.no_remap ? 1 : 0; io.no_touch = no_touch_of(h); io.cscale = h->ocs; io.dbg = h->odbg;
+  io.reuse = 0; io.keep = h->keep ? 1 : 0; io.order = nullptr;
+  return io;
+}
+// a CSC pattern as the create entries take it: column pointers monotone (from 0 where the entry asks for that), row indices in range.  Pp = null: A alone
+static int check_csc(int n, int m, const int *Pp, const int *Pi, const int *Ap, const int *Ai, bool from_zero) {
+  if (from_zero && ((Pp && Pp[0] != 0) || Ap[0] != 0)) return fail(MPCQP_ERR_ARG, "colptr must start at 0");
+  for (int j = 0; j < n; j++) if ((Pp && Pp[j + 1] < Pp[j]) || Ap[j + 1] < Ap[j]) return fail(MPCQP_ERR_ARG, "colptr not monotone");
+  if (Pp) for (int k = Pp[0]; k < Pp[n]; k++) if (Pi[k] < 0 || Pi[k] >= n) return fail(MPCQP_ERR_ARG, "P row index out of range");
+  for (int k = Ap[0]; k < Ap[n]; k++) if (Ai[k] < 0 || Ai[k] >= m) return fail(MPCQP_ERR_ARG, "A row index out of range");
+  return MPCQP_OK;
+}
+
+// ---- mpcqp_create, step by step: what select_kernel chose goes to the device
+#define UP(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
+// the plan's tables (every family reads them) and the offsets of the per-QP slab
+static int upload_plan(mpcqp_handle *h) {
+  const Plan &pl = h->sel.plan; const WsLayout &w = h->sel.wl; DevPlan &dp = h->dp;
+  memset(&dp, 0, sizeof(dp));
+  dp.n = h->n; dp.m = h->m; dp.npad = pl.npad; dp.mpad = pl.mpad; dp.nb = pl.nb; dp.nblk = pl.nblk; dp.nfac = (int)pl.fac.size(); dp.nT = pl.nT;
+  UP(upload_ell(h, pl.A, &dp.A)); UP(upload_ell(h, pl.At, &dp.At)); UP(upload_ell(h, pl.P, &dp.P));
+  UP(upload(h, pl.pos, &dp.pos)); UP(upload(h, pl.perm, &dp.perm));
+  UP(upload(h, pl.fwd_ops, &dp.fwd_ops)); UP(upload(h, pl.bwd_ops, &dp.bwd_ops)); UP(upload(h, pl.bwd_of, &dp.bwd_of));
+  std::vector<int4> f(pl.fac.size());
+  for (size_t i = 0; i < f.size(); i++) f[i] = make_int4(pl.fac[i].type, pl.fac[i].dst, pl.fac[i].a, pl.fac[i].b);
+  UP(upload(h, f, &dp.fac));
+  UP(upload(h, pl.tpos, &dp.tpos)); UP(upload(h, pl.asm_ptr, &dp.asm_ptr)); UP(upload(h, pl.asm_a, &dp.asm_a));
+  UP(upload(h, pl.asm_b, &dp.asm_b)); UP(upload(h, pl.asm_pidx, &dp.asm_pidx)); UP(upload(h, pl.blk_diag, &dp.blk_diag));
+  dp.o_ellA = w.ellA; dp.o_ellAt = w.ellAt; dp.o_ellP = w.ellP; dp.o_Lf = w.Lf; dp.o_Lb = w.Lb; dp.o_T = w.T;
+  dp.o_l = w.l; dp.o_u = w.u; dp.o_D = w.D; dp.o_E = w.E; dp.o_dx = w.dx; dp.o_dy = w.dy; dp.o_Zg = w.Zg; dp.o_Yg = w.Yg; dp.ws_stride = w.stride;
+  return MPCQP_OK;
+}
+// resident families: the level-parallel LDL' plan and the solve schedule
+static int upload_resident(mpcqp_handle *h) {
+  const Selection &s = h->sel; const Plan &pl = s.plan; const ResPlan &rp = s.rplan; DevRes &dr = h->dres;
+  dr.nphase = rp.nphase; dr.ntemp = rp.ntemp; dr.nconst = rp.nconst; dr.rext = rp.rext;
+  dr.nlev = rp.nlev;
+  UP(upload(h, rp.lv_ptr, &dr.lv_ptr)); UP(upload(h, rp.lv_diag, &dr.lv_diag)); UP(upload(h, rp.lw_ptr, &dr.lw_ptr));
+  UP(upload(h, rp.lw_slot, &dr.lw_slot)); UP(upload(h, rp.lw_g, &dr.lw_g)); UP(upload(h, rp.lu_ptr, &dr.lu_ptr));
+  UP(upload(h, rp.lu_dst, &dr.lu_dst)); UP(upload(h, rp.lu_tmp, &dr.lu_tmp)); UP(upload(h, rp.lu_b, &dr.lu_b));
+  UP(upload(h, rp.g_ptr, &dr.g_ptr)); UP(upload(h, rp.g_seg, &dr.g_seg)); dr.n_seg = (int)rp.g_seg.size() / 8; dr.stage = s.gblocks ? res_stage_doubles_gb(pl, rp) : res_stage_doubles(pl, rp);
+  dr.tmp_alias = s.gblocks && !s.oc && gb_tmp_alias(pl, rp) ? 1 : 0;
+  memset(&h->doc, 0, sizeof(h->doc));
+  return MPCQP_OK;
+}
+// on-chip kernels with dense tiles of A (the MPCQP_TILES / MPCQP_VTILES experiments): the tiles and the remainder ELL layouts
+static int upload_tiles(mpcqp_handle *h) {
+  const Selection &s = h->sel; const Plan &pl = s.plan; const TilePlan &tp = s.tplan; DevTile &t = h->doc.tl;
+  t.on = 1; t.ntile = tp.ntile; t.nAr = tp.Ar.nchunks; t.nAtr = tp.Atr.nchunks; t.Ar_entries = tp.Ar.entries(); t.Atr_entries = tp.Atr.entries();
+  UP(upload(h, tp.Ar.chunk_off, &t.Ar_off)); UP(upload(h, tp.Ar.idx, &t.Ar_idx)); UP(upload(h, tp.Ar.src, &t.Ar_src));
+  UP(upload(h, tp.Atr.chunk_off, &t.Atr_off)); UP(upload(h, tp.Atr.idx, &t.Atr_idx)); UP(upload(h, tp.Atr.src, &t.Atr_src));
+  UP(upload(h, tp.tJ, &t.tJ)); UP(upload(h, tp.rowid, &t.rowid));
+  if (s.vtiles) {      // row-major tiles for the vector-ALU form: element (r, c) at 16 r + c (the plan keeps the MFMA operand order [r + 16 (c & 3)][c >> 2])
+    std::vector<int> rm(tp.tsrc.size(), -1);
+    for (size_t tt = 0; tt < tp.tsrc.size() / BLK; tt++) for (int r = 0; r < BS; r++) for (int c = 0; c < BS; c++)
+      rm[tt * BLK + r * BS + c] = tp.tsrc[tt * BLK + (r + BS * (c & 3)) * 4 + (c >> 2)];
+    UP(upload(h, rm, &t.tsrc));
+  } else UP(upload(h, tp.tsrc, &t.tsrc));
+  {   // per-chunk records of fixed size (kernel_onchip.hpp oc_tiles_a / oc_tiles_at): {tile, column block, first row, rows}, padded with the zero tile
+    auto first = [&](int tt) { for (int r = 0; r < BS; r++) if (tp.rowid[(size_t)tt * BS + r] >= 0) return tp.rowid[(size_t)tt * BS + r]; return 0; };
+    auto rows = [&](int tt) { int k = 0; for (int r = 0; r < BS; r++) k += tp.rowid[(size_t)tt * BS + r] >= 0; return k; };
+    std::vector<int> ai(32 * (size_t)pl.A.nchunks, 0), ac(pl.A.nchunks, 0);
+    for (int c = 0; c < pl.A.nchunks; c++) {
+      ac[c] = tp.ta_ptr[c + 1] - tp.ta_ptr[c];
+      for (int u = 0; u < 8; u++) {
+        const int tt = u < ac[c] ? tp.ta_tid[tp.ta_ptr[c] + u] : tp.ntile;
+        int rec[4] = {tt, tp.tJ[tt], first(tt), rows(tt)};
+        std::copy(rec, rec + 4, ai.begin() + 32 * (size_t)c + 4 * u);
+      }
+    }
+    UP(upload(h, ai, &t.ta_info)); UP(upload(h, ac, &t.ta_cnt));
+    std::vector<int> ti(16 * (size_t)pl.At.nchunks, 0);
+    for (int J = 0; J < 4 * pl.At.nchunks; J++) {
+      const int tt = (J < pl.nb && tp.tt_ptr[J + 1] > tp.tt_ptr[J]) ? tp.tt_tid[tp.tt_ptr[J]] : tp.ntile;
+      int rec[4] = {tt, first(tt), rows(tt), 0};
+      std::copy(rec, rec + 4, ti.begin() + 4 * (size_t)J);
+    }
+    UP(upload(h, ti, &t.tt_info));
+  }
+  std::vector<unsigned long long> mask(pl.A.nchunks, 0ull);
+  for (size_t k = 0; k < (size_t)tp.ntile * BS; k++) if (tp.rowid[k] >= 0) mask[tp.rowid[k] / WAVE] |= 1ull << (tp.rowid[k] % WAVE);
+  UP(upload(h, mask, &t.ta_mask));
+  t.o_tile = s.wl.tile; t.o_ellAr = s.wl.ellAr; t.o_ellAtr = s.wl.ellAtr;
+  return MPCQP_OK;
+}
+// on-chip mode: the chain / hub tables, the set-up kernel's copies of the arguments in its own launch shape, and what only the device knows --
+// whether the table has the tile instance, and how many iteration workgroups it holds at once
+static int upload_onchip(mpcqp_handle *h, int cus) {
+  Selection &s = h->sel; const Plan &pl = s.plan; const OcPlan &o = s.ocplan; const ResPlan &rp = s.rplan; DevRes &dr = h->dres; DevOc &d = h->doc;
+  dr.stage = s.stage; dr.rext = oc_rext(rp.nw, std::max<int>(1, (int)o.pairs.size())); dr.nconst = 0; dr.n_seg = 0;
+  d.nbc = o.nbc; d.has_hub = o.has_hub; d.junc = o.junc; d.npw = o.npw; d.nhr = o.nhr; d.nlds = o.nlds; d.ntab = (int)o.tab.size();
+  d.o_chainE = o.o_chainE; d.o_chainF = o.o_chainF; d.o_pos = o.o_pos; d.o_fill = o.o_fill; d.ghub_slot = o.ghub_slot; d.ghub_src = o.ghub_src;
+  d.npair = (int)o.pairs.size(); d.o_pair = o.o_pair; d.nfill = o.nfill; d.o_s = o.o_s; d.o_dbl = o.o_dbl; d.ndbl = (int)o.dbl.size(); d.o_pp = o.o_pp;
+  d.at_poll = s.at_poll; d.at_free = s.at_free;
+  d.a_lds = s.a_lds; d.p_lds = s.p_lds;
+  if (s.vtiles && !mpcqp_kernel_oc_admm_tl(s.waves, s.oc_ng(), s.oc_nh())) s.vtiles = false;      // (the table has the tile instance for two of the shapes only)
+  UP(upload(h, o.tab, &d.tab));
+  UP(upload(h, oc_asm_records(pl), &d.asm_rec));
+  if (s.tiles || s.vtiles) UP(upload_tiles(h));
+  // (after the tables are uploaded: the set-up kernel's copies of the arguments)
+  const SetupShape &su = s.setup; DevRes &ds = h->dres_setup; DevOc &dd = h->doc_setup;
+  ds = dr; dd = d;
+  dd.a_lds = su.a_lds; dd.p_lds = su.p_lds; dd.ix16 = su.ix16; dd.zpad = su.zpad; dd.ixo_a = su.ixo_a; dd.ixo_p = su.ixo_p;
+  ds.stage = su.stage;
+  if (!s.split) return MPCQP_OK;
+  if (s.oc8 && !s.vtiles && !s.a_assign.empty()) UP(upload(h, s.a_assign, &d.a_assign));
+  if (s.oc8) {
+    int nb = 0; h->qslots = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, oc_admm_of(h, false), s.waves * WAVE, (size_t)s.lds) == hipSuccess && nb > 0) {
+      h->qslots = nb * (cus > 0 ? cus : 256);
+    } else (void)hipGetLastError();
+    UP(dalloc(h, &h->qctr, 16 * 16));
+  }
+  if (h->knobs.verbose) fprintf(stderr, "%s, %d resident workgroups\n", setup_shape_text(s).c_str(), h->qslots);
+  return MPCQP_OK;
+}
+// the per-QP slabs and the outputs
+static int alloc_workspace(mpcqp_handle *h) {
+  const size_t stride = (size_t)h->sel.wl.stride, batch = (size_t)h->batch; const int n = h->n, m = h->m;
+  UP(dalloc(h, &h->ws, stride * batch));
+  // the resident kernels only ever write the structural non-zeros of the T tiles (fixed positions, plan.hpp tpos): their zeros are set here, once
+  HIPCHK(hipMemset(h->ws, 0, stride * batch * sizeof(double))); HIPCHK(hipStreamSynchronize(0));
+  UP(dalloc(h, &h->ox, batch * n)); UP(dalloc(h, &h->oy, batch * std::max(m, 1))); UP(dalloc(h, &h->oz, batch * std::max(m, 1)));
+  UP(dalloc(h, &h->oinfo, batch * 4)); UP(dalloc(h, &h->ocs, batch));
+  UP(dalloc(h, &h->ostatus, batch)); UP(dalloc(h, &h->oiters, batch));
+#ifdef MPCQP_TIMING
+  UP(dalloc(h, &h->odbg, batch * 16 + 128));
+#endif
+  // dispatch-hint buffers up front: nothing is allocated inside mpcqp_solve, so a solve can be captured in a HIP graph
+  UP(dalloc(h, &h->order[0], batch)); UP(dalloc(h, &h->order[1], batch));
+  return MPCQP_OK;
+}
+#undef UP
+// the handle's kernel instances: their dynamic-LDS limit, and that the table has them at all
+static int prepare_kernels(mpcqp_handle *h) {
+  const Selection &s = h->sel;
+  if (s.lds > 48 * 1024) {
+    // MaxDynamicSharedMemorySize is a property of the kernel function, shared by every handle that launches it: keep a running
+    // maximum per function so that a later handle with a smaller footprint never lowers the limit under an earlier one
+    static std::mutex mu; static std::map<std::pair<const void *, int>, long> limit;   // (function, device)
+    const void *fns[4] = {res_kernel_of(h, false), res_kernel_of(h, true), nullptr, nullptr};
+    if (s.waves == 0) fns[0] = fns[1] = s.stream_pd8 ? (const void *)mpcqp_admm_kernel<8> : (const void *)mpcqp_admm_kernel<4>;
+    if (s.split) { fns[0] = oc_setup_of(h, false); fns[1] = oc_setup_of(h, true); fns[2] = oc_admm_of(h, false); fns[3] = oc_admm_of(h, true); }
+    std::lock_guard<std::mutex> lock(mu);
+    for (int k = 0; k < 4; k++) {
+      const void *fn = fns[k];
+      if (!fn) continue;
+      const long want_lds = (s.split && k < 2) ? s.setup.lds : s.lds;
+      long &cur = limit[{fn, h->device}];
+      if (want_lds <= cur) continue;
+      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want_lds) != hipSuccess)
+        return fail(MPCQP_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+      cur = want_lds;
+    }
+  }
+  if (s.waves > 0 && !(s.split ? oc_setup_of(h, false) && oc_setup_of(h, true) && oc_admm_of(h, false) && oc_admm_of(h, true) : res_kernel_of(h, false) && res_kernel_of(h, true)))
+    return fail(MPCQP_ERR_STATE, "no kernel instance for this handle (kernel_table.hpp)");
+  return MPCQP_OK;
+}
+// A handle on `family` ("" = the rule's choice, null = MPCQP_VARIANT if set, else the rule): arguments are checked by the callers.
+static int create_handle(int n, int m, int batch, const int *Pp, const int *Pi, const int *Ap, const int *Ai,
+                         const mpcqp_settings *settings, const char *family, const Knobs &knobs, mpcqp_handle **out) {
+  mpcqp_settings st;
+  if (settings) st = *settings; else mpcqp_default_settings(&st);
+  int dev = 0, cus = 0, rc;
+  if ((rc = mpcqp_pick_device(st.device, &dev))) return rc;
+  if (hipSetDevice(dev) != hipSuccess) return fail(MPCQP_ERR_HIP, "hipSetDevice failed");
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+  mpcqp_handle *h = new mpcqp_handle();
+  h->st = st; h->device = dev; h->n = n; h->m = m; h->batch = batch; h->knobs = knobs;
+  h->sel = select_kernel(n, m, batch, Pp, Pi, Ap, Ai, cus, family, knobs);
+  const Selection &s = h->sel;
+  rc = s.err ? fail(s.err, s.error) : MPCQP_OK;
+  if (!rc) rc = upload_plan(h);
+  if (!rc && s.waves > 0) rc = upload_resident(h);
+  if (!rc && s.oc) rc = upload_onchip(h, cus);
+  if (!rc) rc = alloc_workspace(h);
+  if (!rc) rc = prepare_kernels(h);
+  if (!rc && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess || hipEventCreate(&h->ev_mid) != hipSuccess ||
+              hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming) != hipSuccess)) rc = fail(MPCQP_ERR_HIP, "hipEventCreate failed");
+  if (rc) { mpcqp_destroy(h); return rc; }
+  memset(&h->io, 0, sizeof(h->io));
+  h->lpt = !knobs.no_lpt;
+  *out = h;
+  return MPCQP_OK;
+}
+
 extern "C" {
 
 void mpcqp_default_settings(mpcqp_settings *s) {
@@ -244,445 +439,9 @@ int mpcqp_create(int n, int m, int batch, const int *Pp, const int *Pi, const in
   if (!out) return fail(MPCQP_ERR_ARG, "out is null");
   *out = nullptr;
   if (n <= 0 || m < 0 || batch <= 0 || !Pp || !Pi || !Ap || !Ai) return fail(MPCQP_ERR_ARG, "Invalid dimensions.");
-  if (!g_force_variant && !getenv("MPCQP_VARIANT") && getenv("MPCQP_AUTOTUNE") && getenv("MPCQP_AUTOTUNE")[0] == '1')
-    return mpcqp_create_tuned(n, m, batch, Pp, Pi, Ap, Ai, settings, out);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(MPCQP_ERR_NO_GPU, "hipGetDeviceCount found no device");
-  mpcqp_handle *h = new mpcqp_handle();
-  if (settings) h->st = *settings; else mpcqp_default_settings(&h->st);
-  int dev = h->st.device;
-  if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
-  if (dev >= ndev) { delete h; return fail(MPCQP_ERR_ARG, "device ordinal out of range"); }
-  h->device = dev;
-  auto bail = [&](int rc) { mpcqp_destroy(h); return rc; };
-  if (hipSetDevice(dev) != hipSuccess) return bail(fail(MPCQP_ERR_HIP, "hipSetDevice failed"));
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return bail(fail(MPCQP_ERR_HIP, "hipGetDeviceProperties failed"));
-  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
-    return bail(fail(MPCQP_ERR_NO_GPU, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only"));
-  h->n = n; h->m = m; h->batch = batch;
-  h->plan = build_plan(n, m, Pp, Pi, Ap, Ai);
-  if (!h->plan.error.empty()) return bail(fail(MPCQP_ERR_ARG, h->plan.error));
-  const Plan &pl = h->plan;
-  h->wl = ws_layout(pl);
-  h->lds = lds_bytes(pl);
-  // Kernel shape, from measured rules (profiles/r01_variant_grid.txt): factor in LDS with one, two or four waves per
-  // QP while enough QPs fit a CU, else the factor streamed from the HBM slab.  MPCQP_VARIANT=stream|res1|res2|res4|res8|gres4 overrides.
-  {
-    const long LDS_MAX = 160 * 1024;
-    int want = -1;
-    if (const char *e = variant_request()) {
-      std::string v(e);
-      if (v == "stream") want = 0; else if (v == "res1") want = 1; else if (v == "res4") want = 4; else if (v == "res8") want = 8;
-      else if (v == "gres4") { want = 4; h->gblocks = true; }
-      else if (v == "res2") want = 2;
-      else if (v == "gres2") { want = 2; h->gblocks = true; }
-      else if (v == "oc4") { want = 4; h->gblocks = true; h->oc = true; }
-      else if (v == "oc8") { want = 8; h->gblocks = true; h->oc = true; h->oc8 = -1; }
-    }
-    // candidate plans of the multi-wave kernels: ELL chunk widths padded to multiples of 4 (fewer load batches per chunk)
-    // and the stage chain eliminated from both ends (two concurrent half-length chains)
-    const bool twist = !getenv("MPCQP_NO_TWIST");
-    Plan p1 = build_plan(n, m, Pp, Pi, Ap, Ai, -1, true);
-    Plan p4 = build_plan(n, m, Pp, Pi, Ap, Ai, twist ? 2 : -1, true);
-    if (!p1.error.empty() || p1.nblk > h->plan.nblk) p1 = h->plan;
-    if (!p4.error.empty() || p4.nblk > h->plan.nblk) p4 = p1;
-    const bool small_ok = pl.nblk < 4096 && pl.nb < 512;
-    if (want < 0) {
-      // measured on MI355X: one wave per QP with the factor in LDS when it is tiny; four waves per QP
-      // with the factor in LDS when at least two QPs fit per CU; otherwise occupancy beats residency and the factor
-      // blocks are streamed from the HBM slab by the same LDL' / segment machinery (several workgroups per CU)
-      ResPlan r1 = build_res_plan(p1, 1), r4 = build_res_plan(p4, 4);
-      const long l1 = lds_bytes_res(p1, r1), l4 = lds_bytes_res(p4, r4);
-      // latency regime (measured, tools/graph_tick.py): when the whole batch is resident in one round of 4-wave workgroups
-      // (two per CU by registers, one when the factor needs more than half the LDS), four waves per QP with the factor in
-      // LDS finish a QP soonest (double integrator x256: 1.12 ms vs 1.41 ms with one wave per QP; quadrotor N=20 x256:
-      // 1.21 ms vs 1.96 ms with the factor streamed from HBM)
-      const long cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-      // (workgroups of the LDS-resident 4-wave kernel per CU: by LDS, and by the register budget of its instances -- 128 / 168 / 256 VGPRs)
-      const long cap4 = (small_ok && l4 <= LDS_MAX) ? std::min<long>(LDS_MAX / l4, l4 <= 40 * 1024 ? 4 : l4 <= 53 * 1024 ? 3 : 2) : 0;
-      // two waves per QP (168-VGPR instance: up to six per CU): the two half chains of the twisted order each get a wave and nothing idles in
-      // the chain phases.  Taken where it fits more QPs per CU than the 4-wave kernel and at most one fewer than one wave per QP would:
-      // double integrator N=20 (28 KiB, five per CU) 1.87 M QP/s against 1.55 M with one wave and 1.46 M with four; at 21-23 KiB +4...8 %
-      // over one wave; below 15 KiB one wave per QP (11-13 per CU) wins, at 34 KiB and above the 4-wave kernel; same latency as the 4-wave
-      // kernel on a batch of 64-1024
-      const ResPlan r2 = build_res_plan(p4, 2);
-      const long l2 = lds_bytes_res(p4, r2);
-      const long q1 = small_ok && l1 <= LDS_MAX ? LDS_MAX / l1 : 0, q2 = small_ok && l2 <= 40 * 1024 ? std::min<long>(LDS_MAX / l2, 6) : 0;
-      auto oc_takes = [&]() {
-        if (getenv("MPCQP_NO_OC") || !small_ok) return false;
-        auto ok4 = [&](const Plan &q) { const OcPlan o = build_oc_plan(q, 4, 1 << 20, OC_NG, OC_NH); return o.ok && lds_bytes_oc(q, build_res_plan(q, 4, false), o) <= OC_LDS_MAX; };
-        if (ok4(p4)) return true;
-        // (the padded twist -- plan.hpp ordering 3 -- where the hub variables would otherwise share a block with the last frame and spill into a second one: cart-pole N=22, 25)
-        if (!twist) return false;
-        const Plan q = build_plan(n, m, Pp, Pi, Ap, Ai, 3, 1);
-        return q.error.empty() && ok4(q);
-      };
-      if (q2 > cap4 && q2 + 1 >= q1 && !getenv("MPCQP_NO_RES2")) want = 2;
-      // the latency regime above; with three or four 4-wave workgroups per CU they stay ahead of one wave per QP up to about three resident
-      // rounds (double integrator x2048 1.57 vs 1.81 ms, x4096 2.89 vs 2.76 ms)
-      else if (cap4 > 0 && (long)batch <= cus * cap4 * (cap4 >= 3 ? 3 : 1)) {
-        want = 4;
-        // ... and in it the on-chip mode where it takes the pattern: up to two rounds of its two workgroups per CU it finishes a batch sooner than
-        // the LDS-resident kernel at any occupancy (tools/small_batch_scan.py, x 64 ... 1024: quadrotor N = 5 / 10 / 20 0.21 / 0.43 / 0.85 ms against
-        // 0.24 / 0.52 / 1.08, cart-pole N = 20 / 30 0.73 / 1.12 against 0.89 / 1.41, double integrator N = 30 / 50 1.11 / 1.64 against 1.31 / 2.18)
-        if ((long)batch <= cus * 4 && oc_takes()) { h->gblocks = true; h->oc = true; }
-      }
-      // one wave per QP only where it puts more QPs on a CU than the 4-wave kernel has workgroups there (five against four at 28 KiB: +6 %;
-      // four against four at 34-36 KiB: the 4-wave kernel is 23-31 % ahead -- double integrator N=24 / 26, cart-pole N=15)
-      else if (small_ok && l1 <= 40 * 1024 && LDS_MAX / l1 > cap4) want = 1;
-      else {
-        // The on-chip mode (factor in LDS + registers at two workgroups per CU, solves and factorisation on the matrix cores) wherever the pattern is
-        // a block chain with an arrow head that fits it AND the alternative is the LDS-resident 4-wave kernel at two workgroups per CU or a factor
-        // streamed from the slab (measured, profiles/r02_final_variant_grid.txt, x 8192: quadrotor N = 6 ... 20 +8 ... +48 %, cart-pole N = 30 / 40 / 50
-        // +20 / +26 / +37 %, double integrator N = 40 ... 80 +12 ... +64 %).  With three or more resident workgroups per CU the LDS-resident
-        // kernels stay ahead (quadrotor N = 5 2.57 vs 2.06 M QP/s, cart-pole N = 20 818k vs 656k, double integrator N = 30 792k vs 611k).
-        // LDS-resident 4-wave kernel while two fit a CU
-        if (small_ok && l4 <= 80 * 1024) { want = 4; if (l4 > 53 * 1024 && oc_takes()) { h->gblocks = true; h->oc = true; } }
-        // factor streamed from the slab, two waves per QP (168-VGPR instance, six workgroups per CU) while six fit the LDS: ahead of four waves x
-        // four workgroups there (double integrator N=100 145k -> 156k QP/s; at 32 KiB and above four waves win)
-        else if (small_ok && !getenv("MPCQP_NO_RES2") && lds_bytes_res_gb(p4, build_res_plan(p4, 2, true)) <= LDS_MAX / 6) {
-          want = 2; h->gblocks = true;
-          if (oc_takes()) { want = 4; h->oc = true; }
-        }
-        else if (small_ok && lds_bytes_res_gb(p4, build_res_plan(p4, 4, true), !getenv("MPCQP_NO_ZYG")) <= LDS_MAX) { want = 4; h->gblocks = true; h->oc = oc_takes(); }
-        else want = 0;
-      }
-    }
-    // Long chains: where the rules above arrive at a factor streamed from the slab, the eight-wave on-chip instances take the pattern if it is
-    // a block chain with an arrow head of up to 56 blocks that fits one CU (MPCQP_NO_OC8 keeps the global-block kernels)
-    if ((h->oc8 < 0 || (want > 0 && h->gblocks && !h->oc && !variant_request() && !getenv("MPCQP_NO_OC8") && !getenv("MPCQP_NO_OC"))) && small_ok) {
-      Plan p8 = build_plan(n, m, Pp, Pi, Ap, Ai, twist ? 3 : -1, 2);
-      h->oc8 = 0;
-      if (twist && !getenv("MPCQP_NO_DISSECT")) {
-        // the dissected order first (plan.hpp build_plan ordering 4): separators of the stage chain in the hub block where it has room, several twisted pairs of
-        // short chains instead of one pair of long ones
-        Plan pd = build_plan(n, m, Pp, Pi, Ap, Ai, 4, 2);
-        if (pd.error.empty()) {
-          const ResPlan rd = build_res_plan(pd, 8, false);
-          for (int k = 0; k < 2 && !h->oc8; k++) {
-            const OcPlan o = build_oc_plan(pd, 8, 1 << 20, OC8_INST[k].ng, OC8_INST[k].nh, OC8_MAX_CHAIN);
-            if (o.ok && o.has_hub && o.pairs.size() > 1 && lds_bytes_oc(pd, rd, o, OC8_INST[k].zyg) <= OC8_LDS_MAX) {
-              h->ocplan = o; h->oc8 = k + 1; h->oc = true; h->gblocks = true; h->zyg = OC8_INST[k].zyg; want = 8; p4 = pd;
-            }
-          }
-        }
-      }
-      if (!h->oc8 && p8.error.empty()) {
-        const ResPlan r8 = build_res_plan(p8, 8, false);
-        for (int k = 0; k < 2 && !h->oc8; k++) {
-          const OcPlan o = build_oc_plan(p8, 8, 1 << 20, OC8_INST[k].ng, OC8_INST[k].nh, OC8_MAX_CHAIN);
-          // (a pattern without an arrow head -- the reduced form -- runs the same instances with no hub block: two-kernel form only)
-          if (o.ok && (o.has_hub || !getenv("MPCQP_OC_MONO")) && lds_bytes_oc(p8, r8, o, OC8_INST[k].zyg) <= OC8_LDS_MAX) {
-            h->ocplan = o; h->oc8 = k + 1; h->oc = true; h->gblocks = true; h->zyg = OC8_INST[k].zyg; want = 8; p4 = p8;
-          }
-        }
-      }
-      if (!h->oc8 && variant_request() && std::string(variant_request()) == "oc8")
-        return bail(fail(MPCQP_ERR_LIMIT, "the eight-wave on-chip variant does not take this pattern / size"));
-    }
-    if (h->oc && !h->oc8) {
-      // on-chip mode: block tridiagonal + arrow patterns whose factor fits LDS + the registers of the instance at two workgroups per CU
-      const ResPlan r4 = build_res_plan(p4, 4, false);
-      h->oc = false;
-      OcPlan o = small_ok ? build_oc_plan(p4, 4, 1 << 20, OC_NG, OC_NH) : OcPlan();
-      bool dissected4 = false, padded4 = false;
-      if (small_ok && twist && !getenv("MPCQP_NO_PADTWIST")) {
-        // the padded twist (ordering 3: the hub moved up to a block boundary, the chain part whole blocks) where the plain order is not taken -- the hub shares a
-        // block with the last frame and spills into a second one: cart-pole N=22, 25 fell to the LDS-resident kernel, 18 ms against 12 -- or leaves one long chain
-        // where the twist has two (cart-pole N=24: one chain of 7)
-        Plan q = build_plan(n, m, Pp, Pi, Ap, Ai, 3, 2);
-        if (q.error.empty()) {
-          const OcPlan oq = build_oc_plan(q, 4, 1 << 20, OC_NG, OC_NH);
-          auto longest = [](const OcPlan &x) { return std::max(x.chainE.size(), x.chainF.size()); };
-          const bool fits = oq.ok && lds_bytes_oc(q, build_res_plan(q, 4, false), oq) <= OC_LDS_MAX, o_fits = o.ok && lds_bytes_oc(p4, r4, o) <= OC_LDS_MAX;
-          if (fits && (!o_fits || longest(oq) < longest(o))) { o = oq; p4 = q; padded4 = true; }
-        }
-      }
-      if (o.ok && o.has_hub && twist && !getenv("MPCQP_NO_DISSECT") && !getenv("MPCQP_OC_MONO") && !getenv("MPCQP_TILES") && !getenv("MPCQP_VTILES") && !getenv("MPCQP_DOUBLES")) {
-        // the dissected order with one separator: two twisted pairs on the four waves (plan.hpp build_plan ordering 4; its own kernel instances, two-kernel form only)
-        Plan pd = build_plan(n, m, Pp, Pi, Ap, Ai, 4, 2, 1);
-        if (pd.error.empty()) {
-          const OcPlan od = build_oc_plan(pd, 4, 1 << 20, OC_NG, OC_NH);
-          if (od.ok && od.pairs.size() == 2 && lds_bytes_oc(pd, build_res_plan(pd, 4, false), od) <= OC_LDS_MAX) { o = od; p4 = pd; dissected4 = true; }
-        }
-      }
-      if (o.ok && (dissected4 || padded4 || lds_bytes_oc(p4, r4, o) <= OC_LDS_MAX)) {
-        h->ocplan = o; h->oc = true;
-        // same ordering and blocks, ELL widths for this instance's 8 slots in flight (plan.hpp build_ell pad = 2)
-        if (!dissected4 && !padded4 && !getenv("MPCQP_OC_PAD4")) { Plan poc = build_plan(n, m, Pp, Pi, Ap, Ai, twist ? 2 : -1, 2); if (poc.error.empty() && poc.nblk == p4.nblk) p4 = poc; }
-      }
-      if (!h->oc && want == 4 && variant_request() && std::string(variant_request()) == "oc4")
-        return bail(fail(MPCQP_ERR_LIMIT, "the on-chip variant does not take this pattern / size"));
-    }
-    if (want > 0) { h->plan = want >= 2 ? p4 : p1; h->wl = ws_layout(h->plan); }
-    if (want > 0) {
-      h->rplan = build_res_plan(pl, want, h->gblocks && !h->oc);
-      if (h->oc && h->ocplan.has_hub && getenv("MPCQP_TILES") && getenv("MPCQP_TILES")[0] == '1') {
-        // EXPERIMENTAL, opt-in (MPCQP_TILES=1): dense tiles for the two sweeps of the iteration where the pattern has them (dense Jacobian
-        // blocks: the quadrotor's 12 x 16 per stage) and the LDS still fits.  Parity-green, but measured SLOWER than the ELL sweeps in these
-        // register-bound instances (quadrotor N = 20 x 8192: 12.0 - 13.7 ms against 8.68), so the default stays ELL.
-        h->tplan = build_tile_plan(pl, n, m, Ap, Ai, 2);
-        h->tiles = h->tplan.on && h->tplan.max_per_block <= 1 && h->tplan.max_per_chunk <= 8 && h->tplan.rows_consecutive &&
-                   pl.A.nchunks <= 3 * want && pl.At.nchunks <= 2 * want &&      // (kernel_onchip.hpp OC_TILE_MAXA / OC_TILE_MAXT chunk records per wave)
-                   lds_bytes_oc(pl, h->rplan, h->ocplan, h->oc8 && h->zyg, &h->tplan) <= (h->oc8 ? OC8_LDS_MAX : OC_LDS_MAX);
-        if (h->tiles) h->wl = ws_layout(pl, &h->tplan);
-      }
-      if (h->oc && !h->tiles && getenv("MPCQP_VTILES") && getenv("MPCQP_VTILES")[0] == '1' && !getenv("MPCQP_OC_MONO")) {
-        // EXPERIMENT, opt-in (MPCQP_VTILES=1): the two sweeps of the iteration on ONE copy of A's dense blocks -- 16 x 16 tiles, row-major in the slab, multiplied
-        // on the vector ALUs (kernel_oc_split.hpp) -- plus the remainder ELL layouts.  No LDS beyond the ELL form's.  The set-up still writes the two ELL copies:
-        // the residual sweeps of the termination checks and the factorisation read them.
-        h->tplan = build_tile_plan(pl, n, m, Ap, Ai, 2);
-        bool fits = h->tplan.on && h->tplan.max_per_block <= 1 && h->tplan.max_per_chunk <= 8 && h->tplan.rows_consecutive &&
-                    pl.A.nchunks <= 8 * want && pl.At.nchunks <= 16 * want;          // (a wave's tile records ride in the lanes of registers: 8 tiles x 8 chunks of A, 4 blocks x 16 chunks of A')
-        for (int t = 0; t < h->tplan.ntile && fits; t++) {
-          int first = -1; for (int r = 0; r < BS; r++) if (h->tplan.rowid[(size_t)t * BS + r] >= 0) { first = h->tplan.rowid[(size_t)t * BS + r]; break; }
-          fits = first >= 0 && first + BS <= pl.mpad;                                 // (a tile's sixteen rows of w are read as they lie: all inside the vector)
-        }
-        h->vtiles = fits;
-        if (h->vtiles) h->wl = ws_layout(pl, &h->tplan);
-      }
-      long need = h->oc ? lds_bytes_oc(pl, h->rplan, h->ocplan, h->oc8 && h->zyg, h->tiles ? &h->tplan : nullptr) : h->gblocks ? lds_bytes_res_gb(pl, h->rplan) : lds_bytes_res(pl, h->rplan);
-      if (h->oc && !h->tiles && getenv("MPCQP_DOUBLES")) {
-        // EXPERIMENT, opt-in (MPCQP_DOUBLES=<n>): double stages of the solve (plan.hpp oc_add_doubles) where the CU's LDS has room for their product blocks
-        // beside the factor: every one takes a dependent 16 x 16 mat-vec off the critical path of both triangular sweeps.  Parity-green, but measured
-        // SLOWER (cart-pole N=100: 29.1 against 27.8 ms): the four wave-parallel phases it adds (two mat-vecs per double stage and direction, 48 cycles
-        // of matrix pipe per MFMA, four more barriers) cost more than the halved chains save.
-        const long cap = h->oc8 ? OC8_LDS_MAX : OC_LDS_MAX;
-        int nd = (int)std::max<long>(0, (cap - need) / (BLK * 8));
-        nd = std::min(nd, std::max(0, atoi(getenv("MPCQP_DOUBLES"))));
-        for (; nd > 0; nd--) {       // (the table grows with the stages: take as many as still fit)
-          OcPlan o2 = h->ocplan; oc_add_doubles(o2, nd);
-          const long n2 = lds_bytes_oc(pl, h->rplan, o2, h->oc8 && h->zyg, nullptr);
-          if (n2 <= cap) { h->ocplan = o2; need = n2; break; }
-        }
-      }
-      if (h->gblocks && !h->oc && want == 4 && !getenv("MPCQP_NO_ZYG")) {     // (the two-wave global-block kernel has no such instance: forced on a long horizon it took this layout and returned garbage)
-        // long horizons: with z and y in the slab one more workgroup fits per CU (2 -> 3 or 1 -> 2); measured on quadrotor N=50
-        const long alt = lds_bytes_res_gb(pl, h->rplan, true);
-        const long fit = LDS_MAX / need, fit_alt = std::min<long>(LDS_MAX / alt, 3);
-        if (fit <= 2 && fit_alt > fit) { h->zyg = true; need = alt; }
-      }
-      h->occ4 = h->gblocks && !h->oc && !h->zyg && need <= 53 * 1024 && !getenv("MPCQP_GB_OCC2");
-      // LDS between 40 and 53 KiB: three workgroups per CU fit, so the instance compiled for three waves per SIMD (168 VGPRs, no
-      // spills, 8 blocks in flight) replaces the 128-VGPR one (at 42 KiB 92.9k -> 95.8k QP/s on cart-pole N=100, which now fits four per CU
-      // because the temp tiles alias w, plan.hpp gb_tmp_alias: 76.2 -> 73.2 ms per 8192; at 32 KiB it loses, 589k -> 551k)
-      // (with z and y in the slab the 168-VGPR instance at three per CU also beats the 128-VGPR one at four: quadrotor N=50 23.9 vs 26.0 ms)
-      h->occ3 = h->gblocks && !h->oc && need <= 53 * 1024 && (need > 40 * 1024 || h->zyg || getenv("MPCQP_GB_OCC3")) && !getenv("MPCQP_GB_OCC2");
-      if (!small_ok || need > LDS_MAX) return bail(fail(MPCQP_ERR_LIMIT, "resident variant needs " + std::to_string(need) + " B of LDS"));
-      h->lds = need;
-      h->res1x = want == 1 && !h->gblocks && LDS_MAX / need > 8 && !getenv("MPCQP_NO_RES1X");
-      if (!h->gblocks && want == 4 && !getenv("MPCQP_NO_RES3")) h->res3 = need <= 40 * 1024 ? 4 : need <= 53 * 1024 ? 3 : 0;
-      if (const char *pad = getenv("MPCQP_LDS_MIN")) h->lds = std::max<long>(h->lds, atol(pad));   // experiment: limit workgroups per CU
-    }
-    h->variant = want;
-  }
-  if (h->lds > 160 * 1024) return bail(fail(MPCQP_ERR_LIMIT, "LDS footprint " + std::to_string(h->lds) + " B exceeds 160 KiB per CU"));
-  DevPlan &dp = h->dp;
-  memset(&dp, 0, sizeof(dp));
-  dp.n = n; dp.m = m; dp.npad = pl.npad; dp.mpad = pl.mpad; dp.nb = pl.nb; dp.nblk = pl.nblk; dp.nfac = (int)pl.fac.size(); dp.nT = pl.nT;
-  int rc;
-#define UP(expr) if ((rc = (expr))) return bail(rc)
-  UP(upload_ell(h, pl.A, &dp.A)); UP(upload_ell(h, pl.At, &dp.At)); UP(upload_ell(h, pl.P, &dp.P));
-  UP(upload(h, pl.pos, &dp.pos)); UP(upload(h, pl.perm, &dp.perm));
-  UP(upload(h, pl.fwd_ops, &dp.fwd_ops)); UP(upload(h, pl.bwd_ops, &dp.bwd_ops)); UP(upload(h, pl.bwd_of, &dp.bwd_of));
-  {
-    std::vector<int4> f(pl.fac.size());
-    for (size_t i = 0; i < f.size(); i++) f[i] = make_int4(pl.fac[i].type, pl.fac[i].dst, pl.fac[i].a, pl.fac[i].b);
-    UP(upload(h, f, &dp.fac));
-  }
-  UP(upload(h, pl.tpos, &dp.tpos)); UP(upload(h, pl.asm_ptr, &dp.asm_ptr)); UP(upload(h, pl.asm_a, &dp.asm_a));
-  UP(upload(h, pl.asm_b, &dp.asm_b)); UP(upload(h, pl.asm_pidx, &dp.asm_pidx)); UP(upload(h, pl.blk_diag, &dp.blk_diag));
-  if (h->variant > 0) {
-    const ResPlan &rp = h->rplan; DevRes &dr = h->dres;
-    dr.nphase = rp.nphase; dr.ntemp = rp.ntemp; dr.nconst = rp.nconst; dr.rext = rp.rext;
-    dr.nlev = rp.nlev;
-    UP(upload(h, rp.lv_ptr, &dr.lv_ptr)); UP(upload(h, rp.lv_diag, &dr.lv_diag)); UP(upload(h, rp.lw_ptr, &dr.lw_ptr));
-    UP(upload(h, rp.lw_slot, &dr.lw_slot)); UP(upload(h, rp.lw_g, &dr.lw_g)); UP(upload(h, rp.lu_ptr, &dr.lu_ptr));
-    UP(upload(h, rp.lu_dst, &dr.lu_dst)); UP(upload(h, rp.lu_tmp, &dr.lu_tmp)); UP(upload(h, rp.lu_b, &dr.lu_b));
-    UP(upload(h, rp.g_ptr, &dr.g_ptr)); UP(upload(h, rp.g_seg, &dr.g_seg)); dr.n_seg = (int)rp.g_seg.size() / 8; dr.stage = h->gblocks ? res_stage_doubles_gb(pl, rp) : res_stage_doubles(pl, rp);
-    dr.tmp_alias = h->gblocks && !h->oc && gb_tmp_alias(pl, rp) ? 1 : 0;
-    memset(&h->doc, 0, sizeof(h->doc));
-    if (h->oc) {
-      const OcPlan &o = h->ocplan; DevOc &d = h->doc;
-      dr.stage = oc_stage_doubles(o, rp, pl); dr.rext = oc_rext(rp.nw, std::max<int>(1, (int)o.pairs.size())); dr.nconst = 0; dr.n_seg = 0;
-      d.nbc = o.nbc; d.has_hub = o.has_hub; d.junc = o.junc; d.npw = o.npw; d.nhr = o.nhr; d.nlds = o.nlds; d.ntab = (int)o.tab.size();
-      d.o_chainE = o.o_chainE; d.o_chainF = o.o_chainF; d.o_pos = o.o_pos; d.o_fill = o.o_fill; d.ghub_slot = o.ghub_slot; d.ghub_src = o.ghub_src;
-      d.npair = (int)o.pairs.size(); d.o_pair = o.o_pair; d.nfill = o.nfill; d.o_s = o.o_s; d.o_dbl = o.o_dbl; d.ndbl = (int)o.dbl.size(); d.o_pp = o.o_pp;
-      d.at_poll = d.at_free = -1;
-      // (opt-in since the chains run on the 4-block MFMA: they now reach the ticket before wave 3 has the rows -- 913k with, 917k without)
-      // (single-kernel four-wave instance only: the eight-wave solve, oc_solve_long, has no ticket wait, and the two-kernel form sweeps all of A' up front)
-      h->split = !h->tiles && !getenv("MPCQP_OC_MONO") && pl.A.nchunks <= 32 * h->variant && pl.At.nchunks <= 32 * h->variant;
-      if (!h->split || !mpcqp_kernel_oc_admm_tl(h->variant, h->oc8 ? OC8_INST[h->oc8 - 1].ng : OC_NG, !o.has_hub ? 0 : h->oc8 ? OC8_INST[h->oc8 - 1].nh : OC_NH)) h->vtiles = false;      // (a wave's chunk offsets ride in the lanes of one register: kernel_oc_split.hpp oc_my_chunks)
-      if (const char *e = getenv("MPCQP_RESUME_ROUNDS")) h->resume_rounds = std::max(0, std::min(atoi(e), 8));
-      if (getenv("MPCQP_LATE") && !h->tiles && !h->oc8 && !h->split) oc_late_chunks(pl, o, 4, 3 /* OC_POLL_TRIP */, &d.at_poll, &d.at_free);
-      d.a_lds = (long)pl.A.entries() <= dr.stage ? 1 : 0;
-      d.p_lds = d.a_lds && (long)pl.A.entries() + (long)pl.P.entries() <= dr.stage ? 1 : 0;
-      h->setup_nw = h->variant; h->dres_setup = dr; h->lds_setup = 0;
-      UP(upload(h, o.tab, &d.tab));
-      UP(upload(h, oc_asm_records(pl), &d.asm_rec));
-      if (h->tiles || h->vtiles) {
-        const TilePlan &tp = h->tplan; DevTile &t = d.tl;
-        t.on = 1; t.ntile = tp.ntile; t.nAr = tp.Ar.nchunks; t.nAtr = tp.Atr.nchunks; t.Ar_entries = tp.Ar.entries(); t.Atr_entries = tp.Atr.entries();
-        UP(upload(h, tp.Ar.chunk_off, &t.Ar_off)); UP(upload(h, tp.Ar.idx, &t.Ar_idx)); UP(upload(h, tp.Ar.src, &t.Ar_src));
-        UP(upload(h, tp.Atr.chunk_off, &t.Atr_off)); UP(upload(h, tp.Atr.idx, &t.Atr_idx)); UP(upload(h, tp.Atr.src, &t.Atr_src));
-        UP(upload(h, tp.tJ, &t.tJ)); UP(upload(h, tp.rowid, &t.rowid));
-        if (h->vtiles) {      // row-major tiles for the vector-ALU form: element (r, c) at 16 r + c (the plan keeps the MFMA operand order [r + 16 (c & 3)][c >> 2])
-          std::vector<int> rm(tp.tsrc.size(), -1);
-          for (size_t tt = 0; tt < tp.tsrc.size() / BLK; tt++) for (int r = 0; r < BS; r++) for (int c = 0; c < BS; c++)
-            rm[tt * BLK + r * BS + c] = tp.tsrc[tt * BLK + (r + BS * (c & 3)) * 4 + (c >> 2)];
-          UP(upload(h, rm, &t.tsrc));
-        } else UP(upload(h, tp.tsrc, &t.tsrc));
-        {   // per-chunk records of fixed size (kernel_onchip.hpp oc_tiles_a / oc_tiles_at): {tile, column block, first row, rows}, padded with the zero tile
-          auto first = [&](int tt) { for (int r = 0; r < BS; r++) if (tp.rowid[(size_t)tt * BS + r] >= 0) return tp.rowid[(size_t)tt * BS + r]; return 0; };
-          auto rows = [&](int tt) { int k = 0; for (int r = 0; r < BS; r++) k += tp.rowid[(size_t)tt * BS + r] >= 0; return k; };
-          std::vector<int> ai(32 * (size_t)pl.A.nchunks, 0), ac(pl.A.nchunks, 0);
-          for (int c = 0; c < pl.A.nchunks; c++) {
-            ac[c] = tp.ta_ptr[c + 1] - tp.ta_ptr[c];
-            for (int u = 0; u < 8; u++) {
-              const int tt = u < ac[c] ? tp.ta_tid[tp.ta_ptr[c] + u] : tp.ntile;
-              int rec[4] = {tt, tp.tJ[tt], first(tt), rows(tt)};
-              std::copy(rec, rec + 4, ai.begin() + 32 * (size_t)c + 4 * u);
-            }
-          }
-          UP(upload(h, ai, &t.ta_info)); UP(upload(h, ac, &t.ta_cnt));
-          std::vector<int> ti(16 * (size_t)pl.At.nchunks, 0);
-          for (int J = 0; J < 4 * pl.At.nchunks; J++) {
-            const int tt = (J < pl.nb && tp.tt_ptr[J + 1] > tp.tt_ptr[J]) ? tp.tt_tid[tp.tt_ptr[J]] : tp.ntile;
-            int rec[4] = {tt, first(tt), rows(tt), 0};
-            std::copy(rec, rec + 4, ti.begin() + 4 * (size_t)J);
-          }
-          UP(upload(h, ti, &t.tt_info));
-        }
-        std::vector<unsigned long long> mask(pl.A.nchunks, 0ull);
-        for (size_t k = 0; k < (size_t)tp.ntile * BS; k++) if (tp.rowid[k] >= 0) mask[tp.rowid[k] / WAVE] |= 1ull << (tp.rowid[k] % WAVE);
-        UP(upload(h, mask, &t.ta_mask));
-        t.o_tile = h->wl.tile; t.o_ellAr = h->wl.ellAr; t.o_ellAtr = h->wl.ellAtr;
-      }
-    }
-  }
-  if (h->oc) {      // (after the tables are uploaded: the set-up kernel's copies of the arguments)
-    h->doc_setup = h->doc; h->lds_setup = h->lds;
-    if (h->split) {
-      // The set-up as four-wave workgroups with their own LDS request -- the factorisation's scratch blocks and assembly records, the staged values of A
-      // and P where they fit, their 16-bit index tables where those fit too -- and their own vector layout: q stays in the slab, z is never touched, y
-      // holds one n-vector of the Ruiz passes (kernel_oc_split.hpp oc_lds).  Three workgroups per CU (the kernel's 164 VGPRs allow no more) beat two
-      // wherever A's values still fit beside them, and so does an unstaged third against a half-staged pair; a fully staged pair beats an unstaged
-      // three.  Measured (x 8192 unless said, set-up kernel, ms): quadrotor N=20 A + P + index tables at two per CU 2.47, A alone at three 2.35, nothing
-      // staged at three 3.26 (round-4 mid build); cart-pole N=50 2.14 / 1.95; cart-pole N=100 A staged at two 4.28, nothing staged at three 3.99;
-      // quadrotor N=50 nothing fits: two per CU 8.05, squeezed to three 8.55 (not taken: the footprint is what the layout needs).  DESIGN.md 3.9
-      const Plan &pq = h->plan; DevRes &ds = h->dres_setup; DevOc &dd = h->doc_setup;
-      const long scratch = 8L * BLK + ((4L * pq.nblk + 15) / 16) * 16;                 // (plan.hpp oc_stage_doubles: OC_LDL_SCR blocks + the assembly records)
-      const long vec = 2L * pq.npad + oc_rext(h->variant, std::max<int>(1, (int)h->ocplan.pairs.size())) + pq.mpad + pq.npad + 16L * 4 + 16 + 16L * 4;      // x, r; w; y (an n-vector here); the reduction scratch
-      const long tabw = ((long)h->ocplan.o_pos + 1) / 2 + 4 + ((long)pq.A.nchunks + pq.At.nchunks + pq.P.nchunks + 3 + 1 + 1) / 2;
-      const long cu = 160L * 1024, nA = (long)pq.A.entries(), nP = (long)pq.P.entries();
-      struct Shape { long stage, bytes; int a, p, ix16, zpad, ixo_a, ixo_p; bool fits; };
-      const long zoff = 2L * pq.npad + oc_rext(h->variant, std::max<int>(1, (int)h->ocplan.pairs.size()));      // (the z region starts behind x and r: kernel_oc_split.hpp oc_lds<NW, true>)
-      auto shape = [&](const long cap_bytes) {
-        const long cap = cap_bytes / 8;
-        Shape r{scratch, 0, 0, 0, 0, 0, 0, 0, false};
-        if (std::max(scratch, nA) + vec + tabw <= cap) { r.stage = std::max(scratch, nA); r.a = 1; }
-        if (r.a && std::max(scratch, nA + nP) + vec + tabw <= cap) { r.stage = std::max(scratch, nA + nP); r.p = 1; }
-        r.stage = (r.stage + 15) / 16 * 16;
-        long total = r.stage + vec + tabw;
-        const long zA = (nA / 4 + 15) / 16 * 16, zP = (nP / 4 + 15) / 16 * 16, zAP = ((nA + nP) / 4 + 15) / 16 * 16;
-        const bool ix_ok = pq.npad < 65536 && !getenv("MPCQP_NO_IX16");
-        if (r.a && r.p && ix_ok) {      // (the ten Ruiz passes then gather without a round trip to the L2 in front of every batch)
-          if (total + zAP <= cap) { r.ix16 = 3; r.zpad = (int)zAP; } else if (total + zA <= cap) { r.ix16 = 1; r.zpad = (int)zA; }
-          r.ixo_a = (int)(4 * (r.stage + zoff)); r.ixo_p = r.ixo_a + (int)nA;
-          total += r.zpad;
-        } else if (!r.a && ix_ok) {
-          // values in the slab: the index tables alone (a quarter less to read per pass, the gathers' addresses from LDS) -- one of them in the factorisation's
-          // scratch, which is idle until the factorisation starts, the other in the z region where that does not cost a workgroup per CU
-          const bool a_scr = zA <= r.stage, p_scr = zP <= r.stage;
-          auto z_fits = [&](long z) { return total + z <= cap && cu / ((total + z) * 8) == cu / (total * 8); };
-          if (a_scr && z_fits(zP)) { r.ix16 = 3; r.ixo_a = 0; r.zpad = (int)zP; r.ixo_p = (int)(4 * (r.stage + zoff)); }
-          else if (p_scr && z_fits(zA)) { r.ix16 = 3; r.ixo_p = 0; r.zpad = (int)zA; r.ixo_a = (int)(4 * (r.stage + zoff)); }
-          else if (a_scr) { r.ix16 = 1; r.ixo_a = 0; }
-          else if (z_fits(zA)) { r.ix16 = 1; r.zpad = (int)zA; r.ixo_a = (int)(4 * (r.stage + zoff)); }
-          total += r.zpad;
-        }
-        r.bytes = total * 8; r.fits = total <= cap;
-        return r;
-      };
-      Shape sh = shape(cu / 2);
-      if (const char *e = getenv("MPCQP_SETUP_CAP")) sh = shape(atol(e));
-      else { const Shape s3 = shape(cu / 3); if (s3.fits && (s3.a || !(sh.a && sh.p))) sh = s3; }
-      dd.a_lds = sh.a; dd.p_lds = sh.p; dd.ix16 = sh.ix16; dd.zpad = sh.zpad; dd.ixo_a = sh.ixo_a; dd.ixo_p = sh.ixo_p;
-      ds.stage = sh.stage; h->setup_nw = 4; h->lds_setup = sh.bytes;
-      const long vecs = vec + sh.zpad;
-      if (h->oc8 && !h->vtiles && !getenv("MPCQP_NO_ABALANCE")) {
-        // row chunks of A to waves by longest-processing-time over their load batches (a batch = one round trip to memory; plan.hpp ell_batches8)
-        std::vector<int> assign(8 * 32, -1), load(8, 0), cnt(8, 0), order_(pq.A.nchunks);
-        for (int c = 0; c < pq.A.nchunks; c++) order_[c] = c;
-        auto batches = [&](int c) { return ell_batches8(pq.A.chunk_off[c + 1] - pq.A.chunk_off[c]); };
-        std::stable_sort(order_.begin(), order_.end(), [&](int a, int b) { return batches(a) > batches(b); });
-        bool okA = true;
-        for (int c : order_) {
-          int w = 0;
-          for (int v = 1; v < 8; v++) if (load[v] < load[w] || (load[v] == load[w] && cnt[v] < cnt[w])) w = v;
-          if (cnt[w] >= 32) { okA = false; break; }
-          assign[w * 32 + cnt[w]++] = c; load[w] += std::max(1, batches(c));
-        }
-        if (okA) UP(upload(h, assign, &h->doc.a_assign));
-      }
-      if (h->oc8) {
-        int nb = 0; h->qslots = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, oc_admm_of(h, false), h->variant * WAVE, (size_t)h->lds) == hipSuccess && nb > 0) {
-          h->qslots = nb * (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
-        } else (void)hipGetLastError();
-        UP(dalloc(h, &h->qctr, 16 * 16));
-      }
-      if (getenv("MPCQP_VERBOSE")) fprintf(stderr, "mpcqp: set-up kernel shape: 4 waves, %ld B of LDS (values of A %s, of P %s, 16-bit index tables %s; A %ld + P %ld entries, vectors %ld, tables %ld doubles), iteration kernel %ld B, %d resident workgroups\n",
-                                           h->lds_setup, dd.a_lds ? "staged" : "in the slab", dd.p_lds ? "staged" : "in the slab", dd.ix16 == 3 ? "A and P" : dd.ix16 ? "A" : "off", (long)pq.A.entries(), (long)pq.P.entries(), vecs, tabw, (long)h->lds, h->qslots);
-    }
-  }
-  const WsLayout &w = h->wl;
-  dp.o_ellA = w.ellA; dp.o_ellAt = w.ellAt; dp.o_ellP = w.ellP; dp.o_Lf = w.Lf; dp.o_Lb = w.Lb; dp.o_T = w.T;
-  dp.o_l = w.l; dp.o_u = w.u; dp.o_D = w.D; dp.o_E = w.E; dp.o_dx = w.dx; dp.o_dy = w.dy; dp.o_Zg = w.Zg; dp.o_Yg = w.Yg; dp.ws_stride = w.stride;
-  UP(dalloc(h, &h->ws, (size_t)w.stride * batch));
-  // the resident kernels only ever write the structural non-zeros of the T tiles (fixed positions, plan.hpp tpos): their zeros are set here, once
-  UP([&]() -> int { HIPCHK(hipMemset(h->ws, 0, (size_t)w.stride * batch * sizeof(double))); HIPCHK(hipStreamSynchronize(0)); return MPCQP_OK; }());
-  UP(dalloc(h, &h->ox, (size_t)batch * n)); UP(dalloc(h, &h->oy, (size_t)batch * std::max(m, 1))); UP(dalloc(h, &h->oz, (size_t)batch * std::max(m, 1)));
-  UP(dalloc(h, &h->oinfo, (size_t)batch * 4)); UP(dalloc(h, &h->ocs, (size_t)batch));
-  UP(dalloc(h, &h->ostatus, (size_t)batch)); UP(dalloc(h, &h->oiters, (size_t)batch));
-#ifdef MPCQP_TIMING
-  UP(dalloc(h, &h->odbg, (size_t)batch * 16 + 128));
-#endif
-#undef UP
-  h->wide = h->variant == 4 && h->lds > 80 * 1024;
-  h->stream_pd8 = h->lds > 40 * 1024 && !getenv("MPCQP_PD4");   // streaming kernel: 8 blocks in flight when one QP per SIMD is all that fits
-  if (h->lds > 48 * 1024) {
-    // MaxDynamicSharedMemorySize is a property of the kernel function, shared by every handle that launches it: keep a running
-    // maximum per function so that a later handle with a smaller footprint never lowers the limit under an earlier one
-    static std::mutex mu; static std::map<std::pair<const void *, int>, long> limit;   // (function, device)
-    const void *fns[4] = {res_kernel_of(h, false), res_kernel_of(h, true), nullptr, nullptr};
-    if (h->variant == 0) fns[0] = fns[1] = h->stream_pd8 ? (const void *)mpcqp_admm_kernel<8> : (const void *)mpcqp_admm_kernel<4>;
-    if (h->split) { fns[0] = oc_setup_of(h, false); fns[1] = oc_setup_of(h, true); fns[2] = oc_admm_of(h, false); fns[3] = oc_admm_of(h, true); }
-    std::lock_guard<std::mutex> lock(mu);
-    for (int k = 0; k < 4; k++) {
-      const void *fn = fns[k];
-      if (!fn) continue;
-      const long want_lds = (h->split && k < 2) ? h->lds_setup : h->lds;
-      long &cur = limit[{fn, h->device}];
-      if (want_lds <= cur) continue;
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want_lds) != hipSuccess)
-        return bail(fail(MPCQP_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed"));
-      cur = want_lds;
-    }
-  }
-  if (h->variant > 0 && !(h->split ? oc_setup_of(h, false) && oc_setup_of(h, true) && oc_admm_of(h, false) && oc_admm_of(h, true) : res_kernel_of(h, false) && res_kernel_of(h, true)))
-    return bail(fail(MPCQP_ERR_STATE, "no kernel instance for this handle (kernel_table.hpp)"));
-  if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess || hipEventCreate(&h->ev_mid) != hipSuccess) return bail(fail(MPCQP_ERR_HIP, "hipEventCreate failed"));
-  memset(&h->io, 0, sizeof(h->io));
-  h->lpt = !getenv("MPCQP_NO_LPT");
-  {   // dispatch-hint buffers up front: nothing is allocated inside mpcqp_solve, so a solve can be captured in a HIP graph
-    int rc;
-    if ((rc = dalloc(h, &h->order[0], (size_t)batch)) || (rc = dalloc(h, &h->order[1], (size_t)batch))) return bail(rc);
-    if (hipEventCreateWithFlags(&h->ev_order, hipEventDisableTiming) != hipSuccess) return bail(fail(MPCQP_ERR_HIP, "hipEventCreate failed"));
-  }
-  *out = h;
-  return MPCQP_OK;
+  const Knobs knobs = Knobs::from_env();
+  if (!knobs.variant_named && knobs.autotune) return mpcqp_create_tuned(n, m, batch, Pp, Pi, Ap, Ai, settings, out);
+  return create_handle(n, m, batch, Pp, Pi, Ap, Ai, settings, nullptr, knobs, out);
 }
 
 // ---- kernel family by measurement (include/mpcqp.h mpcqp_create_tuned)
@@ -699,11 +458,9 @@ int mpcqp_create_tuned(int n, int m, int batch, const int *Pp, const int *Pi, co
   if (!out) return fail(MPCQP_ERR_ARG, "out is null");
   *out = nullptr;
   if (n <= 0 || m < 0 || batch <= 0 || !Pp || !Pi || !Ap || !Ai) return fail(MPCQP_ERR_ARG, "Invalid dimensions.");
-  if (Pp[0] != 0 || Ap[0] != 0) return fail(MPCQP_ERR_ARG, "colptr must start at 0");
-  for (int j = 0; j < n; j++) if (Pp[j + 1] < Pp[j] || Ap[j + 1] < Ap[j]) return fail(MPCQP_ERR_ARG, "colptr not monotone");
-  for (int k = 0; k < Pp[n]; k++) if (Pi[k] < 0 || Pi[k] >= n) return fail(MPCQP_ERR_ARG, "P row index out of range");      // (before the pattern is hashed and a synthetic QP filled through it)
-  for (int k = 0; k < Ap[n]; k++) if (Ai[k] < 0 || Ai[k] >= m) return fail(MPCQP_ERR_ARG, "A row index out of range");
-  struct Force { const char *prev; explicit Force(const char *v) : prev(g_force_variant) { g_force_variant = v; } ~Force() { g_force_variant = prev; } };
+  if (int rc = check_csc(n, m, Pp, Pi, Ap, Ai, true)) return rc;      // (before the pattern is hashed and a synthetic QP filled through it)
+  const Knobs knobs = Knobs::from_env();
+  auto create = [&](const std::string &family, const mpcqp_settings *sts, mpcqp_handle **o) { return create_handle(n, m, batch, Pp, Pi, Ap, Ai, sts, family == "rule" ? "" : family.c_str(), knobs, o); };
   mpcqp_settings st; if (settings) st = *settings; else mpcqp_default_settings(&st);
   int dev = st.device; if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
   const std::string key = tune_key(n, m, batch, dev, Pp, Pi, Ap, Ai);
@@ -711,11 +468,9 @@ int mpcqp_create_tuned(int n, int m, int batch, const int *Pp, const int *Pi, co
     std::string cached;
     { std::lock_guard<std::mutex> lock(g_tune_mu); auto it = g_tune_cache.find(key); if (it != g_tune_cache.end()) cached = it->second; }
     if (!cached.empty()) {
-      int rc;
-      { Force f(cached == "rule" ? "" : cached.c_str()); rc = mpcqp_create(n, m, batch, Pp, Pi, Ap, Ai, settings, out); }
+      const int rc = create(cached, settings, out);
       if (rc != MPCQP_ERR_LIMIT || cached == "rule") return rc;
-      Force f("");       // the cached family no longer takes the size (other settings): the rule's choice instead of an error
-      return mpcqp_create(n, m, batch, Pp, Pi, Ap, Ai, settings, out);
+      return create("rule", settings, out);       // the cached family no longer takes the size (other settings): the rule's choice instead of an error
     }
   }
   // the synthetic QP on this pattern: P = unit diagonal (other entries 0: positive semidefinite whatever the pattern), A pseudo-random in
@@ -736,8 +491,7 @@ int mpcqp_create_tuned(int n, int m, int batch, const int *Pp, const int *Pi, co
   int last_rc = MPCQP_ERR_LIMIT;
   for (const char *fam : families) {
     mpcqp_handle *h = nullptr;
-    int rc;
-    { Force f(fam); rc = mpcqp_create(n, m, batch, Pp, Pi, Ap, Ai, &ts, &h); }
+    const int rc = create(fam, &ts, &h);
     if (rc != MPCQP_OK) { if (rc != MPCQP_ERR_LIMIT) last_rc = rc; continue; }
     long info[16]; mpcqp_plan_info(h, info);
     const long code = info[15] * 1000000 + info[7];                 // family + LDS footprint: the same kernel instance is timed once
@@ -769,8 +523,7 @@ int mpcqp_create_tuned(int n, int m, int batch, const int *Pp, const int *Pi, co
   if (!best) return last_rc == MPCQP_ERR_LIMIT ? fail(MPCQP_ERR_LIMIT, "no kernel family takes this pattern / size") : last_rc;
   mpcqp_destroy(best);       // (its settings were the tuning run's: the handle that is returned is created afresh with the caller's)
   { std::lock_guard<std::mutex> lock(g_tune_mu); g_tune_cache[key] = best_family; }
-  Force f(best_family == "rule" ? "" : best_family.c_str());
-  return mpcqp_create(n, m, batch, Pp, Pi, Ap, Ai, settings, out);
+  return create(best_family, settings, out);
 }
 
 int mpcqp_create_reduced(int n, int m, int batch, const int *Pp, const int *Pi, const int *Ap, const int *Ai,
@@ -778,19 +531,15 @@ int mpcqp_create_reduced(int n, int m, int batch, const int *Pp, const int *Pi, 
   if (!out) return fail(MPCQP_ERR_ARG, "out is null");
   *out = nullptr;
   if (n <= 0 || m <= 0 || batch <= 0 || !Pp || !Pi || !Ap || !Ai || nfixed < 0 || (nfixed > 0 && !fixed_rows)) return fail(MPCQP_ERR_ARG, "Invalid dimensions.");
-  for (int j = 0; j < n; j++) {
-    if (Pp[j + 1] < Pp[j] || Ap[j + 1] < Ap[j]) return fail(MPCQP_ERR_ARG, "colptr not monotone");
-    for (int k = Pp[j]; k < Pp[j + 1]; k++) if (Pi[k] < 0 || Pi[k] >= n) return fail(MPCQP_ERR_ARG, "P row index out of range");
-    for (int k = Ap[j]; k < Ap[j + 1]; k++) if (Ai[k] < 0 || Ai[k] >= m) return fail(MPCQP_ERR_ARG, "A row index out of range");
-  }
+  if (int rc = check_csc(n, m, Pp, Pi, Ap, Ai, false)) return rc;
   RedMaps rm = build_red_maps(n, m, Pp, Pi, Ap, Ai, nfixed, fixed_rows);
   if (!rm.error.empty()) return fail(MPCQP_ERR_ARG, rm.error);
   mpcqp_handle *inner = nullptr;
   int rc = mpcqp_create(rm.nr, rm.mr, batch, rm.Ppr.data(), rm.Pir.data(), rm.Apr.data(), rm.Air.data(), settings, &inner);
   if (rc) return rc;
   mpcqp_handle *h = new mpcqp_handle();
-  h->inner = inner; h->st = inner->st; h->device = inner->device; h->n = n; h->m = m; h->batch = batch; h->variant = -1;
-  h->plan.n = n; h->plan.m = m; h->plan.nnzP_in = Pp[n]; h->plan.nnzA_in = Ap[n];
+  h->inner = inner; h->st = inner->st; h->device = inner->device; h->n = n; h->m = m; h->batch = batch; h->sel.waves = -1;
+  h->sel.plan.n = n; h->sel.plan.m = m; h->sel.plan.nnzP_in = Pp[n]; h->sel.plan.nnzA_in = Ap[n];
   h->red = rm;
   auto bail = [&](int code) { mpcqp_destroy(h); return code; };
   DevRed &d = h->dred;
@@ -827,11 +576,7 @@ int mpcqp_create_presolved(int n, int m, int batch, const int *Pp, const int *Pi
   if (n <= 0 || m <= 0 || batch <= 0 || !Pp || !Pi || !Ap || !Ai || !l || !u) return fail(MPCQP_ERR_ARG, "Invalid dimensions.");
   if (sl < 0 || su < 0 || (sl && sl < m) || (su && su < m)) return fail(MPCQP_ERR_ARG, "stride smaller than the array it strides (dimension mismatch)");
   if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
-  if (Ap[0] != 0) return fail(MPCQP_ERR_ARG, "colptr must start at 0");
-  for (int j = 0; j < n; j++) {
-    if (Ap[j + 1] < Ap[j]) return fail(MPCQP_ERR_ARG, "colptr not monotone");
-    for (int k = Ap[j]; k < Ap[j + 1]; k++) if (Ai[k] < 0 || Ai[k] >= m) return fail(MPCQP_ERR_ARG, "A row index out of range");
-  }
+  if (int rc = check_csc(n, m, nullptr, nullptr, Ap, Ai, true)) return rc;
   // the bounds of the first update on the host (device arrays: one copy, at creation only)
   const size_t nl = sl ? (size_t)sl * (batch - 1) + m : (size_t)m, nu = su ? (size_t)su * (batch - 1) + m : (size_t)m;
   std::vector<double> hl, hu;
@@ -905,9 +650,9 @@ static int stage(mpcqp_handle *h, double **own, const double *src, long stride, 
 int mpcqp_update(mpcqp_handle *h, const double *P, long sP, const double *q, long sq, const double *A, long sA,
                  const double *l, long sl, const double *u, long su, int mem) {
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-  if (!q || (h->plan.nnzP_in > 0 && !P) || (h->plan.nnzA_in > 0 && !A) || (h->m > 0 && (!l || !u))) return fail(MPCQP_ERR_ARG, "null data pointer");
+  if (!q || (h->sel.plan.nnzP_in > 0 && !P) || (h->sel.plan.nnzA_in > 0 && !A) || (h->m > 0 && (!l || !u))) return fail(MPCQP_ERR_ARG, "null data pointer");
   if (sP < 0 || sq < 0 || sA < 0 || sl < 0 || su < 0) return fail(MPCQP_ERR_ARG, "negative stride");
-  if ((sP && sP < h->plan.nnzP_in) || (sq && sq < h->n) || (sA && sA < h->plan.nnzA_in) || (sl && sl < h->m) || (su && su < h->m))
+  if ((sP && sP < h->sel.plan.nnzP_in) || (sq && sq < h->n) || (sA && sA < h->sel.plan.nnzA_in) || (sl && sl < h->m) || (su && su < h->m))
     return fail(MPCQP_ERR_ARG, "stride smaller than the array it strides (dimension mismatch)");
   HIPCHK(hipSetDevice(h->device));
   DevIO &io = h->io;
@@ -916,9 +661,9 @@ int mpcqp_update(mpcqp_handle *h, const double *P, long sP, const double *q, lon
   } else if (mem == MPCQP_MEM_HOST) {
     if (h->last_stream || h->solved) HIPCHK(hipStreamSynchronize(h->last_stream));
     int rc;
-    if ((rc = stage(h, &h->dP, P ? P : q, sP, h->plan.nnzP_in, &io.P, &io.sP))) return rc;
+    if ((rc = stage(h, &h->dP, P ? P : q, sP, h->sel.plan.nnzP_in, &io.P, &io.sP))) return rc;
     if ((rc = stage(h, &h->dq, q, sq, h->n, &io.q, &io.sq))) return rc;
-    if ((rc = stage(h, &h->dA, A ? A : q, sA, h->plan.nnzA_in, &io.A, &io.sA))) return rc;
+    if ((rc = stage(h, &h->dA, A ? A : q, sA, h->sel.plan.nnzA_in, &io.A, &io.sA))) return rc;
     if ((rc = stage(h, &h->dl, l ? l : q, sl, h->m, &io.l, &io.sl))) return rc;
     if ((rc = stage(h, &h->du, u ? u : q, su, h->m, &io.u, &io.su))) return rc;
   } else return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
@@ -955,7 +700,7 @@ int mpcqp_keep_workspace(mpcqp_handle *h, int enable) {
     if (!h->keep) { h->have_factor = false; h->reuse_next = false; }
     return MPCQP_OK;
   }
-  if (enable && h->variant == 0) return fail(MPCQP_ERR_LIMIT, "the streaming kernel variant does not keep its workspace");
+  if (enable && h->sel.waves == 0) return fail(MPCQP_ERR_LIMIT, "the streaming kernel variant does not keep its workspace");
   h->keep = enable != 0;
   if (!h->keep) { h->have_factor = false; h->reuse_next = false; }
   return MPCQP_OK;
@@ -1002,29 +747,12 @@ int mpcqp_solve(mpcqp_handle *h, void *stream) {
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   if (h->inner) return solve_reduced(h, s);
-  DevIO io = h->io;
-  io.x = h->ox; io.y = h->oy; io.z = h->oz; io.status = h->ostatus; io.iters = h->oiters; io.info = h->oinfo; io.ws = h->ws; io.no_remap = getenv("MPCQP_NO_REMAP") ? 1 : 0; io.no_touch = no_touch_of(h); io.cscale = h->ocs; io.dbg = h->odbg;
-  io.reuse = h->reuse_next ? 1 : 0; io.keep = h->keep ? 1 : 0;
+  DevIO io = io_of_handle(h);
+  io.reuse = h->reuse_next ? 1 : 0;
   io.order = (h->lpt && h->order_cur >= 0) ? h->order[h->order_cur] : nullptr;
   if (io.order && h->last_stream != s) HIPCHK(hipStreamWaitEvent(s, h->ev_order, 0));    // the hint was written on another stream
   HIPCHK(hipEventRecord(h->ev0, s));
-  if (h->variant > 0 && h->split) {     // CuCaQP::initSolver, then CuCaQP::solve
-    int rc = launch_oc_split(h, io, h->batch, io.reuse != 0, s, h->ev_mid, 0);
-    if (rc) return rc;
-  }
-  else if (h->variant > 0) {
-    void *args[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&h->doc};
-    HIPCHK(hipLaunchKernel(res_kernel_of(h, io.reuse != 0), dim3(h->batch), dim3(h->variant * WAVE), args, (size_t)h->lds, s));
-  }
-  else if (h->stream_pd8) hipLaunchKernelGGL(mpcqp_admm_kernel<8>, dim3(h->batch), dim3(WAVE), (size_t)h->lds, s, h->dp, h->st, io);
-  else hipLaunchKernelGGL(mpcqp_admm_kernel<4>, dim3(h->batch), dim3(WAVE), (size_t)h->lds, s, h->dp, h->st, io);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev1, s));
-  if (h->m > 0) {
-    hipLaunchKernelGGL(mpcqp_validate_kernel, dim3((h->batch + 3) / 4), dim3(256), 0, s, h->batch, h->n, h->m, io.l, io.sl, io.u, io.su, io.x, io.y, io.z,
-                       io.status, io.iters, io.info);
-    HIPCHK(hipGetLastError());
-  }
+  if (int rc = launch_batch(h, io, h->batch, io.reuse != 0, s, h->ev_mid, h->ev1, 0)) return rc;
   if (h->lpt && h->batch > 1) {   // order of the next solve from this solve's iteration counts
     const int nxt = h->order_cur == 0 ? 1 : 0;
     hipLaunchKernelGGL(mpcqp_order_kernel, dim3(1), dim3(1024), 0, s, (const int *)h->oiters, h->order[nxt], h->batch, std::max(1, h->st.check_termination));
@@ -1046,32 +774,15 @@ static int launch_slice(mpcqp_handle *h, DevIO io, int b0, int count, hipStream_
   io.x += b0 * n; io.y += b0 * m; io.z += b0 * m; io.status += b0; io.iters += b0; io.info += 4L * b0;
   io.ws += (long)b0 * h->dp.ws_stride; io.cscale += b0;
   if (io.dbg) io.dbg += 16L * b0;
-  io.order = nullptr;
-  if (h->variant > 0 && h->split) {
-    int rc = launch_oc_split(h, io, count, false, s, nullptr, qslot);
-    if (rc) return rc;
-  }
-  else if (h->variant > 0) {
-    void *args[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&h->doc};
-    HIPCHK(hipLaunchKernel(res_kernel_of(h, false), dim3(count), dim3(h->variant * WAVE), args, (size_t)h->lds, s));
-  }
-  else if (h->stream_pd8) hipLaunchKernelGGL(mpcqp_admm_kernel<8>, dim3(count), dim3(WAVE), (size_t)h->lds, s, h->dp, h->st, io);
-  else hipLaunchKernelGGL(mpcqp_admm_kernel<4>, dim3(count), dim3(WAVE), (size_t)h->lds, s, h->dp, h->st, io);
-  HIPCHK(hipGetLastError());
-  if (m > 0) {
-    hipLaunchKernelGGL(mpcqp_validate_kernel, dim3((count + 3) / 4), dim3(256), 0, s, count, h->n, h->m, io.l, io.sl, io.u, io.su, io.x, io.y, io.z,
-                       io.status, io.iters, io.info);
-    HIPCHK(hipGetLastError());
-  }
-  return MPCQP_OK;
+  return launch_batch(h, io, count, false, s, nullptr, nullptr, qslot);
 }
 
 int mpcqp_solve_host(mpcqp_handle *h, const double *P, long sP, const double *q, long sq, const double *A, long sA,
                      const double *l, long sl, const double *u, long su,
                      double *x, double *y, int *status, int *iters, int chunks) {
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
-  if (!q || (h->plan.nnzP_in > 0 && !P) || (h->plan.nnzA_in > 0 && !A) || (h->m > 0 && (!l || !u))) return fail(MPCQP_ERR_ARG, "null data pointer");
-  const long wP = h->plan.nnzP_in, wA = h->plan.nnzA_in, n = h->n, m = h->m;
+  if (!q || (h->sel.plan.nnzP_in > 0 && !P) || (h->sel.plan.nnzA_in > 0 && !A) || (h->m > 0 && (!l || !u))) return fail(MPCQP_ERR_ARG, "null data pointer");
+  const long wP = h->sel.plan.nnzP_in, wA = h->sel.plan.nnzA_in, n = h->n, m = h->m;
   if (h->inner) return fail(MPCQP_ERR_STATE, "mpcqp_solve_host is not available on a reduced handle");
   if ((sP && sP != wP) || sq != n || (sA && sA != wA) || (m > 0 && (sl != m || su != m)))
     return fail(MPCQP_ERR_ARG, "dimension mismatch: mpcqp_solve_host takes dense instance-major arrays (stride = width; 0 shares P or A)");
@@ -1089,12 +800,10 @@ int mpcqp_solve_host(mpcqp_handle *h, const double *P, long sP, const double *q,
   // runtime maps streams onto a few hardware queues (four by default), and with eight compute streams beside the copy stream the copies of a later slice
   // queued up behind kernels of earlier ones (rocprofv3 memory-copy trace: gaps of 0.9 - 1.7 ms in the transfer; 12.3 -> 10.3 ms per step on the north-star
   // batch, against a bound of ~10 ms = transfer of one slice + the launch).  MPCQP_PIPE_STREAMS overrides (1 .. 8).
-  const int ns = std::min(chunks, getenv("MPCQP_PIPE_STREAMS") ? std::max(1, std::min(atoi(getenv("MPCQP_PIPE_STREAMS")), (int)mpcqp_handle::NPIPE)) : 2);
+  const int ns = std::min(chunks, std::min(h->knobs.pipe_streams, (int)mpcqp_handle::NPIPE));
   for (int i = 0; i < ns; i++) if (!h->pipe[i]) HIPCHK(hipStreamCreateWithFlags(&h->pipe[i], hipStreamNonBlocking));
-  DevIO io = h->io;
+  DevIO io = io_of_handle(h);
   io.P = h->dP; io.sP = sP; io.q = h->dq; io.sq = n; io.A = h->dA; io.sA = sA; io.l = h->dl; io.sl = m; io.u = h->du; io.su = m;
-  io.x = h->ox; io.y = h->oy; io.z = h->oz; io.status = h->ostatus; io.iters = h->oiters; io.info = h->oinfo; io.ws = h->ws; io.no_remap = getenv("MPCQP_NO_REMAP") ? 1 : 0; io.no_touch = no_touch_of(h); io.cscale = h->ocs; io.dbg = h->odbg;
-  io.reuse = 0; io.keep = h->keep ? 1 : 0; io.order = nullptr;
   if (sP == 0 && wP) HIPCHK(hipMemcpy(h->dP, P, wP * sizeof(double), hipMemcpyHostToDevice));      // shared matrices: once
   if (sA == 0 && wA) HIPCHK(hipMemcpy(h->dA, A, wA * sizeof(double), hipMemcpyHostToDevice));
   if (!h->pipe_copy) HIPCHK(hipStreamCreateWithFlags(&h->pipe_copy, hipStreamNonBlocking));
@@ -1185,7 +894,7 @@ int mpcqp_last_phase_ms(mpcqp_handle *h, float *setup_ms, float *solve_ms) {
   if (h->inner) return mpcqp_last_phase_ms(h->inner, setup_ms, solve_ms);
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipEventSynchronize(h->ev1));
-  if (!h->split) { *setup_ms = 0.f; HIPCHK(hipEventElapsedTime(solve_ms, h->ev0, h->ev1)); return MPCQP_OK; }
+  if (!h->sel.split) { *setup_ms = 0.f; HIPCHK(hipEventElapsedTime(solve_ms, h->ev0, h->ev1)); return MPCQP_OK; }
   HIPCHK(hipEventElapsedTime(setup_ms, h->ev0, h->ev_mid));
   HIPCHK(hipEventElapsedTime(solve_ms, h->ev_mid, h->ev1));
   return MPCQP_OK;
@@ -1194,21 +903,14 @@ int mpcqp_last_phase_ms(mpcqp_handle *h, float *setup_ms, float *solve_ms) {
 int mpcqp_plan_info(const mpcqp_handle *h, long *o) {
   if (!h || !o) return fail(MPCQP_ERR_ARG, "null pointer");
   if (h->inner) return mpcqp_plan_info(h->inner, o);        // the plan that runs: the reduced pattern's
-  const Plan &pl = h->plan;
-  o[0] = h->n; o[1] = h->m; o[2] = h->batch; o[3] = pl.npad; o[4] = pl.mpad; o[5] = pl.nb; o[6] = pl.nblk; o[7] = h->lds;
-  o[8] = h->wl.stride * 8; o[9] = pl.ordering; o[10] = pl.nnzP_triu; o[11] = pl.nnzA_in; o[12] = pl.nT; o[13] = h->oc ? ((h->tiles || h->vtiles) ? h->tplan.ntile : 0) : (long)pl.fac.size();
-  o[14] = pl.A.slots() + pl.At.slots() + pl.P.slots(); o[15] = h->oc ? 200 + h->variant : h->gblocks ? 100 + h->variant : h->variant;
+  plan_info_of(h->sel, h->n, h->m, h->batch, o);
   return MPCQP_OK;
 }
 
 int mpcqp_oc_info(const mpcqp_handle *h, long *o) {
   if (!h || !o) return fail(MPCQP_ERR_ARG, "null pointer");
   if (h->inner) return mpcqp_oc_info(h->inner, o);
-  for (int k = 0; k < 12; k++) o[k] = 0;
-  o[8] = h->plan.A.slots(); o[9] = h->plan.At.slots(); o[10] = h->plan.P.slots();
-  if (!h->oc) return MPCQP_OK;
-  const OcPlan &p = h->ocplan;
-  o[0] = p.nbc; o[1] = p.has_hub; o[2] = (long)p.chainE.size(); o[3] = (long)p.chainF.size(); o[4] = p.nlds; o[5] = p.npw; o[6] = p.nhr; o[7] = h->split ? 1 + h->resume_rounds : 0; o[11] = (long)std::max<size_t>(1, p.pairs.size());
+  oc_info_of(h->sel, o);
   return MPCQP_OK;
 }
 
@@ -1218,11 +920,11 @@ int mpcqp_debug_scaling(mpcqp_handle *h, int b, double *D, double *E, double *c)
   if (!h->solved) return fail(MPCQP_ERR_STATE, "no solve has been issued");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->last_stream));
-  const Plan &pl = h->plan;
+  const Plan &pl = h->sel.plan;
   std::vector<double> Dp(pl.npad);
-  const double *base = h->ws + (size_t)b * h->wl.stride;
-  if (D) { HIPCHK(hipMemcpy(Dp.data(), base + h->wl.D, pl.npad * sizeof(double), hipMemcpyDeviceToHost)); for (int j = 0; j < h->n; j++) D[j] = Dp[pl.pos[j]]; }
-  if (E && h->m) HIPCHK(hipMemcpy(E, base + h->wl.E, h->m * sizeof(double), hipMemcpyDeviceToHost));
+  const double *base = h->ws + (size_t)b * h->sel.wl.stride;
+  if (D) { HIPCHK(hipMemcpy(Dp.data(), base + h->sel.wl.D, pl.npad * sizeof(double), hipMemcpyDeviceToHost)); for (int j = 0; j < h->n; j++) D[j] = Dp[pl.pos[j]]; }
+  if (E && h->m) HIPCHK(hipMemcpy(E, base + h->sel.wl.E, h->m * sizeof(double), hipMemcpyDeviceToHost));
   if (c) HIPCHK(hipMemcpy(c, h->ocs + b, sizeof(double), hipMemcpyDeviceToHost));
   return MPCQP_OK;
 }

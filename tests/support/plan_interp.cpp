@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../optimal_control_problem_amd/csrc/plan.hpp"
+#include "../../optimal_control_problem_amd/csrc/select.hpp"
 
 using namespace mpcqp;
 
@@ -861,3 +862,25 @@ extern "C" int plan_oc_extras(int n, int m, const int *Pp, const int *Pi, const 
   out[3] = okr; out[4] = (int)(ws_layout(pl).T + ((long)std::max(pl.nT, 1) + 1) * BLK <= ws_layout(pl).l);
   return 0;
 }
+
+// The kernel selection of the library (csrc/select.hpp select_kernel) with the knobs of the environment, as mpcqp_create runs it on a device with `cus`
+// compute units.  forced_family: null = MPCQP_VARIANT or the rule.  Returns 0 and out[0..15] = mpcqp_plan_info, out[16..27] = mpcqp_oc_info,
+// out[28..39] = the set-up launch {waves, LDS bytes, stage doubles, a_lds, p_lds, ix16, zpad, ixo_a, ixo_p, two-kernel form, 0, 0}, out[40..47] =
+// {zyg, occ3, occ4, res1x, res3, wide, oc8 instance, waves whose chunks of A are assigned}; or the error code (1 = MPCQP_ERR_ARG, 5 = MPCQP_ERR_LIMIT).
+static std::string g_select_shape;
+extern "C" int plan_select(int n, int m, int batch, const int *Pp, const int *Pi, const int *Ap, const int *Ai, int cus, const char *forced_family, long *out) {
+  const Selection s = select_kernel(n, m, batch, Pp, Pi, Ap, Ai, cus, forced_family, Knobs::from_env());
+  g_select_shape.clear();
+  if (s.err) return s.err;
+  plan_info_of(s, n, m, batch, out); oc_info_of(s, out + 16);
+  const SetupShape &u = s.setup;
+  const long shape[12] = {u.nw, u.lds, u.stage, u.a_lds, u.p_lds, u.ix16, u.zpad, u.ixo_a, u.ixo_p, s.split, 0, 0};
+  std::copy(shape, shape + 12, out + 28);
+  int waves_a = 0; for (int w = 0; w < 8 && !s.a_assign.empty(); w++) waves_a += s.a_assign[32 * w] >= 0;
+  const long inst[8] = {s.zyg, s.occ3, s.occ4, s.res1x, s.res3, s.wide, s.oc8, waves_a};
+  std::copy(inst, inst + 8, out + 40);
+  if (s.split) g_select_shape = setup_shape_text(s);
+  return 0;
+}
+// the MPCQP_VERBOSE line of the last plan_select, without the resident workgroups (only the device knows them); "" where there is no set-up kernel
+extern "C" const char *plan_select_shape() { return g_select_shape.c_str(); }

@@ -241,3 +241,29 @@ def random_stage_ocp(seed, family="oc4"):
     lbx, ubx, lbg, ubg = mdl.stacked_bounds(x[:, :mdl.f].copy())
     ls = mdl.local_system(p, x, lbx, ubx, lbg, ubg)
     return ls, "nx=%d nu=%d N=%d B=%d n=%d m=%d" % (nx, nu, N, B, ls.n, ls.m), rng
+
+
+def selection_grid():
+    """tests/golden/selection_grid.json: what the library reported per row before select_kernel existed (tools/selection_grid.py)"""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "selection_grid.json")) as f:
+        return json.load(f)
+
+
+def selection_row_id(r):
+    return "%s-N%d-x%d%s%s" % (r["workload"], r["N"], r["batch"], "-reduced" if r["reduced"] else "", "".join("-%s=%s" % kv for kv in sorted(r["env"].items())))
+
+
+def selection_pattern(row, inner=False, _cache={}):
+    """(n, m, Pp, Pi, Ap, Ai, fixed_rows or None) of a row of tests/golden/selection_grid.json (tools/selection_grid.py): a workload's
+    pattern; for a reduced row the parameter rows the reduced form eliminates, or (inner) the reduced pattern its inner handle is created on"""
+    from optimal_control_problem_amd import models
+    key = (row["workload"], row["N"])
+    if key not in _cache:
+        mdl, ls, _ = models.make_workload(row["workload"], 2, N=row["N"])
+        _cache[key] = (ls, list(range(mdl.np)))
+    ls, fixed = _cache[key]
+    if row["reduced"] and inner:
+        ls, fixed = reduce_qp(ls, fixed)[0], None
+    return ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai, (fixed if row["reduced"] else None)

@@ -391,13 +391,34 @@ def test_onchip_is_the_default_for_the_north_star_size(built):
     mdl, ls, _ = models.make_workload("quadrotor", 2, N=20)
     qp = BatchQP(ls.n, ls.m, 8192, ls.Pp, ls.Pi, ls.Ap, ls.Ai); info = qp.plan_info(); qp.close()
     assert info["variant"] == 204 and info["lds_bytes"] <= 80 * 1024
-    # ... and wherever the alternative is a factor streamed from the slab or the LDS-resident kernel at two workgroups per CU (mpcqp.hip
-    # selection rule); with three or more resident workgroups per CU the LDS-resident kernels stay
+    # ... and wherever the alternative is a factor streamed from the slab or the LDS-resident kernel at two workgroups per CU (select.hpp
+    # family_rule); with three or more resident workgroups per CU the LDS-resident kernels stay
     for name, N, want in (("quadrotor", 10, 204), ("cartpole", 40, 204), ("double_integrator", 60, 204), ("quadrotor", 7, 204),
                           ("quadrotor", 5, 4), ("cartpole", 20, 4), ("double_integrator", 20, 2)):
         mdl, ls, _ = models.make_workload(name, 2, N=N)
         qp = BatchQP(ls.n, ls.m, 8192, ls.Pp, ls.Pi, ls.Ap, ls.Ai); info = qp.plan_info(); qp.close()
         assert info["variant"] == want, (name, N, info["variant"])
+
+
+@pytest.mark.parametrize("r", problems.selection_grid()["rows"], ids=problems.selection_row_id)
+def test_library_selects_what_the_grid_records(built, monkeypatch, r):
+    """the library's handle reports, row by row, the plan_info / oc_info of tests/golden/selection_grid.json -- recorded from the library before
+    select_kernel existed; tests/test_select.py holds the CPU function against the same file, so the two agree with each other as well"""
+    import torch
+    from optimal_control_problem_amd import _lib
+    from optimal_control_problem_amd.batch_qp import BatchQP
+    assert torch.cuda.get_device_properties(0).multi_processor_count == problems.selection_grid()["multiProcessorCount"]
+    n, m, Pp, Pi, Ap, Ai, fixed = problems.selection_pattern(r)
+    for k, v in r["env"].items():
+        monkeypatch.setenv(k, v)
+    try:
+        qp = BatchQP(n, m, r["batch"], Pp, Pi, Ap, Ai, fixed_rows=fixed)
+    except _lib.MpcqpError as e:
+        assert e.code == r["rc"] != 0
+        return
+    plan, oc = qp.plan_info(), qp.oc_info(); qp.close()
+    plan.pop("tiles")
+    assert r["rc"] == 0 and plan == r["plan_info"] and oc == r["oc_info"]
 
 
 @pytest.mark.parametrize("knob", ["MPCQP_LATE", "MPCQP_NO_REMAP", "MPCQP_NO_TOUCH", "MPCQP_OC_PAD4"])

@@ -208,7 +208,7 @@ def _run_oc8(ls, NG, NH, zyg, b=0, seed=0, ldl=1):
     return rc, dict(nbc=info[0], has_hub=info[1], junc=info[2], nlds=info[3], nhr=info[4], lds=info[5], LE=info[6], LF=info[7])
 
 
-@pytest.mark.parametrize("name,N,inst,expect", [("quadrotor", 50, (7, 7, 0), dict(nbc=50, has_hub=1, junc=1, nlds=50, LE=24, LF=26)),       # BASELINE config 3 as mpcqp_create takes it: 49 chain blocks + the hub's inverse in LDS, every hub block in registers
+@pytest.mark.parametrize("name,N,inst,expect", [("quadrotor", 50, (7, 7, 0), dict(nbc=50, has_hub=1, junc=1, nlds=50, LE=24, LF=26)),       # BASELINE config 3 as mpcqp_create takes it (test_select.py test_stated_values): 49 chain blocks + the hub's inverse in LDS, every hub block in registers
                                                 ("quadrotor", 50, (7, 5, 1), dict(nbc=50, has_hub=1, junc=1, nlds=60)),                      # (the alternative split: ten hub blocks in LDS, z / y in the slab)
                                                 ("cartpole", 100, (4, 4, 0), dict(nbc=32, has_hub=1, junc=1, nlds=32, LE=15, LF=17)),        # config 4: padded twist, two chains instead of one of 31
                                                 ("quadrotor", 30, (4, 4, 0), dict(nbc=30, junc=1)), ("quadrotor", 40, (7, 7, 0), dict(nbc=40)),
@@ -326,7 +326,7 @@ def test_onchip_long_chain_plan_limits(built):
     assert _run_oc8(ls, 7, 7, 0)[0] == 5
     mdl, ls, _ = models.make_workload("quadrotor", 1, N=40)          # 40 positions do not fit the <4, 4> instance
     assert _run_oc8(ls, 4, 4, 0)[0] == 5 and _run_oc8(ls, 7, 7, 0)[0] == 0
-    mdl, ls, _ = models.make_workload("quadrotor", 1, N=56)          # the tables exist, but the LDS of one CU does not hold it: mpcqp_create keeps the global-block kernel
+    mdl, ls, _ = models.make_workload("quadrotor", 1, N=56)          # the tables exist, but the LDS of one CU does not hold it: mpcqp_create keeps the global-block kernel (test_select.py, the quadrotor N=56 rows)
     rc, info = _run_oc8(ls, 7, 7, 0)
     assert rc == 0 and info["lds"] > 160 * 1024
 

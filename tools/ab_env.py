@@ -28,7 +28,7 @@ for cs in cases:
         for _ in range(5):
             qp.update(*d); qp.solve(); torch.cuda.synchronize(); ms.append(qp.last_kernel_ms())
         got = qp.get(); v = qp.plan_info()["variant"]; qp.close()
-        os.environ.pop(var, None)      # (only now: some switches are read at every solve)
+        os.environ.pop(var, None)      # (a handle reads every switch once, when it is created)
         res[tag] = got
         print("%-18s N=%3d x %5d %-16s variant %3d: kernel %.3f ms (min of %s)" % (name, N, B, tag, v, min(ms[1:]), " ".join("%.3f" % m for m in ms)), flush=True)
     a, b = res["default"], res[var + "=1"]
