@@ -183,6 +183,29 @@ int mpcqp_set_dispatch_hint(mpcqp_handle *h, int enable);
  * have completed. */
 int mpcqp_get(mpcqp_handle *h, double *x, double *y, double *z, int *status, int *iters, double *info, int mem);
 
+/* Solution polishing -- OSQP's `polishing` setting (OsqpEigen::Settings::setPolish) with its `delta` and `polish_refine_iter`; the per-QP outcome is
+ * OSQP's info->status_polish.  The reference never switches it on (its settings are the five of src/sqp_solver/CuCaQP.cpp:163-181), so the default is
+ * off and a handle that never calls mpcqp_set_polish, or calls it with enable = 0, launches exactly what it launched before.  When on, a polish kernel is
+ * queued behind every solve on the solve's stream (mpcqp_solve_host: on each slice's compute stream, ahead of its device-to-host copies): for every instance
+ * that ended MPCQP_SOLVED it guesses the active rows from the iterate (lower: z - l < -y, upper: u - z < y), solves the
+ * regularised KKT system [P + delta I, A_a'; A_a, -delta I] on them (delta in the caller's units: the result does not depend on the equilibration), refines the result refine_iter times against the unregularised matrix, and keeps
+ * it -- x, y, z and info[0..2] are overwritten -- iff OSQP's rule holds (both residuals smaller than ADMM's, or one smaller while the other was below
+ * 1e-10).  status, iters and info[3] never change; an instance that is not polished, or whose candidate is rejected, keeps the ADMM result bit for bit.
+ * The factor of the polish system lives in scratch allocated here (nothing is allocated inside a solve), so a kept workspace's factor survives.
+ * delta <= 0 -> 1e-6, refine_iter < 0 -> 3 (OSQP's defaults).  Reduced handles forward the setting to the handle that runs. */
+#define MPCQP_POLISH_LINSYS_ERROR  -2   /* the polish system had a non-positive pivot: ADMM solution kept */
+#define MPCQP_POLISH_FAILED        -1   /* candidate rejected: ADMM solution kept */
+#define MPCQP_POLISH_NOT_PERFORMED  0   /* polishing off, or status != MPCQP_SOLVED */
+#define MPCQP_POLISH_SUCCESS        1
+int mpcqp_set_polish(mpcqp_handle *h, int enable, double delta, int refine_iter);
+/* OSQP's info->status_polish per QP (polish_status [batch]) and polish_info[4*b ..] = {objective, primal residual, dual residual of the candidate --
+ * accepted or not; NaN when none was built --, number of active rows}.  Either pointer may be NULL.  Of the last solve, ordered on its stream like
+ * mpcqp_get; a reduced handle reports its inner handle's.  MPCQP_ERR_STATE when polishing is off. */
+int mpcqp_get_polish(mpcqp_handle *h, int *polish_status, double *polish_info, int mem);
+/* Duration of the polish kernel of the last mpcqp_solve from HIP events around its launch (OSQP's info->polish_time); mpcqp_last_kernel_ms and
+ * mpcqp_last_phase_ms keep their meaning -- the polish is timed apart.  MPCQP_ERR_STATE when none ran. */
+int mpcqp_last_polish_ms(mpcqp_handle *h, float *ms);
+
 int mpcqp_sync(mpcqp_handle *h);                 /* wait for the last solve / copies */
 void mpcqp_destroy(mpcqp_handle *h);             /* replaces CuCaQP::~CuCaQP (CuCaQP.cpp:16-21) */
 const char *mpcqp_strerror(int code);            /* replaces the std::cerr messages of CuCaQP.cpp */

@@ -56,6 +56,7 @@ class BatchQP:
         self._keep = []
         L = _lib.lib()
         self.nfixed = 0
+        self.polish = False
         if presolve_bounds is not None:
             lp, ls_, lmem, lk = _ptr_stride(presolve_bounds[0], self.m, self.batch, "l"); up, us_, umem, uk = _ptr_stride(presolve_bounds[1], self.m, self.batch, "u")
             if lmem != umem:
@@ -151,6 +152,17 @@ class BatchQP:
             self._keep_rho = a
             _lib.check(_lib.lib().mpcqp_set_rho(self._h, a.ctypes.data, _lib.MEM_HOST))
 
+    def set_polish(self, enable=True, delta=1e-6, refine_iter=3):
+        """OSQP's `polishing` (with `delta`, `polish_refine_iter`): a polish kernel behind every solve refines the instances that ended `solved`
+        on their guessed active set; off by default, as in the reference.  get() then also returns polish_status / polish_info."""
+        _lib.check(_lib.lib().mpcqp_set_polish(self._h, 1 if enable else 0, float(delta), int(refine_iter)))
+        self.polish = bool(enable)
+
+    def last_polish_ms(self):
+        ms = C.c_float()
+        _lib.check(_lib.lib().mpcqp_last_polish_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def solve(self, stream=None):
         _lib.check(_lib.lib().mpcqp_solve(self._h, stream))
 
@@ -193,12 +205,17 @@ class BatchQP:
         if "info" in out:
             info = out.pop("info")
             out.update(obj=info[:, 0], prim_res=info[:, 1], dual_res=info[:, 2], rho=info[:, 3])
+        if self.polish:      # (only then: the dict of a handle without polishing is what it always was)
+            out["polish_status"] = np.empty(B, dtype=np.int32); out["polish_info"] = np.empty((B, 4))
+            _lib.check(_lib.lib().mpcqp_get_polish(self._h, out["polish_status"].ctypes.data, out["polish_info"].ctypes.data, _lib.MEM_HOST))
         return out
 
-    def get_device(self, x=None, y=None, z=None, status=None, iters=None, info=None):
+    def get_device(self, x=None, y=None, z=None, status=None, iters=None, info=None, polish_status=None, polish_info=None):
         """Copy results into caller-owned torch CUDA tensors (device-to-device, on the solve stream)."""
         p = lambda t: None if t is None else t.data_ptr()
         _lib.check(_lib.lib().mpcqp_get(self._h, p(x), p(y), p(z), p(status), p(iters), p(info), _lib.MEM_DEVICE))
+        if polish_status is not None or polish_info is not None:
+            _lib.check(_lib.lib().mpcqp_get_polish(self._h, p(polish_status), p(polish_info), _lib.MEM_DEVICE))
 
     def last_kernel_ms(self):
         ms = C.c_float()

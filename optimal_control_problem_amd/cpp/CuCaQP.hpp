@@ -58,6 +58,13 @@ class CuCaQP {
   // (mpcqp_create_presolved).  An equivalent QP, a shorter ADMM run; the default (false) solves the QP as OSQP does.
   void setPresolveFixedRows(bool on) { if (on != presolve_) { presolve_ = on; dirty_ = true; } }
   int presolvedRows() const { return nfixed_; }
+  // OsqpEigen::Settings::setPolish (OSQP's `polishing`, with OSQP's delta = 1e-6 and polish_refine_iter = 3; mpcqp_set_polish): behind the ADMM loop every
+  // solved instance is refined on its guessed active set.  The reference never calls it, so the default stays off.  Kept across setSystem / initSolver,
+  // also where initSolver creates a new handle.  getPolishStatus: OSQP's info.status_polish (MPCQP_POLISH_*: 1 polished, 0 not performed, -1 candidate
+  // rejected, -2 linear system error) of instance 0, getPolishStatusVector: of every instance.
+  void setPolish(bool polish) { polish_ = polish; }
+  int getPolishStatus() const { return polishStatus_.empty() ? MPCQP_POLISH_NOT_PERFORMED : polishStatus_[0]; }
+  const std::vector<int> &getPolishStatusVector() const { return polishStatus_; }
 
   // data, reference CuCaQP.cpp:43-103 (values are copied, like the reference copies into its members CuCaQP.h:83-87)
   bool setHessianMatrix(const CscView &P) {
@@ -140,6 +147,8 @@ class CuCaQP {
       kept_ = rc == MPCQP_OK && mpcqp_keep_workspace(handle_, 1) == MPCQP_OK;   // not on the streaming kernel variant
     }
     vectorsOnly_ = matricesDirty_ = false; solvedOnce_ = false;
+    if (rc == MPCQP_OK) rc = mpcqp_set_polish(handle_, polish_ ? 1 : 0, 0.0, -1);
+    polishOn_ = polish_ && rc == MPCQP_OK;
     if (rc == MPCQP_OK)
       rc = mpcqp_update(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
                         l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
@@ -161,6 +170,8 @@ class CuCaQP {
     solvedOnce_ = rc == MPCQP_OK;
     solution_.resize((size_t)batch_ * numOfVariables_); status_.resize(batch_); iters_.resize(batch_);
     if (rc == MPCQP_OK) rc = mpcqp_get(handle_, solution_.data(), nullptr, nullptr, status_.data(), iters_.data(), nullptr, MPCQP_MEM_HOST);
+    polishStatus_.assign(batch_, MPCQP_POLISH_NOT_PERFORMED);
+    if (rc == MPCQP_OK && polishOn_) rc = mpcqp_get_polish(handle_, polishStatus_.data(), nullptr, MPCQP_MEM_HOST);
     if (rc != MPCQP_OK) { std::cerr << "Error: Failed to solve problem. Error code: " << rc << std::endl; return false; }
     if (verbose_) std::cout << "mpcqp: status " << status_[0] << " after " << iters_[0] << " ADMM iterations" << std::endl;
     return true;
@@ -284,11 +295,11 @@ class CuCaQP {
 
   int batch_ = 1, numOfVariables_ = 0, numOfConstraints_ = 0;
   bool isInitialized_ = false, verbose_ = false, patternChanged_ = true, dirty_ = false;
-  bool kept_ = false, vectorsOnly_ = false, matricesDirty_ = false, solvedOnce_ = false, presolve_ = false;
+  bool kept_ = false, vectorsOnly_ = false, matricesDirty_ = false, solvedOnce_ = false, presolve_ = false, polish_ = false, polishOn_ = false;
   int nfixed_ = 0;
   mpcqp_settings settings_;
   mpcqp_handle *handle_ = nullptr;
-  std::vector<int> Pp_, Pi_, Ap_, Ai_, status_, iters_;
+  std::vector<int> Pp_, Pi_, Ap_, Ai_, status_, iters_, polishStatus_;
   std::vector<double> Pv_, Av_, q_, l_, u_, solution_;
 #ifdef MPCQP_HAVE_CASADI
   std::vector<int> pc_, pr_, ac_, ar_;

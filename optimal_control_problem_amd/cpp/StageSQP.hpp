@@ -67,6 +67,8 @@ class StageSQP {
     hip(hipMemcpy(x_, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
   }
 
+  // option polish_qp (default off, as the reference leaves OSQP's `polishing` off, :80-85): every QP of the loop is polished (mpcqp_set_polish)
+  void setPolishQP(bool on) { check(mpcqp_set_polish(qp_, on ? 1 : 0, 0.0, -1), "mpcqp_set_polish"); }
   void setTolerance(double tol) { tol_ = tol; }                   // 0 (default) = the reference's fixed iteration count
   int iterationsDone() const { return iterationsDone_; }
 

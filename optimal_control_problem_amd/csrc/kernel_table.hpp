@@ -19,3 +19,18 @@ MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm(int nw, int ng, int nh);        //
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_rf(int nw, int ng, int nh);
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_p4(int rf);                      // four waves, two twisted pairs of chains (dissected order)
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_tl(int nw, int ng, int nh);     // sweeps on dense tiles of A (experiment, MPCQP_VTILES=1)     // re-factorises in place (the last launch of a solve)
+
+// kernel_polish.hpp (k_polish.hip): OSQP's polishing as a post-solve kernel, one wavefront per instance of a slice.  Per-instance pointers stand at the
+// slice's first instance (the kernel indexes by blockIdx); `fac` is the polish factor's own scratch (Lf, Lb, T of one instance: fac_stride doubles)
+struct DevPolish {
+  const double *q; long sq;                 // the caller's (or the handle's owned) q
+  double *x, *y, *z; const int *status; double *info;      // the handle's outputs: the ADMM result in, the accepted candidate out
+  const double *ws, *cscale;                // per-QP slabs (scaled A, A', P, l, u, D, E) and c
+  double *fac; long fac_stride;
+  int *pstatus; double *pinfo;              // MPCQP_POLISH_* and {objective, primal residual, dual residual, active rows} of the candidate
+  double delta; int refine;
+};
+MPCQP_HIDDEN size_t mpcqp_polish_lds(const DevPlan &pl);           // dynamic LDS of one workgroup, bytes
+MPCQP_HIDDEN long mpcqp_polish_fac_doubles(const DevPlan &pl);     // scratch of one instance, doubles
+MPCQP_HIDDEN int mpcqp_polish_prepare(const DevPlan &pl, int device);      // raises the kernel's dynamic-LDS limit where the handle needs it; MPCQP_ERR_LIMIT when it cannot fit
+MPCQP_HIDDEN int mpcqp_polish_launch(const DevPlan &pl, const mpcqp_settings &st, const DevPolish &po, int count, hipStream_t s);

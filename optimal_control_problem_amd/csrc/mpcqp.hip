@@ -82,6 +82,10 @@ struct mpcqp_handle {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev0r = nullptr;   // (ev0r: reduced handles, ordering of the presolve behind a solve on another stream)
   // reduced form (mpcqp_create_reduced): this handle keeps the caller's dimensions, `inner` solves the QP without the eliminated variables
   mpcqp_handle *inner = nullptr; RedMaps red; DevRed dred; double *rx0 = nullptr, *ry0 = nullptr;
+  // polishing (mpcqp_set_polish): off by default; the polish factor's scratch and the per-QP outcome are allocated when it is first switched on
+  bool polish = false, polish_timed = false; double pol_delta = 1e-6; int pol_refine = 3;
+  double *pfac = nullptr; long pfac_stride = 0; int *opstatus = nullptr; double *opinfo = nullptr;
+  hipEvent_t evp0 = nullptr, evp1 = nullptr;
 };
 
 int mpcqp_order_after_last_solve(mpcqp_handle *h, hipStream_t s) {
@@ -215,6 +219,18 @@ static int launch_batch(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipSt
     hipLaunchKernelGGL(mpcqp_validate_kernel, dim3((count + 3) / 4), dim3(256), 0, s, count, h->n, h->m, io.l, io.sl, io.u, io.su, io.x, io.y, io.z,
                        io.status, io.iters, io.info);
     HIPCHK(hipGetLastError());
+  }
+  if (h->polish) {      // OSQP's polish() behind osqp_solve's loop: on the final status (the validation above included), ahead of anything that reads the outputs
+    const long b0 = io.status - h->ostatus;      // (a slice of mpcqp_solve_host: the handle's own buffers are advanced like io's)
+    DevPolish po;
+    po.q = io.q; po.sq = io.sq; po.x = io.x; po.y = io.y; po.z = io.z; po.status = io.status; po.info = io.info; po.ws = io.ws; po.cscale = io.cscale;
+    po.fac = h->pfac + b0 * h->pfac_stride; po.fac_stride = h->pfac_stride; po.pstatus = h->opstatus + b0; po.pinfo = h->opinfo + 4 * b0;
+    po.delta = h->pol_delta; po.refine = h->pol_refine;
+    const bool timed = after_kernel != nullptr;
+    if (timed) HIPCHK(hipEventRecord(h->evp0, s));
+    if (int rc = mpcqp_polish_launch(h->dp, h->st, po, count, s)) return rc;
+    if (timed) HIPCHK(hipEventRecord(h->evp1, s));
+    h->polish_timed = timed;
   }
   return MPCQP_OK;
 }
@@ -872,6 +888,8 @@ void mpcqp_destroy(mpcqp_handle *h) {
   if (h->ev_guard) (void)hipEventDestroy(h->ev_guard);
   if (h->ev_order) (void)hipEventDestroy(h->ev_order);
   if (h->ev0r) (void)hipEventDestroy(h->ev0r);
+  if (h->evp0) (void)hipEventDestroy(h->evp0);
+  if (h->evp1) (void)hipEventDestroy(h->evp1);
   for (int i = 0; i < mpcqp_handle::NPIPE; i++) if (h->pipe[i]) (void)hipStreamDestroy(h->pipe[i]);
   if (h->pipe_copy) (void)hipStreamDestroy(h->pipe_copy);
   for (hipEvent_t e : h->pipe_ev) (void)hipEventDestroy(e);
@@ -897,6 +915,61 @@ int mpcqp_last_phase_ms(mpcqp_handle *h, float *setup_ms, float *solve_ms) {
   if (!h->sel.split) { *setup_ms = 0.f; HIPCHK(hipEventElapsedTime(solve_ms, h->ev0, h->ev1)); return MPCQP_OK; }
   HIPCHK(hipEventElapsedTime(setup_ms, h->ev0, h->ev_mid));
   HIPCHK(hipEventElapsedTime(solve_ms, h->ev_mid, h->ev1));
+  return MPCQP_OK;
+}
+
+int mpcqp_set_polish(mpcqp_handle *h, int enable, double delta, int refine_iter) {
+  if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+  if (h->inner) {
+    const int rc = mpcqp_set_polish(h->inner, enable, delta, refine_iter);
+    if (!rc) h->polish = h->inner->polish;
+    return rc;
+  }
+  if (!enable) { h->polish = false; h->polish_timed = false; return MPCQP_OK; }
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->pfac) {
+    if (int rc = mpcqp_polish_prepare(h->dp, h->device)) return rc;
+    if (h->solved) HIPCHK(hipStreamSynchronize(h->last_stream));
+    const size_t B = h->batch;
+    h->pfac_stride = mpcqp_polish_fac_doubles(h->dp);
+    int rc;
+    if ((rc = dalloc(h, &h->pfac, B * (size_t)h->pfac_stride))) return rc;
+    if ((rc = dalloc(h, &h->opstatus, B))) return rc;
+    if ((rc = dalloc(h, &h->opinfo, B * 4))) return rc;
+    HIPCHK(hipMemset(h->opstatus, 0, B * sizeof(int))); HIPCHK(hipMemset(h->opinfo, 0, B * 4 * sizeof(double)));
+    HIPCHK(hipEventCreate(&h->evp0)); HIPCHK(hipEventCreate(&h->evp1));
+  }
+  h->pol_delta = delta > 0.0 ? delta : 1e-6;
+  h->pol_refine = refine_iter >= 0 ? refine_iter : 3;
+  h->polish = true;
+  return MPCQP_OK;
+}
+
+int mpcqp_get_polish(mpcqp_handle *h, int *polish_status, double *polish_info, int mem) {
+  if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+  if (!h->polish) return fail(MPCQP_ERR_STATE, "polishing is off (mpcqp_set_polish)");
+  if (!h->solved) return fail(MPCQP_ERR_STATE, "no solve has been issued");
+  if (h->inner) {      // (the inner handle ran on the same stream as the expansion behind it)
+    return mpcqp_get_polish(h->inner, polish_status, polish_info, mem);
+  }
+  if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
+  HIPCHK(hipSetDevice(h->device));
+  const hipMemcpyKind k = mem == MPCQP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  hipStream_t s = h->last_stream;
+  const size_t B = h->batch;
+  if (polish_status) HIPCHK(hipMemcpyAsync(polish_status, h->opstatus, B * sizeof(int), k, s));
+  if (polish_info) HIPCHK(hipMemcpyAsync(polish_info, h->opinfo, B * 4 * sizeof(double), k, s));
+  if (mem != MPCQP_MEM_DEVICE) HIPCHK(hipStreamSynchronize(s));
+  return MPCQP_OK;
+}
+
+int mpcqp_last_polish_ms(mpcqp_handle *h, float *ms) {
+  if (!h || !ms) return fail(MPCQP_ERR_ARG, "null pointer");
+  if (h->inner) return mpcqp_last_polish_ms(h->inner, ms);
+  if (!h->solved || !h->polish || !h->polish_timed) return fail(MPCQP_ERR_STATE, "no polish kernel has run behind an mpcqp_solve");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipEventSynchronize(h->evp1));
+  HIPCHK(hipEventElapsedTime(ms, h->evp0, h->evp1));
   return MPCQP_OK;
 }
 

@@ -39,6 +39,7 @@ class CuCaQP:
         self._start = None
         self._rho0 = None
         self._kept = False
+        self._polish = self._polish_applied = False
         self._vectors_dirty = self._matrices_dirty = self._solved_once = False
 
     # -- dimensions (CuCaQP.cpp:23-41)
@@ -66,6 +67,13 @@ class CuCaQP:
 
     def setMaxIteration(self, maxIteration):
         self._kw["max_iter"] = int(maxIteration)
+
+    def setPolish(self, polish):
+        """OsqpEigen::Settings::setPolish (OSQP's `polishing`; the reference never calls it, so the default stays off): refine every solved
+        instance on its guessed active set behind the ADMM loop.  Kept across setSystem / initSolver like the other settings."""
+        self._polish = bool(polish)
+        if self._qp is not None and self._polish != self._polish_applied:
+            self._qp.set_polish(self._polish); self._polish_applied = self._polish
 
     def setPrimalDualStart(self, x0, y0):
         """extension (the reference's private update* fast path made usable, CuCaQP.cpp:106-161): start the next solve's
@@ -228,10 +236,13 @@ class CuCaQP:
                                    self._A[0], self._A[1], device=self._device, **kw)
                 self._pattern_key = key
                 self._kept = False
+                self._polish_applied = False
                 try:
                     self._qp.keep_workspace(True); self._kept = True
                 except _lib.MpcqpError:
                     pass                                  # streaming kernel variant: every solve is a full setup
+            if self._polish != self._polish_applied:       # (a handle initSolver has just created starts with polishing off)
+                self._qp.set_polish(self._polish); self._polish_applied = self._polish
             self._qp.update(self._P[2], self.gradient, self._A[2], self.lowerBound, self.upperBound)
             self._vectors_dirty = self._matrices_dirty = self._solved_once = False
             if self._start is not None:
@@ -278,6 +289,12 @@ class CuCaQP:
 
     def getIterations(self):
         return None if self._result is None else self._result["iters"]
+
+    def getPolishStatus(self):
+        """OSQP's info.status_polish per instance (_lib.POLISH_*: 1 polished, 0 not performed, -1 candidate rejected, -2 linear system error)"""
+        if self._result is None or "polish_status" not in self._result:
+            return np.zeros(self.batch, dtype=np.int32)
+        return self._result["polish_status"]
 
     def getInfo(self):
         return self._result

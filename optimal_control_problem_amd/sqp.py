@@ -139,6 +139,8 @@ class DeviceSQPOptimizationSolver:
         # asserts the matrices are constant, exactly as with OSQP's osqp_update_data_vec.
         self.constant_matrices = bool(options.get("constant_matrices", False))
         self.sqp_tol = float(options.get("sqp_tol", 0.0) or 0.0)      # opt-in convergence stop, see the module docstring
+        # extension: OSQP's `polishing` on every QP of the loop (mpcqp_set_polish); the reference leaves it off (:80-85), and so does the default
+        self.polish_qp = bool(options.get("polish_qp", False))
         self.iterations_done = 0
         self.step_max = None
         self._kept = False
@@ -149,6 +151,8 @@ class DeviceSQPOptimizationSolver:
                           eps_abs=1e-3, eps_rel=1e-3, max_iter=10000, warm_start=1 if self.warm_start_admm else 0, device=device)
         if self.constant_matrices:
             self.qp.keep_workspace(True)
+        if self.polish_qp:
+            self.qp.set_polish(True)
         self.dev = torch.device("cuda", torch.cuda.current_device() if device < 0 else device)
         mk = lambda w, dt=torch.float64: torch.zeros((self.batch, w), dtype=dt, device=self.dev)
         self.x = mk(self.ev.nvar)                        # persists across calls like result_ (:88-91)

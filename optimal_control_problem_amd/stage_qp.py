@@ -74,6 +74,7 @@ class StageQP(BatchQP):
         self._sq = C.c_void_p()
         self._h = C.c_void_p()
         self._keep = []
+        self.polish = False          # (set_polish / get / get_device: BatchQP's, on the handle underneath)
         L = _lib.lib()
         _lib.check(L.mpcqp_stageqp_create(C.byref(d), self.batch, C.byref(self.settings), C.byref(self._sq)))
         self._h = C.c_void_p(L.mpcqp_stageqp_handle(self._sq))

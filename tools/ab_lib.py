@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B of two builds of libmpcqp.so on the same box: kernel time of the bench workloads through a minimal ctypes binding
-(only the entry points every build has).  usage: python tools/ab_lib.py libA.so libB.so ..."""
+(only the entry points every build has).  usage: python tools/ab_lib.py libA.so libB.so ...
+AB_CASES=name:N:batch,... chooses the workloads, AB_EPS=1e-6 the tolerance (eps_abs = eps_rel; default: the library's own, 1e-3)."""
 import ctypes as C
 import os
 import sys
@@ -29,9 +30,13 @@ for rep in range(2):
         L.mpcqp_solve.argtypes = [vp, vp]; L.mpcqp_sync.argtypes = [vp]; L.mpcqp_destroy.argtypes = [vp]
         L.mpcqp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         out = []
+        st = None
+        if os.environ.get("AB_EPS"):
+            L.mpcqp_default_settings.argtypes = [C.POINTER(Settings)]
+            st = Settings(); L.mpcqp_default_settings(C.byref(st)); st.eps_abs = st.eps_rel = float(os.environ["AB_EPS"])
         for key, (ls, d) in data.items():
             h = vp()
-            assert L.mpcqp_create(ls.n, ls.m, key[2], ls.Pp.ctypes.data, ls.Pi.ctypes.data, ls.Ap.ctypes.data, ls.Ai.ctypes.data, None, C.byref(h)) == 0
+            assert L.mpcqp_create(ls.n, ls.m, key[2], ls.Pp.ctypes.data, ls.Pi.ctypes.data, ls.Ap.ctypes.data, ls.Ai.ctypes.data, C.byref(st) if st else None, C.byref(h)) == 0
             ms = []
             for _ in range(6):
                 assert L.mpcqp_update(h, d[0].data_ptr(), ls.P.shape[1], d[1].data_ptr(), ls.n, d[2].data_ptr(), ls.A.shape[1], d[3].data_ptr(), ls.m, d[4].data_ptr(), ls.m, 1) == 0
