@@ -506,7 +506,7 @@ __device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs,
       TS(5);
       can_check = st.check_termination && (iter % st.check_termination == 0);
       const int do_rho = st.adaptive_rho && interval && (iter % interval == 0);
-      const int save = can_check || do_rho;
+      const int save = can_check || do_rho || iter == st.max_iter;      // (the last iteration's steps are what the check behind the loop reads)
       {
         // ztilde = A xtilde fused with relaxation, projection onto [l, u], dual update and w = rho z - y.  l, u, z, y of the row are fetched before
         // the row sum is accumulated.

@@ -1102,7 +1102,7 @@ __global__ void __launch_bounds__(NW * WAVE, MINW) mpcqp_res_kernel(const DevPla
       TS(5);
       can_check = st.check_termination && (iter % st.check_termination == 0);
       const int do_rho = st.adaptive_rho && interval && (iter % interval == 0);
-      const int save = can_check || do_rho;
+      const int save = can_check || do_rho || iter == st.max_iter;      // (the last iteration's steps are what the check behind the loop reads)
       {
         // ztilde = A xtilde fused with relaxation, projection onto [l, u], dual update and w = rho z - y.
         // l, u are fetched before the row sum is accumulated; rho_i and 1/rho_i are selected from the three values

@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(WAVE) mpcqp_admm_kernel(const DevPlan pl, cons
       run_stream<PD>(Lbk, pl.bwd_ops, pl.nblk, cx.R);
       can_check = st.check_termination && (iter % st.check_termination == 0);
       const int do_rho = st.adaptive_rho && interval && (iter % interval == 0);
-      const int save = can_check || do_rho;
+      const int save = can_check || do_rho || iter == st.max_iter;      // (the last iteration's steps are what the check behind the loop reads)
       // ztilde = A xtilde, fused with the z / y updates (projection onto [l, u]) and w = rho z - y
       ell_rows(pl.A, valA, cx.R, [&](int i, double zt) {
         if (i < m) {

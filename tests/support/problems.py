@@ -119,6 +119,102 @@ def warm_point(ls, settings):
     return w["x"], w["y"], dict(settings, warm_start=1)
 
 
+# ---------------------------------------------------------------------------------------------- settings and exit statuses
+# The MPC workloads with two instances spoilt, so that every kernel family (the on-chip ones take stage patterns only) meets certificates of
+# infeasibility next to ordinary solves: id -> (workload, N, batch).  tests/test_settings_recipes.py holds the oracle's outcomes on them to what
+# tests/test_gpu_settings.py relies on.
+HARD_WORKLOADS = {"q20": ("quadrotor", 20, 8), "cp30": ("cartpole", 30, 6), "q50": ("quadrotor", 50, 4), "cp100": ("cartpole", 100, 4)}
+DUAL_INFEASIBLE, PRIMAL_INFEASIBLE = 1, 2          # the instances hard_stage_batch alters
+
+
+def hard_stage_batch(wid, dual=True):
+    """-> (model, LocalSystem, meta) of HARD_WORKLOADS[wid] with
+      * instance 2 primal infeasible: the second frame's first state boxed into [50, 60], which the pinned first frame cannot reach in one step;
+      * instance 1 dual infeasible (dual=True): the last frame's last input -- which no dynamics row reads -- without curvature (its row and column of P
+        zero), with q = -1 and its only row of A (its box) unbounded: an unbounded direction of descent.
+    P is materialised per instance where the workload shares it; meta["dual_rows"]: the rows of A that were unbounded."""
+    name, N, B = HARD_WORKLOADS[wid]
+    mdl, ls, meta = models.make_workload(name, B, N=N)
+    P = np.array(np.broadcast_to(ls.P, (B, len(ls.Pi)))); q, l, u = ls.q.copy(), ls.l.copy(), ls.u.copy()
+    row = mdl.np + mdl.f
+    l[PRIMAL_INFEASIBLE, row], u[PRIMAL_INFEASIBLE, row] = 50.0, 60.0
+    rows_of_j = np.zeros(0, int)
+    if dual:
+        j = ls.n - 1
+        cols = np.repeat(np.arange(ls.n), np.diff(ls.Pp))
+        P[DUAL_INFEASIBLE, (cols == j) | (np.asarray(ls.Pi) == j)] = 0.0
+        q[DUAL_INFEASIBLE, j] = -1.0
+        rows_of_j = np.asarray(ls.Ai[ls.Ap[j]:ls.Ap[j + 1]], int)
+        l[DUAL_INFEASIBLE, rows_of_j] = -np.inf; u[DUAL_INFEASIBLE, rows_of_j] = np.inf
+    hard = models.LocalSystem(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai, P, q, ls.A, l, u, ls.np)
+    return mdl, hard, dict(meta, dual_rows=rows_of_j)
+
+
+# id -> settings: every numeric field of mpcqp_settings that changes what the loop does, at a value other than its default, one at a time (and the
+# iteration limits that end a run off a termination check).  A check_termination = 0 entry carries a small max_iter: nothing else stops such a run.
+from collections import OrderedDict      # noqa: E402
+SETTINGS_MATRIX = OrderedDict([
+    ("default", {}),
+    ("max_iter=24", dict(max_iter=24)),
+    ("max_iter=37", dict(max_iter=37)),
+    ("max_iter=60", dict(max_iter=60)),
+    ("check=0,max_iter=40", dict(check_termination=0, max_iter=40)),
+    ("check=7,max_iter=30", dict(check_termination=7, max_iter=30)),
+    ("check=1", dict(check_termination=1)),
+    ("alpha=1.0", dict(alpha=1.0)),
+    ("scaling=0", dict(scaling=0)),
+    ("scaled_termination=1", dict(scaled_termination=1)),
+    ("eps_dual_inf=1e-7", dict(eps_dual_inf=1e-7)),
+    ("eps_prim_inf=1e-7,eps_dual_inf=1e-2", dict(eps_prim_inf=1e-7, eps_dual_inf=1e-2)),
+    ("alpha=1.9", dict(alpha=1.9)),
+    ("sigma=1e-3", dict(sigma=1e-3)),
+    ("scaling=3", dict(scaling=3)),
+    ("adaptive_rho=0", dict(adaptive_rho=0)),
+    ("rho=1.0", dict(rho=1.0)),
+    ("scaling=25", dict(scaling=25)),
+])
+
+
+def _ends_in_the_tail(st):
+    check, limit = st.get("check_termination", 25), st.get("max_iter", 10000)
+    return check == 0 or limit % check != 0
+
+
+# the settings under which a run that reaches the iteration limit is judged in the code after the loop, not by a termination check inside it
+TAIL_CASES = tuple(k for k, st in SETTINGS_MATRIX.items() if _ends_in_the_tail(st))
+# ... and, of these, the ones under which nothing in the loop looks at the iterates' last steps before that (no check, no rho update) on the quadrotor N=20
+NEVER_SAVED = ("max_iter=24", "check=0,max_iter=40")
+# the settings the kept-workspace leg runs under (the kept path scales q, l, u with parked D, E, c and has its own entry into the loop)
+KEPT_CASES = ("alpha=1.0", "scaling=0", "scaled_termination=1", "check=7,max_iter=30")
+# ... and the reduced-form leg (the settings have to reach the inner handle)
+REDUCED_CASES = ("alpha=1.0", "check=7,max_iter=30")
+
+
+def kept_q(ls):
+    """the q of the second, vectors-only solve of the kept-workspace leg"""
+    return ls.q * (1.0 + 0.1 * np.random.default_rng(17).standard_normal(ls.q.shape))
+
+
+def oracle_kept_solves(ls, q2, nthreads=8, **settings):
+    """-> (full solve, vectors-only solve with q2) of the oracle's kept workspaces (osqp_update_data_vec semantics)"""
+    from oracle import oracle as orc
+    state = orc.State(orc.Pattern(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai), ls.batch, orc.default_settings(**settings))
+    return state.solve(ls.P, ls.q, ls.A, ls.l, ls.u, nthreads=nthreads), state.solve_vectors(q2, ls.l, ls.u, nthreads=nthreads)
+
+
+def oracle_kept_stable_mask(ls, q2, draws=3, nthreads=8, **settings):
+    """oracle_stable_mask for the pair of solves of a kept workspace: -> (mask of the full solve, mask of the vectors-only solve)"""
+    ref = oracle_kept_solves(ls, q2, nthreads, **settings)
+    rng = np.random.default_rng(99)
+    ok = [np.ones(ls.batch, bool), np.ones(ls.batch, bool)]
+    for _ in range(draws):
+        P, A, q, qq = (a * (1.0 + 1e-12 * rng.standard_normal(a.shape)) for a in (ls.P, ls.A, ls.q, q2))
+        got = oracle_kept_solves(models.LocalSystem(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai, P, q, A, ls.l, ls.u), qq, nthreads, **settings)
+        for k in (0, 1):
+            ok[k] &= (got[k]["iters"] == ref[k]["iters"]) & (np.abs(got[k]["rho"] - ref[k]["rho"]) <= 1e-6 * np.abs(ref[k]["rho"])) & (got[k]["status"] == ref[k]["status"])
+    return ok[0], ok[1]
+
+
 BIG_BATCH = 700          # more instances than an MI355X has compute units: the eight-wave instances run one workgroup per CU and queue the rest
 
 
