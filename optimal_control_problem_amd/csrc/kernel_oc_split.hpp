@@ -165,7 +165,23 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     // (the staged values through pointers whose memory the compiler KNOWS: `a_lds ? lds : valA` is a pointer to either, every access through it a
     // flat load that takes both memory paths and waits for both counters -- the whole scaling phase ran on those; one copy of the phase per case)
     const bool a_lds = oc.a_lds, p_lds = oc.p_lds;
-    auto scale_phase = [&](double *sA, double *sP, auto iA, auto iP) __attribute__((always_inline)) {
+    // rg: the instances whose passes keep their fixed operands in registers (kernel_resident.hpp rz_*): A's indices with the LDS offsets of its staged
+    // values, P's values and indices, q of the wave's columns.  Decided per wave and per structure from the chunk offsets; a wave whose list does not
+    // fit walks that structure as before (and P then goes through the slab first, for every wave).
+    auto scale_phase = [&](double *sA, double *sP, auto iA, auto iP, auto rg) __attribute__((always_inline)) {
+    constexpr bool RG = decltype(rg)::value;
+    const int shA = pl.P.nchunks % NW, firstA = (wid + NW - shA) % NW;
+    [[maybe_unused]] unsigned aR[RZ_CAPA], pI[RZ_CAPP / 2]; [[maybe_unused]] double pV[RZ_CAPP], qs[RZ_KP];
+    [[maybe_unused]] RzList<RZ_KA> LA; [[maybe_unused]] RzList<RZ_KP> LP;
+    bool ra = false, rp = false, p_slab = true;      // this wave's A / P from registers; P's unscaled values are needed in the slab
+    if constexpr (RG) {
+      const bool on = !oc.no_ruiz_regs && pl.A.entries <= 65536 && npad <= 65536 && mpad <= 65536;
+      LA = rz_list<NW, RZ_KA, RZ_CAPA>(pl.A.chunk_off, pl.A.nchunks, firstA); LP = rz_list<NW, RZ_KP, RZ_CAPP>(pl.P.chunk_off, pl.P.nchunks, wid);
+      ra = on && LA.fits; rp = on && LP.fits;
+      bool every = on;
+      for (int w = 0; w < NW; w++) every = every && rz_list<NW, RZ_KP, RZ_CAPP>(pl.P.chunk_off, pl.P.nchunks, w).fits;
+      p_slab = !every;
+    }
     // (eight source indices, then the eight values they point at, in flight at a time: one element per trip was two dependent round trips to memory each)
     auto gather8 = [&](const int *__restrict__ src, const double *__restrict__ in, double *dst, const long entries) __attribute__((always_inline)) {
       long e = tid;
@@ -181,7 +197,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
       for (; e < entries; e += NT) { const int sr = src[e]; dst[e] = sr >= 0 ? in[sr] : 0.0; }
     };
     gather8(pl.A.src, inA, sA, pl.A.entries);
-    gather8(pl.P.src, inP, sP, pl.P.entries);
+    if (p_slab) gather8(pl.P.src, inP, sP, pl.P.entries);
     // (the ten passes gather through these: a read from LDS instead of a round trip to the L2 in front of every batch)
     if constexpr (sizeof(*iA) == 2) { for (long e = tid; e < pl.A.entries; e += NT) iA[e] = (unsigned short)pl.A.idx[e]; }
     if constexpr (sizeof(*iP) == 2) { for (long e = tid; e < pl.P.entries; e += NT) iP[e] = (unsigned short)pl.P.idx[e]; }
@@ -190,17 +206,34 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     bsync<NW>();
     for (int j = tid; j < n; j += NT) Qs[pl.pos[j]] = inq[j];
     bsync<NW>();
+    if constexpr (RG) {
+      if (ra) rz_fill_a(LA, iA, lane, aR);
+      if (rp) {
+        rz_fill_p(LP, iP, pl.P.src, inP, lane, pV, pI);
+#pragma unroll
+        for (int q = 0; q < RZ_KP; q++) { const int t = (wid + q * NW) * WAVE + lane; qs[q] = (q < LP.nk && t < npad) ? Qs[t] : 0.0; }
+      }
+    }
     TS(0);
     // ---- modified Ruiz equilibration: D in R, E in W; X = the column-norm accumulators of the sweep over A (one sweep by rows gives the row norm,
     // lane-local, and the column norms, LDS atomic max on the bit pattern); nP = max_k |P_tk| d_k is needed twice per pass -- before and after D
     // is updated -- and swept once (the second value is the next pass's first; it lives in the y region, n doubles long in this kernel)
     c = 1.0;
     double *nPv = cx.Y;
-    if (st.scaling > 0) { for (int ch = wid; ch < pl.P.nchunks; ch += NW) { const int t = ch * WAVE + lane; const double x = ell_chunk_mx(sP, iP, cx.R, cx.coP[ch], cx.coP[ch + 1], lane); if (t < npad) nPv[t] = x; } }
+    if (st.scaling > 0) {
+      if (RG && rp) {
+        if constexpr (RG) {
+          double xs[RZ_KP];
+          rz_pass_p(LP, pV, pI, cx.R, xs);
+#pragma unroll
+          for (int q = 0; q < RZ_KP; q++) { const int t = (wid + q * NW) * WAVE + lane; if (q < LP.nk && t < npad) nPv[t] = xs[q]; }
+        }
+      } else
+      for (int ch = wid; ch < pl.P.nchunks; ch += NW) { const int t = ch * WAVE + lane; const double x = ell_chunk_mx(sP, iP, cx.R, cx.coP[ch], cx.coP[ch + 1], lane); if (t < npad) nPv[t] = x; }
+    }
     // Two barriers per pass: the cost scale's reduction (one max, one sum over the columns of P) is finished by every wave for itself behind the NEXT pass's
     // first barrier -- the partial results wait in RED meanwhile; c is first needed by the D update.  The chunks of A start at the wave where those of P
     // end, so that the pair of sweeps between two barriers is balanced.
-    const int shA = pl.P.nchunks % NW;
     auto cost_scale = [&]() {
       double r0 = cx.RED[0], r1 = cx.RED[1];
       for (int w = 1; w < NW; w++) { r0 = fmax(r0, cx.RED[2 * w]); r1 = r1 + cx.RED[2 * w + 1]; }
@@ -208,7 +241,10 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     };
     for (int it = 0; it < st.scaling; it++) {
       RZ_T0;
-      for (int ch = (wid + NW - shA) % NW; ch < pl.A.nchunks; ch += NW) {
+      if (RG && ra) {
+        if constexpr (RG) rz_pass_a<NW>(LA, aR, sA, cx.R, cx.X, cx.W, firstA, mpad, lane);
+      } else
+      for (int ch = firstA; ch < pl.A.nchunks; ch += NW) {
         const int i = ch * WAVE + lane;
         const double ei = i < mpad ? cx.W[i] : 0.0;
         const double v = ell_chunk_rc(sA, iA, cx.R, ei, cx.X, cx.coA[ch], cx.coA[ch + 1], lane);
@@ -226,6 +262,17 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
       bsync<NW>();
       RZ_T(6);
       double v[2] = {0.0, 0.0};   // 0 qn (max) 1 sum
+      if (RG && rp) {
+        if constexpr (RG) {
+          double xs[RZ_KP];
+          rz_pass_p(LP, pV, pI, cx.R, xs);
+#pragma unroll
+          for (int q = 0; q < RZ_KP; q++) {
+            const int t = (wid + q * NW) * WAVE + lane; const double x = xs[q];
+            if (q < LP.nk && t < npad) { nPv[t] = x; v[1] += c * cx.R[t] * x; v[0] = fmax(v[0], fabs(c * cx.R[t] * qs[q])); }
+          }
+        }
+      } else
       for (int ch = wid; ch < pl.P.nchunks; ch += NW) {
         const int t = ch * WAVE + lane;
         const double x = ell_chunk_mx(sP, iP, cx.R, cx.coP[ch], cx.coP[ch + 1], lane);
@@ -239,6 +286,9 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     c = uni(c); cx.c = c; cx.cinv = uni(1.0 / c);
     TS(1);
     // scale and write out: A <- E A D, A' likewise (gathered from the caller's array), P <- c D P D (coalesced stores of whole 512 B slots; up to 8 slots in flight)
+    // (P first where it comes from the registers: they are free for the other write-outs' batches then; its unscaled values never went to the slab unless
+    // some wave's list did not fit)
+    if constexpr (RG) { if (rp) rz_write_p<NW>(LP, pV, pI, cx.R, valP, c, wid, npad, lane); }
     for (int ch = wid; ch < pl.A.nchunks; ch += NW) {
       const int i = ch * WAVE + lane; const double ei = i < mpad ? cx.W[i] : 0.0;
       ell_map_chunk<false>(sA, pl.A.idx, nullptr, pl.A.idx, valA, cx.coA[ch], cx.coA[ch + 1], lane, [&](double v, int j) { return v * (ei * cx.R[j]); });
@@ -246,7 +296,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     for (int ch = wid; ch < pl.At.nchunks; ch += NW) {
       const int t = ch * WAVE + lane; const double dj = t < npad ? cx.R[t] : 0.0;
       ell_map_chunk<true>(valAt, pl.At.src, inA, pl.At.idx, valAt, cx.coAt[ch], cx.coAt[ch + 1], lane, [&](double v, int i) { return v * (dj * cx.W[i]); });
-      ell_map_chunk<false>(sP, pl.P.idx, nullptr, pl.P.idx, valP, cx.coP[ch], cx.coP[ch + 1], lane, [&](double v, int k) { return v * (c * dj * cx.R[k]); });
+      if (!(RG && rp)) ell_map_chunk<false>(sP, pl.P.idx, nullptr, pl.P.idx, valP, cx.coP[ch], cx.coP[ch + 1], lane, [&](double v, int k) { return v * (c * dj * cx.R[k]); });
     }
     if (oc.tl.on) {
       // the same scaled numbers once more in the layouts of the tile sweeps (experiment, MPCQP_VTILES=1): dense 16 x 16 tiles, row-major (element (r, c)
@@ -281,14 +331,15 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     }
     };
     unsigned short *iA16 = reinterpret_cast<unsigned short *>(lds) + oc.ixo_a, *iP16 = reinterpret_cast<unsigned short *>(lds) + oc.ixo_p;
-    if (a_lds && p_lds && oc.ix16 == 3) scale_phase(lds, lds + pl.A.entries, iA16, iP16);
-    else if (a_lds && p_lds && oc.ix16 == 1) scale_phase(lds, lds + pl.A.entries, iA16, pl.P.idx);
-    else if (a_lds && p_lds) scale_phase(lds, lds + pl.A.entries, pl.A.idx, pl.P.idx);
-    else if (a_lds) scale_phase(lds, valP, pl.A.idx, pl.P.idx);
+    constexpr std::false_type plain{}; constexpr std::true_type regs{};
+    if (a_lds && p_lds && oc.ix16 == 3) scale_phase(lds, lds + pl.A.entries, iA16, iP16, plain);
+    else if (a_lds && p_lds && oc.ix16 == 1) scale_phase(lds, lds + pl.A.entries, iA16, pl.P.idx, plain);
+    else if (a_lds && p_lds) scale_phase(lds, lds + pl.A.entries, pl.A.idx, pl.P.idx, plain);
+    else if (a_lds) scale_phase(lds, valP, pl.A.idx, pl.P.idx, regs);      // (the north-star shape: A staged at three workgroups per CU, no room for index tables)
     // (values in the slab: the index tables alone -- a quarter less to read per pass, and the gathers' addresses come from LDS; quadrotor N=50 set-up 8.05 -> 6.93 ms with A's)
-    else if (oc.ix16 == 3) scale_phase(valA, valP, iA16, iP16);
-    else if (oc.ix16 == 1) scale_phase(valA, valP, iA16, pl.P.idx);
-    else scale_phase(valA, valP, pl.A.idx, pl.P.idx);
+    else if (oc.ix16 == 3) scale_phase(valA, valP, iA16, iP16, regs);
+    else if (oc.ix16 == 1) scale_phase(valA, valP, iA16, pl.P.idx, regs);
+    else scale_phase(valA, valP, pl.A.idx, pl.P.idx, regs);
   }
   bsync<NW>();
   // a kept factor belongs to the rho it was built with: that instance's final rho of the previous solve

@@ -42,6 +42,7 @@ struct DevOc {
   int resume;           // two-kernel form: this launch continues instances that left the iteration kernel for a re-factorisation (kernel_oc_split.hpp)
   int ixo_a, ixo_p;     // ... where those tables start, in 16-bit units from the LDS base (the z region; for shapes without staged values also the factorisation's scratch, idle until then)
   int ix16, zpad;       // set-up kernel (its own vector layout, kernel_oc_split.hpp oc_lds): 16-bit index tables of A (& 1) and P (& 2) in its z region of zpad doubles
+  int no_ruiz_regs = 0; // set-up kernel, switch (MPCQP_NO_RUIZ_REGS=1): every wave reloads the Ruiz passes' fixed operands instead of keeping them in registers (in the struct's tail padding: same size)
 };
 
 // LDS image of a 16x16 block: rows alternate between the two 32-bank halves in a pattern that also separates rows 4 apart, the four

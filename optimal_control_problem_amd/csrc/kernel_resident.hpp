@@ -194,6 +194,188 @@ __device__ __forceinline__ double ell_chunk_mx(const double *__restrict__ val, c
   if (rem & 1) acc = ell_batch_mx<1>(vp, ip, in, acc);
   return acc;
 }
+// ---- the Ruiz passes' fixed operands in registers (set-up kernel of the two-kernel on-chip form, kernel_oc_split.hpp) ----
+// What a sweep over A or P reads besides D and E is the same in all ten passes: the slots' indices (and P's values).  A wave's slot list -- the slots
+// of its chunks, in the order it walks them -- is loaded once into registers the factorisation needs later and the passes leave idle; a pass then
+// touches LDS and registers only.  The capacities are compile-time (plan.hpp RUIZ_REG_*: the registers are indexed by unrolled loops), a wave whose
+// list does not fit keeps ell_chunk_rc / ell_chunk_mx for that structure.  Everything in RzList is wave-uniform.
+constexpr int RZ_U = 4;      // LDS gathers in flight per batch (the capacities are multiples of it)
+constexpr int RZ_KA = RUIZ_REG_CHUNKS_A, RZ_KP = RUIZ_REG_CHUNKS_P, RZ_CAPA = RUIZ_REG_SLOTS_A, RZ_CAPP = RUIZ_REG_SLOTS_P;
+static_assert(RZ_CAPA % RZ_U == 0 && RZ_CAPP % RZ_U == 0 && RZ_CAPP % 2 == 0, "register slot capacities: whole batches, index pairs");
+// chunks owned, their slots, "the list fits"; first ELL slot of chunk k (s0, s1, s2), end of its register slots (e0, e1, e2).  Plain members, picked by
+// comparisons: an array indexed by the running chunk number lands in scratch, and what is read back from there no longer counts as wave-uniform
+template <int K> struct RzList { int nk, tot, fits, s0, s1, s2, e0, e1, e2; };
+static_assert(RUIZ_REG_CHUNKS_A <= 3 && RUIZ_REG_CHUNKS_P <= 3, "RzList holds three chunks");
+// (every member read before the choice: a choice between loads becomes a load from a chosen address, and the struct stays in memory for it)
+__device__ __forceinline__ int rz_pick3(const int a, const int b, const int c, const int k) { return __builtin_amdgcn_readfirstlane(k == 0 ? a : k == 1 ? b : c); }
+template <int K> __device__ __forceinline__ int rz_end(const RzList<K> &L, const int k) { const int a = L.e0, b = L.e1, c = K < 3 ? b : L.e2; return rz_pick3(a, b, c, k); }
+template <int K> __device__ __forceinline__ int rz_s0(const RzList<K> &L, const int k) { const int a = L.s0, b = L.s1, c = K < 3 ? b : L.s2; return rz_pick3(a, b, c, k); }
+template <int K>
+__device__ __forceinline__ void rz_put(double (&a)[K], const int k, const double v) {
+#pragma unroll
+  for (int q = 0; q < K; q++) a[q] = k == q ? v : a[q];
+}
+template <int NW, int K, int CAP>
+__device__ __forceinline__ RzList<K> rz_list(const int *__restrict__ chunk_off, const int nchunks, const int first) {
+  RzList<K> L; L.nk = 0; L.tot = 0;
+  auto one = [&](const int q, int &s0, int &end) {
+    const int ch = first + q * NW; const bool in = q < K && ch < nchunks;
+    const int a = __builtin_amdgcn_readfirstlane(in ? chunk_off[ch] : 0), b = __builtin_amdgcn_readfirstlane(in ? chunk_off[ch + 1] : 0);
+    s0 = a; L.tot += b - a; end = L.tot; L.nk += in;
+  };
+  one(0, L.s0, L.e0); one(1, L.s1, L.e1); one(2, L.s2, L.e2);
+  L.fits = first + K * NW >= nchunks && L.tot <= CAP;
+  return L;
+}
+// walking a list slot by slot: register slot u belongs to chunk k, which covers register slots [beg, beg + w) and starts at ELL slot s0
+struct RzWalk { int k, beg, w, s0; };
+template <int K>
+__device__ __forceinline__ RzWalk rz_walk0(const RzList<K> &L) { return RzWalk{0, 0, L.e0, L.s0}; }
+template <int K>
+__device__ __forceinline__ bool rz_step(const RzList<K> &L, RzWalk &wk, const int u) {      // -> "chunk changed"; only called with u < L.tot (a later chunk has the slot)
+  bool moved = false;
+  while (u == wk.beg + wk.w) { wk.k++; wk.beg += wk.w; wk.w = rz_end(L, wk.k) - wk.beg; wk.s0 = rz_s0(L, wk.k); moved = true; }
+  return moved;
+}
+// A: per slot one register, index << 16 | element (both below 65,536: the caller checks), in ell_chunk_rc's rotated order (lane-dependent: rotated here)
+template <class IT>
+__device__ __forceinline__ void rz_fill_a(const RzList<RZ_KA> &L, const IT *__restrict__ idx, const int lane, unsigned (&aR)[RZ_CAPA]) {
+  RzWalk wk = rz_walk0(L);
+  int r0 = wk.w > 0 ? lane % wk.w : 0;
+#pragma unroll
+  for (int g = 0; g < RZ_CAPA / RZ_U; g++) {
+    unsigned ai[RZ_U];
+#pragma unroll
+    for (int j = 0; j < RZ_U; j++) {
+      const int u = g * RZ_U + j;
+      aR[u] = (unsigned)lane; ai[j] = 0;
+      if (u < L.tot) {
+        if (rz_step(L, wk, u)) r0 = lane % wk.w;
+        int su = u - wk.beg + r0; su -= su >= wk.w ? wk.w : 0;
+        const int e = (wk.s0 + su) * WAVE + lane;
+        aR[u] = (unsigned)e; ai[j] = (unsigned)idx[e];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RZ_U; j++) aR[g * RZ_U + j] |= ai[j] << 16;
+  }
+}
+// P: value (gathered from the caller's array through the slot's source index, as the load phase does) and index, two indices to a register
+__device__ __forceinline__ int rz_pidx(const unsigned (&pI)[RZ_CAPP / 2], const int u) { return (u & 1) ? (int)(pI[u >> 1] >> 16) : (int)(pI[u >> 1] & 0xffffu); }
+// a packed register as the passes see it: opaque, or the LDS addresses derived from it are hoisted out of the pass loop -- three more registers per slot,
+// kept for ten passes (the kernel then needs 223 VGPRs instead of 168)
+__device__ __forceinline__ unsigned rz_opaque(unsigned r) { asm volatile("" : "+v"(r)); return r; }
+template <class IT>
+__device__ __forceinline__ void rz_fill_p(const RzList<RZ_KP> &L, const IT *__restrict__ idx, const int *__restrict__ src, const double *__restrict__ in, const int lane,
+                                          double (&pV)[RZ_CAPP], unsigned (&pI)[RZ_CAPP / 2]) {
+  RzWalk wk = rz_walk0(L);
+#pragma unroll
+  for (int g = 0; g < RZ_CAPP / RZ_U; g++) {
+    int sr[RZ_U]; unsigned ix[RZ_U];
+#pragma unroll
+    for (int j = 0; j < RZ_U; j++) {
+      const int u = g * RZ_U + j;
+      sr[j] = -1; ix[j] = 0;
+      if (u < L.tot) {
+        rz_step(L, wk, u);
+        const int e = (wk.s0 + u - wk.beg) * WAVE + lane;
+        sr[j] = src[e]; ix[j] = (unsigned)idx[e];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RZ_U; j++) pV[g * RZ_U + j] = in[max(sr[j], 0)];
+#pragma unroll
+    for (int j = 0; j < RZ_U; j++) { const int u = g * RZ_U + j; pV[u] = sr[j] >= 0 ? pV[u] : 0.0; }
+#pragma unroll
+    for (int j = 0; j < RZ_U; j += 2) pI[(g * RZ_U + j) >> 1] = ix[j] | (ix[j + 1] << 16);
+  }
+}
+// ell_chunk_rc over the wave's chunks of A: row norms into W in place (E, read by its own lane only), column atomics as there.  The maxima do not care
+// about the order; the products are the same.
+template <int NW>
+__device__ __forceinline__ void rz_pass_a(const RzList<RZ_KA> &L, const unsigned (&aR)[RZ_CAPA], const double *__restrict__ val, const double *din, double *colacc, double *W,
+                                          const int first, const int mpad, const int lane) {
+  auto e_of = [&](const int k) { const int i = (first + k * NW) * WAVE + lane; return (k < L.nk && i < mpad) ? W[i] : 0.0; };
+  double accs[RZ_KA];
+#pragma unroll
+  for (int q = 0; q < RZ_KA; q++) accs[q] = 0.0;
+  int k = 0, nxt = L.e0;
+  double acc = 0.0, ei = e_of(0);
+#pragma unroll
+  for (int g = 0; g < RZ_CAPA / RZ_U; g++) {
+    if (g * RZ_U < L.tot) {
+      double v[RZ_U], x[RZ_U]; unsigned ix[RZ_U];
+#pragma unroll
+      for (int j = 0; j < RZ_U; j++) { const unsigned r = rz_opaque(aR[g * RZ_U + j]); ix[j] = r >> 16; v[j] = fabs(val[r & 0xffffu]); x[j] = din[ix[j]]; }
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int j = 0; j < RZ_U; j++) {
+        const int u = g * RZ_U + j;
+        if (u < L.tot) {
+          while (u == nxt) { rz_put(accs, k, acc); k++; acc = 0.0; ei = e_of(k); nxt = rz_end(L, k); }
+          acc = fmax(acc, v[j] * x[j]);
+          if (v[j] != 0.0) __hip_atomic_fetch_max((lds_u64 *)(colacc + ix[j]), (unsigned long long)__double_as_longlong(v[j] * ei), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
+  }
+  rz_put(accs, k, acc);
+#pragma unroll
+  for (int q = 0; q < RZ_KA; q++) {
+    const int i = (first + q * NW) * WAVE + lane;
+    if (q < L.nk && i < mpad) { const double e = W[i]; W[i] = e * (1.0 / sqrt(limit_scaling(e * accs[q]))); }
+  }
+}
+// ell_chunk_mx over the wave's chunks of P: max_s |p| * in[idx] per chunk into out[k]
+__device__ __forceinline__ void rz_pass_p(const RzList<RZ_KP> &L, const double (&pV)[RZ_CAPP], const unsigned (&pI)[RZ_CAPP / 2], const double *in, double (&out)[RZ_KP]) {
+#pragma unroll
+  for (int q = 0; q < RZ_KP; q++) out[q] = 0.0;
+  int k = 0, nxt = L.e0;
+  double acc = 0.0;
+#pragma unroll
+  for (int g = 0; g < RZ_CAPP / RZ_U; g++) {
+    if (g * RZ_U < L.tot) {
+      double x[RZ_U];
+#pragma unroll
+      for (int j = 0; j < RZ_U; j += 2) { const unsigned r = rz_opaque(pI[(g * RZ_U + j) >> 1]); x[j] = in[r & 0xffffu]; x[j + 1] = in[r >> 16]; }
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int j = 0; j < RZ_U; j++) {
+        const int u = g * RZ_U + j;
+        if (u < L.tot) {
+          while (u == nxt) { rz_put(out, k, acc); k++; acc = 0.0; nxt = rz_end(L, k); }
+          acc = fmax(acc, fabs(pV[u]) * x[j]);
+        }
+      }
+    }
+  }
+  rz_put(out, k, acc);
+}
+// P <- c D P D from the registers: out[e] = p * (c * d_t * d_k), whole 512 B slots as ell_map_chunk stores them
+template <int NW>
+__device__ __forceinline__ void rz_write_p(const RzList<RZ_KP> &L, const double (&pV)[RZ_CAPP], const unsigned (&pI)[RZ_CAPP / 2], const double *D, double *out, const double c,
+                                           const int first, const int npad, const int lane) {
+  auto d_of = [&](const int k) { const int t = (first + k * NW) * WAVE + lane; return (k < L.nk && t < npad) ? D[t] : 0.0; };
+  RzWalk wk = rz_walk0(L);
+  double dj = d_of(0);
+#pragma unroll
+  for (int g = 0; g < RZ_CAPP / RZ_U; g++) {
+    if (g * RZ_U < L.tot) {
+      double x[RZ_U];
+#pragma unroll
+      for (int j = 0; j < RZ_U; j++) x[j] = D[rz_pidx(pI, g * RZ_U + j)];
+#pragma unroll
+      for (int j = 0; j < RZ_U; j++) {
+        const int u = g * RZ_U + j;
+        if (u < L.tot) {
+          if (rz_step(L, wk, u)) dj = d_of(wk.k);
+          out[(long)(wk.s0 + u - wk.beg) * WAVE + lane] = pV[u] * (c * dj * x[j]);
+        }
+      }
+    }
+  }
+}
+
 // out[e] = f(value, index) over the slots of one chunk, 8 / 4 / 2 / 1 slots per batch with all loads of a batch issued before the first use.
 // INDIRECT: the value is gathered from the caller's array through the slot's source index (-1 = padding)
 template <bool INDIRECT, int U, class F>

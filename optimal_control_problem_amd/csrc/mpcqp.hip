@@ -340,6 +340,7 @@ static int upload_onchip(mpcqp_handle *h, int cus) {
   const SetupShape &su = s.setup; DevRes &ds = h->dres_setup; DevOc &dd = h->doc_setup;
   ds = dr; dd = d;
   dd.a_lds = su.a_lds; dd.p_lds = su.p_lds; dd.ix16 = su.ix16; dd.zpad = su.zpad; dd.ixo_a = su.ixo_a; dd.ixo_p = su.ixo_p;
+  dd.no_ruiz_regs = h->knobs.no_ruiz_regs ? 1 : 0;
   ds.stage = su.stage;
   if (!s.split) return MPCQP_OK;
   if (s.oc8 && !s.vtiles && !s.a_assign.empty()) UP(upload(h, s.a_assign, &d.a_assign));

@@ -67,6 +67,16 @@ inline Ell build_ell(const std::vector<std::vector<EllEntry>> &rows, int pad4 = 
   return e;
 }
 
+// Set-up kernel of the two-kernel on-chip form: the Ruiz passes keep a wave's slots of A (indices) and of P (values and indices) in registers when the
+// wave's list fits these compile-time capacities (kernel_resident.hpp rz_list: the same arithmetic on the device).  The wave that starts at chunk
+// `first` owns chunks first, first + nw, ...; the north-star size has 18 - 19 slots of A in two or three chunks and up to 23 of P in two per wave.
+constexpr int RUIZ_REG_CHUNKS_A = 3, RUIZ_REG_SLOTS_A = 20, RUIZ_REG_CHUNKS_P = 2, RUIZ_REG_SLOTS_P = 24;
+inline bool ruiz_regs_fit(const std::vector<int> &chunk_off, int nchunks, int first, int nw, int max_chunks, int max_slots) {
+  int tot = 0;
+  for (int q = 0, ch = first; q < max_chunks && ch < nchunks; q++, ch += nw) tot += chunk_off[ch + 1] - chunk_off[ch];
+  return first + max_chunks * nw >= nchunks && tot <= max_slots;
+}
+
 enum { OP_DIAG = 0, OP_OFF = 1 };
 inline int pack_op(int kind, int src, int dst) { return kind | (src << 1) | (dst << 16); }
 

@@ -64,6 +64,7 @@ struct Knobs {
   // ---- two-kernel on-chip form
   int resume_rounds = 1;      // MPCQP_RESUME_ROUNDS=<0..8>: {re-factorisation, iteration} pairs queued behind a solve before the last pair
   bool no_ix16 = false;       // MPCQP_NO_IX16: set-up kernel without 16-bit index tables in LDS
+  bool no_ruiz_regs = false;  // MPCQP_NO_RUIZ_REGS=1: set-up kernel's Ruiz passes reload their fixed operands (indices, P's values) every pass instead of keeping them in registers
   long setup_cap = LONG_MIN;  // MPCQP_SETUP_CAP=<bytes>: LDS the set-up kernel's shape is fitted to, instead of a half or a third of a CU (LONG_MIN: not set)
   bool no_abalance = false;   // MPCQP_NO_ABALANCE: eight-wave iteration kernel takes A's row chunks round-robin instead of balanced by load batches
   bool no_touch = false;      // MPCQP_NO_TOUCH: no L2 touch by the idle waves during the backward chains (on-chip kernels)
@@ -102,6 +103,7 @@ struct Knobs {
     k.late = set("MPCQP_LATE");
     if (const char *e = getenv("MPCQP_RESUME_ROUNDS")) k.resume_rounds = std::max(0, std::min(atoi(e), 8));
     k.no_ix16 = set("MPCQP_NO_IX16");
+    k.no_ruiz_regs = one("MPCQP_NO_RUIZ_REGS") == 2;
     if (const char *e = getenv("MPCQP_SETUP_CAP")) k.setup_cap = atol(e);
     k.no_abalance = set("MPCQP_NO_ABALANCE");
     k.no_touch = set("MPCQP_NO_TOUCH");
