@@ -146,6 +146,25 @@ int mpcqp_keep_workspace(mpcqp_handle *h, int enable);
 int mpcqp_update_vectors(mpcqp_handle *h, const double *q, long strideq, const double *l, long stridel,
                          const double *u, long strideu, int mem);
 
+/* Kept workspace, new matrices -- what the reference's private, never-called CuCaQP::updateHessianMatrix / updateLinearConstraintsMatrix
+ * (CuCaQP.cpp:106-116,129-140) map to through OsqpEigen: OSQP's osqp_update_data_mat.  The scaling D, E, c of the handle's last full
+ * set-up (mpcqp_update + mpcqp_solve) and every instance's current rho stay; the new P, q, A, l, u are scaled with them (c D P D, c D q,
+ * E A D, E l, E u) and the KKT matrix is factorised again.  The next mpcqp_solve skips the equilibration passes only.  Every instance is
+ * re-factorised: an instance that was MPCQP_NON_CVX gets a fresh verdict from its new matrices.  x / y start from zero, or from
+ * mpcqp_warm_start when settings.warm_start is set.  Strides, mem, borrowing rules and argument checks as in mpcqp_update.
+ * Call order: mpcqp_keep_workspace(h, 1) -> mpcqp_update -> mpcqp_solve -> { mpcqp_update_matrices | mpcqp_update_vectors -> mpcqp_solve }*;
+ * mpcqp_update returns to a full set-up (and to a new scaling); mpcqp_update_vectors behind a matrices solve works on the factor that
+ * solve left; mpcqp_update_vectors between mpcqp_update_matrices and its solve only replaces q, l, u of that solve.
+ * An instance with l_i > u_i on some row is refused as always (MPCQP_UNSOLVED, NaN), for that solve only.  An instance that the last
+ * full set-up refused for that reason has its D, E, c all the same -- the bounds take no part in the scaling -- and is solved here like
+ * every other instance once its bounds are in order.
+ * MPCQP_ERR_STATE without mpcqp_keep_workspace(h, 1) or without a kept solve.  MPCQP_ERR_LIMIT, at this call, on a handle that does not run
+ * the two-kernel on-chip form (streaming, LDS-resident, global-block, MPCQP_OC_MONO, the tile experiments): the handle stays as it was, and
+ * the caller falls back to mpcqp_update.  Reduced handles forward to their inner handle. */
+int mpcqp_update_matrices(mpcqp_handle *h, const double *P, long strideP, const double *q, long strideq,
+                          const double *A, long strideA, const double *l, long stridel,
+                          const double *u, long strideu, int mem);
+
 /* Per-instance starting rho for the following solves (rho0 [batch]; entries <= 0 mean settings.rho; NULL returns to
  * settings.rho for all).  A kept OSQP workspace carries its adapted rho from one problem to the next
  * (osqp_update_* do not reset it) -- the behaviour the reference's unused update* members would have had

@@ -93,17 +93,26 @@ class BatchQP:
             pass
 
     def update(self, P, q, A, l, u):
+        self._update(_lib.lib().mpcqp_update, P, q, A, l, u)
+
+    def update_matrices(self, P, q, A, l, u):
+        """new P, q, A, l, u on the kept scaling (OSQP's osqp_update_data_mat): D, E, c of the last full update() + solve() and every instance's rho stay,
+        the next solve() scales the new data with them and re-factorises.  Needs keep_workspace() and a previous update() + solve(); raises MpcqpError
+        with code ERR_LIMIT on a handle that does not run the two-kernel on-chip form (fall back to update())"""
+        self._update(_lib.lib().mpcqp_update_matrices, P, q, A, l, u)
+
+    def _update(self, entry, P, q, A, l, u):
         B = self.batch
         items = [_ptr_stride(P, self.nnzP, B, "P"), _ptr_stride(q, self.n, B, "q"), _ptr_stride(A, self.nnzA, B, "A"),
                  _ptr_stride(l, self.m, B, "l"), _ptr_stride(u, self.m, B, "u")]
         mems = {it[2] for it in items if it[2] is not None}
         if len(mems) != 1:
             raise ValueError("all of P, q, A, l, u must live in the same memory space")
-        self._keep = [it[3] for it in items]
         args = []
         for ptr, stride, _, _ in items:
             args += [ptr, stride]
-        _lib.check(_lib.lib().mpcqp_update(self._h, *args, mems.pop()))
+        _lib.check(entry(self._h, *args, mems.pop()))
+        self._keep = [it[3] for it in items]
 
     def set_dispatch_hint(self, enable=True):
         """longest-first dispatch order from the previous solve's iteration counts (on by default; changes no result)"""

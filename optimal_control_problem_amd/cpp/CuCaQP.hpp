@@ -63,6 +63,10 @@ class CuCaQP {
   // also where initSolver creates a new handle.  getPolishStatus: OSQP's info.status_polish (MPCQP_POLISH_*: 1 polished, 0 not performed, -1 candidate
   // rejected, -2 linear system error) of instance 0, getPolishStatusVector: of every instance.
   void setPolish(bool polish) { polish_ = polish; }
+  // opt-in (default off): a solve() after updateHessianMatrix / updateLinearConstraintsMatrix keeps the scaling D, E, c of the last initSolver() + solve()
+  // and every instance's rho, scales the new data with them and re-factorises (mpcqp_update_matrices = OSQP's osqp_update_data_mat, what OsqpEigen makes
+  // of the reference's CuCaQP.cpp:106-116,129-140).  A handle that answers MPCQP_ERR_LIMIT runs the full set-up instead, silently.
+  void setKeepScaling(bool keep) { keepScaling_ = keep; }
   int getPolishStatus() const { return polishStatus_.empty() ? MPCQP_POLISH_NOT_PERFORMED : polishStatus_[0]; }
   const std::vector<int> &getPolishStatusVector() const { return polishStatus_; }
 
@@ -109,7 +113,7 @@ class CuCaQP {
 
   // The reference's private update* members (CuCaQP.h:93-101, CuCaQP.cpp:106-161; never called there).  Vectors go through the
   // kept workspace (mpcqp_update_vectors = OSQP's osqp_update_data_vec: scaling, factorisation and rho stay, the next solve()
-  // skips the setup); a matrix update falls back to a full setup at the next solve().
+  // skips the setup); a matrix update falls back to a full setup at the next solve(), unless setKeepScaling(true) sends it through mpcqp_update_matrices.
   bool updateHessianMatrix(const CscView &P) {
     if (!isInitialized_) { std::cerr << "Error: Solver not initialized. Call initSolver() first." << std::endl; return false; }
     const bool same = samePattern(P, Pp_, Pi_);
@@ -143,7 +147,7 @@ class CuCaQP {
       rc = presolve_ ? mpcqp_create_presolved(numOfVariables_, numOfConstraints_, batch_, Pp_.data(), Pi_.data(), Ap_.data(), Ai_.data(), l_.data(), numOfConstraints_,
                                               u_.data(), numOfConstraints_, MPCQP_MEM_HOST, &settings_, &handle_, &nfixed_)
                      : mpcqp_create(numOfVariables_, numOfConstraints_, batch_, Pp_.data(), Pi_.data(), Ap_.data(), Ai_.data(), &settings_, &handle_);
-      patternChanged_ = dirty_ = false;
+      patternChanged_ = dirty_ = false; noMatrixUpdates_ = false;
       kept_ = rc == MPCQP_OK && mpcqp_keep_workspace(handle_, 1) == MPCQP_OK;   // not on the streaming kernel variant
     }
     vectorsOnly_ = matricesDirty_ = false; solvedOnce_ = false;
@@ -162,6 +166,15 @@ class CuCaQP {
     int rc = MPCQP_OK;
     if (vectorsOnly_ && kept_ && solvedOnce_ && !matricesDirty_)
       rc = mpcqp_update_vectors(handle_, q_.data(), numOfVariables_, l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
+    else if (matricesDirty_ && keepScaling_ && kept_ && solvedOnce_ && !noMatrixUpdates_) {
+      rc = mpcqp_update_matrices(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
+                                 l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
+      if (rc == MPCQP_ERR_LIMIT) {      // (this handle's kernel family has no such entry: the full set-up from now on)
+        noMatrixUpdates_ = true;
+        rc = mpcqp_update(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
+                          l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
+      }
+    }
     else if (vectorsOnly_ || matricesDirty_)
       rc = mpcqp_update(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
                         l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
@@ -296,6 +309,7 @@ class CuCaQP {
   int batch_ = 1, numOfVariables_ = 0, numOfConstraints_ = 0;
   bool isInitialized_ = false, verbose_ = false, patternChanged_ = true, dirty_ = false;
   bool kept_ = false, vectorsOnly_ = false, matricesDirty_ = false, solvedOnce_ = false, presolve_ = false, polish_ = false, polishOn_ = false;
+  bool keepScaling_ = false, noMatrixUpdates_ = false;
   int nfixed_ = 0;
   mpcqp_settings settings_;
   mpcqp_handle *handle_ = nullptr;

@@ -69,6 +69,9 @@ class StageSQP {
 
   // option polish_qp (default off, as the reference leaves OSQP's `polishing` off, :80-85): every QP of the loop is polished (mpcqp_set_polish)
   void setPolishQP(bool on) { check(mpcqp_set_polish(qp_, on ? 1 : 0, 0.0, -1), "mpcqp_set_polish"); }
+  // option keep_scaling (default off): the first QP of the solver's life runs the full set-up, every later one keeps its scaling D, E, c and the
+  // instances' rho and only re-factorises (mpcqp_update_matrices = OSQP's osqp_update_data_mat); a handle that answers MPCQP_ERR_LIMIT goes on with full set-ups
+  void setKeepScaling(bool on) { keepScaling_ = on; if (on) check(mpcqp_keep_workspace(qp_, 1), "mpcqp_keep_workspace"); }
   void setTolerance(double tol) { tol_ = tol; }                   // 0 (default) = the reference's fixed iteration count
   int iterationsDone() const { return iterationsDone_; }
 
@@ -79,7 +82,16 @@ class StageSQP {
     up(lbx_, arg.lbx); up(ubx_, arg.ubx); up(lbg_, arg.lbg); up(ubg_, arg.ubg); up(p_, arg.p);
     for (int i = 0; i < stepNum_; i++) {
       check(mpcqp_stage_eval(ocp_, batch_, p_, x_, lbx_, ubx_, lbg_, ubg_, dP_, dq_, dA_, dl_, du_, nullptr), "mpcqp_stage_eval");
-      check(mpcqp_update(qp_, dP_, nnzP(), dq_, n(), dA_, nnzA(), dl_, m(), du_, m(), MPCQP_MEM_DEVICE), "mpcqp_update");
+      int rc = MPCQP_ERR_LIMIT;
+      if (keepScaling_ && scaled_) {
+        rc = mpcqp_update_matrices(qp_, dP_, nnzP(), dq_, n(), dA_, nnzA(), dl_, m(), du_, m(), MPCQP_MEM_DEVICE);
+        if (rc == MPCQP_ERR_LIMIT) keepScaling_ = false;            // for good: this handle's kernel family has no such entry
+        else check(rc, "mpcqp_update_matrices");
+      }
+      if (rc == MPCQP_ERR_LIMIT) {
+        check(mpcqp_update(qp_, dP_, nnzP(), dq_, n(), dA_, nnzA(), dl_, m(), du_, m(), MPCQP_MEM_DEVICE), "mpcqp_update");
+        scaled_ = true;
+      }
       check(mpcqp_solve(qp_, nullptr), "mpcqp_solve");
       check(mpcqp_get(qp_, dw_, nullptr, nullptr, nullptr, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
       check(mpcqp_stage_step(ocp_, batch_, alpha_, dw_, x_, tol_ > 0.0 ? g_ : nullptr, nullptr, nullptr), "mpcqp_stage_step");
@@ -112,6 +124,7 @@ class StageSQP {
   void up(double *dst, const std::vector<double> &src) { if (!src.empty()) hip(hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice)); }
 
   int batch_, stepNum_; double alpha_; double tol_ = 0.0; int iterationsDone_ = 0;
+  bool keepScaling_ = false, scaled_ = false;                     // (scaled_: a full set-up has run on the handle)
   std::vector<double> stepMax_;
   int dims_[8] = {0};
   mpcqp_stage *ocp_ = nullptr; mpcqp_handle *qp_ = nullptr;

@@ -15,6 +15,7 @@ MPCQP_HIDDEN const void *mpcqp_kernel_oc_mono_r0(int nw, int ng, int nh, bool ti
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_mono_r1(int nw, int ng, int nh, bool tiles);
 // kernel_oc_split.hpp: the on-chip mode as set-up + iteration kernels
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_setup(int nw, bool hub, bool reuse);
+MPCQP_HIDDEN const void *mpcqp_kernel_oc_rescale(int nw, bool hub);            // kernel_oc_rescale.hpp: new matrices, kept D, E, c and rho (mpcqp_update_matrices)
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm(int nw, int ng, int nh);        // leaves for a re-factorisation
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_rf(int nw, int ng, int nh);
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_p4(int rf);                      // four waves, two twisted pairs of chains (dissected order)

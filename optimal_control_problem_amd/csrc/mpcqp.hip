@@ -69,6 +69,7 @@ struct mpcqp_handle {
   double *dP = nullptr, *dq = nullptr, *dA = nullptr, *dl = nullptr, *du = nullptr;  // owned copies (host-memory updates)
   double *dx0 = nullptr, *dy0 = nullptr, *drho0 = nullptr;
   bool keep = false, have_factor = false, reuse_next = false;
+  bool rescale_next = false, rescale_done = false;   // mpcqp_update_matrices: solves scale the data with the kept D, E, c and re-factorise; one has run since the call
   int *order[2] = {nullptr, nullptr}; int order_cur = -1; bool lpt = true; hipEvent_t ev_order = nullptr;   // dispatch hint, double-buffered
   static constexpr int NPIPE = 8;
   hipStream_t pipe[NPIPE] = {};               // mpcqp_solve_host: compute streams, one per slice in flight
@@ -146,6 +147,13 @@ static const void *res_kernel_of(const mpcqp_handle *h, bool reuse) {
 }
 // the two kernels of the on-chip mode (kernel_oc_split.hpp): CuCaQP::initSolver and CuCaQP::solve
 static const void *oc_setup_of(const mpcqp_handle *h, bool reuse) { return mpcqp_kernel_oc_setup(h->sel.setup.nw, h->sel.ocplan.has_hub != 0, reuse); }
+// ... and the kernel that takes the set-up's place after mpcqp_update_matrices (kernel_oc_rescale.hpp): in the set-up's launch shape
+static const void *oc_rescale_of(const mpcqp_handle *h) { return mpcqp_kernel_oc_rescale(h->sel.setup.nw, h->sel.ocplan.has_hub != 0); }
+// which handles mpcqp_update_matrices takes: the two-kernel on-chip form without the tile experiment
+static bool takes_matrix_updates(const mpcqp_handle *h) {
+  const Selection &s = h->sel;
+  return s.waves > 0 && s.oc && s.split && !s.tiles && !s.vtiles && oc_rescale_of(h) != nullptr;
+}
 static const void *oc_admm_of(const mpcqp_handle *h, bool rf = false) {
   const Selection &s = h->sel;
   const int nw = s.oc8 ? 8 : 4, ng = s.oc_ng(), nh = s.oc_nh();
@@ -186,7 +194,7 @@ static int launch_oc_split(mpcqp_handle *h, DevIO &io, int count, bool reuse, hi
   void *argr[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&docr};
   void *sargs[] = {(void *)&h->dp, (void *)&h->dres_setup, (void *)&h->st, (void *)&io, (void *)&docs0};
   void *sargr[] = {(void *)&h->dp, (void *)&h->dres_setup, (void *)&h->st, (void *)&io, (void *)&docsr};
-  HIPCHK(hipLaunchKernel(oc_setup_of(h, reuse), grid, block_s, sargs, lds_setup, s));
+  HIPCHK(hipLaunchKernel(io.reuse == 2 ? oc_rescale_of(h) : oc_setup_of(h, reuse), grid, block_s, sargs, lds_setup, s));      // (DevIO.reuse 2: new matrices on the kept scaling)
   if (after_setup) HIPCHK(hipEventRecord(after_setup, s));
   const bool rho_updates = h->st.adaptive_rho != 0;
   args[3] = io_of();
@@ -378,14 +386,14 @@ static int prepare_kernels(mpcqp_handle *h) {
     // MaxDynamicSharedMemorySize is a property of the kernel function, shared by every handle that launches it: keep a running
     // maximum per function so that a later handle with a smaller footprint never lowers the limit under an earlier one
     static std::mutex mu; static std::map<std::pair<const void *, int>, long> limit;   // (function, device)
-    const void *fns[4] = {res_kernel_of(h, false), res_kernel_of(h, true), nullptr, nullptr};
+    const void *fns[5] = {res_kernel_of(h, false), res_kernel_of(h, true), nullptr, nullptr, nullptr};
     if (s.waves == 0) fns[0] = fns[1] = s.stream_pd8 ? (const void *)mpcqp_admm_kernel<8> : (const void *)mpcqp_admm_kernel<4>;
-    if (s.split) { fns[0] = oc_setup_of(h, false); fns[1] = oc_setup_of(h, true); fns[2] = oc_admm_of(h, false); fns[3] = oc_admm_of(h, true); }
+    if (s.split) { fns[0] = oc_setup_of(h, false); fns[1] = oc_setup_of(h, true); fns[2] = oc_admm_of(h, false); fns[3] = oc_admm_of(h, true); fns[4] = oc_rescale_of(h); }
     std::lock_guard<std::mutex> lock(mu);
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < 5; k++) {
       const void *fn = fns[k];
       if (!fn) continue;
-      const long want_lds = (s.split && k < 2) ? s.setup.lds : s.lds;
+      const long want_lds = (s.split && (k < 2 || k == 4)) ? s.setup.lds : s.lds;
       long &cur = limit[{fn, h->device}];
       if (want_lds <= cur) continue;
       if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want_lds) != hipSuccess)
@@ -626,13 +634,14 @@ int mpcqp_create_presolved(int n, int m, int batch, const int *Pp, const int *Pi
 // the solve of a reduced handle: substitute the fixed variables, hand the smaller QP to the inner handle, expand its result
 static int solve_reduced(mpcqp_handle *h, hipStream_t s) {
   mpcqp_handle *in = h->inner; const DevRed &d = h->dred;
-  const bool vectors = h->reuse_next;
+  const bool vectors = h->reuse_next, matrices = h->rescale_next;
   // the presolve overwrites the reduced arrays the previous solve of this handle read: if that one ran on another stream, wait for it
   if (h->solved && h->last_stream != s) { HIPCHK(hipEventRecord(h->ev0r, h->last_stream)); HIPCHK(hipStreamWaitEvent(s, h->ev0r, 0)); }
   hipLaunchKernelGGL(mpcqp_presolve_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io, vectors ? 1 : 0);
   HIPCHK(hipGetLastError());
   int rc;
   if (vectors) rc = mpcqp_update_vectors(in, d.qr, d.nr, d.lr, d.mr, d.ur, d.mr, MPCQP_MEM_DEVICE);
+  else if (matrices) rc = mpcqp_update_matrices(in, d.Pr, d.nnzPr, d.qr, d.nr, d.Ar, d.nnzAr, d.lr, d.mr, d.ur, d.mr, MPCQP_MEM_DEVICE);
   else rc = mpcqp_update(in, d.Pr, d.nnzPr, d.qr, d.nr, d.Ar, d.nnzAr, d.lr, d.mr, d.ur, d.mr, MPCQP_MEM_DEVICE);
   if (rc) return rc;
   if (h->st.warm_start && h->io.x0 && h->io.y0) {
@@ -645,7 +654,7 @@ static int solve_reduced(mpcqp_handle *h, hipStream_t s) {
   hipLaunchKernelGGL(mpcqp_postsolve_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io, in->ox, in->oy, in->oz, in->ostatus, in->oiters, in->oinfo,
                      h->ox, h->oy, h->oz, h->ostatus, h->oiters, h->oinfo);
   HIPCHK(hipGetLastError());
-  h->last_stream = s; h->solved = true; h->have_factor = h->keep; h->reuse_next = false;
+  h->last_stream = s; h->solved = true; h->have_factor = h->keep; h->reuse_next = false; h->rescale_next = false;
   return MPCQP_OK;
 }
 
@@ -664,9 +673,9 @@ static int stage(mpcqp_handle *h, double **own, const double *src, long stride, 
   return MPCQP_OK;
 }
 
-int mpcqp_update(mpcqp_handle *h, const double *P, long sP, const double *q, long sq, const double *A, long sA,
-                 const double *l, long sl, const double *u, long su, int mem) {
-  if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+// what mpcqp_update and mpcqp_update_matrices share: the argument checks, and the five arrays borrowed (device memory) or copied into the handle's own buffers
+static int set_problem_data(mpcqp_handle *h, const double *P, long sP, const double *q, long sq, const double *A, long sA,
+                            const double *l, long sl, const double *u, long su, int mem) {
   if (!q || (h->sel.plan.nnzP_in > 0 && !P) || (h->sel.plan.nnzA_in > 0 && !A) || (h->m > 0 && (!l || !u))) return fail(MPCQP_ERR_ARG, "null data pointer");
   if (sP < 0 || sq < 0 || sA < 0 || sl < 0 || su < 0) return fail(MPCQP_ERR_ARG, "negative stride");
   if ((sP && sP < h->sel.plan.nnzP_in) || (sq && sq < h->n) || (sA && sA < h->sel.plan.nnzA_in) || (sl && sl < h->m) || (su && su < h->m))
@@ -684,7 +693,26 @@ int mpcqp_update(mpcqp_handle *h, const double *P, long sP, const double *q, lon
     if ((rc = stage(h, &h->dl, l ? l : q, sl, h->m, &io.l, &io.sl))) return rc;
     if ((rc = stage(h, &h->du, u ? u : q, su, h->m, &io.u, &io.su))) return rc;
   } else return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
-  h->have_data = true; h->reuse_next = false;
+  return MPCQP_OK;
+}
+
+int mpcqp_update(mpcqp_handle *h, const double *P, long sP, const double *q, long sq, const double *A, long sA,
+                 const double *l, long sl, const double *u, long su, int mem) {
+  if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+  if (int rc = set_problem_data(h, P, sP, q, sq, A, sA, l, sl, u, su, mem)) return rc;
+  h->have_data = true; h->reuse_next = false; h->rescale_next = false;
+  return MPCQP_OK;
+}
+
+int mpcqp_update_matrices(mpcqp_handle *h, const double *P, long sP, const double *q, long sq, const double *A, long sA,
+                          const double *l, long sl, const double *u, long su, int mem) {
+  if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+  if (!h->keep || !h->have_factor)
+    return fail(MPCQP_ERR_STATE, "mpcqp_update_matrices needs mpcqp_keep_workspace(h, 1) and a completed mpcqp_update + mpcqp_solve before it");
+  if (!takes_matrix_updates(h->inner ? h->inner : h))
+    return fail(MPCQP_ERR_LIMIT, "mpcqp_update_matrices: this handle does not run the two-kernel on-chip form (use mpcqp_update)");
+  if (int rc = set_problem_data(h, P, sP, q, sq, A, sA, l, sl, u, su, mem)) return rc;
+  h->reuse_next = false; h->rescale_next = true; h->rescale_done = false;
   return MPCQP_OK;
 }
 
@@ -714,12 +742,12 @@ int mpcqp_keep_workspace(mpcqp_handle *h, int enable) {
     const int rc = mpcqp_keep_workspace(h->inner, enable);
     if (rc) return rc;
     h->keep = enable != 0;
-    if (!h->keep) { h->have_factor = false; h->reuse_next = false; }
+    if (!h->keep) { h->have_factor = false; h->reuse_next = false; h->rescale_next = false; }
     return MPCQP_OK;
   }
   if (enable && h->sel.waves == 0) return fail(MPCQP_ERR_LIMIT, "the streaming kernel variant does not keep its workspace");
   h->keep = enable != 0;
-  if (!h->keep) { h->have_factor = false; h->reuse_next = false; }
+  if (!h->keep) { h->have_factor = false; h->reuse_next = false; h->rescale_next = false; }
   return MPCQP_OK;
 }
 
@@ -740,7 +768,8 @@ int mpcqp_update_vectors(mpcqp_handle *h, const double *q, long sq, const double
     if ((rc = stage(h, &h->dl, l ? l : q, sl, h->m, &io.l, &io.sl))) return rc;
     if ((rc = stage(h, &h->du, u ? u : q, su, h->m, &io.u, &io.su))) return rc;
   } else return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
-  h->reuse_next = true;
+  // (between mpcqp_update_matrices and its solve: that solve scales these vectors with the rest; behind it, the factor it left is kept)
+  if (!(h->rescale_next && !h->rescale_done)) { h->reuse_next = true; h->rescale_next = false; }
   return MPCQP_OK;
 }
 
@@ -765,7 +794,7 @@ int mpcqp_solve(mpcqp_handle *h, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   if (h->inner) return solve_reduced(h, s);
   DevIO io = io_of_handle(h);
-  io.reuse = h->reuse_next ? 1 : 0;
+  io.reuse = h->rescale_next ? 2 : h->reuse_next ? 1 : 0;
   io.order = (h->lpt && h->order_cur >= 0) ? h->order[h->order_cur] : nullptr;
   if (io.order && h->last_stream != s) HIPCHK(hipStreamWaitEvent(s, h->ev_order, 0));    // the hint was written on another stream
   HIPCHK(hipEventRecord(h->ev0, s));
@@ -777,7 +806,7 @@ int mpcqp_solve(mpcqp_handle *h, void *stream) {
     HIPCHK(hipEventRecord(h->ev_order, s));
     h->order_cur = nxt;
   }
-  h->last_stream = s; h->solved = true; h->have_factor = h->keep;
+  h->last_stream = s; h->solved = true; h->have_factor = h->keep; h->rescale_done = h->rescale_next;
   return MPCQP_OK;
 }
 
@@ -849,7 +878,7 @@ int mpcqp_solve_host(mpcqp_handle *h, const double *P, long sP, const double *q,
   HIPCHK(hipStreamSynchronize(h->pipe_copy));
   for (int i = 0; i < ns; i++) HIPCHK(hipStreamSynchronize(h->pipe[i]));
   h->io.P = io.P; h->io.sP = io.sP; h->io.q = io.q; h->io.sq = io.sq; h->io.A = io.A; h->io.sA = io.sA; h->io.l = io.l; h->io.sl = io.sl; h->io.u = io.u; h->io.su = io.su;
-  h->have_data = true; h->reuse_next = false; h->solved = true; h->have_factor = h->keep; h->last_stream = nullptr; h->order_cur = -1;
+  h->have_data = true; h->reuse_next = false; h->rescale_next = false; h->solved = true; h->have_factor = h->keep; h->last_stream = nullptr; h->order_cur = -1;
   return MPCQP_OK;
 }
 

@@ -41,6 +41,7 @@ class CuCaQP:
         self._kept = False
         self._polish = self._polish_applied = False
         self._vectors_dirty = self._matrices_dirty = self._solved_once = False
+        self._keep_scaling = self._no_matrix_updates = False
 
     # -- dimensions (CuCaQP.cpp:23-41)
     def setDimension(self, numOfVariables, numOfConstraints):
@@ -90,6 +91,13 @@ class CuCaQP:
         """extension: per-instance starting rho for the next solves (a kept OSQP workspace carries its adapted rho over);
         None returns to the configured rho"""
         self._rho0 = None if rho0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rho0, np.float64), (self.batch,)))
+
+    def setKeepScaling(self, keep):
+        """extension (off by default): a solve() after updateHessianMatrix / updateLinearConstraintsMatrix keeps the scaling D, E, c of the last
+        initSolver() + solve() and every instance's rho, scales the new data with them and re-factorises (mpcqp_update_matrices = OSQP's
+        osqp_update_data_mat, what OsqpEigen makes of the reference's CuCaQP.cpp:106-116,129-140) instead of running a full set-up.  A handle that
+        does not take such updates runs the full set-up, silently."""
+        self._keep_scaling = bool(keep)
 
     def setSolverSetting(self, **kw):
         """extension: any field of mpcqp_settings (rho, sigma, alpha, scaling, adaptive_rho, ...)"""
@@ -157,7 +165,8 @@ class CuCaQP:
     # -- the reference's private update* members (CuCaQP.cpp:106-161; never called there).  Here they work, with the same
     # bookkeeping as the C++ facade (cpp/CuCaQP.hpp: vectorsOnly_ / matricesDirty_ / solvedOnce_): the next solve() sends the new
     # data -- vectors alone through the kept workspace (mpcqp_update_vectors: scaling, factorisation and rho stay) when a solve
-    # has happened on it and the matrices are unchanged, everything through a full mpcqp_update otherwise.  A matrix with another
+    # has happened on it and the matrices are unchanged, everything through a full mpcqp_update otherwise (or, with setKeepScaling(True),
+    # through mpcqp_update_matrices: new matrices on the kept scaling).  A matrix with another
     # sparsity pattern needs a new plan: the updater refuses it and asks for initSolver().
     def _same_pattern(self, old, new):
         return old is not None and np.array_equal(old[0], new[0]) and np.array_equal(old[1], new[1])
@@ -236,6 +245,7 @@ class CuCaQP:
                                    self._A[0], self._A[1], device=self._device, **kw)
                 self._pattern_key = key
                 self._kept = False
+                self._no_matrix_updates = False
                 self._polish_applied = False
                 try:
                     self._qp.keep_workspace(True); self._kept = True
@@ -257,10 +267,19 @@ class CuCaQP:
         if not self.isInitialized_:
             return _err("Solver not initialized. Call initSolver() first.")
         try:
+            data = (self._P[2], self.gradient, self._A[2], self.lowerBound, self.upperBound)
             if self._vectors_dirty and self._kept and self._solved_once and not self._matrices_dirty:
                 self._qp.update_vectors(self.gradient, self.lowerBound, self.upperBound)
+            elif self._matrices_dirty and self._keep_scaling and self._kept and self._solved_once and not self._no_matrix_updates:
+                try:
+                    self._qp.update_matrices(*data)
+                except _lib.MpcqpError as e:
+                    if e.code != _lib.ERR_LIMIT:
+                        raise
+                    self._no_matrix_updates = True          # (this handle's kernel family has no such entry: the full set-up from now on)
+                    self._qp.update(*data)
             elif self._vectors_dirty or self._matrices_dirty:
-                self._qp.update(self._P[2], self.gradient, self._A[2], self.lowerBound, self.upperBound)
+                self._qp.update(*data)
             self._vectors_dirty = self._matrices_dirty = False
             self._qp.solve()
             self._solved_once = True

@@ -18,6 +18,7 @@ import time
 
 import numpy as np
 
+from . import _lib
 from .cucaqp import CuCaQP
 
 
@@ -138,18 +139,23 @@ class DeviceSQPOptimizationSolver:
         # q, l, u are replaced on the kept workspace (mpcqp_update_vectors): no equilibration, no factorisation.  The caller
         # asserts the matrices are constant, exactly as with OSQP's osqp_update_data_vec.
         self.constant_matrices = bool(options.get("constant_matrices", False))
+        # extension (opt-in): P and A change with every linearisation, their scaling need not -- the first QP of the solver's life runs the full
+        # set-up, every later one keeps its D, E, c and the instances' rho and only re-factorises (mpcqp_update_matrices = OSQP's osqp_update_data_mat).
+        # A handle that does not take such updates (MPCQP_ERR_LIMIT) goes on with full set-ups.
+        self.keep_scaling = bool(options.get("keep_scaling", False))
         self.sqp_tol = float(options.get("sqp_tol", 0.0) or 0.0)      # opt-in convergence stop, see the module docstring
         # extension: OSQP's `polishing` on every QP of the loop (mpcqp_set_polish); the reference leaves it off (:80-85), and so does the default
         self.polish_qp = bool(options.get("polish_qp", False))
         self.iterations_done = 0
         self.step_max = None
         self._kept = False
+        self._scaled = False                             # keep_scaling: a full set-up has run on the handle
         self.batch = int(batch)
         self.ev = StageEvaluator(nlp, device=device, codegen=codegen)
         # reference SQPOptimizationSolver.cpp:80-85
         self.qp = BatchQP(self.ev.n, self.ev.m, self.batch, self.ev.Pp, self.ev.Pi, self.ev.Ap, self.ev.Ai,
                           eps_abs=1e-3, eps_rel=1e-3, max_iter=10000, warm_start=1 if self.warm_start_admm else 0, device=device)
-        if self.constant_matrices:
+        if self.constant_matrices or self.keep_scaling:
             self.qp.keep_workspace(True)
         if self.polish_qp:
             self.qp.set_polish(True)
@@ -190,9 +196,18 @@ class DeviceSQPOptimizationSolver:
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
             if self.constant_matrices and self._kept:
                 self.qp.update_vectors(self.ls["q"], self.ls["l"], self.ls["u"])
+            elif self.keep_scaling and self._scaled:
+                try:
+                    self.qp.update_matrices(self.ls["P"], self.ls["q"], self.ls["A"], self.ls["l"], self.ls["u"])
+                except _lib.MpcqpError as e:
+                    if e.code != _lib.ERR_LIMIT:
+                        raise
+                    self.keep_scaling = False            # for good: this handle's kernel family has no such entry
+                    self.qp.update(self.ls["P"], self.ls["q"], self.ls["A"], self.ls["l"], self.ls["u"])
             else:
                 self.qp.update(self.ls["P"], self.ls["q"], self.ls["A"], self.ls["l"], self.ls["u"])
                 self._kept = self.constant_matrices
+                self._scaled = True
             if self.warm_start_admm:
                 if self._have_start:
                     # after x += alpha * dx the remaining step is (1 - alpha) * dx; duals carry over
