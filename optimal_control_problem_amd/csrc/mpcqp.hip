@@ -683,7 +683,10 @@ static int set_problem_data(mpcqp_handle *h, const double *P, long sP, const dou
   HIPCHK(hipSetDevice(h->device));
   DevIO &io = h->io;
   if (mem == MPCQP_MEM_DEVICE) {
-    io.P = P; io.sP = sP; io.q = q; io.sq = sq; io.A = A; io.sA = sA; io.l = l; io.sl = sl; io.u = u; io.su = su;
+    // (an array that may be NULL because it is empty is pointed at q, as on the host path: the gathers of the set-up kernels load element 0 for a phantom slot
+    // before they discard it -- gather8, rz_fill_p -- and must find memory there)
+    io.P = P ? P : q; io.sP = P ? sP : 0; io.q = q; io.sq = sq; io.A = A ? A : q; io.sA = A ? sA : 0;
+    io.l = l ? l : q; io.sl = l ? sl : 0; io.u = u ? u : q; io.su = u ? su : 0;
   } else if (mem == MPCQP_MEM_HOST) {
     if (h->last_stream || h->solved) HIPCHK(hipStreamSynchronize(h->last_stream));
     int rc;
@@ -760,7 +763,7 @@ int mpcqp_update_vectors(mpcqp_handle *h, const double *q, long sq, const double
   HIPCHK(hipSetDevice(h->device));
   DevIO &io = h->io;
   if (mem == MPCQP_MEM_DEVICE) {
-    io.q = q; io.sq = sq; io.l = l; io.sl = sl; io.u = u; io.su = su;
+    io.q = q; io.sq = sq; io.l = l ? l : q; io.sl = l ? sl : 0; io.u = u ? u : q; io.su = u ? su : 0;      // (m = 0: as in set_problem_data)
   } else if (mem == MPCQP_MEM_HOST) {
     if (h->last_stream || h->solved) HIPCHK(hipStreamSynchronize(h->last_stream));
     int rc;
