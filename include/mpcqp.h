@@ -343,6 +343,45 @@ int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *
 int mpcqp_stage_step(mpcqp_stage *s, int batch, double alpha, const double *dw, double *x, double *step_max,
                      const int *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Local-system evaluation on device for a general (non-stage) NLP.
+ *
+ * The reference hands ANY problem to its SQP: cost and constraints are arbitrary SX over the whole decision vector, CasADi
+ * differentiates them with their true sparsity -- hessian(f, w), jacobian([p; x; g], w), w = [p; x] (reference
+ * src/sqp_solver/SQPOptimizationSolver.cpp:47-77) -- and getLocalSystem is one compiled call per iteration (:100-120), followed by
+ * the damped update and the objective (:171-181).  mpcqp_stage_* above does that on the device for the stage pattern; the entries
+ * below do it for everything else.  `library_path` is a shared library generated by optimal_control_problem_amd/codegen.py
+ * (build_general_device_library) from the traced cost and constraints: one scalar-generic functor with the cost, its
+ * reverse-derived gradient and the constraints, instantiated into the kernels of csrc/general_kernels.hpp (hipcc, gfx950), with
+ * the CSC pattern and the colouring tables that compress the Hessian and Jacobian passes.  Rows [p; x; g], l = [p; lbx; lbg] - c,
+ * u = [p; ubx; ubg] - c with c = [p; x; g(p, x)]; infinite bounds stay infinite.  np = 0 and ng = 0 are allowed (their arrays
+ * have no elements and may be NULL).
+ * Errors: MPCQP_ERR_ARG for null pointers, batch <= 0, a library that cannot be loaded, lacks a symbol or was generated for another
+ * version of the kernels; MPCQP_ERR_NO_GPU without a device. */
+typedef struct mpcqp_nlp mpcqp_nlp;
+
+/* dlopen, ABI version check, tables uploaded once (SQPOptimizationSolver.cpp:47-77: the once-per-problem part); device: HIP
+ * ordinal, -1 = current device */
+int mpcqp_nlp_create(const char *library_path, int device, mpcqp_nlp **out);
+void mpcqp_nlp_destroy(mpcqp_nlp *s);
+/* dims[8] = {nvar, np, ng, n, m, nnz(P), nnz(A), passes}: passes = evaluations of the functor per instance and call (the colours
+ * of the Hessian plus those of the Jacobian; SQPOptimizationSolver.cpp:47-77) */
+int mpcqp_nlp_dims(const mpcqp_nlp *s, int *dims8);
+/* CSC sparsity of P (n x n, both triangles) and A = [I; dg/dw] (m x n), as mpcqp_create takes them (SQPOptimizationSolver.cpp:47-77).
+ * Pp, Ap: n + 1 entries; Pi: nnz(P); Ai: nnz(A).  Host pointers. */
+int mpcqp_nlp_pattern(const mpcqp_nlp *s, int *Pp, int *Pi, int *Ap, int *Ai);
+/* getLocalSystem for `batch` instances (SQPOptimizationSolver.cpp:100-120).  Device pointers, instance-major and dense: p [batch*np],
+ * x, lbx, ubx [batch*nvar], lbg, ubg [batch*ng]  ->  P [batch*nnzP], q [batch*n], A [batch*nnzA], l, u [batch*m].  Every output
+ * element has one writer: two calls on the same input give the same bits.  Asynchronous on `stream`. */
+int mpcqp_nlp_eval(mpcqp_nlp *s, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
+                   const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream);
+/* objective f [batch] (SQPOptimizationSolver.cpp:180-181) and gmax [batch], the max-norm violation of lbg <= g(p, x) <= ubg (0 when
+ * feasible or ng = 0); either output may be NULL; device pointers */
+int mpcqp_nlp_merit(mpcqp_nlp *s, int batch, const double *p, const double *x, const double *lbg, const double *ubg,
+                    double *f, double *gmax, void *stream);
+/* the damped update of SQPOptimizationSolver.cpp:171-177, with the semantics of mpcqp_stage_step (step_max and status optional) */
+int mpcqp_nlp_step(mpcqp_nlp *s, int batch, double alpha, const double *dw, double *x, double *step_max, const int *status, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Structured stage form: the same QP, given by its stage blocks instead of CSC value arrays.
  *

@@ -470,7 +470,9 @@ def _lit(v):
     return repr(float(v)) if "e" in repr(float(v)) or "." in repr(float(v)) else repr(float(v)) + ".0"
 
 
-def _emit_body(tape):
+def _emit_body(tape, streaming=False):
+    if streaming:
+        return _emit_streaming_body(tape)
     nx = tape.nx
     live = tape.live_nodes()
     ref = {}
@@ -498,6 +500,45 @@ def _emit_body(tape):
     for r, o in enumerate(tape.outputs):
         nd = tape.nodes[o]
         lines.append("    out[%d] = %s;" % (r, "T{} + %s" % ref[o] if nd[0] == "const" else ref[o]))
+    return "\n".join(lines)
+
+
+def _emit_streaming_body(tape):
+    """the general evaluator's form of a body: an input is formed by the accessor `in(k)` where it is first used, an output goes to the
+    sink `out(r, value)` as soon as it is produced -- no array of the problem's length lives in the function"""
+    outs_of = {}
+    for r, o in enumerate(tape.outputs):
+        outs_of.setdefault(o, []).append(r)
+    ref = {}
+    lines = []
+
+    def use(i):
+        if i not in ref:
+            nd = tape.nodes[i]
+            if nd[0] == "in":
+                lines.append("    const T x%d = in(%d);" % (nd[1], nd[1])); ref[i] = "x%d" % nd[1]
+            else:
+                ref[i] = _lit(nd[1])
+        return ref[i]
+
+    for i in tape.live_nodes():
+        nd = tape.nodes[i]
+        if nd[0] in ("in", "const"):
+            continue
+        args = [use(a) for a in nd[1:]]
+        if nd[0] in _UNARY:
+            expr = "-%s" % args[0] if nd[0] == "neg" else "%s(%s)" % (_UNARY[nd[0]], args[0])
+        else:
+            expr = "%s %s %s" % (args[0], _BINARY[nd[0]], args[1])
+        lines.append("    const T w%d = %s;" % (i, expr)); ref[i] = "w%d" % i
+        for r in outs_of.get(i, ()):
+            lines.append("    out(%d, w%d);" % (r, i))
+    for r, o in enumerate(tape.outputs):
+        nd = tape.nodes[o]
+        if nd[0] == "const":
+            lines.append("    out(%d, T{} + %s);" % (r, _lit(nd[1])))
+        elif nd[0] == "in":
+            lines.append("    out(%d, %s);" % (r, use(o)))
     return "\n".join(lines)
 
 
@@ -655,7 +696,7 @@ def cache_dir():
 
 def _build(src_text, suffix, cmd_prefix):
     # the key covers everything the library is compiled from: the generated source, every header it includes and the command
-    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "stage_models.hpp", "common.hpp"))
+    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "general_kernels.hpp", "stage_models.hpp", "common.hpp"))
     deps += open(os.path.join(_HERE, "..", "include", "mpcqp.h")).read()
     key = hashlib.sha256((src_text + deps + " ".join(cmd_prefix)).encode()).hexdigest()[:20]
     base = os.path.join(cache_dir(), "user_%s_%s" % (suffix, key))
@@ -677,3 +718,140 @@ def build_device_library(tape):
 
 def build_host_library(tape):
     return _build(_HOST_TMPL % {"functor": emit_functor(tape)}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
+
+
+# ------------------------------------------------------------------------------------------------- general (non-stage) NLPs
+# The local system of general_nlp.GeneralNLP on the device (reference src/sqp_solver/SQPOptimizationSolver.cpp:47-77,100-120): one functor
+# with the bodies F (cost), G (gradient) and C (constraints) over w = [p; x], instantiated into csrc/general_kernels.hpp.
+
+# Largest accepted tape (operations of F, G and C together).  hipcc -O3 for gfx950 was timed on tapes of growing size (DESIGN 6.9 has the
+# table): generation plus compilation of a tape of this size stays under two minutes, and the time grows faster than linearly beyond it.
+GENERAL_TAPE_CAP = 6000
+
+
+class TapeTooLarge(ValueError):
+    """the general device evaluator refuses this problem; str(e) is the reason the facade keeps"""
+
+
+def general_tape_size(model):
+    """operations (neither inputs nor constants) of the three bodies the general evaluator compiles"""
+    count = lambda t: sum(1 for i in t.live_nodes() if t.nodes[i][0] not in ("in", "const")) if t is not None else 0
+    return count(model._ftape) + count(model._gtape) + count(model._ctape)
+
+
+def _ints(v, empty="-1"):
+    v = [int(a) for a in np.asarray(v).ravel()]
+    return ", ".join(str(a) for a in v) if v else empty
+
+
+def emit_general(model, name="GnUser", cap=None):
+    """C++ source of the functor of a general_nlp.GeneralNLP and its tables: dimensions, the CSC index arrays, the colour of every input for
+    the Hessian and for the Jacobian, and the two slot tables (general_eval.compress)"""
+    from .general_eval import compress
+    cap = GENERAL_TAPE_CAP if cap is None else int(cap)
+    size = general_tape_size(model)
+    if size > cap:
+        raise TapeTooLarge("the traced cost, gradient and constraints have %d operations, more than the %d the device evaluator compiles "
+                           "in reasonable time" % (size, cap))
+    c = compress(model)
+    body = lambda t: _emit_body(t, streaming=True) if t is not None else ""
+    fn = "  template <class T, class In, class Out> SM_HD static void %s(const In &in, const Out &out) {\n%s\n  }\n"
+    src = ("struct %s {\n  static constexpr int n = %d, np = %d, nvar = %d, ng = %d, nnzP = %d, nnzA = %d, hp = %d, jp = %d;\n"
+           % (name, model.n, model.np, model.nvar, model.ng, len(model.Pi), len(model.Ai), c["hp"], c["jp"]))
+    # colour of every input (-1: the variable carries no derivative): the seed of pass `pass` is colour == pass
+    src += "  GN_TABLE int hcol[%d] = {%s};\n  GN_TABLE int jcol[%d] = {%s};\n" % (model.n, _ints(c["hcol"]), model.n, _ints(c["jcol"]))
+    src += fn % ("F", body(model._ftape)) + fn % ("G", body(model._gtape)) + fn % ("C", body(model._ctape if model.ng else None))
+    src += "};\n"
+    for nm, v in (("Pp", model.Pp), ("Pi", model.Pi), ("Ap", model.Ap), ("Ai", model.Ai), ("hslot", c["hslot"]), ("jslot", c["jslot"])):
+        src += "static const int %s_%s[] = {%s};\n" % (name, nm, _ints(v))
+    src += "static const int %s_sizes[] = {%d, %d, %d, %d, %d, %d};\n" % (name, model.n + 1, len(model.Pi), model.n + 1, len(model.Ai),
+                                                                       c["hp"] * model.n, c["jp"] * model.ng)
+    return src
+
+
+_GENERAL_COMMON = '''
+static void gn_copy(int *dst, const int *src, int cnt) { if (dst) for (int i = 0; i < cnt; i++) dst[i] = src[i]; }
+extern "C" {
+// {nvar, np, ng, n, m, nnz(P), nnz(A), passes, Hessian passes}
+void %(pre)s_dims(int *d) {
+  d[0] = GnUser::nvar; d[1] = GnUser::np; d[2] = GnUser::ng; d[3] = GnUser::n; d[4] = GnUser::n + GnUser::ng; d[5] = GnUser::nnzP; d[6] = GnUser::nnzA;
+  d[7] = GnUser::hp + GnUser::jp; d[8] = GnUser::hp;
+}
+// host arrays (NULL: skipped): Pp, Ap [n + 1], Pi [nnzP], Ai [nnzA], hcol, jcol [n], hslot [hp * n], jslot [jp * ng]
+void %(pre)s_tables(int *Pp, int *Pi, int *Ap, int *Ai, int *hcol, int *jcol, int *hslot, int *jslot) {
+  gn_copy(Pp, GnUser_Pp, GnUser_sizes[0]); gn_copy(Pi, GnUser_Pi, GnUser_sizes[1]); gn_copy(Ap, GnUser_Ap, GnUser_sizes[2]); gn_copy(Ai, GnUser_Ai, GnUser_sizes[3]);
+  gn_copy(hslot, GnUser_hslot, GnUser_sizes[4]); gn_copy(jslot, GnUser_jslot, GnUser_sizes[5]);
+  if (hcol) for (int i = 0; i < GnUser::n; i++) hcol[i] = GnUser::hcol[i];
+  if (jcol) for (int i = 0; i < GnUser::n; i++) jcol[i] = GnUser::jcol[i];
+}
+}
+'''
+
+_GENERAL_DEVICE_TMPL = '''// generated by optimal_control_problem_amd/codegen.py (emit_general) -- do not edit
+#include "general_kernels.hpp"
+#define GN_TABLE static constexpr
+
+namespace {      // (internal linkage: several generated libraries live in one process, each with its own GnUser)
+%(functor)s}
+''' + _GENERAL_COMMON % {"pre": "mpcqp_general"} + '''
+extern "C" {
+int mpcqp_general_abi() { return GENERAL_ABI_VERSION; }
+int mpcqp_general_eval(const GnDev *gd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
+                       const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream) {
+  return (int)general_launch_eval<GnUser>(*gd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream);
+}
+int mpcqp_general_merit(int batch, const double *p, const double *x, const double *lbg, const double *ubg, double *f, double *gmax, void *stream) {
+  return (int)general_launch_merit<GnUser>(batch, p, x, lbg, ubg, f, gmax, (hipStream_t)stream);
+}
+}
+'''
+
+_GENERAL_HOST_TMPL = '''// generated by optimal_control_problem_amd/codegen.py (emit_general) -- host build of the same functor, for checks without a GPU
+#include <cmath>
+#include "stage_models.hpp"
+#define GN_TABLE static constexpr
+
+namespace {      // (internal linkage: several generated libraries live in one process, each with its own GnUser)
+%(functor)s}
+''' + _GENERAL_COMMON % {"pre": "general_host"} + '''
+// the accessors and sinks of csrc/general_kernels.hpp, on the host, driven by a loop over the passes with the same tables
+struct HSeededIn { const double *w; const int *col; int pass; Dual operator()(int k) const { return Dual{w[k], col[k] == pass ? 1.0 : 0.0}; } };
+struct HValueIn { const double *w; double operator()(int k) const { return w[k]; } };
+struct HHessOut { double *P, *q; const int *slot; bool first;
+  void operator()(int r, Dual v) const { if (slot[r] >= 0) P[slot[r]] = v.d; if (first) q[r] = v.v; } };
+struct HJacOut { double *A, *l, *u; const double *lbg, *ubg; const int *slot; bool first;
+  void operator()(int r, Dual v) const { if (slot[r] >= 0) A[slot[r]] = v.d; if (first) { l[r] = lbg[r] - v.v; u[r] = ubg[r] - v.v; } } };
+struct HCostOut { double *f; void operator()(int, double v) const { *f = v; } };
+struct HViolationOut { const double *lbg, *ubg; double *gmax;
+  void operator()(int r, double v) const { *gmax = std::fmax(*gmax, std::fmax(lbg[r] - v, v - ubg[r])); } };
+extern "C" {
+// one instance: w [n] = [p; x], lbx, ubx [nvar], lbg, ubg [ng] -> P [nnzP], q [n], A [nnzA], l, u [m]
+void general_host_eval(const double *w, const double *lbx, const double *ubx, const double *lbg, const double *ubg,
+                       double *P, double *q, double *A, double *l, double *u) {
+  constexpr int n = GnUser::n, np = GnUser::np, ng = GnUser::ng;
+  for (int pass = 0; pass < GnUser::hp; pass++)
+    GnUser::G<Dual>(HSeededIn{w, GnUser::hcol, pass}, HHessOut{P, q, GnUser_hslot + pass * n, pass == 0});
+  for (int pass = 0; pass < GnUser::jp; pass++)
+    GnUser::C<Dual>(HSeededIn{w, GnUser::jcol, pass}, HJacOut{A, l + n, u + n, lbg, ubg, GnUser_jslot + pass * ng, pass == 0});
+  for (int j = 0; j < n; j++) {
+    A[GnUser_Ap[j]] = 1.0;
+    l[j] = (j < np ? w[j] : lbx[j - np]) - w[j]; u[j] = (j < np ? w[j] : ubx[j - np]) - w[j];
+  }
+}
+void general_host_merit(const double *w, const double *lbg, const double *ubg, double *f, double *gmax) {
+  GnUser::F<double>(HValueIn{w}, HCostOut{f});
+  *gmax = 0.0;
+  if (GnUser::ng > 0) GnUser::C<double>(HValueIn{w}, HViolationOut{lbg, ubg, gmax});
+}
+}
+'''
+
+
+def build_general_device_library(model, cap=None):
+    """gfx950 shared library for mpcqp_nlp_create (hipcc cross-compiles without a GPU); cached by content.  TapeTooLarge beyond the cap."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    return _build(_GENERAL_DEVICE_TMPL % {"functor": emit_general(model, cap=cap)}, "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
+
+
+def build_general_host_library(model, cap=None):
+    return _build(_GENERAL_HOST_TMPL % {"functor": emit_general(model, cap=cap)}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])

@@ -55,6 +55,12 @@ __global__ void __launch_bounds__(256) stage_step_kernel(int batch, int nvar, in
 }
 
 // ------------------------------------------------------------------------------------------ host side
+hipError_t mpcqp_launch_step(int batch, int nvar, int n, int np, double alpha, const double *dw, double *x, double *step_max, const int *status,
+                             hipStream_t st) {
+  stage_step_kernel<<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(batch, nvar, n, np, alpha, dw, x, step_max, status);
+  return hipGetLastError();
+}
+
 extern "C" {
 
 int mpcqp_stage_default(int model, int horizon, mpcqp_stage_desc *d) {
@@ -276,9 +282,7 @@ int mpcqp_stage_step(mpcqp_stage *s, int batch, double alpha, const double *dw, 
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if (batch <= 0 || !dw || !x) return mpcqp_set_error(MPCQP_ERR_ARG, "bad batch or null data pointer");
   MPCQP_HIPCHK(hipSetDevice(s->device));
-  hipStream_t st = (hipStream_t)stream;
-  stage_step_kernel<<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(batch, s->sd.nvar, s->sd.n, s->sd.np, alpha, dw, x, step_max, status);
-  MPCQP_HIPCHK(hipGetLastError());
+  MPCQP_HIPCHK(mpcqp_launch_step(batch, s->sd.nvar, s->sd.n, s->sd.np, alpha, dw, x, step_max, status, (hipStream_t)stream));
   return MPCQP_OK;
 }
 

@@ -1,0 +1,165 @@
+"""GeneralEvaluator: getLocalSystem on the GPU for a general (non-stage) NLP (include/mpcqp.h, mpcqp_nlp_*).
+
+general_nlp.GeneralNLP evaluates the local system of ANY problem on the host -- the gradient tape once, then one complex-step pass per
+Hessian and Jacobian column (reference src/sqp_solver/SQPOptimizationSolver.cpp:47-77,100-120 does the same with CasADi's compiled
+function).  Here the same tapes are emitted as one scalar-generic functor (codegen.emit_general), compiled for gfx950 and run by the
+kernels of csrc/general_kernels.hpp: forward-mode duals over the reverse-derived gradient for the Hessian, over the constraints for the
+Jacobian.
+
+Compression by colouring.  A pass per column would cost O(n) evaluations per instance.  The columns of a structure matrix are
+partitioned into colours such that no two columns of a colour share a structurally non-zero row (greedy, in column order, on the full
+symmetric pattern for the Hessian; columns without an entry get no colour).  A pass seeds the dual part 1.0 on every input of its
+colour; the dual part of output row r is then exactly the entry (r, c) of the ONE column c of that colour that has row r: direct
+recovery.  slot[pass][r] names the CSC value slot of that entry (-1: none) in the order GeneralNLP.Pp / Pi / Ap / Ai define."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def colour_columns(mask):
+    """greedy distance-1 colouring of the columns of a boolean structure matrix [rows, cols]: (colour [cols] with -1 for a column without
+    entries, number of colours).  No two columns of one colour share a row."""
+    mask = np.asarray(mask, bool)
+    rows, cols = mask.shape
+    colour = np.full(cols, -1, np.int32)
+    used = []                                   # used[c]: rows taken by the columns of colour c
+    for j in range(cols):
+        col = mask[:, j]
+        if not col.any():
+            continue
+        for c, taken in enumerate(used):
+            if not (taken & col).any():
+                taken |= col; colour[j] = c
+                break
+        else:
+            used.append(col.copy()); colour[j] = len(used) - 1
+    return colour, len(used)
+
+
+def slot_table(mask, colour, ncolours, colptr, first=0):
+    """slot[pass, r]: CSC value slot of entry (r, c), c the column of colour `pass` with row r, else -1.  colptr: the CSC column
+    pointers; `first`: entries of the column that precede this block's rows (the identity entry of A)"""
+    mask = np.asarray(mask, bool)
+    rows, cols = mask.shape
+    slot = np.full((max(ncolours, 0), rows), -1, np.int32)
+    for j in range(cols):
+        if colour[j] < 0:
+            continue
+        r = np.nonzero(mask[:, j])[0]
+        slot[colour[j], r] = int(colptr[j]) + first + np.arange(len(r))
+    return slot
+
+
+def compress(model):
+    """colours and slot tables of a general_nlp.GeneralNLP.  hp >= 1 (pass 0 also writes the gradient, whether or not the Hessian has an
+    entry); jp = 0 without general rows, else >= 1 (pass 0 also writes their bounds)"""
+    n, ng = model.n, model.ng
+    hcol, nh = colour_columns(model.hm)
+    hp = max(nh, 1)
+    hslot = np.full((hp, n), -1, np.int32); hslot[:nh] = slot_table(model.hm, hcol, nh, model.Pp)
+    jm = model.am[n:]
+    jcol, nj = colour_columns(jm) if ng else (np.full(n, -1, np.int32), 0)
+    jp = max(nj, 1) if ng else 0
+    jslot = np.full((jp, ng), -1, np.int32)
+    if ng:
+        jslot[:nj] = slot_table(jm, jcol, nj, model.Ap, first=1)
+    return dict(hcol=hcol, jcol=jcol, hp=hp, jp=jp, hslot=hslot, jslot=jslot, hcolours=nh, jcolours=nj)
+
+
+def _bind(L):
+    if getattr(L, "_nlp_bound", False):
+        return L
+    vp = C.c_void_p
+    L.mpcqp_nlp_create.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
+    L.mpcqp_nlp_destroy.argtypes = [vp]
+    L.mpcqp_nlp_destroy.restype = None
+    L.mpcqp_nlp_dims.argtypes = [vp, vp]
+    L.mpcqp_nlp_pattern.argtypes = [vp, vp, vp, vp, vp]
+    L.mpcqp_nlp_eval.argtypes = [vp, C.c_int] + [vp] * 11 + [vp]
+    L.mpcqp_nlp_merit.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.mpcqp_nlp_step.argtypes = [vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]
+    L._nlp_bound = True
+    return L
+
+
+def _check(t, shape, name):
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+        raise ValueError("%s: expected a contiguous float64 CUDA tensor" % name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: expected shape %s, got %s (dimension mismatch)" % (name, tuple(shape), tuple(t.shape)))
+    return t.data_ptr() or None                 # (an array without elements -- np = 0, ng = 0 -- has no address)
+
+
+class GeneralEvaluator:
+    """the surface of stage_eval.StageEvaluator the device SQP loop uses, for a general_nlp.GeneralNLP.  library: the generated
+    gfx950 library (codegen.build_general_device_library; codegen.TapeTooLarge when the problem is refused)"""
+
+    def __init__(self, model, device=-1, cap=None, library=None):
+        from . import codegen
+        self.model = model
+        self.library = library if library is not None else codegen.build_general_device_library(model, cap=cap)
+        L = _bind(_lib.lib())
+        self._h = C.c_void_p()
+        _lib.check(L.mpcqp_nlp_create(self.library.encode(), int(device), C.byref(self._h)))
+        dims = np.zeros(8, np.int32)
+        _lib.check(L.mpcqp_nlp_dims(self._h, dims.ctypes.data))
+        self.nvar, self.np, self.ng, self.n, self.m, self.nnzP, self.nnzA, self.passes = [int(v) for v in dims]
+        self.Pp = np.zeros(self.n + 1, np.int32); self.Pi = np.zeros(self.nnzP, np.int32)
+        self.Ap = np.zeros(self.n + 1, np.int32); self.Ai = np.zeros(self.nnzA, np.int32)
+        _lib.check(L.mpcqp_nlp_pattern(self._h, self.Pp.ctypes.data, self.Pi.ctypes.data, self.Ap.ctypes.data, self.Ai.ctypes.data))
+        self._bounds = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            _lib.lib().mpcqp_nlp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def alloc(self, batch, device="cuda"):
+        """output buffers of one evaluation: dict P, q, A, l, u"""
+        import torch
+        mk = lambda w: torch.empty((batch, w), dtype=torch.float64, device=device)
+        return dict(P=mk(self.nnzP), q=mk(self.n), A=mk(self.nnzA), l=mk(self.m), u=mk(self.m))
+
+    def eval(self, p, x, lbx, ubx, lbg, ubg, out=None, stream=None):
+        B = x.shape[0]
+        if out is None:
+            out = self.alloc(B, x.device)
+        args = [_check(p, (B, self.np), "p"), _check(x, (B, self.nvar), "x"), _check(lbx, (B, self.nvar), "lbx"),
+                _check(ubx, (B, self.nvar), "ubx"), _check(lbg, (B, self.ng), "lbg"), _check(ubg, (B, self.ng), "ubg"),
+                _check(out["P"], (B, self.nnzP), "P"), _check(out["q"], (B, self.n), "q"), _check(out["A"], (B, self.nnzA), "A"),
+                _check(out["l"], (B, self.m), "l"), _check(out["u"], (B, self.m), "u")]
+        _lib.check(_lib.lib().mpcqp_nlp_eval(self._h, B, *args, stream))
+        self._bounds = (lbg, ubg)
+        return out
+
+    def merit(self, p, x, stream=None, lbg=None, ubg=None):
+        """objective f [B] and the max-norm violation of lbg <= g <= ubg [B]; the bounds are those of the last eval unless given"""
+        import torch
+        B = x.shape[0]
+        if lbg is None or ubg is None:
+            if self._bounds is None:
+                raise ValueError("merit needs the constraint bounds: give lbg and ubg, or call eval first")
+            lbg, ubg = self._bounds
+        f = torch.empty(B, dtype=torch.float64, device=x.device); g = torch.empty(B, dtype=torch.float64, device=x.device)
+        _lib.check(_lib.lib().mpcqp_nlp_merit(self._h, B, _check(p, (B, self.np), "p"), _check(x, (B, self.nvar), "x"),
+                                              _check(lbg, (B, self.ng), "lbg"), _check(ubg, (B, self.ng), "ubg"), f.data_ptr(), g.data_ptr(), stream))
+        return f, g
+
+    def step(self, alpha, dw, x, stream=None, status=None):
+        """x += alpha * dw[:, np:] in place; returns max|alpha dx| per instance.  status (int32 CUDA tensor [B], optional):
+        instances whose QP did not return a point keep their x"""
+        import torch
+        B = x.shape[0]
+        sm = torch.empty(B, dtype=torch.float64, device=x.device)
+        _lib.check(_lib.lib().mpcqp_nlp_step(self._h, B, float(alpha), _check(dw, (B, self.n), "dw"), _check(x, (B, self.nvar), "x"),
+                                             sm.data_ptr(), None if status is None else status.data_ptr(), stream))
+        return sm

@@ -242,10 +242,14 @@ class OptimalControlProblem:
 
     SOLVER_TYPES = ("IPOPT", "SQP", "CUDA_SQP", "MIXED")
 
-    def __init__(self, configNode, batch=1, qp_solver=None, device_resident=None):
+    def __init__(self, configNode, batch=1, qp_solver=None, device_resident=None, general_device=False):
         """device_resident: run the whole SQP tick on the GPU -- the dynamics are traced, emitted as code and compiled for
         gfx950 at genSolver() (codegen.py).  Default: the YAML's solver_settings.gen_code, the flag with which the reference
-        generates and compiles its C code at the same point (reference src/OptimalControlProblem.cpp:263-287)."""
+        generates and compiles its C code at the same point (reference src/OptimalControlProblem.cpp:263-287).
+        general_device (opt-in): a problem that takes the general path (not a stage pattern) is compiled for the device as well -- cost,
+        gradient and constraints over the whole vector as one generated library (codegen.build_general_device_library, mpcqp_nlp_*) --
+        and runs the device loop on it; genCode() returns that library.  A problem too large to compile in reasonable time stays on
+        the host loop, with the reason in generalDeviceReason_.  Ignored when a qp_solver is injected."""
         if not self.validateConfig(configNode):
             raise RuntimeError("Invalid configuration file")                        # OptimalControlProblem.cpp:16-18
         self.OCPConfigPtr_ = OCPConfig(configNode)
@@ -260,6 +264,9 @@ class OptimalControlProblem:
         self.batch = int(batch)
         self._qp_solver = qp_solver
         self.deviceResident = self.solverSettings["genCode"] if device_resident is None else bool(device_resident)
+        self.generalDevice = bool(general_device)
+        self.generalDeviceReason_ = None             # why a general-path problem stayed on the host loop although general_device was asked for
+        self.generalLibrary_ = None
         self.constraints_, self.constraintNames_ = [], []
         self.constraintLowerBounds_, self.constraintUpperBounds_ = [], []
         self.costs_ = []
@@ -328,6 +335,11 @@ class OptimalControlProblem:
         """generate + compile the local-system evaluation for the GPU (the reference's genCode writes C for the NLP solver and
         shells out to gcc, OptimalControlProblem.cpp:263-287,602-640); returns the path of the shared library"""
         from . import codegen
+        if getattr(self, "generalPath_", False) and self.generalDevice and self._qp_solver is None:
+            # the local-system function of ANY problem, saved as a library (the reference's genCode does that for whatever it was given)
+            if self.generalLibrary_ is None:
+                self.generalLibrary_ = codegen.build_general_device_library(self.model_)
+            return self.generalLibrary_
         if getattr(self, "generalPath_", False):
             raise NotImplementedError("gen_code compiles the stage pattern for the device; this problem takes the general path (%s)" % self.generalPathReason_)
         model = self.model_ if self.model_ is not None else self._compile_stage_model()
@@ -372,7 +384,20 @@ class OptimalControlProblem:
                 print("OptimalControlProblem: not a stage pattern (%s); general host evaluation, QPs on the GPU" % why)
         options = {"max_iter": self.solverSettings["stepNum"], "alpha": self.solverSettings["alpha"],
                    "verbose": self.solverSettings["verbose"]}
-        if self.deviceResident and self._qp_solver is None and not self.generalPath_:
+        self.generalDeviceReason_ = None; self.generalLibrary_ = None
+        if self.generalPath_ and self.generalDevice and self._qp_solver is None:
+            from . import codegen
+            try:
+                self.generalLibrary_ = codegen.build_general_device_library(self.model_)
+            except codegen.TapeTooLarge as why:
+                self.generalDeviceReason_ = str(why)
+                if self.solverSettings["verbose"]:
+                    print("OptimalControlProblem: general device evaluation refused (%s); host evaluation" % why)
+        if self.generalLibrary_ is not None:
+            from .general_eval import GeneralEvaluator
+            ev = GeneralEvaluator(self.model_, library=self.generalLibrary_)
+            self.OSQPSolverPtr_ = DeviceSQPOptimizationSolver(self.model_, options, batch=self.batch, evaluator=ev)
+        elif self.deviceResident and self._qp_solver is None and not self.generalPath_:
             self.OSQPSolverPtr_ = DeviceSQPOptimizationSolver(self.model_, options, batch=self.batch)
         else:
             self.OSQPSolverPtr_ = SQPOptimizationSolver(self.model_, options, batch=self.batch, qp_solver=self._qp_solver)

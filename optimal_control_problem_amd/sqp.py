@@ -121,9 +121,10 @@ class DeviceSQPOptimizationSolver:
     """The same outer loop with every step on the GPU: local-system evaluation
     (mpcqp_stage_eval, replaces getLocalSystem :100-120), QP (mpcqp_update on borrowed device arrays + mpcqp_solve), damped
     update (mpcqp_stage_step, :171-177) and objective (mpcqp_stage_merit, :180-181).  The iterate, bounds and QP data never
-    visit the host; only the returned x / f do.  For the stage-OCP zoo models (models.StageOCP subclasses)."""
+    visit the host; only the returned x / f do.  For the stage-OCP zoo models (models.StageOCP subclasses); with `evaluator` (an object
+    with the StageEvaluator surface the loop uses, e.g. general_eval.GeneralEvaluator: mpcqp_nlp_*) for any problem that has one."""
 
-    def __init__(self, nlp, options, batch=1, device=-1, codegen=None):
+    def __init__(self, nlp, options, batch=1, device=-1, codegen=None, evaluator=None):
         import torch
         from .batch_qp import BatchQP
         from .stage_eval import StageEvaluator
@@ -151,7 +152,7 @@ class DeviceSQPOptimizationSolver:
         self._kept = False
         self._scaled = False                             # keep_scaling: a full set-up has run on the handle
         self.batch = int(batch)
-        self.ev = StageEvaluator(nlp, device=device, codegen=codegen)
+        self.ev = evaluator if evaluator is not None else StageEvaluator(nlp, device=device, codegen=codegen)
         # reference SQPOptimizationSolver.cpp:80-85
         self.qp = BatchQP(self.ev.n, self.ev.m, self.batch, self.ev.Pp, self.ev.Pi, self.ev.Ap, self.ev.Ai,
                           eps_abs=1e-3, eps_rel=1e-3, max_iter=10000, warm_start=1 if self.warm_start_admm else 0, device=device)
@@ -182,7 +183,9 @@ class DeviceSQPOptimizationSolver:
             t = a.to(self.dev, torch.float64)
         else:
             t = torch.as_tensor(np.asarray(a, float), dtype=torch.float64, device=self.dev)
-        t = t.reshape(-1, w) if w else t.reshape(-1, 0)
+        if w == 0:                                       # (np = 0 or ng = 0 with a general evaluator: an array without elements)
+            return torch.zeros((self.batch, 0), dtype=torch.float64, device=self.dev)
+        t = t.reshape(-1, w)
         return t.expand(self.batch, w).contiguous()
 
     def getOptimalSolution(self, arg, to_host=True):
