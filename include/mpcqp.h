@@ -308,6 +308,15 @@ int mpcqp_stage_create(const mpcqp_stage_desc *d, mpcqp_stage **out);
  * objective is then sum_k l(s_k, u_k, p) with its exact Hessian (the reference's hessian(f, w), SQPOptimizationSolver.cpp:55-60) in
  * the structure the generated code reports (mpcqp_stage_pattern), and d->Q, d->R, mpcqp_stage_set_weights do not apply. */
 int mpcqp_stage_create_user(const mpcqp_stage_desc *d, const char *library_path, mpcqp_stage **out);
+/* Opt-in trajectory tracking: one reference state per frame.  In the reference this needs nothing special -- setReference takes an SX of any size
+ * (src/OptimalControlProblem.cpp:570-572), computeOptimalTrajectory checks only that the size matches (:85-90), and the user subtracts slice k of
+ * the reference in the cost term of step k.  In the formulation w = [p; x], rows [p; x; g] (SQPOptimizationSolver.cpp:47-77) the parameter block
+ * is then p = [r_0; ...; r_{horizon-1}], np = horizon * nx, every p_k coupled to its own frame only: the objective is
+ *     sum_k (s_k - r_k)' Q_k (s_k - r_k) + u_k' R_k u_k      or, with a generated stage cost,      sum_k l(s_k, u_k, r_k).
+ * library_path NULL: a zoo model (d->model); else a library generated with per_frame_reference (it exports mpcqp_user_pref, which returns 1).
+ * MPCQP_ERR_ARG for a library generated without it -- and mpcqp_stage_create_user returns MPCQP_ERR_ARG for one generated with it.
+ * Every other mpcqp_stage_* entry works on the handle unchanged, with p [batch * horizon * nx]. */
+int mpcqp_stage_create_tracking(const mpcqp_stage_desc *d, const char *library_path /* NULL = zoo model */, mpcqp_stage **out);
 void mpcqp_stage_destroy(mpcqp_stage *s);
 /* Per-frame diagonal weights (terminal costs, ramps): Qk [horizon * nx], Rk [horizon * nu], host pointers, copied; frame k is
  * weighted by Qk[k*nx ...], Rk[k*nu ...] instead of desc.Q, desc.R (the reference calls addVectorCost once per step, so weights may

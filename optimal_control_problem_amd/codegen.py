@@ -428,13 +428,16 @@ def _trace_link(kfun, nx, nu, nk):
     return tape
 
 
-def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None):
+def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
     the diagonal tracking weights; lterm: the same for the last frame only (terminal cost).  Their gradients are derived
-    on the tape (reverse mode); the kernels differentiate those once more with dual numbers for the exact Hessian."""
+    on the tape (reverse mode); the kernels differentiate those once more with dual numbers for the exact Hessian.
+    per_frame_reference: the library is emitted for trajectory tracking (models.StageOCP.per_frame_reference: frame k's cost takes its own
+    reference r_k, mpcqp_stage_create_tracking loads it); the traced functions are the same."""
     tape = _trace_fn(F, nx, nu, nx, "F must return the next state")
+    tape.pref = bool(per_frame_reference)
     tape.nh = int(nh) if hfun is not None else 0
     tape.path = None
     if tape.nh:
@@ -562,6 +565,8 @@ def emit_functor(tape, name="SmUser"):
         # L: out[0] = l(s, u, r); LG: out[nx + nu + nx] = dl / d[s; u; r]; LT, LTG: the terminal frame's
         for fn, tp in (("L", cost["L"]), ("LG", cost["G"]), ("LT", cost["LT"] or cost["L"]), ("LTG", cost["GT"] or cost["G"])):
             src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *r, T *out) {\n%s\n  }\n" % (fn, _emit_body(tp))
+    if getattr(tape, "pref", False):
+        src += "  static constexpr bool pref = true;\n"
     src += "};\n"
     lo = ", ".join(_blit(v) for v in tape.h_lo) if nh else "0.0"
     hi = ", ".join(_blit(v) for v in tape.h_hi) if nh else "0.0"
@@ -710,10 +715,20 @@ def _build(src_text, suffix, cmd_prefix):
     return so
 
 
+def device_source(tape):
+    """the translation unit of a stage library.  Traced with per_frame_reference: SmUser::pref, the PF = true kernel instances only, and the
+    export mpcqp_user_pref() by which mpcqp_stage_create_tracking / _create_user tell the two kinds apart; else the text it always was"""
+    src = _DEVICE_TMPL % {"functor": emit_functor(tape)}
+    if getattr(tape, "pref", False):
+        src = src.replace("stage_launch_eval<SmUser>", "stage_launch_eval<SmUser, SmUser::pref>").replace("stage_launch_merit<SmUser>", "stage_launch_merit<SmUser, SmUser::pref>")
+        src = src.replace("int mpcqp_user_nh() {", "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\nint mpcqp_user_nh() {")
+    return src
+
+
 def build_device_library(tape):
-    """gfx950 shared library for mpcqp_stage_create_user (hipcc cross-compiles without a GPU); cached by content"""
+    """gfx950 shared library for mpcqp_stage_create_user / _create_tracking (hipcc cross-compiles without a GPU); cached by content"""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    return _build(_DEVICE_TMPL % {"functor": emit_functor(tape)}, "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
+    return _build(device_source(tape), "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
 
 
 def build_host_library(tape):

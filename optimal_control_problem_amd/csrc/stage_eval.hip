@@ -94,21 +94,22 @@ int mpcqp_stage_default(int model, int horizon, mpcqp_stage_desc *d) {
 }
 
 static int stage_create_common(const mpcqp_stage_desc *d, int nx, int nu, int nh, const double *h_lo, const double *h_hi, mpcqp_stage *s,
-                               const unsigned char *cost_mask = nullptr, int nk = 0, const double *k_lo = nullptr, const double *k_hi = nullptr) {
+                               const unsigned char *cost_mask = nullptr, int nk = 0, const double *k_lo = nullptr, const double *k_hi = nullptr,
+                               bool pref = false) {
   int dev = 0;
   if (int rc = mpcqp_pick_device(d->device, &dev)) return rc;
   s->desc = *d; s->device = dev;
   StageDev &sd = s->sd;
   sd.model = d->model; sd.N = d->horizon; sd.dt = d->dt; sd.nx = nx; sd.nu = nu;
-  sd.f = sd.nx + sd.nu; sd.np = sd.nx; sd.nvar = sd.N * sd.f; sd.n = sd.np + sd.nvar;
+  sd.f = sd.nx + sd.nu; sd.pref = pref ? 1 : 0; sd.np = pref ? sd.N * sd.nx : sd.nx; sd.nvar = sd.N * sd.f; sd.n = sd.np + sd.nvar;
   sd.nh = nh; sd.nk = nk; sd.ngd = (sd.N - 1) * sd.nx; sd.ng = sd.ngd + sd.N * nh + (sd.N - 1) * nk; sd.m = sd.n + sd.ng;
   for (int i = 0; i < SM_MAXNK; i++) { sd.k_lo[i] = (k_lo && i < nk) ? k_lo[i] : -INFINITY; sd.k_hi[i] = (k_hi && i < nk) ? k_hi[i] : INFINITY; }
   for (int i = 0; i < SM_MAXNH; i++) { sd.h_lo[i] = (h_lo && i < nh) ? h_lo[i] : -INFINITY; sd.h_hi[i] = (h_hi && i < nh) ? h_hi[i] : INFINITY; }
   for (int i = 0; i < SM_MAXNX; i++) sd.Q[i] = d->Q[i];
   for (int i = 0; i < SM_MAXNU; i++) sd.R[i] = d->R[i];
   for (int i = 0; i < SM_NPAR; i++) sd.par[i] = d->par[i];
-  sm_build_pattern(sd.nx, sd.nu, sd.N, sd.nh, sd.nk, s->Pp, s->Pi, s->Ap, s->Ai);
-  if (cost_mask) sm_build_cost_pattern(sd.nx, sd.nu, sd.N, cost_mask, s->Pp, s->Pi);
+  sm_build_pattern(sd.nx, sd.nu, sd.N, sd.nh, sd.nk, s->Pp, s->Pi, s->Ap, s->Ai, pref);
+  if (cost_mask) sm_build_cost_pattern(sd.nx, sd.nu, sd.N, cost_mask, s->Pp, s->Pi, pref);
   sd.nnzP = (int)s->Pi.size(); sd.nnzA = (int)s->Ai.size();
   if (hipSetDevice(dev) != hipSuccess) return mpcqp_set_error(MPCQP_ERR_HIP, "hipSetDevice failed");
   const size_t bytes = (size_t)(sd.n + 1) * sizeof(int);
@@ -127,7 +128,7 @@ static int stage_create_common(const mpcqp_stage_desc *d, int nx, int nu, int nh
   return MPCQP_OK;
 }
 
-int mpcqp_stage_create(const mpcqp_stage_desc *d, mpcqp_stage **out) {
+static int stage_create_zoo(const mpcqp_stage_desc *d, bool pref, mpcqp_stage **out) {
   if (!out) return mpcqp_set_error(MPCQP_ERR_ARG, "out is null");
   *out = nullptr;
   if (!d) return mpcqp_set_error(MPCQP_ERR_ARG, "desc is null");
@@ -136,12 +137,13 @@ int mpcqp_stage_create(const mpcqp_stage_desc *d, mpcqp_stage **out) {
   int nx, nu;
   sm_model_dims(d->model, &nx, &nu);
   mpcqp_stage *s = new mpcqp_stage();
-  if (int rc = stage_create_common(d, nx, nu, 0, nullptr, nullptr, s)) { mpcqp_stage_destroy(s); return rc; }
+  if (int rc = stage_create_common(d, nx, nu, 0, nullptr, nullptr, s, nullptr, 0, nullptr, nullptr, pref)) { mpcqp_stage_destroy(s); return rc; }
   *out = s;
   return MPCQP_OK;
 }
 
-int mpcqp_stage_create_user(const mpcqp_stage_desc *d, const char *library_path, mpcqp_stage **out) {
+// a generated library says with the optional export mpcqp_user_pref() whether it was traced for per-frame references; the entry point asks for one kind
+static int stage_create_library(const mpcqp_stage_desc *d, const char *library_path, bool pref, mpcqp_stage **out) {
   if (!out) return mpcqp_set_error(MPCQP_ERR_ARG, "out is null");
   *out = nullptr;
   if (!d || !library_path) return mpcqp_set_error(MPCQP_ERR_ARG, "null argument");
@@ -154,6 +156,12 @@ int mpcqp_stage_create_user(const mpcqp_stage_desc *d, const char *library_path,
   auto me = (user_merit_fn)dlsym(lib, "mpcqp_user_merit");
   if (!abi || !dims || !ev || !me) { dlclose(lib); return mpcqp_set_error(MPCQP_ERR_ARG, "the library does not export mpcqp_user_abi/dims/eval/merit"); }
   if (abi() != STAGE_ABI_VERSION) { dlclose(lib); return mpcqp_set_error(MPCQP_ERR_ARG, "the library was generated for another version of the stage kernels; regenerate it"); }
+  auto pf = (int (*)())dlsym(lib, "mpcqp_user_pref");
+  if ((pf && pf() != 0) != pref) {
+    dlclose(lib);
+    return mpcqp_set_error(MPCQP_ERR_ARG, pref ? "the library was generated for one shared reference; mpcqp_stage_create_user takes it"
+                                               : "the library was generated for per-frame references; mpcqp_stage_create_tracking takes it");
+  }
   int nx = 0, nu = 0, nh = 0;
   dims(&nx, &nu);
   auto nhf = (int (*)())dlsym(lib, "mpcqp_user_nh");
@@ -177,9 +185,17 @@ int mpcqp_stage_create_user(const mpcqp_stage_desc *d, const char *library_path,
   std::vector<unsigned char> mask((size_t)(2 * nx + nu) * (2 * nx + nu));
   auto cf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_cost");
   s->general_cost = cf && cf(mask.data());
-  if (int rc = stage_create_common(&dd, nx, nu, nh, h_lo, h_hi, s, s->general_cost ? mask.data() : nullptr, nk, k_lo, k_hi)) { mpcqp_stage_destroy(s); return rc; }
+  if (int rc = stage_create_common(&dd, nx, nu, nh, h_lo, h_hi, s, s->general_cost ? mask.data() : nullptr, nk, k_lo, k_hi, pref)) { mpcqp_stage_destroy(s); return rc; }
   *out = s;
   return MPCQP_OK;
+}
+
+int mpcqp_stage_create(const mpcqp_stage_desc *d, mpcqp_stage **out) { return stage_create_zoo(d, false, out); }
+
+int mpcqp_stage_create_user(const mpcqp_stage_desc *d, const char *library_path, mpcqp_stage **out) { return stage_create_library(d, library_path, false, out); }
+
+int mpcqp_stage_create_tracking(const mpcqp_stage_desc *d, const char *library_path, mpcqp_stage **out) {
+  return library_path ? stage_create_library(d, library_path, true, out) : stage_create_zoo(d, true, out);
 }
 
 void mpcqp_stage_destroy(mpcqp_stage *s) {
@@ -253,9 +269,12 @@ int mpcqp_stage_eval(mpcqp_stage *s, int batch, const double *p, const double *x
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
   switch (s->sd.model) {
-    case SM_DOUBLE_INTEGRATOR: e = stage_launch_eval<SmDoubleIntegrator>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
-    case SM_QUADROTOR: e = stage_launch_eval<SmQuadrotor>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
-    case SM_CARTPOLE: e = stage_launch_eval<SmCartPole>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
+    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_eval<SmDoubleIntegrator, true>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st)
+                                            : stage_launch_eval<SmDoubleIntegrator>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
+    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_eval<SmQuadrotor, true>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st)
+                                            : stage_launch_eval<SmQuadrotor>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
+    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_eval<SmCartPole, true>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st)
+                                            : stage_launch_eval<SmCartPole>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
     case MPCQP_MODEL_USER: e = (hipError_t)s->user_eval(&s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream); break;
   }
   MPCQP_HIPCHK(e);
@@ -269,9 +288,9 @@ int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
   switch (s->sd.model) {
-    case SM_DOUBLE_INTEGRATOR: e = stage_launch_merit<SmDoubleIntegrator>(s->sd, batch, p, x, f, gmax, st); break;
-    case SM_QUADROTOR: e = stage_launch_merit<SmQuadrotor>(s->sd, batch, p, x, f, gmax, st); break;
-    case SM_CARTPOLE: e = stage_launch_merit<SmCartPole>(s->sd, batch, p, x, f, gmax, st); break;
+    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_merit<SmDoubleIntegrator, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmDoubleIntegrator>(s->sd, batch, p, x, f, gmax, st); break;
+    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_merit<SmQuadrotor, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmQuadrotor>(s->sd, batch, p, x, f, gmax, st); break;
+    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_merit<SmCartPole, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmCartPole>(s->sd, batch, p, x, f, gmax, st); break;
     case MPCQP_MODEL_USER: e = (hipError_t)s->user_merit(&s->sd, batch, p, x, f, gmax, stream); break;
   }
   MPCQP_HIPCHK(e);

@@ -7,11 +7,12 @@
 #include <hip/hip_runtime.h>
 #include "stage_models.hpp"
 
-#define STAGE_ABI_VERSION 6
+#define STAGE_ABI_VERSION 7
 
 struct StageDev {
   int model, N, nx, nu, f, np, n, m, ng, nvar, nnzP, nnzA;   // ng = all general rows: (N-1)*nx dynamics rows, then N*nh path rows, then (N-1)*nk link rows
   int nh, ngd, nk;
+  int pref;   // per-frame references (mpcqp_stage_create_tracking): p = [r_0; ...; r_{N-1}], np = N nx, frame k's cost terms take r_k (the PF = true kernels)
   double h_lo[SM_MAXNH], h_hi[SM_MAXNH];   // path-constraint bounds, for the merit kernel's violation measure
   double k_lo[SM_MAXNK], k_hi[SM_MAXNK];   // link-constraint bounds (the same on every stage), likewise
   double dt;
@@ -22,7 +23,10 @@ struct StageDev {
   const double *h_lok, *h_hik;  // optional per-frame path-constraint bounds [N * nh] (device; NULL = h_lo, h_hi on every frame)
 };
 
-template <class M>
+// PF (per-frame references, StageDev::pref): the parameter block holds one reference state per frame.  Parameter column j = k nx + i is thread j of
+// its instance, as before; the cooperative mapping pads the N nx parameter slots up to a multiple of f, so that every frame's f lanes still start
+// at a multiple of f (threads per instance ceil(N nx / f) f + N f).  Adjacent lanes still own adjacent columns: the store streams stay contiguous.
+template <class M, bool PF = false>
 __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch, const double *__restrict__ p, const double *__restrict__ x,
                                                          const double *__restrict__ lbx, const double *__restrict__ ubx,
                                                          const double *__restrict__ lbg, const double *__restrict__ ubg,
@@ -34,15 +38,49 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
   constexpr bool COOP = sm_has_coop<M>::value && (64 % f == 0) && nx <= f;
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int n = sd.n, N = sd.N;
-  const int per = COOP ? f * (N + 1) : n;
+  const int npar = PF ? N * nx : nx;                                  // parameter columns
+  const int ppad = PF ? (npar + f - 1) / f * f : f;                   // their thread slots under the cooperative mapping
+  const int per = COOP ? ppad + f * N : n;
   if (gid >= (long)batch * per) return;
   const int b = (int)(gid / per), jt = (int)(gid - (long)b * per);
-  if (COOP && jt < f && jt >= nx) return;       // (padding lanes of the parameter group)
-  const int j = COOP ? (jt < f ? jt : jt - f + nx) : jt;
-  const double *pb = p + (long)b * nx, *xb = x + (long)b * sd.nvar;
+  if (COOP && jt < ppad && jt >= npar) return;       // (padding lanes of the parameter group)
+  const int j = COOP ? (jt < ppad ? jt : jt - ppad + npar) : jt;
+  const double *pb = p + (long)b * npar, *xb = x + (long)b * sd.nvar;
   double *Pc = P + (long)b * sd.nnzP + sd.Pp[j], *Ac = A + (long)b * sd.nnzA + sd.Ap[j];
   double *qb = q + (long)b * n, *lb = l + (long)b * sd.m, *ub = u + (long)b * sd.m;
-  if (j < nx) {
+  if constexpr (PF) {
+    if (j < npar) {
+      // column p_k[i]: only frame k takes r_k.  Diagonal cost: H = {d2f/dr_k[i]2, d2f/dr_k[i] ds_k[i]} = {2 Q_k,i, -2 Q_k,i}, grad = -2 Q_k,i (s_k[i] - r_k[i]);
+      // general cost: one pass of frame k's gradient on dual numbers seeded on r_k[i], rows p_k first, then the frame's.  Rows l = u = p - p.
+      const int k = j / nx, i = j - k * nx;
+      const double *fr = xb + k * f, *rk = pb + k * nx;
+      const double pi = rk[i];
+      if constexpr (M::has_cost) {
+        constexpr int nl = f + nx;
+        const unsigned char *mk = sd.hmask + f + i;
+        Dual s[nx], uu[nu], rr[nx], g[nl];
+#pragma unroll
+        for (int a = 0; a < nx; a++) { s[a] = {fr[a], 0.0}; rr[a] = {rk[a], a == i ? 1.0 : 0.0}; }
+#pragma unroll
+        for (int a = 0; a < nu; a++) uu[a] = {fr[nx + a], 0.0};
+        if (M::has_term && k == N - 1) M::template LTG<Dual>(s, uu, rr, g); else M::template LG<Dual>(s, uu, rr, g);
+        int e = 0;
+        double gv = 0.0;
+#pragma unroll
+        for (int r = 0; r < nx; r++) { if (mk[(f + r) * nl]) Pc[e++] = g[f + r].d; gv = r == i ? g[f + r].v : gv; }
+#pragma unroll
+        for (int r = 0; r < f; r++) if (mk[r * nl]) Pc[e++] = g[r].d;
+        qb[j] = gv;
+      } else {
+        const double Qi = sd.Qk ? sd.Qk[j] : sd.Q[i];
+        Pc[0] = 2.0 * Qi; Pc[1] = -2.0 * Qi;
+        qb[j] = -2.0 * Qi * (fr[i] - pi);
+      }
+      Ac[0] = 1.0;
+      lb[j] = pi - pi; ub[j] = pi - pi;
+      return;
+    }
+  } else if (j < nx) {
     const double pi = pb[j];
     if constexpr (M::has_cost) {
       // general stage cost: column p_i of the Hessian = sum over the frames of d(grad l_k)/dr_i (dual numbers through the
@@ -93,8 +131,9 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
     lb[j] = pi - pi; ub[j] = pi - pi;
     return;
   }
-  const int jj = j - nx, k = jj / f, c = jj - k * f;
+  const int jj = j - npar, k = jj / f, c = jj - k * f;
   const double *fr = xb + k * f;
+  if constexpr (PF) pb += k * nx;               // frame k's reference r_k stands where p stood
   const double xv = fr[c];
   Dual s[nx], uu[nu];
 #pragma unroll
@@ -198,16 +237,16 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
 }
 
 // one wave per instance: lanes stride over the frames, butterfly reduction (fixed order => deterministic)
-template <class M>
+template <class M, bool PF = false>
 __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch, const double *__restrict__ p, const double *__restrict__ x,
                                                           double *__restrict__ fout, double *__restrict__ gout) {
   constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
   const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (b >= batch) return;
-  const double *pb = p + (long)b * nx, *xb = x + (long)b * sd.nvar;
+  const double *pb0 = p + (long)b * (PF ? sd.N * nx : nx), *xb = x + (long)b * sd.nvar;
   double cost = 0.0, gmax = 0.0;
   for (int k = lane; k < sd.N; k += 64) {
-    const double *fr = xb + k * f;
+    const double *fr = xb + k * f, *pb = PF ? pb0 + k * nx : pb0;      // (PF: frame k's reference r_k)
     double s[nx], uu[nu];
 #pragma unroll
     for (int i = 0; i < nx; i++) s[i] = fr[i];
@@ -259,16 +298,17 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
 
 
 // launchers shared by the zoo dispatch and generated libraries
-template <class M>
+template <class M, bool PF = false>
 inline hipError_t stage_launch_eval(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                                     const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st) {
   constexpr int f = M::nx + M::nu;
-  const long threads = (long)batch * ((sm_has_coop<M>::value && (64 % f == 0) && M::nx <= f) ? f * (sd.N + 1) : sd.n);
-  stage_eval_kernel<M><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u);
+  const int ppad = PF ? (sd.N * M::nx + f - 1) / f * f : f;
+  const long threads = (long)batch * ((sm_has_coop<M>::value && (64 % f == 0) && M::nx <= f) ? ppad + f * sd.N : sd.n);
+  stage_eval_kernel<M, PF><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u);
   return hipGetLastError();
 }
-template <class M>
+template <class M, bool PF = false>
 inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st) {
-  stage_merit_kernel<M><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, p, x, f, gmax);
+  stage_merit_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, p, x, f, gmax);
   return hipGetLastError();
 }

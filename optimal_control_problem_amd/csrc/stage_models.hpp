@@ -175,19 +175,23 @@ inline void sm_model_dims(int model, int *nx, int *nu) {
 //   A column j: row j; for a state column of frame k >= 1 the +1 of s_k in g_{k-1}[c]; for k < N-1 the nx rows of g_k;
 //   then the nh path-constraint rows of frame k (rows [p; x; g; h; r], h_k behind all dynamics rows), then the nk link-constraint
 //   rows r_{k-1} and r_k this frame takes part in (r_k = K(frame_k, frame_{k+1}), k < N - 1, behind all path rows)
-inline void sm_build_pattern(int nx, int nu, int N, int nh, int nk, std::vector<int> &Pp, std::vector<int> &Pi, std::vector<int> &Ap, std::vector<int> &Ai) {
-  const int f = nx + nu, np = nx, n = np + N * f;
+// pref (per-frame references, p = [r_0; ...; r_{N-1}], np = N nx): column p_k[i] has the rows p_k[i], s_k[i]; column s_k[i] the rows p_k[i], s_k[i];
+// A is the same with the larger identity block
+inline void sm_build_pattern(int nx, int nu, int N, int nh, int nk, std::vector<int> &Pp, std::vector<int> &Pi, std::vector<int> &Ap, std::vector<int> &Ai,
+                             bool pref = false) {
+  const int f = nx + nu, np = pref ? N * nx : nx, n = np + N * f;
   Pp.assign(1, 0); Ap.assign(1, 0); Pi.clear(); Ai.clear();
   for (int i = 0; i < np; i++) {
     Pi.push_back(i);
-    for (int k = 0; k < N; k++) Pi.push_back(np + k * f + i);
+    if (pref) Pi.push_back(np + (i / nx) * f + i % nx);
+    else for (int k = 0; k < N; k++) Pi.push_back(np + k * f + i);
     Pp.push_back((int)Pi.size());
     Ai.push_back(i); Ap.push_back((int)Ai.size());
   }
   for (int k = 0; k < N; k++)
     for (int c = 0; c < f; c++) {
       const int j = np + k * f + c;
-      if (c < nx) Pi.push_back(c);
+      if (c < nx) Pi.push_back(pref ? k * nx + c : c);
       Pi.push_back(j);
       Pp.push_back((int)Pi.size());
       Ai.push_back(j);
@@ -204,9 +208,26 @@ inline void sm_build_pattern(int nx, int nu, int N, int nh, int nk, std::vector<
 // the local variables [s; u; r] (row-major nl x nl, nl = f + nx, symmetric, diagonal set).  Both triangles, rows ascending:
 //   column p_i: rows p_r with mask[f + r][f + i], then per frame k the rows frame_k[r] with mask[r][f + i]
 //   column frame_k[c]: rows p_i with mask[f + i][c], then rows frame_k[r] with mask[r][c]
-inline void sm_build_cost_pattern(int nx, int nu, int N, const unsigned char *mask, std::vector<int> &Pp, std::vector<int> &Pi) {
-  const int f = nx + nu, np = nx, nl = f + np;
+// pref (sum_k l(s_k, u_k, r_k), the mask still over [s; u; r]): column p_k[i]: rows p_k[r] with mask[f + r][f + i], then rows frame_k[r] with mask[r][f + i];
+//   column frame_k[c]: rows p_k[i] with mask[f + i][c], then rows frame_k[r] with mask[r][c]
+inline void sm_build_cost_pattern(int nx, int nu, int N, const unsigned char *mask, std::vector<int> &Pp, std::vector<int> &Pi, bool pref = false) {
+  const int f = nx + nu, np = pref ? N * nx : nx, nl = f + nx;
   Pp.assign(1, 0); Pi.clear();
+  if (pref) {
+    for (int k = 0; k < N; k++)
+      for (int i = 0; i < nx; i++) {
+        for (int r = 0; r < nx; r++) if (mask[(f + r) * nl + f + i]) Pi.push_back(k * nx + r);
+        for (int r = 0; r < f; r++) if (mask[r * nl + f + i]) Pi.push_back(np + k * f + r);
+        Pp.push_back((int)Pi.size());
+      }
+    for (int k = 0; k < N; k++)
+      for (int c = 0; c < f; c++) {
+        for (int i = 0; i < nx; i++) if (mask[(f + i) * nl + c]) Pi.push_back(k * nx + i);
+        for (int r = 0; r < f; r++) if (mask[r * nl + c]) Pi.push_back(np + k * f + r);
+        Pp.push_back((int)Pi.size());
+      }
+    return;
+  }
   for (int i = 0; i < np; i++) {
     for (int r = 0; r < np; r++) if (mask[(f + r) * nl + f + i]) Pi.push_back(r);
     for (int k = 0; k < N; k++)

@@ -194,6 +194,11 @@ class StageOCP:
     # src/OptimalControlProblem.cpp:491-497) and its QP uses the exact Hessian (SQPOptimizationSolver.cpp:55-60); here the
     # callables are traced (codegen.trace_cost), the gradient is derived on the tape and the Hessian is its derivative.
     lcost = None; lterm = None
+    # opt-in trajectory tracking: one reference state per frame, p = [r_0; ...; r_{N-1}] (np = N nx), and frame k's cost terms take r_k:
+    # sum_k (s_k - r_k)' Q_k (s_k - r_k) + u_k' R_k u_k, or sum_k l(s_k, u_k, r_k).  The reference needs nothing special for it: setReference
+    # takes an SX of any size (src/OptimalControlProblem.cpp:570-572), computeOptimalTrajectory checks the size only (:85-90) and the user
+    # subtracts slice k in the cost of step k.  Variables stay [p; frames], rows [p; frames; dynamics; path; link]; only np grows.
+    per_frame_reference = False
 
     def __init__(self, N, dt, Q, R):
         self.N, self.dt = int(N), float(dt)
@@ -203,7 +208,8 @@ class StageOCP:
         self.varying_weights = self.Q.ndim == 2 or self.R.ndim == 2
         self.Qk = np.broadcast_to(self.Q, (int(N), self.nx)).copy(); self.Rk = np.broadcast_to(self.R, (int(N), self.nu)).copy()
         self.f = self.nx + self.nu
-        self.np = self.nx
+        self.pref = bool(self.per_frame_reference)
+        self.np = self.N * self.nx if self.pref else self.nx
         self.nvar = self.N * self.f
         self.n = self.np + self.nvar
         self.ngd = (self.N - 1) * self.nx                 # dynamics rows
@@ -230,14 +236,14 @@ class StageOCP:
         Pp = [0]; Pi = []
         self._P_pp = np.zeros(npp, np.int64); self._P_ps = np.zeros((N, nx), np.int64)  # value slots
         self._P_sp = np.zeros((N, nx), np.int64); self._P_ss = np.zeros((N, nx), np.int64); self._P_uu = np.zeros((N, nu), np.int64)
-        for i in range(npp):                       # column p_i
+        for i in range(npp):                       # column p_i (per-frame references: column p_k[i'], i = k nx + i', rows p_k[i'], s_k[i'])
             self._P_pp[i] = len(Pi); Pi.append(i)
-            for k in range(N):
-                self._P_sp[k, i] = len(Pi); Pi.append(npp + k * f + i)   # row s_k[i], col p_i
+            for k in ([i // nx] if self.pref else range(N)):
+                self._P_sp[k, i % nx] = len(Pi); Pi.append(npp + k * f + i % nx)   # row s_k[i], col p_i
             Pp.append(len(Pi))
         for k in range(N):
             for i in range(nx):                    # column s_k[i]
-                self._P_ps[k, i] = len(Pi); Pi.append(i)
+                self._P_ps[k, i] = len(Pi); Pi.append(k * nx + i if self.pref else i)
                 self._P_ss[k, i] = len(Pi); Pi.append(npp + k * f + i)
                 Pp.append(len(Pi))
             for i in range(nu):
@@ -282,6 +288,25 @@ class StageOCP:
         nx, f, N, npp = self.nx, self.f, self.N, self.np
         mk = self.cost_mask
         Pp = [0]; Pi = []; src = []
+        if self.pref:
+            # per-frame references: nothing sums over the frames, every entry is one element of frame k's Hessian over [s; u; r_k]
+            for k in range(N):
+                for i in range(nx):
+                    for r in range(nx):
+                        if mk[f + r, f + i]: Pi.append(k * nx + r); src.append((k, f + r, f + i))
+                    for r in range(f):
+                        if mk[r, f + i]: Pi.append(npp + k * f + r); src.append((k, r, f + i))
+                    Pp.append(len(Pi))
+            for k in range(N):
+                for c in range(f):
+                    for i in range(nx):
+                        if mk[f + i, c]: Pi.append(k * nx + i); src.append((k, f + i, c))
+                    for r in range(f):
+                        if mk[r, c]: Pi.append(npp + k * f + r); src.append((k, r, c))
+                    Pp.append(len(Pi))
+            self.Pp = np.asarray(Pp, np.int32); self.Pi = np.asarray(Pi, np.int32)
+            self._P_src = np.asarray(src, np.int64)
+            return
         for i in range(npp):
             for r in range(npp):
                 if mk[f + r, f + i]: Pi.append(r); src.append((-1, f + r, f + i))
@@ -301,7 +326,7 @@ class StageOCP:
 
     def _cost_inputs(self, p, x):
         s, u = self.frames(x)
-        r = np.broadcast_to(p[:, None, :], s.shape)
+        r = p.reshape(s.shape) if self.pref else np.broadcast_to(p[:, None, :], s.shape)
         return [s[..., i] for i in range(self.nx)] + [u[..., i] for i in range(self.nu)] + [r[..., i] for i in range(self.nx)]
 
     def _cost_eval(self, tape, ttape, inputs):
@@ -361,7 +386,7 @@ class StageOCP:
         if self.general_cost:
             return self._cost_eval(self._ltape, self._lttape, self._cost_inputs(p, x))[0].sum(axis=1)
         s, u = self.frames(x)
-        e = s - p[:, None, :]
+        e = s - (p.reshape(s.shape) if self.pref else p[:, None, :])
         if self.varying_weights:
             return np.einsum("bki,ki->b", e * e, self.Qk) + np.einsum("bki,ki->b", u * u, self.Rk)
         return np.einsum("bki,i->b", e * e, self.Q) + np.einsum("bki,i->b", u * u, self.R)
@@ -392,7 +417,7 @@ class StageOCP:
     def local_system(self, p, x, lbx, ubx, lbg, ubg):
         B = x.shape[0]; N, nx, nu, f, npp, n = self.N, self.nx, self.nu, self.f, self.np, self.n
         s, u = self.frames(x)
-        e = s - p[:, None, :]
+        e = s - (p.reshape(s.shape) if self.pref else p[:, None, :])
         q = np.zeros((B, n))
         if self.general_cost:
             grad, hess = self.cost_derivatives(p, x)
@@ -400,16 +425,19 @@ class StageOCP:
             P = np.zeros((B, len(self.Pi)))
             P[:, summed] = hess[:, :, src[summed, 1], src[summed, 2]].sum(axis=1)
             P[:, ~summed] = hess[:, src[~summed, 0], src[~summed, 1], src[~summed, 2]]
-            q[:, :npp] = grad[:, :, f:].sum(axis=1)
+            q[:, :npp] = grad[:, :, f:].reshape(B, -1) if self.pref else grad[:, :, f:].sum(axis=1)
             q[:, npp:] = grad[:, :, :f].reshape(B, -1)
         else:
             # Hessian values are constant
             Pv = np.zeros(len(self.Pi))
-            Pv[self._P_pp] = 2.0 * self.Qk.sum(axis=0) if self.varying_weights else 2.0 * N * self.Q
+            Pv[self._P_pp] = 2.0 * self.Qk.ravel() if self.pref else 2.0 * self.Qk.sum(axis=0) if self.varying_weights else 2.0 * N * self.Q
             Pv[self._P_sp] = -2.0 * self.Qk; Pv[self._P_ps] = -2.0 * self.Qk
             Pv[self._P_ss] = 2.0 * self.Qk; Pv[self._P_uu] = 2.0 * self.Rk
             P = np.broadcast_to(Pv, (B, len(Pv))).copy()
-            q[:, :npp] = -2.0 * (np.einsum("bki,ki->bi", e, self.Qk) if self.varying_weights else np.einsum("bki,i->bi", e, self.Q))
+            if self.pref:
+                q[:, :npp] = (-2.0 * e * self.Qk).reshape(B, -1)
+            else:
+                q[:, :npp] = -2.0 * (np.einsum("bki,ki->bi", e, self.Qk) if self.varying_weights else np.einsum("bki,i->bi", e, self.Q))
             qf = q[:, npp:].reshape(B, N, f)
             qf[:, :, :nx] = 2.0 * e * self.Qk; qf[:, :, nx:] = 2.0 * u * self.Rk
         J = self.dF(s[:, :-1, :], u[:, :-1, :])                 # [B, N-1, nx, f]

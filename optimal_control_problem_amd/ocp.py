@@ -36,8 +36,27 @@ class Var(Expr):
 
 
 class Reference(Expr):
-    def __init__(self, size):
+    def __init__(self, size, frames=None):
         self.size = size
+        self.frames = frames
+
+    def frame(self, k):
+        """slice k of a reference that stacks one block per frame, [r_0; ...; r_{N-1}]: what a tracking cost of step k subtracts.  In the
+        reference the user slices the SX that setReference returned (src/OptimalControlProblem.cpp:570-572)."""
+        if not self.frames or self.size % self.frames:
+            raise ValueError("a reference of size %d does not split into one block per frame (%s frames)" % (self.size, self.frames))
+        if k < 0 or k >= self.frames:
+            raise IndexError("Frame ID out of range")
+        w = self.size // self.frames
+        return ReferenceFrame(self, int(k), k * w, (k + 1) * w)
+
+
+class ReferenceFrame(Expr):
+    """slice [start, stop) of the reference parameter vector: block k of a per-frame reference (Reference.frame)"""
+
+    def __init__(self, ref, k, start, stop):
+        self.ref, self.k, self.start, self.stop = ref, k, start, stop
+        self.size = stop - start
 
 
 class Diff(Expr):
@@ -102,6 +121,8 @@ def evaluate_expression(e, X, p):
         return X[e.start:e.stop]
     if isinstance(e, Reference):
         return p
+    if isinstance(e, ReferenceFrame):
+        return p[e.start:e.stop]
     if isinstance(e, Diff):
         return evaluate_expression(e.a, X, p) - evaluate_expression(e.b, X, p)
     if isinstance(e, Dynamics):
@@ -217,8 +238,11 @@ def _as_scalar(v):
 class _FacadeStageOCP(models.StageOCP):
     name = "facade_ocp"
 
-    def __init__(self, nx, nu, N, dt, Q, R, F, lo, hi, h=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, k=None, nk=0, k_lo=None, k_hi=None):
+    def __init__(self, nx, nu, N, dt, Q, R, F, lo, hi, h=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, k=None, nk=0, k_lo=None, k_hi=None,
+                 per_frame_reference=False):
         self.nx, self.nu, self._F, self._lo, self._hi = nx, nu, F, lo, hi
+        if per_frame_reference:
+            self.per_frame_reference = True
         self._h, self.nh, self.h_lo, self.h_hi = h, int(nh), h_lo, h_hi
         self._k, self.nk, self.k_lo, self.k_hi = k, int(nk), k_lo, k_hi
         self.lcost, self.lterm = lcost, lterm
@@ -287,7 +311,7 @@ class OptimalControlProblem:
 
     # -- builders (:444-497,574-600)
     def setReference(self, size):
-        self.reference_ = Reference(int(size))
+        self.reference_ = Reference(int(size), self.OCPConfigPtr_.getHorizon())
         return self.reference_
 
     def getReference(self):
@@ -345,7 +369,8 @@ class OptimalControlProblem:
         model = self.model_ if self.model_ is not None else self._compile_stage_model()
         h_lo, h_hi = model.path_bounds() if model.nh else (None, None)
         tape = codegen.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
-                             lcost=model.lcost if model.general_cost else None, lterm=model.lterm if model.general_cost else None)
+                             lcost=model.lcost if model.general_cost else None, lterm=model.lterm if model.general_cost else None,
+                             **({"per_frame_reference": True} if model.per_frame_reference else {}))
         return codegen.build_device_library(tape)
 
     def getConstraints(self):
@@ -398,6 +423,10 @@ class OptimalControlProblem:
             ev = GeneralEvaluator(self.model_, library=self.generalLibrary_)
             self.OSQPSolverPtr_ = DeviceSQPOptimizationSolver(self.model_, options, batch=self.batch, evaluator=ev)
         elif self.deviceResident and self._qp_solver is None and not self.generalPath_:
+            if self.model_.per_frame_reference:
+                # a per-frame reference is a block of N nx pinned parameters: in full form the QP leaves the on-chip kernel families, with the
+                # pinned rows eliminated it returns to them without a hub.  Tracking problems only: every other problem keeps its handle.
+                options["presolve_fixed_rows"] = True
             self.OSQPSolverPtr_ = DeviceSQPOptimizationSolver(self.model_, options, batch=self.batch)
         else:
             self.OSQPSolverPtr_ = SQPOptimizationSolver(self.model_, options, batch=self.batch, qp_solver=self._qp_solver)
@@ -438,6 +467,16 @@ class OptimalControlProblem:
         Qk = np.zeros((N, nx)); Rk = np.zeros((N, nu))        # per-step weights: terminal costs and ramps are ordinary here
         seenQ, seenR = set(), set()
         lcost = lterm = None
+        # tracking stage pattern: the reference stacks one state per frame (size N nx) and every term of step k takes reference.frame(k);
+        # kinds collects what the terms take ("whole" reference or their own "frame"), a mixture is no stage pattern
+        kinds = set()
+
+        def ref_kind(r, step):
+            if r is self.reference_:
+                return "whole"
+            if isinstance(r, ReferenceFrame) and r.ref is self.reference_ and r.k == step and r.size == nx:
+                return "frame"
+            return None
         general = [c for c in self.costs_ if isinstance(c, StageCost)]
         if general:
             # general stage cost: one StageCost per frame, the same function on every frame but (optionally) the last
@@ -445,8 +484,9 @@ class OptimalControlProblem:
                 raise NotImplementedError("general costs: exactly one StageCost term per frame and no other cost terms")
             general.sort(key=lambda c: c.state.step)
             for k, c in enumerate(general):
-                if not (c.state.name == s0.name and c.inp.name == u0.name and c.inp.step == k and c.reference is self.reference_):
-                    raise NotImplementedError("a StageCost takes the state, the input and the reference of its own frame")
+                if not (c.state.name == s0.name and c.inp.name == u0.name and c.inp.step == k and ref_kind(c.reference, k)):
+                    raise NotImplementedError("a StageCost takes the state, the input and the reference (or reference.frame(k)) of its own frame")
+                kinds.add(ref_kind(c.reference, k))
             lcost = general[0].l
             if any(c.l != lcost for c in general[:-1]):
                 raise NotImplementedError("the stage cost must be the same function on every frame except the last")
@@ -456,7 +496,8 @@ class OptimalControlProblem:
             kind, w, e = term if isinstance(term, tuple) else (None, None, None)
             if kind != "weighted_square":
                 raise NotImplementedError("only addVectorCost terms and StageCost terms are compiled")
-            if isinstance(e, Diff) and isinstance(e.a, Var) and isinstance(e.b, Reference) and e.a.name == s0.name:
+            if isinstance(e, Diff) and isinstance(e.a, Var) and e.a.name == s0.name and ref_kind(e.b, e.a.step) and self.reference_ is not None:
+                kinds.add(ref_kind(e.b, e.a.step))
                 Qk[e.a.step] += w; seenQ.add(e.a.step)        # repeated terms on one step add up, like the SX sum (:491-497)
             elif isinstance(e, Var) and e.name == u0.name:
                 Rk[e.step] += w; seenR.add(e.step)
@@ -466,7 +507,12 @@ class OptimalControlProblem:
         Q, R = (Qk[0], Rk[0]) if same else (Qk, Rk)
         if seenQ != set(range(N)) or seenR != set(range(N)):
             raise NotImplementedError("tracking and input costs must be added for every step")
-        if self.reference_ is None or self.reference_.size != nx:
+        if len(kinds) > 1:
+            raise NotImplementedError("tracking terms must all take the whole reference or all take reference.frame(k) of their own step")
+        tracking = kinds == {"frame"}
+        if tracking and self.reference_.size != N * nx:
+            raise NotImplementedError("a per-frame reference must stack one state per frame")
+        if not tracking and (self.reference_ is None or self.reference_.size != nx):
             raise NotImplementedError("reference must have the state's dimension")
         h = None; nh = 0; h_lo = h_hi = None
         if path:
@@ -491,7 +537,8 @@ class OptimalControlProblem:
                 raise NotImplementedError("the link constraint's bounds must be the same on every stage")
         # rows of the compiled model: dynamics rows in frame order, then the path rows in frame order, then the link rows in stage order
         self._row_order = [i for _, i in sorted((self.constraints_[i].a.step, i) for i in dyn_idx)] + path_idx + link_idx
-        return _FacadeStageOCP(nx, nu, N, cfg.getDt(), Q, R, F, cfg.getLowerBounds()[0], cfg.getUpperBounds()[0], h, nh, h_lo, h_hi, lcost, lterm, kf, nk, k_lo, k_hi)
+        return _FacadeStageOCP(nx, nu, N, cfg.getDt(), Q, R, F, cfg.getLowerBounds()[0], cfg.getUpperBounds()[0], h, nh, h_lo, h_hi, lcost, lterm, kf, nk, k_lo, k_hi,
+                               per_frame_reference=tracking)
 
     # -- computeOptimalTrajectory (:78-222), CUDA_SQP arm
     def computeOptimalTrajectory(self, frame, reference):

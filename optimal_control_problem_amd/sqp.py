@@ -147,19 +147,23 @@ class DeviceSQPOptimizationSolver:
         self.sqp_tol = float(options.get("sqp_tol", 0.0) or 0.0)      # opt-in convergence stop, see the module docstring
         # extension: OSQP's `polishing` on every QP of the loop (mpcqp_set_polish); the reference leaves it off (:80-85), and so does the default
         self.polish_qp = bool(options.get("polish_qp", False))
+        # extension (opt-in): the QP handle comes from mpcqp_create_presolved -- every singleton row of A with l = u in the first local system (the
+        # parameter block's rows p - p, the first frame as computeOptimalTrajectory pins it) is found and its variable substituted before the solve.
+        # The handle is therefore created at the first getOptimalSolution, after the first evaluation.  It inherits that entry's promise: the rows
+        # found fixed keep l = u in every later call -- true for p always, and for the first frame as long as it stays pinned; an instance that
+        # breaks it comes back MPCQP_UNSOLVED / NaN (include/mpcqp.h).  Warm start, carried rho, keep_scaling and polish_qp go through the reduced
+        # handle's forwarding.  Meant for per-frame references, whose N nx parameters push the full form off the on-chip kernels.
+        self.presolve_fixed_rows = bool(options.get("presolve_fixed_rows", False))
         self.iterations_done = 0
         self.step_max = None
         self._kept = False
         self._scaled = False                             # keep_scaling: a full set-up has run on the handle
         self.batch = int(batch)
         self.ev = evaluator if evaluator is not None else StageEvaluator(nlp, device=device, codegen=codegen)
-        # reference SQPOptimizationSolver.cpp:80-85
-        self.qp = BatchQP(self.ev.n, self.ev.m, self.batch, self.ev.Pp, self.ev.Pi, self.ev.Ap, self.ev.Ai,
-                          eps_abs=1e-3, eps_rel=1e-3, max_iter=10000, warm_start=1 if self.warm_start_admm else 0, device=device)
-        if self.constant_matrices or self.keep_scaling:
-            self.qp.keep_workspace(True)
-        if self.polish_qp:
-            self.qp.set_polish(True)
+        self._device = device
+        self.qp = None
+        if not self.presolve_fixed_rows:
+            self._create_qp(None)
         self.dev = torch.device("cuda", torch.cuda.current_device() if device < 0 else device)
         mk = lambda w, dt=torch.float64: torch.zeros((self.batch, w), dtype=dt, device=self.dev)
         self.x = mk(self.ev.nvar)                        # persists across calls like result_ (:88-91)
@@ -171,6 +175,16 @@ class DeviceSQPOptimizationSolver:
         self.admm_iterations = []
         self.f = None; self.gmax = None
         self._have_start = False                         # like last_qp_info of the host loop: survives across calls
+
+    def _create_qp(self, presolve_bounds):
+        from .batch_qp import BatchQP
+        # reference SQPOptimizationSolver.cpp:80-85
+        self.qp = BatchQP(self.ev.n, self.ev.m, self.batch, self.ev.Pp, self.ev.Pi, self.ev.Ap, self.ev.Ai, presolve_bounds=presolve_bounds,
+                          eps_abs=1e-3, eps_rel=1e-3, max_iter=10000, warm_start=1 if self.warm_start_admm else 0, device=self._device)
+        if self.constant_matrices or self.keep_scaling:
+            self.qp.keep_workspace(True)
+        if self.polish_qp:
+            self.qp.set_polish(True)
 
     def setInitialGuess(self, x):
         """extension: the reference ignores arg["x0"] and starts from zero (:88-91); this overwrites the stored iterate"""
@@ -197,6 +211,9 @@ class DeviceSQPOptimizationSolver:
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         for i in range(self.stepNum_):
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
+            if self.qp is None:                          # presolve_fixed_rows: the fixed rows are read off this first system's bounds
+                torch.cuda.current_stream(self.dev).synchronize()
+                self._create_qp((self.ls["l"], self.ls["u"]))
             if self.constant_matrices and self._kept:
                 self.qp.update_vectors(self.ls["q"], self.ls["l"], self.ls["u"])
             elif self.keep_scaling and self._scaled:
@@ -246,4 +263,6 @@ class DeviceSQPOptimizationSolver:
         return {"x": self.x.cpu().numpy(), "f": self.f.cpu().numpy()}
 
     def close(self):
-        self.qp.close(); self.ev.close()
+        if self.qp is not None:
+            self.qp.close()
+        self.ev.close()

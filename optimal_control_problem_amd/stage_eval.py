@@ -25,6 +25,7 @@ def _bind(L):
     L.mpcqp_stage_default.argtypes = [C.c_int, C.c_int, C.POINTER(StageDesc)]
     L.mpcqp_stage_create.argtypes = [C.POINTER(StageDesc), C.POINTER(vp)]
     L.mpcqp_stage_create_user.argtypes = [C.POINTER(StageDesc), C.c_char_p, C.POINTER(vp)]
+    L.mpcqp_stage_create_tracking.argtypes = [C.POINTER(StageDesc), C.c_char_p, C.POINTER(vp)]
     L.mpcqp_stage_destroy.argtypes = [vp]
     L.mpcqp_stage_destroy.restype = None
     L.mpcqp_stage_set_weights.argtypes = [vp, dp, dp]
@@ -62,8 +63,10 @@ class StageEvaluator:
         """model: a models.StageOCP instance (its N, dt, Q, R are used), or name + horizon for the library's defaults
         (mpcqp_stage_default).  Built-in zoo models run the library's compiled functors; any other model -- or any model
         with codegen=True -- has its discrete map model.F traced, emitted as a functor and compiled for gfx950
-        (optimal_control_problem_amd.codegen; the reference's gen_code / load_lib flow)."""
+        (optimal_control_problem_amd.codegen; the reference's gen_code / load_lib flow).  A model with per_frame_reference (trajectory
+        tracking, p = [r_0; ...; r_{N-1}]) gets its handle from mpcqp_stage_create_tracking."""
         L = _bind(_lib.lib())
+        self.per_frame_reference = bool(getattr(model, "per_frame_reference", False)) if model is not None else False
         d = StageDesc()
         self.library = None
         if model is not None:
@@ -92,7 +95,8 @@ class StageEvaluator:
                 h_lo, h_hi = model.path_bounds()
                 self.tape = cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
                                      lcost=model.lcost if general else None, lterm=model.lterm if general else None,
-                                     kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None)
+                                     kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
+                                     **({"per_frame_reference": True} if self.per_frame_reference else {}))
                 self.library = cg.build_device_library(self.tape)
             else:
                 for i, v in enumerate(model_params(model)): d.par[i] = float(v)
@@ -101,7 +105,9 @@ class StageEvaluator:
         d.device = int(device)
         self.desc = d
         self._h = C.c_void_p()
-        if self.library is not None:
+        if self.per_frame_reference:
+            _lib.check(L.mpcqp_stage_create_tracking(C.byref(d), self.library.encode() if self.library is not None else None, C.byref(self._h)))
+        elif self.library is not None:
             _lib.check(L.mpcqp_stage_create_user(C.byref(d), self.library.encode(), C.byref(self._h)))
         else:
             _lib.check(L.mpcqp_stage_create(C.byref(d), C.byref(self._h)))
