@@ -351,6 +351,41 @@ int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *
  * when given, instances whose QP status is not MPCQP_SOLVED / _SOLVED_INACCURATE / _MAX_ITER_REACHED keep their x. */
 int mpcqp_stage_step(mpcqp_stage *s, int batch, double alpha, const double *dw, double *x, double *step_max,
                      const int *status, void *stream);
+/* Receding-horizon hand-over between two MPC ticks, one kernel for the batch.  In the reference the step between two calls of
+ * computeOptimalTrajectory is the caller's: the new first frame is pinned through lbx / ubx (src/OptimalControlProblem.cpp:93-96), the plant is
+ * the caller's own code, and the next solve starts from the previous trajectory unshifted because result_ persists (SQPOptimizationSolver.cpp:88-91,
+ * OptimalControlProblem.cpp:113).  Here, per instance b, with X_k = [s_k; u_k] the frames of x_in, f = nx + nu, and ok = (status == NULL or
+ * status[b] is MPCQP_SOLVED / _SOLVED_INACCURATE / _MAX_ITER_REACHED, the set mpcqp_stage_step uses):
+ *   plant       s+ = s_meas[b] when s_meas is given, else F(s_0, u_0) by the handle's own discrete map, plus w[b] when w is given;
+ *               u+ = ok ? u_1 : u_0 (a failed QP holds the applied input)
+ *   trajectory  x_out = [s+; u+], X_2, ..., X_{N-1}, tail, with tail = X_{N-1} (MPCQP_TAIL_REPEAT) or [F(s_{N-1}, u_{N-1}); u_{N-1}] (MPCQP_TAIL_ROLLOUT)
+ *   pin         the first f entries of lbx[b] and ubx[b] become [s+; u+], in place; nothing else in those arrays is touched
+ *   references  tracking handles only: p_out = r_1, ..., r_{N-1}, then r_new[b] (NULL: r_{N-1} again)
+ *   QP start    dw_out [batch * n] from dw_in (both or neither): the parameter part copied (tracking: shifted by nx, zero last block), the frames
+ *               shifted by f with a zero last block; y_out [batch * m] from y_in (both or neither): each row block of [p; x; dynamics; path; link]
+ *               shifted by its own stage width (nx or as dw; f; nx; nh; nk) with a zero last block.  An instance that is not ok gets all zeros
+ *               (its dw and y are NaN after an infeasible QP).
+ *   logs        applied [batch * f] = X_0; stage_cost [batch] = the k = 0 term of mpcqp_stage_merit's objective at X_0, against r_0 on a tracking
+ *               handle and against p[b] [batch * nx] otherwise (p is read for this only and must be given with stage_cost there)
+ * All pointers are device memory; x_in, x_out, lbx, ubx are required, the rest may be NULL.  Out of place: x_out != x_in, dw_out != dw_in,
+ * y_out != y_in, p_out != p_in.  Asynchronous on `stream`.  MPCQP_ERR_ARG for a bad argument; MPCQP_ERR_LIMIT for a generated library
+ * from before this entry (it does not export mpcqp_user_advance; regenerate it). */
+#define MPCQP_TAIL_REPEAT 0
+#define MPCQP_TAIL_ROLLOUT 1
+typedef struct mpcqp_stage_advance_args {
+  const double *x_in; double *x_out;   /* [batch * horizon * f]                                      */
+  double *lbx, *ubx;                   /* [batch * horizon * f], first f entries per instance written */
+  const int *status;                   /* [batch], optional                                          */
+  const double *s_meas, *w;            /* [batch * nx], optional, at most one of them                */
+  const double *p;                     /* [batch * nx], non-tracking handles, for stage_cost only    */
+  const double *p_in; double *p_out;   /* [batch * horizon * nx], tracking handles (required there)  */
+  const double *r_new;                 /* [batch * nx], tracking handles, optional                   */
+  const double *dw_in; double *dw_out; /* [batch * n], optional pair                                 */
+  const double *y_in; double *y_out;   /* [batch * m], optional pair                                 */
+  double *applied, *stage_cost;        /* [batch * f], [batch], optional                             */
+  int tail;                            /* MPCQP_TAIL_*                                               */
+} mpcqp_stage_advance_args;
+int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Local-system evaluation on device for a general (non-stage) NLP.

@@ -6,7 +6,7 @@ the library or a gfx950 device is missing (there is no CPU fallback)."""
 from . import models  # noqa: F401
 
 __all__ = ["models", "BatchQP", "StageQP", "CuCaQP", "SQPOptimizationSolver", "DeviceSQPOptimizationSolver", "StageEvaluator",
-           "OptimalControlProblem", "OCPConfig"]
+           "OptimalControlProblem", "OCPConfig", "ClosedLoopMPC"]
 
 
 def __getattr__(name):
@@ -28,4 +28,7 @@ def __getattr__(name):
     if name in ("OptimalControlProblem", "OCPConfig"):
         from . import ocp
         return getattr(ocp, name)
+    if name == "ClosedLoopMPC":
+        from .mpc import ClosedLoopMPC
+        return ClosedLoopMPC
     raise AttributeError(name)

@@ -604,6 +604,10 @@ int mpcqp_user_eval(const StageDev *sd, int batch, const double *p, const double
 int mpcqp_user_merit(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
   return (int)stage_launch_merit<SmUser>(*sd, batch, p, x, f, gmax, (hipStream_t)stream);
 }
+// the hand-over between two MPC ticks (mpcqp_stage_advance)
+int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream) {
+  return (int)stage_launch_advance<SmUser>(*sd, batch, *a, (hipStream_t)stream);
+}
 }
 '''
 
@@ -721,6 +725,7 @@ def device_source(tape):
     src = _DEVICE_TMPL % {"functor": emit_functor(tape)}
     if getattr(tape, "pref", False):
         src = src.replace("stage_launch_eval<SmUser>", "stage_launch_eval<SmUser, SmUser::pref>").replace("stage_launch_merit<SmUser>", "stage_launch_merit<SmUser, SmUser::pref>")
+        src = src.replace("stage_launch_advance<SmUser>", "stage_launch_advance<SmUser, SmUser::pref>")
         src = src.replace("int mpcqp_user_nh() {", "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\nint mpcqp_user_nh() {")
     return src
 

@@ -21,6 +21,7 @@
 typedef int (*user_eval_fn)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *,
                             const double *, double *, double *, double *, double *, double *, void *);
 typedef int (*user_merit_fn)(const StageDev *, int, const double *, const double *, double *, double *, void *);
+typedef int (*user_advance_fn)(const StageDev *, int, const mpcqp_stage_advance_args *, void *);
 
 struct mpcqp_stage {
   mpcqp_stage_desc desc;
@@ -34,6 +35,7 @@ struct mpcqp_stage {
   void *user_lib = nullptr;           // dlopen handle of a generated dynamics library (model == MPCQP_MODEL_USER)
   user_eval_fn user_eval = nullptr;
   user_merit_fn user_merit = nullptr;
+  user_advance_fn user_advance = nullptr;   // optional export: libraries generated before mpcqp_stage_advance have none
   bool general_cost = false;          // the library carries its own stage cost: Q, R and mpcqp_stage_set_weights do not apply
 };
 
@@ -181,6 +183,7 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   if (nk > 0) kb(k_lo, k_hi);
   mpcqp_stage *s = new mpcqp_stage();
   s->user_lib = lib; s->user_eval = ev; s->user_merit = me;
+  s->user_advance = (user_advance_fn)dlsym(lib, "mpcqp_user_advance");
   mpcqp_stage_desc dd = *d; dd.model = MPCQP_MODEL_USER;
   std::vector<unsigned char> mask((size_t)(2 * nx + nu) * (2 * nx + nu));
   auto cf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_cost");
@@ -302,6 +305,41 @@ int mpcqp_stage_step(mpcqp_stage *s, int batch, double alpha, const double *dw, 
   if (batch <= 0 || !dw || !x) return mpcqp_set_error(MPCQP_ERR_ARG, "bad batch or null data pointer");
   MPCQP_HIPCHK(hipSetDevice(s->device));
   MPCQP_HIPCHK(mpcqp_launch_step(batch, s->sd.nvar, s->sd.n, s->sd.np, alpha, dw, x, step_max, status, (hipStream_t)stream));
+  return MPCQP_OK;
+}
+
+int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (!a->x_in || !a->x_out || !a->lbx || !a->ubx) return mpcqp_set_error(MPCQP_ERR_ARG, "x_in, x_out, lbx and ubx are required");
+  if (a->x_out == a->x_in) return mpcqp_set_error(MPCQP_ERR_ARG, "the shift is out of place: x_out must differ from x_in");
+  if ((a->dw_in == nullptr) != (a->dw_out == nullptr) || (a->y_in == nullptr) != (a->y_out == nullptr))
+    return mpcqp_set_error(MPCQP_ERR_ARG, "give both dw_in and dw_out (y_in and y_out) or neither");
+  if ((a->dw_out && a->dw_out == a->dw_in) || (a->y_out && a->y_out == a->y_in))
+    return mpcqp_set_error(MPCQP_ERR_ARG, "the shift is out of place: dw_out / y_out must differ from dw_in / y_in");
+  if (s->sd.pref) {
+    if (!a->p_in || !a->p_out) return mpcqp_set_error(MPCQP_ERR_ARG, "a tracking handle needs p_in and p_out");
+    if (a->p_out == a->p_in) return mpcqp_set_error(MPCQP_ERR_ARG, "the shift is out of place: p_out must differ from p_in");
+    if (a->p) return mpcqp_set_error(MPCQP_ERR_ARG, "p belongs to non-tracking handles; a tracking handle takes its references from p_in");
+  } else {
+    if (a->p_in || a->p_out || a->r_new) return mpcqp_set_error(MPCQP_ERR_ARG, "p_in, p_out and r_new belong to tracking handles");
+    if (a->stage_cost && !a->p) return mpcqp_set_error(MPCQP_ERR_ARG, "stage_cost needs the reference p");
+  }
+  if (a->w && a->s_meas) return mpcqp_set_error(MPCQP_ERR_ARG, "a disturbance applies to the simulated plant only: give w or s_meas, not both");
+  if (a->tail != MPCQP_TAIL_REPEAT && a->tail != MPCQP_TAIL_ROLLOUT) return mpcqp_set_error(MPCQP_ERR_ARG, "unknown tail");
+  if (s->sd.model == MPCQP_MODEL_USER && !s->user_advance)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_advance (generated before this entry); regenerate it");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  switch (s->sd.model) {
+    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_advance<SmDoubleIntegrator, true>(s->sd, batch, *a, st) : stage_launch_advance<SmDoubleIntegrator>(s->sd, batch, *a, st); break;
+    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_advance<SmQuadrotor, true>(s->sd, batch, *a, st) : stage_launch_advance<SmQuadrotor>(s->sd, batch, *a, st); break;
+    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_advance<SmCartPole, true>(s->sd, batch, *a, st) : stage_launch_advance<SmCartPole>(s->sd, batch, *a, st); break;
+    case MPCQP_MODEL_USER: e = (hipError_t)s->user_advance(&s->sd, batch, a, stream); break;
+  }
+  MPCQP_HIPCHK(e);
   return MPCQP_OK;
 }
 

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "stage_models.hpp"
+#include "../../include/mpcqp.h"
 
 #define STAGE_ABI_VERSION 7
 
@@ -296,6 +297,108 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
   if (lane == 0) { if (fout) fout[b] = cost; if (gout) gout[b] = gmax; }
 }
 
+// out[base + i] = in[base + i + width] over `count` blocks of `width` entries, the last block zero; all zero for an instance that is not ok
+__device__ __forceinline__ void stage_shift_block(double *__restrict__ out, const double *__restrict__ in, int base, int width, int count, bool ok, int lane) {
+  const int tot = width * count, keep = tot - width;
+  for (int i = lane; i < tot; i += 64) {
+    double v = 0.0;
+    if (ok && i < keep) v = in[base + i + width];
+    out[base + i] = v;
+  }
+}
+
+// Receding-horizon hand-over between two ticks (mpcqp_stage_advance).  One wave per instance like the merit kernel, lanes striding over the
+// elements of every array: pure data movement but for two runs of F<double> -- the plant step F(s_0, u_0) on lane 0 and the rollout tail
+// F(s_{N-1}, u_{N-1}) on lane 1, one pass of the wave for both -- and the k = 0 cost term on lane 0.  Their nx results go by wave shuffle to the
+// lanes c < nx that store them, so every store stream is contiguous.  No LDS, no atomics, one writer per output element.
+template <class M, bool PF = false>
+__global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int batch, mpcqp_stage_advance_args a) {
+  constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
+  static_assert(f <= 64, "a frame is stored by one pass of the wave");
+  const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (b >= batch) return;
+  const int N = sd.N, nvar = sd.nvar, np = sd.np, n = sd.n, last = (N - 1) * f;
+  const double *xi = a.x_in + (long)b * nvar;
+  double *xo = a.x_out + (long)b * nvar;
+  bool ok = true;
+  if (a.status) { const int s = a.status[b]; ok = s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
+  const bool rollout = a.tail == MPCQP_TAIL_ROLLOUT;
+  double Fo[nx];
+#pragma unroll
+  for (int i = 0; i < nx; i++) Fo[i] = 0.0;
+  if (lane < 2) {
+    const double *fr = xi + (lane == 0 ? 0 : last);
+    double s[nx], uu[nu];
+#pragma unroll
+    for (int i = 0; i < nx; i++) s[i] = fr[i];
+#pragma unroll
+    for (int i = 0; i < nu; i++) uu[i] = fr[nx + i];
+    if (lane == 0 ? a.s_meas == nullptr : rollout) M::template F<double>(sd.par, sd.dt, s, uu, Fo);
+    if (lane == 0 && a.stage_cost) {
+      // the k = 0 term of stage_merit_kernel's objective, in its order of operations
+      const double *pb = PF ? a.p_in + (long)b * np : a.p + (long)b * nx;
+      double cost = 0.0;
+      if constexpr (M::has_cost) {
+        double rr[nx], lv[1];
+#pragma unroll
+        for (int i = 0; i < nx; i++) rr[i] = pb[i];
+        M::template L<double>(s, uu, rr, lv);
+        cost += lv[0];
+      } else {
+#pragma unroll
+        for (int i = 0; i < nx; i++) { const double e = s[i] - pb[i]; cost += e * e * (sd.Qk ? sd.Qk[i] : sd.Q[i]); }
+#pragma unroll
+        for (int i = 0; i < nu; i++) cost += uu[i] * uu[i] * (sd.Rk ? sd.Rk[i] : sd.R[i]);
+      }
+      a.stage_cost[b] = cost;
+    }
+  }
+  double v0 = 0.0, vt = 0.0;      // lane c < nx: element c of F(X_0) and of F(X_{N-1})
+#pragma unroll
+  for (int i = 0; i < nx; i++) {
+    const double t0 = __shfl(Fo[i], 0, 64), t1 = __shfl(Fo[i], 1, 64);
+    if (lane == i) { v0 = t0; vt = t1; }
+  }
+  if (lane < f) {
+    const int c = lane;
+    double v;
+    if (c < nx) {
+      if (a.s_meas) v = a.s_meas[(long)b * nx + c];
+      else { v = v0; if (a.w) v += a.w[(long)b * nx + c]; }
+    } else {
+      v = ok ? xi[f + c] : xi[c];
+    }
+    xo[c] = v; a.lbx[(long)b * nvar + c] = v; a.ubx[(long)b * nvar + c] = v;
+    if (a.applied) a.applied[(long)b * f + c] = xi[c];
+    double t = xi[last + c];
+    if (rollout && c < nx) t = vt;
+    xo[last + c] = t;
+  }
+  for (int i = f + lane; i < last; i += 64) xo[i] = xi[i + f];
+  if constexpr (PF) {
+    const double *pi = a.p_in + (long)b * np;
+    double *po = a.p_out + (long)b * np;
+    for (int i = lane; i < np; i += 64) po[i] = i < np - nx ? pi[i + nx] : a.r_new ? a.r_new[(long)b * nx + i - (np - nx)] : pi[i];
+  }
+  if (a.dw_out) {
+    const double *di = a.dw_in + (long)b * n;
+    double *dout = a.dw_out + (long)b * n;
+    if constexpr (PF) stage_shift_block(dout, di, 0, nx, N, ok, lane);
+    else if (lane < nx) dout[lane] = ok ? di[lane] : 0.0;
+    stage_shift_block(dout, di, np, f, N, ok, lane);
+  }
+  if (a.y_out) {
+    const double *yi = a.y_in + (long)b * sd.m;
+    double *yo = a.y_out + (long)b * sd.m;
+    if constexpr (PF) stage_shift_block(yo, yi, 0, nx, N, ok, lane);
+    else if (lane < nx) yo[lane] = ok ? yi[lane] : 0.0;
+    stage_shift_block(yo, yi, np, f, N, ok, lane);
+    stage_shift_block(yo, yi, n, nx, N - 1, ok, lane);
+    stage_shift_block(yo, yi, n + sd.ngd, sd.nh, N, ok, lane);
+    stage_shift_block(yo, yi, n + sd.ngd + N * sd.nh, sd.nk, N - 1, ok, lane);
+  }
+}
+
 
 // launchers shared by the zoo dispatch and generated libraries
 template <class M, bool PF = false>
@@ -310,5 +413,10 @@ inline hipError_t stage_launch_eval(const StageDev &sd, int batch, const double 
 template <class M, bool PF = false>
 inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st) {
   stage_merit_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, p, x, f, gmax);
+  return hipGetLastError();
+}
+template <class M, bool PF = false>
+inline hipError_t stage_launch_advance(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st) {
+  stage_advance_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a);
   return hipGetLastError();
 }

@@ -478,6 +478,72 @@ class StageOCP:
             lbg[:, self.ngd + self.N * self.nh:] = lo.ravel(); ubg[:, self.ngd + self.N * self.nh:] = hi.ravel()
         return lbx, ubx, lbg, ubg
 
+    # -- the hand-over between two MPC ticks (include/mpcqp.h, mpcqp_stage_advance; csrc/stage_kernels.hpp stage_advance_kernel) ----------
+    STATUS_OK = (1, 2, 7)      # solved, solved_inaccurate, max_iter_reached: the QP returned a point (what mpcqp_stage_step takes too)
+
+    def _shift_blocks(self, v, base, width, count, ok):
+        """block k of `count` blocks of `width` entries from `base` becomes block k + 1, the last one zero; all zero where not ok"""
+        out = np.zeros((v.shape[0], width * count))
+        keep = width * (count - 1)
+        out[:, :keep] = v[:, base + width:base + width + keep]
+        out[~ok] = 0.0
+        return out
+
+    def advance(self, x, lbx, ubx, status=None, s_meas=None, w=None, tail="rollout", p=None, r_new=None, dw=None, y=None):
+        """Host statement of mpcqp_stage_advance, out of place: x, lbx, ubx [B, nvar] -> dict with the shifted trajectory `x`, the re-pinned
+        `lbx`, `ubx`, `applied` = frame 0 of x, and -- when their inputs are given -- `p` (per-frame references [B, N nx], last block r_new or
+        repeated), `dw` [B, n], `y` [B, m] (every row block shifted by its own stage width, zero last block, all zero where the QP failed) and
+        `stage_cost` (the k = 0 term of `objective`; p is the shared reference [B, nx] or the per-frame block).  The plant is s_meas when
+        given, else F(s_0, u_0) (+ w); the input u_1 where status is in STATUS_OK (or status is None), else u_0 is held."""
+        if tail not in ("repeat", "rollout"):
+            raise ValueError("tail must be 'repeat' or 'rollout'")
+        if s_meas is not None and w is not None:
+            raise ValueError("give w or s_meas, not both")
+        B, N, nx, f, npp, n = x.shape[0], self.N, self.nx, self.f, self.np, self.n
+        X = np.asarray(x, float).reshape(B, N, f)
+        ok = np.ones(B, bool) if status is None else np.isin(np.asarray(status), self.STATUS_OK)
+        if s_meas is not None:
+            sp = np.array(s_meas, float).reshape(B, nx)
+        else:
+            sp = np.asarray(self.F(X[:, 0, :nx], X[:, 0, nx:]), float)
+            if w is not None:
+                sp = sp + np.asarray(w, float).reshape(B, nx)
+        up = np.where(ok[:, None], X[:, 1, nx:], X[:, 0, nx:])
+        Xo = np.empty_like(X)
+        Xo[:, 0, :nx] = sp; Xo[:, 0, nx:] = up
+        Xo[:, 1:N - 1] = X[:, 2:]
+        Xo[:, N - 1] = X[:, N - 1]
+        if tail == "rollout":
+            Xo[:, N - 1, :nx] = self.F(X[:, N - 1, :nx], X[:, N - 1, nx:])
+        out = {"x": Xo.reshape(B, -1), "lbx": np.array(lbx, float), "ubx": np.array(ubx, float), "applied": X[:, 0].copy()}
+        out["lbx"][:, :f] = Xo[:, 0]; out["ubx"][:, :f] = Xo[:, 0]
+        if self.pref and p is not None:
+            P = np.asarray(p, float).reshape(B, N, nx)
+            out["p"] = np.concatenate([P[:, 1:], (P[:, -1:] if r_new is None else np.asarray(r_new, float).reshape(B, 1, nx))], axis=1).reshape(B, -1)
+        par = (lambda v: self._shift_blocks(v, 0, nx, N, ok)) if self.pref else (lambda v: np.where(ok[:, None], v[:, :nx], 0.0))
+        if dw is not None:
+            dw = np.asarray(dw, float)
+            out["dw"] = np.concatenate([par(dw), self._shift_blocks(dw, npp, f, N, ok)], axis=1)
+        if y is not None:
+            y = np.asarray(y, float)
+            out["y"] = np.concatenate([par(y), self._shift_blocks(y, npp, f, N, ok), self._shift_blocks(y, n, nx, N - 1, ok),
+                                       self._shift_blocks(y, n + self.ngd, self.nh, N, ok),
+                                       self._shift_blocks(y, n + self.ngd + N * self.nh, self.nk, N - 1, ok)], axis=1)
+        if p is not None:
+            r0 = np.asarray(p, float).reshape(B, -1)[:, :nx]
+            s0, u0 = X[:, 0, :nx], X[:, 0, nx:]
+            if self.general_cost:
+                ins = [s0[:, i] for i in range(nx)] + [u0[:, i] for i in range(self.nu)] + [r0[:, i] for i in range(nx)]
+                out["stage_cost"] = np.broadcast_to(np.asarray(self._ltape.evaluate(ins)[0], float), (B,)).copy()
+            else:
+                c = np.zeros(B)
+                for i in range(nx):
+                    e = s0[:, i] - r0[:, i]; c = c + e * e * self.Qk[0, i]
+                for i in range(self.nu):
+                    c = c + u0[:, i] * u0[:, i] * self.Rk[0, i]
+                out["stage_cost"] = c
+        return out
+
 
 class DoubleIntegrator(StageOCP):
     """nx=2, nu=1 LQ-MPC (BASELINE.json configs[1]):

@@ -175,6 +175,7 @@ class DeviceSQPOptimizationSolver:
         self.admm_iterations = []
         self.f = None; self.gmax = None
         self._have_start = False                         # like last_qp_info of the host loop: survives across calls
+        self._start_clean = False                        # set by mpc.ClosedLoopMPC: mpcqp_stage_advance already zeroed the failed instances' start
 
     def _create_qp(self, presolve_bounds):
         from .batch_qp import BatchQP
@@ -232,7 +233,7 @@ class DeviceSQPOptimizationSolver:
                 if self._have_start:
                     # after x += alpha * dx the remaining step is (1 - alpha) * dx; duals carry over
                     self.dw.mul_(1.0 - self.alpha_)
-                    if self.skip_failed_steps:               # an infeasible QP returns NaN: restart that instance cold
+                    if self.skip_failed_steps and not self._start_clean:   # an infeasible QP returns NaN: restart that instance cold
                         torch.nan_to_num_(self.dw, nan=0.0); torch.nan_to_num_(self.y, nan=0.0)
                     if self.carry_rho:
                         self.rho.copy_(self.info[:, 3]); self.qp.set_rho(self.rho)
@@ -243,6 +244,7 @@ class DeviceSQPOptimizationSolver:
             self.qp.solve(stream)
             self.qp.get_device(x=self.dw, y=self.y, status=self.status, iters=self.iters, info=self.info)
             self._have_start = True
+            self._start_clean = False
             step = ev.step(self.alpha_, self.dw, self.x, stream=stream, status=self.status if self.skip_failed_steps else None)
             self.f, self.gmax = ev.merit(p, self.x, stream=stream)
             self.admm_iterations.append(self.iters.clone())

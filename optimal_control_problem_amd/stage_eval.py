@@ -18,6 +18,15 @@ class StageDesc(C.Structure):
                 ("R", C.c_double * 8), ("par", C.c_double * 8), ("device", C.c_int)]
 
 
+class AdvanceArgs(C.Structure):
+    """mpcqp_stage_advance_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("x_in", "x_out", "lbx", "ubx", "status", "s_meas", "w", "p", "p_in", "p_out", "r_new",
+                                          "dw_in", "dw_out", "y_in", "y_out", "applied", "stage_cost")] + [("tail", C.c_int)]
+
+
+TAILS = {"repeat": 0, "rollout": 1}
+
+
 def _bind(L):
     if getattr(L, "_stage_bound", False):
         return L
@@ -36,6 +45,7 @@ def _bind(L):
     L.mpcqp_stage_eval.argtypes = [vp, C.c_int] + [dp] * 11 + [vp]
     L.mpcqp_stage_merit.argtypes = [vp, C.c_int, dp, dp, dp, dp, vp]
     L.mpcqp_stage_step.argtypes = [vp, C.c_int, C.c_double, dp, dp, dp, vp, vp]
+    L.mpcqp_stage_advance.argtypes = [vp, C.c_int, C.POINTER(AdvanceArgs), vp]
     L._stage_bound = True
     return L
 
@@ -171,3 +181,29 @@ class StageEvaluator:
         _lib.check(_lib.lib().mpcqp_stage_step(self._h, B, float(alpha), _check(dw, (B, self.n), "dw"), _check(x, (B, self.nvar), "x"),
                                                sm.data_ptr(), None if status is None else status.data_ptr(), stream))
         return sm
+
+    def advance(self, x_in, x_out, lbx, ubx, status=None, s_meas=None, w=None, tail="rollout", p=None, p_in=None, p_out=None, r_new=None,
+                dw_in=None, dw_out=None, y_in=None, y_out=None, applied=None, stage_cost=None, stream=None):
+        """the hand-over between two MPC ticks in one kernel (mpcqp_stage_advance; models.StageOCP.advance is its host statement): the plant
+        step, the trajectory shifted by one frame into x_out, the first frame pinned in lbx / ubx (in place), and optionally the shifted
+        references, QP start and duals and the logs.  Arrays are contiguous float64 CUDA tensors (status int32); out of place throughout."""
+        import torch
+        B = x_in.shape[0]
+        f = self.nx + self.nu
+        a = AdvanceArgs()
+        if tail not in TAILS:
+            raise ValueError("tail must be 'repeat' or 'rollout'")
+        a.tail = TAILS[tail]
+        for name, t, w_ in (("x_in", x_in, self.nvar), ("x_out", x_out, self.nvar), ("lbx", lbx, self.nvar), ("ubx", ubx, self.nvar),
+                            ("s_meas", s_meas, self.nx), ("w", w, self.nx), ("p", p, self.nx), ("p_in", p_in, self.np), ("p_out", p_out, self.np),
+                            ("r_new", r_new, self.nx), ("dw_in", dw_in, self.n), ("dw_out", dw_out, self.n), ("y_in", y_in, self.m),
+                            ("y_out", y_out, self.m), ("applied", applied, f)):
+            if t is not None:
+                setattr(a, name, _check(t, (B, w_), name))
+        if stage_cost is not None:
+            a.stage_cost = _check(stage_cost, (B,), "stage_cost")
+        if status is not None:
+            if not (isinstance(status, torch.Tensor) and status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and tuple(status.shape) == (B,)):
+                raise ValueError("status: expected a contiguous int32 CUDA tensor of shape (%d,)" % B)
+            a.status = status.data_ptr()
+        _lib.check(_lib.lib().mpcqp_stage_advance(self._h, B, C.byref(a), stream))
