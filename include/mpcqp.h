@@ -386,6 +386,42 @@ typedef struct mpcqp_stage_advance_args {
   int tail;                            /* MPCQP_TAIL_*                                               */
 } mpcqp_stage_advance_args;
 int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_args *a, void *stream);
+/* Per-instance step length by an l1-merit backtracking search, one kernel for the batch (opt-in; replaces one mpcqp_stage_step + mpcqp_stage_merit
+ * pair).  The reference takes result.x += alpha * solution[pSize:] with one alpha for every iteration (SQPOptimizationSolver.cpp:171-177: no
+ * line search, no merit function); this entry departs from those lines.  Per instance b, with dx = dw[np:] and ok = (status == NULL or status[b] is
+ * MPCQP_SOLVED / _SOLVED_INACCURATE / _MAX_ITER_REACHED, the set mpcqp_stage_step uses):
+ *   violation  v(x) = sum |s_{k+1} - F(s_k, u_k)| + sum over the path and link rows of max(lo - h, 0) + max(h - hi, 0) (the bounds
+ *              mpcqp_stage_merit uses) + sum over all nvar entries of max(lbx - x, 0) + max(x - ubx, 0); an infinite bound contributes 0
+ *   merit      phi(x) = f(p, x) + mu_b v(x), f being mpcqp_stage_merit's objective
+ *   penalty    mu_b = max(mu[b] if given, mu_min, mu_factor * max_{np <= i < m} |y_i|), y the multipliers of the QP just solved; written back to
+ *              mu[b], so the penalty never decreases from one call to the next
+ *   slope      D = min(0, sum_{j >= np} q_j dw_j - mu_b v(x)), q the gradient mpcqp_stage_eval wrote at x
+ *   search     alpha_j = alpha0 * beta^j, j = 0 .. candidates - 1: the first j with phi(x + alpha_j dx) finite and <= phi(x) + c1 alpha_j D is
+ *              taken, accepted[b] = j.  None: alpha_{candidates-1} if its merit is finite, accepted[b] = -1; else alpha = 0, accepted[b] = -2.
+ *              An instance that is not ok keeps x bit for bit, alpha = 0, accepted[b] = -2, mu[b] untouched (its dw and y are not read).
+ *   update     x += alpha dx in place, by mpcqp_stage_step's expression: candidates = 1 reproduces mpcqp_stage_step(alpha0) on finite data
+ *   outputs    alpha_out, step_max = max |alpha dx|, f_out and gmax_out = what mpcqp_stage_merit returns at the new x (taken from the chosen
+ *              candidate's evaluation), phi [batch * 2] = {phi(x_old), phi(x_new)} under mu_b
+ * All pointers are device memory.  Asynchronous on `stream`.  MPCQP_ERR_ARG for a null required pointer, candidates outside 1..8, beta outside
+ * (0, 1), alpha0 <= 0, c1 outside [0, 1); MPCQP_ERR_LIMIT for a generated library from before this entry (it does not export
+ * mpcqp_user_linesearch; regenerate it). */
+#define MPCQP_LINESEARCH_MAX_CANDIDATES 8
+typedef struct mpcqp_stage_linesearch_args {
+  const double *p;                     /* [batch * np]                                               */
+  double *x;                           /* [batch * nvar], in / out                                   */
+  const double *lbx, *ubx;             /* [batch * nvar]                                             */
+  const double *q, *dw;                /* [batch * n]: gradient at x, QP solution                    */
+  const double *y;                     /* [batch * m]: QP multipliers                                */
+  const int *status;                   /* [batch], optional                                          */
+  double *mu;                          /* [batch], optional, in / out                                */
+  double *alpha_out;                   /* [batch], optional                                          */
+  int *accepted;                       /* [batch], optional                                          */
+  double *step_max, *f_out, *gmax_out; /* [batch], optional                                          */
+  double *phi;                         /* [batch * 2], optional                                      */
+  double alpha0, beta, c1, mu_min, mu_factor;
+  int candidates;                      /* 1 .. MPCQP_LINESEARCH_MAX_CANDIDATES                       */
+} mpcqp_stage_linesearch_args;
+int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesearch_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Local-system evaluation on device for a general (non-stage) NLP.

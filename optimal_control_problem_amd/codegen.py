@@ -608,6 +608,10 @@ int mpcqp_user_merit(const StageDev *sd, int batch, const double *p, const doubl
 int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream) {
   return (int)stage_launch_advance<SmUser>(*sd, batch, *a, (hipStream_t)stream);
 }
+// the per-instance merit line search (mpcqp_stage_linesearch)
+int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
+  return (int)stage_launch_linesearch<SmUser>(*sd, batch, *a, (hipStream_t)stream);
+}
 }
 '''
 
@@ -726,6 +730,7 @@ def device_source(tape):
     if getattr(tape, "pref", False):
         src = src.replace("stage_launch_eval<SmUser>", "stage_launch_eval<SmUser, SmUser::pref>").replace("stage_launch_merit<SmUser>", "stage_launch_merit<SmUser, SmUser::pref>")
         src = src.replace("stage_launch_advance<SmUser>", "stage_launch_advance<SmUser, SmUser::pref>")
+        src = src.replace("stage_launch_linesearch<SmUser>", "stage_launch_linesearch<SmUser, SmUser::pref>")
         src = src.replace("int mpcqp_user_nh() {", "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\nint mpcqp_user_nh() {")
     return src
 

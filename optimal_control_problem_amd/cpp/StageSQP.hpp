@@ -6,7 +6,9 @@
 // Same quirks as the reference: a fixed number of iterations (step_num), no line search, the iterate persists across calls
 // and starts at zero, arg.x0 is ignored.  Opt-in extension: setTolerance(t) adds a convergence stop that the reference has
 // only under `verbose` (:183-197) -- the loop ends after the first iteration in which every instance moved by less than t
-// (max-norm of alpha * dx, mpcqp_stage_step's step_max).  Header-only; needs the HIP runtime for the device buffers (hipMalloc / hipMemcpy).
+// (max-norm of alpha * dx, mpcqp_stage_step's step_max).  Opt-in as well: setLineSearch(candidates, beta, c1) replaces the one alpha of :171-177
+// by a step length per instance from an l1-merit backtracking search that starts at alpha (mpcqp_stage_linesearch, one kernel in place of
+// the step; the penalty persists across iterations and calls); alphaTaken() reports the last iteration's step lengths.  Header-only; needs the HIP runtime for the device buffers (hipMalloc / hipMemcpy).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -40,6 +42,7 @@ class StageSQP {
   }
   ~StageSQP() {
     for (double *p : bufs_) (void)hipFree(p);
+    if (status_) (void)hipFree(status_);
     if (qp_) mpcqp_destroy(qp_);
     if (ocp_) mpcqp_stage_destroy(ocp_);
   }
@@ -65,6 +68,7 @@ class StageSQP {
   void setInitialGuess(const std::vector<double> &x) {            // extension: the reference always starts from zero
     need(x.size(), (size_t)batch_ * nvar(), "x");
     hip(hipMemcpy(x_, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (mu_) hip(hipMemset(mu_, 0, (size_t)batch_ * sizeof(double)));
   }
 
   // option polish_qp (default off, as the reference leaves OSQP's `polishing` off, :80-85): every QP of the loop is polished (mpcqp_set_polish)
@@ -73,6 +77,19 @@ class StageSQP {
   // instances' rho and only re-factorises (mpcqp_update_matrices = OSQP's osqp_update_data_mat); a handle that answers MPCQP_ERR_LIMIT goes on with full set-ups
   void setKeepScaling(bool on) { keepScaling_ = on; if (on) check(mpcqp_keep_workspace(qp_, 1), "mpcqp_keep_workspace"); }
   void setTolerance(double tol) { tol_ = tol; }                   // 0 (default) = the reference's fixed iteration count
+  // option line_search (default off: candidates = 0): per-instance step length, first candidate alpha, then alpha beta, alpha beta^2, ...
+  // (1 <= candidates <= 8, 0 < beta < 1, 0 <= c1 < 1; the penalty's mu_min = 1 and mu_factor = 1.1 as in the Python loops)
+  void setLineSearch(int candidates, double beta = 0.5, double c1 = 1e-4) {
+    if (candidates < 0 || candidates > MPCQP_LINESEARCH_MAX_CANDIDATES) throw std::invalid_argument("candidates must be in 0..8");
+    lsCandidates_ = candidates; lsBeta_ = beta; lsC1_ = c1;
+    if (candidates > 0 && !y_) {
+      const size_t B = batch_;
+      y_ = dalloc(B * m()); mu_ = dalloc(B); alphaOut_ = dalloc(B);
+      hip(hipMemset(mu_, 0, B * sizeof(double)));
+      hip(hipMalloc(&status_, B * sizeof(int)));
+    }
+  }
+  const std::vector<double> &alphaTaken() const { return alphaTaken_; }      // per instance, last iteration (empty without the line search)
   int iterationsDone() const { return iterationsDone_; }
 
   Result getOptimalSolution(const Arg &arg) {
@@ -93,8 +110,17 @@ class StageSQP {
         scaled_ = true;
       }
       check(mpcqp_solve(qp_, nullptr), "mpcqp_solve");
-      check(mpcqp_get(qp_, dw_, nullptr, nullptr, nullptr, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
-      check(mpcqp_stage_step(ocp_, batch_, alpha_, dw_, x_, tol_ > 0.0 ? g_ : nullptr, nullptr, nullptr), "mpcqp_stage_step");
+      if (lsCandidates_ > 0) {
+        check(mpcqp_get(qp_, dw_, y_, nullptr, status_, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
+        mpcqp_stage_linesearch_args ls = {};
+        ls.p = p_; ls.x = x_; ls.lbx = lbx_; ls.ubx = ubx_; ls.q = dq_; ls.dw = dw_; ls.y = y_; ls.status = status_; ls.mu = mu_;
+        ls.alpha_out = alphaOut_; ls.step_max = tol_ > 0.0 ? g_ : nullptr;
+        ls.alpha0 = alpha_; ls.beta = lsBeta_; ls.c1 = lsC1_; ls.mu_min = 1.0; ls.mu_factor = 1.1; ls.candidates = lsCandidates_;
+        check(mpcqp_stage_linesearch(ocp_, batch_, &ls, nullptr), "mpcqp_stage_linesearch");
+      } else {
+        check(mpcqp_get(qp_, dw_, nullptr, nullptr, nullptr, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
+        check(mpcqp_stage_step(ocp_, batch_, alpha_, dw_, x_, tol_ > 0.0 ? g_ : nullptr, nullptr, nullptr), "mpcqp_stage_step");
+      }
       iterationsDone_ = i + 1;
       if (tol_ > 0.0) {                                           // one vector of step norms back to the host per iteration
         stepMax_.resize(B);
@@ -106,6 +132,10 @@ class StageSQP {
       }
     }
     check(mpcqp_stage_merit(ocp_, batch_, p_, x_, f_, g_, nullptr), "mpcqp_stage_merit");
+    if (lsCandidates_ > 0 && stepNum_ > 0) {
+      alphaTaken_.resize(B);
+      hip(hipMemcpy(alphaTaken_.data(), alphaOut_, B * sizeof(double), hipMemcpyDeviceToHost));
+    }
     Result r; r.x.resize(B * nvar()); r.f.resize(B); violation_.resize(B);
     hip(hipMemcpy(r.x.data(), x_, r.x.size() * sizeof(double), hipMemcpyDeviceToHost));
     hip(hipMemcpy(r.f.data(), f_, B * sizeof(double), hipMemcpyDeviceToHost));
@@ -126,6 +156,9 @@ class StageSQP {
   int batch_, stepNum_; double alpha_; double tol_ = 0.0; int iterationsDone_ = 0;
   bool keepScaling_ = false, scaled_ = false;                     // (scaled_: a full set-up has run on the handle)
   std::vector<double> stepMax_;
+  int lsCandidates_ = 0; double lsBeta_ = 0.5, lsC1_ = 1e-4;      // line search: 0 candidates = off
+  double *y_ = nullptr, *mu_ = nullptr, *alphaOut_ = nullptr; int *status_ = nullptr;
+  std::vector<double> alphaTaken_;
   int dims_[8] = {0};
   mpcqp_stage *ocp_ = nullptr; mpcqp_handle *qp_ = nullptr;
   double *x_ = nullptr, *dP_ = nullptr, *dq_ = nullptr, *dA_ = nullptr, *dl_ = nullptr, *du_ = nullptr, *dw_ = nullptr, *f_ = nullptr, *g_ = nullptr;

@@ -22,6 +22,7 @@ typedef int (*user_eval_fn)(const StageDev *, int, const double *, const double 
                             const double *, double *, double *, double *, double *, double *, void *);
 typedef int (*user_merit_fn)(const StageDev *, int, const double *, const double *, double *, double *, void *);
 typedef int (*user_advance_fn)(const StageDev *, int, const mpcqp_stage_advance_args *, void *);
+typedef int (*user_linesearch_fn)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *);
 
 struct mpcqp_stage {
   mpcqp_stage_desc desc;
@@ -36,6 +37,7 @@ struct mpcqp_stage {
   user_eval_fn user_eval = nullptr;
   user_merit_fn user_merit = nullptr;
   user_advance_fn user_advance = nullptr;   // optional export: libraries generated before mpcqp_stage_advance have none
+  user_linesearch_fn user_linesearch = nullptr;   // optional export, likewise (mpcqp_stage_linesearch)
   bool general_cost = false;          // the library carries its own stage cost: Q, R and mpcqp_stage_set_weights do not apply
 };
 
@@ -184,6 +186,7 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   mpcqp_stage *s = new mpcqp_stage();
   s->user_lib = lib; s->user_eval = ev; s->user_merit = me;
   s->user_advance = (user_advance_fn)dlsym(lib, "mpcqp_user_advance");
+  s->user_linesearch = (user_linesearch_fn)dlsym(lib, "mpcqp_user_linesearch");
   mpcqp_stage_desc dd = *d; dd.model = MPCQP_MODEL_USER;
   std::vector<unsigned char> mask((size_t)(2 * nx + nu) * (2 * nx + nu));
   auto cf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_cost");
@@ -338,6 +341,32 @@ int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_arg
     case SM_QUADROTOR: e = s->sd.pref ? stage_launch_advance<SmQuadrotor, true>(s->sd, batch, *a, st) : stage_launch_advance<SmQuadrotor>(s->sd, batch, *a, st); break;
     case SM_CARTPOLE: e = s->sd.pref ? stage_launch_advance<SmCartPole, true>(s->sd, batch, *a, st) : stage_launch_advance<SmCartPole>(s->sd, batch, *a, st); break;
     case MPCQP_MODEL_USER: e = (hipError_t)s->user_advance(&s->sd, batch, a, stream); break;
+  }
+  MPCQP_HIPCHK(e);
+  return MPCQP_OK;
+}
+
+int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (!a->p || !a->x || !a->lbx || !a->ubx || !a->q || !a->dw || !a->y) return mpcqp_set_error(MPCQP_ERR_ARG, "p, x, lbx, ubx, q, dw and y are required");
+  if (a->candidates < 1 || a->candidates > MPCQP_LINESEARCH_MAX_CANDIDATES) return mpcqp_set_error(MPCQP_ERR_ARG, "candidates must be in 1..8");
+  if (!(a->beta > 0.0 && a->beta < 1.0)) return mpcqp_set_error(MPCQP_ERR_ARG, "beta must lie in (0, 1)");
+  if (!(a->alpha0 > 0.0) || !std::isfinite(a->alpha0)) return mpcqp_set_error(MPCQP_ERR_ARG, "alpha0 must be positive");
+  if (!(a->c1 >= 0.0 && a->c1 < 1.0)) return mpcqp_set_error(MPCQP_ERR_ARG, "c1 must lie in [0, 1)");
+  if (!(a->mu_min >= 0.0) || !(a->mu_factor >= 0.0) || !std::isfinite(a->mu_min) || !std::isfinite(a->mu_factor))
+    return mpcqp_set_error(MPCQP_ERR_ARG, "mu_min and mu_factor must be finite and not negative");
+  if (s->sd.model == MPCQP_MODEL_USER && !s->user_linesearch)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_linesearch (generated before this entry); regenerate it");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  switch (s->sd.model) {
+    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_linesearch<SmDoubleIntegrator, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmDoubleIntegrator>(s->sd, batch, *a, st); break;
+    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_linesearch<SmQuadrotor, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmQuadrotor>(s->sd, batch, *a, st); break;
+    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_linesearch<SmCartPole, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmCartPole>(s->sd, batch, *a, st); break;
+    case MPCQP_MODEL_USER: e = (hipError_t)s->user_linesearch(&s->sd, batch, a, stream); break;
   }
   MPCQP_HIPCHK(e);
   return MPCQP_OK;

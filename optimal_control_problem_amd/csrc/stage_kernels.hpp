@@ -399,6 +399,168 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
   }
 }
 
+// per-candidate accumulators of the line search: the candidate is known at run time only, the registers are addressed statically (an unrolled
+// select written as a compile-time recursion: a loop over j, even one that is unrolled later, is turned back into a dynamically indexed array
+// by the optimiser, and that array goes to scratch)
+template <int NC, int J = 0> __device__ __forceinline__ void stage_ls_add(double (&acc)[NC], int c, double v) {
+  if constexpr (J < NC) { acc[J] = J == c ? acc[J] + v : acc[J]; stage_ls_add<NC, J + 1>(acc, c, v); }
+}
+template <int NC, int J = 0> __device__ __forceinline__ void stage_ls_max(double (&acc)[NC], int c, double v) {
+  if constexpr (J < NC) { acc[J] = J == c ? fmax(acc[J], v) : acc[J]; stage_ls_max<NC, J + 1>(acc, c, v); }
+}
+template <int NC, int J = NC - 1> __device__ __forceinline__ double stage_ls_get(const double (&acc)[NC], int c) {
+  if constexpr (J == 0) return acc[0];
+  else return J == c ? acc[J] : stage_ls_get<NC, J - 1>(acc, c);
+}
+
+// Per-instance l1-merit backtracking line search (mpcqp_stage_linesearch; models.StageOCP.line_search is its host statement).  One wave per
+// instance like the merit kernel.  Work items are (candidate, frame) pairs over (K + 1) N, strided over the 64 lanes; candidate 0 is the base point
+// x, candidate j >= 1 the point x + alpha0 beta^(j-1) dx.  An item adds frame k's cost, l1 violation and max-norm violation at its candidate to the
+// lane's per-candidate partial sums; the box terms, q' dx and max |y| stride over their arrays; one butterfly in fixed order reduces everything
+// (two runs give the same bits) and leaves the totals on every lane, so the decision is taken redundantly by all of them.  x is written after that,
+// by stage_step_kernel's expression: every read of x precedes it in program order of the same wave.  No LDS, no atomics, one writer per output.
+template <class M, bool PF = false>
+__global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int batch, mpcqp_stage_linesearch_args a) {
+  constexpr int nx = M::nx, nu = M::nu, f = nx + nu, NC = MPCQP_LINESEARCH_MAX_CANDIDATES + 1;
+  const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (b >= batch) return;
+  const int N = sd.N, nvar = sd.nvar, np = sd.np;
+  bool ok = true;
+  if (a.status) { const int s = a.status[b]; ok = s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
+  const int K = ok ? a.candidates : 0;          // an instance whose QP returned no point evaluates the base point only: its dw, y are not read
+  double *xb = a.x + (long)b * nvar;
+  const double *pb0 = a.p + (long)b * np, *dxb = a.dw + (long)b * sd.n + np;
+  double al[NC];                                // al[0] = 0: the base point
+  al[0] = 0.0; al[1] = a.alpha0;
+#pragma unroll
+  for (int j = 2; j < NC; j++) al[j] = al[j - 1] * a.beta;
+  double cost[NC], vio[NC], gmx[NC];
+#pragma unroll
+  for (int j = 0; j < NC; j++) { cost[j] = 0.0; vio[j] = 0.0; gmx[j] = 0.0; }
+  for (int t = lane; t < (K + 1) * N; t += 64) {
+    const int c = t / N, k = t - c * N;
+    const double ac = stage_ls_get(al, c);
+    const double *fr = xb + k * f, *dfr = dxb + k * f, *pb = PF ? pb0 + k * nx : pb0;
+    double s[nx], uu[nu];
+#pragma unroll
+    for (int i = 0; i < nx; i++) { s[i] = fr[i]; if (c > 0) s[i] += ac * dfr[i]; }
+#pragma unroll
+    for (int i = 0; i < nu; i++) { uu[i] = fr[nx + i]; if (c > 0) uu[i] += ac * dfr[nx + i]; }
+    double lc = 0.0, lv = 0.0, lg = 0.0;
+    // the objective and the max-norm violation exactly as stage_merit_kernel forms them, the l1 violation next to the latter
+    if constexpr (M::has_cost) {
+      double rr[nx], lval[1];
+#pragma unroll
+      for (int i = 0; i < nx; i++) rr[i] = pb[i];
+      if (M::has_term && k == N - 1) M::template LT<double>(s, uu, rr, lval); else M::template L<double>(s, uu, rr, lval);
+      lc += lval[0];
+    } else {
+#pragma unroll
+      for (int i = 0; i < nx; i++) { const double e = s[i] - pb[i]; lc += e * e * (sd.Qk ? sd.Qk[k * nx + i] : sd.Q[i]); }
+#pragma unroll
+      for (int i = 0; i < nu; i++) lc += uu[i] * uu[i] * (sd.Rk ? sd.Rk[k * nu + i] : sd.R[i]);
+    }
+    if (k < N - 1) {
+      double out[nx];
+      M::template F<double>(sd.par, sd.dt, s, uu, out);
+#pragma unroll
+      for (int i = 0; i < nx; i++) {
+        double sn = fr[f + i];
+        if (c > 0) sn += ac * dfr[f + i];
+        const double d = fabs(sn - out[i]);
+        lv += d; lg = fmax(lg, d);
+      }
+    }
+    if constexpr (M::nh > 0) {
+      double hv[M::nh];
+      M::template H<double>(s, uu, hv);
+#pragma unroll
+      for (int i = 0; i < M::nh; i++) {
+        const double lo = sd.h_lok ? sd.h_lok[k * M::nh + i] : sd.h_lo[i], hi = sd.h_hik ? sd.h_hik[k * M::nh + i] : sd.h_hi[i];
+        lv += fmax(lo - hv[i], 0.0) + fmax(hv[i] - hi, 0.0);
+        lg = fmax(lg, fmax(lo - hv[i], hv[i] - hi));
+      }
+    }
+    if constexpr (M::nk > 0) {
+      if (k < N - 1) {
+        double ns[nx], nun[nu], kv[M::nk];
+#pragma unroll
+        for (int i = 0; i < nx; i++) { ns[i] = fr[f + i]; if (c > 0) ns[i] += ac * dfr[f + i]; }
+#pragma unroll
+        for (int i = 0; i < nu; i++) { nun[i] = fr[f + nx + i]; if (c > 0) nun[i] += ac * dfr[f + nx + i]; }
+        M::template K<double>(s, uu, ns, nun, kv);
+#pragma unroll
+        for (int i = 0; i < M::nk; i++) {
+          lv += fmax(sd.k_lo[i] - kv[i], 0.0) + fmax(kv[i] - sd.k_hi[i], 0.0);
+          lg = fmax(lg, fmax(sd.k_lo[i] - kv[i], kv[i] - sd.k_hi[i]));
+        }
+      }
+    }
+    stage_ls_add(cost, c, lc); stage_ls_add(vio, c, lv); stage_ls_max(gmx, c, lg);
+  }
+  // box terms of every candidate, q' dx, max |y| over the box and general rows
+  double qd = 0.0, ymax = 0.0;
+  {
+    const double *lb = a.lbx + (long)b * nvar, *ub = a.ubx + (long)b * nvar, *qb = a.q + (long)b * sd.n + np;
+    for (int i = lane; i < nvar; i += 64) {
+      const double xv = xb[i], lo = lb[i], hi = ub[i];
+      vio[0] += fmax(lo - xv, 0.0) + fmax(xv - hi, 0.0);
+      if (ok) {
+        const double dv = dxb[i];
+        qd += qb[i] * dv;
+#pragma unroll
+        for (int j = 1; j < NC; j++)
+          if (j <= K) { const double xc = xv + al[j] * dv; vio[j] += fmax(lo - xc, 0.0) + fmax(xc - hi, 0.0); }
+      }
+    }
+    if (ok) {
+      const double *yb = a.y + (long)b * sd.m;
+      for (int i = np + lane; i < sd.m; i += 64) ymax = fmax(ymax, fabs(yb[i]));
+    }
+  }
+  for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < NC; j++) {
+      cost[j] += __shfl_xor(cost[j], o, 64); vio[j] += __shfl_xor(vio[j], o, 64); gmx[j] = fmax(gmx[j], __shfl_xor(gmx[j], o, 64));
+    }
+    qd += __shfl_xor(qd, o, 64); ymax = fmax(ymax, __shfl_xor(ymax, o, 64));
+  }
+  // the decision, the same on every lane
+  double mu = a.mu_min;
+  if (a.mu) mu = fmax(mu, a.mu[b]);
+  if (ok) mu = fmax(mu, a.mu_factor * ymax);
+  double phi[NC];
+#pragma unroll
+  for (int j = 0; j < NC; j++) phi[j] = cost[j] + mu * vio[j];
+  double D = qd - mu * vio[0];
+  D = D < 0.0 ? D : 0.0;
+  int sel = 0, acc = -2;                        // sel: the candidate taken (0 = stay), acc: what `accepted` reports
+  if (ok) {
+    bool found = false;
+#pragma unroll
+    for (int j = 1; j < NC; j++)
+      if (j <= K && !found && isfinite(phi[j]) && phi[j] <= phi[0] + a.c1 * al[j] * D) { found = true; sel = j; acc = j - 1; }
+    if (!found && isfinite(stage_ls_get(phi, K))) { sel = K; acc = -1; }
+  }
+  const double alpha = stage_ls_get(al, sel);
+  double mx = 0.0;
+  if (sel > 0) {
+    for (int i = lane; i < nvar; i += 64) {
+      const double d = alpha * dxb[i];
+      xb[i] += d; mx = fmax(mx, fabs(d));
+    }
+    for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+  }
+  if (lane == 0) {
+    if (a.mu && ok) a.mu[b] = mu;
+    if (a.alpha_out) a.alpha_out[b] = alpha;
+    if (a.accepted) a.accepted[b] = acc;
+    if (a.step_max) a.step_max[b] = mx;
+    if (a.f_out) a.f_out[b] = stage_ls_get(cost, sel);
+    if (a.gmax_out) a.gmax_out[b] = stage_ls_get(gmx, sel);
+    if (a.phi) { a.phi[2 * (long)b] = phi[0]; a.phi[2 * (long)b + 1] = stage_ls_get(phi, sel); }
+  }
+}
 
 // launchers shared by the zoo dispatch and generated libraries
 template <class M, bool PF = false>
@@ -418,5 +580,10 @@ inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const double
 template <class M, bool PF = false>
 inline hipError_t stage_launch_advance(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st) {
   stage_advance_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a);
+  return hipGetLastError();
+}
+template <class M, bool PF = false>
+inline hipError_t stage_launch_linesearch(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st) {
+  stage_linesearch_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a);
   return hipGetLastError();
 }

@@ -544,6 +544,88 @@ class StageOCP:
                 out["stage_cost"] = c
         return out
 
+    # -- the per-instance merit line search (include/mpcqp.h, mpcqp_stage_linesearch; csrc/stage_kernels.hpp stage_linesearch_kernel) ----------
+    LINE_SEARCH_DEFAULTS = {"candidates": 4, "beta": 0.5, "c1": 1e-4, "mu_min": 1.0, "mu_factor": 1.1}
+
+    def violation(self, x, lbx, ubx):
+        """(v [B], gmax [B]): the l1 violation measure of the line search -- dynamics defects, path and link rows outside their bounds, entries of
+        x outside lbx / ubx; an infinite bound contributes 0 -- and the max-norm violation mpcqp_stage_merit returns (no box terms in that one)"""
+        with np.errstate(all="ignore"):
+            x = np.asarray(x, float)
+            d = np.abs(self.constraints(x))
+            v = d.sum(axis=1)
+            g = np.fmax.reduce(d, axis=1, initial=0.0)
+            rows = []
+            if self.nh:
+                lo, hi = self.path_bounds()
+                rows.append((self.path_values(x), lo.ravel(), hi.ravel()))
+            if self.nk:
+                lo, hi = self.link_bounds()
+                rows.append((self.link_values(x), lo.ravel(), hi.ravel()))
+            for h, lo, hi in rows:
+                v = v + (np.fmax(lo - h, 0.0) + np.fmax(h - hi, 0.0)).sum(axis=1)
+                g = np.fmax(g, np.fmax.reduce(np.fmax(lo - h, h - hi), axis=1, initial=0.0))
+            v = v + (np.fmax(lbx - x, 0.0) + np.fmax(x - ubx, 0.0)).sum(axis=1)
+        return v, g
+
+    def line_search(self, p, x, lbx, ubx, q, dw, y, status=None, mu=None, alpha0=1.0, candidates=4, beta=0.5, c1=1e-4, mu_min=1.0, mu_factor=1.1):
+        """Host statement of mpcqp_stage_linesearch: an l1-merit backtracking search per instance.  x [B, nvar] (float64 array) and, when given,
+        mu [B] are updated in place.  phi(x) = objective(p, x) + mu_b v(x) with mu_b = max(mu[b], mu_min, mu_factor max_{i >= np} |y_i|);
+        D = min(0, q[np:]' dw[np:] - mu_b v(x)); the first alpha_j = alpha0 beta^j, j < candidates, whose phi(x + alpha_j dx) is finite and
+        <= phi(x) + c1 alpha_j D is taken (accepted = j).  None: alpha_{K-1} when its merit is finite (accepted = -1), else alpha = 0
+        (accepted = -2).  An instance whose status is not in STATUS_OK keeps x, gets alpha = 0, accepted = -2, and its mu stays.
+        Returns a dict: x, alpha, accepted, step_max = max|alpha dx|, f and gmax at the new x, phi [B, 2] = phi(x_old), phi(x_new), mu = mu_b,
+        and for the tests D [B], alphas [K], phis [B, K + 1] (base point first; NaN where not evaluated)."""
+        K = int(candidates)
+        if not 1 <= K <= 8:
+            raise ValueError("candidates must be in 1..8")
+        if not 0.0 < beta < 1.0:
+            raise ValueError("beta must lie in (0, 1)")
+        if not (alpha0 > 0.0 and np.isfinite(alpha0)):
+            raise ValueError("alpha0 must be positive")
+        if not 0.0 <= c1 < 1.0:
+            raise ValueError("c1 must lie in [0, 1)")
+        if not (0.0 <= mu_min < np.inf and 0.0 <= mu_factor < np.inf):
+            raise ValueError("mu_min and mu_factor must be finite and not negative")
+        B, npp = x.shape[0], self.np
+        p = np.asarray(p, float); lbx = np.asarray(lbx, float); ubx = np.asarray(ubx, float)
+        ok = np.ones(B, bool) if status is None else np.isin(np.asarray(status), self.STATUS_OK)
+        alphas = np.empty(K)
+        alphas[0] = alpha0
+        for j in range(1, K):
+            alphas[j] = alphas[j - 1] * beta
+        with np.errstate(all="ignore"):
+            dx = np.where(ok[:, None], np.asarray(dw, float)[:, npp:], 0.0)
+            mub = np.full(B, float(mu_min)) if mu is None else np.fmax(mu_min, np.asarray(mu, float))
+            ymax = np.fmax.reduce(np.abs(np.where(ok[:, None], np.asarray(y, float)[:, npp:], 0.0)), axis=1, initial=0.0)
+            mub = np.where(ok, np.fmax(mub, mu_factor * ymax), mub)
+            cost = np.full((B, K + 1), np.nan); vio = np.full((B, K + 1), np.nan); gmx = np.full((B, K + 1), np.nan)
+            for j in range(K + 1):
+                xc = x if j == 0 else x + alphas[j - 1] * dx
+                cost[:, j] = self.objective(p, xc)
+                vio[:, j], gmx[:, j] = self.violation(xc, lbx, ubx)
+            phis = cost + mub[:, None] * vio
+            D = (np.asarray(q, float)[:, npp:] * dx).sum(axis=1) - mub * vio[:, 0]
+            D = np.where(D < 0.0, D, 0.0)
+            sel = np.zeros(B, np.int64); acc = np.full(B, -2, np.int64)
+            found = ~ok
+            for j in range(1, K + 1):
+                take = ~found & np.isfinite(phis[:, j]) & (phis[:, j] <= phis[:, 0] + c1 * alphas[j - 1] * D)
+                sel[take] = j; acc[take] = j - 1
+                found = found | take
+            last = ~found & np.isfinite(phis[:, K])
+            sel[last] = K; acc[last] = -1
+            alpha = np.where(sel > 0, alphas[np.maximum(sel, 1) - 1], 0.0)
+            step = alpha[:, None] * dx
+            moved = sel > 0
+            x[moved] = x[moved] + step[moved]
+            phis[~ok, 1:] = np.nan
+        if mu is not None:
+            mu[ok] = mub[ok]
+        rows = np.arange(B)
+        return {"x": x, "alpha": alpha, "accepted": acc, "step_max": np.where(moved, np.abs(step).max(axis=1), 0.0), "f": cost[rows, sel],
+                "gmax": gmx[rows, sel], "phi": np.stack([phis[:, 0], phis[rows, sel]], axis=1), "mu": mub, "D": D, "alphas": alphas, "phis": phis}
+
 
 class DoubleIntegrator(StageOCP):
     """nx=2, nu=1 LQ-MPC (BASELINE.json configs[1]):

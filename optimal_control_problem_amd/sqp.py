@@ -10,6 +10,11 @@ exists only when verbose (:183-197).  Opt-in extension (SURVEY.md section 8 row 
 a real convergence stop that does not depend on `verbose` -- the loop ends after the first iteration in which every
 instance of the batch moved by less than t (max-norm of the step actually taken, alpha * dx: what mpcqp_stage_step
 reports per instance); `iterations_done` tells how many iterations ran.  Without the option the loop is the reference's.
+Opt-in as well: options["line_search"] = True, or a dict with any of candidates, beta, c1, mu_min, mu_factor (defaults 4, 0.5, 1e-4, 1.0, 1.1),
+replaces the one alpha of :171-177 by a step length per instance, chosen by an l1-merit backtracking search that starts at options["alpha"]
+(models.StageOCP.line_search states the rule, mpcqp_stage_linesearch runs it on the device).  An instance whose QP returned no point keeps its
+iterate; the penalty persists across iterations and calls; `alpha_taken` and `accepted` hold the last iteration's step lengths and candidate
+indices; with warm_start_admm the remaining step is (1 - alpha_b) dx per instance.  Stage OCPs only.
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -20,6 +25,21 @@ import numpy as np
 
 from . import _lib
 from .cucaqp import CuCaQP
+
+
+def _line_search_options(value):
+    """options["line_search"]: None / False = off; True = the defaults; a dict overrides some of them"""
+    if value is None or value is False:
+        return None
+    from .models import StageOCP
+    opts = dict(StageOCP.LINE_SEARCH_DEFAULTS)
+    if value is not True:
+        unknown = set(value) - set(opts)
+        if unknown:
+            raise ValueError("line_search: unknown keys %s (known: %s)" % (sorted(unknown), sorted(opts)))
+        opts.update(value)
+    opts["candidates"] = int(opts["candidates"])
+    return opts
 
 
 class SQPOptimizationSolver:
@@ -48,6 +68,12 @@ class SQPOptimizationSolver:
         # and carry each instance's adapted rho into its next QP, as a kept OSQP workspace would (with warm_start_admm)
         self.carry_rho = bool(options.get("carry_rho", False))
         self.sqp_tol = float(options.get("sqp_tol", 0.0) or 0.0)
+        self.line_search = _line_search_options(options.get("line_search"))
+        if self.line_search is not None and not hasattr(nlp, "line_search"):
+            raise ValueError("line_search needs a stage OCP (models.StageOCP): the merit line search is not available for a general NLP")
+        self.alpha_taken = None; self.accepted = None; self.gmax = None
+        self.last_line_search = None                     # the NumPy statement's full result for the last iteration
+        self._mu = None                                  # the penalty, monotone across iterations and calls
         self.iterations_done = 0
         self.step_max = None
         self.admm_iterations = []
@@ -58,6 +84,7 @@ class SQPOptimizationSolver:
 
     def setInitialGuess(self, x):
         """extension: the reference ignores arg["x0"] and starts from zero (:88-91); this overwrites the stored iterate"""
+        self._mu = None
         self.result_["x"] = np.array(np.broadcast_to(np.asarray(x, float).reshape(-1, self.result_["x"].shape[1]), self.result_["x"].shape))
         self.last_qp_info = None
 
@@ -80,7 +107,15 @@ class SQPOptimizationSolver:
             self.qpSolver_.setSystem(localSystem)
             if self.warm_start_admm and hasattr(self.qpSolver_, "setPrimalDualStart"):
                 info = self.last_qp_info
-                if info is not None and np.isfinite(info["x"]).all() and np.isfinite(info["y"]).all():
+                if self.line_search is not None and info is not None and self.alpha_taken is not None:
+                    # the remaining step is (1 - alpha_b) dx per instance; an instance whose QP returned NaN restarts cold
+                    fin = np.isfinite(info["x"]).all(axis=1) & np.isfinite(info["y"]).all(axis=1)
+                    with np.errstate(invalid="ignore"):
+                        x0 = np.where(fin[:, None], (1.0 - self.alpha_taken)[:, None] * info["x"], 0.0)
+                    self.qpSolver_.setPrimalDualStart(x0, np.where(fin[:, None], info["y"], 0.0))
+                    if self.carry_rho and hasattr(self.qpSolver_, "setRhoStart"):
+                        self.qpSolver_.setRhoStart(info["rho"])
+                elif info is not None and np.isfinite(info["x"]).all() and np.isfinite(info["y"]).all():
                     # after the damped update x += alpha * dx the remaining step is (1 - alpha) * dx; duals carry over
                     self.qpSolver_.setPrimalDualStart((1.0 - self.alpha_) * info["x"], info["y"])
                     if self.carry_rho and hasattr(self.qpSolver_, "setRhoStart"):
@@ -95,10 +130,24 @@ class SQPOptimizationSolver:
             if self.last_qp_info is not None and "iters" in self.last_qp_info:
                 self.admm_iterations.append(np.asarray(self.last_qp_info["iters"]).copy())
             oldRes = self.result_["x"].copy()
-            self.result_["x"] = self.result_["x"] + self.alpha_ * solution[:, pSize:]
-            self.result_["f"] = self.model.objective(p, self.result_["x"])
+            if self.line_search is not None:
+                info = self.last_qp_info
+                if info is None or "y" not in info:
+                    raise ValueError("line_search needs a QP backend that reports its multipliers (getInfo()['y'])")
+                if self._mu is None:
+                    self._mu = np.zeros(B)
+                nvar = self.model.n - pSize
+                box = [np.broadcast_to(np.asarray(arg[k], float).reshape(-1, nvar), (B, nvar)) for k in ("lbx", "ubx")]
+                ls = self.model.line_search(p, self.result_["x"], box[0], box[1], localSystem.q, solution, info["y"], status=info.get("status"),
+                                            mu=self._mu, alpha0=self.alpha_, **self.line_search)
+                self.result_["f"] = ls["f"]; self.gmax = ls["gmax"]
+                self.alpha_taken = ls["alpha"]; self.accepted = ls["accepted"]; self.last_line_search = ls
+                self.step_max = ls["step_max"]
+            else:
+                self.result_["x"] = self.result_["x"] + self.alpha_ * solution[:, pSize:]
+                self.result_["f"] = self.model.objective(p, self.result_["x"])
+                self.step_max = np.abs(self.alpha_ * solution[:, pSize:]).max(axis=1)
             self.iterations_done = i + 1
-            self.step_max = np.abs(self.alpha_ * solution[:, pSize:]).max(axis=1)
             if self.verbose_:
                 normDelta = np.linalg.norm(self.result_["x"] - oldRes, axis=1).max()
                 print("SQP iter %d/%d  max|dx| %.3e  f[0] %.6g" % (i + 1, self.stepNum_, normDelta, self.result_["f"][0]))
@@ -154,6 +203,12 @@ class DeviceSQPOptimizationSolver:
         # breaks it comes back MPCQP_UNSOLVED / NaN (include/mpcqp.h).  Warm start, carried rho, keep_scaling and polish_qp go through the reduced
         # handle's forwarding.  Meant for per-frame references, whose N nx parameters push the full form off the on-chip kernels.
         self.presolve_fixed_rows = bool(options.get("presolve_fixed_rows", False))
+        # extension (opt-in): a step length per instance by an l1-merit backtracking search starting at options["alpha"] -- one kernel
+        # (mpcqp_stage_linesearch) in place of the step + merit pair; see the module docstring.  It always honours the QP status.
+        self.line_search = _line_search_options(options.get("line_search"))
+        if self.line_search is not None and evaluator is not None:
+            raise ValueError("line_search is limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has no merit line search")
+        self.alpha_taken = None; self.accepted = None
         self.iterations_done = 0
         self.step_max = None
         self._kept = False
@@ -176,6 +231,10 @@ class DeviceSQPOptimizationSolver:
         self.f = None; self.gmax = None
         self._have_start = False                         # like last_qp_info of the host loop: survives across calls
         self._start_clean = False                        # set by mpc.ClosedLoopMPC: mpcqp_stage_advance already zeroed the failed instances' start
+        if self.line_search is not None:
+            self.mu = torch.zeros(self.batch, dtype=torch.float64, device=self.dev)      # the penalty, monotone across iterations and calls
+            self._ls_out = {k: torch.zeros(self.batch, dtype=torch.float64, device=self.dev) for k in ("alpha", "step_max", "f", "gmax")}
+            self._ls_out["accepted"] = torch.zeros(self.batch, dtype=torch.int32, device=self.dev)
 
     def _create_qp(self, presolve_bounds):
         from .batch_qp import BatchQP
@@ -191,6 +250,8 @@ class DeviceSQPOptimizationSolver:
         """extension: the reference ignores arg["x0"] and starts from zero (:88-91); this overwrites the stored iterate"""
         self.x.copy_(self._dev(x, self.ev.nvar))
         self._have_start = False
+        if self.line_search is not None:
+            self.mu.zero_()
 
     def _dev(self, a, w):
         import torch
@@ -232,8 +293,11 @@ class DeviceSQPOptimizationSolver:
             if self.warm_start_admm:
                 if self._have_start:
                     # after x += alpha * dx the remaining step is (1 - alpha) * dx; duals carry over
-                    self.dw.mul_(1.0 - self.alpha_)
-                    if self.skip_failed_steps and not self._start_clean:   # an infeasible QP returns NaN: restart that instance cold
+                    if self.line_search is not None and self.alpha_taken is not None:
+                        self.dw.mul_((1.0 - self.alpha_taken).unsqueeze(1))      # (1 - alpha_b) dx per instance
+                    else:
+                        self.dw.mul_(1.0 - self.alpha_)
+                    if (self.skip_failed_steps or self.line_search is not None) and not self._start_clean:   # an infeasible QP returns NaN: restart that instance cold
                         torch.nan_to_num_(self.dw, nan=0.0); torch.nan_to_num_(self.y, nan=0.0)
                     if self.carry_rho:
                         self.rho.copy_(self.info[:, 3]); self.qp.set_rho(self.rho)
@@ -245,8 +309,14 @@ class DeviceSQPOptimizationSolver:
             self.qp.get_device(x=self.dw, y=self.y, status=self.status, iters=self.iters, info=self.info)
             self._have_start = True
             self._start_clean = False
-            step = ev.step(self.alpha_, self.dw, self.x, stream=stream, status=self.status if self.skip_failed_steps else None)
-            self.f, self.gmax = ev.merit(p, self.x, stream=stream)
+            if self.line_search is not None:
+                ls = ev.line_search(p, self.x, lbx, ubx, self.ls["q"], self.dw, self.y, status=self.status, mu=self.mu, alpha0=self.alpha_,
+                                    out=self._ls_out, stream=stream, **self.line_search)
+                step, self.f, self.gmax = ls["step_max"], ls["f"], ls["gmax"]
+                self.alpha_taken, self.accepted = ls["alpha"], ls["accepted"]
+            else:
+                step = ev.step(self.alpha_, self.dw, self.x, stream=stream, status=self.status if self.skip_failed_steps else None)
+                self.f, self.gmax = ev.merit(p, self.x, stream=stream)
             self.admm_iterations.append(self.iters.clone())
             self.iterations_done = i + 1
             self.step_max = step

@@ -27,6 +27,13 @@ class AdvanceArgs(C.Structure):
 TAILS = {"repeat": 0, "rollout": 1}
 
 
+class LineSearchArgs(C.Structure):
+    """mpcqp_stage_linesearch_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("p", "x", "lbx", "ubx", "q", "dw", "y", "status", "mu", "alpha_out", "accepted", "step_max", "f_out",
+                                          "gmax_out", "phi")] + \
+               [(k, C.c_double) for k in ("alpha0", "beta", "c1", "mu_min", "mu_factor")] + [("candidates", C.c_int)]
+
+
 def _bind(L):
     if getattr(L, "_stage_bound", False):
         return L
@@ -46,6 +53,7 @@ def _bind(L):
     L.mpcqp_stage_merit.argtypes = [vp, C.c_int, dp, dp, dp, dp, vp]
     L.mpcqp_stage_step.argtypes = [vp, C.c_int, C.c_double, dp, dp, dp, vp, vp]
     L.mpcqp_stage_advance.argtypes = [vp, C.c_int, C.POINTER(AdvanceArgs), vp]
+    L.mpcqp_stage_linesearch.argtypes = [vp, C.c_int, C.POINTER(LineSearchArgs), vp]
     L._stage_bound = True
     return L
 
@@ -207,3 +215,34 @@ class StageEvaluator:
                 raise ValueError("status: expected a contiguous int32 CUDA tensor of shape (%d,)" % B)
             a.status = status.data_ptr()
         _lib.check(_lib.lib().mpcqp_stage_advance(self._h, B, C.byref(a), stream))
+
+    def line_search(self, p, x, lbx, ubx, q, dw, y, status=None, mu=None, alpha0=1.0, candidates=4, beta=0.5, c1=1e-4, mu_min=1.0, mu_factor=1.1,
+                    out=None, phi=None, stream=None):
+        """a per-instance step length by an l1-merit backtracking search, then x += alpha_b dx in place, in one kernel (mpcqp_stage_linesearch;
+        models.StageOCP.line_search is its host statement).  Replaces a step + merit pair: returns a dict of device tensors alpha, accepted
+        (int32), step_max, f, gmax [B] (`out`: such a dict to write into) and phi [B, 2] when a tensor is given for it.  mu [B], when given, is the
+        persistent penalty, updated in place.  Arrays are contiguous float64 CUDA tensors (status, accepted: int32)."""
+        import torch
+        B = x.shape[0]
+        a = LineSearchArgs()
+        for name, t, w_ in (("p", p, self.np), ("x", x, self.nvar), ("lbx", lbx, self.nvar), ("ubx", ubx, self.nvar), ("q", q, self.n),
+                            ("dw", dw, self.n), ("y", y, self.m)):
+            setattr(a, name, _check(t, (B, w_), name))
+        if out is None:
+            out = {k: torch.empty(B, dtype=torch.float64, device=x.device) for k in ("alpha", "step_max", "f", "gmax")}
+            out["accepted"] = torch.empty(B, dtype=torch.int32, device=x.device)
+        for name, key in (("alpha_out", "alpha"), ("step_max", "step_max"), ("f_out", "f"), ("gmax_out", "gmax")):
+            setattr(a, name, _check(out[key], (B,), key))
+        for name, t in (("status", status), ("accepted", out["accepted"])):
+            if t is not None:
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B,)):
+                    raise ValueError("%s: expected a contiguous int32 CUDA tensor of shape (%d,)" % (name, B))
+                setattr(a, name, t.data_ptr())
+        if mu is not None:
+            a.mu = _check(mu, (B,), "mu")
+        if phi is not None:
+            a.phi = _check(phi, (B, 2), "phi")
+            out["phi"] = phi
+        a.alpha0, a.beta, a.c1, a.mu_min, a.mu_factor, a.candidates = float(alpha0), float(beta), float(c1), float(mu_min), float(mu_factor), int(candidates)
+        _lib.check(_lib.lib().mpcqp_stage_linesearch(self._h, B, C.byref(a), stream))
+        return out
