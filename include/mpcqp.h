@@ -329,6 +329,22 @@ int mpcqp_stage_set_weights(mpcqp_stage *s, const double *Qk, const double *Rk);
  * differ by frame).  The QP itself takes its bounds from lbg / ubg of mpcqp_stage_eval either way.  NULL, NULL returns to the
  * bounds baked into the generated library. */
 int mpcqp_stage_set_path_bounds(mpcqp_stage *s, const double *lo, const double *hi);
+/* Per-instance plant parameters: a batch of different robots on one handle (opt-in).  Without this entry every instance of a
+ * launch shares desc.par (a generated library: the defaults it was generated with).  theta [batch * MPCQP_STAGE_NPAR], row b = instance b's
+ * parameters in the order of the MPCQP_MODEL_* comments above (a generated library: the order of the model's theta); entries past
+ * mpcqp_stage_param_count are never read.  The values are copied into a buffer the handle owns (mem = MPCQP_MEM_HOST or MPCQP_MEM_DEVICE) before
+ * the call returns.  which = MPCQP_PARAMS_MODEL: what mpcqp_stage_eval, _merit, _linesearch and the rollout tail of mpcqp_stage_advance use;
+ * which = MPCQP_PARAMS_PLANT: what the plant step F(s_0, u_0) of mpcqp_stage_advance uses (not read when s_meas is given) -- as long as it is
+ * not set, the plant is the model.  theta = NULL returns that set to the shared values.  The parameters are data of the dynamics: they are not QP
+ * variables, do not join p, and the QP pattern does not depend on them.  A launch whose batch exceeds a stored set's is MPCQP_ERR_ARG, a smaller
+ * one uses the first rows.  MPCQP_ERR_ARG as well for a handle whose mpcqp_stage_param_count is 0 (the double integrator; a library generated
+ * without parameters, every library from before this entry included), a bad `which`, or batch <= 0 with a non-NULL theta. */
+#define MPCQP_STAGE_NPAR 8
+#define MPCQP_PARAMS_MODEL 0
+#define MPCQP_PARAMS_PLANT 1
+/* 7 quadrotor, 4 cart-pole, 0 double integrator, ntheta of a generated library */
+int mpcqp_stage_param_count(const mpcqp_stage *s);
+int mpcqp_stage_set_instance_params(mpcqp_stage *s, int which, int batch, const double *theta, int mem);
 /* dims[8] = {nx, nu, np, n, m, nnz(P), nnz(A), horizon * (nx + nu)} */
 int mpcqp_stage_dims(const mpcqp_stage *s, int *dims8);
 /* 1 when the evaluator was generated with its own stage cost (mpcqp_stage_create_user above), 0 for diagonal tracking weights */

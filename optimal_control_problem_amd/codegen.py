@@ -378,11 +378,49 @@ def _array_function(tape, func, args, kwargs):
     raise TypeError("NumPy function %s cannot be traced" % func.__name__)
 
 
-def _trace_fn(fn, nx, nu, n_out, what):
-    tape = Tape(nx + nu)
+NTHETA_MAX = 8        # MPCQP_STAGE_NPAR: the width of a parameter row
+
+
+class _ThetaGuard:
+    """stands in for model.theta while a function other than F is traced: parameters are data of the dynamics only"""
+
+    def __init__(self, what):
+        self._what = what
+
+    def _refuse(self, *a, **k):
+        raise ValueError("%s reads self.theta: model parameters are supported in F / cdyn only (not in hfun, kfun, lcost, lterm)" % self._what)
+
+    __getitem__ = __iter__ = __len__ = __array__ = __add__ = __radd__ = __mul__ = __rmul__ = __sub__ = __rsub__ = __truediv__ = __rtruediv__ = __neg__ = _refuse
+
+
+class _bound_theta:
+    """model.theta = value for the duration of a trace (a model without parameters, or no model: nothing happens)"""
+
+    def __init__(self, model, value):
+        self.model, self.value = model, value
+
+    def __enter__(self):
+        if self.model is not None:
+            self.saved = self.model.theta
+            self.model.theta = self.value
+
+    def __exit__(self, *exc):
+        if self.model is not None:
+            self.model.theta = self.saved
+        return False
+
+
+def _trace_fn(fn, nx, nu, n_out, what, ntheta=0, model=None):
+    """ntheta > 0: that many extra tape inputs behind [s; u], bound to model.theta while fn runs (the plant parameters: par[i] in the emitted code)"""
+    tape = Tape(nx + nu + ntheta)
     s = TV(tape, [TS(tape, i) for i in range(nx)])
     u = TV(tape, [TS(tape, nx + i) for i in range(nu)])
-    out = fn(s, u)
+    if ntheta:
+        with _bound_theta(model, TV(tape, [TS(tape, nx + nu + i) for i in range(ntheta)])):
+            out = fn(s, u)
+        tape.in_names = [("s", nx), ("u", nu), ("par", ntheta)]
+    else:
+        out = fn(s, u)
     if isinstance(out, TS):
         out = TV(tape, [out])
     if isinstance(out, (list, tuple)):
@@ -428,36 +466,59 @@ def _trace_link(kfun, nx, nu, nk):
     return tape
 
 
-def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False):
+def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False,
+          ntheta=0, theta0=None, model=None):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
     the diagonal tracking weights; lterm: the same for the last frame only (terminal cost).  Their gradients are derived
     on the tape (reverse mode); the kernels differentiate those once more with dual numbers for the exact Hessian.
     per_frame_reference: the library is emitted for trajectory tracking (models.StageOCP.per_frame_reference: frame k's cost takes its own
-    reference r_k, mpcqp_stage_create_tracking loads it); the traced functions are the same."""
-    tape = _trace_fn(F, nx, nu, nx, "F must return the next state")
+    reference r_k, mpcqp_stage_create_tracking loads it); the traced functions are the same.
+    ntheta = k (<= 8), theta0 = the k default values: the model (`model`, or the object F is bound to) reads its plant parameters as
+    self.theta[i] inside F / cdyn; while F is traced, self.theta holds k extra tape inputs, emitted as par[i] -- data of the functor, not constants
+    of its code, so that mpcqp_stage_set_instance_params can give every instance its own.  Any other traced function that touches self.theta
+    raises a ValueError."""
+    ntheta = int(ntheta)
+    if ntheta > NTHETA_MAX:
+        raise ValueError("at most %d model parameters are supported (ntheta = %d)" % (NTHETA_MAX, ntheta))
+    if model is None:
+        model = getattr(F, "__self__", None)
+    guarded = model if ntheta else None       # whose theta the other traces may not read (without parameters in the trace, theta is numbers like any other)
+    if ntheta:
+        if model is None:
+            raise ValueError("ntheta needs the model whose theta F reads (model=, or F as a bound method)")
+        theta0 = np.asarray(model.theta if theta0 is None else theta0, float).ravel()
+        if theta0.size != ntheta:
+            raise ValueError("theta0 must hold ntheta = %d values" % ntheta)
+    tape = _trace_fn(F, nx, nu, nx, "F must return the next state", ntheta, model)
+    tape.ntheta = ntheta
+    tape.theta0 = [float(v) for v in theta0] if ntheta else []
     tape.pref = bool(per_frame_reference)
     tape.nh = int(nh) if hfun is not None else 0
     tape.path = None
     if tape.nh:
-        tape.path = _trace_fn(hfun, nx, nu, tape.nh, "hfun must return the path-constraint values")
+        with _bound_theta(guarded, _ThetaGuard("hfun")):
+            tape.path = _trace_fn(hfun, nx, nu, tape.nh, "hfun must return the path-constraint values")
         tape.h_lo = [float(v) for v in np.broadcast_to(np.asarray(h_lo, float), (tape.nh,))]
         tape.h_hi = [float(v) for v in np.broadcast_to(np.asarray(h_hi, float), (tape.nh,))]
     # link constraint k_lo <= kfun(s_k, u_k, s_{k+1}, u_{k+1}) <= k_hi between consecutive frames (rate limits and the like)
     tape.nk = int(nk) if kfun is not None else 0
     tape.link = None
     if tape.nk:
-        tape.link = _trace_link(kfun, nx, nu, tape.nk)
+        with _bound_theta(guarded, _ThetaGuard("kfun")):
+            tape.link = _trace_link(kfun, nx, nu, tape.nk)
         tape.k_lo = [float(v) for v in np.broadcast_to(np.asarray(k_lo, float), (tape.nk,))]
         tape.k_hi = [float(v) for v in np.broadcast_to(np.asarray(k_hi, float), (tape.nk,))]
     tape.cost = None
     if lcost is not None:
-        L, G = trace_cost(lcost, nx, nu, nx)
+        with _bound_theta(guarded, _ThetaGuard("lcost")):
+            L, G = trace_cost(lcost, nx, nu, nx)
         mask = hessian_mask(G)
         LT = GT = None
         if lterm is not None:
-            LT, GT = trace_cost(lterm, nx, nu, nx)
+            with _bound_theta(guarded, _ThetaGuard("lterm")):
+                LT, GT = trace_cost(lterm, nx, nu, nx)
             mask = mask | hessian_mask(GT)
         mask = mask | np.eye(mask.shape[0], dtype=bool)      # keep the diagonal in the pattern
         tape.cost = dict(L=L, G=G, LT=LT, GT=GT, mask=mask)
@@ -480,6 +541,14 @@ def _emit_body(tape, streaming=False):
     live = tape.live_nodes()
     ref = {}
     lines = []
+    # nodes that depend on parameters and constants only are plain doubles next to T = Dual (a parameter carries no derivative): they mix with T
+    # through the double-Dual operators, as literals do
+    par_from = tape.nx + tape.nu if getattr(tape, "ntheta", 0) else tape.n_in
+    plain = set()
+    for i in live:
+        nd = tape.nodes[i]
+        if nd[0] == "const" or (nd[0] == "in" and nd[1] >= par_from) or (nd[0] not in ("in", "const") and all(a in plain for a in nd[1:])):
+            plain.add(i)
     for i in live:
         nd = tape.nodes[i]
         if nd[0] == "in":
@@ -497,12 +566,11 @@ def _emit_body(tape, streaming=False):
         elif nd[0] in _UNARY:
             f = _UNARY[nd[0]]
             expr = "-%s" % ref[nd[1]] if nd[0] == "neg" else "%s(%s)" % (f, ref[nd[1]])
-            lines.append("    const T w%d = %s;" % (i, expr)); ref[i] = "w%d" % i
+            lines.append("    const %s w%d = %s;" % ("double" if i in plain else "T", i, expr)); ref[i] = "w%d" % i
         else:
-            lines.append("    const T w%d = %s %s %s;" % (i, ref[nd[1]], _BINARY[nd[0]], ref[nd[2]])); ref[i] = "w%d" % i
+            lines.append("    const %s w%d = %s %s %s;" % ("double" if i in plain else "T", i, ref[nd[1]], _BINARY[nd[0]], ref[nd[2]])); ref[i] = "w%d" % i
     for r, o in enumerate(tape.outputs):
-        nd = tape.nodes[o]
-        lines.append("    out[%d] = %s;" % (r, "T{} + %s" % ref[o] if nd[0] == "const" else ref[o]))
+        lines.append("    out[%d] = %s;" % (r, "T{} + %s" % ref[o] if o in plain else ref[o]))
     return "\n".join(lines)
 
 
@@ -556,11 +624,14 @@ def emit_functor(tape, name="SmUser"):
     cost = getattr(tape, "cost", None)
     hbody = _emit_body(tape.path) if nh else ""
     kbody = _emit_body(tape.link) if nk else ""
-    src = ("struct %s {\n  static constexpr int nx = %d, nu = %d, nh = %d, nk = %d, has_cost = %d, has_term = %d;\n"
-           "  template <class T> SM_HD static void F(const double *, double, const T *s, const T *u, T *out) {\n%s\n  }\n"
+    nth = getattr(tape, "ntheta", 0)
+    # (ntheta > 0: the plant parameters are par[i] in F's body -- data of the launch, sd.par or the instance's row)
+    fmt = ("struct %s {\n  static constexpr int nx = %d, nu = %d, nh = %d, nk = %d, has_cost = %d, has_term = %d;\n"
+           + ("  static constexpr int ntheta = %d;\n" % nth if nth else "") +
+           "  template <class T> SM_HD static void F(const double *" + ("par" if nth else "") + ", double, const T *s, const T *u, T *out) {\n%s\n  }\n"
            "  template <class T> SM_HD static void H(const T *s, const T *u, T *out) {\n%s\n  }\n"
-           "  template <class T> SM_HD static void K(const T *s, const T *u, const T *sn, const T *un, T *out) {\n%s\n  }\n"
-           % (name, tape.nx, tape.nu, nh, nk, 1 if cost else 0, 1 if cost and cost["LT"] is not None else 0, _emit_body(tape), hbody, kbody))
+           "  template <class T> SM_HD static void K(const T *s, const T *u, const T *sn, const T *un, T *out) {\n%s\n  }\n")
+    src = fmt % (name, tape.nx, tape.nu, nh, nk, 1 if cost else 0, 1 if cost and cost["LT"] is not None else 0, _emit_body(tape), hbody, kbody)
     if cost:
         # L: out[0] = l(s, u, r); LG: out[nx + nu + nx] = dl / d[s; u; r]; LT, LTG: the terminal frame's
         for fn, tp in (("L", cost["L"]), ("LG", cost["G"]), ("LT", cost["LT"] or cost["L"]), ("LTG", cost["GT"] or cost["G"])):
@@ -576,6 +647,8 @@ def emit_functor(tape, name="SmUser"):
     src += "static const double %s_k_lo[] = {%s};\nstatic const double %s_k_hi[] = {%s};\n" % (name, klo, name, khi)
     mk = ", ".join(str(int(v)) for v in cost["mask"].ravel()) if cost else "0"
     src += "static const unsigned char %s_cost_mask[] = {%s};\n" % (name, mk)
+    if nth:
+        src += "static const double %s_theta0[] = {%s};\n" % (name, ", ".join(_lit(v) for v in tape.theta0))
     return src
 
 
@@ -612,6 +685,25 @@ int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
   return (int)stage_launch_linesearch<SmUser>(*sd, batch, *a, (hipStream_t)stream);
 }
+%(params)s}
+'''
+
+# a model with parameters (ntheta > 0) only: their count, their defaults (they become sd.par of the handle) and the per-instance-parameter
+# launchers (mpcqp_stage_set_instance_params; theta, plant: device rows [batch * SM_NPAR], null = the shared values)
+_DEVICE_PARAMS_TMPL = '''int mpcqp_user_ntheta() { return SmUser::ntheta; }
+void mpcqp_user_theta0(double *par) { for (int i = 0; i < SmUser::ntheta; i++) par[i] = SmUser_theta0[i]; }
+int mpcqp_user_eval_pp(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
+                       const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream, const double *theta) {
+  return (int)stage_launch_eval<SmUser, false>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr});
+}
+int mpcqp_user_merit_pp(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream, const double *theta) {
+  return (int)stage_launch_merit<SmUser, false>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr});
+}
+int mpcqp_user_advance_pp(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream, const double *theta, const double *plant) {
+  return (int)stage_launch_advance<SmUser, false>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant});
+}
+int mpcqp_user_linesearch_pp(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream, const double *theta) {
+  return (int)stage_launch_linesearch<SmUser, false>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr});
 }
 '''
 
@@ -646,7 +738,19 @@ void user_host_eval(const double *s, const double *u, double *out, double *jac) 
     Dual sd[nx], ud[nu], od[nx];
     for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
     for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
-    SmUser::F<Dual>(nullptr, 0.0, sd, ud, od);
+    SmUser::F<Dual>(%(theta0)s, 0.0, sd, ud, od);
+    for (int r = 0; r < nx; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
+  }
+}
+// the same with the parameter vector given (theta [ntheta]; a functor without parameters ignores it)
+int user_host_ntheta() { return %(ntheta)d; }
+void user_host_eval_theta(const double *theta, const double *s, const double *u, double *out, double *jac) {
+  constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu;
+  for (int c = 0; c < f; c++) {
+    Dual sd[nx], ud[nu], od[nx];
+    for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
+    for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
+    SmUser::F<Dual>(theta, 0.0, sd, ud, od);
     for (int r = 0; r < nx; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
   }
 }
@@ -726,8 +830,10 @@ def _build(src_text, suffix, cmd_prefix):
 def device_source(tape):
     """the translation unit of a stage library.  Traced with per_frame_reference: SmUser::pref, the PF = true kernel instances only, and the
     export mpcqp_user_pref() by which mpcqp_stage_create_tracking / _create_user tell the two kinds apart; else the text it always was"""
-    src = _DEVICE_TMPL % {"functor": emit_functor(tape)}
+    nth = getattr(tape, "ntheta", 0)
+    src = _DEVICE_TMPL % {"functor": emit_functor(tape), "params": _DEVICE_PARAMS_TMPL if nth else ""}
     if getattr(tape, "pref", False):
+        src = src.replace("<SmUser, false>", "<SmUser, SmUser::pref>")
         src = src.replace("stage_launch_eval<SmUser>", "stage_launch_eval<SmUser, SmUser::pref>").replace("stage_launch_merit<SmUser>", "stage_launch_merit<SmUser, SmUser::pref>")
         src = src.replace("stage_launch_advance<SmUser>", "stage_launch_advance<SmUser, SmUser::pref>")
         src = src.replace("stage_launch_linesearch<SmUser>", "stage_launch_linesearch<SmUser, SmUser::pref>")
@@ -742,7 +848,8 @@ def build_device_library(tape):
 
 
 def build_host_library(tape):
-    return _build(_HOST_TMPL % {"functor": emit_functor(tape)}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
+    nth = getattr(tape, "ntheta", 0)
+    return _build(_HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr"}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
 
 
 # ------------------------------------------------------------------------------------------------- general (non-stage) NLPs

@@ -65,6 +65,20 @@ class StageSQP {
     check(mpcqp_stage_set_path_bounds(ocp_, lo.data(), hi.data()), "mpcqp_stage_set_path_bounds");
   }
 
+  // per-instance plant parameters (mpcqp_stage_set_instance_params): values [batch * paramCount()], row b = instance b's parameters in the model's
+  // order; which = MPCQP_PARAMS_MODEL (every evaluation of the loop) or MPCQP_PARAMS_PLANT (the plant step of mpcqp_stage_advance, for callers that
+  // run the hand-over on stage()); an empty vector returns that set to the shared values
+  int paramCount() const { return mpcqp_stage_param_count(ocp_); }
+  void setInstanceParams(int which, const std::vector<double> &values) {
+    if (values.empty()) { check(mpcqp_stage_set_instance_params(ocp_, which, 0, nullptr, MPCQP_MEM_HOST), "mpcqp_stage_set_instance_params"); return; }
+    const int k = paramCount();
+    need(values.size(), (size_t)batch_ * (k > 0 ? k : 1), "values");
+    std::vector<double> rows((size_t)batch_ * MPCQP_STAGE_NPAR, 0.0);
+    for (int b = 0; b < batch_; b++) for (int i = 0; i < k; i++) rows[(size_t)b * MPCQP_STAGE_NPAR + i] = values[(size_t)b * k + i];
+    check(mpcqp_stage_set_instance_params(ocp_, which, batch_, rows.data(), MPCQP_MEM_HOST), "mpcqp_stage_set_instance_params");
+  }
+  mpcqp_stage *stage() const { return ocp_; }
+
   void setInitialGuess(const std::vector<double> &x) {            // extension: the reference always starts from zero
     need(x.size(), (size_t)batch_ * nvar(), "x");
     hip(hipMemcpy(x_, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));

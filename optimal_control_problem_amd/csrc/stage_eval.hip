@@ -23,6 +23,20 @@ typedef int (*user_eval_fn)(const StageDev *, int, const double *, const double 
 typedef int (*user_merit_fn)(const StageDev *, int, const double *, const double *, double *, double *, void *);
 typedef int (*user_advance_fn)(const StageDev *, int, const mpcqp_stage_advance_args *, void *);
 typedef int (*user_linesearch_fn)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *);
+// the per-instance-parameter launchers of a generated library (ntheta > 0): the same arguments, then the device rows ([batch * SM_NPAR]; advance
+// takes the model rows and the plant rows, either may be null = the shared values)
+typedef int (*user_eval_pp_fn)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *,
+                               const double *, double *, double *, double *, double *, double *, void *, const double *);
+typedef int (*user_merit_pp_fn)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *);
+typedef int (*user_advance_pp_fn)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *);
+typedef int (*user_linesearch_pp_fn)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *);
+
+// the zoo's PP instances (quadrotor, cart-pole) live in stage_eval_pp.hip, a translation unit of their own that compiles beside this one
+hipError_t mpcqp_launch_eval_pp(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx, const double *lbg,
+                                const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st, StageTheta th);
+hipError_t mpcqp_launch_merit_pp(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st, StageTheta th);
+hipError_t mpcqp_launch_advance_pp(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st, StageTheta th);
+hipError_t mpcqp_launch_linesearch_pp(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st, StageTheta th);
 
 struct mpcqp_stage {
   mpcqp_stage_desc desc;
@@ -39,7 +53,24 @@ struct mpcqp_stage {
   user_advance_fn user_advance = nullptr;   // optional export: libraries generated before mpcqp_stage_advance have none
   user_linesearch_fn user_linesearch = nullptr;   // optional export, likewise (mpcqp_stage_linesearch)
   bool general_cost = false;          // the library carries its own stage cost: Q, R and mpcqp_stage_set_weights do not apply
+  // per-instance parameters (mpcqp_stage_set_instance_params): set `which` is in force when th_batch[which] > 0
+  int ntheta = 0;                     // entries of a row the model reads: 7 quadrotor, 4 cart-pole, 0 double integrator, mpcqp_user_ntheta of a library
+  double *dth[2] = {nullptr, nullptr};
+  int th_batch[2] = {0, 0}, th_cap[2] = {0, 0};
+  user_eval_pp_fn user_eval_pp = nullptr;
+  user_merit_pp_fn user_merit_pp = nullptr;
+  user_advance_pp_fn user_advance_pp = nullptr;
+  user_linesearch_pp_fn user_linesearch_pp = nullptr;
+  const double *theta(int which) const { return th_batch[which] > 0 ? dth[which] : nullptr; }
 };
+
+// a launch may not be larger than a stored parameter set
+static int stage_theta_batch_ok(const mpcqp_stage *s, int which, int batch) {
+  if (s->th_batch[which] > 0 && batch > s->th_batch[which])
+    return mpcqp_set_error(MPCQP_ERR_ARG, which == MPCQP_PARAMS_MODEL ? "batch is larger than the stored per-instance model parameters (mpcqp_stage_set_instance_params)"
+                                                                      : "batch is larger than the stored per-instance plant parameters (mpcqp_stage_set_instance_params)");
+  return MPCQP_OK;
+}
 
 __global__ void __launch_bounds__(256) stage_step_kernel(int batch, int nvar, int n, int np, double alpha, const double *__restrict__ dw,
                                                          double *__restrict__ x, double *__restrict__ step_max, const int *__restrict__ status) {
@@ -141,6 +172,7 @@ static int stage_create_zoo(const mpcqp_stage_desc *d, bool pref, mpcqp_stage **
   int nx, nu;
   sm_model_dims(d->model, &nx, &nu);
   mpcqp_stage *s = new mpcqp_stage();
+  s->ntheta = d->model == SM_QUADROTOR ? SmQuadrotor::ntheta : d->model == SM_CARTPOLE ? SmCartPole::ntheta : 0;
   if (int rc = stage_create_common(d, nx, nu, 0, nullptr, nullptr, s, nullptr, 0, nullptr, nullptr, pref)) { mpcqp_stage_destroy(s); return rc; }
   *out = s;
   return MPCQP_OK;
@@ -188,6 +220,24 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   s->user_advance = (user_advance_fn)dlsym(lib, "mpcqp_user_advance");
   s->user_linesearch = (user_linesearch_fn)dlsym(lib, "mpcqp_user_linesearch");
   mpcqp_stage_desc dd = *d; dd.model = MPCQP_MODEL_USER;
+  // optional exports of a library generated with parameters: their count, their defaults (which become sd.par: d->par stays ignored for a
+  // generated library) and the four PP launchers.  A library without them -- every one generated before this entry -- has no parameters.
+  {
+    auto ntf = (int (*)())dlsym(lib, "mpcqp_user_ntheta");
+    auto t0f = (void (*)(double *))dlsym(lib, "mpcqp_user_theta0");
+    s->user_eval_pp = (user_eval_pp_fn)dlsym(lib, "mpcqp_user_eval_pp");
+    s->user_merit_pp = (user_merit_pp_fn)dlsym(lib, "mpcqp_user_merit_pp");
+    s->user_advance_pp = (user_advance_pp_fn)dlsym(lib, "mpcqp_user_advance_pp");
+    s->user_linesearch_pp = (user_linesearch_pp_fn)dlsym(lib, "mpcqp_user_linesearch_pp");
+    const int nt = ntf ? ntf() : 0;
+    if (nt < 0 || nt > SM_NPAR || (nt > 0 && !(t0f && s->user_eval_pp && s->user_merit_pp && s->user_advance_pp && s->user_linesearch_pp))) {
+      mpcqp_stage_destroy(s);
+      return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares parameters but not 0..8 of them, or lacks mpcqp_user_theta0 or a _pp launcher");
+    }
+    s->ntheta = nt;
+    for (int i = 0; i < SM_NPAR; i++) dd.par[i] = 0.0;
+    if (nt > 0) t0f(dd.par);
+  }
   std::vector<unsigned char> mask((size_t)(2 * nx + nu) * (2 * nx + nu));
   auto cf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_cost");
   s->general_cost = cf && cf(mask.data());
@@ -214,6 +264,7 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   if (s->dmask) (void)hipFree(s->dmask);
   if (s->dhlo) (void)hipFree(s->dhlo);
   if (s->dhhi) (void)hipFree(s->dhhi);
+  for (int w = 0; w < 2; w++) if (s->dth[w]) (void)hipFree(s->dth[w]);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -250,6 +301,32 @@ int mpcqp_stage_set_path_bounds(mpcqp_stage *s, const double *lo, const double *
   return MPCQP_OK;
 }
 
+int mpcqp_stage_param_count(const mpcqp_stage *s) { return s ? s->ntheta : 0; }
+
+int mpcqp_stage_set_instance_params(mpcqp_stage *s, int which, int batch, const double *theta, int mem) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (s->ntheta == 0)
+    return mpcqp_set_error(MPCQP_ERR_ARG, s->sd.model == MPCQP_MODEL_USER
+                                              ? "this library was generated without parameters (ntheta = 0): its constants are part of the code; declare ntheta and theta on the model and regenerate"
+                                              : "this model has no parameters (mpcqp_stage_param_count is 0)");
+  if (which != MPCQP_PARAMS_MODEL && which != MPCQP_PARAMS_PLANT) return mpcqp_set_error(MPCQP_ERR_ARG, "which must be MPCQP_PARAMS_MODEL or MPCQP_PARAMS_PLANT");
+  if (!theta) { s->th_batch[which] = 0; return MPCQP_OK; }      // back to the shared values; the buffer stays for the next call
+  if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return mpcqp_set_error(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const size_t bytes = (size_t)batch * SM_NPAR * sizeof(double);
+  if (batch > s->th_cap[which]) {
+    double *nb = nullptr;
+    MPCQP_HIPCHK(hipMalloc(&nb, bytes));
+    MPCQP_HIPCHK(hipDeviceSynchronize());       // a launch that reads the old rows may still be queued
+    if (s->dth[which]) (void)hipFree(s->dth[which]);
+    s->dth[which] = nb; s->th_cap[which] = batch; s->th_batch[which] = 0;
+  }
+  MPCQP_HIPCHK(hipMemcpy(s->dth[which], theta, bytes, mem == MPCQP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+  s->th_batch[which] = batch;
+  return MPCQP_OK;
+}
+
 int mpcqp_stage_dims(const mpcqp_stage *s, int *o) {
   if (!s || !o) return mpcqp_set_error(MPCQP_ERR_ARG, "null argument");
   const StageDev &d = s->sd;
@@ -271,9 +348,16 @@ int mpcqp_stage_eval(mpcqp_stage *s, int batch, const double *p, const double *x
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
   if (!p || !x || !lbx || !ubx || !lbg || !ubg || !P || !q || !A || !l || !u) return mpcqp_set_error(MPCQP_ERR_ARG, "null data pointer");
+  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
   MPCQP_HIPCHK(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
+  if (const double *th = s->theta(MPCQP_PARAMS_MODEL)) {
+    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_eval_pp(&s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th)
+                                        : mpcqp_launch_eval_pp(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st, StageTheta{th, nullptr});
+    MPCQP_HIPCHK(e);
+    return MPCQP_OK;
+  }
   switch (s->sd.model) {
     case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_eval<SmDoubleIntegrator, true>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st)
                                             : stage_launch_eval<SmDoubleIntegrator>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
@@ -290,9 +374,16 @@ int mpcqp_stage_eval(mpcqp_stage *s, int batch, const double *p, const double *x
 int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if (batch <= 0 || !p || !x) return mpcqp_set_error(MPCQP_ERR_ARG, "bad batch or null data pointer");
+  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
   MPCQP_HIPCHK(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
+  if (const double *th = s->theta(MPCQP_PARAMS_MODEL)) {
+    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_merit_pp(&s->sd, batch, p, x, f, gmax, stream, th)
+                                        : mpcqp_launch_merit_pp(s->sd, batch, p, x, f, gmax, st, StageTheta{th, nullptr});
+    MPCQP_HIPCHK(e);
+    return MPCQP_OK;
+  }
   switch (s->sd.model) {
     case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_merit<SmDoubleIntegrator, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmDoubleIntegrator>(s->sd, batch, p, x, f, gmax, st); break;
     case SM_QUADROTOR: e = s->sd.pref ? stage_launch_merit<SmQuadrotor, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmQuadrotor>(s->sd, batch, p, x, f, gmax, st); break;
@@ -333,9 +424,17 @@ int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_arg
   if (a->tail != MPCQP_TAIL_REPEAT && a->tail != MPCQP_TAIL_ROLLOUT) return mpcqp_set_error(MPCQP_ERR_ARG, "unknown tail");
   if (s->sd.model == MPCQP_MODEL_USER && !s->user_advance)
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_advance (generated before this entry); regenerate it");
+  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
+  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_PLANT, batch)) return rc;
   MPCQP_HIPCHK(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
+  if (s->theta(MPCQP_PARAMS_MODEL) || s->theta(MPCQP_PARAMS_PLANT)) {
+    const StageTheta th{s->theta(MPCQP_PARAMS_MODEL), s->theta(MPCQP_PARAMS_PLANT)};
+    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_advance_pp(&s->sd, batch, a, stream, th.model, th.plant) : mpcqp_launch_advance_pp(s->sd, batch, *a, st, th);
+    MPCQP_HIPCHK(e);
+    return MPCQP_OK;
+  }
   switch (s->sd.model) {
     case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_advance<SmDoubleIntegrator, true>(s->sd, batch, *a, st) : stage_launch_advance<SmDoubleIntegrator>(s->sd, batch, *a, st); break;
     case SM_QUADROTOR: e = s->sd.pref ? stage_launch_advance<SmQuadrotor, true>(s->sd, batch, *a, st) : stage_launch_advance<SmQuadrotor>(s->sd, batch, *a, st); break;
@@ -359,9 +458,16 @@ int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesear
     return mpcqp_set_error(MPCQP_ERR_ARG, "mu_min and mu_factor must be finite and not negative");
   if (s->sd.model == MPCQP_MODEL_USER && !s->user_linesearch)
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_linesearch (generated before this entry); regenerate it");
+  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
   MPCQP_HIPCHK(hipSetDevice(s->device));
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipSuccess;
+  if (const double *th = s->theta(MPCQP_PARAMS_MODEL)) {
+    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_linesearch_pp(&s->sd, batch, a, stream, th)
+                                        : mpcqp_launch_linesearch_pp(s->sd, batch, *a, st, StageTheta{th, nullptr});
+    MPCQP_HIPCHK(e);
+    return MPCQP_OK;
+  }
   switch (s->sd.model) {
     case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_linesearch<SmDoubleIntegrator, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmDoubleIntegrator>(s->sd, batch, *a, st); break;
     case SM_QUADROTOR: e = s->sd.pref ? stage_launch_linesearch<SmQuadrotor, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmQuadrotor>(s->sd, batch, *a, st); break;

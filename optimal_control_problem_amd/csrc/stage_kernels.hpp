@@ -24,15 +24,28 @@ struct StageDev {
   const double *h_lok, *h_hik;  // optional per-frame path-constraint bounds [N * nh] (device; NULL = h_lo, h_hi on every frame)
 };
 
+// PP (per-instance plant parameters, mpcqp_stage_set_instance_params): rows of SM_NPAR doubles, instance b's at [b * SM_NPAR], in the order of
+// StageDev::par.  `model` is what the controller believes (eval, merit, linesearch, the rollout tail of advance), `plant` what the plant step of
+// advance uses; a null set stands for the shared values sd.par.  The PP instances of the four kernels below take one StageTheta as an extra,
+// last argument -- the template's trailing pack PP is empty or {StageTheta}, so the instances without it keep their signature and their code.
+struct StageTheta { const double *model, *plant; };
+__device__ __forceinline__ StageTheta stage_theta() { return {nullptr, nullptr}; }
+__device__ __forceinline__ StageTheta stage_theta(StageTheta t) { return t; }
+// how many entries of a parameter row the functor reads (M::ntheta; functors without the member read none)
+template <class M, class = void> struct sm_ntheta : std::integral_constant<int, 0> {};
+template <class M> struct sm_ntheta<M, std::void_t<decltype(M::ntheta)>> : std::integral_constant<int, M::ntheta> {};
+
 // PF (per-frame references, StageDev::pref): the parameter block holds one reference state per frame.  Parameter column j = k nx + i is thread j of
 // its instance, as before; the cooperative mapping pads the N nx parameter slots up to a multiple of f, so that every frame's f lanes still start
 // at a multiple of f (threads per instance ceil(N nx / f) f + N f).  Adjacent lanes still own adjacent columns: the store streams stay contiguous.
-template <class M, bool PF = false>
+template <class M, bool PF = false, class... PP>
 __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch, const double *__restrict__ p, const double *__restrict__ x,
                                                          const double *__restrict__ lbx, const double *__restrict__ ubx,
                                                          const double *__restrict__ lbg, const double *__restrict__ ubg,
                                                          double *__restrict__ P, double *__restrict__ q, double *__restrict__ A,
-                                                         double *__restrict__ l, double *__restrict__ u) {
+                                                         double *__restrict__ l, double *__restrict__ u, PP... pp) {
+  constexpr bool HASPP = sizeof...(PP) > 0;
+  constexpr int NT = sm_ntheta<M>::value > 0 ? sm_ntheta<M>::value : 1;
   constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
   // cooperative functors (sm_has_coop): the f lanes of a stage sit in one wave at a multiple of f -- the parameter columns get a group of f thread
   // slots of their own (nx of them used), every frame the next f; threads per instance f (N + 1) instead of n
@@ -44,6 +57,16 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
   const int per = COOP ? ppad + f * N : n;
   if (gid >= (long)batch * per) return;
   const int b = (int)(gid / per), jt = (int)(gid - (long)b * per);
+  // PP: a wave holds lanes of several instances (the cooperative quadrotor at N = 2: 48 thread slots per instance), so b and the parameter row are
+  // per lane; the entries the functor reads are loaded once, here, and live in registers from then on
+  double th[NT];
+  const double *par = sd.par;
+  if constexpr (HASPP) {
+    const double *row = stage_theta(pp...).model + (long)b * SM_NPAR;
+#pragma unroll
+    for (int i = 0; i < NT; i++) th[i] = row[i];
+    par = th;
+  }
   if (COOP && jt < ppad && jt >= npar) return;       // (padding lanes of the parameter group)
   const int j = COOP ? (jt < ppad ? jt : jt - ppad + npar) : jt;
   const double *pb = p + (long)b * npar, *xb = x + (long)b * sd.nvar;
@@ -171,7 +194,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
   if (k >= 1 && c < nx) Ac[a++] = 1.0;
   if (k < N - 1) {
     Dual out[nx];
-    if constexpr (COOP) M::Fc(sd.par, sd.dt, s, uu, out, c); else M::template F<Dual>(sd.par, sd.dt, s, uu, out);
+    if constexpr (COOP) M::Fc(par, sd.dt, s, uu, out, c); else M::template F<Dual>(par, sd.dt, s, uu, out);
 #pragma unroll
     for (int r = 0; r < nx; r++) Ac[a + r] = -out[r].d;
     a += nx;
@@ -238,12 +261,16 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
 }
 
 // one wave per instance: lanes stride over the frames, butterfly reduction (fixed order => deterministic)
-template <class M, bool PF = false>
+template <class M, bool PF = false, class... PP>
 __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch, const double *__restrict__ p, const double *__restrict__ x,
-                                                          double *__restrict__ fout, double *__restrict__ gout) {
+                                                          double *__restrict__ fout, double *__restrict__ gout, PP... pp) {
   constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
   const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (b >= batch) return;
+  // PP: b is the same on every lane of the wave, which the compiler cannot see through threadIdx.x >> 6; said so, the row's address is
+  // scalar, its entries arrive by scalar loads and F sees a uniform pointer, as it does with sd.par
+  const double *par = sd.par;
+  if constexpr (sizeof...(PP) > 0) par = stage_theta(pp...).model + (long)__builtin_amdgcn_readfirstlane(b) * SM_NPAR;
   const double *pb0 = p + (long)b * (PF ? sd.N * nx : nx), *xb = x + (long)b * sd.nvar;
   double cost = 0.0, gmax = 0.0;
   for (int k = lane; k < sd.N; k += 64) {
@@ -267,7 +294,7 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
     }
     if (k < sd.N - 1) {
       double out[nx];
-      M::template F<double>(sd.par, sd.dt, s, uu, out);
+      M::template F<double>(par, sd.dt, s, uu, out);
 #pragma unroll
       for (int i = 0; i < nx; i++) gmax = fmax(gmax, fabs(fr[f + i] - out[i]));
     }
@@ -311,8 +338,8 @@ __device__ __forceinline__ void stage_shift_block(double *__restrict__ out, cons
 // elements of every array: pure data movement but for two runs of F<double> -- the plant step F(s_0, u_0) on lane 0 and the rollout tail
 // F(s_{N-1}, u_{N-1}) on lane 1, one pass of the wave for both -- and the k = 0 cost term on lane 0.  Their nx results go by wave shuffle to the
 // lanes c < nx that store them, so every store stream is contiguous.  No LDS, no atomics, one writer per output element.
-template <class M, bool PF = false>
-__global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int batch, mpcqp_stage_advance_args a) {
+template <class M, bool PF = false, class... PP>
+__global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int batch, mpcqp_stage_advance_args a, PP... pp) {
   constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
   static_assert(f <= 64, "a frame is stored by one pass of the wave");
   const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -333,7 +360,19 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
     for (int i = 0; i < nx; i++) s[i] = fr[i];
 #pragma unroll
     for (int i = 0; i < nu; i++) uu[i] = fr[nx + i];
-    if (lane == 0 ? a.s_meas == nullptr : rollout) M::template F<double>(sd.par, sd.dt, s, uu, Fo);
+    if constexpr (sizeof...(PP) > 0) {
+      // PP: the plant step (lane 0) takes the plant row, or the model row when no plant set is stored; the rollout tail (lane 1) the model
+      // row; a set that is not stored stands for sd.par.  Values, not addresses, are selected: sd.par stays in its scalar registers
+      constexpr int NT = sm_ntheta<M>::value > 0 ? sm_ntheta<M>::value : 1;
+      const StageTheta t = stage_theta(pp...);
+      const double *row = lane == 0 && t.plant ? t.plant : t.model;
+      double th[NT];
+#pragma unroll
+      for (int i = 0; i < NT; i++) th[i] = row ? row[(long)b * SM_NPAR + i] : sd.par[i];
+      if (lane == 0 ? a.s_meas == nullptr : rollout) M::template F<double>(th, sd.dt, s, uu, Fo);
+    } else {
+      if (lane == 0 ? a.s_meas == nullptr : rollout) M::template F<double>(sd.par, sd.dt, s, uu, Fo);
+    }
     if (lane == 0 && a.stage_cost) {
       // the k = 0 term of stage_merit_kernel's objective, in its order of operations
       const double *pb = PF ? a.p_in + (long)b * np : a.p + (long)b * nx;
@@ -419,11 +458,13 @@ template <int NC, int J = NC - 1> __device__ __forceinline__ double stage_ls_get
 // lane's per-candidate partial sums; the box terms, q' dx and max |y| stride over their arrays; one butterfly in fixed order reduces everything
 // (two runs give the same bits) and leaves the totals on every lane, so the decision is taken redundantly by all of them.  x is written after that,
 // by stage_step_kernel's expression: every read of x precedes it in program order of the same wave.  No LDS, no atomics, one writer per output.
-template <class M, bool PF = false>
-__global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int batch, mpcqp_stage_linesearch_args a) {
+template <class M, bool PF = false, class... PP>
+__global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int batch, mpcqp_stage_linesearch_args a, PP... pp) {
   constexpr int nx = M::nx, nu = M::nu, f = nx + nu, NC = MPCQP_LINESEARCH_MAX_CANDIDATES + 1;
   const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (b >= batch) return;
+  const double *par = sd.par;      // PP: the instance's row through a wave-uniform b, as in stage_merit_kernel
+  if constexpr (sizeof...(PP) > 0) par = stage_theta(pp...).model + (long)__builtin_amdgcn_readfirstlane(b) * SM_NPAR;
   const int N = sd.N, nvar = sd.nvar, np = sd.np;
   bool ok = true;
   if (a.status) { const int s = a.status[b]; ok = s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
@@ -462,7 +503,7 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
     }
     if (k < N - 1) {
       double out[nx];
-      M::template F<double>(sd.par, sd.dt, s, uu, out);
+      M::template F<double>(par, sd.dt, s, uu, out);
 #pragma unroll
       for (int i = 0; i < nx; i++) {
         double sn = fr[f + i];
@@ -563,27 +604,29 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
 }
 
 // launchers shared by the zoo dispatch and generated libraries
-template <class M, bool PF = false>
+// (PP: empty, or one StageTheta behind the stream -- the per-instance-parameter instances)
+template <class M, bool PF = false, class... PP>
 inline hipError_t stage_launch_eval(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
-                                    const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st) {
+                                    const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st,
+                                    PP... pp) {
   constexpr int f = M::nx + M::nu;
   const int ppad = PF ? (sd.N * M::nx + f - 1) / f * f : f;
   const long threads = (long)batch * ((sm_has_coop<M>::value && (64 % f == 0) && M::nx <= f) ? ppad + f * sd.N : sd.n);
-  stage_eval_kernel<M, PF><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u);
+  stage_eval_kernel<M, PF, PP...><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, pp...);
   return hipGetLastError();
 }
-template <class M, bool PF = false>
-inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st) {
-  stage_merit_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, p, x, f, gmax);
+template <class M, bool PF = false, class... PP>
+inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st, PP... pp) {
+  stage_merit_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, p, x, f, gmax, pp...);
   return hipGetLastError();
 }
-template <class M, bool PF = false>
-inline hipError_t stage_launch_advance(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st) {
-  stage_advance_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a);
+template <class M, bool PF = false, class... PP>
+inline hipError_t stage_launch_advance(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st, PP... pp) {
+  stage_advance_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a, pp...);
   return hipGetLastError();
 }
-template <class M, bool PF = false>
-inline hipError_t stage_launch_linesearch(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st) {
-  stage_linesearch_kernel<M, PF><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a);
+template <class M, bool PF = false, class... PP>
+inline hipError_t stage_launch_linesearch(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st, PP... pp) {
+  stage_linesearch_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a, pp...);
   return hipGetLastError();
 }

@@ -83,7 +83,7 @@ SM_HD void sm_rk4(const double *par, double h, const T *s, const T *u, T *out) {
 
 // nx = 2, nu = 1; exact zero-order-hold map (models.py DoubleIntegrator.F); no parameters
 struct SmDoubleIntegrator {
-  static constexpr int nx = 2, nu = 1, nh = 0, nk = 0, has_cost = 0, has_term = 0;
+  static constexpr int nx = 2, nu = 1, nh = 0, nk = 0, has_cost = 0, has_term = 0, ntheta = 0;
   template <class T> SM_HD static void H(const T *, const T *, T *) {}
   template <class T> SM_HD static void F(const double *, double h, const T *s, const T *u, T *out) {
     out[0] = s[0] + h * s[1] + ((0.5 * h) * h) * u[0];
@@ -93,7 +93,7 @@ struct SmDoubleIntegrator {
 
 // 12-state quadrotor (models.py Quadrotor.cdyn); par = {mass, grav, arm, kappa, Jx, Jy, Jz}
 struct SmQuadrotor {
-  static constexpr int nx = 12, nu = 4, nh = 0, nk = 0, has_cost = 0, has_term = 0;
+  static constexpr int nx = 12, nu = 4, nh = 0, nk = 0, has_cost = 0, has_term = 0, ntheta = 7;
   static constexpr int coop = 1;      // has Fc: the lanes of a stage evaluate the trigonometry together (stage_kernels.hpp)
   template <class T> SM_HD static void H(const T *, const T *, T *) {}
   // t = {sin, cos} of roll, pitch, yaw
@@ -144,7 +144,7 @@ struct SmQuadrotor {
 
 // cart-pole, s = [x, theta, xdot, thetadot], theta = 0 upright (models.py CartPole.cdyn); par = {mc, mp, length, grav}
 struct SmCartPole {
-  static constexpr int nx = 4, nu = 1, nh = 0, nk = 0, has_cost = 0, has_term = 0;
+  static constexpr int nx = 4, nu = 1, nh = 0, nk = 0, has_cost = 0, has_term = 0, ntheta = 4;
   template <class T> SM_HD static void H(const T *, const T *, T *) {}
   template <class T> SM_HD static void cdyn(const double *par, const T *s, const T *u, T *ds) {
     const double mc = par[0], mp = par[1], len = par[2], grav = par[3];

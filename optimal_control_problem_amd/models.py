@@ -199,9 +199,49 @@ class StageOCP:
     # takes an SX of any size (src/OptimalControlProblem.cpp:570-572), computeOptimalTrajectory checks the size only (:85-90) and the user
     # subtracts slice k in the cost of step k.  Variables stay [p; frames], rows [p; frames; dynamics; path; link]; only np grows.
     per_frame_reference = False
+    # opt-in plant parameters: a model declares ntheta = k <= 8 and theta = np.array([...]) (the defaults) and reads self.theta[i] inside F or cdyn
+    # (not in hfun, kfun, lcost, lterm).  The zoo classes map their attributes (mass, length, ...) onto the same vector, in the order of
+    # stage_eval.model_params.  set_instance_params gives every instance of a batch its own row: a batch of different robots.
+    ntheta = 0; theta = None
+    NTHETA_MAX = 8
+    _theta_rows = None; _plant_rows = None
+
+    def set_instance_params(self, theta=None, plant=None):
+        """Host statement of mpcqp_stage_set_instance_params.  theta [B, ntheta]: instance b's parameters, what local_system, objective,
+        constraints, violation, line_search and the rollout tail of advance use; plant [B, ntheta]: what the plant step of advance uses (unset:
+        the model's rows).  None returns that set to the shared values self.theta.  A call with more instances than rows is a ValueError, a
+        smaller batch uses the first rows.  The methods evaluate instance by instance with that instance's values put on the object: this is
+        the checker, its batches are small.  With nothing set every method returns the bits it always did."""
+        rows = []
+        for v, what in ((theta, "theta"), (plant, "plant")):
+            if v is not None:
+                if self.ntheta == 0:
+                    raise ValueError("this model has no parameters (ntheta = 0)")
+                v = np.array(v, float)
+                if v.ndim != 2 or v.shape[1] != self.ntheta or v.shape[0] < 1:
+                    raise ValueError("%s: expected an array [B, %d]" % (what, self.ntheta))
+            rows.append(v)
+        self._theta_rows, self._plant_rows = rows
+
+    def _each_instance(self, rows, B, fn):
+        """[fn(slice(b, b + 1)) for every instance b], each with row b of `rows` as self.theta and no per-instance set in force"""
+        if rows.shape[0] < B:
+            raise ValueError("batch %d is larger than the stored per-instance parameters (%d rows)" % (B, rows.shape[0]))
+        saved = (np.array(self.theta, float), self._theta_rows, self._plant_rows)
+        out = []
+        try:
+            self._theta_rows = self._plant_rows = None
+            for b in range(B):
+                self.theta = rows[b].copy()
+                out.append(fn(slice(b, b + 1)))
+        finally:
+            self.theta, self._theta_rows, self._plant_rows = saved
+        return out
 
     def __init__(self, N, dt, Q, R):
         self.N, self.dt = int(N), float(dt)
+        if self.ntheta > self.NTHETA_MAX:
+            raise ValueError("a model may declare at most %d parameters (ntheta = %d)" % (self.NTHETA_MAX, self.ntheta))
         # diagonal weights, the same for every frame ([nx], [nu]) or one row per frame ([N, nx], [N, nu]: terminal costs,
         # ramps) -- addVectorCost is called per step in the reference (readme.md:121-128), so weights may differ by step
         self.Q = np.asarray(Q, float); self.R = np.asarray(R, float)
@@ -383,6 +423,8 @@ class StageOCP:
         return X[:, :, :self.nx], X[:, :, self.nx:]
 
     def objective(self, p, x):
+        if self._theta_rows is not None:       # (the parameters enter F only; evaluated per instance like every other method, for one rule)
+            return np.concatenate(self._each_instance(self._theta_rows, x.shape[0], lambda i: self.objective(p[i], x[i])))
         if self.general_cost:
             return self._cost_eval(self._ltape, self._lttape, self._cost_inputs(p, x))[0].sum(axis=1)
         s, u = self.frames(x)
@@ -407,6 +449,8 @@ class StageOCP:
 
     def constraints(self, x):
         """dynamics defects only (the equality rows)"""
+        if self._theta_rows is not None:
+            return np.concatenate(self._each_instance(self._theta_rows, x.shape[0], lambda i: self.constraints(x[i])))
         s, u = self.frames(x)
         return (s[:, 1:, :] - self.F(s[:, :-1, :], u[:, :-1, :])).reshape(x.shape[0], -1)
 
@@ -415,6 +459,10 @@ class StageOCP:
         return np.asarray(self.hfun(s, u)).reshape(x.shape[0], -1)
 
     def local_system(self, p, x, lbx, ubx, lbg, ubg):
+        if self._theta_rows is not None:
+            one = self._each_instance(self._theta_rows, x.shape[0], lambda i: self.local_system(p[i], x[i], lbx[i], ubx[i], lbg[i], ubg[i]))
+            cat = lambda k: np.concatenate([getattr(o, k) for o in one])
+            return LocalSystem(self.n, self.m, self.Pp, self.Pi, self.Ap, self.Ai, cat("P"), cat("q"), cat("A"), cat("l"), cat("u"), self.np)
         B = x.shape[0]; N, nx, nu, f, npp, n = self.N, self.nx, self.nu, self.f, self.np, self.n
         s, u = self.frames(x)
         e = s - (p.reshape(s.shape) if self.pref else p[:, None, :])
@@ -499,6 +547,21 @@ class StageOCP:
             raise ValueError("tail must be 'repeat' or 'rollout'")
         if s_meas is not None and w is not None:
             raise ValueError("give w or s_meas, not both")
+        if self._theta_rows is not None or self._plant_rows is not None:
+            # the rollout tail and everything else by the model rows; the plant step F(s_0, u_0) by the plant rows (unset: the model's)
+            B = x.shape[0]
+            mrows = self._theta_rows if self._theta_rows is not None else np.broadcast_to(np.array(self.theta, float), (B, self.ntheta))
+            prows = self._plant_rows if self._plant_rows is not None else mrows
+            sl = lambda v, i, dt=float: None if v is None else np.asarray(v, dt).reshape(B, -1)[i]
+            call = lambda i: self.advance(sl(x, i), sl(lbx, i), sl(ubx, i), None if status is None else np.asarray(status).reshape(B)[i], sl(s_meas, i), sl(w, i),
+                                          tail, sl(p, i), sl(r_new, i), sl(dw, i), sl(y, i))
+            one = self._each_instance(mrows, B, call)
+            out = {k: np.concatenate([o[k] for o in one]) for k in one[0]}
+            if s_meas is None:
+                plant = np.concatenate([o["x"][:, :self.nx] for o in self._each_instance(prows, B, call)])
+                for k in ("x", "lbx", "ubx"):
+                    out[k][:, :self.nx] = plant
+            return out
         B, N, nx, f, npp, n = x.shape[0], self.N, self.nx, self.f, self.np, self.n
         X = np.asarray(x, float).reshape(B, N, f)
         ok = np.ones(B, bool) if status is None else np.isin(np.asarray(status), self.STATUS_OK)
@@ -550,6 +613,9 @@ class StageOCP:
     def violation(self, x, lbx, ubx):
         """(v [B], gmax [B]): the l1 violation measure of the line search -- dynamics defects, path and link rows outside their bounds, entries of
         x outside lbx / ubx; an infinite bound contributes 0 -- and the max-norm violation mpcqp_stage_merit returns (no box terms in that one)"""
+        if self._theta_rows is not None:
+            one = self._each_instance(self._theta_rows, np.shape(x)[0], lambda i: self.violation(np.asarray(x, float)[i], np.asarray(lbx, float)[i], np.asarray(ubx, float)[i]))
+            return np.concatenate([o[0] for o in one]), np.concatenate([o[1] for o in one])
         with np.errstate(all="ignore"):
             x = np.asarray(x, float)
             d = np.abs(self.constraints(x))
@@ -589,6 +655,15 @@ class StageOCP:
             raise ValueError("mu_min and mu_factor must be finite and not negative")
         B, npp = x.shape[0], self.np
         p = np.asarray(p, float); lbx = np.asarray(lbx, float); ubx = np.asarray(ubx, float)
+        if self._theta_rows is not None:
+            # x[i] and mu[i] are views: the in-place updates of the per-instance calls land in the caller's arrays
+            st = None if status is None else np.asarray(status)
+            one = self._each_instance(self._theta_rows, B, lambda i: self.line_search(
+                p[i], x[i], lbx[i], ubx[i], np.asarray(q, float)[i], np.asarray(dw, float)[i], np.asarray(y, float)[i], None if st is None else st[i],
+                None if mu is None else mu[i], alpha0, candidates, beta, c1, mu_min, mu_factor))
+            out = {k: np.concatenate([o[k] for o in one]) for k in one[0] if k not in ("x", "alphas")}
+            out["x"] = x; out["alphas"] = one[0]["alphas"]
+            return out
         ok = np.ones(B, bool) if status is None else np.isin(np.asarray(status), self.STATUS_OK)
         alphas = np.empty(K)
         alphas[0] = alpha0
@@ -652,6 +727,17 @@ class Quadrotor(StageOCP):
     nx = 12; nu = 4; name = "quadrotor"
     mass = 1.0; grav = 9.81; arm = 0.2; kappa = 0.05
     inertia = np.array([0.01, 0.01, 0.02])
+    ntheta = 7
+
+    @property
+    def theta(self):
+        """{mass, grav, arm, kappa, Jx, Jy, Jz}: the attributes as one vector (stage_eval.model_params)"""
+        return np.array([self.mass, self.grav, self.arm, self.kappa] + [float(v) for v in self.inertia])
+
+    @theta.setter
+    def theta(self, v):
+        self.mass, self.grav, self.arm, self.kappa = v[0], v[1], v[2], v[3]
+        self.inertia = np.array(v[4:7], float)
 
     def __init__(self, N=20, dt=0.02):
         super().__init__(N, dt, [10.0] * 3 + [1.0] * 3 + [1.0] * 3 + [0.1] * 3, [0.1] * 4)
@@ -694,6 +780,16 @@ class CartPole(StageOCP):
     thetadot] with theta = 0 upright, |u| <= 20 N, track +-2.4 m, dt = 0.02; Gauss-Newton Hessian = 2Q."""
     nx = 4; nu = 1; name = "cartpole"
     mc = 1.0; mp = 0.1; length = 0.5; grav = 9.81
+    ntheta = 4
+
+    @property
+    def theta(self):
+        """{mc, mp, length, grav}: the attributes as one vector (stage_eval.model_params)"""
+        return np.array([self.mc, self.mp, self.length, self.grav])
+
+    @theta.setter
+    def theta(self, v):
+        self.mc, self.mp, self.length, self.grav = v[0], v[1], v[2], v[3]
 
     def __init__(self, N=100, dt=0.02):
         super().__init__(N, dt, [1.0, 10.0, 0.1, 0.1], [0.01])

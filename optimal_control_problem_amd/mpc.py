@@ -51,6 +51,17 @@ class ClosedLoopMPC:
         self.ticks = 0
         self._ready = True
 
+    def set_instance_params(self, model=None, plant=None):
+        """a fleet: one row of plant parameters per instance, [batch, param_count] each (NumPy or CUDA tensor).  model: what the controller
+        believes (every evaluation of the SQP loop and the rollout tail); plant: what the simulated plant step F(s_0, u_0) between two ticks
+        uses -- unset, the plant is the controller's model.  None returns that set to the model's shared values.  A plant-model mismatch
+        is then studied on the device: nominal controller, randomised plants (examples/fleet_mpc.py)."""
+        for v in (model, plant):
+            if v is not None and int(np.shape(v)[0]) != self.batch:
+                raise ValueError("expected %d rows, one per instance" % self.batch)
+        self.ev.set_instance_params(model, plant=False)
+        self.ev.set_instance_params(plant, plant=True)
+
     @property
     def x(self):
         """the trajectory the next tick starts from [B, N f] (device)"""

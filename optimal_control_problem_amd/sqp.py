@@ -253,6 +253,15 @@ class DeviceSQPOptimizationSolver:
         if self.line_search is not None:
             self.mu.zero_()
 
+    def setInstanceParams(self, theta):
+        """extension: one row of plant parameters per instance, [batch, param_count] (NumPy or CUDA tensor), for every evaluation of the loop
+        (StageEvaluator.set_instance_params, the model's set); None returns to the shared values.  Stage OCPs only."""
+        if not hasattr(self.ev, "set_instance_params"):
+            raise ValueError("per-instance parameters are limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has none")
+        if theta is not None and int(np.shape(theta)[0]) != self.batch:
+            raise ValueError("theta: expected %d rows, one per instance" % self.batch)
+        self.ev.set_instance_params(theta)
+
     def _dev(self, a, w):
         import torch
         if isinstance(a, torch.Tensor):

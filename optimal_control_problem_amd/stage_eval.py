@@ -25,6 +25,8 @@ class AdvanceArgs(C.Structure):
 
 
 TAILS = {"repeat": 0, "rollout": 1}
+NPAR = 8                                  # MPCQP_STAGE_NPAR: the width of a parameter row
+PARAMS_MODEL, PARAMS_PLANT = 0, 1         # MPCQP_PARAMS_*
 
 
 class LineSearchArgs(C.Structure):
@@ -46,6 +48,8 @@ def _bind(L):
     L.mpcqp_stage_destroy.restype = None
     L.mpcqp_stage_set_weights.argtypes = [vp, dp, dp]
     L.mpcqp_stage_set_path_bounds.argtypes = [vp, dp, dp]
+    L.mpcqp_stage_param_count.argtypes = [vp]
+    L.mpcqp_stage_set_instance_params.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int]
     L.mpcqp_stage_dims.argtypes = [vp, vp]
     L.mpcqp_stage_has_cost.argtypes = [vp]
     L.mpcqp_stage_pattern.argtypes = [vp, vp, vp, vp, vp]
@@ -111,10 +115,14 @@ class StageEvaluator:
             if use_codegen:
                 from . import codegen as cg
                 h_lo, h_hi = model.path_bounds()
+                # a model that declares parameters (ntheta, theta) keeps them as data of the generated functor.  The zoo classes, when they take this
+                # path (a path / link constraint, a general cost), keep their constants in the code as before: no parameters on that handle
+                nth = 0 if isinstance(model, (_m.Quadrotor, _m.CartPole)) else int(getattr(model, "ntheta", 0))
+                pkw = {"ntheta": nth, "theta0": model.theta, "model": model} if nth else {}
                 self.tape = cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
                                      lcost=model.lcost if general else None, lterm=model.lterm if general else None,
                                      kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
-                                     **({"per_frame_reference": True} if self.per_frame_reference else {}))
+                                     **({"per_frame_reference": True} if self.per_frame_reference else {}), **pkw)
                 self.library = cg.build_device_library(self.tape)
             else:
                 for i, v in enumerate(model_params(model)): d.par[i] = float(v)
@@ -140,6 +148,7 @@ class StageEvaluator:
         self.nx, self.nu, self.np, self.n, self.m, self.nnzP, self.nnzA, self.nvar = [int(v) for v in dims]
         self.ng = self.m - self.n
         self.general_cost = bool(L.mpcqp_stage_has_cost(self._h))
+        self.param_count = int(L.mpcqp_stage_param_count(self._h))      # parameters per instance (mpcqp_stage_set_instance_params); 0: none
         self.Pp = np.zeros(self.n + 1, np.int32); self.Pi = np.zeros(self.nnzP, np.int32)
         self.Ap = np.zeros(self.n + 1, np.int32); self.Ai = np.zeros(self.nnzA, np.int32)
         _lib.check(L.mpcqp_stage_pattern(self._h, self.Pp.ctypes.data, self.Pi.ctypes.data, self.Ap.ctypes.data, self.Ai.ctypes.data))
@@ -154,6 +163,37 @@ class StageEvaluator:
             self.close()
         except Exception:
             pass
+
+    def set_instance_params(self, theta, plant=False):
+        """one parameter row per instance (mpcqp_stage_set_instance_params; models.StageOCP.set_instance_params is its host statement).  theta: a
+        NumPy array or a float64 CUDA tensor [B, param_count] (or [B, 8], used as it is), copied; None returns the set to the shared values.
+        plant=False: the model's set (eval, merit, line_search, the rollout tail of advance); plant=True: the set the plant step of advance uses."""
+        L = _lib.lib()
+        which = PARAMS_PLANT if plant else PARAMS_MODEL
+        if theta is None:
+            _lib.check(L.mpcqp_stage_set_instance_params(self._h, which, 0, None, _lib.MEM_HOST))
+            return
+        try:
+            import torch
+            is_t = isinstance(theta, torch.Tensor)
+        except ImportError:
+            is_t = False
+        if is_t and not theta.is_cuda:
+            theta, is_t = theta.numpy(), False
+        if not is_t:
+            theta = np.asarray(theta, dtype=np.float64)
+        if theta.ndim != 2 or theta.shape[0] < 1 or (theta.shape[1] not in (self.param_count, NPAR) and self.param_count > 0):
+            raise ValueError("theta: expected shape [B, %d], got %s (dimension mismatch)" % (self.param_count, tuple(theta.shape)))
+        B, w = int(theta.shape[0]), int(theta.shape[1])
+        if is_t:
+            if theta.dtype != torch.float64:
+                raise ValueError("theta: expected a float64 tensor")
+            rows = theta.contiguous() if w == NPAR else torch.cat([theta, theta.new_zeros((B, NPAR - w))], dim=1).contiguous()
+            _lib.check(L.mpcqp_stage_set_instance_params(self._h, which, B, rows.data_ptr(), _lib.MEM_DEVICE))
+        else:
+            rows = np.zeros((B, NPAR))
+            rows[:, :min(w, NPAR)] = theta[:, :NPAR]
+            _lib.check(L.mpcqp_stage_set_instance_params(self._h, which, B, rows.ctypes.data, _lib.MEM_HOST))
 
     def alloc(self, batch, device="cuda"):
         """output buffers of one evaluation: dict P, q, A, l, u"""

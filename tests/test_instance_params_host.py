@@ -1,0 +1,181 @@
+"""CPU: per-instance plant parameters -- the C interface's declarations, the NumPy statement (models.StageOCP.set_instance_params), the host build of
+a generated functor with parameters, and the inputs the GPU tests rely on (tests/support/instance_params_cases.py)."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from optimal_control_problem_amd import _lib, codegen, models
+from tests.support import instance_params_cases as ipc
+from tests.support import linesearch_cases as lc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("mpcqp_stage_param_count", "mpcqp_stage_set_instance_params")
+
+
+def _bits(a, b):
+    a = np.ascontiguousarray(a, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def test_header_exports_and_library_agree(built):
+    hdr = open(os.path.join(ROOT, "include", "mpcqp.h")).read()
+    assert re.search(r"int mpcqp_stage_param_count\(const mpcqp_stage \*s\);", hdr)
+    assert re.search(r"int mpcqp_stage_set_instance_params\(mpcqp_stage \*s, int which, int batch, const double \*theta, int mem\);", hdr)
+    for name, value in (("MPCQP_STAGE_NPAR", 8), ("MPCQP_PARAMS_MODEL", 0), ("MPCQP_PARAMS_PLANT", 1)):
+        assert re.search(r"#define %s %d\b" % (name, value), hdr), name
+    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True, check=True).stdout
+    for e in ENTRIES:
+        assert e in _lib.EXPORTS and re.search(r" T %s$" % e, syms, re.M), e
+
+
+def _one_instance_model(kind, row):
+    m = ipc.model(kind)
+    m.theta = np.array(row)
+    return m
+
+
+@pytest.mark.parametrize("kind", ipc.KINDS)
+def test_statement_equals_one_model_per_instance(kind):
+    """rows in force = B one-instance models, bit for bit, in every method that honours them; nothing set = the bits of a model that never had the call"""
+    c = ipc.kernel_case(kind)
+    B = ipc.BATCH
+    ls = ipc.statement(c, "local_system")
+    f, g = ipc.statement(c, "merit")
+    mu0 = np.array([0.0, 50.0, 0.5, 7.0, 0.0, 3.0, 1e4])
+    se = ipc.statement(c, "line_search", mu=mu0.copy())
+    adv = ipc.statement(c, "advance", plant=True, w=c["w"])
+    c["model"].set_instance_params(c["theta"])
+    cons = c["model"].constraints(c["x"])
+    c["model"].set_instance_params()
+    for b in range(B):
+        i = slice(b, b + 1)
+        m = _one_instance_model(kind, c["theta"][b])
+        one = m.local_system(c["p"][i], c["x"][i], c["lbx"][i], c["ubx"][i], c["lbg"][i], c["ubg"][i])
+        for k in ("P", "q", "A", "l", "u"):
+            assert _bits(getattr(ls, k)[i], getattr(one, k)), (kind, b, k)
+        assert _bits(f[i], m.objective(c["p"][i], c["x"][i])) and _bits(g[i], m.violation(c["x"][i], c["lbx"][i], c["ubx"][i])[1])
+        assert _bits(cons[i], m.constraints(c["x"][i]))
+        s1 = m.line_search(c["p"][i], c["x"][i].copy(), c["lbx"][i], c["ubx"][i], c["ls"].q[i], c["dw"][i], c["y"][i], status=c["status"][i], mu=mu0[i].copy())
+        for k in ("x", "alpha", "step_max", "f", "gmax", "phi", "mu"):
+            assert _bits(se[k][i], s1[k]), (kind, b, k)
+        assert np.array_equal(se["accepted"][i], s1["accepted"])
+        a1 = m.advance(c["x"][i], c["lbx"][i], c["ubx"][i], status=c["status"][i], w=c["w"][i], p=c["p"][i], dw=c["dw"][i], y=c["y"][i])
+        mp = _one_instance_model(kind, c["plant"][b])
+        ap = mp.advance(c["x"][i], c["lbx"][i], c["ubx"][i], status=c["status"][i], w=c["w"][i], p=c["p"][i], dw=c["dw"][i], y=c["y"][i])
+        nx = m.nx
+        assert _bits(adv["x"][i, :nx], ap["x"][:, :nx]) and _bits(adv["x"][i, nx:], a1["x"][:, nx:]), (kind, b)      # plant step: plant row; tail: model row
+        assert _bits(adv["lbx"][i, :nx], ap["x"][:, :nx]) and _bits(adv["ubx"][i, :nx], ap["x"][:, :nx])
+        for k in ("applied", "dw", "y", "stage_cost"):
+            assert _bits(adv[k][i], a1[k]), (kind, b, k)
+    # nothing set: today's bits
+    fresh = ipc.model(kind)
+    a = c["model"].local_system(c["p"], c["x"], c["lbx"], c["ubx"], c["lbg"], c["ubg"]); b_ = fresh.local_system(c["p"], c["x"], c["lbx"], c["ubx"], c["lbg"], c["ubg"])
+    assert all(_bits(getattr(a, k), getattr(b_, k)) for k in ("P", "q", "A", "l", "u"))
+    assert _bits(c["model"].advance(c["x"], c["lbx"], c["ubx"])["x"], fresh.advance(c["x"], c["lbx"], c["ubx"])["x"])
+    assert _bits(np.asarray(c["model"].theta, float), np.asarray(fresh.theta, float))
+
+
+def test_statement_refusals():
+    m = models.CartPole(3)
+    with pytest.raises(ValueError):
+        m.set_instance_params(np.ones((2, 5)))                      # four parameters, not five
+    with pytest.raises(ValueError, match="no parameters"):
+        models.DoubleIntegrator(3).set_instance_params(np.ones((2, 1)))
+    m.set_instance_params(np.tile(m.theta, (2, 1)))
+    x = np.zeros((3, m.nvar))
+    with pytest.raises(ValueError, match="larger than the stored"):
+        m.constraints(x)                                            # three instances, two rows
+    assert m.constraints(x[:1]).shape == (1, m.ngd)                 # a smaller batch uses the first rows
+
+    class TooMany(models.StageOCP):
+        nx, nu, ntheta = 1, 1, 9
+    with pytest.raises(ValueError, match="at most 8"):
+        TooMany(3, 0.1, [1.0], [1.0])
+    p = ipc.param_pendulum()
+    with pytest.raises(ValueError, match="at most 8"):
+        codegen.trace(p.F, p.nx, p.nu, ntheta=9, theta0=np.zeros(9))
+
+
+def test_traced_functions_other_than_F_may_not_read_theta():
+    bad = ipc.param_pendulum(cls=ipc.ThetaInPath)
+    with pytest.raises(ValueError, match="hfun reads self.theta"):
+        codegen.trace(bad.F, bad.nx, bad.nu, bad.hfun, 1, bad.h_lo, bad.h_hi, ntheta=2)
+    assert _bits(bad.theta, ipc.ParamPendulum.theta)                # the model's values are back in place after the refused trace
+
+
+def test_generated_functor_with_parameters_matches_numpy():
+    """the host build of the ntheta = 2 functor against the model's own F and dF, at the bar of tests/test_gpu_stage_eval.py, for the defaults and for
+    other parameter vectors; a functor without parameters emits none of it"""
+    m = ipc.param_pendulum()
+    tape = codegen.trace(m.F, m.nx, m.nu, m.hfun, 1, m.h_lo, m.h_hi, kfun=m.kfun, nk=1, k_lo=m.k_lo, k_hi=m.k_hi, ntheta=2)
+    src = codegen.device_source(tape)
+    for name in ("mpcqp_user_ntheta", "mpcqp_user_theta0", "mpcqp_user_eval_pp", "mpcqp_user_merit_pp", "mpcqp_user_advance_pp", "mpcqp_user_linesearch_pp",
+                 "static constexpr int ntheta = 2", "par[0]", "par[1]"):
+        assert name in src, name
+    q = ipc.plain_pendulum()
+    plain = codegen.device_source(codegen.trace(q.F, q.nx, q.nu))
+    assert "ntheta" not in plain and "_pp" not in plain and "StageTheta" not in plain
+    L = C.CDLL(codegen.build_host_library(tape))
+    assert L.user_host_ntheta() == 2
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    rng = np.random.default_rng(3)
+    for th in (m.theta.copy(), np.array([0.4, 0.3]), np.array([1.6, 0.0])):
+        one = ipc.param_pendulum(); one.theta = th
+        for _ in range(4):
+            s = rng.normal(0.0, 0.7, 2); u = rng.normal(0.0, 1.0, 1)
+            out = np.zeros(2); jac = np.zeros(6)
+            L.user_host_eval_theta(vp(th), vp(s), vp(u), vp(out), vp(jac))
+            F = one.F(s, u); J = one.dF(s, u)
+            assert (np.abs(out - F) <= 1e-12 * np.maximum(1.0, np.abs(F))).all()
+            assert (np.abs(jac.reshape(2, 3) - J) <= 1e-12 * np.maximum(1.0, np.abs(J))).all()
+            if th is not None and np.array_equal(th, m.theta):     # the defaults are what the form without the vector uses
+                o2 = np.zeros(2); j2 = np.zeros(6)
+                L.user_host_eval(vp(s), vp(u), vp(o2), vp(j2))
+                assert _bits(o2, out) and _bits(j2, jac)
+
+
+@pytest.mark.parametrize("name", ipc.RECIPES)
+def test_recipes_are_feasible_and_the_parameter_shows(name):
+    """pins the inputs of the GPU loop test: every QP of the two recipes ends solved on the CPU oracle, and s_1 after the loop shows the parameter"""
+    from tests.support.oracle_backend import OracleCuCaQP
+    mdl, th, arg = ipc.recipe(name)
+    B = th.shape[0]
+    for search in (False, True):
+        sol, log = ipc.host_loop(mdl, th, arg, OracleCuCaQP(batch=B, nthreads=4), line_search=search)
+        assert all((it["status"] == 1).all() for it in log), [it["status"] for it in log]
+        if search:
+            assert not any(lc.undecided(it["ls"]).any() for it in log)
+    sol, log = ipc.host_loop(mdl, th, arg, OracleCuCaQP(batch=B, nthreads=4))
+    s1 = log[-1]["x"].reshape(B, mdl.N, mdl.f)[:, 1, :mdl.nx]
+    got = s1[:, 3] if name == "cartpole" else s1[:, 8]              # angular velocity of the pole; vertical velocity
+    want = [0.180, 0.108, 0.072, 0.054] if name == "cartpole" else [0.171, -0.0003, -0.071]
+    print(name, got)
+    assert np.abs(got - want).max() < 2e-3, got
+
+
+@pytest.mark.parametrize("kind", ipc.KINDS)
+def test_the_parameter_matters_in_the_statement(kind):
+    """the two instances of GPU test 2 differ by more than 1e-3 in the dynamics blocks of A and in gmax"""
+    mdl, th, p, x, lbx, ubx, lbg, ubg = ipc.matters_case(kind)
+    mdl.set_instance_params(th)
+    try:
+        ls = mdl.local_system(p, x, lbx, ubx, lbg, ubg)
+        g = mdl.violation(x, lbx, ubx)[1]
+    finally:
+        mdl.set_instance_params()
+    blk = mdl._A_blk.ravel()
+    assert np.abs(ls.A[0, blk] - ls.A[1, blk]).max() > 1e-3 and abs(g[0] - g[1]) > 1e-3
+    rest = np.setdiff1d(np.arange(ls.A.shape[1]), blk)
+    assert _bits(ls.A[0, rest], ls.A[1, rest]) and _bits(ls.P[0], ls.P[1]) and _bits(ls.q[0], ls.q[1])
+
+
+@pytest.mark.parametrize("kind", ipc.KINDS)
+def test_line_search_inputs_have_no_undecided_instance(kind):
+    c = ipc.kernel_case(kind)
+    for K in (1, 4):
+        out = ipc.statement(c, "line_search", candidates=K)
+        assert not lc.undecided(out).any(), (kind, K)
