@@ -652,6 +652,7 @@ def emit_functor(tape, name="SmUser"):
     return src
 
 
+# pf, pfpp: the launchers' PF template argument, written after SmUser or in full; pref: the export mpcqp_user_pref of a tracking library
 _DEVICE_TMPL = '''// generated by optimal_control_problem_amd/codegen.py -- do not edit
 #include "stage_kernels.hpp"
 
@@ -659,7 +660,7 @@ _DEVICE_TMPL = '''// generated by optimal_control_problem_amd/codegen.py -- do n
 extern "C" {
 int mpcqp_user_abi() { return STAGE_ABI_VERSION; }
 void mpcqp_user_dims(int *nx, int *nu) { *nx = SmUser::nx; *nu = SmUser::nu; }
-int mpcqp_user_nh() { return SmUser::nh; }
+%(pref)sint mpcqp_user_nh() { return SmUser::nh; }
 void mpcqp_user_path_bounds(double *lo, double *hi) { for (int i = 0; i < SmUser::nh; i++) { lo[i] = SmUser_h_lo[i]; hi[i] = SmUser_h_hi[i]; } }
 int mpcqp_user_nk() { return SmUser::nk; }
 void mpcqp_user_link_bounds(double *lo, double *hi) { for (int i = 0; i < SmUser::nk; i++) { lo[i] = SmUser_k_lo[i]; hi[i] = SmUser_k_hi[i]; } }
@@ -672,18 +673,18 @@ int mpcqp_user_cost(unsigned char *mask) {
 }
 int mpcqp_user_eval(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                     const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream) {
-  return (int)stage_launch_eval<SmUser>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream);
+  return (int)stage_launch_eval<SmUser%(pf)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream);
 }
 int mpcqp_user_merit(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
-  return (int)stage_launch_merit<SmUser>(*sd, batch, p, x, f, gmax, (hipStream_t)stream);
+  return (int)stage_launch_merit<SmUser%(pf)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream);
 }
 // the hand-over between two MPC ticks (mpcqp_stage_advance)
 int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream) {
-  return (int)stage_launch_advance<SmUser>(*sd, batch, *a, (hipStream_t)stream);
+  return (int)stage_launch_advance<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream);
 }
 // the per-instance merit line search (mpcqp_stage_linesearch)
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
-  return (int)stage_launch_linesearch<SmUser>(*sd, batch, *a, (hipStream_t)stream);
+  return (int)stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream);
 }
 %(params)s}
 '''
@@ -694,16 +695,16 @@ _DEVICE_PARAMS_TMPL = '''int mpcqp_user_ntheta() { return SmUser::ntheta; }
 void mpcqp_user_theta0(double *par) { for (int i = 0; i < SmUser::ntheta; i++) par[i] = SmUser_theta0[i]; }
 int mpcqp_user_eval_pp(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                        const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream, const double *theta) {
-  return (int)stage_launch_eval<SmUser, false>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr});
+  return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr});
 }
 int mpcqp_user_merit_pp(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream, const double *theta) {
-  return (int)stage_launch_merit<SmUser, false>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr});
+  return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr});
 }
 int mpcqp_user_advance_pp(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream, const double *theta, const double *plant) {
-  return (int)stage_launch_advance<SmUser, false>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant});
+  return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant});
 }
 int mpcqp_user_linesearch_pp(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream, const double *theta) {
-  return (int)stage_launch_linesearch<SmUser, false>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr});
+  return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr});
 }
 '''
 
@@ -830,15 +831,10 @@ def _build(src_text, suffix, cmd_prefix):
 def device_source(tape):
     """the translation unit of a stage library.  Traced with per_frame_reference: SmUser::pref, the PF = true kernel instances only, and the
     export mpcqp_user_pref() by which mpcqp_stage_create_tracking / _create_user tell the two kinds apart; else the text it always was"""
-    nth = getattr(tape, "ntheta", 0)
-    src = _DEVICE_TMPL % {"functor": emit_functor(tape), "params": _DEVICE_PARAMS_TMPL if nth else ""}
-    if getattr(tape, "pref", False):
-        src = src.replace("<SmUser, false>", "<SmUser, SmUser::pref>")
-        src = src.replace("stage_launch_eval<SmUser>", "stage_launch_eval<SmUser, SmUser::pref>").replace("stage_launch_merit<SmUser>", "stage_launch_merit<SmUser, SmUser::pref>")
-        src = src.replace("stage_launch_advance<SmUser>", "stage_launch_advance<SmUser, SmUser::pref>")
-        src = src.replace("stage_launch_linesearch<SmUser>", "stage_launch_linesearch<SmUser, SmUser::pref>")
-        src = src.replace("int mpcqp_user_nh() {", "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\nint mpcqp_user_nh() {")
-    return src
+    pf = getattr(tape, "pref", False)
+    sub = {"pf": ", SmUser::pref" if pf else "", "pfpp": "SmUser::pref" if pf else "false",
+           "pref": "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\n" if pf else ""}
+    return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if getattr(tape, "ntheta", 0) else "")
 
 
 def build_device_library(tape):

@@ -18,18 +18,31 @@
 #include "common.hpp"
 #include "stage_kernels.hpp"
 
-typedef int (*user_eval_fn)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *,
-                            const double *, double *, double *, double *, double *, double *, void *);
-typedef int (*user_merit_fn)(const StageDev *, int, const double *, const double *, double *, double *, void *);
-typedef int (*user_advance_fn)(const StageDev *, int, const mpcqp_stage_advance_args *, void *);
-typedef int (*user_linesearch_fn)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *);
-// the per-instance-parameter launchers of a generated library (ntheta > 0): the same arguments, then the device rows ([batch * SM_NPAR]; advance
-// takes the model rows and the plant rows, either may be null = the shared values)
-typedef int (*user_eval_pp_fn)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *,
-                               const double *, double *, double *, double *, double *, double *, void *, const double *);
-typedef int (*user_merit_pp_fn)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *);
-typedef int (*user_advance_pp_fn)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *);
-typedef int (*user_linesearch_pp_fn)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *);
+// The launchers a generated library exports (model == MPCQP_MODEL_USER).  advance and linesearch are optional: a library generated before
+// those entries has none.  The _pp four are the per-instance-parameter launchers of a library with ntheta > 0: the same arguments, then the
+// device rows ([batch * SM_NPAR]; advance takes the model rows and the plant rows, either may be null = the shared values).
+struct StageUserLib {
+  int (*eval)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *, const double *, double *,
+              double *, double *, double *, double *, void *) = nullptr;
+  int (*merit)(const StageDev *, int, const double *, const double *, double *, double *, void *) = nullptr;
+  int (*advance)(const StageDev *, int, const mpcqp_stage_advance_args *, void *) = nullptr;
+  int (*linesearch)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *) = nullptr;
+  int (*eval_pp)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *, const double *, double *,
+                 double *, double *, double *, double *, void *, const double *) = nullptr;
+  int (*merit_pp)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *) = nullptr;
+  int (*advance_pp)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *) = nullptr;
+  int (*linesearch_pp)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *) = nullptr;
+  bool all_pp() const { return eval_pp && merit_pp && advance_pp && linesearch_pp; }
+};
+template <class Fn> static void stage_sym(void *lib, const char *name, Fn *&fn) { fn = (Fn *)dlsym(lib, name); }
+static StageUserLib stage_user_lib(void *lib) {
+  StageUserLib u;
+  stage_sym(lib, "mpcqp_user_eval", u.eval); stage_sym(lib, "mpcqp_user_merit", u.merit);
+  stage_sym(lib, "mpcqp_user_advance", u.advance); stage_sym(lib, "mpcqp_user_linesearch", u.linesearch);
+  stage_sym(lib, "mpcqp_user_eval_pp", u.eval_pp); stage_sym(lib, "mpcqp_user_merit_pp", u.merit_pp);
+  stage_sym(lib, "mpcqp_user_advance_pp", u.advance_pp); stage_sym(lib, "mpcqp_user_linesearch_pp", u.linesearch_pp);
+  return u;
+}
 
 // the zoo's PP instances (quadrotor, cart-pole) live in stage_eval_pp.hip, a translation unit of their own that compiles beside this one
 hipError_t mpcqp_launch_eval_pp(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx, const double *lbg,
@@ -48,19 +61,12 @@ struct mpcqp_stage {
   double *dhlo = nullptr, *dhhi = nullptr;   // per-frame path bounds (mpcqp_stage_set_path_bounds)
   unsigned char *dmask = nullptr;     // Hessian structure of a generated general stage cost
   void *user_lib = nullptr;           // dlopen handle of a generated dynamics library (model == MPCQP_MODEL_USER)
-  user_eval_fn user_eval = nullptr;
-  user_merit_fn user_merit = nullptr;
-  user_advance_fn user_advance = nullptr;   // optional export: libraries generated before mpcqp_stage_advance have none
-  user_linesearch_fn user_linesearch = nullptr;   // optional export, likewise (mpcqp_stage_linesearch)
+  StageUserLib user;
   bool general_cost = false;          // the library carries its own stage cost: Q, R and mpcqp_stage_set_weights do not apply
   // per-instance parameters (mpcqp_stage_set_instance_params): set `which` is in force when th_batch[which] > 0
   int ntheta = 0;                     // entries of a row the model reads: 7 quadrotor, 4 cart-pole, 0 double integrator, mpcqp_user_ntheta of a library
   double *dth[2] = {nullptr, nullptr};
   int th_batch[2] = {0, 0}, th_cap[2] = {0, 0};
-  user_eval_pp_fn user_eval_pp = nullptr;
-  user_merit_pp_fn user_merit_pp = nullptr;
-  user_advance_pp_fn user_advance_pp = nullptr;
-  user_linesearch_pp_fn user_linesearch_pp = nullptr;
   const double *theta(int which) const { return th_batch[which] > 0 ? dth[which] : nullptr; }
 };
 
@@ -94,6 +100,24 @@ hipError_t mpcqp_launch_step(int batch, int nvar, int n, int np, double alpha, c
                              hipStream_t st) {
   stage_step_kernel<<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(batch, nvar, n, np, alpha, dw, x, step_max, status);
   return hipGetLastError();
+}
+
+// The common tail of the four entry points that launch a model's kernel, after their own argument checks: a launch may not be larger than a
+// stored parameter set (plant: advance reads the plant's set too), then one of four launches -- a generated library or the zoo, with the shared
+// parameters or with per-instance rows.  zoo(tag) launches the plain zoo instance of StageTag tag; zoo_pp(th) calls the PP twin in
+// stage_eval_pp.hip; user() and user_pp(th) call the library's exports.
+template <class Zoo, class ZooPP, class User, class UserPP>
+static int stage_launch(mpcqp_stage *s, int batch, bool plant, Zoo zoo, ZooPP zoo_pp, User user, UserPP user_pp) {
+  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
+  if (plant) if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_PLANT, batch)) return rc;
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const StageTheta th{s->theta(MPCQP_PARAMS_MODEL), plant ? s->theta(MPCQP_PARAMS_PLANT) : nullptr};
+  const bool pp = th.model || th.plant;
+  hipError_t e;
+  if (s->sd.model == MPCQP_MODEL_USER) e = (hipError_t)(pp ? user_pp(th) : user());
+  else e = pp ? zoo_pp(th) : stage_visit_zoo(s->sd.model, s->sd.pref != 0, zoo);
+  MPCQP_HIPCHK(e);
+  return MPCQP_OK;
 }
 
 extern "C" {
@@ -188,9 +212,8 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   if (!lib) return mpcqp_set_error(MPCQP_ERR_ARG, std::string("cannot load the dynamics library: ") + dlerror());
   auto abi = (int (*)())dlsym(lib, "mpcqp_user_abi");
   auto dims = (void (*)(int *, int *))dlsym(lib, "mpcqp_user_dims");
-  auto ev = (user_eval_fn)dlsym(lib, "mpcqp_user_eval");
-  auto me = (user_merit_fn)dlsym(lib, "mpcqp_user_merit");
-  if (!abi || !dims || !ev || !me) { dlclose(lib); return mpcqp_set_error(MPCQP_ERR_ARG, "the library does not export mpcqp_user_abi/dims/eval/merit"); }
+  const StageUserLib user = stage_user_lib(lib);
+  if (!abi || !dims || !user.eval || !user.merit) { dlclose(lib); return mpcqp_set_error(MPCQP_ERR_ARG, "the library does not export mpcqp_user_abi/dims/eval/merit"); }
   if (abi() != STAGE_ABI_VERSION) { dlclose(lib); return mpcqp_set_error(MPCQP_ERR_ARG, "the library was generated for another version of the stage kernels; regenerate it"); }
   auto pf = (int (*)())dlsym(lib, "mpcqp_user_pref");
   if ((pf && pf() != 0) != pref) {
@@ -216,21 +239,15 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   double k_lo[SM_MAXNK], k_hi[SM_MAXNK];
   if (nk > 0) kb(k_lo, k_hi);
   mpcqp_stage *s = new mpcqp_stage();
-  s->user_lib = lib; s->user_eval = ev; s->user_merit = me;
-  s->user_advance = (user_advance_fn)dlsym(lib, "mpcqp_user_advance");
-  s->user_linesearch = (user_linesearch_fn)dlsym(lib, "mpcqp_user_linesearch");
+  s->user_lib = lib; s->user = user;
   mpcqp_stage_desc dd = *d; dd.model = MPCQP_MODEL_USER;
   // optional exports of a library generated with parameters: their count, their defaults (which become sd.par: d->par stays ignored for a
-  // generated library) and the four PP launchers.  A library without them -- every one generated before this entry -- has no parameters.
+  // generated library) and the four PP launchers (StageUserLib).  A library without them -- every one generated before this entry -- has no parameters.
   {
     auto ntf = (int (*)())dlsym(lib, "mpcqp_user_ntheta");
     auto t0f = (void (*)(double *))dlsym(lib, "mpcqp_user_theta0");
-    s->user_eval_pp = (user_eval_pp_fn)dlsym(lib, "mpcqp_user_eval_pp");
-    s->user_merit_pp = (user_merit_pp_fn)dlsym(lib, "mpcqp_user_merit_pp");
-    s->user_advance_pp = (user_advance_pp_fn)dlsym(lib, "mpcqp_user_advance_pp");
-    s->user_linesearch_pp = (user_linesearch_pp_fn)dlsym(lib, "mpcqp_user_linesearch_pp");
     const int nt = ntf ? ntf() : 0;
-    if (nt < 0 || nt > SM_NPAR || (nt > 0 && !(t0f && s->user_eval_pp && s->user_merit_pp && s->user_advance_pp && s->user_linesearch_pp))) {
+    if (nt < 0 || nt > SM_NPAR || (nt > 0 && !(t0f && user.all_pp()))) {
       mpcqp_stage_destroy(s);
       return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares parameters but not 0..8 of them, or lacks mpcqp_user_theta0 or a _pp launcher");
     }
@@ -269,20 +286,26 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   delete s;
 }
 
+// two optional per-frame arrays on the device (da, db: the handle's buffers, allocated on first use; sa, sb: StageDev's pointers).  a, b null:
+// back to the shared values, the buffers stay for the next call
+static int stage_upload_pair(mpcqp_stage *s, const double *a, const double *b, size_t bytes_a, size_t bytes_b, double **da, double **db,
+                             const double **sa, const double **sb) {
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  if (!a) { *sa = nullptr; *sb = nullptr; return MPCQP_OK; }
+  if (!*da) MPCQP_HIPCHK(hipMalloc(da, bytes_a));
+  if (!*db) MPCQP_HIPCHK(hipMalloc(db, bytes_b));
+  MPCQP_HIPCHK(hipMemcpy(*da, a, bytes_a, hipMemcpyHostToDevice));
+  MPCQP_HIPCHK(hipMemcpy(*db, b, bytes_b, hipMemcpyHostToDevice));
+  *sa = *da; *sb = *db;
+  return MPCQP_OK;
+}
+
 int mpcqp_stage_set_weights(mpcqp_stage *s, const double *Qk, const double *Rk) {
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if ((Qk == nullptr) != (Rk == nullptr)) return mpcqp_set_error(MPCQP_ERR_ARG, "give both weight arrays or neither");
   if (s->general_cost) return mpcqp_set_error(MPCQP_ERR_ARG, "this evaluator was generated with its own stage cost; diagonal weights do not apply");
-  MPCQP_HIPCHK(hipSetDevice(s->device));
   StageDev &sd = s->sd;
-  if (!Qk) { sd.Qk = nullptr; sd.Rk = nullptr; return MPCQP_OK; }
-  const size_t bq = (size_t)sd.N * sd.nx * sizeof(double), br = (size_t)sd.N * sd.nu * sizeof(double);
-  if (!s->dQk) MPCQP_HIPCHK(hipMalloc(&s->dQk, bq));
-  if (!s->dRk) MPCQP_HIPCHK(hipMalloc(&s->dRk, br));
-  MPCQP_HIPCHK(hipMemcpy(s->dQk, Qk, bq, hipMemcpyHostToDevice));
-  MPCQP_HIPCHK(hipMemcpy(s->dRk, Rk, br, hipMemcpyHostToDevice));
-  sd.Qk = s->dQk; sd.Rk = s->dRk;
-  return MPCQP_OK;
+  return stage_upload_pair(s, Qk, Rk, (size_t)sd.N * sd.nx * sizeof(double), (size_t)sd.N * sd.nu * sizeof(double), &s->dQk, &s->dRk, &sd.Qk, &sd.Rk);
 }
 
 int mpcqp_stage_set_path_bounds(mpcqp_stage *s, const double *lo, const double *hi) {
@@ -290,15 +313,8 @@ int mpcqp_stage_set_path_bounds(mpcqp_stage *s, const double *lo, const double *
   if ((lo == nullptr) != (hi == nullptr)) return mpcqp_set_error(MPCQP_ERR_ARG, "give both bound arrays or neither");
   StageDev &sd = s->sd;
   if (sd.nh == 0) return mpcqp_set_error(MPCQP_ERR_ARG, "this evaluator has no path constraint");
-  MPCQP_HIPCHK(hipSetDevice(s->device));
-  if (!lo) { sd.h_lok = nullptr; sd.h_hik = nullptr; return MPCQP_OK; }
   const size_t bytes = (size_t)sd.N * sd.nh * sizeof(double);
-  if (!s->dhlo) MPCQP_HIPCHK(hipMalloc(&s->dhlo, bytes));
-  if (!s->dhhi) MPCQP_HIPCHK(hipMalloc(&s->dhhi, bytes));
-  MPCQP_HIPCHK(hipMemcpy(s->dhlo, lo, bytes, hipMemcpyHostToDevice));
-  MPCQP_HIPCHK(hipMemcpy(s->dhhi, hi, bytes, hipMemcpyHostToDevice));
-  sd.h_lok = s->dhlo; sd.h_hik = s->dhhi;
-  return MPCQP_OK;
+  return stage_upload_pair(s, lo, hi, bytes, bytes, &s->dhlo, &s->dhhi, &sd.h_lok, &sd.h_hik);
 }
 
 int mpcqp_stage_param_count(const mpcqp_stage *s) { return s ? s->ntheta : 0; }
@@ -348,50 +364,25 @@ int mpcqp_stage_eval(mpcqp_stage *s, int batch, const double *p, const double *x
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
   if (!p || !x || !lbx || !ubx || !lbg || !ubg || !P || !q || !A || !l || !u) return mpcqp_set_error(MPCQP_ERR_ARG, "null data pointer");
-  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
-  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const StageDev &sd = s->sd;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  if (const double *th = s->theta(MPCQP_PARAMS_MODEL)) {
-    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_eval_pp(&s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th)
-                                        : mpcqp_launch_eval_pp(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st, StageTheta{th, nullptr});
-    MPCQP_HIPCHK(e);
-    return MPCQP_OK;
-  }
-  switch (s->sd.model) {
-    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_eval<SmDoubleIntegrator, true>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st)
-                                            : stage_launch_eval<SmDoubleIntegrator>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
-    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_eval<SmQuadrotor, true>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st)
-                                            : stage_launch_eval<SmQuadrotor>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
-    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_eval<SmCartPole, true>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st)
-                                            : stage_launch_eval<SmCartPole>(s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); break;
-    case MPCQP_MODEL_USER: e = (hipError_t)s->user_eval(&s->sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream); break;
-  }
-  MPCQP_HIPCHK(e);
-  return MPCQP_OK;
+  return stage_launch(s, batch, false,
+      [&](auto t) { using T = decltype(t); return stage_launch_eval<typename T::M, T::PF>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); },
+      [&](StageTheta th) { return mpcqp_launch_eval_pp(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st, th); },
+      [&] { return s->user.eval(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream); },
+      [&](StageTheta th) { return s->user.eval_pp(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th.model); });
 }
 
 int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if (batch <= 0 || !p || !x) return mpcqp_set_error(MPCQP_ERR_ARG, "bad batch or null data pointer");
-  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
-  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const StageDev &sd = s->sd;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  if (const double *th = s->theta(MPCQP_PARAMS_MODEL)) {
-    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_merit_pp(&s->sd, batch, p, x, f, gmax, stream, th)
-                                        : mpcqp_launch_merit_pp(s->sd, batch, p, x, f, gmax, st, StageTheta{th, nullptr});
-    MPCQP_HIPCHK(e);
-    return MPCQP_OK;
-  }
-  switch (s->sd.model) {
-    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_merit<SmDoubleIntegrator, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmDoubleIntegrator>(s->sd, batch, p, x, f, gmax, st); break;
-    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_merit<SmQuadrotor, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmQuadrotor>(s->sd, batch, p, x, f, gmax, st); break;
-    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_merit<SmCartPole, true>(s->sd, batch, p, x, f, gmax, st) : stage_launch_merit<SmCartPole>(s->sd, batch, p, x, f, gmax, st); break;
-    case MPCQP_MODEL_USER: e = (hipError_t)s->user_merit(&s->sd, batch, p, x, f, gmax, stream); break;
-  }
-  MPCQP_HIPCHK(e);
-  return MPCQP_OK;
+  return stage_launch(s, batch, false,
+      [&](auto t) { using T = decltype(t); return stage_launch_merit<typename T::M, T::PF>(sd, batch, p, x, f, gmax, st); },
+      [&](StageTheta th) { return mpcqp_launch_merit_pp(sd, batch, p, x, f, gmax, st, th); },
+      [&] { return s->user.merit(&sd, batch, p, x, f, gmax, stream); },
+      [&](StageTheta th) { return s->user.merit_pp(&sd, batch, p, x, f, gmax, stream, th.model); });
 }
 
 int mpcqp_stage_step(mpcqp_stage *s, int batch, double alpha, const double *dw, double *x, double *step_max, const int *status, void *stream) {
@@ -422,27 +413,15 @@ int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_arg
   }
   if (a->w && a->s_meas) return mpcqp_set_error(MPCQP_ERR_ARG, "a disturbance applies to the simulated plant only: give w or s_meas, not both");
   if (a->tail != MPCQP_TAIL_REPEAT && a->tail != MPCQP_TAIL_ROLLOUT) return mpcqp_set_error(MPCQP_ERR_ARG, "unknown tail");
-  if (s->sd.model == MPCQP_MODEL_USER && !s->user_advance)
+  if (s->sd.model == MPCQP_MODEL_USER && !s->user.advance)
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_advance (generated before this entry); regenerate it");
-  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
-  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_PLANT, batch)) return rc;
-  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const StageDev &sd = s->sd;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  if (s->theta(MPCQP_PARAMS_MODEL) || s->theta(MPCQP_PARAMS_PLANT)) {
-    const StageTheta th{s->theta(MPCQP_PARAMS_MODEL), s->theta(MPCQP_PARAMS_PLANT)};
-    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_advance_pp(&s->sd, batch, a, stream, th.model, th.plant) : mpcqp_launch_advance_pp(s->sd, batch, *a, st, th);
-    MPCQP_HIPCHK(e);
-    return MPCQP_OK;
-  }
-  switch (s->sd.model) {
-    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_advance<SmDoubleIntegrator, true>(s->sd, batch, *a, st) : stage_launch_advance<SmDoubleIntegrator>(s->sd, batch, *a, st); break;
-    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_advance<SmQuadrotor, true>(s->sd, batch, *a, st) : stage_launch_advance<SmQuadrotor>(s->sd, batch, *a, st); break;
-    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_advance<SmCartPole, true>(s->sd, batch, *a, st) : stage_launch_advance<SmCartPole>(s->sd, batch, *a, st); break;
-    case MPCQP_MODEL_USER: e = (hipError_t)s->user_advance(&s->sd, batch, a, stream); break;
-  }
-  MPCQP_HIPCHK(e);
-  return MPCQP_OK;
+  return stage_launch(s, batch, true,
+      [&](auto t) { using T = decltype(t); return stage_launch_advance<typename T::M, T::PF>(sd, batch, *a, st); },
+      [&](StageTheta th) { return mpcqp_launch_advance_pp(sd, batch, *a, st, th); },
+      [&] { return s->user.advance(&sd, batch, a, stream); },
+      [&](StageTheta th) { return s->user.advance_pp(&sd, batch, a, stream, th.model, th.plant); });
 }
 
 int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
@@ -456,26 +435,15 @@ int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesear
   if (!(a->c1 >= 0.0 && a->c1 < 1.0)) return mpcqp_set_error(MPCQP_ERR_ARG, "c1 must lie in [0, 1)");
   if (!(a->mu_min >= 0.0) || !(a->mu_factor >= 0.0) || !std::isfinite(a->mu_min) || !std::isfinite(a->mu_factor))
     return mpcqp_set_error(MPCQP_ERR_ARG, "mu_min and mu_factor must be finite and not negative");
-  if (s->sd.model == MPCQP_MODEL_USER && !s->user_linesearch)
+  if (s->sd.model == MPCQP_MODEL_USER && !s->user.linesearch)
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_linesearch (generated before this entry); regenerate it");
-  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
-  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const StageDev &sd = s->sd;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  if (const double *th = s->theta(MPCQP_PARAMS_MODEL)) {
-    e = s->sd.model == MPCQP_MODEL_USER ? (hipError_t)s->user_linesearch_pp(&s->sd, batch, a, stream, th)
-                                        : mpcqp_launch_linesearch_pp(s->sd, batch, *a, st, StageTheta{th, nullptr});
-    MPCQP_HIPCHK(e);
-    return MPCQP_OK;
-  }
-  switch (s->sd.model) {
-    case SM_DOUBLE_INTEGRATOR: e = s->sd.pref ? stage_launch_linesearch<SmDoubleIntegrator, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmDoubleIntegrator>(s->sd, batch, *a, st); break;
-    case SM_QUADROTOR: e = s->sd.pref ? stage_launch_linesearch<SmQuadrotor, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmQuadrotor>(s->sd, batch, *a, st); break;
-    case SM_CARTPOLE: e = s->sd.pref ? stage_launch_linesearch<SmCartPole, true>(s->sd, batch, *a, st) : stage_launch_linesearch<SmCartPole>(s->sd, batch, *a, st); break;
-    case MPCQP_MODEL_USER: e = (hipError_t)s->user_linesearch(&s->sd, batch, a, stream); break;
-  }
-  MPCQP_HIPCHK(e);
-  return MPCQP_OK;
+  return stage_launch(s, batch, false,
+      [&](auto t) { using T = decltype(t); return stage_launch_linesearch<typename T::M, T::PF>(sd, batch, *a, st); },
+      [&](StageTheta th) { return mpcqp_launch_linesearch_pp(sd, batch, *a, st, th); },
+      [&] { return s->user.linesearch(&sd, batch, a, stream); },
+      [&](StageTheta th) { return s->user.linesearch_pp(&sd, batch, a, stream, th.model); });
 }
 
 }  // extern "C"

@@ -35,6 +35,13 @@ __device__ __forceinline__ StageTheta stage_theta(StageTheta t) { return t; }
 template <class M, class = void> struct sm_ntheta : std::integral_constant<int, 0> {};
 template <class M> struct sm_ntheta<M, std::void_t<decltype(M::ntheta)>> : std::integral_constant<int, M::ntheta> {};
 
+// the QP returned a point (solved, solved inaccurately, or stopped at the iteration limit): its dw, y may be used
+__device__ __forceinline__ bool stage_status_ok(int s) { return s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
+// the generated stage cost (M::has_cost); the last frame takes the terminal one where the model has it
+template <class M, class T> __device__ __forceinline__ void stage_cost_value(bool last, const T *s, const T *u, const T *r, T *out) {
+  if (M::has_term && last) M::template LT<T>(s, u, r, out); else M::template L<T>(s, u, r, out);
+}
+
 // PF (per-frame references, StageDev::pref): the parameter block holds one reference state per frame.  Parameter column j = k nx + i is thread j of
 // its instance, as before; the cooperative mapping pads the N nx parameter slots up to a multiple of f, so that every frame's f lanes still start
 // at a multiple of f (threads per instance ceil(N nx / f) f + N f).  Adjacent lanes still own adjacent columns: the store streams stay contiguous.
@@ -284,7 +291,7 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
       double rr[nx], lv[1];
 #pragma unroll
       for (int i = 0; i < nx; i++) rr[i] = pb[i];
-      if (M::has_term && k == sd.N - 1) M::template LT<double>(s, uu, rr, lv); else M::template L<double>(s, uu, rr, lv);
+      stage_cost_value<M, double>(k == sd.N - 1, s, uu, rr, lv);
       cost += lv[0];
     } else {
 #pragma unroll
@@ -348,7 +355,7 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
   const double *xi = a.x_in + (long)b * nvar;
   double *xo = a.x_out + (long)b * nvar;
   bool ok = true;
-  if (a.status) { const int s = a.status[b]; ok = s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
+  if (a.status) ok = stage_status_ok(a.status[b]);
   const bool rollout = a.tail == MPCQP_TAIL_ROLLOUT;
   double Fo[nx];
 #pragma unroll
@@ -467,7 +474,7 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
   if constexpr (sizeof...(PP) > 0) par = stage_theta(pp...).model + (long)__builtin_amdgcn_readfirstlane(b) * SM_NPAR;
   const int N = sd.N, nvar = sd.nvar, np = sd.np;
   bool ok = true;
-  if (a.status) { const int s = a.status[b]; ok = s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
+  if (a.status) ok = stage_status_ok(a.status[b]);
   const int K = ok ? a.candidates : 0;          // an instance whose QP returned no point evaluates the base point only: its dw, y are not read
   double *xb = a.x + (long)b * nvar;
   const double *pb0 = a.p + (long)b * np, *dxb = a.dw + (long)b * sd.n + np;
@@ -493,7 +500,7 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
       double rr[nx], lval[1];
 #pragma unroll
       for (int i = 0; i < nx; i++) rr[i] = pb[i];
-      if (M::has_term && k == N - 1) M::template LT<double>(s, uu, rr, lval); else M::template L<double>(s, uu, rr, lval);
+      stage_cost_value<M, double>(k == N - 1, s, uu, rr, lval);
       lc += lval[0];
     } else {
 #pragma unroll
@@ -629,4 +636,20 @@ template <class M, bool PF = false, class... PP>
 inline hipError_t stage_launch_linesearch(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st, PP... pp) {
   stage_linesearch_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a, pp...);
   return hipGetLastError();
+}
+
+// The model zoo, listed once: fn(StageTag<M, PF>{}) for the functor of `model` and the kind of reference.  A new zoo functor is one more case
+// here.  PARAMS: only the functors that read parameters (the PP instances exist for those alone); any other model is an invalid value.
+template <class M_, bool PF_> struct StageTag { using M = M_; static constexpr bool PF = PF_; };
+template <class M, bool PARAMS, class Fn> inline hipError_t stage_visit_model(bool pref, Fn &fn) {
+  if constexpr (PARAMS && sm_ntheta<M>::value == 0) return hipErrorInvalidValue;
+  else return pref ? fn(StageTag<M, true>{}) : fn(StageTag<M, false>{});
+}
+template <bool PARAMS = false, class Fn> inline hipError_t stage_visit_zoo(int model, bool pref, Fn fn) {
+  switch (model) {
+    case SM_DOUBLE_INTEGRATOR: return stage_visit_model<SmDoubleIntegrator, PARAMS>(pref, fn);
+    case SM_QUADROTOR: return stage_visit_model<SmQuadrotor, PARAMS>(pref, fn);
+    case SM_CARTPOLE: return stage_visit_model<SmCartPole, PARAMS>(pref, fn);
+  }
+  return hipErrorInvalidValue;
 }

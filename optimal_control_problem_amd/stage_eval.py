@@ -80,6 +80,13 @@ def _check(t, shape, name):
     return t.data_ptr()
 
 
+def _check_int32(t, B, name):
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B,)):
+        raise ValueError("%s: expected a contiguous int32 CUDA tensor of shape (%d,)" % (name, B))
+    return t.data_ptr()
+
+
 class StageEvaluator:
     def __init__(self, model=None, name=None, horizon=None, device=-1, codegen=None):
         """model: a models.StageOCP instance (its N, dt, Q, R are used), or name + horizon for the library's defaults
@@ -235,7 +242,6 @@ class StageEvaluator:
         """the hand-over between two MPC ticks in one kernel (mpcqp_stage_advance; models.StageOCP.advance is its host statement): the plant
         step, the trajectory shifted by one frame into x_out, the first frame pinned in lbx / ubx (in place), and optionally the shifted
         references, QP start and duals and the logs.  Arrays are contiguous float64 CUDA tensors (status int32); out of place throughout."""
-        import torch
         B = x_in.shape[0]
         f = self.nx + self.nu
         a = AdvanceArgs()
@@ -251,9 +257,7 @@ class StageEvaluator:
         if stage_cost is not None:
             a.stage_cost = _check(stage_cost, (B,), "stage_cost")
         if status is not None:
-            if not (isinstance(status, torch.Tensor) and status.is_cuda and status.dtype == torch.int32 and status.is_contiguous() and tuple(status.shape) == (B,)):
-                raise ValueError("status: expected a contiguous int32 CUDA tensor of shape (%d,)" % B)
-            a.status = status.data_ptr()
+            a.status = _check_int32(status, B, "status")
         _lib.check(_lib.lib().mpcqp_stage_advance(self._h, B, C.byref(a), stream))
 
     def line_search(self, p, x, lbx, ubx, q, dw, y, status=None, mu=None, alpha0=1.0, candidates=4, beta=0.5, c1=1e-4, mu_min=1.0, mu_factor=1.1,
@@ -275,9 +279,7 @@ class StageEvaluator:
             setattr(a, name, _check(out[key], (B,), key))
         for name, t in (("status", status), ("accepted", out["accepted"])):
             if t is not None:
-                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B,)):
-                    raise ValueError("%s: expected a contiguous int32 CUDA tensor of shape (%d,)" % (name, B))
-                setattr(a, name, t.data_ptr())
+                setattr(a, name, _check_int32(t, B, name))
         if mu is not None:
             a.mu = _check(mu, (B,), "mu")
         if phi is not None:
