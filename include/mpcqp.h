@@ -349,6 +349,14 @@ int mpcqp_stage_set_instance_params(mpcqp_stage *s, int which, int batch, const 
 int mpcqp_stage_dims(const mpcqp_stage *s, int *dims8);
 /* 1 when the evaluator was generated with its own stage cost (mpcqp_stage_create_user above), 0 for diagonal tracking weights */
 int mpcqp_stage_has_cost(const mpcqp_stage *s);
+/* 1 when the library was generated with a link cost llink(s_k, u_k, s_{k+1}, u_{k+1}), summed over the stages k = 0 .. horizon-2 on top of the
+ * frame cost (diagonal weights or a generated stage cost): a move penalty (u_{k+1} - u_k)' S (u_{k+1} - u_k), a slew penalty on a state.  In the
+ * reference any SX over two frames is a cost term (addScalarCost, src/OptimalControlProblem.cpp:491-497); here the library exports
+ * mpcqp_user_link_cost, the structure of the term's Hessian over [s; u; s_next; u_next], and P couples frame k to frame k + 1 in exactly that
+ * structure (both triangles; mpcqp_stage_pattern and nnz(P) of mpcqp_stage_dims report it) with the exact Hessian of the objective.  The term
+ * takes no reference and no parameters; mpcqp_stage_merit and _linesearch include it, the stage_cost log of mpcqp_stage_advance (the k = 0 frame
+ * term) does not.  0 for the zoo models and for a library without the export (every one generated before this entry). */
+int mpcqp_stage_has_link_cost(const mpcqp_stage *s);
 /* CSC sparsity of P (n x n, both triangles, as CasADi hands it to CuCaQP) and A = [I; dg/dw] (m x n): the arrays
  * mpcqp_create takes.  Pp, Ap: n + 1 entries; Pi: nnz(P); Ai: nnz(A).  Host pointers. */
 int mpcqp_stage_pattern(const mpcqp_stage *s, int *Pp, int *Pi, int *Ap, int *Ai);

@@ -388,7 +388,7 @@ class _ThetaGuard:
         self._what = what
 
     def _refuse(self, *a, **k):
-        raise ValueError("%s reads self.theta: model parameters are supported in F / cdyn only (not in hfun, kfun, lcost, lterm)" % self._what)
+        raise ValueError("%s reads self.theta: model parameters are supported in F / cdyn only (not in hfun, kfun, lcost, lterm, llink)" % self._what)
 
     __getitem__ = __iter__ = __len__ = __array__ = __add__ = __radd__ = __mul__ = __rmul__ = __sub__ = __rsub__ = __truediv__ = __rtruediv__ = __neg__ = _refuse
 
@@ -466,8 +466,28 @@ def _trace_link(kfun, nx, nu, nk):
     return tape
 
 
+def trace_link_cost(llink, nx, nu):
+    """link cost llink(s, u, s_next, u_next) -> scalar on tracers; returns (value tape, gradient tape) over the inputs [s; u; s_next; u_next]"""
+    tape = Tape(2 * (nx + nu))
+    mk = lambda a, b: TV(tape, [TS(tape, i) for i in range(a, b)])
+    f = nx + nu
+    out = llink(mk(0, nx), mk(nx, f), mk(f, f + nx), mk(f + nx, 2 * f))
+    if isinstance(out, TV) and len(out) == 1:
+        out = out.items[0]
+    if isinstance(out, (int, float, np.integer, np.floating)):
+        out = TS._lift(tape, out)
+    if not isinstance(out, TS):
+        raise ValueError("the link cost must return one scalar")
+    tape.outputs = [out.idx]
+    tape.nx, tape.nu = nx, nu
+    tape.in_names = [("s", nx), ("u", nu), ("sn", nx), ("un", nu)]
+    g = gradient_tape(tape)
+    g.in_names = tape.in_names
+    return tape, g
+
+
 def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False,
-          ntheta=0, theta0=None, model=None):
+          ntheta=0, theta0=None, model=None, llink=None):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
@@ -478,7 +498,10 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     ntheta = k (<= 8), theta0 = the k default values: the model (`model`, or the object F is bound to) reads its plant parameters as
     self.theta[i] inside F / cdyn; while F is traced, self.theta holds k extra tape inputs, emitted as par[i] -- data of the functor, not constants
     of its code, so that mpcqp_stage_set_instance_params can give every instance its own.  Any other traced function that touches self.theta
-    raises a ValueError."""
+    raises a ValueError.
+    llink(s, u, s_next, u_next) -> scalar: a link cost, summed over the stages k = 0 .. N-2 on top of the frame cost (a move penalty
+    (u_{k+1} - u_k)' S (u_{k+1} - u_k) and the like).  It takes no reference and no theta.  tape.link_cost holds its value tape, its gradient
+    tape and the exact structure of its Hessian over [s; u; s_next; u_next] (no diagonal is forced into it)."""
     ntheta = int(ntheta)
     if ntheta > NTHETA_MAX:
         raise ValueError("at most %d model parameters are supported (ntheta = %d)" % (NTHETA_MAX, ntheta))
@@ -524,6 +547,11 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
         tape.cost = dict(L=L, G=G, LT=LT, GT=GT, mask=mask)
     elif lterm is not None:
         raise ValueError("a terminal cost needs a stage cost")
+    tape.link_cost = None
+    if llink is not None:
+        with _bound_theta(guarded, _ThetaGuard("llink")):
+            LK, LKG = trace_link_cost(llink, nx, nu)
+        tape.link_cost = dict(L=LK, G=LKG, mask=hessian_mask(LKG))
     return tape
 
 
@@ -638,6 +666,14 @@ def emit_functor(tape, name="SmUser"):
             src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *r, T *out) {\n%s\n  }\n" % (fn, _emit_body(tp))
     if getattr(tape, "pref", False):
         src += "  static constexpr bool pref = true;\n"
+    link_cost = getattr(tape, "link_cost", None)
+    if link_cost:
+        # LK: out[0] = llink(s, u, sn, un); LKG: out[2 f] = its gradient over [s; u; sn; un]; lmask: the structure of its Hessian, row-major (2 f)^2
+        src += "  static constexpr int has_link_cost = 1;\n"
+        for fn, tp in (("LK", link_cost["L"]), ("LKG", link_cost["G"])):
+            src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *sn, const T *un, T *out) {\n%s\n  }\n" % (fn, _emit_body(tp))
+        lm = link_cost["mask"]
+        src += "  static constexpr unsigned char lmask[%d] = {%s};\n" % (lm.size, ", ".join(str(int(v)) for v in lm.ravel()))
     src += "};\n"
     lo = ", ".join(_blit(v) for v in tape.h_lo) if nh else "0.0"
     hi = ", ".join(_blit(v) for v in tape.h_hi) if nh else "0.0"
@@ -686,7 +722,16 @@ int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
   return (int)stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream);
 }
-%(params)s}
+%(params)s%(link_cost)s}
+'''
+
+# a model with a link cost (llink) only: 1 and the structure of its Hessian over [s; u; s_next; u_next] (row-major (2 f)^2 bytes).  A library
+# without the export -- every one generated before this entry -- has no link cost
+_DEVICE_LINK_COST_TMPL = '''int mpcqp_user_link_cost(unsigned char *mask) {
+  constexpr int n2 = 2 * (SmUser::nx + SmUser::nu);
+  for (int i = 0; i < n2 * n2; i++) mask[i] = SmUser::lmask[i];
+  return 1;
+}
 '''
 
 # a model with parameters (ntheta > 0) only: their count, their defaults (they become sd.par of the handle) and the per-instance-parameter
@@ -770,7 +815,7 @@ void user_host_link(const double *s, const double *u, const double *sn, const do
     }
   }
 }
-int user_host_has_cost() { return SmUser::has_cost; }
+%(link_cost)sint user_host_has_cost() { return SmUser::has_cost; }
 void user_host_cost(const double *s, const double *u, const double *r, int term, double *val, double *grad, double *hess) {
   host_cost<SmUser>(s, u, r, term, val, grad, hess);
 }
@@ -785,6 +830,21 @@ void user_host_path(const double *s, const double *u, double *out, double *jac) 
     for (int r = 0; r < nh; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
   }
 }
+}
+'''
+
+
+# val [1], grad [2 f], hess [(2 f)^2] row-major over [s; u; s_next; u_next]: the gradient on duals, one direction per pass (what a device thread does)
+_HOST_LINK_COST_TMPL = '''void user_host_link_cost(const double *s, const double *u, const double *sn, const double *un, double *val, double *grad, double *hess) {
+  constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu;
+  SmUser::LK<double>(s, u, sn, un, val);
+  for (int c = 0; c < 2 * f; c++) {
+    Dual sd[nx], ud[nu], snd[nx], und[nu], gd[2 * f];
+    for (int i = 0; i < nx; i++) { sd[i] = {s[i], i == c ? 1.0 : 0.0}; snd[i] = {sn[i], f + i == c ? 1.0 : 0.0}; }
+    for (int i = 0; i < nu; i++) { ud[i] = {u[i], nx + i == c ? 1.0 : 0.0}; und[i] = {un[i], f + nx + i == c ? 1.0 : 0.0}; }
+    SmUser::LKG<Dual>(sd, ud, snd, und, gd);
+    for (int i = 0; i < 2 * f; i++) { hess[i * 2 * f + c] = gd[i].d; grad[i] = gd[i].v; }
+  }
 }
 '''
 
@@ -834,7 +894,8 @@ def device_source(tape):
     pf = getattr(tape, "pref", False)
     sub = {"pf": ", SmUser::pref" if pf else "", "pfpp": "SmUser::pref" if pf else "false",
            "pref": "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\n" if pf else ""}
-    return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if getattr(tape, "ntheta", 0) else "")
+    return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if getattr(tape, "ntheta", 0) else "",
+                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "")
 
 
 def build_device_library(tape):
@@ -845,7 +906,8 @@ def build_device_library(tape):
 
 def build_host_library(tape):
     nth = getattr(tape, "ntheta", 0)
-    return _build(_HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr"}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
+    return _build(_HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr",
+                                "link_cost": _HOST_LINK_COST_TMPL if getattr(tape, "link_cost", None) else ""}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
 
 
 # ------------------------------------------------------------------------------------------------- general (non-stage) NLPs

@@ -63,6 +63,7 @@ struct mpcqp_stage {
   void *user_lib = nullptr;           // dlopen handle of a generated dynamics library (model == MPCQP_MODEL_USER)
   StageUserLib user;
   bool general_cost = false;          // the library carries its own stage cost: Q, R and mpcqp_stage_set_weights do not apply
+  bool link_cost = false;             // the library carries a link cost between consecutive frames (mpcqp_user_link_cost): P couples frame k to k + 1
   // per-instance parameters (mpcqp_stage_set_instance_params): set `which` is in force when th_batch[which] > 0
   int ntheta = 0;                     // entries of a row the model reads: 7 quadrotor, 4 cart-pole, 0 double integrator, mpcqp_user_ntheta of a library
   double *dth[2] = {nullptr, nullptr};
@@ -154,7 +155,7 @@ int mpcqp_stage_default(int model, int horizon, mpcqp_stage_desc *d) {
 
 static int stage_create_common(const mpcqp_stage_desc *d, int nx, int nu, int nh, const double *h_lo, const double *h_hi, mpcqp_stage *s,
                                const unsigned char *cost_mask = nullptr, int nk = 0, const double *k_lo = nullptr, const double *k_hi = nullptr,
-                               bool pref = false) {
+                               bool pref = false, const unsigned char *link_mask = nullptr) {
   int dev = 0;
   if (int rc = mpcqp_pick_device(d->device, &dev)) return rc;
   s->desc = *d; s->device = dev;
@@ -167,8 +168,8 @@ static int stage_create_common(const mpcqp_stage_desc *d, int nx, int nu, int nh
   for (int i = 0; i < SM_MAXNX; i++) sd.Q[i] = d->Q[i];
   for (int i = 0; i < SM_MAXNU; i++) sd.R[i] = d->R[i];
   for (int i = 0; i < SM_NPAR; i++) sd.par[i] = d->par[i];
-  sm_build_pattern(sd.nx, sd.nu, sd.N, sd.nh, sd.nk, s->Pp, s->Pi, s->Ap, s->Ai, pref);
-  if (cost_mask) sm_build_cost_pattern(sd.nx, sd.nu, sd.N, cost_mask, s->Pp, s->Pi, pref);
+  sm_build_pattern(sd.nx, sd.nu, sd.N, sd.nh, sd.nk, s->Pp, s->Pi, s->Ap, s->Ai, pref, link_mask);
+  if (cost_mask) sm_build_cost_pattern(sd.nx, sd.nu, sd.N, cost_mask, s->Pp, s->Pi, pref, link_mask);
   sd.nnzP = (int)s->Pi.size(); sd.nnzA = (int)s->Ai.size();
   if (hipSetDevice(dev) != hipSuccess) return mpcqp_set_error(MPCQP_ERR_HIP, "hipSetDevice failed");
   const size_t bytes = (size_t)(sd.n + 1) * sizeof(int);
@@ -258,7 +259,13 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   std::vector<unsigned char> mask((size_t)(2 * nx + nu) * (2 * nx + nu));
   auto cf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_cost");
   s->general_cost = cf && cf(mask.data());
-  if (int rc = stage_create_common(&dd, nx, nu, nh, h_lo, h_hi, s, s->general_cost ? mask.data() : nullptr, nk, k_lo, k_hi, pref)) { mpcqp_stage_destroy(s); return rc; }
+  // optional export of a library generated with a link cost (llink): the structure of its Hessian over [s; u; s_next; u_next], which joins the
+  // pattern of P; the kernels of that library carry the same table.  A library without it -- every one generated before this entry -- has none.
+  std::vector<unsigned char> lmask((size_t)4 * (nx + nu) * (nx + nu));
+  auto lf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_link_cost");
+  s->link_cost = lf && lf(lmask.data());
+  if (int rc = stage_create_common(&dd, nx, nu, nh, h_lo, h_hi, s, s->general_cost ? mask.data() : nullptr, nk, k_lo, k_hi, pref,
+                                   s->link_cost ? lmask.data() : nullptr)) { mpcqp_stage_destroy(s); return rc; }
   *out = s;
   return MPCQP_OK;
 }
@@ -351,6 +358,8 @@ int mpcqp_stage_dims(const mpcqp_stage *s, int *o) {
 }
 
 int mpcqp_stage_has_cost(const mpcqp_stage *s) { return s && s->general_cost ? 1 : 0; }
+
+int mpcqp_stage_has_link_cost(const mpcqp_stage *s) { return s && s->link_cost ? 1 : 0; }
 
 int mpcqp_stage_pattern(const mpcqp_stage *s, int *Pp, int *Pi, int *Ap, int *Ai) {
   if (!s || !Pp || !Pi || !Ap || !Ai) return mpcqp_set_error(MPCQP_ERR_ARG, "null argument");

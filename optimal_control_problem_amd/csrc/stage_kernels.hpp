@@ -171,7 +171,90 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
   for (int i = 0; i < nx; i++) s[i] = {fr[i], i == c ? 1.0 : 0.0};
 #pragma unroll
   for (int i = 0; i < nu; i++) uu[i] = {fr[nx + i], nx + i == c ? 1.0 : 0.0};
-  if constexpr (M::has_cost) {
+  if constexpr (sm_has_link_cost<M>::value) {
+    // Link cost sum_{k<N-1} llink(frame_k, frame_{k+1}) (generated functors: LK, LKG, lmask).  Column frame_k[c] takes part in pair k-1 as the second
+    // frame and in pair k as the first: up to two more passes of the generated gradient LKG on dual numbers, the seed on this column.  Rows in
+    // the pattern's order (sm_frame_column_rows): the p rows, then frame k-1's rows M^{k-1}[r][f + c], then frame k's -- the frame term first, then
+    // M^{k-1}[f + r][f + c], then M^k[r][c], a fixed order -- then frame k+1's rows M^k[f + r][c].  One writer per entry, as everywhere here.
+    constexpr int f2 = 2 * f;
+    const bool first = k >= 1, second = k < N - 1;      // this column is the second frame of a pair / the first frame of one
+    // the rows of this column as bit sets (sm_link_bits: four loads), empty where the pair does not exist
+    const unsigned bprev = first ? sm_link_bits<M>::tab.prev[c] : 0u, bown1 = first ? sm_link_bits<M>::tab.own1[c] : 0u;
+    const unsigned bown0 = second ? sm_link_bits<M>::tab.own0[c] : 0u, bnext = second ? sm_link_bits<M>::tab.next[c] : 0u;
+    unsigned bbase;                // the rows of frame k the frame term has in this column
+    int e = 0;
+    double hb[f], ha[f], gv;       // frame k's rows of the frame term's column and of pair k-1's; q[j]
+    if constexpr (M::has_cost) {
+      constexpr int nl = f + nx;
+      const unsigned char *mk = sd.hmask + c;
+      Dual rr[nx], g[nl];
+#pragma unroll
+      for (int i = 0; i < nx; i++) rr[i] = {pb[i], 0.0};
+      if (M::has_term && k == N - 1) M::template LTG<Dual>(s, uu, rr, g); else M::template LG<Dual>(s, uu, rr, g);
+#pragma unroll
+      for (int i = 0; i < nx; i++) if (mk[(f + i) * nl]) Pc[e++] = g[f + i].d;
+      gv = 0.0; bbase = 0u;
+#pragma unroll
+      for (int r = 0; r < f; r++) { hb[r] = g[r].d; gv = r == c ? g[r].v : gv; bbase |= (mk[r * nl] ? 1u : 0u) << r; }
+    } else {
+      double w;
+      if (c < nx) {
+        w = sd.Qk ? sd.Qk[k * nx + c] : sd.Q[c];
+        Pc[e++] = -2.0 * w;
+        gv = 2.0 * (xv - pb[c]) * w;
+      } else {
+        w = sd.Rk ? sd.Rk[k * nu + c - nx] : sd.R[c - nx];
+        gv = 2.0 * xv * w;
+      }
+#pragma unroll
+      for (int r = 0; r < f; r++) hb[r] = r == c ? 2.0 * w : 0.0;
+      bbase = 1u << c;
+    }
+    Dual os[nx], ou[nu], g2[f2];
+#pragma unroll
+    for (int r = 0; r < f; r++) ha[r] = 0.0;
+    if (first) {
+      const double *pf = fr - f;
+#pragma unroll
+      for (int i = 0; i < nx; i++) os[i] = {pf[i], 0.0};
+#pragma unroll
+      for (int i = 0; i < nu; i++) ou[i] = {pf[nx + i], 0.0};
+      M::template LKG<Dual>(os, ou, s, uu, g2);
+      double ga = 0.0;
+#pragma unroll
+      for (int r = 0; r < f; r++) if ((bprev >> r) & 1u) Pc[e++] = g2[r].d;
+#pragma unroll
+      for (int r = 0; r < f; r++) { ha[r] = g2[f + r].d; ga = r == c ? g2[f + r].v : ga; }
+      gv += ga;
+    }
+    if (second) {
+      const double *nf = fr + f;
+#pragma unroll
+      for (int i = 0; i < nx; i++) os[i] = {nf[i], 0.0};
+#pragma unroll
+      for (int i = 0; i < nu; i++) ou[i] = {nf[nx + i], 0.0};
+      M::template LKG<Dual>(s, uu, os, ou, g2);
+      double gb = 0.0;
+#pragma unroll
+      for (int r = 0; r < f; r++) gb = r == c ? g2[r].v : gb;
+      gv += gb;
+    }
+#pragma unroll
+    for (int r = 0; r < f; r++) {
+      const bool hasb = (bbase >> r) & 1u, hasa = (bown1 >> r) & 1u, has2 = (bown0 >> r) & 1u;
+      if (hasb || hasa || has2) {
+        double v = hasb ? hb[r] : 0.0;
+        if (hasa) v += ha[r];
+        if (has2) v += g2[r].d;
+        Pc[e++] = v;
+      }
+    }
+    if (second) {
+#pragma unroll
+      for (int r = 0; r < f; r++) if ((bnext >> r) & 1u) Pc[e++] = g2[f + r].d;
+    }
+    qb[j] = gv;
+  } else if constexpr (M::has_cost) {
     // column frame_k[c] of the Hessian of l_k: the dual parts of the generated gradient, rows p first, then the frame's
     constexpr int nl = f + nx;
     const unsigned char *mk = sd.hmask + c;
@@ -299,6 +382,18 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
 #pragma unroll
       for (int i = 0; i < nu; i++) cost += uu[i] * uu[i] * (sd.Rk ? sd.Rk[k * nu + i] : sd.R[i]);
     }
+    if constexpr (sm_has_link_cost<M>::value) {
+      // the link cost of stage k = llink(frame_k, frame_{k+1}), behind the frame's own term
+      if (k < sd.N - 1) {
+        double ns[nx], nun[nu], lk[1];
+#pragma unroll
+        for (int i = 0; i < nx; i++) ns[i] = fr[f + i];
+#pragma unroll
+        for (int i = 0; i < nu; i++) nun[i] = fr[f + nx + i];
+        M::template LK<double>(s, uu, ns, nun, lk);
+        cost += lk[0];
+      }
+    }
     if (k < sd.N - 1) {
       double out[nx];
       M::template F<double>(par, sd.dt, s, uu, out);
@@ -343,7 +438,8 @@ __device__ __forceinline__ void stage_shift_block(double *__restrict__ out, cons
 
 // Receding-horizon hand-over between two ticks (mpcqp_stage_advance).  One wave per instance like the merit kernel, lanes striding over the
 // elements of every array: pure data movement but for two runs of F<double> -- the plant step F(s_0, u_0) on lane 0 and the rollout tail
-// F(s_{N-1}, u_{N-1}) on lane 1, one pass of the wave for both -- and the k = 0 cost term on lane 0.  Their nx results go by wave shuffle to the
+// F(s_{N-1}, u_{N-1}) on lane 1, one pass of the wave for both -- and the k = 0 cost term on lane 0 (the frame term only: a link cost,
+// sm_has_link_cost, is not part of that log).  Their nx results go by wave shuffle to the
 // lanes c < nx that store them, so every store stream is contiguous.  No LDS, no atomics, one writer per output element.
 template <class M, bool PF = false, class... PP>
 __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int batch, mpcqp_stage_advance_args a, PP... pp) {
@@ -507,6 +603,18 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
       for (int i = 0; i < nx; i++) { const double e = s[i] - pb[i]; lc += e * e * (sd.Qk ? sd.Qk[k * nx + i] : sd.Q[i]); }
 #pragma unroll
       for (int i = 0; i < nu; i++) lc += uu[i] * uu[i] * (sd.Rk ? sd.Rk[k * nu + i] : sd.R[i]);
+    }
+    if constexpr (sm_has_link_cost<M>::value) {
+      // the link cost of stage k at this candidate, as stage_merit_kernel adds it
+      if (k < N - 1) {
+        double ns[nx], nun[nu], lk[1];
+#pragma unroll
+        for (int i = 0; i < nx; i++) { ns[i] = fr[f + i]; if (c > 0) ns[i] += ac * dfr[f + i]; }
+#pragma unroll
+        for (int i = 0; i < nu; i++) { nun[i] = fr[f + nx + i]; if (c > 0) nun[i] += ac * dfr[f + nx + i]; }
+        M::template LK<double>(s, uu, ns, nun, lk);
+        lc += lk[0];
+      }
     }
     if (k < N - 1) {
       double out[nx];

@@ -199,6 +199,12 @@ class StageOCP:
     # takes an SX of any size (src/OptimalControlProblem.cpp:570-572), computeOptimalTrajectory checks the size only (:85-90) and the user
     # subtracts slice k in the cost of step k.  Variables stay [p; frames], rows [p; frames; dynamics; path; link]; only np grows.
     per_frame_reference = False
+    # optional link cost: llink(s, u, s_next, u_next) -> [...], summed over the stages k = 0 .. N-2 and added to the frame cost (diagonal weights or
+    # lcost / lterm): f += sum_{k<N-1} llink(s_k, u_k, s_{k+1}, u_{k+1}) -- a move penalty (u_{k+1} - u_k)' S (u_{k+1} - u_k), a slew penalty on a state.
+    # It takes no reference and no theta (a link cost that needs either stays on the facade's general path).  Any SX over two frames is a cost term
+    # in the reference (addScalarCost, src/OptimalControlProblem.cpp:491-497); here the callable is traced (codegen.trace_link_cost), its gradient is
+    # derived on the tape and its exact Hessian M (2 f x 2 f) couples frame k to frame k + 1 in P, as the dynamics and the link constraints do in A.
+    llink = None
     # opt-in plant parameters: a model declares ntheta = k <= 8 and theta = np.array([...]) (the defaults) and reads self.theta[i] inside F or cdyn
     # (not in hfun, kfun, lcost, lterm).  The zoo classes map their attributes (mass, length, ...) onto the same vector, in the order of
     # stage_eval.model_params.  set_instance_params gives every instance of a batch its own row: a batch of different robots.
@@ -265,6 +271,11 @@ class StageOCP:
                 self._lttape, self._gttape = codegen.trace_cost(self.lterm, self.nx, self.nu, self.nx)
                 mask = mask | codegen.hessian_mask(self._gttape)
             self.cost_mask = mask | np.eye(mask.shape[0], dtype=bool)
+        self.link_cost = self.llink is not None
+        if self.link_cost:
+            from . import codegen
+            self._lktape, self._lkgtape = codegen.trace_link_cost(self.llink, self.nx, self.nu)
+            self.lmask = codegen.hessian_mask(self._lkgtape)      # exact structure of M over [s; u; s_next; u_next]: no diagonal forced in
         self._build_pattern()
         if self.general_cost:
             self._build_cost_pattern()
@@ -276,20 +287,22 @@ class StageOCP:
         Pp = [0]; Pi = []
         self._P_pp = np.zeros(npp, np.int64); self._P_ps = np.zeros((N, nx), np.int64)  # value slots
         self._P_sp = np.zeros((N, nx), np.int64); self._P_ss = np.zeros((N, nx), np.int64); self._P_uu = np.zeros((N, nu), np.int64)
+        self._P_la, self._P_lb = [], []
         for i in range(npp):                       # column p_i (per-frame references: column p_k[i'], i = k nx + i', rows p_k[i'], s_k[i'])
             self._P_pp[i] = len(Pi); Pi.append(i)
             for k in ([i // nx] if self.pref else range(N)):
                 self._P_sp[k, i % nx] = len(Pi); Pi.append(npp + k * f + i % nx)   # row s_k[i], col p_i
             Pp.append(len(Pi))
         for k in range(N):
-            for i in range(nx):                    # column s_k[i]
-                self._P_ps[k, i] = len(Pi); Pi.append(k * nx + i if self.pref else i)
-                self._P_ss[k, i] = len(Pi); Pi.append(npp + k * f + i)
-                Pp.append(len(Pi))
-            for i in range(nu):
-                self._P_uu[k, i] = len(Pi); Pi.append(npp + k * f + nx + i)
+            for c in range(f):                     # column s_k[c], u_k[c - nx]: the p row of a state, then the frame rows (the diagonal and the link cost's)
+                if c < nx:
+                    self._P_ps[k, c] = len(Pi); Pi.append(k * nx + c if self.pref else c)
+                own = self._frame_column_rows(Pi, k, c, lambda r: r == c)
+                if c < nx: self._P_ss[k, c] = own[c]
+                else: self._P_uu[k, c - nx] = own[c]
                 Pp.append(len(Pi))
         self.Pp = np.asarray(Pp, np.int32); self.Pi = np.asarray(Pi, np.int32)
+        self._P_la = np.asarray(self._P_la, np.int64).reshape(-1, 4); self._P_lb = np.asarray(self._P_lb, np.int64).reshape(-1, 4)
         # A = [I_n; dg/dw]; dg_k/dframe_k dense nx x f, dg_k/ds_{k+1} = I
         Ap = [0]; Ai = []
         self._A_id = np.zeros(n, np.int64)
@@ -322,47 +335,78 @@ class StageOCP:
                 Ap.append(len(Ai))
         self.Ap = np.asarray(Ap, np.int32); self.Ai = np.asarray(Ai, np.int32)
 
+    def _frame_column_rows(self, Pi, k, c, base):
+        """append to Pi the rows of column frame_k[c] that lie in the frames (behind its p rows), ascending: with a link cost the rows frame_{k-1}[r]
+        with lmask[r][f + c] (k >= 1); the rows frame_k[r] with base(r), lmask[r][c] (k < N-1) or lmask[f + r][f + c] (k >= 1); the rows
+        frame_{k+1}[r] with lmask[f + r][c] (k < N-1).  Returns {r: slot} of the frame_k rows.  The link entries go to the slot tables
+        _P_la (what pair k-1 adds, this column in its second frame) and _P_lb (pair k, first frame): rows (slot, pair, row of M, column of M)."""
+        f, N, npp = self.f, self.N, self.np
+        lm = self.lmask if self.link_cost else None
+        own = {}
+        if lm is not None and k >= 1:
+            for r in range(f):
+                if lm[r, f + c]: self._P_la.append((len(Pi), k - 1, r, f + c)); Pi.append(npp + (k - 1) * f + r)
+        for r in range(f):
+            a = lm is not None and k >= 1 and lm[f + r, f + c]
+            b = lm is not None and k < N - 1 and lm[r, c]
+            if base(r) or a or b:
+                own[r] = len(Pi)
+                if a: self._P_la.append((len(Pi), k - 1, f + r, f + c))
+                if b: self._P_lb.append((len(Pi), k, r, c))
+                Pi.append(npp + k * f + r)
+        if lm is not None and k < N - 1:
+            for r in range(f):
+                if lm[f + r, c]: self._P_lb.append((len(Pi), k, f + r, c)); Pi.append(npp + (k + 1) * f + r)
+        return own
+
     def _build_cost_pattern(self):
         """P structure of a general stage cost (csrc/stage_models.hpp sm_build_cost_pattern): both triangles, rows ascending;
-        per entry the Hessian element it takes: (frame k or -1 = summed over the frames, local row, local column)"""
+        _P_src: per entry of the frame cost the Hessian element it takes and its slot: (frame k or -1 = summed over the frames, local row,
+        local column, slot).  Without a link cost the slots are 0 .. nnz(P)-1 in order; with one, the entries only it has lie between them."""
         nx, f, N, npp = self.nx, self.f, self.N, self.np
         mk = self.cost_mask
         Pp = [0]; Pi = []; src = []
+        self._P_la, self._P_lb = [], []
+
+        def frame_rows(k, c):      # the frame rows of column frame_k[c]: entry `slot` takes element (k, r, c) of the frame Hessian where the cost's mask has it
+            for r, slot in self._frame_column_rows(Pi, k, c, lambda r: mk[r, c]).items():
+                if mk[r, c]: src.append((k, r, c, slot))
+
+        def finish():
+            self.Pp = np.asarray(Pp, np.int32); self.Pi = np.asarray(Pi, np.int32)
+            self._P_src = np.asarray(src, np.int64)
+            self._P_la = np.asarray(self._P_la, np.int64).reshape(-1, 4); self._P_lb = np.asarray(self._P_lb, np.int64).reshape(-1, 4)
         if self.pref:
             # per-frame references: nothing sums over the frames, every entry is one element of frame k's Hessian over [s; u; r_k]
             for k in range(N):
                 for i in range(nx):
                     for r in range(nx):
-                        if mk[f + r, f + i]: Pi.append(k * nx + r); src.append((k, f + r, f + i))
+                        if mk[f + r, f + i]: src.append((k, f + r, f + i, len(Pi))); Pi.append(k * nx + r)
                     for r in range(f):
-                        if mk[r, f + i]: Pi.append(npp + k * f + r); src.append((k, r, f + i))
+                        if mk[r, f + i]: src.append((k, r, f + i, len(Pi))); Pi.append(npp + k * f + r)
                     Pp.append(len(Pi))
             for k in range(N):
                 for c in range(f):
                     for i in range(nx):
-                        if mk[f + i, c]: Pi.append(k * nx + i); src.append((k, f + i, c))
-                    for r in range(f):
-                        if mk[r, c]: Pi.append(npp + k * f + r); src.append((k, r, c))
+                        if mk[f + i, c]: src.append((k, f + i, c, len(Pi))); Pi.append(k * nx + i)
+                    frame_rows(k, c)
                     Pp.append(len(Pi))
-            self.Pp = np.asarray(Pp, np.int32); self.Pi = np.asarray(Pi, np.int32)
-            self._P_src = np.asarray(src, np.int64)
+            finish()
             return
         for i in range(npp):
             for r in range(npp):
-                if mk[f + r, f + i]: Pi.append(r); src.append((-1, f + r, f + i))
+                if mk[f + r, f + i]: src.append((-1, f + r, f + i, len(Pi))); Pi.append(r)
             for k in range(N):
                 for r in range(f):
-                    if mk[r, f + i]: Pi.append(npp + k * f + r); src.append((k, r, f + i))
+                    if mk[r, f + i]: src.append((k, r, f + i, len(Pi))); Pi.append(npp + k * f + r)
             Pp.append(len(Pi))
         for k in range(N):
             for c in range(f):
                 for i in range(npp):
-                    if mk[f + i, c]: Pi.append(i); src.append((k, f + i, c))
-                for r in range(f):
-                    if mk[r, c]: Pi.append(npp + k * f + r); src.append((k, r, c))
+                    if mk[f + i, c]: src.append((k, f + i, c, len(Pi))); Pi.append(i)
+                frame_rows(k, c)
                 Pp.append(len(Pi))
-        self.Pp = np.asarray(Pp, np.int32); self.Pi = np.asarray(Pi, np.int32)
-        self._P_src = np.asarray(src, np.int64)
+        finish()
 
     def _cost_inputs(self, p, x):
         s, u = self.frames(x)
@@ -425,6 +469,12 @@ class StageOCP:
     def objective(self, p, x):
         if self._theta_rows is not None:       # (the parameters enter F only; evaluated per instance like every other method, for one rule)
             return np.concatenate(self._each_instance(self._theta_rows, x.shape[0], lambda i: self.objective(p[i], x[i])))
+        if self.link_cost:
+            return self._frame_objective(p, x) + self.link_cost_values(x).sum(axis=1)
+        return self._frame_objective(p, x)
+
+    def _frame_objective(self, p, x):
+        """the sum of the frame terms (everything but the link cost)"""
         if self.general_cost:
             return self._cost_eval(self._ltape, self._lttape, self._cost_inputs(p, x))[0].sum(axis=1)
         s, u = self.frames(x)
@@ -432,6 +482,30 @@ class StageOCP:
         if self.varying_weights:
             return np.einsum("bki,ki->b", e * e, self.Qk) + np.einsum("bki,ki->b", u * u, self.Rk)
         return np.einsum("bki,i->b", e * e, self.Q) + np.einsum("bki,i->b", u * u, self.R)
+
+    def _link_cost_inputs(self, x):
+        s, u = self.frames(x)
+        return ([s[:, :-1, i] for i in range(self.nx)] + [u[:, :-1, i] for i in range(self.nu)]
+                + [s[:, 1:, i] for i in range(self.nx)] + [u[:, 1:, i] for i in range(self.nu)])
+
+    def link_cost_values(self, x):
+        """[B, N-1]: llink(s_k, u_k, s_{k+1}, u_{k+1}) on every stage"""
+        ins = self._link_cost_inputs(x)
+        return np.broadcast_to(np.asarray(self._lktape.evaluate(ins)[0]), ins[0].shape)
+
+    def link_cost_derivatives(self, x):
+        """(grad [B, N-1, 2 f], hess [B, N-1, 2 f, 2 f]) of the link cost on every stage over [s_k; u_k; s_{k+1}; u_{k+1}]: gradient tape evaluated
+        directly, Hessian columns by complex-step differentiation of the gradient tape (exact to rounding), like cost_derivatives"""
+        ins = self._link_cost_inputs(x)
+        n2 = len(ins); shape = ins[0].shape
+        ev = lambda v: np.stack([np.broadcast_to(np.asarray(o), shape) for o in self._lkgtape.evaluate(v)], axis=-1)
+        grad = ev(ins).astype(float)
+        hess = np.zeros(shape + (n2, n2)); eps = 1e-30
+        for c in range(n2):
+            pert = [v.astype(complex) for v in ins]
+            pert[c] = pert[c] + 1j * eps
+            hess[..., :, c] = ev(pert).imag / eps
+        return grad, hess
 
     def dh(self, s, u):
         """[..., nh, f] Jacobian of hfun wrt [s; u] by complex-step differentiation"""
@@ -471,8 +545,8 @@ class StageOCP:
             grad, hess = self.cost_derivatives(p, x)
             src = self._P_src; summed = src[:, 0] < 0
             P = np.zeros((B, len(self.Pi)))
-            P[:, summed] = hess[:, :, src[summed, 1], src[summed, 2]].sum(axis=1)
-            P[:, ~summed] = hess[:, src[~summed, 0], src[~summed, 1], src[~summed, 2]]
+            P[:, src[summed, 3]] = hess[:, :, src[summed, 1], src[summed, 2]].sum(axis=1)
+            P[:, src[~summed, 3]] = hess[:, src[~summed, 0], src[~summed, 1], src[~summed, 2]]
             q[:, :npp] = grad[:, :, f:].reshape(B, -1) if self.pref else grad[:, :, f:].sum(axis=1)
             q[:, npp:] = grad[:, :, :f].reshape(B, -1)
         else:
@@ -488,6 +562,15 @@ class StageOCP:
                 q[:, :npp] = -2.0 * (np.einsum("bki,ki->bi", e, self.Qk) if self.varying_weights else np.einsum("bki,i->bi", e, self.Q))
             qf = q[:, npp:].reshape(B, N, f)
             qf[:, :, :nx] = 2.0 * e * self.Qk; qf[:, :, nx:] = 2.0 * u * self.Rk
+        if self.link_cost:
+            # the link cost, in the order the device sums it: the frame term stands; then what pair k-1 adds (this frame its second), then pair k
+            gl, Ml = self.link_cost_derivatives(x)               # [B, N-1, 2 f], [B, N-1, 2 f, 2 f]
+            la, lb = self._P_la, self._P_lb
+            P[:, la[:, 0]] += Ml[:, la[:, 1], la[:, 2], la[:, 3]]
+            P[:, lb[:, 0]] += Ml[:, lb[:, 1], lb[:, 2], lb[:, 3]]
+            qf = q[:, npp:].reshape(B, N, f)
+            qf[:, 1:] += gl[..., f:]
+            qf[:, :-1] += gl[..., :f]
         J = self.dF(s[:, :-1, :], u[:, :-1, :])                 # [B, N-1, nx, f]
         A = np.zeros((B, len(self.Ai)))
         A[:, self._A_id] = 1.0

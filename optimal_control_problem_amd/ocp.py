@@ -7,8 +7,8 @@ method (the IPOPT / qpOASES / MIXED arms are third-p
 CasADi is not available here, so the symbolic SX expressions the reference's builders take are replaced by a tiny
 expression layer that covers what a stage-structured OCP needs: variable slices of a frame (OCPConfig.getVariable),
 the reference parameter vector, differences, and a discrete-dynamics call.  genSolver() recognises the resulting
-structure (quadratic tracking cost with diagonal weights or a general traced stage cost, dynamics defects between
-consecutive frames, per-frame path constraints) and builds the
+structure (quadratic tracking cost with diagonal weights or a general traced stage cost, optionally a link cost between
+consecutive frames, dynamics defects between consecutive frames, per-frame path constraints, link constraints) and builds the
 batched local-system evaluator (models.StageOCP) that plays the role of the CasADi-generated localSystemFunction_
 (reference src/sqp_solver/SQPOptimizationSolver.cpp:74-77).  One object may drive a batch of independent instances.
 """
@@ -101,6 +101,18 @@ class StageCost(Expr):
         self.size = 1
 
 
+class LinkCost(Expr):
+    """l(state_k, input_k, state_{k+1}, input_{k+1}) of two consecutive frames: a scalar cost term that couples them -- a move penalty
+    (u_{k+1} - u_k)' S (u_{k+1} - u_k), a jerk or slew penalty, smoothness of a state -- given as a NumPy callable on [..., nx], [..., nu],
+    [..., nx], [..., nu] returning [...]; used with addScalarCost(LinkCost(...)) on every stage k = 0 .. N-2, in order, beside the addVectorCost
+    terms or the per-frame StageCost terms.  Stands for the SX terms over two frames the reference sums (src/OptimalControlProblem.cpp:491-497).
+    The term takes no reference: a link cost that needs the reference is a General term and takes the general path."""
+
+    def __init__(self, l, state, inp, state_next, inp_next):
+        self.l, self.state, self.inp, self.state_next, self.inp_next = l, state, inp, state_next, inp_next
+        self.size = 1
+
+
 class General(Expr):
     """fn(X, p) over the WHOLE decision vector X (horizon x frameSize, reference OCPConfig.cpp:29-46) and the parameter vector p: any
     expression the stage pattern does not cover -- terms coupling frames that are not neighbours, different functions per frame, terms
@@ -133,6 +145,8 @@ def evaluate_expression(e, X, p):
         return e.k(evaluate_expression(e.state, X, p), evaluate_expression(e.inp, X, p), evaluate_expression(e.state_next, X, p), evaluate_expression(e.inp_next, X, p))
     if isinstance(e, StageCost):
         return e.l(evaluate_expression(e.state, X, p), evaluate_expression(e.inp, X, p), evaluate_expression(e.reference, X, p))
+    if isinstance(e, LinkCost):
+        return e.l(evaluate_expression(e.state, X, p), evaluate_expression(e.inp, X, p), evaluate_expression(e.state_next, X, p), evaluate_expression(e.inp_next, X, p))
     if isinstance(e, General):
         return e.fn(X, p)
     raise TypeError("not a facade expression: %r" % (e,))
@@ -239,8 +253,9 @@ class _FacadeStageOCP(models.StageOCP):
     name = "facade_ocp"
 
     def __init__(self, nx, nu, N, dt, Q, R, F, lo, hi, h=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, k=None, nk=0, k_lo=None, k_hi=None,
-                 per_frame_reference=False):
+                 per_frame_reference=False, llink=None):
         self.nx, self.nu, self._F, self._lo, self._hi = nx, nu, F, lo, hi
+        self.llink = llink
         if per_frame_reference:
             self.per_frame_reference = True
         self._h, self.nh, self.h_lo, self.h_hi = h, int(nh), h_lo, h_hi
@@ -370,7 +385,8 @@ class OptimalControlProblem:
         h_lo, h_hi = model.path_bounds() if model.nh else (None, None)
         tape = codegen.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
                              lcost=model.lcost if model.general_cost else None, lterm=model.lterm if model.general_cost else None,
-                             **({"per_frame_reference": True} if model.per_frame_reference else {}))
+                             **({"per_frame_reference": True} if model.per_frame_reference else {}),
+                             **({"llink": model.llink} if model.link_cost else {}))
         return codegen.build_device_library(tape)
 
     def getConstraints(self):
@@ -477,10 +493,26 @@ class OptimalControlProblem:
             if isinstance(r, ReferenceFrame) and r.ref is self.reference_ and r.k == step and r.size == nx:
                 return "frame"
             return None
-        general = [c for c in self.costs_ if isinstance(c, StageCost)]
+        # link cost: one LinkCost per stage k = 0 .. N-2, in order, the same function of (frame k, frame k + 1) on every stage; the other terms are
+        # the frame cost, in either form
+        link_costs = [c for c in self.costs_ if isinstance(c, LinkCost)]
+        frame_costs = [c for c in self.costs_ if not isinstance(c, LinkCost)]
+        llink = None
+        if link_costs:
+            if len(link_costs) != N - 1:
+                raise NotImplementedError("link costs: exactly one LinkCost term per stage k = 0 .. N-2 (%d terms for %d stages)" % (len(link_costs), N - 1))
+            llink = link_costs[0].l
+            for k, c in enumerate(link_costs):
+                if c.l != llink:
+                    raise NotImplementedError("the link cost must be the same function on every stage")
+                if not (all(isinstance(v, Var) for v in (c.state, c.inp, c.state_next, c.inp_next)) and c.state.step == k and c.inp.step == k
+                        and c.state_next.step == k + 1 and c.inp_next.step == k + 1 and c.state.name == s0.name and c.inp.name == u0.name
+                        and c.state_next.name == s0.name and c.inp_next.name == u0.name):
+                    raise NotImplementedError("a LinkCost takes (state_k, input_k, state_{k+1}, input_{k+1}), added for the stages k = 0 .. N-2 in order")
+        general = [c for c in frame_costs if isinstance(c, StageCost)]
         if general:
             # general stage cost: one StageCost per frame, the same function on every frame but (optionally) the last
-            if len(general) != len(self.costs_) or sorted(c.state.step for c in general) != list(range(N)):
+            if len(general) != len(frame_costs) or sorted(c.state.step for c in general) != list(range(N)):
                 raise NotImplementedError("general costs: exactly one StageCost term per frame and no other cost terms")
             general.sort(key=lambda c: c.state.step)
             for k, c in enumerate(general):
@@ -492,10 +524,10 @@ class OptimalControlProblem:
                 raise NotImplementedError("the stage cost must be the same function on every frame except the last")
             lterm = general[-1].l if general[-1].l != lcost else None
             seenQ = seenR = set(range(N))
-        for term in ([] if general else self.costs_):
+        for term in ([] if general else frame_costs):
             kind, w, e = term if isinstance(term, tuple) else (None, None, None)
             if kind != "weighted_square":
-                raise NotImplementedError("only addVectorCost terms and StageCost terms are compiled")
+                raise NotImplementedError("only addVectorCost terms, StageCost terms and LinkCost terms are compiled")
             if isinstance(e, Diff) and isinstance(e.a, Var) and e.a.name == s0.name and ref_kind(e.b, e.a.step) and self.reference_ is not None:
                 kinds.add(ref_kind(e.b, e.a.step))
                 Qk[e.a.step] += w; seenQ.add(e.a.step)        # repeated terms on one step add up, like the SX sum (:491-497)
@@ -538,7 +570,7 @@ class OptimalControlProblem:
         # rows of the compiled model: dynamics rows in frame order, then the path rows in frame order, then the link rows in stage order
         self._row_order = [i for _, i in sorted((self.constraints_[i].a.step, i) for i in dyn_idx)] + path_idx + link_idx
         return _FacadeStageOCP(nx, nu, N, cfg.getDt(), Q, R, F, cfg.getLowerBounds()[0], cfg.getUpperBounds()[0], h, nh, h_lo, h_hi, lcost, lterm, kf, nk, k_lo, k_hi,
-                               per_frame_reference=tracking)
+                               per_frame_reference=tracking, llink=llink)
 
     # -- computeOptimalTrajectory (:78-222), CUDA_SQP arm
     def computeOptimalTrajectory(self, frame, reference):

@@ -52,6 +52,7 @@ def _bind(L):
     L.mpcqp_stage_set_instance_params.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int]
     L.mpcqp_stage_dims.argtypes = [vp, vp]
     L.mpcqp_stage_has_cost.argtypes = [vp]
+    L.mpcqp_stage_has_link_cost.argtypes = [vp]
     L.mpcqp_stage_pattern.argtypes = [vp, vp, vp, vp, vp]
     L.mpcqp_stage_eval.argtypes = [vp, C.c_int] + [dp] * 11 + [vp]
     L.mpcqp_stage_merit.argtypes = [vp, C.c_int, dp, dp, dp, dp, vp]
@@ -107,10 +108,11 @@ class StageEvaluator:
                     zoo = True
             general = bool(getattr(model, "general_cost", False))
             nk = int(getattr(model, "nk", 0))
-            use_codegen = (not zoo or model.nh > 0 or nk > 0 or general) if codegen is None else bool(codegen)
-            if not use_codegen and (model.nh > 0 or nk > 0 or not zoo or general):
+            link_cost = bool(getattr(model, "link_cost", False))
+            use_codegen = (not zoo or model.nh > 0 or nk > 0 or general or link_cost) if codegen is None else bool(codegen)
+            if not use_codegen and (model.nh > 0 or nk > 0 or not zoo or general or link_cost):
                 raise ValueError("this model needs the generated evaluator (codegen=True): it is not a built-in zoo model, or has a path / link "
-                                 "constraint or a general stage cost")
+                                 "constraint, a general stage cost or a link cost")
             _lib.check(L.mpcqp_stage_default(MODEL_IDS.get(model.name, 0) if zoo else 0, int(model.N), C.byref(d)))
             d.dt = float(model.dt)
             if model.nx > 16 or model.nu > 8:
@@ -129,7 +131,8 @@ class StageEvaluator:
                 self.tape = cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
                                      lcost=model.lcost if general else None, lterm=model.lterm if general else None,
                                      kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
-                                     **({"per_frame_reference": True} if self.per_frame_reference else {}), **pkw)
+                                     **({"per_frame_reference": True} if self.per_frame_reference else {}), **pkw,
+                                     **({"llink": model.llink} if link_cost else {}))
                 self.library = cg.build_device_library(self.tape)
             else:
                 for i, v in enumerate(model_params(model)): d.par[i] = float(v)
@@ -155,6 +158,7 @@ class StageEvaluator:
         self.nx, self.nu, self.np, self.n, self.m, self.nnzP, self.nnzA, self.nvar = [int(v) for v in dims]
         self.ng = self.m - self.n
         self.general_cost = bool(L.mpcqp_stage_has_cost(self._h))
+        self.link_cost = bool(L.mpcqp_stage_has_link_cost(self._h))      # a link cost between consecutive frames (models.StageOCP.llink)
         self.param_count = int(L.mpcqp_stage_param_count(self._h))      # parameters per instance (mpcqp_stage_set_instance_params); 0: none
         self.Pp = np.zeros(self.n + 1, np.int32); self.Pi = np.zeros(self.nnzP, np.int32)
         self.Ap = np.zeros(self.n + 1, np.int32); self.Ai = np.zeros(self.nnzA, np.int32)
