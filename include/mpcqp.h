@@ -345,6 +345,30 @@ int mpcqp_stage_set_path_bounds(mpcqp_stage *s, const double *lo, const double *
 /* 7 quadrotor, 4 cart-pole, 0 double integrator, ntheta of a generated library */
 int mpcqp_stage_param_count(const mpcqp_stage *s);
 int mpcqp_stage_set_instance_params(mpcqp_stage *s, int which, int batch, const double *theta, int mem);
+/* Stage data: per-frame, per-instance values in the path constraint and the costs -- a batch of different worlds on one handle (opt-in; DESIGN.md
+ * 6.15).  In the reference the parameter SX may appear in any constraint or cost term (src/OptimalControlProblem.cpp:444-497); acados and ACADO
+ * know the same as stage-wise parameters / online data.  A library generated from a model that declares nsd = k (1 <= k <= MPCQP_STAGE_MAXSD) reads
+ * k values d[0..k-1] inside hfun, lcost and lterm (not in F, kfun or llink): an obstacle's centre, a corridor's width, a scheduled weight.  Without
+ * a stored set every frame of every instance takes the defaults the library was generated with.  The values are data: they are not QP variables,
+ * add no column, row or entry of P or A, and mpcqp_stage_pattern / _dims are those of the same model with the numbers written as constants.
+ * mpcqp_stage_data_count: k of a generated library, 0 for the zoo models and for a library generated without stage data (every library from before
+ * this entry included), 0 for a null handle.
+ * mpcqp_stage_set_stage_data: d [batch * horizon * nsd], row (b, k) = what frame k of instance b takes, copied into a buffer the handle owns
+ * (mem = MPCQP_MEM_HOST or MPCQP_MEM_DEVICE) before the call returns; mpcqp_stage_eval, _merit, _linesearch and the stage_cost log of
+ * mpcqp_stage_advance (the k = 0 term, with d_0 as it stands before any shift) use it from then on.  d = NULL returns to the defaults (batch and
+ * mem are then ignored).  A launch whose batch exceeds the stored set's is MPCQP_ERR_ARG, a smaller one uses the first rows.  MPCQP_ERR_ARG as
+ * well for a null handle, a handle whose mpcqp_stage_data_count is 0, batch <= 0 with a non-NULL d, or a bad mem; MPCQP_ERR_HIP when the
+ * allocation or the copy fails.
+ * mpcqp_stage_shift_data: the receding-horizon hand-over of the stored set, one kernel on `stream`: row (b, k) becomes row (b, k + 1) for
+ * k < horizon - 1, the last row d_new[b] (d_new [batch * nsd], device memory) or, with d_new = NULL, the old last row again.  Out of place between
+ * two buffers of the handle, which are then swapped: launches enqueued on the same stream afterwards see the shifted set.  The data describe the
+ * world, so they shift whatever the QP's status was, as the per-frame references do in mpcqp_stage_advance; call it after that entry, which
+ * still reads d_0.  MPCQP_ERR_STATE when no set is stored (the defaults do not shift); MPCQP_ERR_ARG for a null handle, a handle without stage
+ * data, or a batch that is not the stored set's (every stored row shifts). */
+#define MPCQP_STAGE_MAXSD 8
+int mpcqp_stage_data_count(const mpcqp_stage *s);
+int mpcqp_stage_set_stage_data(mpcqp_stage *s, int batch, const double *d, int mem);
+int mpcqp_stage_shift_data(mpcqp_stage *s, int batch, const double *d_new /* [batch * nsd], device, may be NULL */, void *stream);
 /* dims[8] = {nx, nu, np, n, m, nnz(P), nnz(A), horizon * (nx + nu)} */
 int mpcqp_stage_dims(const mpcqp_stage *s, int *dims8);
 /* 1 when the evaluator was generated with its own stage cost (mpcqp_stage_create_user above), 0 for diagonal tracking weights */

@@ -188,8 +188,9 @@ def tangent_outputs(tape, k):
 
 
 def hessian_mask(gtape):
-    """structural sparsity [n_in, n_in] of the Hessian whose gradient tape is gtape (entries that are not identically zero)"""
-    n = gtape.n_in
+    """structural sparsity [n, n] of the Hessian whose gradient tape is gtape (entries that are not identically zero); n = the gradient's length:
+    all inputs, or the leading [s; u; r] block of a cost that also reads stage data (those carry no derivative)"""
+    n = len(gtape.outputs)
     mask = np.zeros((n, n), bool)
     for k in range(n):
         t, d = tangent_outputs(gtape, k)
@@ -379,6 +380,7 @@ def _array_function(tape, func, args, kwargs):
 
 
 NTHETA_MAX = 8        # MPCQP_STAGE_NPAR: the width of a parameter row
+NSD_MAX = 8           # MPCQP_STAGE_MAXSD (SM_MAXSD): the most stage-data values a frame may take
 
 
 class _ThetaGuard:
@@ -393,29 +395,47 @@ class _ThetaGuard:
     __getitem__ = __iter__ = __len__ = __array__ = __add__ = __radd__ = __mul__ = __rmul__ = __sub__ = __rsub__ = __truediv__ = __rtruediv__ = __neg__ = _refuse
 
 
-class _bound_theta:
-    """model.theta = value for the duration of a trace (a model without parameters, or no model: nothing happens)"""
+class _SdataGuard:
+    """stands in for model.sdata while F, kfun or llink is traced: stage data are data of the path constraint and the frame costs only"""
 
-    def __init__(self, model, value):
-        self.model, self.value = model, value
+    def __init__(self, what):
+        self._what = what
+
+    def _refuse(self, *a, **k):
+        raise ValueError("%s reads self.sdata: stage data are supported in hfun, lcost and lterm only (not in F / cdyn, kfun, llink)" % self._what)
+
+    __getitem__ = __iter__ = __len__ = __array__ = __add__ = __radd__ = __mul__ = __rmul__ = __sub__ = __rsub__ = __truediv__ = __rtruediv__ = __neg__ = _refuse
+
+
+class _bound_theta:
+    """model.theta (or model.<attr>) = value for the duration of a trace (a model without parameters, or no model: nothing happens)"""
+
+    def __init__(self, model, value, attr="theta"):
+        self.model, self.value, self.attr = model, value, attr
 
     def __enter__(self):
         if self.model is not None:
-            self.saved = self.model.theta
-            self.model.theta = self.value
+            self.saved = getattr(self.model, self.attr)
+            setattr(self.model, self.attr, self.value)
 
     def __exit__(self, *exc):
         if self.model is not None:
-            self.model.theta = self.saved
+            setattr(self.model, self.attr, self.saved)
         return False
 
 
-def _trace_fn(fn, nx, nu, n_out, what, ntheta=0, model=None):
-    """ntheta > 0: that many extra tape inputs behind [s; u], bound to model.theta while fn runs (the plant parameters: par[i] in the emitted code)"""
-    tape = Tape(nx + nu + ntheta)
+def _trace_fn(fn, nx, nu, n_out, what, ntheta=0, model=None, nsd=0):
+    """ntheta > 0: that many extra tape inputs behind [s; u], bound to model.theta while fn runs (the plant parameters: par[i] in the emitted code).
+    nsd > 0 (hfun): that many extra inputs behind [s; u], bound to model.sdata (the frame's stage data: d[i] in the emitted code)"""
+    tape = Tape(nx + nu + ntheta + nsd)
     s = TV(tape, [TS(tape, i) for i in range(nx)])
     u = TV(tape, [TS(tape, nx + i) for i in range(nu)])
-    if ntheta:
+    if nsd:
+        with _bound_theta(model, TV(tape, [TS(tape, nx + nu + i) for i in range(nsd)]), "sdata"):
+            out = fn(s, u)
+        tape.in_names = [("s", nx), ("u", nu), ("d", nsd)]
+        tape.plain_from = nx + nu
+    elif ntheta:
         with _bound_theta(model, TV(tape, [TS(tape, nx + nu + i) for i in range(ntheta)])):
             out = fn(s, u)
         tape.in_names = [("s", nx), ("u", nu), ("par", ntheta)]
@@ -432,11 +452,14 @@ def _trace_fn(fn, nx, nu, n_out, what, ntheta=0, model=None):
     return tape
 
 
-def trace_cost(lfun, nx, nu, nr):
-    """stage cost l(s, u, r) -> scalar on tracers; returns (value tape, gradient tape) over inputs [s; u; r]"""
-    tape = Tape(nx + nu + nr)
+def trace_cost(lfun, nx, nu, nr, nsd=0, model=None):
+    """stage cost l(s, u, r) -> scalar on tracers; returns (value tape, gradient tape) over inputs [s; u; r].  nsd > 0: that many extra inputs
+    behind r, bound to model.sdata while lfun runs (the frame's stage data); the gradient keeps the [s; u; r] block only"""
+    nl = nx + nu + nr
+    tape = Tape(nl + nsd)
     mk = lambda a, b: TV(tape, [TS(tape, i) for i in range(a, b)])
-    out = lfun(mk(0, nx), mk(nx, nx + nu), mk(nx + nu, nx + nu + nr))
+    with _bound_theta(model if nsd else None, mk(nl, nl + nsd), "sdata"):
+        out = lfun(mk(0, nx), mk(nx, nx + nu), mk(nx + nu, nl))
     if isinstance(out, TV) and len(out) == 1:
         out = out.items[0]
     if isinstance(out, (int, float, np.integer, np.floating)):
@@ -445,7 +468,12 @@ def trace_cost(lfun, nx, nu, nr):
         raise ValueError("the stage cost must return one scalar")
     tape.outputs = [out.idx]
     tape.nx, tape.nu, tape.nr = nx, nu, nr
-    return tape, gradient_tape(tape)
+    g = gradient_tape(tape)
+    if nsd:
+        g.outputs = g.outputs[:nl]
+        tape.in_names = g.in_names = [("s", nx), ("u", nu), ("r", nr), ("d", nsd)]
+        tape.plain_from = g.plain_from = nl
+    return tape, g
 
 
 def _trace_link(kfun, nx, nu, nk):
@@ -487,7 +515,7 @@ def trace_link_cost(llink, nx, nu):
 
 
 def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False,
-          ntheta=0, theta0=None, model=None, llink=None):
+          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
@@ -501,8 +529,15 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     raises a ValueError.
     llink(s, u, s_next, u_next) -> scalar: a link cost, summed over the stages k = 0 .. N-2 on top of the frame cost (a move penalty
     (u_{k+1} - u_k)' S (u_{k+1} - u_k) and the like).  It takes no reference and no theta.  tape.link_cost holds its value tape, its gradient
-    tape and the exact structure of its Hessian over [s; u; s_next; u_next] (no diagonal is forced into it)."""
+    tape and the exact structure of its Hessian over [s; u; s_next; u_next] (no diagonal is forced into it).
+    nsd = k (<= 8), sdata0 = the k default values: the model reads its stage data as self.sdata[i] inside hfun, lcost and lterm (a cost that does
+    is a method of the model); while those are traced, self.sdata holds k extra tape inputs, emitted as d[i] -- data of the launch
+    (mpcqp_stage_set_stage_data gives every frame of every instance its own row), without a derivative: the gradient and the Hessian's structure
+    are over [s; u; r] as before.  F / cdyn, kfun and llink take none: reading self.sdata there raises a ValueError."""
     ntheta = int(ntheta)
+    nsd = int(nsd)
+    if nsd > NSD_MAX:
+        raise ValueError("at most %d stage-data values are supported (nsd = %d)" % (NSD_MAX, nsd))
     if ntheta > NTHETA_MAX:
         raise ValueError("at most %d model parameters are supported (ntheta = %d)" % (NTHETA_MAX, ntheta))
     if model is None:
@@ -514,7 +549,18 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
         theta0 = np.asarray(model.theta if theta0 is None else theta0, float).ravel()
         if theta0.size != ntheta:
             raise ValueError("theta0 must hold ntheta = %d values" % ntheta)
-    tape = _trace_fn(F, nx, nu, nx, "F must return the next state", ntheta, model)
+    if nsd:
+        if model is None:
+            raise ValueError("nsd needs the model whose sdata hfun / lcost / lterm read (model=, or F as a bound method)")
+        sdata0 = np.asarray(model.sdata if sdata0 is None else sdata0, float).ravel()
+        if sdata0.size != nsd:
+            raise ValueError("sdata0 must hold nsd = %d values" % nsd)
+    unread = model if nsd else None           # whose sdata F, kfun and llink may not read
+    with _bound_theta(unread, _SdataGuard("F"), "sdata"):
+        tape = _trace_fn(F, nx, nu, nx, "F must return the next state", ntheta, model)
+    if nsd:
+        tape.nsd = nsd
+        tape.sdata0 = [float(v) for v in sdata0]
     tape.ntheta = ntheta
     tape.theta0 = [float(v) for v in theta0] if ntheta else []
     tape.pref = bool(per_frame_reference)
@@ -522,26 +568,26 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     tape.path = None
     if tape.nh:
         with _bound_theta(guarded, _ThetaGuard("hfun")):
-            tape.path = _trace_fn(hfun, nx, nu, tape.nh, "hfun must return the path-constraint values")
+            tape.path = _trace_fn(hfun, nx, nu, tape.nh, "hfun must return the path-constraint values", model=model, nsd=nsd)
         tape.h_lo = [float(v) for v in np.broadcast_to(np.asarray(h_lo, float), (tape.nh,))]
         tape.h_hi = [float(v) for v in np.broadcast_to(np.asarray(h_hi, float), (tape.nh,))]
     # link constraint k_lo <= kfun(s_k, u_k, s_{k+1}, u_{k+1}) <= k_hi between consecutive frames (rate limits and the like)
     tape.nk = int(nk) if kfun is not None else 0
     tape.link = None
     if tape.nk:
-        with _bound_theta(guarded, _ThetaGuard("kfun")):
+        with _bound_theta(guarded, _ThetaGuard("kfun")), _bound_theta(unread, _SdataGuard("kfun"), "sdata"):
             tape.link = _trace_link(kfun, nx, nu, tape.nk)
         tape.k_lo = [float(v) for v in np.broadcast_to(np.asarray(k_lo, float), (tape.nk,))]
         tape.k_hi = [float(v) for v in np.broadcast_to(np.asarray(k_hi, float), (tape.nk,))]
     tape.cost = None
     if lcost is not None:
         with _bound_theta(guarded, _ThetaGuard("lcost")):
-            L, G = trace_cost(lcost, nx, nu, nx)
+            L, G = trace_cost(lcost, nx, nu, nx, nsd, model)
         mask = hessian_mask(G)
         LT = GT = None
         if lterm is not None:
             with _bound_theta(guarded, _ThetaGuard("lterm")):
-                LT, GT = trace_cost(lterm, nx, nu, nx)
+                LT, GT = trace_cost(lterm, nx, nu, nx, nsd, model)
             mask = mask | hessian_mask(GT)
         mask = mask | np.eye(mask.shape[0], dtype=bool)      # keep the diagonal in the pattern
         tape.cost = dict(L=L, G=G, LT=LT, GT=GT, mask=mask)
@@ -549,7 +595,7 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
         raise ValueError("a terminal cost needs a stage cost")
     tape.link_cost = None
     if llink is not None:
-        with _bound_theta(guarded, _ThetaGuard("llink")):
+        with _bound_theta(guarded, _ThetaGuard("llink")), _bound_theta(unread, _SdataGuard("llink"), "sdata"):
             LK, LKG = trace_link_cost(llink, nx, nu)
         tape.link_cost = dict(L=LK, G=LKG, mask=hessian_mask(LKG))
     return tape
@@ -572,6 +618,7 @@ def _emit_body(tape, streaming=False):
     # nodes that depend on parameters and constants only are plain doubles next to T = Dual (a parameter carries no derivative): they mix with T
     # through the double-Dual operators, as literals do
     par_from = tape.nx + tape.nu if getattr(tape, "ntheta", 0) else tape.n_in
+    par_from = getattr(tape, "plain_from", par_from)      # (stage data, d[i]: plain doubles as well)
     plain = set()
     for i in live:
         nd = tape.nodes[i]
@@ -653,17 +700,20 @@ def emit_functor(tape, name="SmUser"):
     hbody = _emit_body(tape.path) if nh else ""
     kbody = _emit_body(tape.link) if nk else ""
     nth = getattr(tape, "ntheta", 0)
+    nsd = getattr(tape, "nsd", 0)
+    dsig = "const double *d, " if nsd else ""      # (nsd > 0: H, L, LG, LT, LTG take the frame's stage-data row d behind their inputs)
     # (ntheta > 0: the plant parameters are par[i] in F's body -- data of the launch, sd.par or the instance's row)
     fmt = ("struct %s {\n  static constexpr int nx = %d, nu = %d, nh = %d, nk = %d, has_cost = %d, has_term = %d;\n"
-           + ("  static constexpr int ntheta = %d;\n" % nth if nth else "") +
+           + ("  static constexpr int ntheta = %d;\n" % nth if nth else "")
+           + ("  static constexpr int nsd = %d;\n  static constexpr double sdata0[%d] = {%s};\n" % (nsd, nsd, ", ".join(_lit(v) for v in tape.sdata0)) if nsd else "") +
            "  template <class T> SM_HD static void F(const double *" + ("par" if nth else "") + ", double, const T *s, const T *u, T *out) {\n%s\n  }\n"
-           "  template <class T> SM_HD static void H(const T *s, const T *u, T *out) {\n%s\n  }\n"
+           "  template <class T> SM_HD static void H(const T *s, const T *u, " + dsig + "T *out) {\n%s\n  }\n"
            "  template <class T> SM_HD static void K(const T *s, const T *u, const T *sn, const T *un, T *out) {\n%s\n  }\n")
     src = fmt % (name, tape.nx, tape.nu, nh, nk, 1 if cost else 0, 1 if cost and cost["LT"] is not None else 0, _emit_body(tape), hbody, kbody)
     if cost:
         # L: out[0] = l(s, u, r); LG: out[nx + nu + nx] = dl / d[s; u; r]; LT, LTG: the terminal frame's
         for fn, tp in (("L", cost["L"]), ("LG", cost["G"]), ("LT", cost["LT"] or cost["L"]), ("LTG", cost["GT"] or cost["G"])):
-            src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *r, T *out) {\n%s\n  }\n" % (fn, _emit_body(tp))
+            src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *r, %sT *out) {\n%s\n  }\n" % (fn, dsig, _emit_body(tp))
     if getattr(tape, "pref", False):
         src += "  static constexpr bool pref = true;\n"
     link_cost = getattr(tape, "link_cost", None)
@@ -685,6 +735,8 @@ def emit_functor(tape, name="SmUser"):
     src += "static const unsigned char %s_cost_mask[] = {%s};\n" % (name, mk)
     if nth:
         src += "static const double %s_theta0[] = {%s};\n" % (name, ", ".join(_lit(v) for v in tape.theta0))
+    if nsd:
+        src += "static const double %s_sdata0[] = {%s};\n" % (name, ", ".join(_lit(v) for v in tape.sdata0))
     return src
 
 
@@ -709,20 +761,20 @@ int mpcqp_user_cost(unsigned char *mask) {
 }
 int mpcqp_user_eval(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                     const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream) {
-  return (int)stage_launch_eval<SmUser%(pf)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream);
+  return (int)stage_launch_eval<SmUser%(pf)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream%(sdarg)s);
 }
 int mpcqp_user_merit(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
-  return (int)stage_launch_merit<SmUser%(pf)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream);
+  return (int)stage_launch_merit<SmUser%(pf)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream%(sdarg)s);
 }
 // the hand-over between two MPC ticks (mpcqp_stage_advance)
 int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream) {
-  return (int)stage_launch_advance<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream);
+  return (int)stage_launch_advance<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream%(sdarg)s);
 }
 // the per-instance merit line search (mpcqp_stage_linesearch)
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
-  return (int)stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream);
+  return (int)stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream%(sdarg)s);
 }
-%(params)s%(link_cost)s}
+%(params)s%(link_cost)s%(sdata)s}
 '''
 
 # a model with a link cost (llink) only: 1 and the structure of its Hessian over [s; u; s_next; u_next] (row-major (2 f)^2 bytes).  A library
@@ -740,18 +792,48 @@ _DEVICE_PARAMS_TMPL = '''int mpcqp_user_ntheta() { return SmUser::ntheta; }
 void mpcqp_user_theta0(double *par) { for (int i = 0; i < SmUser::ntheta; i++) par[i] = SmUser_theta0[i]; }
 int mpcqp_user_eval_pp(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                        const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream, const double *theta) {
-  return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr});
+  return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
 }
 int mpcqp_user_merit_pp(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream, const double *theta) {
-  return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr});
+  return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
 }
 int mpcqp_user_advance_pp(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream, const double *theta, const double *plant) {
-  return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant});
+  return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant}%(sdarg)s);
 }
 int mpcqp_user_linesearch_pp(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream, const double *theta) {
-  return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr});
+  return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
 }
 '''
+
+# a model with stage data (nsd > 0) only: their count, their defaults and the launchers mpcqp_stage_* uses for such a library -- theta / plant: the
+# per-instance parameter rows (null; a library that also has ntheta > 0: null or the rows), d: the data rows [batch * horizon * nsd], null = the defaults.
+# Every instance of such a library carries a StageData; the plain and the _pp exports above pass a null one
+_DEVICE_SDATA_TMPL = '''int mpcqp_user_nsd() { return SmUser::nsd; }
+void mpcqp_user_sdata0(double *d) { for (int i = 0; i < SmUser::nsd; i++) d[i] = SmUser_sdata0[i]; }
+int mpcqp_user_eval_sd(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
+                       const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream, const double *theta,
+                       const double *d) {
+%(th_eval)s  return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageData{d});
+}
+int mpcqp_user_merit_sd(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream, const double *theta,
+                        const double *d) {
+%(th_merit)s  return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageData{d});
+}
+int mpcqp_user_advance_sd(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream, const double *theta, const double *plant,
+                          const double *d) {
+%(th_advance)s  return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageData{d});
+}
+int mpcqp_user_linesearch_sd(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream, const double *theta, const double *d) {
+%(th_linesearch)s  return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageData{d});
+}
+'''
+# (the same launches with the parameter rows in front, in a library that has both)
+_DEVICE_SDATA_THETA = {
+    "th_eval": "  if (theta) return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n",
+    "th_merit": "  if (theta) return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n",
+    "th_advance": "  if (theta || plant) return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant}, StageData{d});\n",
+    "th_linesearch": "  if (theta) return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n",
+}
 
 _HOST_TMPL = '''// generated by optimal_control_problem_amd/codegen.py -- host build of the same functor, for checks without a GPU
 #include <cmath>
@@ -763,14 +845,14 @@ template <class M> static void host_cost(const double *s, const double *u, const
   if constexpr (M::has_cost != 0) {
     constexpr int nx = M::nx, nu = M::nu, nl = 2 * nx + nu;
     double v[1];
-    if (term) M::template LT<double>(s, u, r, v); else M::template L<double>(s, u, r, v);
+    if (term) M::template LT<double>(s, u, r, %(hd)sv); else M::template L<double>(s, u, r, %(hd)sv);
     val[0] = v[0];
     for (int c = 0; c < nl; c++) {
       Dual sd[nx], ud[nu], rd[nx], gd[nl];
       for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
       for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
       for (int i = 0; i < nx; i++) rd[i] = {r[i], nx + nu + i == c ? 1.0 : 0.0};
-      if (term) M::template LTG<Dual>(sd, ud, rd, gd); else M::template LG<Dual>(sd, ud, rd, gd);
+      if (term) M::template LTG<Dual>(sd, ud, rd, %(hd)sgd); else M::template LG<Dual>(sd, ud, rd, %(hd)sgd);
       for (int i = 0; i < nl; i++) { hess[i * nl + c] = gd[i].d; grad[i] = gd[i].v; }
     }
   }
@@ -826,10 +908,46 @@ void user_host_path(const double *s, const double *u, double *out, double *jac) 
     Dual sd[nx], ud[nu], od[nh > 0 ? nh : 1];
     for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
     for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
-    SmUser::H<Dual>(sd, ud, od);
+    SmUser::H<Dual>(sd, ud, %(hd)sod);
     for (int r = 0; r < nh; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
   }
 }
+%(sdata)s}
+'''
+
+# a functor with stage data only: the path constraint and the cost with a data row d [nsd] given (the exports above use the defaults)
+_HOST_SDATA_TMPL = '''int user_host_nsd() { return SmUser::nsd; }
+void user_host_sdata0(double *d) { for (int i = 0; i < SmUser::nsd; i++) d[i] = SmUser_sdata0[i]; }
+void user_host_path_d(const double *s, const double *u, const double *d, double *out, double *jac) {
+  constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu, nh = SmUser::nh;
+  for (int c = 0; c < f; c++) {
+    Dual sd[nx], ud[nu], od[nh > 0 ? nh : 1];
+    for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
+    for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
+    SmUser::H<Dual>(sd, ud, d, od);
+    for (int r = 0; r < nh; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
+  }
+}
+}
+template <class M> static void host_cost_d(const double *s, const double *u, const double *r, const double *d, int term, double *val, double *grad, double *hess) {
+  if constexpr (M::has_cost != 0) {
+    constexpr int nx = M::nx, nu = M::nu, nl = 2 * nx + nu;
+    double v[1];
+    if (term) M::template LT<double>(s, u, r, d, v); else M::template L<double>(s, u, r, d, v);
+    val[0] = v[0];
+    for (int c = 0; c < nl; c++) {
+      Dual sd[nx], ud[nu], rd[nx], gd[nl];
+      for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
+      for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
+      for (int i = 0; i < nx; i++) rd[i] = {r[i], nx + nu + i == c ? 1.0 : 0.0};
+      if (term) M::template LTG<Dual>(sd, ud, rd, d, gd); else M::template LG<Dual>(sd, ud, rd, d, gd);
+      for (int i = 0; i < nl; i++) { hess[i * nl + c] = gd[i].d; grad[i] = gd[i].v; }
+    }
+  }
+}
+extern "C" {
+void user_host_cost_d(const double *s, const double *u, const double *r, const double *d, int term, double *val, double *grad, double *hess) {
+  host_cost_d<SmUser>(s, u, r, d, term, val, grad, hess);
 }
 '''
 
@@ -892,10 +1010,15 @@ def device_source(tape):
     """the translation unit of a stage library.  Traced with per_frame_reference: SmUser::pref, the PF = true kernel instances only, and the
     export mpcqp_user_pref() by which mpcqp_stage_create_tracking / _create_user tell the two kinds apart; else the text it always was"""
     pf = getattr(tape, "pref", False)
+    nsd, nth = getattr(tape, "nsd", 0), getattr(tape, "ntheta", 0)
     sub = {"pf": ", SmUser::pref" if pf else "", "pfpp": "SmUser::pref" if pf else "false",
-           "pref": "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\n" if pf else ""}
-    return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if getattr(tape, "ntheta", 0) else "",
-                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "")
+           "pref": "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\n" if pf else "",
+           "sdarg": ", StageData{nullptr}" if nsd else ""}      # (a library with stage data: every kernel instance takes a StageData)
+    sdata = ""
+    if nsd:
+        sdata = _DEVICE_SDATA_TMPL % dict(sub, **{k: (v % sub if nth else "") for k, v in _DEVICE_SDATA_THETA.items()})
+    return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if nth else "",
+                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "", sdata=sdata)
 
 
 def build_device_library(tape):
@@ -904,10 +1027,16 @@ def build_device_library(tape):
     return _build(device_source(tape), "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
 
 
+def host_source(tape):
+    """the translation unit of the host build (a functor with stage data: the exports without a data row use the defaults)"""
+    nth, nsd = getattr(tape, "ntheta", 0), getattr(tape, "nsd", 0)
+    return _HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr",
+                         "link_cost": _HOST_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "",
+                         "hd": "SmUser_sdata0, " if nsd else "", "sdata": _HOST_SDATA_TMPL if nsd else ""}
+
+
 def build_host_library(tape):
-    nth = getattr(tape, "ntheta", 0)
-    return _build(_HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr",
-                                "link_cost": _HOST_LINK_COST_TMPL if getattr(tape, "link_cost", None) else ""}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
+    return _build(host_source(tape), "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
 
 
 # ------------------------------------------------------------------------------------------------- general (non-stage) NLPs

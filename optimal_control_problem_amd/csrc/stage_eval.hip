@@ -20,7 +20,9 @@
 
 // The launchers a generated library exports (model == MPCQP_MODEL_USER).  advance and linesearch are optional: a library generated before
 // those entries has none.  The _pp four are the per-instance-parameter launchers of a library with ntheta > 0: the same arguments, then the
-// device rows ([batch * SM_NPAR]; advance takes the model rows and the plant rows, either may be null = the shared values).
+// device rows ([batch * SM_NPAR]; advance takes the model rows and the plant rows, either may be null = the shared values).  The _sd four are the
+// launchers of a library with stage data (nsd > 0): the same arguments, then the parameter rows (null, or the rows of a library that also has
+// ntheta > 0) and the data rows ([batch * horizon * nsd], null = the defaults on every frame).
 struct StageUserLib {
   int (*eval)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *, const double *, double *,
               double *, double *, double *, double *, void *) = nullptr;
@@ -32,7 +34,13 @@ struct StageUserLib {
   int (*merit_pp)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *) = nullptr;
   int (*advance_pp)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *) = nullptr;
   int (*linesearch_pp)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *) = nullptr;
+  int (*eval_sd)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *, const double *, double *,
+                 double *, double *, double *, double *, void *, const double *, const double *) = nullptr;
+  int (*merit_sd)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *, const double *) = nullptr;
+  int (*advance_sd)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *, const double *) = nullptr;
+  int (*linesearch_sd)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *, const double *) = nullptr;
   bool all_pp() const { return eval_pp && merit_pp && advance_pp && linesearch_pp; }
+  bool all_sd() const { return eval_sd && merit_sd && advance_sd && linesearch_sd; }
 };
 template <class Fn> static void stage_sym(void *lib, const char *name, Fn *&fn) { fn = (Fn *)dlsym(lib, name); }
 static StageUserLib stage_user_lib(void *lib) {
@@ -41,6 +49,8 @@ static StageUserLib stage_user_lib(void *lib) {
   stage_sym(lib, "mpcqp_user_advance", u.advance); stage_sym(lib, "mpcqp_user_linesearch", u.linesearch);
   stage_sym(lib, "mpcqp_user_eval_pp", u.eval_pp); stage_sym(lib, "mpcqp_user_merit_pp", u.merit_pp);
   stage_sym(lib, "mpcqp_user_advance_pp", u.advance_pp); stage_sym(lib, "mpcqp_user_linesearch_pp", u.linesearch_pp);
+  stage_sym(lib, "mpcqp_user_eval_sd", u.eval_sd); stage_sym(lib, "mpcqp_user_merit_sd", u.merit_sd);
+  stage_sym(lib, "mpcqp_user_advance_sd", u.advance_sd); stage_sym(lib, "mpcqp_user_linesearch_sd", u.linesearch_sd);
   return u;
 }
 
@@ -69,6 +79,11 @@ struct mpcqp_stage {
   double *dth[2] = {nullptr, nullptr};
   int th_batch[2] = {0, 0}, th_cap[2] = {0, 0};
   const double *theta(int which) const { return th_batch[which] > 0 ? dth[which] : nullptr; }
+  // stage data (mpcqp_stage_set_stage_data): rows [sd_batch * N * nsd] in dsd[sd_cur]; the other buffer takes the next shift (mpcqp_stage_shift_data)
+  int nsd = 0;                        // values per frame the library's hfun / lcost / lterm read (mpcqp_user_nsd); 0: the zoo, a library without
+  double *dsd[2] = {nullptr, nullptr};
+  int sd_cur = 0, sd_batch = 0, sd_cap = 0;
+  const double *sdata() const { return sd_batch > 0 ? dsd[sd_cur] : nullptr; }
 };
 
 // a launch may not be larger than a stored parameter set
@@ -77,6 +92,16 @@ static int stage_theta_batch_ok(const mpcqp_stage *s, int which, int batch) {
     return mpcqp_set_error(MPCQP_ERR_ARG, which == MPCQP_PARAMS_MODEL ? "batch is larger than the stored per-instance model parameters (mpcqp_stage_set_instance_params)"
                                                                       : "batch is larger than the stored per-instance plant parameters (mpcqp_stage_set_instance_params)");
   return MPCQP_OK;
+}
+
+// The receding-horizon hand-over of the stage data (mpcqp_stage_shift_data), out of place: out[b, k, :] = in[b, k + 1, :] for k < N - 1, the last
+// row d_new[b, :] or, without one, in[b, N - 1, :] again.  One thread per element, adjacent threads adjacent elements; one writer per element.
+__global__ void __launch_bounds__(256) stage_shift_data_kernel(int batch, int N, int nsd, const double *__restrict__ in, const double *__restrict__ d_new,
+                                                               double *__restrict__ out) {
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x, per = (long)N * nsd;
+  if (gid >= (long)batch * per) return;
+  const long b = gid / per, r = gid - b * per;
+  out[gid] = r < per - nsd ? in[gid + nsd] : d_new ? d_new[b * nsd + (r - (per - nsd))] : in[gid];
 }
 
 __global__ void __launch_bounds__(256) stage_step_kernel(int batch, int nvar, int n, int np, double alpha, const double *__restrict__ dw,
@@ -104,18 +129,19 @@ hipError_t mpcqp_launch_step(int batch, int nvar, int n, int np, double alpha, c
 }
 
 // The common tail of the four entry points that launch a model's kernel, after their own argument checks: a launch may not be larger than a
-// stored parameter set (plant: advance reads the plant's set too), then one of four launches -- a generated library or the zoo, with the shared
-// parameters or with per-instance rows.  zoo(tag) launches the plain zoo instance of StageTag tag; zoo_pp(th) calls the PP twin in
-// stage_eval_pp.hip; user() and user_pp(th) call the library's exports.
-template <class Zoo, class ZooPP, class User, class UserPP>
-static int stage_launch(mpcqp_stage *s, int batch, bool plant, Zoo zoo, ZooPP zoo_pp, User user, UserPP user_pp) {
+// stored parameter set (plant: advance reads the plant's set too) or than the stored stage data, then one of five launches -- a generated library or the
+// zoo, with the shared parameters or with per-instance rows; a library with stage data always through its _sd exports.  zoo(tag) launches the plain
+// zoo instance of StageTag tag; zoo_pp(th) calls the PP twin in stage_eval_pp.hip; user(), user_pp(th) and user_sd(th, d) call the library's exports.
+template <class Zoo, class ZooPP, class User, class UserPP, class UserSD>
+static int stage_launch(mpcqp_stage *s, int batch, bool plant, Zoo zoo, ZooPP zoo_pp, User user, UserPP user_pp, UserSD user_sd) {
   if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
   if (plant) if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_PLANT, batch)) return rc;
+  if (s->sd_batch > 0 && batch > s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch is larger than the stored stage data (mpcqp_stage_set_stage_data)");
   MPCQP_HIPCHK(hipSetDevice(s->device));
   const StageTheta th{s->theta(MPCQP_PARAMS_MODEL), plant ? s->theta(MPCQP_PARAMS_PLANT) : nullptr};
   const bool pp = th.model || th.plant;
   hipError_t e;
-  if (s->sd.model == MPCQP_MODEL_USER) e = (hipError_t)(pp ? user_pp(th) : user());
+  if (s->sd.model == MPCQP_MODEL_USER) e = (hipError_t)(s->nsd > 0 ? user_sd(th, s->sdata()) : pp ? user_pp(th) : user());
   else e = pp ? zoo_pp(th) : stage_visit_zoo(s->sd.model, s->sd.pref != 0, zoo);
   MPCQP_HIPCHK(e);
   return MPCQP_OK;
@@ -256,6 +282,17 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
     for (int i = 0; i < SM_NPAR; i++) dd.par[i] = 0.0;
     if (nt > 0) t0f(dd.par);
   }
+  // optional export of a library generated with stage data: how many values per frame its hfun / lcost / lterm read; such a library is always
+  // launched through its four _sd exports.  A library without it -- every one generated before this entry -- has none.
+  {
+    auto nsf = (int (*)())dlsym(lib, "mpcqp_user_nsd");
+    const int ns = nsf ? nsf() : 0;
+    if (ns < 0 || ns > SM_MAXSD || (ns > 0 && !user.all_sd())) {
+      mpcqp_stage_destroy(s);
+      return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares stage data but not 0..8 values per frame, or lacks an _sd launcher");
+    }
+    s->nsd = ns;
+  }
   std::vector<unsigned char> mask((size_t)(2 * nx + nu) * (2 * nx + nu));
   auto cf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_cost");
   s->general_cost = cf && cf(mask.data());
@@ -289,6 +326,7 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   if (s->dhlo) (void)hipFree(s->dhlo);
   if (s->dhhi) (void)hipFree(s->dhhi);
   for (int w = 0; w < 2; w++) if (s->dth[w]) (void)hipFree(s->dth[w]);
+  for (int w = 0; w < 2; w++) if (s->dsd[w]) (void)hipFree(s->dsd[w]);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -350,6 +388,45 @@ int mpcqp_stage_set_instance_params(mpcqp_stage *s, int which, int batch, const 
   return MPCQP_OK;
 }
 
+int mpcqp_stage_data_count(const mpcqp_stage *s) { return s ? s->nsd : 0; }
+
+int mpcqp_stage_set_stage_data(mpcqp_stage *s, int batch, const double *d, int mem) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (s->nsd == 0)
+    return mpcqp_set_error(MPCQP_ERR_ARG, s->sd.model == MPCQP_MODEL_USER
+                                              ? "this library was generated without stage data (nsd = 0): the numbers in its constraints and costs are part of the code; declare nsd and sdata on the model and regenerate"
+                                              : "the built-in models take no stage data (mpcqp_stage_data_count is 0)");
+  if (!d) { s->sd_batch = 0; return MPCQP_OK; }      // back to the defaults; the buffers stay for the next call
+  if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return mpcqp_set_error(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const size_t bytes = (size_t)batch * s->sd.N * s->nsd * sizeof(double);
+  if (batch > s->sd_cap) {
+    double *nb[2] = {nullptr, nullptr};
+    MPCQP_HIPCHK(hipMalloc(&nb[0], bytes));
+    if (hipMalloc(&nb[1], bytes) != hipSuccess) { (void)hipFree(nb[0]); return mpcqp_set_error(MPCQP_ERR_HIP, "hipMalloc of the stage data failed"); }
+    MPCQP_HIPCHK(hipDeviceSynchronize());       // a launch that reads the old rows may still be queued
+    for (int w = 0; w < 2; w++) { if (s->dsd[w]) (void)hipFree(s->dsd[w]); s->dsd[w] = nb[w]; }
+    s->sd_cap = batch; s->sd_batch = 0; s->sd_cur = 0;
+  }
+  MPCQP_HIPCHK(hipMemcpy(s->dsd[s->sd_cur], d, bytes, mem == MPCQP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+  s->sd_batch = batch;
+  return MPCQP_OK;
+}
+
+int mpcqp_stage_shift_data(mpcqp_stage *s, int batch, const double *d_new, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (s->nsd == 0) return mpcqp_set_error(MPCQP_ERR_ARG, "this handle takes no stage data (mpcqp_stage_data_count is 0)");
+  if (s->sd_batch == 0) return mpcqp_set_error(MPCQP_ERR_STATE, "no stage data are stored (mpcqp_stage_set_stage_data): the defaults do not shift");
+  if (batch != s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be that of the stored stage data: every stored row shifts");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const long tot = (long)batch * s->sd.N * s->nsd;
+  stage_shift_data_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, (hipStream_t)stream>>>(batch, s->sd.N, s->nsd, s->dsd[s->sd_cur], d_new, s->dsd[1 - s->sd_cur]);
+  MPCQP_HIPCHK(hipGetLastError());
+  s->sd_cur = 1 - s->sd_cur;
+  return MPCQP_OK;
+}
+
 int mpcqp_stage_dims(const mpcqp_stage *s, int *o) {
   if (!s || !o) return mpcqp_set_error(MPCQP_ERR_ARG, "null argument");
   const StageDev &d = s->sd;
@@ -379,7 +456,8 @@ int mpcqp_stage_eval(mpcqp_stage *s, int batch, const double *p, const double *x
       [&](auto t) { using T = decltype(t); return stage_launch_eval<typename T::M, T::PF>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); },
       [&](StageTheta th) { return mpcqp_launch_eval_pp(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st, th); },
       [&] { return s->user.eval(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream); },
-      [&](StageTheta th) { return s->user.eval_pp(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th.model); });
+      [&](StageTheta th) { return s->user.eval_pp(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th.model); },
+      [&](StageTheta th, const double *d) { return s->user.eval_sd(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th.model, d); });
 }
 
 int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
@@ -391,7 +469,8 @@ int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *
       [&](auto t) { using T = decltype(t); return stage_launch_merit<typename T::M, T::PF>(sd, batch, p, x, f, gmax, st); },
       [&](StageTheta th) { return mpcqp_launch_merit_pp(sd, batch, p, x, f, gmax, st, th); },
       [&] { return s->user.merit(&sd, batch, p, x, f, gmax, stream); },
-      [&](StageTheta th) { return s->user.merit_pp(&sd, batch, p, x, f, gmax, stream, th.model); });
+      [&](StageTheta th) { return s->user.merit_pp(&sd, batch, p, x, f, gmax, stream, th.model); },
+      [&](StageTheta th, const double *d) { return s->user.merit_sd(&sd, batch, p, x, f, gmax, stream, th.model, d); });
 }
 
 int mpcqp_stage_step(mpcqp_stage *s, int batch, double alpha, const double *dw, double *x, double *step_max, const int *status, void *stream) {
@@ -430,7 +509,8 @@ int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_arg
       [&](auto t) { using T = decltype(t); return stage_launch_advance<typename T::M, T::PF>(sd, batch, *a, st); },
       [&](StageTheta th) { return mpcqp_launch_advance_pp(sd, batch, *a, st, th); },
       [&] { return s->user.advance(&sd, batch, a, stream); },
-      [&](StageTheta th) { return s->user.advance_pp(&sd, batch, a, stream, th.model, th.plant); });
+      [&](StageTheta th) { return s->user.advance_pp(&sd, batch, a, stream, th.model, th.plant); },
+      [&](StageTheta th, const double *d) { return s->user.advance_sd(&sd, batch, a, stream, th.model, th.plant, d); });
 }
 
 int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
@@ -452,7 +532,8 @@ int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesear
       [&](auto t) { using T = decltype(t); return stage_launch_linesearch<typename T::M, T::PF>(sd, batch, *a, st); },
       [&](StageTheta th) { return mpcqp_launch_linesearch_pp(sd, batch, *a, st, th); },
       [&] { return s->user.linesearch(&sd, batch, a, stream); },
-      [&](StageTheta th) { return s->user.linesearch_pp(&sd, batch, a, stream, th.model); });
+      [&](StageTheta th) { return s->user.linesearch_pp(&sd, batch, a, stream, th.model); },
+      [&](StageTheta th, const double *d) { return s->user.linesearch_sd(&sd, batch, a, stream, th.model, d); });
 }
 
 }  // extern "C"

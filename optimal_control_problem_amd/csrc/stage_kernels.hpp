@@ -29,17 +29,52 @@ struct StageDev {
 // advance uses; a null set stands for the shared values sd.par.  The PP instances of the four kernels below take one StageTheta as an extra,
 // last argument -- the template's trailing pack PP is empty or {StageTheta}, so the instances without it keep their signature and their code.
 struct StageTheta { const double *model, *plant; };
-__device__ __forceinline__ StageTheta stage_theta() { return {nullptr, nullptr}; }
-__device__ __forceinline__ StageTheta stage_theta(StageTheta t) { return t; }
+// SD (stage data, mpcqp_stage_set_stage_data): rows of M::nsd doubles, frame k of instance b at [(b * N + k) * nsd] -- values the generated hfun,
+// lcost and lterm read as d[i] (an obstacle's centre, a scheduled weight): data, not variables, no derivative is taken with respect to them.  A null
+// pointer stands for the defaults M::sdata0 on every frame.  The SD instances take one StageData as the last argument, behind the StageTheta of
+// a PP instance: the trailing pack is {}, {StageTheta}, {StageData} or {StageTheta, StageData}, and an instance without an element keeps its
+// signature and its code.  Generated functors only: the zoo declares no nsd.
+struct StageData { const double *d; };
+constexpr int SM_MAXSD = 8;
+template <class T, class... PP> inline constexpr bool stage_has = (std::is_same_v<T, PP> || ...);
+// the pack's element of type T, or a null one
+template <class T> __device__ __forceinline__ T stage_get() { return T{}; }
+template <class T, class A, class... R> __device__ __forceinline__ T stage_get(A a, R... r) {
+  if constexpr (std::is_same_v<T, A>) return a; else return stage_get<T>(r...);
+}
+template <class... PP> __device__ __forceinline__ StageTheta stage_theta(PP... pp) { return stage_get<StageTheta>(pp...); }
 // how many entries of a parameter row the functor reads (M::ntheta; functors without the member read none)
 template <class M, class = void> struct sm_ntheta : std::integral_constant<int, 0> {};
 template <class M> struct sm_ntheta<M, std::void_t<decltype(M::ntheta)>> : std::integral_constant<int, M::ntheta> {};
+// how many stage-data values per frame the functor reads (M::nsd; functors without the member read none and keep the signatures without d)
+template <class M, class = void> struct sm_nsd : std::integral_constant<int, 0> {};
+template <class M> struct sm_nsd<M, std::void_t<decltype(M::nsd)>> : std::integral_constant<int, M::nsd> {};
+template <class M> inline constexpr int sm_nsd_regs = sm_nsd<M>::value > 0 ? sm_nsd<M>::value : 1;
+// frame k's row of instance b into registers (a functor without stage data: nothing)
+template <class M, class... PP> __device__ __forceinline__ void stage_load_data(double (&dv)[sm_nsd_regs<M>], int b, int N, int k, PP... pp) {
+  if constexpr (sm_nsd<M>::value > 0) {
+    constexpr int nsd = sm_nsd<M>::value;
+    const double *dp = stage_get<StageData>(pp...).d;
+    if (dp) dp += ((long)b * N + k) * nsd;
+#pragma unroll
+    for (int i = 0; i < nsd; i++) dv[i] = dp ? dp[i] : M::sdata0[i];
+  }
+}
+// H, and the generated gradient of the frame cost (the last frame the terminal one's), of a functor with or without stage data
+template <class M, class T> __device__ __forceinline__ void stage_path(const T *s, const T *u, const double *d, T *out) {
+  if constexpr (sm_nsd<M>::value > 0) M::template H<T>(s, u, d, out); else M::template H<T>(s, u, out);
+}
+template <class M, class T> __device__ __forceinline__ void stage_cost_grad(bool last, const T *s, const T *u, const T *r, const double *d, T *out) {
+  if constexpr (sm_nsd<M>::value > 0) { if (M::has_term && last) M::template LTG<T>(s, u, r, d, out); else M::template LG<T>(s, u, r, d, out); }
+  else { if (M::has_term && last) M::template LTG<T>(s, u, r, out); else M::template LG<T>(s, u, r, out); }
+}
 
 // the QP returned a point (solved, solved inaccurately, or stopped at the iteration limit): its dw, y may be used
 __device__ __forceinline__ bool stage_status_ok(int s) { return s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
 // the generated stage cost (M::has_cost); the last frame takes the terminal one where the model has it
-template <class M, class T> __device__ __forceinline__ void stage_cost_value(bool last, const T *s, const T *u, const T *r, T *out) {
-  if (M::has_term && last) M::template LT<T>(s, u, r, out); else M::template L<T>(s, u, r, out);
+template <class M, class T> __device__ __forceinline__ void stage_cost_value(bool last, const T *s, const T *u, const T *r, const double *d, T *out) {
+  if constexpr (sm_nsd<M>::value > 0) { if (M::has_term && last) M::template LT<T>(s, u, r, d, out); else M::template L<T>(s, u, r, d, out); }
+  else { if (M::has_term && last) M::template LT<T>(s, u, r, out); else M::template L<T>(s, u, r, out); }
 }
 
 // PF (per-frame references, StageDev::pref): the parameter block holds one reference state per frame.  Parameter column j = k nx + i is thread j of
@@ -51,7 +86,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
                                                          const double *__restrict__ lbg, const double *__restrict__ ubg,
                                                          double *__restrict__ P, double *__restrict__ q, double *__restrict__ A,
                                                          double *__restrict__ l, double *__restrict__ u, PP... pp) {
-  constexpr bool HASPP = sizeof...(PP) > 0;
+  constexpr bool HASPP = stage_has<StageTheta, PP...>;
   constexpr int NT = sm_ntheta<M>::value > 0 ? sm_ntheta<M>::value : 1;
   constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
   // cooperative functors (sm_has_coop): the f lanes of a stage sit in one wave at a multiple of f -- the parameter columns get a group of f thread
@@ -90,11 +125,13 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
         constexpr int nl = f + nx;
         const unsigned char *mk = sd.hmask + f + i;
         Dual s[nx], uu[nu], rr[nx], g[nl];
+        double dv[sm_nsd_regs<M>];
+        stage_load_data<M>(dv, b, N, k, pp...);
 #pragma unroll
         for (int a = 0; a < nx; a++) { s[a] = {fr[a], 0.0}; rr[a] = {rk[a], a == i ? 1.0 : 0.0}; }
 #pragma unroll
         for (int a = 0; a < nu; a++) uu[a] = {fr[nx + a], 0.0};
-        if (M::has_term && k == N - 1) M::template LTG<Dual>(s, uu, rr, g); else M::template LG<Dual>(s, uu, rr, g);
+        stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
         int e = 0;
         double gv = 0.0;
 #pragma unroll
@@ -125,15 +162,17 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
 #pragma unroll
       for (int r = 0; r < nx; r++) acc[r] = 0.0;
       Dual s[nx], uu[nu], rr[nx], g[nl];
+      double dv[sm_nsd_regs<M>];
 #pragma unroll
       for (int i = 0; i < nx; i++) rr[i] = {pb[i], i == j ? 1.0 : 0.0};
       for (int k = 0; k < N; k++) {
         const double *fr = xb + k * f;
+        stage_load_data<M>(dv, b, N, k, pp...);
 #pragma unroll
         for (int i = 0; i < nx; i++) s[i] = {fr[i], 0.0};
 #pragma unroll
         for (int i = 0; i < nu; i++) uu[i] = {fr[nx + i], 0.0};
-        if (M::has_term && k == N - 1) M::template LTG<Dual>(s, uu, rr, g); else M::template LG<Dual>(s, uu, rr, g);
+        stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
         double gv = 0.0;
 #pragma unroll
         for (int r = 0; r < nx; r++) { acc[r] += g[f + r].d; gv = r == j ? g[f + r].v : gv; }
@@ -166,6 +205,9 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
   const double *fr = xb + k * f;
   if constexpr (PF) pb += k * nx;               // frame k's reference r_k stands where p stood
   const double xv = fr[c];
+  // SD: the f lanes of a frame read the same row, once, into registers: hfun and the frame cost below take it from there
+  double dv[sm_nsd_regs<M>];
+  stage_load_data<M>(dv, b, N, k, pp...);
   Dual s[nx], uu[nu];
 #pragma unroll
   for (int i = 0; i < nx; i++) s[i] = {fr[i], i == c ? 1.0 : 0.0};
@@ -190,7 +232,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
       Dual rr[nx], g[nl];
 #pragma unroll
       for (int i = 0; i < nx; i++) rr[i] = {pb[i], 0.0};
-      if (M::has_term && k == N - 1) M::template LTG<Dual>(s, uu, rr, g); else M::template LG<Dual>(s, uu, rr, g);
+      stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
 #pragma unroll
       for (int i = 0; i < nx; i++) if (mk[(f + i) * nl]) Pc[e++] = g[f + i].d;
       gv = 0.0; bbase = 0u;
@@ -261,7 +303,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
     Dual rr[nx], g[nl];
 #pragma unroll
     for (int i = 0; i < nx; i++) rr[i] = {pb[i], 0.0};
-    if (M::has_term && k == N - 1) M::template LTG<Dual>(s, uu, rr, g); else M::template LG<Dual>(s, uu, rr, g);
+    stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
     int e = 0;
     double gv = 0.0;
 #pragma unroll
@@ -301,7 +343,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
     // path constraint rows of this frame: column c of +dh/d[s; u]; lane c < nh also owns the shifted bounds of row h_k[c]
     constexpr int nh = M::nh;
     Dual hv[nh];
-    M::template H<Dual>(s, uu, hv);
+    stage_path<M, Dual>(s, uu, dv, hv);
 #pragma unroll
     for (int r = 0; r < nh; r++) Ac[a + r] = hv[r].d;
     a += nh;
@@ -360,7 +402,7 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
   // PP: b is the same on every lane of the wave, which the compiler cannot see through threadIdx.x >> 6; said so, the row's address is
   // scalar, its entries arrive by scalar loads and F sees a uniform pointer, as it does with sd.par
   const double *par = sd.par;
-  if constexpr (sizeof...(PP) > 0) par = stage_theta(pp...).model + (long)__builtin_amdgcn_readfirstlane(b) * SM_NPAR;
+  if constexpr (stage_has<StageTheta, PP...>) par = stage_theta(pp...).model + (long)__builtin_amdgcn_readfirstlane(b) * SM_NPAR;
   const double *pb0 = p + (long)b * (PF ? sd.N * nx : nx), *xb = x + (long)b * sd.nvar;
   double cost = 0.0, gmax = 0.0;
   for (int k = lane; k < sd.N; k += 64) {
@@ -370,11 +412,13 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
     for (int i = 0; i < nx; i++) s[i] = fr[i];
 #pragma unroll
     for (int i = 0; i < nu; i++) uu[i] = fr[nx + i];
+    double dv[sm_nsd_regs<M>];      // SD: lane k reads row k
+    stage_load_data<M>(dv, b, sd.N, k, pp...);
     if constexpr (M::has_cost) {
       double rr[nx], lv[1];
 #pragma unroll
       for (int i = 0; i < nx; i++) rr[i] = pb[i];
-      stage_cost_value<M, double>(k == sd.N - 1, s, uu, rr, lv);
+      stage_cost_value<M, double>(k == sd.N - 1, s, uu, rr, dv, lv);
       cost += lv[0];
     } else {
 #pragma unroll
@@ -402,7 +446,7 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
     }
     if constexpr (M::nh > 0) {
       double hv[M::nh];
-      M::template H<double>(s, uu, hv);
+      stage_path<M, double>(s, uu, dv, hv);
 #pragma unroll
       for (int i = 0; i < M::nh; i++) {
         const double lo = sd.h_lok ? sd.h_lok[k * M::nh + i] : sd.h_lo[i], hi = sd.h_hik ? sd.h_hik[k * M::nh + i] : sd.h_hi[i];
@@ -463,7 +507,7 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
     for (int i = 0; i < nx; i++) s[i] = fr[i];
 #pragma unroll
     for (int i = 0; i < nu; i++) uu[i] = fr[nx + i];
-    if constexpr (sizeof...(PP) > 0) {
+    if constexpr (stage_has<StageTheta, PP...>) {
       // PP: the plant step (lane 0) takes the plant row, or the model row when no plant set is stored; the rollout tail (lane 1) the model
       // row; a set that is not stored stands for sd.par.  Values, not addresses, are selected: sd.par stays in its scalar registers
       constexpr int NT = sm_ntheta<M>::value > 0 ? sm_ntheta<M>::value : 1;
@@ -484,7 +528,9 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
         double rr[nx], lv[1];
 #pragma unroll
         for (int i = 0; i < nx; i++) rr[i] = pb[i];
-        M::template L<double>(s, uu, rr, lv);
+        double dv[sm_nsd_regs<M>];      // SD: the k = 0 term takes d_0, the row before any shift
+        stage_load_data<M>(dv, b, N, 0, pp...);
+        stage_cost_value<M, double>(false, s, uu, rr, dv, lv);
         cost += lv[0];
       } else {
 #pragma unroll
@@ -567,7 +613,7 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
   const int lane = threadIdx.x & 63, b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (b >= batch) return;
   const double *par = sd.par;      // PP: the instance's row through a wave-uniform b, as in stage_merit_kernel
-  if constexpr (sizeof...(PP) > 0) par = stage_theta(pp...).model + (long)__builtin_amdgcn_readfirstlane(b) * SM_NPAR;
+  if constexpr (stage_has<StageTheta, PP...>) par = stage_theta(pp...).model + (long)__builtin_amdgcn_readfirstlane(b) * SM_NPAR;
   const int N = sd.N, nvar = sd.nvar, np = sd.np;
   bool ok = true;
   if (a.status) ok = stage_status_ok(a.status[b]);
@@ -591,12 +637,14 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
 #pragma unroll
     for (int i = 0; i < nu; i++) { uu[i] = fr[nx + i]; if (c > 0) uu[i] += ac * dfr[nx + i]; }
     double lc = 0.0, lv = 0.0, lg = 0.0;
+    double dv[sm_nsd_regs<M>];      // SD: frame k's row (an item is one frame at one candidate)
+    stage_load_data<M>(dv, b, N, k, pp...);
     // the objective and the max-norm violation exactly as stage_merit_kernel forms them, the l1 violation next to the latter
     if constexpr (M::has_cost) {
       double rr[nx], lval[1];
 #pragma unroll
       for (int i = 0; i < nx; i++) rr[i] = pb[i];
-      stage_cost_value<M, double>(k == N - 1, s, uu, rr, lval);
+      stage_cost_value<M, double>(k == N - 1, s, uu, rr, dv, lval);
       lc += lval[0];
     } else {
 #pragma unroll
@@ -629,7 +677,7 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
     }
     if constexpr (M::nh > 0) {
       double hv[M::nh];
-      M::template H<double>(s, uu, hv);
+      stage_path<M, double>(s, uu, dv, hv);
 #pragma unroll
       for (int i = 0; i < M::nh; i++) {
         const double lo = sd.h_lok ? sd.h_lok[k * M::nh + i] : sd.h_lo[i], hi = sd.h_hik ? sd.h_hik[k * M::nh + i] : sd.h_hi[i];
@@ -719,7 +767,7 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
 }
 
 // launchers shared by the zoo dispatch and generated libraries
-// (PP: empty, or one StageTheta behind the stream -- the per-instance-parameter instances)
+// (PP: empty, or a StageTheta and / or a StageData behind the stream -- the per-instance-parameter and the stage-data instances)
 template <class M, bool PF = false, class... PP>
 inline hipError_t stage_launch_eval(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                                     const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st,

@@ -212,6 +212,56 @@ class StageOCP:
     NTHETA_MAX = 8
     _theta_rows = None; _plant_rows = None
 
+    # opt-in stage data: a model declares nsd = k <= 8 and sdata = np.array([...]) (the defaults) and reads self.sdata[i] inside hfun, lcost and
+    # lterm (not in F / cdyn, kfun, llink; a cost that reads it is a method, not a staticmethod).  The values are data of the world -- an obstacle's
+    # centre, a corridor's width, a scheduled weight -- not variables: no column, row or entry of P or A comes with them.  set_stage_data gives
+    # every frame of every instance its own row: a batch of different worlds.  In the reference the parameter SX may appear in any
+    # constraint or cost (src/OptimalControlProblem.cpp:444-497).
+    nsd = 0; sdata = None
+    NSD_MAX = 8
+    _sdata_rows = None
+
+    def set_stage_data(self, d=None):
+        """Host statement of mpcqp_stage_set_stage_data.  d [B, N, nsd]: frame k of instance b takes row d[b, k] in hfun, lcost and lterm -- in
+        path_values, dh, constraints, objective, cost_derivatives, local_system, violation, line_search and the stage_cost of advance (d[b, 0]).
+        None returns to the defaults self.sdata on every frame.  A call with more instances than rows is a ValueError, a smaller batch uses the
+        first rows.  With nothing set every method returns the bits it always did."""
+        if d is not None:
+            if self.nsd == 0:
+                raise ValueError("this model has no stage data (nsd = 0)")
+            d = np.array(d, float)
+            if d.ndim != 3 or d.shape[0] < 1 or d.shape[1:] != (self.N, self.nsd):
+                raise ValueError("d: expected an array [B, %d, %d], got %s" % (self.N, self.nsd, d.shape))
+        self._sdata_rows = d
+
+    def shift_stage_data(self, d_new=None):
+        """Host statement of mpcqp_stage_shift_data: row (b, k) becomes row (b, k + 1), the last row d_new [B, nsd] or, without one, the old
+        last row again.  The data describe the world: they shift whatever the QP's status was."""
+        if self._sdata_rows is None:
+            raise ValueError("no stage data are stored (set_stage_data): the defaults do not shift")
+        d = self._sdata_rows
+        last = d[:, -1:] if d_new is None else np.asarray(d_new, float).reshape(d.shape[0], 1, self.nsd)
+        self._sdata_rows = np.concatenate([d[:, 1:], last], axis=1)
+
+    def _stage_data(self, B):
+        """[B, N, nsd]: the rows in force for a batch of B instances"""
+        if self._sdata_rows is None:
+            return np.broadcast_to(np.asarray(self.sdata, float), (B, self.N, self.nsd))
+        if self._sdata_rows.shape[0] < B:
+            raise ValueError("batch %d is larger than the stored stage data (%d instances)" % (B, self._sdata_rows.shape[0]))
+        return self._sdata_rows[:B]
+
+    def _hfun(self, s, u, rows=None):
+        """hfun on frames [B, N, .] (rows: a frame subset of the data, [B, n, nsd]) with self.sdata[i] = the [B, N] values of the rows in force"""
+        if self.nsd == 0:
+            return self.hfun(s, u)
+        saved = self.sdata
+        try:
+            self.sdata = np.moveaxis(self._stage_data(s.shape[0]) if rows is None else rows, -1, 0)
+            return self.hfun(s, u)
+        finally:
+            self.sdata = saved
+
     def set_instance_params(self, theta=None, plant=None):
         """Host statement of mpcqp_stage_set_instance_params.  theta [B, ntheta]: instance b's parameters, what local_system, objective,
         constraints, violation, line_search and the rollout tail of advance use; plant [B, ntheta]: what the plant step of advance uses (unset:
@@ -234,20 +284,30 @@ class StageOCP:
         if rows.shape[0] < B:
             raise ValueError("batch %d is larger than the stored per-instance parameters (%d rows)" % (B, rows.shape[0]))
         saved = (np.array(self.theta, float), self._theta_rows, self._plant_rows)
+        data = self._sdata_rows
+        if data is not None and data.shape[0] < B:
+            raise ValueError("batch %d is larger than the stored stage data (%d instances)" % (B, data.shape[0]))
         out = []
         try:
             self._theta_rows = self._plant_rows = None
             for b in range(B):
                 self.theta = rows[b].copy()
+                if data is not None:
+                    self._sdata_rows = data[b:b + 1]      # the one-instance call sees its own stage data
                 out.append(fn(slice(b, b + 1)))
         finally:
             self.theta, self._theta_rows, self._plant_rows = saved
+            self._sdata_rows = data
         return out
 
     def __init__(self, N, dt, Q, R):
         self.N, self.dt = int(N), float(dt)
         if self.ntheta > self.NTHETA_MAX:
             raise ValueError("a model may declare at most %d parameters (ntheta = %d)" % (self.NTHETA_MAX, self.ntheta))
+        if self.nsd > self.NSD_MAX:
+            raise ValueError("a model may declare at most %d stage-data values (nsd = %d)" % (self.NSD_MAX, self.nsd))
+        if self.nsd and np.size(self.sdata) != self.nsd:
+            raise ValueError("sdata must hold the nsd = %d default values" % self.nsd)
         # diagonal weights, the same for every frame ([nx], [nu]) or one row per frame ([N, nx], [N, nu]: terminal costs,
         # ramps) -- addVectorCost is called per step in the reference (readme.md:121-128), so weights may differ by step
         self.Q = np.asarray(Q, float); self.R = np.asarray(R, float)
@@ -264,11 +324,12 @@ class StageOCP:
         self.general_cost = self.lcost is not None
         if self.general_cost:
             from . import codegen
-            self._ltape, self._gtape = codegen.trace_cost(self.lcost, self.nx, self.nu, self.nx)
+            dkw = {"nsd": self.nsd, "model": self} if self.nsd else {}
+            self._ltape, self._gtape = codegen.trace_cost(self.lcost, self.nx, self.nu, self.nx, **dkw)
             mask = codegen.hessian_mask(self._gtape)
             self._lttape = self._gttape = None
             if self.lterm is not None:
-                self._lttape, self._gttape = codegen.trace_cost(self.lterm, self.nx, self.nu, self.nx)
+                self._lttape, self._gttape = codegen.trace_cost(self.lterm, self.nx, self.nu, self.nx, **dkw)
                 mask = mask | codegen.hessian_mask(self._gttape)
             self.cost_mask = mask | np.eye(mask.shape[0], dtype=bool)
         self.link_cost = self.llink is not None
@@ -411,7 +472,11 @@ class StageOCP:
     def _cost_inputs(self, p, x):
         s, u = self.frames(x)
         r = p.reshape(s.shape) if self.pref else np.broadcast_to(p[:, None, :], s.shape)
-        return [s[..., i] for i in range(self.nx)] + [u[..., i] for i in range(self.nu)] + [r[..., i] for i in range(self.nx)]
+        ins = [s[..., i] for i in range(self.nx)] + [u[..., i] for i in range(self.nu)] + [r[..., i] for i in range(self.nx)]
+        if self.nsd:       # the frames' stage data behind [s; u; r]: inputs of the tapes without a derivative
+            d = self._stage_data(x.shape[0])
+            ins += [d[..., i] for i in range(self.nsd)]
+        return ins
 
     def _cost_eval(self, tape, ttape, inputs):
         """outputs of tape on every frame [B, N], the last frame taken from ttape when there is a terminal cost"""
@@ -426,7 +491,7 @@ class StageOCP:
         """(grad [B, N, nl], hess [B, N, nl, nl]) of the stage cost on every frame over [s; u; r]: gradient tape evaluated
         directly, Hessian columns by complex-step differentiation of the gradient tape (exact to rounding)"""
         inputs = self._cost_inputs(p, x)
-        nl = len(inputs); B, N = inputs[0].shape
+        nl = len(inputs) - self.nsd; B, N = inputs[0].shape
         grad = np.stack(self._cost_eval(self._gtape, self._gttape, inputs), axis=-1)
         hess = np.zeros((B, N, nl, nl)); eps = 1e-30
         for c in range(nl):
@@ -508,17 +573,17 @@ class StageOCP:
         return grad, hess
 
     def dh(self, s, u):
-        """[..., nh, f] Jacobian of hfun wrt [s; u] by complex-step differentiation"""
+        """[..., nh, f] Jacobian of hfun wrt [s; u] by complex-step differentiation (a model with stage data: s, u are all frames [B, N, .])"""
         eps = 1e-30
         out = np.empty(s.shape[:-1] + (self.nh, self.f))
         sc = s.astype(complex); uc = u.astype(complex)
         for c in range(self.f):
             if c < self.nx:
                 sp = sc.copy(); sp[..., c] += 1j * eps
-                out[..., :, c] = np.asarray(self.hfun(sp, uc)).imag / eps
+                out[..., :, c] = np.asarray(self._hfun(sp, uc)).imag / eps
             else:
                 up = uc.copy(); up[..., c - self.nx] += 1j * eps
-                out[..., :, c] = np.asarray(self.hfun(sc, up)).imag / eps
+                out[..., :, c] = np.asarray(self._hfun(sc, up)).imag / eps
         return out
 
     def constraints(self, x):
@@ -530,7 +595,7 @@ class StageOCP:
 
     def path_values(self, x):
         s, u = self.frames(x)
-        return np.asarray(self.hfun(s, u)).reshape(x.shape[0], -1)
+        return np.asarray(self._hfun(s, u)).reshape(x.shape[0], -1)
 
     def local_system(self, p, x, lbx, ubx, lbg, ubg):
         if self._theta_rows is not None:
@@ -579,7 +644,7 @@ class StageOCP:
         g = (s[:, 1:, :] - self.F(s[:, :-1, :], u[:, :-1, :])).reshape(B, -1)
         if self.nh:
             A[:, self._A_h.ravel()] = self.dh(s, u).reshape(B, -1)
-            g = np.concatenate([g, np.asarray(self.hfun(s, u)).reshape(B, -1)], axis=1)
+            g = np.concatenate([g, np.asarray(self._hfun(s, u)).reshape(B, -1)], axis=1)
         if self.nk:
             Jk = self.dk(s[:, :-1], u[:, :-1], s[:, 1:], u[:, 1:])          # [B, N-1, nk, 2 f]
             A[:, self._A_k0.ravel()] = Jk[..., :f].reshape(B, -1)
@@ -680,6 +745,9 @@ class StageOCP:
             s0, u0 = X[:, 0, :nx], X[:, 0, nx:]
             if self.general_cost:
                 ins = [s0[:, i] for i in range(nx)] + [u0[:, i] for i in range(self.nu)] + [r0[:, i] for i in range(nx)]
+                if self.nsd:       # the k = 0 term takes d_0, the row before any shift
+                    d0 = self._stage_data(B)[:, 0]
+                    ins += [d0[:, i] for i in range(self.nsd)]
                 out["stage_cost"] = np.broadcast_to(np.asarray(self._ltape.evaluate(ins)[0], float), (B,)).copy()
             else:
                 c = np.zeros(B)

@@ -8,7 +8,7 @@ state never leave the device; x, dw, y and p are double-buffered because the shi
 
 shift=False keeps the reference's hand-over for comparison: result_ persists (SQPOptimizationSolver.cpp:88-91, OptimalControlProblem.cpp:113), so
 the next tick starts from the previous trajectory unshifted and the duals of stage k are offered to stage k; only the first frame is re-pinned.
-The references still move by one frame per tick -- they are data about the world, not a warm start."""
+The references still move by one frame per tick -- they are data about the world, not a warm start -- and so do the stage data (set_stage_data)."""
 import numpy as np
 
 from .sqp import DeviceSQPOptimizationSolver
@@ -36,6 +36,7 @@ class ClosedLoopMPC:
         self.applied = mk(B, ev.nx + ev.nu); self.stage_cost = mk(B)
         self.ticks = 0
         self._ready = False
+        self._has_data = False
 
     def reset(self, frame0, reference=None, x0=None):
         """frame0 [B, f] (or [f]): the measured state and the input being applied, pinned as the first frame.  reference: p, [B, nx] -- or
@@ -62,6 +63,15 @@ class ClosedLoopMPC:
         self.ev.set_instance_params(model, plant=False)
         self.ev.set_instance_params(plant, plant=True)
 
+    def set_stage_data(self, d):
+        """different worlds: one row of stage data per frame and instance, [batch, horizon, nsd] (NumPy or CUDA tensor) -- what the model's hfun,
+        lcost and lterm read as self.sdata (an obstacle's predicted path, a scheduled weight).  Every tick moves the stored set up by one frame
+        after the hand-over (tick's d_new enters at the end of the horizon).  None returns to the model's defaults, which do not move."""
+        if d is not None and int(np.shape(d)[0]) != self.batch:
+            raise ValueError("expected %d instances" % self.batch)
+        self.ev.set_stage_data(d)
+        self._has_data = d is not None
+
     @property
     def x(self):
         """the trajectory the next tick starts from [B, N f] (device)"""
@@ -70,10 +80,11 @@ class ClosedLoopMPC:
     def _arr(self, a, w):
         return None if a is None else self.sol._dev(a, w)
 
-    def tick(self, measured=None, disturbance=None, r_new=None):
+    def tick(self, measured=None, disturbance=None, r_new=None, d_new=None):
         """solve at the pinned first frame, then hand over.  measured [B, nx]: the plant's state after this tick (a real plant); without it
         the model's own map is applied on the device, plus `disturbance` [B, nx] when given.  r_new [B, nx]: the reference entering the
-        horizon (per_frame_reference models; omitted: the last one repeats).  Returns device tensors, overwritten by the next tick:
+        horizon (per_frame_reference models; omitted: the last one repeats).  d_new [B, nsd]: the stage-data row entering the horizon (a stored
+        set only; omitted: the last row repeats); the set shifts with shift=False as well, like the references.  Returns device tensors, overwritten by the next tick:
         applied [B, f] (the frame that was applied), status, iters [B] of the tick's last QP, stage_cost [B] (the k = 0 cost term)."""
         import torch
         if not self._ready:
@@ -81,6 +92,8 @@ class ClosedLoopMPC:
         sol, ev = self.sol, self.ev
         if r_new is not None and not ev.per_frame_reference:
             raise ValueError("r_new belongs to per_frame_reference models")
+        if d_new is not None and not self._has_data:
+            raise ValueError("d_new needs a stored set of stage data (set_stage_data)")
         sol.getOptimalSolution({"p": self.p, "lbx": self.lbx, "ubx": self.ubx, "lbg": self.lbg, "ubg": self.ubg}, to_host=False)
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         pf = ev.per_frame_reference
@@ -89,6 +102,8 @@ class ClosedLoopMPC:
                    tail=self.tail, p=None if pf else self.p, p_in=self.p if pf else None, p_out=self._p2, r_new=self._arr(r_new, ev.nx) if pf else None,
                    dw_in=sol.dw if moved else None, dw_out=self._dw2 if moved else None, y_in=sol.y if moved else None,
                    y_out=self._y2 if moved else None, applied=self.applied, stage_cost=self.stage_cost, stream=stream)
+        if self._has_data:       # after advance, whose stage_cost log still took d_0
+            ev.shift_stage_data(self._arr(d_new, ev.nsd), stream=stream)
         if pf:
             self.p, self._p2 = self._p2, self.p
         if self.shift:

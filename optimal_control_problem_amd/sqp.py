@@ -262,6 +262,15 @@ class DeviceSQPOptimizationSolver:
             raise ValueError("theta: expected %d rows, one per instance" % self.batch)
         self.ev.set_instance_params(theta)
 
+    def setStageData(self, d):
+        """extension: one row of stage data per frame and instance, [batch, horizon, nsd] (NumPy or CUDA tensor), for every evaluation of the loop
+        (StageEvaluator.set_stage_data); None returns to the model's defaults.  Stage OCPs only."""
+        if not hasattr(self.ev, "set_stage_data"):
+            raise ValueError("stage data are limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has none")
+        if d is not None and int(np.shape(d)[0]) != self.batch:
+            raise ValueError("d: expected %d instances" % self.batch)
+        self.ev.set_stage_data(d)
+
     def _dev(self, a, w):
         import torch
         if isinstance(a, torch.Tensor):

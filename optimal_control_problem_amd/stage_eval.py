@@ -50,6 +50,9 @@ def _bind(L):
     L.mpcqp_stage_set_path_bounds.argtypes = [vp, dp, dp]
     L.mpcqp_stage_param_count.argtypes = [vp]
     L.mpcqp_stage_set_instance_params.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int]
+    L.mpcqp_stage_data_count.argtypes = [vp]
+    L.mpcqp_stage_set_stage_data.argtypes = [vp, C.c_int, dp, C.c_int]
+    L.mpcqp_stage_shift_data.argtypes = [vp, C.c_int, dp, vp]
     L.mpcqp_stage_dims.argtypes = [vp, vp]
     L.mpcqp_stage_has_cost.argtypes = [vp]
     L.mpcqp_stage_has_link_cost.argtypes = [vp]
@@ -128,6 +131,10 @@ class StageEvaluator:
                 # path (a path / link constraint, a general cost), keep their constants in the code as before: no parameters on that handle
                 nth = 0 if isinstance(model, (_m.Quadrotor, _m.CartPole)) else int(getattr(model, "ntheta", 0))
                 pkw = {"ntheta": nth, "theta0": model.theta, "model": model} if nth else {}
+                # a model that declares stage data (nsd, sdata) keeps them as data of the generated hfun / lcost / lterm
+                nsd = int(getattr(model, "nsd", 0))
+                if nsd:
+                    pkw = dict(pkw, nsd=nsd, sdata0=model.sdata, model=model)
                 self.tape = cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
                                      lcost=model.lcost if general else None, lterm=model.lterm if general else None,
                                      kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
@@ -160,6 +167,9 @@ class StageEvaluator:
         self.general_cost = bool(L.mpcqp_stage_has_cost(self._h))
         self.link_cost = bool(L.mpcqp_stage_has_link_cost(self._h))      # a link cost between consecutive frames (models.StageOCP.llink)
         self.param_count = int(L.mpcqp_stage_param_count(self._h))      # parameters per instance (mpcqp_stage_set_instance_params); 0: none
+        self.nsd = int(L.mpcqp_stage_data_count(self._h))               # stage-data values per frame (mpcqp_stage_set_stage_data); 0: none
+        self.horizon = int(d.horizon)
+        self._sd_batch = 0
         self.Pp = np.zeros(self.n + 1, np.int32); self.Pi = np.zeros(self.nnzP, np.int32)
         self.Ap = np.zeros(self.n + 1, np.int32); self.Ai = np.zeros(self.nnzA, np.int32)
         _lib.check(L.mpcqp_stage_pattern(self._h, self.Pp.ctypes.data, self.Pi.ctypes.data, self.Ap.ctypes.data, self.Ai.ctypes.data))
@@ -205,6 +215,42 @@ class StageEvaluator:
             rows = np.zeros((B, NPAR))
             rows[:, :min(w, NPAR)] = theta[:, :NPAR]
             _lib.check(L.mpcqp_stage_set_instance_params(self._h, which, B, rows.ctypes.data, _lib.MEM_HOST))
+
+    def set_stage_data(self, d):
+        """one row of stage data per frame and instance (mpcqp_stage_set_stage_data; models.StageOCP.set_stage_data is its host statement).  d: a
+        NumPy array or a float64 CUDA tensor [B, horizon, nsd], copied; None returns to the defaults on every frame."""
+        L = _lib.lib()
+        if d is None:
+            _lib.check(L.mpcqp_stage_set_stage_data(self._h, 0, None, _lib.MEM_HOST))
+            self._sd_batch = 0
+            return
+        try:
+            import torch
+            is_t = isinstance(d, torch.Tensor)
+        except ImportError:
+            is_t = False
+        if is_t and not d.is_cuda:
+            d, is_t = d.numpy(), False
+        if not is_t:
+            d = np.ascontiguousarray(d, dtype=np.float64)
+        if d.ndim != 3 or d.shape[0] < 1 or (self.nsd > 0 and tuple(d.shape[1:]) != (self.horizon, self.nsd)):
+            raise ValueError("d: expected shape [B, %d, %d], got %s (dimension mismatch)" % (self.horizon, self.nsd, tuple(d.shape)))
+        B = int(d.shape[0])
+        if is_t:
+            if d.dtype != torch.float64:
+                raise ValueError("d: expected a float64 tensor")
+            d = d.contiguous()
+            _lib.check(L.mpcqp_stage_set_stage_data(self._h, B, d.data_ptr(), _lib.MEM_DEVICE))
+        else:
+            _lib.check(L.mpcqp_stage_set_stage_data(self._h, B, d.ctypes.data, _lib.MEM_HOST))
+        self._sd_batch = B
+
+    def shift_stage_data(self, d_new=None, stream=None):
+        """the receding-horizon hand-over of the stored stage data in one kernel (mpcqp_stage_shift_data; models.StageOCP.shift_stage_data is its
+        host statement): every row moves up by one frame, the last row becomes d_new [B, nsd] (a contiguous float64 CUDA tensor) or repeats"""
+        B = self._sd_batch
+        ptr = None if d_new is None else _check(d_new, (B, self.nsd), "d_new")
+        _lib.check(_lib.lib().mpcqp_stage_shift_data(self._h, B, ptr, stream))
 
     def alloc(self, batch, device="cuda"):
         """output buffers of one evaluation: dict P, q, A, l, u"""
