@@ -470,6 +470,33 @@ typedef struct mpcqp_stage_linesearch_args {
   int candidates;                      /* 1 .. MPCQP_LINESEARCH_MAX_CANDIDATES                       */
 } mpcqp_stage_linesearch_args;
 int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesearch_args *a, void *stream);
+/* Convexify the frame term of a general stage cost on the device (opt-in).  mpcqp_stage_eval writes the exact Hessian of the traced
+ * cost into P, and a non-convex lcost / lterm makes the QP MPCQP_NON_CVX, as OSQP rejects it in the reference.  This entry, called on the P
+ * mpcqp_stage_eval just wrote at the same (p, x), replaces every frame's Hessian H_k over [s_k; u_k; r] (the terminal cost's on the last frame) by
+ * V f(Lambda) V', H_k = V Lambda V':
+ *   MPCQP_CONVEXIFY_PROJECT  f(lam) = max(lam, eps)         MPCQP_CONVEXIFY_MIRROR  f(lam) = max(|lam|, eps)
+ * A frame with lam_min(H_k) >= eps is untouched: nothing of it is written, and an instance without a touched frame keeps every bit of P.  For a
+ * touched frame the correction f(H_k) - H_k is ADDED to the frame's slots of P, both triangles; in a handle with one shared reference the
+ * p-p block takes the sum of the corrections over the touched frames, k ascending, in a second pass.  q, A, l, u are not arguments: the gradient
+ * stays exact, only the curvature the QP sees changes.  A link cost's own entries are not convexified (it must be convex for P to be positive
+ * semidefinite).  No floating-point atomics: the result is bitwise repeatable and does not depend on the batch size or the instance's position.
+ * Needs a library generated from a model with convexify = True: its cost pattern is closed under the fill-in of V f(Lambda) V' (every pair of
+ * indices inside one connected component of the Hessian's sparsity graph), and it exports mpcqp_user_convexify.  The handle's stored stage
+ * data and per-frame references are honoured.  Stateless but for a scratch buffer the handle grows on first use; asynchronous on `stream`.
+ * touched[b]: the number of touched frames of instance b; lam_min[b * horizon + k]: lam_min(H_k) before the change.
+ * MPCQP_ERR_LIMIT (with the reason) for a built-in model or a library without the export; MPCQP_ERR_ARG for a mode other than the two, eps <= 0
+ * or not finite, a null a, P, x or p, batch < 1, or a batch larger than the stored stage data. */
+#define MPCQP_CONVEXIFY_PROJECT 1
+#define MPCQP_CONVEXIFY_MIRROR  2
+typedef struct mpcqp_stage_convexify_args {
+  int mode; double eps;                /* MPCQP_CONVEXIFY_*; eps > 0, finite                          */
+  const double *p, *x;                 /* [batch * np], [batch * nvar]: as mpcqp_stage_eval           */
+  double *P;                           /* [batch * nnzP], in / out: as mpcqp_stage_eval wrote it      */
+  int *touched;                        /* [batch], optional                                          */
+  double *lam_min;                     /* [batch * horizon], optional                                */
+} mpcqp_stage_convexify_args;
+int mpcqp_stage_has_convexify(const mpcqp_stage *s);
+int mpcqp_stage_convexify(mpcqp_stage *s, int batch, const mpcqp_stage_convexify_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Local-system evaluation on device for a general (non-stage) NLP.

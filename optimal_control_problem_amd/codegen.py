@@ -199,6 +199,19 @@ def hessian_mask(gtape):
     return mask | mask.T
 
 
+def closed_mask(mask):
+    """the component closure of a symmetric structure: every pair of indices inside one connected component of the graph of mask | eye.  V f(Lambda) V'
+    of a matrix with that structure fills in inside the components and nowhere else, so this is the pattern a convexified Hessian needs
+    (models.StageOCP.convexify)"""
+    m = np.asarray(mask, bool)
+    m = m | m.T | np.eye(m.shape[0], dtype=bool)
+    while True:
+        r = (m.astype(np.int64) @ m.astype(np.int64)) > 0
+        if np.array_equal(r, m):
+            return m
+        m = r
+
+
 class TS:
     """scalar tracer"""
     __array_priority__ = 1000
@@ -515,7 +528,7 @@ def trace_link_cost(llink, nx, nu):
 
 
 def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False,
-          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None):
+          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None, convexify=False):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
@@ -533,7 +546,9 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     nsd = k (<= 8), sdata0 = the k default values: the model reads its stage data as self.sdata[i] inside hfun, lcost and lterm (a cost that does
     is a method of the model); while those are traced, self.sdata holds k extra tape inputs, emitted as d[i] -- data of the launch
     (mpcqp_stage_set_stage_data gives every frame of every instance its own row), without a derivative: the gradient and the Hessian's structure
-    are over [s; u; r] as before.  F / cdyn, kfun and llink take none: reading self.sdata there raises a ValueError."""
+    are over [s; u; r] as before.  F / cdyn, kfun and llink take none: reading self.sdata there raises a ValueError.
+    convexify (models.StageOCP.convexify; needs lcost): the cost's mask becomes its component closure (closed_mask) and the library exports
+    mpcqp_user_convexify, the launcher of mpcqp_stage_convexify.  Without it the library is the text it always was."""
     ntheta = int(ntheta)
     nsd = int(nsd)
     if nsd > NSD_MAX:
@@ -590,9 +605,14 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
                 LT, GT = trace_cost(lterm, nx, nu, nx, nsd, model)
             mask = mask | hessian_mask(GT)
         mask = mask | np.eye(mask.shape[0], dtype=bool)      # keep the diagonal in the pattern
+        if convexify:
+            mask = closed_mask(mask)
+            tape.convexify = True
         tape.cost = dict(L=L, G=G, LT=LT, GT=GT, mask=mask)
     elif lterm is not None:
         raise ValueError("a terminal cost needs a stage cost")
+    elif convexify:
+        raise ValueError("convexify needs a stage cost (lcost): diagonal weights have nothing to convexify")
     tape.link_cost = None
     if llink is not None:
         with _bound_theta(guarded, _ThetaGuard("llink")), _bound_theta(unread, _SdataGuard("llink"), "sdata"):
@@ -774,7 +794,18 @@ int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
   return (int)stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream%(sdarg)s);
 }
-%(params)s%(link_cost)s%(sdata)s}
+%(params)s%(link_cost)s%(sdata)s%(convexify)s}
+'''
+
+# a model with convexify = True only: the launcher of mpcqp_stage_convexify (w: the handle's slot tables and scratch), and for a library with stage
+# data the form that takes the data rows.  A library without the export takes no convexification
+_DEVICE_CONVEXIFY_TMPL = '''int mpcqp_user_convexify(const StageDev *sd, int batch, const mpcqp_stage_convexify_args *a, const StageCvxBuf *w, void *stream) {
+  return (int)stage_launch_convexify<SmUser%(pf)s>(*sd, batch, *a, *w, (hipStream_t)stream%(sdarg)s);
+}
+'''
+_DEVICE_CONVEXIFY_SD_TMPL = '''int mpcqp_user_convexify_sd(const StageDev *sd, int batch, const mpcqp_stage_convexify_args *a, const StageCvxBuf *w, void *stream, const double *d) {
+  return (int)stage_launch_convexify<SmUser, %(pfpp)s>(*sd, batch, *a, *w, (hipStream_t)stream, StageData{d});
+}
 '''
 
 # a model with a link cost (llink) only: 1 and the structure of its Hessian over [s; u; s_next; u_next] (row-major (2 f)^2 bytes).  A library
@@ -992,7 +1023,7 @@ def cache_dir():
 
 def _build(src_text, suffix, cmd_prefix):
     # the key covers everything the library is compiled from: the generated source, every header it includes and the command
-    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "general_kernels.hpp", "stage_models.hpp", "common.hpp"))
+    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "stage_convexify.hpp", "general_kernels.hpp", "stage_models.hpp", "common.hpp"))
     deps += open(os.path.join(_HERE, "..", "include", "mpcqp.h")).read()
     key = hashlib.sha256((src_text + deps + " ".join(cmd_prefix)).encode()).hexdigest()[:20]
     base = os.path.join(cache_dir(), "user_%s_%s" % (suffix, key))
@@ -1017,8 +1048,11 @@ def device_source(tape):
     sdata = ""
     if nsd:
         sdata = _DEVICE_SDATA_TMPL % dict(sub, **{k: (v % sub if nth else "") for k, v in _DEVICE_SDATA_THETA.items()})
+    cvx = ""
+    if getattr(tape, "convexify", False):
+        cvx = _DEVICE_CONVEXIFY_TMPL % sub + (_DEVICE_CONVEXIFY_SD_TMPL % sub if nsd else "")
     return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if nth else "",
-                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "", sdata=sdata)
+                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "", sdata=sdata, convexify=cvx)
 
 
 def build_device_library(tape):

@@ -39,6 +39,10 @@ struct StageUserLib {
   int (*merit_sd)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *, const double *) = nullptr;
   int (*advance_sd)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *, const double *) = nullptr;
   int (*linesearch_sd)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *, const double *) = nullptr;
+  // optional, a library generated from a model with convexify = True (mpcqp_stage_convexify): the handle's tables and scratch, then the stream;
+  // the _sd form of a library with stage data takes the data rows last (lcost / lterm read no theta: there is no _pp form)
+  int (*convexify)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, void *) = nullptr;
+  int (*convexify_sd)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, void *, const double *) = nullptr;
   bool all_pp() const { return eval_pp && merit_pp && advance_pp && linesearch_pp; }
   bool all_sd() const { return eval_sd && merit_sd && advance_sd && linesearch_sd; }
 };
@@ -51,6 +55,7 @@ static StageUserLib stage_user_lib(void *lib) {
   stage_sym(lib, "mpcqp_user_advance_pp", u.advance_pp); stage_sym(lib, "mpcqp_user_linesearch_pp", u.linesearch_pp);
   stage_sym(lib, "mpcqp_user_eval_sd", u.eval_sd); stage_sym(lib, "mpcqp_user_merit_sd", u.merit_sd);
   stage_sym(lib, "mpcqp_user_advance_sd", u.advance_sd); stage_sym(lib, "mpcqp_user_linesearch_sd", u.linesearch_sd);
+  stage_sym(lib, "mpcqp_user_convexify", u.convexify); stage_sym(lib, "mpcqp_user_convexify_sd", u.convexify_sd);
   return u;
 }
 
@@ -84,6 +89,12 @@ struct mpcqp_stage {
   double *dsd[2] = {nullptr, nullptr};
   int sd_cur = 0, sd_batch = 0, sd_cap = 0;
   const double *sdata() const { return sd_batch > 0 ? dsd[sd_cur] : nullptr; }
+  // convexification (mpcqp_stage_convexify): the slot tables of the frame term, built with the handle of a library that exports the launcher, and
+  // the scratch of the launch ([cvx_cap * N * nx * nx] doubles, then [cvx_cap * N] flags), sized on first use like the stage-data buffers
+  bool convexify = false;
+  int *dslots = nullptr;
+  double *dcvx = nullptr;
+  int cvx_cap = 0;
 };
 
 // a launch may not be larger than a stored parameter set
@@ -214,6 +225,34 @@ static int stage_create_common(const mpcqp_stage_desc *d, int nx, int nu, int nh
   return MPCQP_OK;
 }
 
+// Slot tables of mpcqp_stage_convexify (StageCvxBuf): element (r, c) of frame k's Hessian over [s; u; r] sits in column col(c), row row(r) of P --
+// local index t < f is variable np + k f + t, t >= f the reference entry t - f (per-frame references: k nx + t - f); the slot is found in the
+// pattern itself, so a link cost's extra rows in a frame column are stepped over.  The r-r block of a shared reference goes to ppslot.
+static int stage_build_convexify_tables(mpcqp_stage *s, const unsigned char *mask) {
+  const StageDev &sd = s->sd;
+  const int f = sd.f, nx = sd.nx, nl = f + nx, N = sd.N;
+  std::vector<int> tab((size_t)N * nl * nl + (size_t)nx * nx, -1);
+  auto var = [&](int k, int t) { return t < f ? sd.np + k * f + t : (sd.pref ? k * nx : 0) + t - f; };
+  auto find = [&](int row, int col) {
+    for (int e = s->Pp[col]; e < s->Pp[col + 1]; e++) if (s->Pi[e] == row) return e;
+    return -1;
+  };
+  for (int k = 0; k < N; k++)
+    for (int r = 0; r < nl; r++)
+      for (int c = 0; c < nl; c++) {
+        if (!mask[r * nl + c] || (!sd.pref && r >= f && c >= f)) continue;
+        tab[((size_t)k * nl + r) * nl + c] = find(var(k, r), var(k, c));
+      }
+  if (!sd.pref)
+    for (int r = 0; r < nx; r++)
+      for (int c = 0; c < nx; c++) if (mask[(f + r) * nl + f + c]) tab[(size_t)N * nl * nl + r * nx + c] = find(r, c);
+  if (hipMalloc(&s->dslots, tab.size() * sizeof(int)) != hipSuccess ||
+      hipMemcpy(s->dslots, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    return mpcqp_set_error(MPCQP_ERR_HIP, "upload of the convexification tables failed");
+  s->convexify = true;
+  return MPCQP_OK;
+}
+
 static int stage_create_zoo(const mpcqp_stage_desc *d, bool pref, mpcqp_stage **out) {
   if (!out) return mpcqp_set_error(MPCQP_ERR_ARG, "out is null");
   *out = nullptr;
@@ -303,6 +342,11 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   s->link_cost = lf && lf(lmask.data());
   if (int rc = stage_create_common(&dd, nx, nu, nh, h_lo, h_hi, s, s->general_cost ? mask.data() : nullptr, nk, k_lo, k_hi, pref,
                                    s->link_cost ? lmask.data() : nullptr)) { mpcqp_stage_destroy(s); return rc; }
+  // optional export of a library generated with convexify = True: the launcher of mpcqp_stage_convexify.  Its cost mask is closed under the
+  // fill-in of the correction, so every element the kernel adds has a slot in the pattern just built; the tables say which.
+  if (s->general_cost && user.convexify && (s->nsd == 0 || user.convexify_sd)) {
+    if (int rc = stage_build_convexify_tables(s, mask.data())) { mpcqp_stage_destroy(s); return rc; }
+  }
   *out = s;
   return MPCQP_OK;
 }
@@ -327,6 +371,8 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   if (s->dhhi) (void)hipFree(s->dhhi);
   for (int w = 0; w < 2; w++) if (s->dth[w]) (void)hipFree(s->dth[w]);
   for (int w = 0; w < 2; w++) if (s->dsd[w]) (void)hipFree(s->dsd[w]);
+  if (s->dslots) (void)hipFree(s->dslots);
+  if (s->dcvx) (void)hipFree(s->dcvx);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -534,6 +580,37 @@ int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesear
       [&] { return s->user.linesearch(&sd, batch, a, stream); },
       [&](StageTheta th) { return s->user.linesearch_pp(&sd, batch, a, stream, th.model); },
       [&](StageTheta th, const double *d) { return s->user.linesearch_sd(&sd, batch, a, stream, th.model, d); });
+}
+
+int mpcqp_stage_has_convexify(const mpcqp_stage *s) { return s && s->convexify ? 1 : 0; }
+
+int mpcqp_stage_convexify(mpcqp_stage *s, int batch, const mpcqp_stage_convexify_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (a->mode != MPCQP_CONVEXIFY_PROJECT && a->mode != MPCQP_CONVEXIFY_MIRROR)
+    return mpcqp_set_error(MPCQP_ERR_ARG, "mode must be MPCQP_CONVEXIFY_PROJECT or MPCQP_CONVEXIFY_MIRROR");
+  if (!(a->eps > 0.0) || !std::isfinite(a->eps)) return mpcqp_set_error(MPCQP_ERR_ARG, "eps must be positive and finite");
+  if (!a->P || !a->x || (s->sd.np > 0 && !a->p)) return mpcqp_set_error(MPCQP_ERR_ARG, "p, x and P are required");
+  if (s->sd.model != MPCQP_MODEL_USER)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the built-in models have diagonal weights: there is nothing to convexify (a generated model with lcost and convexify = True has)");
+  if (!s->convexify)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_convexify: regenerate it from a model with a stage cost (lcost) and convexify = True");
+  if (s->sd_batch > 0 && batch > s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch is larger than the stored stage data (mpcqp_stage_set_stage_data)");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const StageDev &sd = s->sd;
+  const size_t nx2 = (size_t)sd.nx * sd.nx;
+  if (batch > s->cvx_cap) {
+    double *nb = nullptr;
+    MPCQP_HIPCHK(hipMalloc(&nb, (size_t)batch * sd.N * (nx2 * sizeof(double) + sizeof(int))));
+    MPCQP_HIPCHK(hipDeviceSynchronize());       // a launch that uses the old scratch may still be queued
+    if (s->dcvx) (void)hipFree(s->dcvx);
+    s->dcvx = nb; s->cvx_cap = batch;
+  }
+  const int nl = sd.f + sd.nx;
+  const StageCvxBuf w{s->dslots, s->dslots + (size_t)sd.N * nl * nl, s->dcvx, (int *)(s->dcvx + (size_t)s->cvx_cap * sd.N * nx2)};
+  MPCQP_HIPCHK((hipError_t)(s->nsd > 0 ? s->user.convexify_sd(&sd, batch, a, &w, stream, s->sdata()) : s->user.convexify(&sd, batch, a, &w, stream)));
+  return MPCQP_OK;
 }
 
 }  // extern "C"

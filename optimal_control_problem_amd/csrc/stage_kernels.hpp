@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "stage_models.hpp"
+#include "stage_convexify.hpp"
 #include "../../include/mpcqp.h"
 
 #define STAGE_ABI_VERSION 7
@@ -766,6 +767,99 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
   }
 }
 
+// Convexification of the frame term of a general stage cost (mpcqp_stage_convexify; models.StageOCP.convexify_system is its host statement; the
+// eigen-solve is stage_convexify.hpp).  One group of W lanes per (instance, frame), W the smallest of 16 / 32 / 64 that holds nl = 2 nx + nu; a block
+// holds as many groups as 48 KB of static LDS and 256 threads allow, always whole waves.  Per group: the tile A (the frame's Hessian, then its
+// eigenvalues on the diagonal) and the eigenvectors V, nl x nl doubles each, in LDS -- they are indexed at run time, as registers they would be scratch.
+template <class M> struct stage_cvx {
+  static constexpr int nl = 2 * M::nx + M::nu;
+  static constexpr int W = nl <= 16 ? 16 : nl <= 32 ? 32 : 64;
+  static constexpr int tile = 2 * nl * nl;                          // doubles per group
+  static constexpr int fit = (48 * 1024) / (tile * 8), per_wave = 64 / W;
+  static constexpr int waves = fit / per_wave >= 4 ? 4 : fit / per_wave >= 1 ? fit / per_wave : 1;
+  static constexpr int G = waves * per_wave;                        // groups per block
+  static_assert(G * tile * 8 <= 64 * 1024, "the tiles of a block fit its static LDS");
+};
+// what the handle lends a convexify launch (device memory): slots [N * nl * nl], the slot of P that takes element (r, c) of frame k's correction, -1 =
+// none (outside the pattern, or the r-r block of a shared reference); ppslot [nx * nx], the slot of the shared p-p entry (r, c), -1 = none (all of
+// them for per-frame references, whose r-r entries are frame slots); rr [batch * N * nx * nx], the r-r parts of the touched frames' corrections
+// on their way to the second pass; flags [batch * N], 1 = the frame was touched
+struct StageCvxBuf { const int *slots, *ppslot; double *rr; int *flags; };
+
+template <class M, bool PF = false, class... PP>
+__global__ void __launch_bounds__(stage_cvx<M>::G * stage_cvx<M>::W) stage_convexify_kernel(StageDev sd, int batch, mpcqp_stage_convexify_args a,
+                                                                                            StageCvxBuf w, PP... pp) {
+  using C = stage_cvx<M>;
+  constexpr int nx = M::nx, nu = M::nu, f = nx + nu, nl = C::nl, W = C::W, G = C::G;
+  __shared__ double lds[G][2][nl * nl];
+  const int grp = threadIdx.x / W, lane = threadIdx.x - grp * W;
+  const int N = sd.N;
+  const long item = (long)blockIdx.x * G + grp;                     // (instance, frame); a group past the end walks the barriers without work
+  const bool live = item < (long)batch * N;
+  const int b = live ? (int)(item / N) : 0, k = live ? (int)(item - (long)b * N) : 0;
+  double *A = lds[grp][0], *V = lds[grp][1];
+  if (live && lane < nl) {
+    // column `lane` of H_k: one pass of the generated gradient on dual numbers seeded on input `lane` of [s; u; r_k] -- the call, and so the
+    // bits, of stage_eval_kernel's columns
+    const double *fr = a.x + (long)b * sd.nvar + k * f, *rk = a.p + (long)b * sd.np + (PF ? k * nx : 0);
+    Dual s[nx], uu[nu], rr[nx], g[nl];
+    double dv[sm_nsd_regs<M>];
+    stage_load_data<M>(dv, b, N, k, pp...);
+#pragma unroll
+    for (int i = 0; i < nx; i++) { s[i] = {fr[i], i == lane ? 1.0 : 0.0}; rr[i] = {rk[i], f + i == lane ? 1.0 : 0.0}; }
+#pragma unroll
+    for (int i = 0; i < nu; i++) uu[i] = {fr[nx + i], nx + i == lane ? 1.0 : 0.0};
+    stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
+#pragma unroll
+    for (int r = 0; r < nl; r++) A[r * nl + lane] = g[r].d;
+  }
+  sm_jacobi<W>(A, V, nl, lane, live);
+  const double lmin = sm_convexify_lam_min<W>(A, nl, lane);
+  const bool touched = live && lmin < a.eps;
+  if (touched) {
+    // the correction, entry by entry: one lane per entry, one entry per slot -- read, add, write
+    double *Pb = a.P + (long)b * sd.nnzP;
+    const int *sl = w.slots + (long)k * nl * nl;
+    for (int e = lane; e < nl * nl; e += W) {
+      const int r = e / nl, c = e - r * nl, slot = sl[e];
+      const bool shared_rr = !PF && r >= f && c >= f;
+      if (slot >= 0 || shared_rr) {
+        const double d = sm_convexify_delta(A, V, nl, r, c, a.mode, a.eps);
+        if (slot >= 0) Pb[slot] += d;
+        else w.rr[item * (nx * nx) + (r - f) * nx + (c - f)] = d;
+      }
+    }
+  }
+  if (live && lane == 0) {
+    w.flags[item] = touched ? 1 : 0;
+    if (a.lam_min) a.lam_min[item] = lmin;
+  }
+}
+
+// the second pass: thread (b, e) adds to the shared p-p entry e of instance b the sum of the touched frames' corrections, k ascending, from 0.0 --
+// the order of the statement -- and writes nothing where no frame was touched; thread (b, 0) counts the touched frames.  (A template only so that
+// the kernel exists in the libraries that launch it.)
+template <class M>
+__global__ void __launch_bounds__(256) stage_convexify_sum_kernel(int batch, int N, int nnzP, StageCvxBuf w, double *__restrict__ P, int *__restrict__ touched) {
+  constexpr int nx2 = M::nx * M::nx;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)batch * nx2) return;
+  const int b = (int)(gid / nx2), e = (int)(gid - (long)b * nx2);
+  const int *fl = w.flags + (long)b * N;
+  if (e == 0 && touched) {
+    int cnt = 0;
+    for (int k = 0; k < N; k++) cnt += fl[k];
+    touched[b] = cnt;
+  }
+  const int slot = w.ppslot[e];
+  if (slot < 0) return;
+  double acc = 0.0;
+  bool any = false;
+  for (int k = 0; k < N; k++)
+    if (fl[k]) { acc += w.rr[((long)b * N + k) * nx2 + e]; any = true; }
+  if (any) P[(long)b * nnzP + slot] += acc;
+}
+
 // launchers shared by the zoo dispatch and generated libraries
 // (PP: empty, or a StageTheta and / or a StageData behind the stream -- the per-instance-parameter and the stage-data instances)
 template <class M, bool PF = false, class... PP>
@@ -792,6 +886,19 @@ template <class M, bool PF = false, class... PP>
 inline hipError_t stage_launch_linesearch(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st, PP... pp) {
   stage_linesearch_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a, pp...);
   return hipGetLastError();
+}
+template <class M, bool PF = false, class... PP>
+inline hipError_t stage_launch_convexify(const StageDev &sd, int batch, const mpcqp_stage_convexify_args &a, const StageCvxBuf &w, hipStream_t st, PP... pp) {
+  if constexpr (M::has_cost != 0) {
+    using C = stage_cvx<M>;
+    const long items = (long)batch * sd.N, entries = (long)batch * M::nx * M::nx;
+    stage_convexify_kernel<M, PF, PP...><<<(unsigned)((items + C::G - 1) / C::G), C::G * C::W, 0, st>>>(sd, batch, a, w, pp...);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    stage_convexify_sum_kernel<M><<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(batch, sd.N, sd.nnzP, w, a.P, a.touched);
+    return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;
+  }
 }
 
 // The model zoo, listed once: fn(StageTag<M, PF>{}) for the functor of `model` and the kind of reference.  A new zoo functor is one more case

@@ -221,6 +221,14 @@ class StageOCP:
     NSD_MAX = 8
     _sdata_rows = None
 
+    # opt-in convexification of the frame term: a model with lcost sets convexify = True when its cost is not convex everywhere (a
+    # Gaussian bump, an inverse-distance potential, a cosine swing-up term).  The QP otherwise takes the exact, indefinite Hessian and comes back
+    # NON_CVX.  The flag closes cost_mask under the fill-in of V f(Lambda) V' -- every pair of indices inside one connected component of the
+    # Hessian's sparsity graph -- so that convexify_system (host) and mpcqp_stage_convexify (device) find a slot for every entry of the
+    # correction, and makes the generated library export the launcher.  Without the flag nothing changes: the same mask, pattern and source.
+    convexify = False
+    CONVEXIFY_MODES = {"project": 1, "mirror": 2}      # MPCQP_CONVEXIFY_*
+
     def set_stage_data(self, d=None):
         """Host statement of mpcqp_stage_set_stage_data.  d [B, N, nsd]: frame k of instance b takes row d[b, k] in hfun, lcost and lterm -- in
         path_values, dh, constraints, objective, cost_derivatives, local_system, violation, line_search and the stage_cost of advance (d[b, 0]).
@@ -332,6 +340,8 @@ class StageOCP:
                 self._lttape, self._gttape = codegen.trace_cost(self.lterm, self.nx, self.nu, self.nx, **dkw)
                 mask = mask | codegen.hessian_mask(self._gttape)
             self.cost_mask = mask | np.eye(mask.shape[0], dtype=bool)
+            if self.convexify:
+                self.cost_mask = codegen.closed_mask(self.cost_mask)
         self.link_cost = self.llink is not None
         if self.link_cost:
             from . import codegen
@@ -499,6 +509,45 @@ class StageOCP:
             ins[c] = ins[c] + 1j * eps
             hess[..., :, c] = np.stack(self._cost_eval(self._gtape, self._gttape, ins), axis=-1).imag / eps
         return grad, hess
+
+    def convexify_system(self, p, x, P, mode="project", eps=1e-6):
+        """Host statement of mpcqp_stage_convexify.  P [B, nnzP] as local_system wrote it at (p, x) -> (P_new, touched [B] int, lam_min [B, N]).
+        Every frame's Hessian H_k over [s_k; u_k; r] (cost_derivatives; the terminal cost's on the last frame) with lam_min(H_k) < eps is
+        replaced by V f(Lambda) V', f(lam) = max(lam, eps) (project) or max(|lam|, eps) (mirror): the correction D_k = f(H_k) - H_k = V (f(Lambda) -
+        Lambda) V' (np.linalg.eigh on the full block) is added to the frame's slots (_P_src), and the summed entries of a shared reference's p-p
+        block take the sum of D_k over the touched frames, k ascending.  An untouched frame writes nothing; q, A, l, u do not change."""
+        if not (self.general_cost and self.convexify):
+            raise ValueError("convexify needs a model with a stage cost (lcost) and convexify = True")
+        if mode not in self.CONVEXIFY_MODES:
+            raise ValueError("mode must be 'project' or 'mirror'")
+        eps = float(eps)
+        if not (eps > 0.0 and np.isfinite(eps)):
+            raise ValueError("eps must be positive and finite")
+        p = np.asarray(p, float); x = np.asarray(x, float)
+        _, hess = self.cost_derivatives(p, x)
+        B, N, nl = hess.shape[:3]
+        P_new = np.array(P, float)
+        touched = np.zeros(B, np.int64); lam_min = np.zeros((B, N))
+        src = self._P_src
+        per_frame = [src[src[:, 0] == k] for k in range(N)]
+        summed = src[src[:, 0] < 0]
+        for b in range(B):
+            acc = np.zeros((nl, nl)); any_touched = False
+            for k in range(N):
+                lam, V = np.linalg.eigh(hess[b, k])
+                lam_min[b, k] = lam[0]
+                if not lam[0] < eps:
+                    continue
+                a = np.abs(lam) if mode == "mirror" else lam
+                D = (V * (np.maximum(a, eps) - lam)) @ V.T
+                D = 0.5 * (D + D.T)                          # (both triangles the same bits)
+                touched[b] += 1; any_touched = True
+                e = per_frame[k]
+                P_new[b, e[:, 3]] += D[e[:, 1], e[:, 2]]
+                acc += D
+            if any_touched and len(summed):
+                P_new[b, summed[:, 3]] += acc[summed[:, 1], summed[:, 2]]
+        return P_new, touched, lam_min
 
     # -- dynamics (override) ---------------------------------------------------------------------
     def cdyn(self, s, u):

@@ -15,6 +15,9 @@ replaces the one alpha of :171-177 by a step length per instance, chosen by an l
 (models.StageOCP.line_search states the rule, mpcqp_stage_linesearch runs it on the device).  An instance whose QP returned no point keeps its
 iterate; the penalty persists across iterations and calls; `alpha_taken` and `accepted` hold the last iteration's step lengths and candidate
 indices; with warm_start_admm the remaining step is (1 - alpha_b) dx per instance.  Stage OCPs only.
+Opt-in as well: options["convexify"] = "project", "mirror" or a dict {mode, eps} replaces, before every QP, each frame Hessian of a general stage cost that has
+an eigenvalue below eps by V f(Lambda) V' (models.StageOCP.convexify_system states the rule, mpcqp_stage_convexify runs it on the device); the gradient stays
+exact; `convexified` holds the touched-frame counts per iteration.  For models with lcost that set convexify = True.
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -40,6 +43,32 @@ def _line_search_options(value):
         opts.update(value)
     opts["candidates"] = int(opts["candidates"])
     return opts
+
+
+def _convexify_options(value, model):
+    """options["convexify"]: None / False = off; "project" / "mirror"; or a dict {mode, eps}.  Returns None or (mode, eps)."""
+    if value is None or value is False:
+        return None
+    from .models import StageOCP
+    opts = {"mode": "project", "eps": 1e-6}
+    if isinstance(value, str):
+        opts["mode"] = value
+    elif isinstance(value, dict):
+        unknown = set(value) - set(opts)
+        if unknown:
+            raise ValueError("convexify: unknown keys %s (known: %s)" % (sorted(unknown), sorted(opts)))
+        opts.update(value)
+    else:
+        raise ValueError("convexify: expected None, 'project', 'mirror' or a dict {mode, eps}")
+    if opts["mode"] not in StageOCP.CONVEXIFY_MODES:
+        raise ValueError("convexify: mode must be 'project' or 'mirror'")
+    eps = float(opts["eps"])
+    if not (eps > 0.0 and np.isfinite(eps)):
+        raise ValueError("convexify: eps must be positive and finite")
+    if not (getattr(model, "general_cost", False) and getattr(model, "convexify", False)):
+        raise ValueError("convexify needs a stage OCP with a stage cost (lcost) that sets convexify = True: the flag closes the cost's pattern "
+                         "under the fill-in and makes the generated library export the kernel")
+    return opts["mode"], eps
 
 
 class SQPOptimizationSolver:
@@ -68,9 +97,15 @@ class SQPOptimizationSolver:
         # and carry each instance's adapted rho into its next QP, as a kept OSQP workspace would (with warm_start_admm)
         self.carry_rho = bool(options.get("carry_rho", False))
         self.sqp_tol = float(options.get("sqp_tol", 0.0) or 0.0)
+        # extension, as in the device loop: an instance whose QP returned no point keeps its iterate (the reference adds the NaN solution, :171-177)
+        self.skip_failed_steps = bool(options.get("skip_failed_steps", False))
         self.line_search = _line_search_options(options.get("line_search"))
         if self.line_search is not None and not hasattr(nlp, "line_search"):
             raise ValueError("line_search needs a stage OCP (models.StageOCP): the merit line search is not available for a general NLP")
+        # opt-in: every frame Hessian of a general stage cost with an eigenvalue below eps is replaced by a positive definite one before the QP
+        # (models.StageOCP.convexify_system); `convexified` holds the touched-frame counts per instance, one array per iteration
+        self.convexify = _convexify_options(options.get("convexify"), nlp)
+        self.convexified = []
         self.alpha_taken = None; self.accepted = None; self.gmax = None
         self.last_line_search = None                     # the NumPy statement's full result for the last iteration
         self._mu = None                                  # the penalty, monotone across iterations and calls
@@ -103,6 +138,9 @@ class SQPOptimizationSolver:
         for i in range(self.stepNum_):
             t0 = time.perf_counter()
             localSystem = self.getLocalSystem(arg)
+            if self.convexify is not None:
+                localSystem.P, touched, _ = self.model.convexify_system(p, self.result_["x"], localSystem.P, *self.convexify)
+                self.convexified.append(touched)
             t1 = time.perf_counter()
             self.qpSolver_.setSystem(localSystem)
             if self.warm_start_admm and hasattr(self.qpSolver_, "setPrimalDualStart"):
@@ -144,9 +182,12 @@ class SQPOptimizationSolver:
                 self.alpha_taken = ls["alpha"]; self.accepted = ls["accepted"]; self.last_line_search = ls
                 self.step_max = ls["step_max"]
             else:
-                self.result_["x"] = self.result_["x"] + self.alpha_ * solution[:, pSize:]
+                step = self.alpha_ * solution[:, pSize:]
+                if self.skip_failed_steps and self.last_qp_info is not None and "status" in self.last_qp_info:
+                    step = np.where(np.isin(np.asarray(self.last_qp_info["status"]), (1, 2, 7))[:, None], step, 0.0)
+                self.result_["x"] = self.result_["x"] + step
                 self.result_["f"] = self.model.objective(p, self.result_["x"])
-                self.step_max = np.abs(self.alpha_ * solution[:, pSize:]).max(axis=1)
+                self.step_max = np.abs(step).max(axis=1)
             self.iterations_done = i + 1
             if self.verbose_:
                 normDelta = np.linalg.norm(self.result_["x"] - oldRes, axis=1).max()
@@ -208,6 +249,15 @@ class DeviceSQPOptimizationSolver:
         self.line_search = _line_search_options(options.get("line_search"))
         if self.line_search is not None and evaluator is not None:
             raise ValueError("line_search is limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has no merit line search")
+        # extension (opt-in): one mpcqp_stage_convexify on P between the evaluation and the QP update; the touched-frame counts are
+        # kept per iteration in `convexified`, a list of int tensors like admm_iterations
+        if options.get("convexify") not in (None, False):
+            if evaluator is not None:
+                raise ValueError("convexify is limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has no frame Hessians to convexify")
+            if self.constant_matrices:
+                raise ValueError("convexify does not combine with constant_matrices: a touched frame changes P, which that option promises is constant")
+        self.convexify = _convexify_options(options.get("convexify"), nlp)
+        self.convexified = []
         self.alpha_taken = None; self.accepted = None
         self.iterations_done = 0
         self.step_max = None
@@ -228,6 +278,7 @@ class DeviceSQPOptimizationSolver:
         self.iters = torch.zeros(self.batch, dtype=torch.int32, device=self.dev)
         self.info = mk(4); self.rho = torch.zeros(self.batch, dtype=torch.float64, device=self.dev)
         self.admm_iterations = []
+        self._touched = torch.zeros(self.batch, dtype=torch.int32, device=self.dev) if self.convexify is not None else None
         self.f = None; self.gmax = None
         self._have_start = False                         # like last_qp_info of the host loop: survives across calls
         self._start_clean = False                        # set by mpc.ClosedLoopMPC: mpcqp_stage_advance already zeroed the failed instances' start
@@ -291,6 +342,9 @@ class DeviceSQPOptimizationSolver:
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         for i in range(self.stepNum_):
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
+            if self.convexify is not None:
+                ev.convexify(p, self.x, self.ls["P"], self.convexify[0], self.convexify[1], touched=self._touched, stream=stream)
+                self.convexified.append(self._touched.clone())
             if self.qp is None:                          # presolve_fixed_rows: the fixed rows are read off this first system's bounds
                 torch.cuda.current_stream(self.dev).synchronize()
                 self._create_qp((self.ls["l"], self.ls["u"]))

@@ -36,6 +36,14 @@ class LineSearchArgs(C.Structure):
                [(k, C.c_double) for k in ("alpha0", "beta", "c1", "mu_min", "mu_factor")] + [("candidates", C.c_int)]
 
 
+class ConvexifyArgs(C.Structure):
+    """mpcqp_stage_convexify_args (include/mpcqp.h)"""
+    _fields_ = [("mode", C.c_int), ("eps", C.c_double)] + [(k, C.c_void_p) for k in ("p", "x", "P", "touched", "lam_min")]
+
+
+CONVEXIFY_MODES = {"project": 1, "mirror": 2}      # MPCQP_CONVEXIFY_*
+
+
 def _bind(L):
     if getattr(L, "_stage_bound", False):
         return L
@@ -62,6 +70,8 @@ def _bind(L):
     L.mpcqp_stage_step.argtypes = [vp, C.c_int, C.c_double, dp, dp, dp, vp, vp]
     L.mpcqp_stage_advance.argtypes = [vp, C.c_int, C.POINTER(AdvanceArgs), vp]
     L.mpcqp_stage_linesearch.argtypes = [vp, C.c_int, C.POINTER(LineSearchArgs), vp]
+    L.mpcqp_stage_has_convexify.argtypes = [vp]
+    L.mpcqp_stage_convexify.argtypes = [vp, C.c_int, C.POINTER(ConvexifyArgs), vp]
     L._stage_bound = True
     return L
 
@@ -139,7 +149,8 @@ class StageEvaluator:
                                      lcost=model.lcost if general else None, lterm=model.lterm if general else None,
                                      kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
                                      **({"per_frame_reference": True} if self.per_frame_reference else {}), **pkw,
-                                     **({"llink": model.llink} if link_cost else {}))
+                                     **({"llink": model.llink} if link_cost else {}),
+                                     **({"convexify": True} if general and getattr(model, "convexify", False) else {}))
                 self.library = cg.build_device_library(self.tape)
             else:
                 for i, v in enumerate(model_params(model)): d.par[i] = float(v)
@@ -168,6 +179,7 @@ class StageEvaluator:
         self.link_cost = bool(L.mpcqp_stage_has_link_cost(self._h))      # a link cost between consecutive frames (models.StageOCP.llink)
         self.param_count = int(L.mpcqp_stage_param_count(self._h))      # parameters per instance (mpcqp_stage_set_instance_params); 0: none
         self.nsd = int(L.mpcqp_stage_data_count(self._h))               # stage-data values per frame (mpcqp_stage_set_stage_data); 0: none
+        self.has_convexify = bool(L.mpcqp_stage_has_convexify(self._h))  # the library carries the launcher of mpcqp_stage_convexify (model.convexify)
         self.horizon = int(d.horizon)
         self._sd_batch = 0
         self.Pp = np.zeros(self.n + 1, np.int32); self.Pi = np.zeros(self.nnzP, np.int32)
@@ -338,3 +350,20 @@ class StageEvaluator:
         a.alpha0, a.beta, a.c1, a.mu_min, a.mu_factor, a.candidates = float(alpha0), float(beta), float(c1), float(mu_min), float(mu_factor), int(candidates)
         _lib.check(_lib.lib().mpcqp_stage_linesearch(self._h, B, C.byref(a), stream))
         return out
+
+    def convexify(self, p, x, P, mode="project", eps=1e-6, touched=None, lam_min=None, stream=None):
+        """the frame Hessians with an eigenvalue below eps replaced by V f(Lambda) V' inside P, in place (mpcqp_stage_convexify;
+        models.StageOCP.convexify_system is its host statement).  P [B, nnzP] is what eval just wrote at the same (p, x); touched (int32 [B]) and
+        lam_min (float64 [B, horizon]) are optional outputs.  A model that sets convexify = True (and has lcost) only.  Returns P."""
+        if mode not in CONVEXIFY_MODES:
+            raise ValueError("mode must be 'project' or 'mirror'")
+        B = x.shape[0]
+        a = ConvexifyArgs()
+        a.mode, a.eps = CONVEXIFY_MODES[mode], float(eps)
+        a.p, a.x, a.P = _check(p, (B, self.np), "p"), _check(x, (B, self.nvar), "x"), _check(P, (B, self.nnzP), "P")
+        if touched is not None:
+            a.touched = _check_int32(touched, B, "touched")
+        if lam_min is not None:
+            a.lam_min = _check(lam_min, (B, self.horizon), "lam_min")
+        _lib.check(_lib.lib().mpcqp_stage_convexify(self._h, B, C.byref(a), stream))
+        return P
