@@ -68,7 +68,7 @@ def _skip_coupled():
     model = GeneralNLP(3 * N, 2, cost, cons)
     lbx = np.tile([-INF, -2.0, -1.0], N); ubx = np.tile([INF, 2.0, 1.0], N)
     lbg = np.concatenate([np.zeros(2 * (N - 1)), -d * np.ones(N - 2)]); ubg = np.concatenate([np.zeros(2 * (N - 1)), d * np.ones(N - 2)])
-    return dict(name="skip_coupled", model=model, lbx=lbx, ubx=ubx, lbg=lbg, ubg=ubg, p0=np.zeros(2), scale=0.5)
+    return dict(name="skip_coupled", model=model, lbx=lbx, ubx=ubx, lbg=lbg, ubg=ubg, p0=np.zeros(2), scale=0.5, cost=cost, constraints=cons)
 
 
 PENDULUM_N = 6

@@ -2,7 +2,12 @@
 differences, no code shared with the product): the host path's local system (models.StageOCP, general_nlp.GeneralNLP) on the CPU, the
 device evaluator (mpcqp_stage_eval) under -m gpu.  The cost and the dynamics defects are written out here, stage by stage, from the
 model's discrete map -- the formulation under test (w = [p; x], rows [p; x; g], shifted bounds, the 2Q Hessian of sum w e^2) is the
-reference's src/sqp_solver/SQPOptimizationSolver.cpp:47-120."""
+reference's src/sqp_solver/SQPOptimizationSolver.cpp:47-120.
+
+This file covers the three zoo models with diagonal weights, one shared reference and dynamics rows only, by central differences in double at
+1e-5.  Everything added since -- path and link rows, per-frame weights, bounds and references, lcost / lterm / llink, theta, stage data,
+convexification, the line search, the hand-over, the general device path -- is held at 1e-12 against a 60-digit restatement in
+tests/test_nlp_hp_host.py (the statement) and tests/test_gpu_nlp_hp.py (the kernels); see DESIGN 6.17."""
 import numpy as np
 import pytest
 
