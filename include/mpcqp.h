@@ -497,6 +497,37 @@ typedef struct mpcqp_stage_convexify_args {
 } mpcqp_stage_convexify_args;
 int mpcqp_stage_has_convexify(const mpcqp_stage *s);
 int mpcqp_stage_convexify(mpcqp_stage *s, int batch, const mpcqp_stage_convexify_args *a, void *stream);
+/* The exact Hessian of the Lagrangian on the device (opt-in).  The reference's QP takes hessian(f, w), the Hessian of the cost alone
+ * (src/sqp_solver/SQPOptimizationSolver.cpp:55-60), and so does mpcqp_stage_eval; this entry departs from those lines.  With the rows
+ * c(w) = [p; x; s_{k+1} - F(s_k, u_k); h(s_k, u_k); kfun(...)] and their multipliers y [m] -- what mpcqp_get returns and mpcqp_stage_linesearch takes --
+ * the Lagrangian is L = f + y'c, and since the rows p and x are linear its Hessian is that of f plus, on every frame's [s_k; u_k] block,
+ *   C_k = - sum_i y_dyn[k, i] d2F_i(s_k, u_k)  (k < horizon - 1)  + sum_i y_path[k, i] d2h_i(s_k, u_k),
+ *   y_dyn[k, i] = y[np + nvar + k nx + i],  y_path[k, i] = y[np + nvar + (horizon - 1) nx + k nh + i].
+ * Called on the P mpcqp_stage_eval just wrote at the same (p, x), it ADDS C_k to the frame's slots of P, both triangles: one thread per
+ * (instance, frame, column), the column formed as -FG.d + HG.d by one pass each of the generated gradients of lam'F and mu'h on dual numbers, each
+ * entry read, added to and written by one thread.  No floating-point atomics: the result is bitwise repeatable and does not depend on the batch size
+ * or the instance's position.  F takes the instance's stored parameter row, h the frame's stored stage data, as in mpcqp_stage_eval.  With
+ * mode = MPCQP_CONVEXIFY_PROJECT / _MIRROR the rule of mpcqp_stage_convexify then runs on H_k^L = H_k + C_k (C_k zero-padded over r) in place of H_k,
+ * on the updated P: a frame it does not touch holds the bits mode = 0 gives; touched and lam_min are written as there (mode = 0 writes neither).
+ * status [batch], when given: an instance whose QP status is not MPCQP_SOLVED / _SOLVED_INACCURATE / _MAX_ITER_REACHED is neither read nor
+ * written (its y is NaN after an infeasible QP); with a mode its touched is 0 and its lam_min stays.  q, A, l, u are not arguments.
+ * Link constraints are not covered: their curvature couples two frames, and a model with a nonlinear kfun is refused when it is traced (a linear
+ * one contributes nothing); a link cost is a cost and already exact.  Needs a library generated from a model with lcost and exact_hessian = True:
+ * the structure of C_k is part of its cost pattern and it exports mpcqp_user_lagrangian.  Asynchronous on `stream`.
+ * MPCQP_ERR_LIMIT (with the reason) for a built-in model, a library without the export, and mode != 0 on a library without convexify = True;
+ * MPCQP_ERR_ARG for a null a, x, y, P (or p with a mode), a mode other than 0 and the two, eps <= 0 or not finite with a mode, batch < 1, or a batch
+ * larger than the stored stage data or parameter rows. */
+typedef struct mpcqp_stage_lagrangian_args {
+  const double *p, *x;                 /* [batch * np], [batch * nvar]: as mpcqp_stage_eval           */
+  const double *y;                     /* [batch * m]: multiplier estimate, rows [p; x; dyn; path; link] */
+  const int *status;                   /* [batch], optional                                          */
+  double *P;                           /* [batch * nnzP], in / out: as mpcqp_stage_eval wrote it      */
+  int mode; double eps;                /* 0 = add only; MPCQP_CONVEXIFY_PROJECT / _MIRROR with eps    */
+  int *touched;                        /* [batch], optional, as mpcqp_stage_convexify                */
+  double *lam_min;                     /* [batch * horizon], optional, as mpcqp_stage_convexify      */
+} mpcqp_stage_lagrangian_args;
+int mpcqp_stage_has_exact_hessian(const mpcqp_stage *s);
+int mpcqp_stage_lagrangian(mpcqp_stage *s, int batch, const mpcqp_stage_lagrangian_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Local-system evaluation on device for a general (non-stage) NLP.

@@ -527,8 +527,64 @@ def trace_link_cost(llink, nx, nu):
     return tape, g
 
 
+def _contracted_gradient(fn, nx, nu, n_out, mult, what, model=None, attr=None, nattr=0, attr_name=None):
+    """gradient over [s; u] of the scalar mult' fn(s, u), the multipliers `mult` (n_out of them) being extra tape inputs without a derivative, like
+    theta and sdata: inputs [s; u; par (nattr, attr = "theta")?; mult; d (nattr, attr = "sdata")?] -> outputs [f]"""
+    f = nx + nu
+    lead = nattr if attr == "theta" else 0
+    tape = Tape(f + nattr + n_out)
+    mk = lambda a, b: TV(tape, [TS(tape, i) for i in range(a, b)])
+    m0 = f + lead
+    d0 = f if attr == "theta" else m0 + n_out
+    with _bound_theta(model if nattr else None, mk(d0, d0 + nattr), attr or "theta"):
+        out = fn(mk(0, nx), mk(nx, f))
+    if isinstance(out, TS):
+        out = TV(tape, [out])
+    if isinstance(out, (list, tuple)):
+        out = TV(tape, [TS._lift(tape, v) for v in out])
+    if not isinstance(out, TV) or len(out) != n_out:
+        raise ValueError("%s, %d components" % (what, n_out))
+    acc = TS(tape, tape.const(0.0))
+    for i, v in enumerate(out.items):
+        acc = TS(tape, tape.s_add(acc.idx, tape.s_mul(m0 + i, TS._lift(tape, v).idx)))
+    tape.outputs = [acc.idx]
+    tape.nx, tape.nu = nx, nu
+    g = gradient_tape(tape)
+    g.outputs = g.outputs[:f]
+    g.in_names = [("s", nx), ("u", nu)] + ([("par", nattr)] if lead else []) + [(mult, n_out)] + ([(attr_name, nattr)] if nattr and not lead else [])
+    g.plain_from = f
+    return g
+
+
+def trace_curvature(F, nx, nu, hfun=None, nh=0, ntheta=0, nsd=0, model=None):
+    """The constraint curvature of the exact Lagrangian Hessian (models.StageOCP.exact_hessian): the gradient tapes over [s; u] of the
+    contracted scalars lam' F(s, u) (inputs [s; u; par; lam]) and mu' hfun(s, u) (inputs [s; u; mu; d]) and the structure of their Hessians, valid
+    for any multipliers.  Returns dict(FG, HG (None without a path constraint), mask [f, f])."""
+    guarded = model if ntheta else None
+    unread = model if nsd else None
+    with _bound_theta(unread, _SdataGuard("F"), "sdata"):
+        FG = _contracted_gradient(F, nx, nu, nx, "lam", "F must return the next state", model, "theta" if ntheta else None, ntheta)
+    mask = hessian_mask(FG)
+    HG = None
+    if hfun is not None and nh:
+        with _bound_theta(guarded, _ThetaGuard("hfun")):
+            HG = _contracted_gradient(hfun, nx, nu, nh, "mu", "hfun must return the path-constraint values", model, "sdata" if nsd else None, nsd, "d")
+        mask = mask | hessian_mask(HG)
+    return dict(FG=FG, HG=HG, mask=mask)
+
+
+def link_is_linear(link):
+    """no output of the link-constraint tape has a second derivative (a rate limit and the like)"""
+    for o in link.outputs:
+        t = link.clone()
+        t.outputs = [o]
+        if hessian_mask(gradient_tape(t)).any():
+            return False
+    return True
+
+
 def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False,
-          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None, convexify=False):
+          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None, convexify=False, exact_hessian=False):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
@@ -548,7 +604,11 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     (mpcqp_stage_set_stage_data gives every frame of every instance its own row), without a derivative: the gradient and the Hessian's structure
     are over [s; u; r] as before.  F / cdyn, kfun and llink take none: reading self.sdata there raises a ValueError.
     convexify (models.StageOCP.convexify; needs lcost): the cost's mask becomes its component closure (closed_mask) and the library exports
-    mpcqp_user_convexify, the launcher of mpcqp_stage_convexify.  Without it the library is the text it always was."""
+    mpcqp_user_convexify, the launcher of mpcqp_stage_convexify.  Without it the library is the text it always was.
+    exact_hessian (models.StageOCP.exact_hessian; needs lcost, whose pattern has the off-diagonal slots): the functors FG and HG, the gradients over
+    [s; u] of lam' F and mu' hfun (trace_curvature); the structure of their Hessians joins the [s; u] block of the cost's mask before the closure of
+    convexify, and the library exports the launchers of mpcqp_stage_lagrangian.  A nonlinear kfun is refused: its curvature couples two frames.
+    Without it the library is the text it always was."""
     ntheta = int(ntheta)
     nsd = int(nsd)
     if nsd > NSD_MAX:
@@ -605,6 +665,12 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
                 LT, GT = trace_cost(lterm, nx, nu, nx, nsd, model)
             mask = mask | hessian_mask(GT)
         mask = mask | np.eye(mask.shape[0], dtype=bool)      # keep the diagonal in the pattern
+        if exact_hessian:
+            if tape.nk and not link_is_linear(tape.link):
+                raise ValueError("exact_hessian does not cover a nonlinear link constraint (kfun): its curvature couples two frames; a linear kfun "
+                                 "(rate limits) is fine")
+            tape.exact = trace_curvature(F, nx, nu, hfun if tape.nh else None, tape.nh, ntheta, nsd, model)
+            mask[:nx + nu, :nx + nu] |= tape.exact["mask"]
         if convexify:
             mask = closed_mask(mask)
             tape.convexify = True
@@ -613,6 +679,8 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
         raise ValueError("a terminal cost needs a stage cost")
     elif convexify:
         raise ValueError("convexify needs a stage cost (lcost): diagonal weights have nothing to convexify")
+    elif exact_hessian:
+        raise ValueError("exact_hessian needs a stage cost (lcost): the pattern of diagonal weights has no off-diagonal slots for the curvature")
     tape.link_cost = None
     if llink is not None:
         with _bound_theta(guarded, _ThetaGuard("llink")), _bound_theta(unread, _SdataGuard("llink"), "sdata"):
@@ -744,6 +812,14 @@ def emit_functor(tape, name="SmUser"):
             src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *sn, const T *un, T *out) {\n%s\n  }\n" % (fn, _emit_body(tp))
         lm = link_cost["mask"]
         src += "  static constexpr unsigned char lmask[%d] = {%s};\n" % (lm.size, ", ".join(str(int(v)) for v in lm.ravel()))
+    exact = getattr(tape, "exact", None)
+    if exact:
+        # FG: out[f] = d(lam' F)/d[s; u]; HG: out[f] = d(mu' H)/d[s; u] -- the multipliers are plain doubles like par and d (mpcqp_stage_lagrangian)
+        src += "  static constexpr int has_exact = 1;\n"
+        src += ("  template <class T> SM_HD static void FG(const double *" + ("par" if nth else "") + ", double, const T *s, const T *u, const double *lam, T *out) {\n%s\n  }\n"
+                % _emit_body(exact["FG"]))
+        if exact["HG"] is not None:
+            src += "  template <class T> SM_HD static void HG(const T *s, const T *u, const double *mu, %sT *out) {\n%s\n  }\n" % (dsig, _emit_body(exact["HG"]))
     src += "};\n"
     lo = ", ".join(_blit(v) for v in tape.h_lo) if nh else "0.0"
     hi = ", ".join(_blit(v) for v in tape.h_hi) if nh else "0.0"
@@ -757,6 +833,8 @@ def emit_functor(tape, name="SmUser"):
         src += "static const double %s_theta0[] = {%s};\n" % (name, ", ".join(_lit(v) for v in tape.theta0))
     if nsd:
         src += "static const double %s_sdata0[] = {%s};\n" % (name, ", ".join(_lit(v) for v in tape.sdata0))
+    if exact:
+        src += "static const unsigned char %s_curv_mask[] = {%s};\n" % (name, ", ".join(str(int(v)) for v in exact["mask"].ravel()))
     return src
 
 
@@ -794,8 +872,33 @@ int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
   return (int)stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream%(sdarg)s);
 }
-%(params)s%(link_cost)s%(sdata)s%(convexify)s}
+%(params)s%(link_cost)s%(sdata)s%(convexify)s%(exact)s}
 '''
+
+# a model with exact_hessian = True only: 1 and the structure of the constraint curvature over [s; u] (row-major f^2 bytes), and the launchers of
+# mpcqp_stage_lagrangian (slots: the handle's table of the curvature's slots; w: the convexification tables and scratch, used when a->mode != 0);
+# the _pp form of a library with parameters takes the rows, the _sd form of a library with stage data the rows of both.  A library without the
+# exports takes no constraint curvature
+_DEVICE_EXACT_TMPL = '''int mpcqp_user_exact_hessian(unsigned char *mask) {
+  constexpr int f = SmUser::nx + SmUser::nu;
+  for (int i = 0; i < f * f; i++) mask[i] = SmUser_curv_mask[i];
+  return 1;
+}
+int mpcqp_user_lagrangian(const StageDev *sd, int batch, const mpcqp_stage_lagrangian_args *a, const int *slots, const StageCvxBuf *w, void *stream) {
+  return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream%(sdarg)s);
+}
+'''
+_DEVICE_EXACT_PP_TMPL = '''int mpcqp_user_lagrangian_pp(const StageDev *sd, int batch, const mpcqp_stage_lagrangian_args *a, const int *slots, const StageCvxBuf *w, void *stream,
+                             const double *theta) {
+  return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
+}
+'''
+_DEVICE_EXACT_SD_TMPL = '''int mpcqp_user_lagrangian_sd(const StageDev *sd, int batch, const mpcqp_stage_lagrangian_args *a, const int *slots, const StageCvxBuf *w, void *stream,
+                             const double *theta, const double *d) {
+%(th_lagrangian)s  return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream, StageData{d});
+}
+'''
+_DEVICE_EXACT_SD_THETA = "  if (theta) return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n"
 
 # a model with convexify = True only: the launcher of mpcqp_stage_convexify (w: the handle's slot tables and scratch), and for a library with stage
 # data the form that takes the data rows.  A library without the export takes no convexification
@@ -943,7 +1046,28 @@ void user_host_path(const double *s, const double *u, double *out, double *jac) 
     for (int r = 0; r < nh; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
   }
 }
-%(sdata)s}
+%(sdata)s%(exact)s}
+'''
+
+# a functor with exact_hessian only: C [f * f] row-major = -sum_i lam_i d2F_i + sum_i mu_i d2h_i over [s; u], column c by one pass of FG (dyn != 0) and
+# HG on duals seeded on c, formed as -FG.d + HG.d (what a device thread does); theta [ntheta] and d [nsd] may be null = the defaults
+_HOST_EXACT_TMPL = '''void user_host_curvature(const double *theta, const double *s, const double *u, const double *lam, const double *mu, const double *d, int dyn, double *C) {
+  constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu;
+  (void)theta; (void)mu; (void)d;
+  for (int c = 0; c < f; c++) {
+    Dual sd[nx], ud[nu], gf[f], gh[f];
+    for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
+    for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
+    for (int r = 0; r < f; r++) { gf[r] = {0.0, 0.0}; gh[r] = {0.0, 0.0}; }
+    if (dyn) SmUser::FG<Dual>(%(th)s, 0.0, sd, ud, lam, gf);
+%(hg)s    for (int r = 0; r < f; r++) {
+      double v = 0.0;
+      if (dyn) v = -gf[r].d;
+      if (SmUser::nh > 0) v += gh[r].d;
+      C[r * f + c] = v;
+    }
+  }
+}
 '''
 
 # a functor with stage data only: the path constraint and the cost with a data row d [nsd] given (the exports above use the defaults)
@@ -1051,8 +1175,14 @@ def device_source(tape):
     cvx = ""
     if getattr(tape, "convexify", False):
         cvx = _DEVICE_CONVEXIFY_TMPL % sub + (_DEVICE_CONVEXIFY_SD_TMPL % sub if nsd else "")
+    exact = ""
+    if getattr(tape, "exact", None):
+        sub = dict(sub, cvxpp="true" if getattr(tape, "convexify", False) else "false")
+        exact = _DEVICE_EXACT_TMPL % sub + (_DEVICE_EXACT_PP_TMPL % sub if nth else "")
+        if nsd:
+            exact += _DEVICE_EXACT_SD_TMPL % dict(sub, th_lagrangian=_DEVICE_EXACT_SD_THETA % sub if nth else "")
     return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if nth else "",
-                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "", sdata=sdata, convexify=cvx)
+                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "", sdata=sdata, convexify=cvx, exact=exact)
 
 
 def build_device_library(tape):
@@ -1066,7 +1196,17 @@ def host_source(tape):
     nth, nsd = getattr(tape, "ntheta", 0), getattr(tape, "nsd", 0)
     return _HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr",
                          "link_cost": _HOST_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "",
-                         "hd": "SmUser_sdata0, " if nsd else "", "sdata": _HOST_SDATA_TMPL if nsd else ""}
+                         "hd": "SmUser_sdata0, " if nsd else "", "sdata": _HOST_SDATA_TMPL if nsd else "", "exact": _host_exact(tape, nth, nsd)}
+
+
+def _host_exact(tape, nth, nsd):
+    exact = getattr(tape, "exact", None)
+    if not exact:
+        return ""
+    hg = ""
+    if exact["HG"] is not None:
+        hg = "    SmUser::HG<Dual>(sd, ud, mu, %sgh);\n" % ("d ? d : SmUser_sdata0, " if nsd else "")
+    return _HOST_EXACT_TMPL % {"th": "theta ? theta : SmUser_theta0" if nth else "nullptr", "hg": hg}
 
 
 def build_host_library(tape):

@@ -43,6 +43,12 @@ struct StageUserLib {
   // the _sd form of a library with stage data takes the data rows last (lcost / lterm read no theta: there is no _pp form)
   int (*convexify)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, void *) = nullptr;
   int (*convexify_sd)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, void *, const double *) = nullptr;
+  // optional, a library generated from a model with exact_hessian = True (mpcqp_stage_lagrangian): the curvature's slot table, the convexification's
+  // tables and scratch (null when the library has none), then the stream; the _pp form takes the parameter rows, the _sd form the rows of both
+  int (*lagrangian)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, void *) = nullptr;
+  int (*lagrangian_pp)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, void *, const double *) = nullptr;
+  int (*lagrangian_sd)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, void *, const double *,
+                       const double *) = nullptr;
   bool all_pp() const { return eval_pp && merit_pp && advance_pp && linesearch_pp; }
   bool all_sd() const { return eval_sd && merit_sd && advance_sd && linesearch_sd; }
 };
@@ -56,6 +62,8 @@ static StageUserLib stage_user_lib(void *lib) {
   stage_sym(lib, "mpcqp_user_eval_sd", u.eval_sd); stage_sym(lib, "mpcqp_user_merit_sd", u.merit_sd);
   stage_sym(lib, "mpcqp_user_advance_sd", u.advance_sd); stage_sym(lib, "mpcqp_user_linesearch_sd", u.linesearch_sd);
   stage_sym(lib, "mpcqp_user_convexify", u.convexify); stage_sym(lib, "mpcqp_user_convexify_sd", u.convexify_sd);
+  stage_sym(lib, "mpcqp_user_lagrangian", u.lagrangian); stage_sym(lib, "mpcqp_user_lagrangian_pp", u.lagrangian_pp);
+  stage_sym(lib, "mpcqp_user_lagrangian_sd", u.lagrangian_sd);
   return u;
 }
 
@@ -95,6 +103,10 @@ struct mpcqp_stage {
   int *dslots = nullptr;
   double *dcvx = nullptr;
   int cvx_cap = 0;
+  // the exact Lagrangian Hessian (mpcqp_stage_lagrangian): the slot table of the constraint curvature [N * f * f], built with the handle of a
+  // library that exports the launchers
+  bool exact = false;
+  int *dlslots = nullptr;
 };
 
 // a launch may not be larger than a stored parameter set
@@ -253,6 +265,26 @@ static int stage_build_convexify_tables(mpcqp_stage *s, const unsigned char *mas
   return MPCQP_OK;
 }
 
+// Slot table of mpcqp_stage_lagrangian: element (r, c) of frame k's curvature C_k over [s; u] sits in column np + k f + c, row np + k f + r of P; -1
+// outside the curvature's structure `mask` (f^2 bytes).  The slot is found in the pattern itself, as for the convexification tables.
+static int stage_build_lagrangian_table(mpcqp_stage *s, const unsigned char *mask) {
+  const StageDev &sd = s->sd;
+  const int f = sd.f, N = sd.N;
+  std::vector<int> tab((size_t)N * f * f, -1);
+  for (int k = 0; k < N; k++)
+    for (int r = 0; r < f; r++)
+      for (int c = 0; c < f; c++) {
+        if (!mask[r * f + c]) continue;
+        const int col = sd.np + k * f + c, row = sd.np + k * f + r;
+        for (int e = s->Pp[col]; e < s->Pp[col + 1]; e++) if (s->Pi[e] == row) tab[((size_t)k * f + r) * f + c] = e;
+      }
+  if (hipMalloc(&s->dlslots, tab.size() * sizeof(int)) != hipSuccess ||
+      hipMemcpy(s->dlslots, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+    return mpcqp_set_error(MPCQP_ERR_HIP, "upload of the curvature's slot table failed");
+  s->exact = true;
+  return MPCQP_OK;
+}
+
 static int stage_create_zoo(const mpcqp_stage_desc *d, bool pref, mpcqp_stage **out) {
   if (!out) return mpcqp_set_error(MPCQP_ERR_ARG, "out is null");
   *out = nullptr;
@@ -347,6 +379,15 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   if (s->general_cost && user.convexify && (s->nsd == 0 || user.convexify_sd)) {
     if (int rc = stage_build_convexify_tables(s, mask.data())) { mpcqp_stage_destroy(s); return rc; }
   }
+  // optional exports of a library generated with exact_hessian = True: the structure of the constraint curvature over [s; u] -- part of the cost mask,
+  // so every element has a slot in the pattern just built -- and the launchers of mpcqp_stage_lagrangian, one for every kind of data the library takes
+  {
+    auto ef = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_exact_hessian");
+    std::vector<unsigned char> cmask((size_t)(nx + nu) * (nx + nu));
+    if (s->general_cost && ef && ef(cmask.data()) && user.lagrangian && (s->ntheta == 0 || user.lagrangian_pp) && (s->nsd == 0 || user.lagrangian_sd)) {
+      if (int rc = stage_build_lagrangian_table(s, cmask.data())) { mpcqp_stage_destroy(s); return rc; }
+    }
+  }
   *out = s;
   return MPCQP_OK;
 }
@@ -373,6 +414,7 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   for (int w = 0; w < 2; w++) if (s->dsd[w]) (void)hipFree(s->dsd[w]);
   if (s->dslots) (void)hipFree(s->dslots);
   if (s->dcvx) (void)hipFree(s->dcvx);
+  if (s->dlslots) (void)hipFree(s->dlslots);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -584,6 +626,22 @@ int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesear
 
 int mpcqp_stage_has_convexify(const mpcqp_stage *s) { return s && s->convexify ? 1 : 0; }
 
+// the scratch of a convexification launch, grown on first use, and the handle's tables as the kernels take them
+static int stage_convexify_buffers(mpcqp_stage *s, int batch, StageCvxBuf *w) {
+  const StageDev &sd = s->sd;
+  const size_t nx2 = (size_t)sd.nx * sd.nx;
+  if (batch > s->cvx_cap) {
+    double *nb = nullptr;
+    MPCQP_HIPCHK(hipMalloc(&nb, (size_t)batch * sd.N * (nx2 * sizeof(double) + sizeof(int))));
+    MPCQP_HIPCHK(hipDeviceSynchronize());       // a launch that uses the old scratch may still be queued
+    if (s->dcvx) (void)hipFree(s->dcvx);
+    s->dcvx = nb; s->cvx_cap = batch;
+  }
+  const int nl = sd.f + sd.nx;
+  *w = StageCvxBuf{s->dslots, s->dslots + (size_t)sd.N * nl * nl, s->dcvx, (int *)(s->dcvx + (size_t)s->cvx_cap * sd.N * nx2)};
+  return MPCQP_OK;
+}
+
 int mpcqp_stage_convexify(mpcqp_stage *s, int batch, const mpcqp_stage_convexify_args *a, void *stream) {
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
@@ -599,17 +657,39 @@ int mpcqp_stage_convexify(mpcqp_stage *s, int batch, const mpcqp_stage_convexify
   if (s->sd_batch > 0 && batch > s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch is larger than the stored stage data (mpcqp_stage_set_stage_data)");
   MPCQP_HIPCHK(hipSetDevice(s->device));
   const StageDev &sd = s->sd;
-  const size_t nx2 = (size_t)sd.nx * sd.nx;
-  if (batch > s->cvx_cap) {
-    double *nb = nullptr;
-    MPCQP_HIPCHK(hipMalloc(&nb, (size_t)batch * sd.N * (nx2 * sizeof(double) + sizeof(int))));
-    MPCQP_HIPCHK(hipDeviceSynchronize());       // a launch that uses the old scratch may still be queued
-    if (s->dcvx) (void)hipFree(s->dcvx);
-    s->dcvx = nb; s->cvx_cap = batch;
-  }
-  const int nl = sd.f + sd.nx;
-  const StageCvxBuf w{s->dslots, s->dslots + (size_t)sd.N * nl * nl, s->dcvx, (int *)(s->dcvx + (size_t)s->cvx_cap * sd.N * nx2)};
+  StageCvxBuf w;
+  if (int rc = stage_convexify_buffers(s, batch, &w)) return rc;
   MPCQP_HIPCHK((hipError_t)(s->nsd > 0 ? s->user.convexify_sd(&sd, batch, a, &w, stream, s->sdata()) : s->user.convexify(&sd, batch, a, &w, stream)));
+  return MPCQP_OK;
+}
+
+int mpcqp_stage_has_exact_hessian(const mpcqp_stage *s) { return s && s->exact ? 1 : 0; }
+
+int mpcqp_stage_lagrangian(mpcqp_stage *s, int batch, const mpcqp_stage_lagrangian_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (a->mode != 0 && a->mode != MPCQP_CONVEXIFY_PROJECT && a->mode != MPCQP_CONVEXIFY_MIRROR)
+    return mpcqp_set_error(MPCQP_ERR_ARG, "mode must be 0, MPCQP_CONVEXIFY_PROJECT or MPCQP_CONVEXIFY_MIRROR");
+  if (a->mode != 0 && (!(a->eps > 0.0) || !std::isfinite(a->eps))) return mpcqp_set_error(MPCQP_ERR_ARG, "eps must be positive and finite");
+  if (!a->P || !a->x || !a->y || (a->mode != 0 && s->sd.np > 0 && !a->p)) return mpcqp_set_error(MPCQP_ERR_ARG, "x, y and P (with a mode: p) are required");
+  if (s->sd.model != MPCQP_MODEL_USER)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the built-in models have diagonal weights: their pattern has no slots for the constraint curvature (a generated model with lcost and exact_hessian = True has)");
+  if (!s->exact)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_lagrangian: regenerate it from a model with a stage cost (lcost) and exact_hessian = True");
+  if (a->mode != 0 && !s->convexify)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "a mode needs the convexification: regenerate the library from a model that also sets convexify = True");
+  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
+  if (s->sd_batch > 0 && batch > s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch is larger than the stored stage data (mpcqp_stage_set_stage_data)");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const StageDev &sd = s->sd;
+  StageCvxBuf w;
+  if (a->mode != 0) if (int rc = stage_convexify_buffers(s, batch, &w)) return rc;
+  const StageCvxBuf *wp = a->mode != 0 ? &w : nullptr;
+  const double *th = s->theta(MPCQP_PARAMS_MODEL);
+  MPCQP_HIPCHK((hipError_t)(s->nsd > 0 ? s->user.lagrangian_sd(&sd, batch, a, s->dlslots, wp, stream, th, s->sdata())
+                            : th     ? s->user.lagrangian_pp(&sd, batch, a, s->dlslots, wp, stream, th)
+                                     : s->user.lagrangian(&sd, batch, a, s->dlslots, wp, stream)));
   return MPCQP_OK;
 }
 

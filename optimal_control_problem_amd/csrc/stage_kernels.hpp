@@ -786,17 +786,104 @@ template <class M> struct stage_cvx {
 // on their way to the second pass; flags [batch * N], 1 = the frame was touched
 struct StageCvxBuf { const int *slots, *ppslot; double *rr; int *flags; };
 
+// The exact Lagrangian Hessian (mpcqp_stage_lagrangian; models.StageOCP.constraint_curvature and lagrangian_system are its host statement; DESIGN
+// 6.18).  Generated functors with M::has_exact carry FG and HG, the gradients over [s; u] of lam' F and mu' H with the multipliers as plain doubles.
+// StageExact is the pack element that switches the curvature on in stage_convexify_kernel (off by default: an instance without it keeps its
+// signature and its code): y [batch * m] the multiplier estimate, rows [p; x; dynamics; path; link]; status [batch] or null.
+struct StageExact { const double *y; const int *status; };
+template <class M, class = void> struct sm_has_exact : std::false_type {};
+template <class M> struct sm_has_exact<M, std::void_t<decltype(M::has_exact)>> : std::bool_constant<M::has_exact != 0> {};
+// column c of C_k = -sum_i lam_i d2F_i + sum_i mu_i d2h_i over [s_k; u_k]: the dual parts of FG (k < N-1) and HG on the frame seeded on c, formed as
+// -FG.d + HG.d in that order.  yb: the instance's row of y; par: the parameters F takes; dv: the frame's stage data
+template <class M> __device__ __forceinline__ void stage_curvature_column(const StageDev &sd, int k, const Dual *s, const Dual *uu, const double *yb,
+                                                                          const double *par, const double *dv, double (&cv)[M::nx + M::nu]) {
+  constexpr int nx = M::nx, f = M::nx + M::nu;
+#pragma unroll
+  for (int r = 0; r < f; r++) cv[r] = 0.0;
+  if (k < sd.N - 1) {
+    const double *yd = yb + sd.n + k * nx;
+    double lam[nx];
+#pragma unroll
+    for (int i = 0; i < nx; i++) lam[i] = yd[i];
+    Dual g[f];
+    M::template FG<Dual>(par, sd.dt, s, uu, lam, g);
+#pragma unroll
+    for (int r = 0; r < f; r++) cv[r] = -g[r].d;
+  }
+  if constexpr (M::nh > 0) {
+    constexpr int nh = M::nh;
+    const double *yh = yb + sd.n + sd.ngd + k * nh;
+    double mu[nh];
+#pragma unroll
+    for (int i = 0; i < nh; i++) mu[i] = yh[i];
+    Dual g[f];
+    if constexpr (sm_nsd<M>::value > 0) M::template HG<Dual>(s, uu, mu, dv, g); else M::template HG<Dual>(s, uu, mu, g);
+#pragma unroll
+    for (int r = 0; r < f; r++) cv[r] += g[r].d;
+  }
+}
+
+// One thread per (instance, frame, column c of [s; u]): the column of C_k is added to its slots of P through the table the handle built from the
+// pattern (slots [N * f * f], entry (k, r, c), -1 = outside the curvature's structure).  Each entry has one writer -- read, add, write; no atomics --
+// so the result is bitwise repeatable and does not depend on the batch or the instance's position.  Adjacent lanes own adjacent columns: the store
+// streams are those of stage_eval_kernel.  An instance whose status is given and is not one with a point is neither read nor written.
+template <class M, class... PP>
+__global__ void __launch_bounds__(256) stage_lagrangian_kernel(StageDev sd, int batch, const double *__restrict__ x, StageExact ex,
+                                                               const int *__restrict__ slots, double *__restrict__ P, PP... pp) {
+  constexpr int NT = sm_ntheta<M>::value > 0 ? sm_ntheta<M>::value : 1;
+  constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int N = sd.N, per = N * f;
+  if (gid >= (long)batch * per) return;
+  const int b = (int)(gid / per), jj = (int)(gid - (long)b * per), k = jj / f, c = jj - k * f;
+  if (ex.status && !stage_status_ok(ex.status[b])) return;
+  double th[NT];
+  const double *par = sd.par;
+  if constexpr (stage_has<StageTheta, PP...>) {
+    const double *row = stage_theta(pp...).model + (long)b * SM_NPAR;
+#pragma unroll
+    for (int i = 0; i < NT; i++) th[i] = row[i];
+    par = th;
+  }
+  const double *fr = x + (long)b * sd.nvar + k * f;
+  double dv[sm_nsd_regs<M>];
+  stage_load_data<M>(dv, b, N, k, pp...);
+  Dual s[nx], uu[nu];
+#pragma unroll
+  for (int i = 0; i < nx; i++) s[i] = {fr[i], i == c ? 1.0 : 0.0};
+#pragma unroll
+  for (int i = 0; i < nu; i++) uu[i] = {fr[nx + i], nx + i == c ? 1.0 : 0.0};
+  double cv[f];
+  stage_curvature_column<M>(sd, k, s, uu, ex.y + (long)b * sd.m, par, dv, cv);
+  const int *sl = slots + (long)k * f * f + c;
+  double *Pb = P + (long)b * sd.nnzP;
+#pragma unroll
+  for (int r = 0; r < f; r++) {
+    const int slot = sl[r * f];
+    if (slot >= 0) Pb[slot] += cv[r];
+  }
+}
+
+// PP may hold a StageExact (mpcqp_stage_lagrangian with a mode): the tile is then H_k^L = H_k + C_k, C_k zero-padded over r -- the lanes < f add
+// stage_curvature_column's values, the expression stage_lagrangian_kernel added to P before this launch -- F takes the StageTheta of the pack, and an
+// instance whose status has no point is skipped (no read, no write but its flags = 0)
 template <class M, bool PF = false, class... PP>
 __global__ void __launch_bounds__(stage_cvx<M>::G * stage_cvx<M>::W) stage_convexify_kernel(StageDev sd, int batch, mpcqp_stage_convexify_args a,
                                                                                             StageCvxBuf w, PP... pp) {
   using C = stage_cvx<M>;
+  constexpr bool EX = stage_has<StageExact, PP...>;
   constexpr int nx = M::nx, nu = M::nu, f = nx + nu, nl = C::nl, W = C::W, G = C::G;
   __shared__ double lds[G][2][nl * nl];
   const int grp = threadIdx.x / W, lane = threadIdx.x - grp * W;
   const int N = sd.N;
   const long item = (long)blockIdx.x * G + grp;                     // (instance, frame); a group past the end walks the barriers without work
-  const bool live = item < (long)batch * N;
+  bool live = item < (long)batch * N;
   const int b = live ? (int)(item / N) : 0, k = live ? (int)(item - (long)b * N) : 0;
+  [[maybe_unused]] const bool inside = live;
+  if constexpr (EX) {
+    const StageExact ex = stage_get<StageExact>(pp...);
+    if (live && ex.status && !stage_status_ok(ex.status[b])) live = false;
+  }
   double *A = lds[grp][0], *V = lds[grp][1];
   if (live && lane < nl) {
     // column `lane` of H_k: one pass of the generated gradient on dual numbers seeded on input `lane` of [s; u; r_k] -- the call, and so the
@@ -810,8 +897,25 @@ __global__ void __launch_bounds__(stage_cvx<M>::G * stage_cvx<M>::W) stage_conve
 #pragma unroll
     for (int i = 0; i < nu; i++) uu[i] = {fr[nx + i], nx + i == lane ? 1.0 : 0.0};
     stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
+    if constexpr (EX) {
+      constexpr int NT = sm_ntheta<M>::value > 0 ? sm_ntheta<M>::value : 1;
+      double cv[f], th[NT];
+      const double *par = sd.par;
+      if constexpr (stage_has<StageTheta, PP...>) {
+        const double *row = stage_theta(pp...).model + (long)b * SM_NPAR;
 #pragma unroll
-    for (int r = 0; r < nl; r++) A[r * nl + lane] = g[r].d;
+        for (int i = 0; i < NT; i++) th[i] = row[i];
+        par = th;
+      }
+#pragma unroll
+      for (int r = 0; r < f; r++) cv[r] = 0.0;
+      if (lane < f) stage_curvature_column<M>(sd, k, s, uu, stage_get<StageExact>(pp...).y + (long)b * sd.m, par, dv, cv);
+#pragma unroll
+      for (int r = 0; r < nl; r++) A[r * nl + lane] = r < f ? g[r].d + cv[r] : g[r].d;
+    } else {
+#pragma unroll
+      for (int r = 0; r < nl; r++) A[r * nl + lane] = g[r].d;
+    }
   }
   sm_jacobi<W>(A, V, nl, lane, live);
   const double lmin = sm_convexify_lam_min<W>(A, nl, lane);
@@ -833,6 +937,9 @@ __global__ void __launch_bounds__(stage_cvx<M>::G * stage_cvx<M>::W) stage_conve
   if (live && lane == 0) {
     w.flags[item] = touched ? 1 : 0;
     if (a.lam_min) a.lam_min[item] = lmin;
+  }
+  if constexpr (EX) {
+    if (inside && !live && lane == 0) w.flags[item] = 0;      // a skipped instance: the second pass finds no touched frame
   }
 }
 
@@ -896,6 +1003,35 @@ inline hipError_t stage_launch_convexify(const StageDev &sd, int batch, const mp
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     stage_convexify_sum_kernel<M><<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(batch, sd.N, sd.nnzP, w, a.P, a.touched);
     return hipGetLastError();
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+
+// mpcqp_stage_lagrangian: the add kernel, then -- with a mode -- the convexify kernel with the StageExact element and its sum kernel on the updated P,
+// so that a frame the convexification does not touch holds the bits mode = 0 gives.  slots: the curvature's table; w: the convexification's (mode != 0)
+// (CVX: the library also carries the convexification -- without it only the add kernel is instantiated and a mode is an invalid value)
+template <class M, bool PF, bool CVX, class... PP>
+inline hipError_t stage_launch_lagrangian(const StageDev &sd, int batch, const mpcqp_stage_lagrangian_args &a, const int *slots, const StageCvxBuf *w,
+                                          hipStream_t st, PP... pp) {
+  if constexpr (sm_has_exact<M>::value) {
+    const StageExact ex{a.y, a.status};
+    const long threads = (long)batch * sd.N * (M::nx + M::nu);
+    stage_lagrangian_kernel<M, PP...><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(sd, batch, a.x, ex, slots, a.P, pp...);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (a.mode == 0) return hipSuccess;
+    if constexpr (CVX) {
+      if (!w) return hipErrorInvalidValue;
+      using C = stage_cvx<M>;
+      const mpcqp_stage_convexify_args ca{a.mode, a.eps, a.p, a.x, a.P, a.touched, a.lam_min};
+      const long items = (long)batch * sd.N, entries = (long)batch * M::nx * M::nx;
+      stage_convexify_kernel<M, PF, PP..., StageExact><<<(unsigned)((items + C::G - 1) / C::G), C::G * C::W, 0, st>>>(sd, batch, ca, *w, pp..., ex);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+      stage_convexify_sum_kernel<M><<<(unsigned)((entries + 255) / 256), 256, 0, st>>>(batch, sd.N, sd.nnzP, *w, a.P, a.touched);
+      return hipGetLastError();
+    } else {
+      return hipErrorInvalidValue;
+    }
   } else {
     return hipErrorInvalidValue;
   }

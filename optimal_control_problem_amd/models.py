@@ -229,6 +229,13 @@ class StageOCP:
     convexify = False
     CONVEXIFY_MODES = {"project": 1, "mirror": 2}      # MPCQP_CONVEXIFY_*
 
+    # opt-in exact Lagrangian Hessian: a model with lcost sets exact_hessian = True and the SQP loops (options["exact_hessian"]) add the
+    # curvature of the constraints, C_k = -sum_i lam_i d2F_i + sum_i mu_i d2h_i over [s_k; u_k], to the Hessian of the cost that the reference's QP
+    # takes (hessian(f, w), src/sqp_solver/SQPOptimizationSolver.cpp:55-60).  The flag ORs the structure of C_k into the [s; u] block of cost_mask
+    # (before the closure of convexify), so that lagrangian_system (host) and mpcqp_stage_lagrangian (device) find a slot for every entry, and makes
+    # the generated library carry the functors FG, HG and export the launchers.  Without the flag nothing changes: the same mask, pattern and source.
+    exact_hessian = False
+
     def set_stage_data(self, d=None):
         """Host statement of mpcqp_stage_set_stage_data.  d [B, N, nsd]: frame k of instance b takes row d[b, k] in hfun, lcost and lterm -- in
         path_values, dh, constraints, objective, cost_derivatives, local_system, violation, line_search and the stage_cost of advance (d[b, 0]).
@@ -340,8 +347,12 @@ class StageOCP:
                 self._lttape, self._gttape = codegen.trace_cost(self.lterm, self.nx, self.nu, self.nx, **dkw)
                 mask = mask | codegen.hessian_mask(self._gttape)
             self.cost_mask = mask | np.eye(mask.shape[0], dtype=bool)
+            if self.exact_hessian:
+                self._trace_curvature(codegen)
             if self.convexify:
                 self.cost_mask = codegen.closed_mask(self.cost_mask)
+        elif self.exact_hessian:
+            raise ValueError("exact_hessian needs a stage cost (lcost): the pattern of diagonal weights has no off-diagonal slots for the curvature")
         self.link_cost = self.llink is not None
         if self.link_cost:
             from . import codegen
@@ -544,6 +555,113 @@ class StageOCP:
                 touched[b] += 1; any_touched = True
                 e = per_frame[k]
                 P_new[b, e[:, 3]] += D[e[:, 1], e[:, 2]]
+                acc += D
+            if any_touched and len(summed):
+                P_new[b, summed[:, 3]] += acc[summed[:, 1], summed[:, 2]]
+        return P_new, touched, lam_min
+
+    # -- the exact Lagrangian Hessian (include/mpcqp.h, mpcqp_stage_lagrangian; csrc/stage_kernels.hpp stage_lagrangian_kernel) ----------
+    def _trace_curvature(self, codegen):
+        """the gradient tapes of lam' F and mu' hfun over [s; u] (codegen.trace_curvature, what the generated library compiles) and the structure of
+        their Hessians, which joins the [s; u] block of cost_mask"""
+        if self.nk and not codegen.link_is_linear(codegen._trace_link(self.kfun, self.nx, self.nu, self.nk)):
+            raise ValueError("exact_hessian does not cover a nonlinear link constraint (kfun): its curvature couples two frames; a linear kfun "
+                             "(rate limits) is fine")
+        # (the zoo classes on the generated path keep their constants in the code: no parameter inputs, as in stage_eval.StageEvaluator)
+        self._curv_ntheta = 0 if isinstance(self, (Quadrotor, CartPole)) else int(self.ntheta)
+        t = codegen.trace_curvature(self.F, self.nx, self.nu, self.hfun if self.nh else None, self.nh, self._curv_ntheta, self.nsd, self)
+        self._fgtape, self._hgtape, self.curvature_mask = t["FG"], t["HG"], t["mask"]
+        self.cost_mask[:self.f, :self.f] |= self.curvature_mask
+
+    @staticmethod
+    def _tape_hessian(gtape, inputs, f):
+        """[..., f, f]: the derivative of the gradient tape's f outputs over its first f inputs, column by column by complex-step differentiation
+        (exact to rounding), like cost_derivatives"""
+        shape = np.shape(inputs[0]); eps = 1e-30
+        out = np.zeros(shape + (f, f))
+        for c in range(f):
+            ins = [np.asarray(v).astype(complex) for v in inputs]
+            ins[c] = ins[c] + 1j * eps
+            out[..., :, c] = np.stack([np.broadcast_to(np.asarray(o), shape) for o in gtape.evaluate(ins)], axis=-1).imag / eps
+        return out
+
+    def constraint_curvature(self, x, y):
+        """C [B, N, f, f]: the curvature of the constraints at x under the multipliers y [B, m] (rows [p; x; dynamics; path; link], what mpcqp_get
+        returns), C_k = -sum_i y_dyn[k, i] d2F_i(s_k, u_k) (k < N-1) + sum_i y_path[k, i] d2h_i(s_k, u_k), formed as -CF + CH.  F takes the
+        instance's parameter row, hfun the frame's stage-data row.  The rows p and x are linear; a link constraint must be (trace refuses another)."""
+        if not (self.general_cost and self.exact_hessian):
+            raise ValueError("the constraint curvature needs a model with a stage cost (lcost) and exact_hessian = True")
+        x = np.asarray(x, float); y = np.asarray(y, float)
+        B = x.shape[0]; N, nx, nh, f, n = self.N, self.nx, self.nh, self.f, self.n
+        s, u = self.frames(x)
+        frame = [s[..., i] for i in range(nx)] + [u[..., i] for i in range(self.nu)]
+        lam = np.zeros((B, N, nx))
+        lam[:, :N - 1] = y[:, n:n + self.ngd].reshape(B, N - 1, nx)
+        par = []
+        if self._curv_ntheta:
+            rows = self._theta_rows
+            if rows is not None and rows.shape[0] < B:
+                raise ValueError("batch %d is larger than the stored per-instance parameters (%d rows)" % (B, rows.shape[0]))
+            rows = np.broadcast_to(np.asarray(self.theta, float), (B, self._curv_ntheta)) if rows is None else rows[:B]
+            par = [np.broadcast_to(rows[:, i:i + 1], (B, N)) for i in range(self._curv_ntheta)]
+        C = -self._tape_hessian(self._fgtape, frame + par + [lam[..., i] for i in range(nx)], f)
+        C[:, N - 1] = 0.0                                       # the last frame has no dynamics row
+        if nh:
+            mu = y[:, n + self.ngd:n + self.ngd + N * nh].reshape(B, N, nh)
+            d = self._stage_data(B) if self.nsd else None
+            data = [d[..., i] for i in range(self.nsd)] if self.nsd else []
+            C = C + self._tape_hessian(self._hgtape, frame + [mu[..., i] for i in range(nh)] + data, f)
+        return C
+
+    def lagrangian_system(self, p, x, y, P, status=None, mode=None, eps=1e-6):
+        """Host statement of mpcqp_stage_lagrangian.  P [B, nnzP] as local_system wrote it at (p, x) -> (P_new, touched [B] int, lam_min [B, N]).
+        Every frame's curvature C_k (constraint_curvature) is added to the frame's slots of the [s; u] block (_P_src; the entries of curvature_mask).
+        With mode ("project" / "mirror"; a model that also sets convexify = True) the rule of convexify_system then runs on H_k^L = H_k + C_k, C_k
+        zero-padded over r: a frame with lam_min(H_k^L) < eps takes the correction V (f(Lambda) - Lambda) V' on top, a shared reference's p-p block the
+        sum over the touched frames, k ascending; an untouched frame keeps the bits mode = None gives.  An instance whose status is not in STATUS_OK
+        keeps every bit of P, counts no touched frame and has lam_min = NaN.  Without mode, touched is zero and lam_min NaN.  q, A, l, u do not change."""
+        if not (self.general_cost and self.exact_hessian):
+            raise ValueError("the Lagrangian Hessian needs a model with a stage cost (lcost) and exact_hessian = True")
+        if mode is not None:
+            if not self.convexify:
+                raise ValueError("a mode needs a model that also sets convexify = True")
+            if mode not in self.CONVEXIFY_MODES:
+                raise ValueError("mode must be None, 'project' or 'mirror'")
+            eps = float(eps)
+            if not (eps > 0.0 and np.isfinite(eps)):
+                raise ValueError("eps must be positive and finite")
+        p = np.asarray(p, float); x = np.asarray(x, float)
+        C = self.constraint_curvature(x, y)
+        B, N, f = C.shape[:3]
+        ok = np.ones(B, bool) if status is None else np.isin(np.asarray(status), self.STATUS_OK)
+        P_new = np.array(P, float)
+        touched = np.zeros(B, np.int64); lam_min = np.full((B, N), np.nan)
+        src = self._P_src
+        e = src[(src[:, 0] >= 0) & (src[:, 1] < f) & (src[:, 2] < f)]
+        e = e[self.curvature_mask[e[:, 1], e[:, 2]]]
+        for b in np.nonzero(ok)[0]:
+            P_new[b, e[:, 3]] += C[b, e[:, 0], e[:, 1], e[:, 2]]
+        if mode is None:
+            return P_new, touched, lam_min
+        _, hess = self.cost_derivatives(p, x)
+        nl = hess.shape[2]
+        per_frame = [src[src[:, 0] == k] for k in range(N)]
+        summed = src[src[:, 0] < 0]
+        for b in np.nonzero(ok)[0]:
+            acc = np.zeros((nl, nl)); any_touched = False
+            for k in range(N):
+                HL = hess[b, k].copy()
+                HL[:f, :f] += C[b, k]
+                lam, V = np.linalg.eigh(HL)
+                lam_min[b, k] = lam[0]
+                if not lam[0] < eps:
+                    continue
+                a = np.abs(lam) if mode == "mirror" else lam
+                D = (V * (np.maximum(a, eps) - lam)) @ V.T
+                D = 0.5 * (D + D.T)                          # (both triangles the same bits)
+                touched[b] += 1; any_touched = True
+                ek = per_frame[k]
+                P_new[b, ek[:, 3]] += D[ek[:, 1], ek[:, 2]]
                 acc += D
             if any_touched and len(summed):
                 P_new[b, summed[:, 3]] += acc[summed[:, 1], summed[:, 2]]

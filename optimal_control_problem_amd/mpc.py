@@ -23,6 +23,9 @@ class ClosedLoopMPC:
         if tail not in ("repeat", "rollout"):
             raise ValueError("tail must be 'repeat' or 'rollout'")
         opts = dict(options or {})
+        if opts.get("exact_hessian"):
+            raise ValueError("exact_hessian is not available in ClosedLoopMPC: the multiplier estimate would need its own shift in advance, and "
+                             "running a tick with unshifted multipliers would be silently wrong")
         opts.setdefault("max_iter", 1); opts.setdefault("alpha", 1.0); opts.setdefault("skip_failed_steps", True)
         self.model, self.batch, self.tail, self.shift = model, int(batch), tail, bool(shift)
         self.sol = DeviceSQPOptimizationSolver(model, opts, batch=self.batch, device=device, codegen=codegen)

@@ -18,6 +18,11 @@ indices; with warm_start_admm the remaining step is (1 - alpha_b) dx per instanc
 Opt-in as well: options["convexify"] = "project", "mirror" or a dict {mode, eps} replaces, before every QP, each frame Hessian of a general stage cost that has
 an eigenvalue below eps by V f(Lambda) V' (models.StageOCP.convexify_system states the rule, mpcqp_stage_convexify runs it on the device); the gradient stays
 exact; `convexified` holds the touched-frame counts per iteration.  For models with lcost that set convexify = True.
+Opt-in as well: options["exact_hessian"] = True adds the curvature of the constraints to P before every QP, so that the QP takes the Hessian of the
+Lagrangian instead of the reference's hessian(f, w) (:55-60; models.StageOCP.lagrangian_system states the rule, mpcqp_stage_lagrangian runs it on the
+device).  The loops keep a multiplier estimate lam [batch, m], zero at the start -- the first QP is the reference's -- and after each QP the instances
+whose QP returned a point take lam += alpha_b (y - lam), alpha_b the step length actually taken; setInitialGuess resets it.  With options["convexify"]
+the same call convexifies H_k + C_k.  For models with lcost that set exact_hessian = True.
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -71,6 +76,16 @@ def _convexify_options(value, model):
     return opts["mode"], eps
 
 
+def _exact_hessian_option(value, model):
+    """options["exact_hessian"]: falsy = off; True needs a stage OCP with a stage cost that sets exact_hessian = True"""
+    if not value:
+        return False
+    if not (getattr(model, "general_cost", False) and getattr(model, "exact_hessian", False)):
+        raise ValueError("exact_hessian needs a stage OCP with a stage cost (lcost) that sets exact_hessian = True: the flag puts the curvature's "
+                         "structure into the pattern and makes the generated library carry the kernel")
+    return True
+
+
 class SQPOptimizationSolver:
     def __init__(self, nlp, options, batch=1, qp_solver=None):
         """nlp: a models.* object (local_system / objective / n, m, np, nx...).  options: max_iter, alpha, verbose."""
@@ -106,6 +121,9 @@ class SQPOptimizationSolver:
         # (models.StageOCP.convexify_system); `convexified` holds the touched-frame counts per instance, one array per iteration
         self.convexify = _convexify_options(options.get("convexify"), nlp)
         self.convexified = []
+        # opt-in: the QP takes the Hessian of the Lagrangian under the multiplier estimate `lam` (models.StageOCP.lagrangian_system)
+        self.exact_hessian = _exact_hessian_option(options.get("exact_hessian"), nlp)
+        self.lam = np.zeros((self.batch, nlp.m)) if self.exact_hessian else None
         self.alpha_taken = None; self.accepted = None; self.gmax = None
         self.last_line_search = None                     # the NumPy statement's full result for the last iteration
         self._mu = None                                  # the penalty, monotone across iterations and calls
@@ -120,6 +138,8 @@ class SQPOptimizationSolver:
     def setInitialGuess(self, x):
         """extension: the reference ignores arg["x0"] and starts from zero (:88-91); this overwrites the stored iterate"""
         self._mu = None
+        if self.exact_hessian:
+            self.lam = np.zeros_like(self.lam)
         self.result_["x"] = np.array(np.broadcast_to(np.asarray(x, float).reshape(-1, self.result_["x"].shape[1]), self.result_["x"].shape))
         self.last_qp_info = None
 
@@ -138,7 +158,12 @@ class SQPOptimizationSolver:
         for i in range(self.stepNum_):
             t0 = time.perf_counter()
             localSystem = self.getLocalSystem(arg)
-            if self.convexify is not None:
+            if self.exact_hessian:
+                mode, eps = self.convexify if self.convexify is not None else (None, 1e-6)
+                localSystem.P, touched, _ = self.model.lagrangian_system(p, self.result_["x"], self.lam, localSystem.P, None, mode, eps)
+                if self.convexify is not None:
+                    self.convexified.append(touched)
+            elif self.convexify is not None:
                 localSystem.P, touched, _ = self.model.convexify_system(p, self.result_["x"], localSystem.P, *self.convexify)
                 self.convexified.append(touched)
             t1 = time.perf_counter()
@@ -188,6 +213,14 @@ class SQPOptimizationSolver:
                 self.result_["x"] = self.result_["x"] + step
                 self.result_["f"] = self.model.objective(p, self.result_["x"])
                 self.step_max = np.abs(step).max(axis=1)
+            if self.exact_hessian:
+                info = self.last_qp_info
+                if info is None or "y" not in info:
+                    raise ValueError("exact_hessian needs a QP backend that reports its multipliers (getInfo()['y'])")
+                got = np.isin(np.asarray(info["status"]), (1, 2, 7)) if "status" in info else np.ones(B, bool)
+                a = self.alpha_taken[:, None] if self.line_search is not None else self.alpha_
+                with np.errstate(invalid="ignore"):
+                    self.lam = np.where(got[:, None], self.lam + a * (np.asarray(info["y"], float) - self.lam), self.lam)
             self.iterations_done = i + 1
             if self.verbose_:
                 normDelta = np.linalg.norm(self.result_["x"] - oldRes, axis=1).max()
@@ -258,6 +291,14 @@ class DeviceSQPOptimizationSolver:
                 raise ValueError("convexify does not combine with constant_matrices: a touched frame changes P, which that option promises is constant")
         self.convexify = _convexify_options(options.get("convexify"), nlp)
         self.convexified = []
+        # extension (opt-in): one mpcqp_stage_lagrangian on P between the evaluation and the QP update, under the multiplier estimate
+        # `lam`; with convexify its mode and eps go into that call in place of the separate mpcqp_stage_convexify
+        if options.get("exact_hessian"):
+            if evaluator is not None:
+                raise ValueError("exact_hessian is limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has no constraint curvature kernel")
+            if self.constant_matrices:
+                raise ValueError("exact_hessian does not combine with constant_matrices: the curvature changes P, which that option promises is constant")
+        self.exact_hessian = _exact_hessian_option(options.get("exact_hessian"), nlp)
         self.alpha_taken = None; self.accepted = None
         self.iterations_done = 0
         self.step_max = None
@@ -279,6 +320,9 @@ class DeviceSQPOptimizationSolver:
         self.info = mk(4); self.rho = torch.zeros(self.batch, dtype=torch.float64, device=self.dev)
         self.admm_iterations = []
         self._touched = torch.zeros(self.batch, dtype=torch.int32, device=self.dev) if self.convexify is not None else None
+        self.lam = mk(self.ev.m) if self.exact_hessian else None      # the multiplier estimate, zero at the start: the first QP is the reference's
+        if self.exact_hessian and not self.ev.has_exact_hessian:
+            raise ValueError("exact_hessian: the evaluator's library does not carry the kernel (a generated model with lcost and exact_hessian = True does)")
         self.f = None; self.gmax = None
         self._have_start = False                         # like last_qp_info of the host loop: survives across calls
         self._start_clean = False                        # set by mpc.ClosedLoopMPC: mpcqp_stage_advance already zeroed the failed instances' start
@@ -303,6 +347,8 @@ class DeviceSQPOptimizationSolver:
         self._have_start = False
         if self.line_search is not None:
             self.mu.zero_()
+        if self.exact_hessian:
+            self.lam.zero_()
 
     def setInstanceParams(self, theta):
         """extension: one row of plant parameters per instance, [batch, param_count] (NumPy or CUDA tensor), for every evaluation of the loop
@@ -342,7 +388,12 @@ class DeviceSQPOptimizationSolver:
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         for i in range(self.stepNum_):
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
-            if self.convexify is not None:
+            if self.exact_hessian:
+                mode, eps = self.convexify if self.convexify is not None else (None, 1e-6)
+                ev.lagrangian(p, self.x, self.lam, self.ls["P"], mode=mode, eps=eps, touched=self._touched, stream=stream)
+                if self.convexify is not None:
+                    self.convexified.append(self._touched.clone())
+            elif self.convexify is not None:
                 ev.convexify(p, self.x, self.ls["P"], self.convexify[0], self.convexify[1], touched=self._touched, stream=stream)
                 self.convexified.append(self._touched.clone())
             if self.qp is None:                          # presolve_fixed_rows: the fixed rows are read off this first system's bounds
@@ -389,6 +440,11 @@ class DeviceSQPOptimizationSolver:
             else:
                 step = ev.step(self.alpha_, self.dw, self.x, stream=stream, status=self.status if self.skip_failed_steps else None)
                 self.f, self.gmax = ev.merit(p, self.x, stream=stream)
+            if self.exact_hessian:
+                # lam += alpha_b (y - lam) where the QP returned a point (its y is NaN elsewhere); elementwise torch, no kernel
+                got = ((self.status == 1) | (self.status == 2) | (self.status == 7)).unsqueeze(1)
+                a = self.alpha_taken.unsqueeze(1) if self.line_search is not None else self.alpha_
+                self.lam.copy_(torch.where(got, self.lam + a * (self.y - self.lam), self.lam))
             self.admm_iterations.append(self.iters.clone())
             self.iterations_done = i + 1
             self.step_max = step

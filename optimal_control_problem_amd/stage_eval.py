@@ -44,6 +44,12 @@ class ConvexifyArgs(C.Structure):
 CONVEXIFY_MODES = {"project": 1, "mirror": 2}      # MPCQP_CONVEXIFY_*
 
 
+class LagrangianArgs(C.Structure):
+    """mpcqp_stage_lagrangian_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("p", "x", "y", "status", "P")] + [("mode", C.c_int), ("eps", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("touched", "lam_min")]
+
+
 def _bind(L):
     if getattr(L, "_stage_bound", False):
         return L
@@ -72,6 +78,8 @@ def _bind(L):
     L.mpcqp_stage_linesearch.argtypes = [vp, C.c_int, C.POINTER(LineSearchArgs), vp]
     L.mpcqp_stage_has_convexify.argtypes = [vp]
     L.mpcqp_stage_convexify.argtypes = [vp, C.c_int, C.POINTER(ConvexifyArgs), vp]
+    L.mpcqp_stage_has_exact_hessian.argtypes = [vp]
+    L.mpcqp_stage_lagrangian.argtypes = [vp, C.c_int, C.POINTER(LagrangianArgs), vp]
     L._stage_bound = True
     return L
 
@@ -83,6 +91,32 @@ def model_params(model):
     if model.name == "cartpole":
         return [model.mc, model.mp, model.length, model.grav]
     return []
+
+
+def model_tape(model):
+    """the tape StageEvaluator generates a model's library from (codegen.trace with everything the model declares): codegen.build_device_library of it
+    is the library the evaluator loads, so a library can be cross-compiled ahead of the first run on a machine without a GPU"""
+    from . import codegen as cg
+    from . import models as _m
+    general = bool(getattr(model, "general_cost", False))
+    nk = int(getattr(model, "nk", 0))
+    link_cost = bool(getattr(model, "link_cost", False))
+    h_lo, h_hi = model.path_bounds()
+    # a model that declares parameters (ntheta, theta) keeps them as data of the generated functor.  The zoo classes, when they take this
+    # path (a path / link constraint, a general cost), keep their constants in the code as before: no parameters on that handle
+    nth = 0 if isinstance(model, (_m.Quadrotor, _m.CartPole)) else int(getattr(model, "ntheta", 0))
+    pkw = {"ntheta": nth, "theta0": model.theta, "model": model} if nth else {}
+    # a model that declares stage data (nsd, sdata) keeps them as data of the generated hfun / lcost / lterm
+    nsd = int(getattr(model, "nsd", 0))
+    if nsd:
+        pkw = dict(pkw, nsd=nsd, sdata0=model.sdata, model=model)
+    return cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
+                    lcost=model.lcost if general else None, lterm=model.lterm if general else None,
+                    kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
+                    **({"per_frame_reference": True} if getattr(model, "per_frame_reference", False) else {}), **pkw,
+                    **({"llink": model.llink} if link_cost else {}),
+                    **({"convexify": True} if general and getattr(model, "convexify", False) else {}),
+                    **({"exact_hessian": True} if general and getattr(model, "exact_hessian", False) else {}))
 
 
 def _check(t, shape, name):
@@ -136,21 +170,7 @@ class StageEvaluator:
             for i in range(8): d.par[i] = 0.0
             if use_codegen:
                 from . import codegen as cg
-                h_lo, h_hi = model.path_bounds()
-                # a model that declares parameters (ntheta, theta) keeps them as data of the generated functor.  The zoo classes, when they take this
-                # path (a path / link constraint, a general cost), keep their constants in the code as before: no parameters on that handle
-                nth = 0 if isinstance(model, (_m.Quadrotor, _m.CartPole)) else int(getattr(model, "ntheta", 0))
-                pkw = {"ntheta": nth, "theta0": model.theta, "model": model} if nth else {}
-                # a model that declares stage data (nsd, sdata) keeps them as data of the generated hfun / lcost / lterm
-                nsd = int(getattr(model, "nsd", 0))
-                if nsd:
-                    pkw = dict(pkw, nsd=nsd, sdata0=model.sdata, model=model)
-                self.tape = cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
-                                     lcost=model.lcost if general else None, lterm=model.lterm if general else None,
-                                     kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
-                                     **({"per_frame_reference": True} if self.per_frame_reference else {}), **pkw,
-                                     **({"llink": model.llink} if link_cost else {}),
-                                     **({"convexify": True} if general and getattr(model, "convexify", False) else {}))
+                self.tape = model_tape(model)
                 self.library = cg.build_device_library(self.tape)
             else:
                 for i, v in enumerate(model_params(model)): d.par[i] = float(v)
@@ -180,6 +200,7 @@ class StageEvaluator:
         self.param_count = int(L.mpcqp_stage_param_count(self._h))      # parameters per instance (mpcqp_stage_set_instance_params); 0: none
         self.nsd = int(L.mpcqp_stage_data_count(self._h))               # stage-data values per frame (mpcqp_stage_set_stage_data); 0: none
         self.has_convexify = bool(L.mpcqp_stage_has_convexify(self._h))  # the library carries the launcher of mpcqp_stage_convexify (model.convexify)
+        self.has_exact_hessian = bool(L.mpcqp_stage_has_exact_hessian(self._h))  # ... and the launchers of mpcqp_stage_lagrangian (model.exact_hessian)
         self.horizon = int(d.horizon)
         self._sd_batch = 0
         self.Pp = np.zeros(self.n + 1, np.int32); self.Pi = np.zeros(self.nnzP, np.int32)
@@ -366,4 +387,25 @@ class StageEvaluator:
         if lam_min is not None:
             a.lam_min = _check(lam_min, (B, self.horizon), "lam_min")
         _lib.check(_lib.lib().mpcqp_stage_convexify(self._h, B, C.byref(a), stream))
+        return P
+
+    def lagrangian(self, p, x, y, P, status=None, mode=None, eps=1e-6, touched=None, lam_min=None, stream=None):
+        """the curvature of the constraints under the multipliers y [B, m] added to P, in place: P becomes the Hessian of the Lagrangian
+        (mpcqp_stage_lagrangian; models.StageOCP.lagrangian_system is its host statement).  P [B, nnzP] is what eval just wrote at the same (p, x).
+        mode None adds only; "project" / "mirror" then convexify H_k + C_k with eps, touched (int32 [B]) and lam_min (float64 [B, horizon]) being the
+        optional outputs of convexify.  status (int32 [B], optional): an instance whose QP returned no point is neither read nor written.  A model
+        that sets exact_hessian = True (and has lcost) only; a mode needs convexify = True as well.  Returns P."""
+        if mode is not None and mode not in CONVEXIFY_MODES:
+            raise ValueError("mode must be None, 'project' or 'mirror'")
+        B = x.shape[0]
+        a = LagrangianArgs()
+        a.mode, a.eps = (0 if mode is None else CONVEXIFY_MODES[mode]), float(eps)
+        a.p, a.x, a.y, a.P = _check(p, (B, self.np), "p"), _check(x, (B, self.nvar), "x"), _check(y, (B, self.m), "y"), _check(P, (B, self.nnzP), "P")
+        if status is not None:
+            a.status = _check_int32(status, B, "status")
+        if touched is not None:
+            a.touched = _check_int32(touched, B, "touched")
+        if lam_min is not None:
+            a.lam_min = _check(lam_min, (B, self.horizon), "lam_min")
+        _lib.check(_lib.lib().mpcqp_stage_lagrangian(self._h, B, C.byref(a), stream))
         return P
