@@ -97,9 +97,13 @@ int mpcqp_create_tuned(int n, int m, int batch,
  * dimensions (the multiplier of an eliminated row from stationarity of its variable).  The handle is used like any other
  * (update / update_vectors / warm_start / set_rho / solve / get; mpcqp_solve_host and mpcqp_debug_scaling are not available).
  * It is a different, shorter ADMM run on an equivalent QP: x agrees with the full form within the termination tolerance, not
- * in the last digits, and status / iteration counts / info are the reduced run's (info[0] without the constant the eliminated
- * variables contribute).  An instance that breaks the promise (l != u on a named row) is refused like one with crossed
- * bounds (MPCQP_UNSOLVED, NaN).  mpcqp_update_vectors reads the P and A arrays of the last mpcqp_update again (the eliminated
+ * in the last digits, and status / iteration counts / info are the reduced run's, stated for the caller's QP: info[0] is the
+ * caller's objective at the returned x (the constant q_f'x_f + 1/2 x_f'P_ff x_f of the eliminated variables is added to the
+ * reduced run's objective; mpcqp_get_polish reports the candidate's objective the same way), info[1] and info[2] are the
+ * residuals of the caller's QP at the returned point (the eliminated rows and the stationarity of the eliminated variables hold
+ * to rounding).  An instance without a point -- a certificate of infeasibility, MPCQP_NON_CVX, crossed bounds -- is NaN in all
+ * of x, y, z, as from mpcqp_create.  An instance that breaks the promise (l != u on a named row) is refused like one with
+ * crossed bounds (MPCQP_UNSOLVED, x, y, z and info[0..2] NaN, 0 iterations).  mpcqp_update_vectors reads the P and A arrays of the last mpcqp_update again (the eliminated
  * columns enter q, l, u): device pointers borrowed there must still be valid.  The default stays the full form. */
 int mpcqp_create_reduced(int n, int m, int batch,
                          const int *P_colptr, const int *P_rowidx,
@@ -112,7 +116,8 @@ int mpcqp_create_reduced(int n, int m, int batch,
  * reference's formulation produces by itself: 0 <= dp <= 0 on the parameter block (SQPOptimizationSolver.cpp:117) and the first frame pinned
  * through lbx = ubx (src/OptimalControlProblem.cpp:93-96).  A caller that arrives through CuCaQP / OptimalControlProblem and cannot name rows
  * gets the reduced form this way (CuCaQP::setPresolveFixedRows(true) in cpp/CuCaQP.hpp).  Returns the handle of mpcqp_create_reduced on those rows
- * (an ordinary handle when there are none) and their number in *nfixed (may be NULL).  The promise "l = u on these rows in every later update" is
+ * (an ordinary handle when there are none) and the number of rows it eliminates in *nfixed (may be NULL; a QP whose every variable is pinned keeps
+ * one variable, so n - 1 at the most).  The promise "l = u on these rows in every later update" is
  * checked per instance as there (MPCQP_UNSOLVED, NaN for an instance that breaks it).  The default stays the full form. */
 int mpcqp_create_presolved(int n, int m, int batch, const int *Pp, const int *Pi, const int *Ap, const int *Ai,
                            const double *l, long sl, const double *u, long su, int mem,
@@ -219,7 +224,7 @@ int mpcqp_get(mpcqp_handle *h, double *x, double *y, double *z, int *status, int
 int mpcqp_set_polish(mpcqp_handle *h, int enable, double delta, int refine_iter);
 /* OSQP's info->status_polish per QP (polish_status [batch]) and polish_info[4*b ..] = {objective, primal residual, dual residual of the candidate --
  * accepted or not; NaN when none was built --, number of active rows}.  Either pointer may be NULL.  Of the last solve, ordered on its stream like
- * mpcqp_get; a reduced handle reports its inner handle's.  MPCQP_ERR_STATE when polishing is off. */
+ * mpcqp_get; a reduced handle reports its inner handle's, with the objective in the caller's terms.  MPCQP_ERR_STATE when polishing is off. */
 int mpcqp_get_polish(mpcqp_handle *h, int *polish_status, double *polish_info, int mem);
 /* Duration of the polish kernel of the last mpcqp_solve from HIP events around its launch (OSQP's info->polish_time); mpcqp_last_kernel_ms and
  * mpcqp_last_phase_ms keep their meaning -- the polish is timed apart.  MPCQP_ERR_STATE when none ran. */

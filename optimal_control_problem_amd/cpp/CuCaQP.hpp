@@ -12,6 +12,7 @@
 // One object may hold a batch of QPs of one sparsity (value arrays instance-major); batch = 1 is the drop-in case.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <iostream>
 #include <vector>
@@ -141,9 +142,13 @@ class CuCaQP {
     }
     if (!anyValid) { std::cerr << "Error: Failed to initialize solver. (lower bound greater than upper bound)" << std::endl; return false; }
     int rc = MPCQP_OK;
+    // a presolved handle eliminates the rows that were pinned when it was created: bounds that pin another set of rows (a row unpinned by a later
+    // setSystem would be refused per instance, MPCQP_UNSOLVED / NaN, where the reference solves the QP) get a handle of their own
+    if (presolve_ && handle_ && !patternChanged_ && pinnedRows() != fixedRows_) dirty_ = true;
     if (!handle_ || patternChanged_ || dirty_) {
       clearSolver();
       nfixed_ = 0;
+      fixedRows_ = presolve_ ? pinnedRows() : std::vector<int>();
       rc = presolve_ ? mpcqp_create_presolved(numOfVariables_, numOfConstraints_, batch_, Pp_.data(), Pi_.data(), Ap_.data(), Ai_.data(), l_.data(), numOfConstraints_,
                                               u_.data(), numOfConstraints_, MPCQP_MEM_HOST, &settings_, &handle_, &nfixed_)
                      : mpcqp_create(numOfVariables_, numOfConstraints_, batch_, Pp_.data(), Pi_.data(), Ap_.data(), Ai_.data(), &settings_, &handle_);
@@ -163,6 +168,8 @@ class CuCaQP {
 
   bool solve() {                                                 // reference CuCaQP.cpp:199-211
     if (!isInitialized_) { std::cerr << "Error: Solver not initialized. Call initSolver() first." << std::endl; return false; }
+    // (updateLowerBound / updateUpperBound on a presolved handle: bounds that pin another set of rows need a new handle, as in initSolver)
+    if (presolve_ && vectorsOnly_ && pinnedRows() != fixedRows_ && !initSolver()) return false;
     int rc = MPCQP_OK;
     if (vectorsOnly_ && kept_ && solvedOnce_ && !matricesDirty_)
       rc = mpcqp_update_vectors(handle_, q_.data(), numOfVariables_, l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
@@ -283,6 +290,26 @@ class CuCaQP {
 #endif
 
  private:
+  // the rows mpcqp_create_presolved eliminates for the stored bounds, by its own rule: a single entry in A, l = u (to 1e-9 max(1, |l|), |l| < 1e20) in every
+  // instance, the first such row of a variable, and never every variable
+  std::vector<int> pinnedRows() const {
+    const int n = numOfVariables_, m = numOfConstraints_;
+    std::vector<int> cnt(m, 0), col(m, -1), rows;
+    if (Ap_.size() != (size_t)n + 1 || l_.size() != (size_t)batch_ * m || u_.size() != (size_t)batch_ * m) return rows;
+    for (int j = 0; j < n; j++) for (int k = Ap_[j]; k < Ap_[j + 1]; k++) { cnt[Ai_[k]]++; col[Ai_[k]] = j; }
+    std::vector<char> taken(n, 0);
+    for (int i = 0; i < m; i++) {
+      if (cnt[i] != 1 || taken[col[i]]) continue;
+      bool eq = true;
+      for (int b = 0; b < batch_ && eq; b++) {
+        const double lo = l_[(size_t)b * m + i], up = u_[(size_t)b * m + i];
+        eq = std::fabs(up - lo) <= 1e-9 * std::max(1.0, std::fabs(lo)) && std::fabs(lo) < 1e20;
+      }
+      if (eq) { rows.push_back(i); taken[col[i]] = 1; }
+    }
+    if ((int)rows.size() >= n) rows.resize(n - 1);
+    return rows;
+  }
   bool assignPattern(const CscView &M, std::vector<int> &cp, std::vector<int> &ri) {
     std::vector<int> ncp(M.colptr, M.colptr + M.cols + 1), nri(M.rowidx, M.rowidx + M.colptr[M.cols]);
     bool changed = ncp != cp || nri != ri;
@@ -313,7 +340,7 @@ class CuCaQP {
   int nfixed_ = 0;
   mpcqp_settings settings_;
   mpcqp_handle *handle_ = nullptr;
-  std::vector<int> Pp_, Pi_, Ap_, Ai_, status_, iters_, polishStatus_;
+  std::vector<int> Pp_, Pi_, Ap_, Ai_, status_, iters_, polishStatus_, fixedRows_;
   std::vector<double> Pv_, Av_, q_, l_, u_, solution_;
 #ifdef MPCQP_HAVE_CASADI
   std::vector<int> pc_, pr_, ac_, ar_;

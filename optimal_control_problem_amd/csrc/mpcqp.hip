@@ -625,8 +625,8 @@ int mpcqp_create_presolved(int n, int m, int batch, const int *Pp, const int *Pi
     }
     if (eq) { rows.push_back(i); taken[col[i]] = 1; }
   }
-  if (nfixed_out) *nfixed_out = (int)rows.size();
   if ((int)rows.size() >= n) rows.resize(n - 1);       // (a QP with every variable fixed keeps one: the reduced pattern needs a variable)
+  if (nfixed_out) *nfixed_out = (int)rows.size();      // (what is eliminated: after the clip)
   if (rows.empty()) return mpcqp_create(n, m, batch, Pp, Pi, Ap, Ai, settings, out);      // nothing to eliminate: the ordinary handle
   return mpcqp_create_reduced(n, m, batch, Pp, Pi, Ap, Ai, (int)rows.size(), rows.data(), settings, out);
 }
@@ -651,8 +651,10 @@ static int solve_reduced(mpcqp_handle *h, hipStream_t s) {
     if ((rc = mpcqp_warm_start(in, h->rx0, h->ry0, MPCQP_MEM_DEVICE))) return rc;
   }
   if ((rc = mpcqp_solve(in, (void *)s))) return rc;
+  const bool pol = in->polish && h->opinfo;      // (the inner handle's polish outcome comes back with the objective's constant, like info[0])
   hipLaunchKernelGGL(mpcqp_postsolve_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io, in->ox, in->oy, in->oz, in->ostatus, in->oiters, in->oinfo,
-                     h->ox, h->oy, h->oz, h->ostatus, h->oiters, h->oinfo);
+                     pol ? in->opstatus : (const int *)nullptr, pol ? in->opinfo : (const double *)nullptr,
+                     h->ox, h->oy, h->oz, h->ostatus, h->oiters, h->oinfo, h->opstatus, h->opinfo);
   HIPCHK(hipGetLastError());
   h->last_stream = s; h->solved = true; h->have_factor = h->keep; h->reuse_next = false; h->rescale_next = false;
   return MPCQP_OK;
@@ -954,7 +956,14 @@ int mpcqp_last_phase_ms(mpcqp_handle *h, float *setup_ms, float *solve_ms) {
 int mpcqp_set_polish(mpcqp_handle *h, int enable, double delta, int refine_iter) {
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
   if (h->inner) {
-    const int rc = mpcqp_set_polish(h->inner, enable, delta, refine_iter);
+    int rc = mpcqp_set_polish(h->inner, enable, delta, refine_iter);
+    if (!rc && h->inner->polish && !h->opinfo) {      // the expansion's copy of the polish outcome (nothing is allocated inside a solve)
+      HIPCHK(hipSetDevice(h->device));
+      const size_t B = h->batch;
+      if ((rc = dalloc(h, &h->opstatus, B))) return rc;
+      if ((rc = dalloc(h, &h->opinfo, B * 4))) return rc;
+      HIPCHK(hipMemset(h->opstatus, 0, B * sizeof(int))); HIPCHK(hipMemset(h->opinfo, 0, B * 4 * sizeof(double)));
+    }
     if (!rc) h->polish = h->inner->polish;
     return rc;
   }
@@ -982,9 +991,7 @@ int mpcqp_get_polish(mpcqp_handle *h, int *polish_status, double *polish_info, i
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
   if (!h->polish) return fail(MPCQP_ERR_STATE, "polishing is off (mpcqp_set_polish)");
   if (!h->solved) return fail(MPCQP_ERR_STATE, "no solve has been issued");
-  if (h->inner) {      // (the inner handle ran on the same stream as the expansion behind it)
-    return mpcqp_get_polish(h->inner, polish_status, polish_info, mem);
-  }
+  // (a reduced handle: its own copy, which the expansion wrote -- the inner handle's outcome with the candidate's objective in the caller's terms)
   if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
   HIPCHK(hipSetDevice(h->device));
   const hipMemcpyKind k = mem == MPCQP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;

@@ -12,7 +12,9 @@
 // pattern, and x, y, z come back in the caller's dimensions: x_fixed as substituted, z_fixed = l, and the multiplier of an
 // eliminated row from stationarity of its variable,  y_i = -(q_j + (P x)_j + sum_kept a_kj y_k) / a_ij.
 // The result is a solution of the same QP to the same tolerances, from a different (shorter) ADMM run: iteration counts and the
-// last digits differ from the full form, which stays the default.
+// last digits differ from the full form, which stays the default.  info[0] is the caller's objective at the returned x (the constant
+// q_f'x_f + 1/2 x_f'P_ff x_f is added to the reduced run's); the residuals are the reduced run's, which are the caller's QP's at the expanded point
+// (the eliminated rows and the stationarity of the eliminated variables hold exactly).
 struct RedMaps {
   int n = 0, m = 0, nr = 0, mr = 0, nfix = 0, nnzP = 0, nnzA = 0;
   std::vector<int> Ppr, Pir, Apr, Air;              // reduced patterns (CSC)
@@ -115,42 +117,70 @@ __global__ void __launch_bounds__(256) mpcqp_presolve_kernel(const DevRed rd, co
     double s = 0.0;
     for (int e = rd.lc_ptr[ir]; e < rd.lc_ptr[ir + 1]; e++) s += A[rd.lc_src[e]] * xf[rd.lc_k[e]];
     const double lo = l[rd.kept_row[ir]], up = u[rd.kept_row[ir]];
+    if (lo > up) bad = 1;      // crossed bounds on a kept row: refused here, since the shifted pair can round to an equality
     rd.lr[(long)b * rd.mr + ir] = lo <= -Q_INFTY ? lo : lo - s;                 // an infinite bound stays infinite
     rd.ur[(long)b * rd.mr + ir] = up >= Q_INFTY ? up : up - s;
   }
+  __syncthreads();
   if (tid == 0) rd.bad[b] = bad;
 }
 
-// xr, yr, zr: the reduced handle's outputs; x, y, z, status...: the outer handle's
+// xr, yr, zr: the reduced handle's outputs; x, y, z, status...: the outer handle's.  pstr, pinr (null without polishing): the inner handle's polish
+// outcome, copied to pst, pin with the same constant on the candidate's objective.
+// An instance without a point -- refused, or ended by the inner handle on a certificate, as non-convex or on crossed bounds -- is NaN in all of x, y, z,
+// which is what a handle of the full form writes for it.
+// info[0] is the caller's objective at the returned x: the reduced run's  1/2 x_r'P_rr x_r + (q_r + P_rf x_f)'x_r  plus the constant the eliminated
+// variables contribute,  q_f'x_f + 1/2 x_f'P_ff x_f,  summed per thread over its eliminated variables and then over the threads in a fixed tree.
 __global__ void __launch_bounds__(256) mpcqp_postsolve_kernel(const DevRed rd, const DevIO io, const double *xr, const double *yr, const double *zr, const int *str,
-                                                              const int *itr, const double *infr, double *x, double *y, double *z, int *status, int *iters, double *info) {
+                                                              const int *itr, const double *infr, const int *pstr, const double *pinr, double *x, double *y,
+                                                              double *z, int *status, int *iters, double *info, int *pst, double *pin) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const double *P = io.P + (long)b * io.sP, *A = io.A + (long)b * io.sA, *q = io.q + (long)b * io.sq, *l = io.l + (long)b * io.sl;
   const double *xf = rd.xfix + (long)b * rd.nfix;
   const bool refused = rd.bad[b] != 0;
+  const int stb = str[b];
+  const bool point = !refused && (stb == MPCQP_SOLVED || stb == MPCQP_SOLVED_INACCURATE || stb == MPCQP_MAX_ITER_REACHED);
   double *xo = x + (long)b * rd.n, *yo = y + (long)b * rd.m, *zo = z + (long)b * rd.m;
-  for (int j = tid; j < rd.n; j += 256) { const int v = rd.var_of[j]; xo[j] = refused ? NAN : (v >= 0 ? xr[(long)b * rd.nr + v] : xf[-1 - v]); }
+  __shared__ double part[256];
+  for (int j = tid; j < rd.n; j += 256) { const int v = rd.var_of[j]; xo[j] = !point ? NAN : (v >= 0 ? xr[(long)b * rd.nr + v] : xf[-1 - v]); }
   for (int i = tid; i < rd.m; i += 256) {
     const int v = rd.row_of[i];
     if (v >= 0) {
       double sh = 0.0;                                         // z = A x in the caller's rows: the substituted part comes back
       for (int e = rd.lc_ptr[v]; e < rd.lc_ptr[v + 1]; e++) sh += A[rd.lc_src[e]] * xf[rd.lc_k[e]];
-      yo[i] = refused ? NAN : yr[(long)b * rd.mr + v]; zo[i] = refused ? NAN : zr[(long)b * rd.mr + v] + sh;
+      yo[i] = !point ? NAN : yr[(long)b * rd.mr + v]; zo[i] = !point ? NAN : zr[(long)b * rd.mr + v] + sh;
     }
-    else zo[i] = refused ? NAN : l[i];
+    else zo[i] = !point ? NAN : l[i];
   }
   __syncthreads();      // xo is complete (global memory written by this workgroup, read back below)
+  double c0 = 0.0;
   for (int k = tid; k < rd.nfix; k += 256) {
     const int j = rd.fix_row[k];      // the eliminated row
     // stationarity of the eliminated variable: q_j + (P x)_j + sum_kept a_kj y_k + a_ij y_i = 0
-    double s = q[rd.fix_var[k]];
-    for (int e = rd.yp_ptr[k]; e < rd.yp_ptr[k + 1]; e++) s += P[rd.yp_src[e]] * xo[rd.yp_var[e]];
+    const double qk = q[rd.fix_var[k]];
+    double s = qk, pff = 0.0;
+    for (int e = rd.yp_ptr[k]; e < rd.yp_ptr[k + 1]; e++) {
+      const int i = rd.yp_var[e]; const double p = P[rd.yp_src[e]];
+      s += p * xo[i];
+      if (rd.var_of[i] < 0) pff += p * xf[-1 - rd.var_of[i]];       // (P_ff x_f)_k
+    }
     for (int e = rd.ya_ptr[k]; e < rd.ya_ptr[k + 1]; e++) s += A[rd.ya_src[e]] * yr[(long)b * rd.mr + rd.ya_row[e]];
-    yo[j] = refused ? NAN : -s / A[rd.fix_src[k]];
+    yo[j] = !point ? NAN : -s / A[rd.fix_src[k]];
+    c0 += xf[k] * (qk + 0.5 * pff);
   }
+  part[tid] = c0;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) { if (tid < w) part[tid] += part[tid + w]; __syncthreads(); }
   if (tid == 0) {
-    status[b] = refused ? MPCQP_UNSOLVED : str[b]; iters[b] = refused ? 0 : itr[b];
-    for (int t = 0; t < 4; t++) info[4L * b + t] = infr[4L * b + t];
+    c0 = part[0];
+    status[b] = refused ? MPCQP_UNSOLVED : stb; iters[b] = refused ? 0 : itr[b];
+    for (int t = 0; t < 4; t++) info[4L * b + t] = refused && t < 3 ? NAN : infr[4L * b + t];      // (refused: what crossed bounds get from the full form)
+    if (point) info[4L * b] += c0;
+    if (pinr) {
+      pst[b] = refused ? MPCQP_POLISH_NOT_PERFORMED : pstr[b];
+      for (int t = 0; t < 4; t++) pin[4L * b + t] = refused ? (t < 3 ? NAN : 0.0) : pinr[4L * b + t];
+      if (!refused) pin[4L * b] += c0;      // (NaN where no candidate was built)
+    }
   }
 }
 

@@ -42,6 +42,8 @@ class CuCaQP:
         self._polish = self._polish_applied = False
         self._vectors_dirty = self._matrices_dirty = self._solved_once = False
         self._keep_scaling = self._no_matrix_updates = False
+        self._presolve = False
+        self._fixed_rows = None
 
     # -- dimensions (CuCaQP.cpp:23-41)
     def setDimension(self, numOfVariables, numOfConstraints):
@@ -98,6 +100,31 @@ class CuCaQP:
         osqp_update_data_mat, what OsqpEigen makes of the reference's CuCaQP.cpp:106-116,129-140) instead of running a full set-up.  A handle that
         does not take such updates runs the full set-up, silently."""
         self._keep_scaling = bool(keep)
+
+    def setPresolveFixedRows(self, on):
+        """extension (off by default; cpp/CuCaQP.hpp has the same switch): variables that a singleton row pins -- l = u in every instance, the reference's
+        0 <= dp <= 0 rows and the first frame -- are found from the bounds at initSolver() and substituted before the solve (mpcqp_create_presolved).
+        Bounds that pin another set of rows at a later initSolver() / update*Bound get a handle of their own."""
+        self._presolve = bool(on)
+
+    def presolvedRows(self):
+        return 0 if self._qp is None else self._qp.nfixed
+
+    def _pinned_rows(self):
+        """the rows mpcqp_create_presolved eliminates for the stored bounds, by its own rule: a single entry in A, l = u (to 1e-9 max(1, |l|), |l| < 1e20) in
+        every instance, the first such row of a variable, and never every variable"""
+        n, m = self.numOfVariables_, self.numOfConstraints_
+        Ap, Ai = self._A[0], self._A[1]
+        cnt = np.bincount(Ai, minlength=m)
+        col = np.zeros(m, dtype=np.int64); col[Ai] = np.repeat(np.arange(n), np.diff(Ap))
+        lo = np.asarray(self.lowerBound, float).reshape(-1, m); up = np.asarray(self.upperBound, float).reshape(-1, m)
+        with np.errstate(invalid="ignore"):
+            eq = ((np.abs(up - lo) <= 1e-9 * np.maximum(1.0, np.abs(lo))) & (np.abs(lo) < 1e20)).all(axis=0)
+        rows, taken = [], set()
+        for i in np.flatnonzero((cnt == 1) & eq):
+            if col[i] not in taken:
+                rows.append(int(i)); taken.add(col[i])
+        return tuple(rows[:n - 1] if len(rows) >= n else rows)
 
     def setSolverSetting(self, **kw):
         """extension: any field of mpcqp_settings (rho, sigma, alpha, scaling, adaptive_rho, ...)"""
@@ -235,12 +262,16 @@ class CuCaQP:
             # are refused one by one (status MPCQP_UNSOLVED) and only a batch without any valid instance fails here
             return _err("Failed to initialize solver. (lower bound greater than upper bound)")
         key = (self.numOfVariables_, self.numOfConstraints_, self.batch, self._P[0].tobytes(), self._P[1].tobytes(),
-               self._A[0].tobytes(), self._A[1].tobytes(), tuple(sorted((k, v) for k, v in self._kw.items())))
+               self._A[0].tobytes(), self._A[1].tobytes(), tuple(sorted((k, v) for k, v in self._kw.items())),
+               self._pinned_rows() if self._presolve else None)          # (a presolved handle eliminates the rows that were pinned when it was created)
         try:
             if self._qp is None or key != self._pattern_key:
                 if self._qp is not None:
                     self._qp.close()
                 kw = {k: v for k, v in self._kw.items() if k not in ("verbose", "warm_start_flag")}
+                if self._presolve:
+                    kw["presolve_bounds"] = (self.lowerBound, self.upperBound)
+                self._fixed_rows = key[-1]
                 self._qp = BatchQP(self.numOfVariables_, self.numOfConstraints_, self.batch, self._P[0], self._P[1],
                                    self._A[0], self._A[1], device=self._device, **kw)
                 self._pattern_key = key
@@ -266,6 +297,8 @@ class CuCaQP:
     def solve(self):
         if not self.isInitialized_:
             return _err("Solver not initialized. Call initSolver() first.")
+        if self._presolve and self._vectors_dirty and self._pinned_rows() != self._fixed_rows and not self.initSolver():
+            return False                    # (update*Bound on a presolved handle: bounds that pin another set of rows need a new handle, as in initSolver)
         try:
             data = (self._P[2], self.gradient, self._A[2], self.lowerBound, self.upperBound)
             if self._vectors_dirty and self._kept and self._solved_once and not self._matrices_dirty:
