@@ -572,6 +572,39 @@ int mpcqp_nlp_merit(mpcqp_nlp *s, int batch, const double *p, const double *x, c
                     double *f, double *gmax, void *stream);
 /* the damped update of SQPOptimizationSolver.cpp:171-177, with the semantics of mpcqp_stage_step (step_max and status optional) */
 int mpcqp_nlp_step(mpcqp_nlp *s, int batch, double alpha, const double *dw, double *x, double *step_max, const int *status, void *stream);
+/* Per-instance step length by an l1-merit backtracking search for a general NLP, one kernel for the batch (opt-in; replaces one mpcqp_nlp_step +
+ * mpcqp_nlp_merit pair).  The reference takes result.x += alpha * solution[pSize:] with one alpha for every iteration
+ * (SQPOptimizationSolver.cpp:171-177: no line search, no merit function); this entry departs from those lines.  The rule is the one of
+ * mpcqp_stage_linesearch above, word for word -- penalty, slope, search, update, outputs, the treatment of an instance that is not ok -- with
+ * these two measures:
+ *   violation  v(x) = sum over the ng general rows of max(lbg - g, 0) + max(g - ubg, 0) + sum over all nvar entries of max(lbx - x, 0) +
+ *              max(x - ubx, 0); an infinite bound contributes 0
+ *   objective  f(p, x) and gmax_out are what mpcqp_nlp_merit returns (gmax: general rows only, floor 0), bit for bit at the new x
+ *   update     x += alpha dx in place, by mpcqp_nlp_step's expression: candidates = 1 reproduces mpcqp_nlp_step(alpha0) bit for bit on finite data
+ * The result is bitwise repeatable and does not depend on the batch size or on the instance's position in the batch.  All pointers are device
+ * memory (p may be NULL when np = 0, lbg / ubg when ng = 0).  Asynchronous on `stream`; nothing is allocated, a captured graph replays it.
+ * MPCQP_ERR_ARG for a null handle, batch <= 0, a null argument block or required pointer, candidates outside 1..8, beta outside (0, 1),
+ * alpha0 <= 0, c1 outside [0, 1), mu_min or mu_factor negative or not finite; MPCQP_ERR_LIMIT for a generated library without the export
+ * mpcqp_general_linesearch -- one generated before this entry, or with line_search=False; regenerate it.  The handle stays usable after either.
+ * mpcqp_nlp_has_linesearch: 1 when the handle's library carries the kernel, 0 otherwise or for a null handle. */
+typedef struct mpcqp_nlp_linesearch_args {
+  const double *p;                     /* [batch * np]                                               */
+  double *x;                           /* [batch * nvar], in / out                                   */
+  const double *lbx, *ubx;             /* [batch * nvar]                                             */
+  const double *lbg, *ubg;             /* [batch * ng]                                               */
+  const double *q, *dw;                /* [batch * n]: gradient at x, QP solution                    */
+  const double *y;                     /* [batch * m]: QP multipliers                                */
+  const int *status;                   /* [batch], optional                                          */
+  double *mu;                          /* [batch], optional, in / out                                */
+  double *alpha_out;                   /* [batch], optional                                          */
+  int *accepted;                       /* [batch], optional                                          */
+  double *step_max, *f_out, *gmax_out; /* [batch], optional                                          */
+  double *phi;                         /* [batch * 2], optional                                      */
+  double alpha0, beta, c1, mu_min, mu_factor;
+  int candidates;                      /* 1 .. MPCQP_LINESEARCH_MAX_CANDIDATES                       */
+} mpcqp_nlp_linesearch_args;
+int mpcqp_nlp_has_linesearch(const mpcqp_nlp *s);
+int mpcqp_nlp_linesearch(mpcqp_nlp *s, int batch, const mpcqp_nlp_linesearch_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Structured stage form: the same QP, given by its stage blocks instead of CSC value arrays.

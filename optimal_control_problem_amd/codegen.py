@@ -1147,7 +1147,7 @@ def cache_dir():
 
 def _build(src_text, suffix, cmd_prefix):
     # the key covers everything the library is compiled from: the generated source, every header it includes and the command
-    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "stage_convexify.hpp", "general_kernels.hpp", "stage_models.hpp", "common.hpp"))
+    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "stage_convexify.hpp", "general_kernels.hpp", "general_linesearch.hpp", "stage_models.hpp", "common.hpp"))
     deps += open(os.path.join(_HERE, "..", "include", "mpcqp.h")).read()
     key = hashlib.sha256((src_text + deps + " ".join(cmd_prefix)).encode()).hexdigest()[:20]
     base = os.path.join(cache_dir(), "user_%s_%s" % (suffix, key))
@@ -1296,12 +1296,20 @@ int mpcqp_general_eval(const GnDev *gd, int batch, const double *p, const double
 int mpcqp_general_merit(int batch, const double *p, const double *x, const double *lbg, const double *ubg, double *f, double *gmax, void *stream) {
   return (int)general_launch_merit<GnUser>(batch, p, x, lbg, ubg, f, gmax, (hipStream_t)stream);
 }
+%(linesearch)s}
+'''
+
+# the optional export behind mpcqp_nlp_linesearch (found by dlsym: GnDev and GENERAL_ABI_VERSION are unchanged)
+_GENERAL_DEVICE_LINESEARCH = '''// the per-instance merit line search (mpcqp_nlp_linesearch)
+int mpcqp_general_linesearch(int batch, const mpcqp_nlp_linesearch_args *a, void *stream) {
+  return (int)general_launch_linesearch<GnUser>(batch, *a, (hipStream_t)stream);
 }
 '''
 
 _GENERAL_HOST_TMPL = '''// generated by optimal_control_problem_amd/codegen.py (emit_general) -- host build of the same functor, for checks without a GPU
 #include <cmath>
 #include "stage_models.hpp"
+#include "general_linesearch.hpp"
 #define GN_TABLE static constexpr
 
 namespace {      // (internal linkage: several generated libraries live in one process, each with its own GnUser)
@@ -1337,13 +1345,71 @@ void general_host_merit(const double *w, const double *lbg, const double *ubg, d
   if (GnUser::ng > 0) GnUser::C<double>(HValueIn{w}, HViolationOut{lbg, ubg, gmax});
 }
 }
+// the line search's accessor and sink (GnCandidateIn, GnMeritOut) on the host
+struct HCandidateIn { const double *p, *x, *d; double alpha; bool base;      // d: dx on a candidate, x on the base point, which never touches dx
+  double operator()(int k) const {
+    if (k < GnUser::np) return p[k];
+    const double xv = x[k - GnUser::np], c = gn_ls_point(xv, alpha, d[k - GnUser::np]);
+    return base ? xv : c;
+  } };
+struct HMeritOut { const double *lbg, *ubg; double *v, *gmax;
+  void operator()(int r, double g) const { *gmax = std::fmax(*gmax, std::fmax(lbg[r] - g, g - ubg[r])); *v += gn_ls_outside(lbg[r], g, ubg[r]); } };
+extern "C" {
+// mpcqp_nlp_linesearch for ONE instance on host arrays: the kernel's lanes become a loop over the candidates, the rule is the same text
+// (csrc/general_linesearch.hpp).  phis [candidates + 1] (optional): the merits, base point first, NaN where not evaluated; D_out (optional): the slope
+void general_host_linesearch(const mpcqp_nlp_linesearch_args *a, double *phis, double *D_out) {
+  constexpr int n = GnUser::n, np = GnUser::np, nvar = GnUser::nvar, ng = GnUser::ng, NC = MPCQP_LINESEARCH_MAX_CANDIDATES + 1;
+  bool ok = true;
+  if (a->status) ok = gn_ls_status_ok(a->status[0]);
+  const int K = ok ? a->candidates : 0;
+  const double *dx = a->dw + np;                      // (not read for an instance that is not ok)
+  double cost[NC], vio[NC], gmx[NC], phi[NC];
+  for (int j = 0; j <= K; j++) {
+    cost[j] = 0.0; vio[j] = 0.0; gmx[j] = 0.0;
+    const HCandidateIn in{a->p, a->x, j == 0 ? a->x : dx, j == 0 ? 0.0 : gn_ls_alpha(a->alpha0, a->beta, j - 1), j == 0};
+    GnUser::F<double>(in, HCostOut{&cost[j]});
+    if (ng > 0) GnUser::C<double>(in, HMeritOut{a->lbg, a->ubg, &vio[j], &gmx[j]});
+    for (int i = 0; i < nvar; i++) vio[j] += gn_ls_outside(a->lbx[i], in(np + i), a->ubx[i]);
+  }
+  double qd = 0.0, ymax = 0.0;
+  if (ok) {
+    for (int i = 0; i < nvar; i++) qd += a->q[np + i] * dx[i];
+    for (int i = np; i < n + ng; i++) ymax = std::fmax(ymax, std::fabs(a->y[i]));
+  }
+  const double mu = gn_ls_penalty(a->mu != nullptr, a->mu ? a->mu[0] : 0.0, a->mu_min, a->mu_factor, ok, ymax);
+  for (int j = 0; j <= K; j++) phi[j] = gn_ls_merit(cost[j], mu, vio[j]);
+  const double D = gn_ls_slope(qd, mu, vio[0]);
+  int acc;
+  const int sel = gn_ls_decide(K, a->candidates, a->alpha0, a->beta, a->c1, D, [&](int j) { return j <= K ? phi[j] : 0.0; }, &acc);
+  const double alpha_sel = sel > 0 ? gn_ls_alpha(a->alpha0, a->beta, sel - 1) : 0.0;
+  double mx = 0.0;
+  if (sel > 0)
+    for (int i = 0; i < nvar; i++) { a->x[i] = gn_ls_point(a->x[i], alpha_sel, dx[i]); mx = std::fmax(mx, std::fabs(alpha_sel * dx[i])); }
+  if (a->mu && ok) a->mu[0] = mu;
+  if (a->alpha_out) a->alpha_out[0] = alpha_sel;
+  if (a->accepted) a->accepted[0] = acc;
+  if (a->step_max) a->step_max[0] = mx;
+  if (a->f_out) a->f_out[0] = cost[sel];
+  if (a->gmax_out) a->gmax_out[0] = gmx[sel];
+  if (a->phi) { a->phi[0] = phi[0]; a->phi[1] = phi[sel]; }
+  if (phis) for (int j = 0; j <= a->candidates; j++) phis[j] = j <= K ? phi[j] : std::nan("");
+  if (D_out) *D_out = D;
+}
+}
 '''
 
 
-def build_general_device_library(model, cap=None):
-    """gfx950 shared library for mpcqp_nlp_create (hipcc cross-compiles without a GPU); cached by content.  TapeTooLarge beyond the cap."""
+def general_device_source(model, cap=None, line_search=True):
+    """the translation unit of a general library; line_search=False leaves the export mpcqp_general_linesearch (and its kernel) out: the text of a
+    library generated before mpcqp_nlp_linesearch"""
+    return _GENERAL_DEVICE_TMPL % {"functor": emit_general(model, cap=cap), "linesearch": _GENERAL_DEVICE_LINESEARCH if line_search else ""}
+
+
+def build_general_device_library(model, cap=None, line_search=True):
+    """gfx950 shared library for mpcqp_nlp_create (hipcc cross-compiles without a GPU); cached by content.  TapeTooLarge beyond the cap.
+    line_search=False: without the line-search kernel (mpcqp_nlp_linesearch then answers MPCQP_ERR_LIMIT)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    return _build(_GENERAL_DEVICE_TMPL % {"functor": emit_general(model, cap=cap)}, "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
+    return _build(general_device_source(model, cap=cap, line_search=line_search), "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
 
 
 def build_general_host_library(model, cap=None):

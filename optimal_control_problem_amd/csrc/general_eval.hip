@@ -3,9 +3,10 @@
 // Replaces the construction and the per-iteration call of localSystemFunction_ for problems the stage pattern does not cover
 // (reference src/sqp_solver/SQPOptimizationSolver.cpp:47-77,100-120) and the update / objective of :171-181.  The kernels live in
 // general_kernels.hpp and are instantiated by the generated unit; this file loads it, checks its ABI version, uploads its tables once
-// and forwards the calls.  Nothing is allocated inside eval / merit / step, so a captured graph replays them.
+// and forwards the calls.  Nothing is allocated inside eval / merit / step / linesearch, so a captured graph replays them.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -16,6 +17,7 @@
 typedef int (*gn_eval_fn)(const GnDev *, int, const double *, const double *, const double *, const double *, const double *, const double *,
                           double *, double *, double *, double *, double *, void *);
 typedef int (*gn_merit_fn)(int, const double *, const double *, const double *, const double *, double *, double *, void *);
+typedef int (*gn_linesearch_fn)(int, const mpcqp_nlp_linesearch_args *, void *);
 
 struct mpcqp_nlp {
   GnDev gd;
@@ -25,6 +27,7 @@ struct mpcqp_nlp {
   void *lib = nullptr;
   gn_eval_fn eval = nullptr;
   gn_merit_fn merit = nullptr;
+  gn_linesearch_fn linesearch = nullptr;   // optional: a library generated before mpcqp_nlp_linesearch (or without it) does not export it
 };
 
 extern "C" {
@@ -52,6 +55,7 @@ int mpcqp_nlp_create(const char *library_path, int device, mpcqp_nlp **out) {
   if (int rc = mpcqp_pick_device(device, &dev)) { dlclose(lib); return rc; }
   mpcqp_nlp *s = new mpcqp_nlp();
   s->lib = lib; s->eval = ev; s->merit = me; s->device = dev;
+  s->linesearch = (gn_linesearch_fn)dlsym(lib, "mpcqp_general_linesearch");
   const int jp = passes - hp;
   s->Pp.resize(n + 1); s->Pi.resize(nnzP); s->Ap.resize(n + 1); s->Ai.resize(nnzA);
   std::vector<int> tab((size_t)(n + 1) + (size_t)hp * n + (size_t)jp * ng);
@@ -125,6 +129,28 @@ int mpcqp_nlp_step(mpcqp_nlp *s, int batch, double alpha, const double *dw, doub
   if (batch <= 0 || !dw || !x) return mpcqp_set_error(MPCQP_ERR_ARG, "bad batch or null data pointer");
   MPCQP_HIPCHK(hipSetDevice(s->device));
   MPCQP_HIPCHK(mpcqp_launch_step(batch, s->gd.nvar, s->gd.n, s->gd.np, alpha, dw, x, step_max, status, (hipStream_t)stream));
+  return MPCQP_OK;
+}
+
+int mpcqp_nlp_has_linesearch(const mpcqp_nlp *s) { return s && s->linesearch ? 1 : 0; }
+
+int mpcqp_nlp_linesearch(mpcqp_nlp *s, int batch, const mpcqp_nlp_linesearch_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "nlp handle is null");
+  if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  const GnDev &d = s->gd;
+  if ((!a->p && d.np > 0) || !a->x || !a->lbx || !a->ubx || ((!a->lbg || !a->ubg) && d.ng > 0) || !a->q || !a->dw || !a->y)
+    return mpcqp_set_error(MPCQP_ERR_ARG, "p, x, lbx, ubx, lbg, ubg, q, dw and y are required (p with np > 0, lbg and ubg with ng > 0)");
+  if (a->candidates < 1 || a->candidates > MPCQP_LINESEARCH_MAX_CANDIDATES) return mpcqp_set_error(MPCQP_ERR_ARG, "candidates must be in 1..8");
+  if (!(a->beta > 0.0 && a->beta < 1.0)) return mpcqp_set_error(MPCQP_ERR_ARG, "beta must lie in (0, 1)");
+  if (!(a->alpha0 > 0.0) || !std::isfinite(a->alpha0)) return mpcqp_set_error(MPCQP_ERR_ARG, "alpha0 must be positive");
+  if (!(a->c1 >= 0.0 && a->c1 < 1.0)) return mpcqp_set_error(MPCQP_ERR_ARG, "c1 must lie in [0, 1)");
+  if (!(a->mu_min >= 0.0) || !(a->mu_factor >= 0.0) || !std::isfinite(a->mu_min) || !std::isfinite(a->mu_factor))
+    return mpcqp_set_error(MPCQP_ERR_ARG, "mu_min and mu_factor must be finite and not negative");
+  if (!s->linesearch)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_general_linesearch (generated before this entry, or without it); regenerate it");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  MPCQP_HIPCHK((hipError_t)s->linesearch(batch, a, stream));
   return MPCQP_OK;
 }
 

@@ -19,6 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "stage_models.hpp"
+#include "general_linesearch.hpp"
 
 #define GENERAL_ABI_VERSION 1
 
@@ -37,6 +38,18 @@ template <class M, const int *COLOUR> struct GnSeededIn {
 template <class M> struct GnValueIn {
   const double *p, *x;
   __device__ __forceinline__ double operator()(int k) const { return k < M::np ? p[k] : x[k - M::np]; }
+};
+
+// the point a lane of the line search evaluates: x itself on the base lane, else x + alpha dx.  The base lane must not touch dx at all (a failed
+// QP leaves NaN there, and x + 0 * NaN is NaN), and a load under a condition would turn every input into a branch: so `d` is dx on a candidate
+// lane and x on the base lane -- one unconditional load from memory the lane may read -- and the value is chosen after the arithmetic
+template <class M> struct GnCandidateIn {
+  const double *p, *x, *d; double alpha; bool base;
+  __device__ __forceinline__ double operator()(int k) const {
+    if (k < M::np) return p[k];
+    const double xv = x[k - M::np], c = gn_ls_point(xv, alpha, d[k - M::np]);
+    return base ? xv : c;
+  }
 };
 
 // ---- sinks: an output goes to its slot, or nowhere
@@ -63,6 +76,14 @@ struct GnCostOut {
 struct GnViolationOut {
   const double *lbg, *ubg; double *gmax;
   __device__ __forceinline__ void operator()(int r, double v) const { *gmax = fmax(*gmax, fmax(lbg[r] - v, v - ubg[r])); }
+};
+// the l1 violation of the line search next to the max-norm violation, the latter exactly as GnViolationOut keeps it
+struct GnMeritOut {
+  const double *lbg, *ubg; double *v, *gmax;
+  __device__ __forceinline__ void operator()(int r, double g) const {
+    *gmax = fmax(*gmax, fmax(lbg[r] - g, g - ubg[r]));
+    *v += gn_ls_outside(lbg[r], g, ubg[r]);
+  }
 };
 
 template <class M>
@@ -123,6 +144,72 @@ __global__ void __launch_bounds__(256) general_merit_kernel(int batch, const dou
   }
 }
 
+// Per-instance l1-merit backtracking line search (mpcqp_nlp_linesearch; general_nlp.GeneralNLP.line_search is its NumPy statement, the rule itself
+// is general_linesearch.hpp).  A group of W lanes serves one instance, W = gn_ls_group_width(candidates) handed in as a value: lane 0 evaluates the
+// base point x, lane j >= 1 the candidate x + alpha0 beta^(j-1) dx, lanes beyond the candidates idle; an instance whose QP returned no point runs
+// lane 0 only and never reads its dw or y.  A lane runs F and C once each at its own point (GnCandidateIn forms it where it is used) and sums the
+// box terms of that point; the lanes of a group read the same addresses, a broadcast load as in general_eval_kernel.  q' dx and max |y| stride over
+// the group and are reduced by one xor butterfly in fixed order; the merits travel by shuffles, every lane takes the same decision.  x is written
+// after that, strided over the group, by gn_ls_point: every read of x precedes the write in program order of the same wave, and the selected
+// lane's f and gmax ARE mpcqp_nlp_merit at the x written.  No LDS, no atomics, one writer per output, no array in a thread.
+template <class M>
+__global__ void __launch_bounds__(256) general_linesearch_kernel(int batch, int W, mpcqp_nlp_linesearch_args a) {
+  constexpr int n = M::n, np = M::np, nvar = M::nvar, ng = M::ng;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long b = gid / W;
+  const int lane = (int)(gid - b * W);
+  if (b >= batch) return;                       // (whole groups leave: the shuffles below stay inside a group)
+  bool ok = true;
+  if (a.status) ok = gn_ls_status_ok(a.status[b]);
+  const int K = ok ? a.candidates : 0;
+  double *xb = a.x + b * nvar;
+  const double *dxb = a.dw + b * n + np;
+  const bool base = lane == 0;
+  const double alpha = base ? 0.0 : gn_ls_alpha(a.alpha0, a.beta, lane - 1);
+  double cost = 0.0, vio = 0.0, gmx = 0.0;
+  if (lane <= K) {
+    const GnCandidateIn<M> in{a.p + b * np, xb, base ? xb : dxb, alpha, base};
+    M::template F<double>(in, GnCostOut{&cost});
+    if constexpr (ng > 0) M::template C<double>(in, GnMeritOut{a.lbg + b * ng, a.ubg + b * ng, &vio, &gmx});
+    const double *lb = a.lbx + b * nvar, *ub = a.ubx + b * nvar;
+    // (kept as a loop: unrolled over a constant nvar, its four loads per entry are all drawn to the top and the inputs of F and C stay alive for it)
+#pragma unroll 4
+    for (int i = 0; i < nvar; i++) vio += gn_ls_outside(lb[i], in(np + i), ub[i]);
+  }
+  double qd = 0.0, ymax = 0.0;
+  if (ok) {
+    const double *qb = a.q + b * n + np, *yb = a.y + b * (n + ng);
+    for (int i = lane; i < nvar; i += W) qd += qb[i] * dxb[i];
+    for (int i = np + lane; i < n + ng; i += W) ymax = fmax(ymax, fabs(yb[i]));
+  }
+  for (int o = W >> 1; o >= 1; o >>= 1) { qd += __shfl_xor(qd, o, W); ymax = fmax(ymax, __shfl_xor(ymax, o, W)); }
+  // the decision, the same on every lane of the group
+  const double mu = gn_ls_penalty(a.mu != nullptr, a.mu ? a.mu[b] : 0.0, a.mu_min, a.mu_factor, ok, ymax);
+  const double phi = gn_ls_merit(cost, mu, vio);
+  const double D = gn_ls_slope(qd, mu, __shfl(vio, 0, W));
+  int acc;
+  const int sel = gn_ls_decide(K, a.candidates, a.alpha0, a.beta, a.c1, D, [&](int j) { return __shfl(phi, j, W); }, &acc);
+  const double alpha_sel = sel > 0 ? gn_ls_alpha(a.alpha0, a.beta, sel - 1) : 0.0;
+  const double f_sel = __shfl(cost, sel, W), g_sel = __shfl(gmx, sel, W), phi_0 = __shfl(phi, 0, W), phi_sel = __shfl(phi, sel, W);
+  double mx = 0.0;
+  if (sel > 0) {
+    for (int i = lane; i < nvar; i += W) {
+      const double dv = dxb[i], d = alpha_sel * dv;
+      xb[i] = gn_ls_point(xb[i], alpha_sel, dv); mx = fmax(mx, fabs(d));
+    }
+  }
+  for (int o = W >> 1; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, W));
+  if (base) {
+    if (a.mu && ok) a.mu[b] = mu;
+    if (a.alpha_out) a.alpha_out[b] = alpha_sel;
+    if (a.accepted) a.accepted[b] = acc;
+    if (a.step_max) a.step_max[b] = mx;
+    if (a.f_out) a.f_out[b] = f_sel;
+    if (a.gmax_out) a.gmax_out[b] = g_sel;
+    if (a.phi) { a.phi[2 * b] = phi_0; a.phi[2 * b + 1] = phi_sel; }
+  }
+}
+
 template <class M>
 inline hipError_t general_launch_eval(const GnDev &gd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                                       const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st) {
@@ -135,5 +222,12 @@ template <class M>
 inline hipError_t general_launch_merit(int batch, const double *p, const double *x, const double *lbg, const double *ubg, double *f, double *gmax,
                                        hipStream_t st) {
   general_merit_kernel<M><<<(unsigned)((batch + 255) / 256), 256, 0, st>>>(batch, p, x, lbg, ubg, f, gmax);
+  return hipGetLastError();
+}
+// (no allocation, no synchronisation: a captured graph replays the launch)
+template <class M>
+inline hipError_t general_launch_linesearch(int batch, const mpcqp_nlp_linesearch_args &a, hipStream_t st) {
+  const int W = gn_ls_group_width(a.candidates);
+  general_linesearch_kernel<M><<<(unsigned)(((long)batch * W + 255) / 256), 256, 0, st>>>(batch, W, a);
   return hipGetLastError();
 }

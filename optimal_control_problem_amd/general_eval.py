@@ -68,6 +68,13 @@ def compress(model):
     return dict(hcol=hcol, jcol=jcol, hp=hp, jp=jp, hslot=hslot, jslot=jslot, hcolours=nh, jcolours=nj)
 
 
+class LineSearchArgs(C.Structure):
+    """mpcqp_nlp_linesearch_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("p", "x", "lbx", "ubx", "lbg", "ubg", "q", "dw", "y", "status", "mu", "alpha_out", "accepted", "step_max",
+                                          "f_out", "gmax_out", "phi")] + \
+               [(k, C.c_double) for k in ("alpha0", "beta", "c1", "mu_min", "mu_factor")] + [("candidates", C.c_int)]
+
+
 def _bind(L):
     if getattr(L, "_nlp_bound", False):
         return L
@@ -80,6 +87,8 @@ def _bind(L):
     L.mpcqp_nlp_eval.argtypes = [vp, C.c_int] + [vp] * 11 + [vp]
     L.mpcqp_nlp_merit.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.mpcqp_nlp_step.argtypes = [vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]
+    L.mpcqp_nlp_has_linesearch.argtypes = [vp]
+    L.mpcqp_nlp_linesearch.argtypes = [vp, C.c_int, C.POINTER(LineSearchArgs), vp]
     L._nlp_bound = True
     return L
 
@@ -93,14 +102,22 @@ def _check(t, shape, name):
     return t.data_ptr() or None                 # (an array without elements -- np = 0, ng = 0 -- has no address)
 
 
+def _check_int32(t, B, name):
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B,)):
+        raise ValueError("%s: expected a contiguous int32 CUDA tensor of shape (%d,)" % (name, B))
+    return t.data_ptr()
+
+
 class GeneralEvaluator:
     """the surface of stage_eval.StageEvaluator the device SQP loop uses, for a general_nlp.GeneralNLP.  library: the generated
-    gfx950 library (codegen.build_general_device_library; codegen.TapeTooLarge when the problem is refused)"""
+    gfx950 library (codegen.build_general_device_library; codegen.TapeTooLarge when the problem is refused).  line_search=False builds the
+    library without the line-search kernel (has_line_search is then False); ignored when `library` is given"""
 
-    def __init__(self, model, device=-1, cap=None, library=None):
+    def __init__(self, model, device=-1, cap=None, library=None, line_search=True):
         from . import codegen
         self.model = model
-        self.library = library if library is not None else codegen.build_general_device_library(model, cap=cap)
+        self.library = library if library is not None else codegen.build_general_device_library(model, cap=cap, line_search=line_search)
         L = _bind(_lib.lib())
         self._h = C.c_void_p()
         _lib.check(L.mpcqp_nlp_create(self.library.encode(), int(device), C.byref(self._h)))
@@ -111,6 +128,7 @@ class GeneralEvaluator:
         self.Ap = np.zeros(self.n + 1, np.int32); self.Ai = np.zeros(self.nnzA, np.int32)
         _lib.check(L.mpcqp_nlp_pattern(self._h, self.Pp.ctypes.data, self.Pi.ctypes.data, self.Ap.ctypes.data, self.Ai.ctypes.data))
         self._bounds = None
+        self.has_line_search = bool(L.mpcqp_nlp_has_linesearch(self._h))      # the library exports mpcqp_general_linesearch
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -163,3 +181,37 @@ class GeneralEvaluator:
         _lib.check(_lib.lib().mpcqp_nlp_step(self._h, B, float(alpha), _check(dw, (B, self.n), "dw"), _check(x, (B, self.nvar), "x"),
                                              sm.data_ptr(), None if status is None else status.data_ptr(), stream))
         return sm
+
+    def line_search(self, p, x, lbx, ubx, q, dw, y, status=None, mu=None, alpha0=1.0, candidates=4, beta=0.5, c1=1e-4, mu_min=1.0, mu_factor=1.1,
+                    out=None, phi=None, stream=None, lbg=None, ubg=None):
+        """a per-instance step length by an l1-merit backtracking search, then x += alpha_b dx in place, in one kernel (mpcqp_nlp_linesearch;
+        general_nlp.GeneralNLP.line_search is its host statement).  Replaces a step + merit pair: returns a dict of device tensors alpha, accepted
+        (int32), step_max, f, gmax [B] (`out`: such a dict to write into) and phi [B, 2] when a tensor is given for it.  mu [B], when given, is the
+        persistent penalty, updated in place.  The bounds of the general rows are those of the last eval unless given.  Arrays are contiguous
+        float64 CUDA tensors (status, accepted: int32)."""
+        import torch
+        B = x.shape[0]
+        if lbg is None or ubg is None:
+            if self._bounds is None:
+                raise ValueError("line_search needs the constraint bounds: give lbg and ubg, or call eval first")
+            lbg, ubg = self._bounds
+        a = LineSearchArgs()
+        for name, t, w_ in (("p", p, self.np), ("x", x, self.nvar), ("lbx", lbx, self.nvar), ("ubx", ubx, self.nvar), ("lbg", lbg, self.ng),
+                            ("ubg", ubg, self.ng), ("q", q, self.n), ("dw", dw, self.n), ("y", y, self.m)):
+            setattr(a, name, _check(t, (B, w_), name))
+        if out is None:
+            out = {k: torch.empty(B, dtype=torch.float64, device=x.device) for k in ("alpha", "step_max", "f", "gmax")}
+            out["accepted"] = torch.empty(B, dtype=torch.int32, device=x.device)
+        for name, key in (("alpha_out", "alpha"), ("step_max", "step_max"), ("f_out", "f"), ("gmax_out", "gmax")):
+            setattr(a, name, _check(out[key], (B,), key))
+        for name, t in (("status", status), ("accepted", out["accepted"])):
+            if t is not None:
+                setattr(a, name, _check_int32(t, B, name))
+        if mu is not None:
+            a.mu = _check(mu, (B,), "mu")
+        if phi is not None:
+            a.phi = _check(phi, (B, 2), "phi")
+            out["phi"] = phi
+        a.alpha0, a.beta, a.c1, a.mu_min, a.mu_factor, a.candidates = float(alpha0), float(beta), float(c1), float(mu_min), float(mu_factor), int(candidates)
+        _lib.check(_lib.lib().mpcqp_nlp_linesearch(self._h, B, C.byref(a), stream))
+        return out

@@ -125,6 +125,87 @@ class GeneralNLP:
         H = 0.5 * (H + H.transpose(0, 2, 1))
         return grad, H, gv, J
 
+    # -- the per-instance merit line search (include/mpcqp.h, mpcqp_nlp_linesearch; csrc/general_kernels.hpp general_linesearch_kernel) ------
+    STATUS_OK = (1, 2, 7)                  # MPCQP_SOLVED, _SOLVED_INACCURATE, _MAX_ITER_REACHED: the QP returned a point
+    line_search_takes_row_bounds = True    # the SQP loops hand lbg / ubg to line_search (a stage OCP carries its row bounds itself)
+
+    def violation(self, p, x, lbx, ubx, lbg, ubg):
+        """(v [B], gmax [B]): the l1 violation measure of the line search -- general rows outside lbg / ubg, entries of x outside lbx / ubx; an
+        infinite bound contributes 0 -- and the max-norm violation mpcqp_nlp_merit returns (general rows only, floor 0)"""
+        with np.errstate(all="ignore"):
+            x = np.asarray(x, float)
+            B = x.shape[0]
+            g = self.constraints(np.broadcast_to(np.asarray(p, float), (B, self.np)), x)
+            lbg = np.broadcast_to(np.asarray(lbg, float).reshape(-1, self.ng) if self.ng else np.zeros((1, 0)), (B, self.ng))
+            ubg = np.broadcast_to(np.asarray(ubg, float).reshape(-1, self.ng) if self.ng else np.zeros((1, 0)), (B, self.ng))
+            v = (np.fmax(lbg - g, 0.0) + np.fmax(g - ubg, 0.0)).sum(axis=1)
+            gmax = np.fmax.reduce(np.fmax(lbg - g, g - ubg), axis=1, initial=0.0)
+            v = v + (np.fmax(lbx - x, 0.0) + np.fmax(x - ubx, 0.0)).sum(axis=1)
+        return v, gmax
+
+    def line_search(self, p, x, lbx, ubx, q, dw, y, status=None, mu=None, alpha0=1.0, candidates=4, beta=0.5, c1=1e-4, mu_min=1.0, mu_factor=1.1,
+                    lbg=None, ubg=None):
+        """Host statement of mpcqp_nlp_linesearch: models.StageOCP.line_search word for word, with this class's violation(p, x, lbx, ubx, lbg, ubg)
+        and objective(p, x).  x [B, nvar] (float64 array) and, when given, mu [B] are updated in place.  phi(x) = f + mu_b v(x) with
+        mu_b = max(mu[b], mu_min, mu_factor max_{i >= np} |y_i|); D = min(0, q[np:]' dw[np:] - mu_b v(x)); the first alpha_j = alpha0 beta^j,
+        j < candidates, whose phi(x + alpha_j dx) is finite and <= phi(x) + c1 alpha_j D is taken (accepted = j).  None: alpha_{K-1} when its
+        merit is finite (accepted = -1), else alpha = 0 (accepted = -2).  An instance whose status is not in STATUS_OK keeps x, gets alpha = 0,
+        accepted = -2, and its mu stays.  lbg, ubg [B, ng]: required when the problem has general rows.  Returns the same dict."""
+        K = int(candidates)
+        if not 1 <= K <= 8:
+            raise ValueError("candidates must be in 1..8")
+        if not 0.0 < beta < 1.0:
+            raise ValueError("beta must lie in (0, 1)")
+        if not (alpha0 > 0.0 and np.isfinite(alpha0)):
+            raise ValueError("alpha0 must be positive")
+        if not 0.0 <= c1 < 1.0:
+            raise ValueError("c1 must lie in [0, 1)")
+        if not (0.0 <= mu_min < np.inf and 0.0 <= mu_factor < np.inf):
+            raise ValueError("mu_min and mu_factor must be finite and not negative")
+        if self.ng and (lbg is None or ubg is None):
+            raise ValueError("line_search needs the constraint bounds lbg and ubg of a problem with general rows")
+        B, npp = x.shape[0], self.np
+        p = np.broadcast_to(np.asarray(p, float).reshape(-1, npp) if npp else np.zeros((1, 0)), (B, npp))
+        lbx = np.asarray(lbx, float); ubx = np.asarray(ubx, float)
+        lbg = np.zeros((B, 0)) if not self.ng else np.asarray(lbg, float)
+        ubg = np.zeros((B, 0)) if not self.ng else np.asarray(ubg, float)
+        ok = np.ones(B, bool) if status is None else np.isin(np.asarray(status), self.STATUS_OK)
+        alphas = np.empty(K)
+        alphas[0] = alpha0
+        for j in range(1, K):
+            alphas[j] = alphas[j - 1] * beta
+        with np.errstate(all="ignore"):
+            dx = np.where(ok[:, None], np.asarray(dw, float)[:, npp:], 0.0)
+            mub = np.full(B, float(mu_min)) if mu is None else np.fmax(mu_min, np.asarray(mu, float))
+            ymax = np.fmax.reduce(np.abs(np.where(ok[:, None], np.asarray(y, float)[:, npp:], 0.0)), axis=1, initial=0.0)
+            mub = np.where(ok, np.fmax(mub, mu_factor * ymax), mub)
+            cost = np.full((B, K + 1), np.nan); vio = np.full((B, K + 1), np.nan); gmx = np.full((B, K + 1), np.nan)
+            for j in range(K + 1):
+                xc = x if j == 0 else x + alphas[j - 1] * dx
+                cost[:, j] = self.objective(p, xc)
+                vio[:, j], gmx[:, j] = self.violation(p, xc, lbx, ubx, lbg, ubg)
+            phis = cost + mub[:, None] * vio
+            D = (np.asarray(q, float)[:, npp:] * dx).sum(axis=1) - mub * vio[:, 0]
+            D = np.where(D < 0.0, D, 0.0)
+            sel = np.zeros(B, np.int64); acc = np.full(B, -2, np.int64)
+            found = ~ok
+            for j in range(1, K + 1):
+                take = ~found & np.isfinite(phis[:, j]) & (phis[:, j] <= phis[:, 0] + c1 * alphas[j - 1] * D)
+                sel[take] = j; acc[take] = j - 1
+                found = found | take
+            last = ~found & np.isfinite(phis[:, K])
+            sel[last] = K; acc[last] = -1
+            alpha = np.where(sel > 0, alphas[np.maximum(sel, 1) - 1], 0.0)
+            step = alpha[:, None] * dx
+            moved = sel > 0
+            x[moved] = x[moved] + step[moved]
+            phis[~ok, 1:] = np.nan
+        if mu is not None:
+            mu[ok] = mub[ok]
+        rows = np.arange(B)
+        return {"x": x, "alpha": alpha, "accepted": acc, "step_max": np.where(moved, np.abs(step).max(axis=1), 0.0), "f": cost[rows, sel],
+                "gmax": gmx[rows, sel], "phi": np.stack([phis[:, 0], phis[rows, sel]], axis=1), "mu": mub, "D": D, "alphas": alphas, "phis": phis}
+
     def local_system(self, p, x, lbx, ubx, lbg, ubg):
         """reference SQPOptimizationSolver.cpp:47-77,100-120: P = Hessian of f wrt w, q = gradient, A = [I; dg/dw], bounds shifted by the
         current [p; x; g]"""

@@ -296,6 +296,13 @@ class OptimalControlProblem:
         self.solverSettings = dict(maxIter=int(s["max_iter"]), warmStart=bool(s["warm_start"]),
                                    alpha=float(s["SQP_settings"]["alpha"]), stepNum=int(s["SQP_settings"]["step_num"]),
                                    verbose=bool(s["verbose"]), genCode=bool(s["gen_code"]), loadLib=bool(s["load_lib"]))
+        # extension (opt-in, no such key in the reference's YAML): SQP_settings.line_search -- absent or false = the reference's one alpha; true, or a
+        # map with any of candidates, beta, c1, mu_min, mu_factor = a step length per instance by the l1-merit search (sqp.py).  Checked here.
+        from .sqp import _line_search_options
+        ls = s["SQP_settings"].get("line_search")
+        if not (ls is None or isinstance(ls, (bool, dict))):
+            raise ValueError("SQP_settings.line_search: expected true, false or a map of candidates, beta, c1, mu_min, mu_factor")
+        self.lineSearch_ = None if _line_search_options(ls) is None else (True if ls is True else dict(ls))
         method = str(s["solve_method"])
         if method not in self.SOLVER_TYPES:
             raise ValueError("Unknown solver type: " + method)                       # :43-45
@@ -425,6 +432,8 @@ class OptimalControlProblem:
                 print("OptimalControlProblem: not a stage pattern (%s); general host evaluation, QPs on the GPU" % why)
         options = {"max_iter": self.solverSettings["stepNum"], "alpha": self.solverSettings["alpha"],
                    "verbose": self.solverSettings["verbose"]}
+        if self.lineSearch_ is not None:
+            options["line_search"] = self.lineSearch_        # to whichever of the three solvers below is built
         self.generalDeviceReason_ = None; self.generalLibrary_ = None
         if self.generalPath_ and self.generalDevice and self._qp_solver is None:
             from . import codegen

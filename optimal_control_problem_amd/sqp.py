@@ -14,7 +14,8 @@ Opt-in as well: options["line_search"] = True, or a dict with any of candidates,
 replaces the one alpha of :171-177 by a step length per instance, chosen by an l1-merit backtracking search that starts at options["alpha"]
 (models.StageOCP.line_search states the rule, mpcqp_stage_linesearch runs it on the device).  An instance whose QP returned no point keeps its
 iterate; the penalty persists across iterations and calls; `alpha_taken` and `accepted` hold the last iteration's step lengths and candidate
-indices; with warm_start_admm the remaining step is (1 - alpha_b) dx per instance.  Stage OCPs only.
+indices; with warm_start_admm the remaining step is (1 - alpha_b) dx per instance.  Stage OCPs, and general NLPs as well
+(general_nlp.GeneralNLP.line_search states the same rule with the general rows' violation, mpcqp_nlp_linesearch runs it on the device).
 Opt-in as well: options["convexify"] = "project", "mirror" or a dict {mode, eps} replaces, before every QP, each frame Hessian of a general stage cost that has
 an eigenvalue below eps by V f(Lambda) V' (models.StageOCP.convexify_system states the rule, mpcqp_stage_convexify runs it on the device); the gradient stays
 exact; `convexified` holds the touched-frame counts per iteration.  For models with lcost that set convexify = True.
@@ -116,7 +117,7 @@ class SQPOptimizationSolver:
         self.skip_failed_steps = bool(options.get("skip_failed_steps", False))
         self.line_search = _line_search_options(options.get("line_search"))
         if self.line_search is not None and not hasattr(nlp, "line_search"):
-            raise ValueError("line_search needs a stage OCP (models.StageOCP): the merit line search is not available for a general NLP")
+            raise ValueError("line_search needs a stage OCP (models.StageOCP) or a general NLP (general_nlp.GeneralNLP): this model states no merit line search")
         # opt-in: every frame Hessian of a general stage cost with an eigenvalue below eps is replaced by a positive definite one before the QP
         # (models.StageOCP.convexify_system); `convexified` holds the touched-frame counts per instance, one array per iteration
         self.convexify = _convexify_options(options.get("convexify"), nlp)
@@ -201,8 +202,12 @@ class SQPOptimizationSolver:
                     self._mu = np.zeros(B)
                 nvar = self.model.n - pSize
                 box = [np.broadcast_to(np.asarray(arg[k], float).reshape(-1, nvar), (B, nvar)) for k in ("lbx", "ubx")]
+                rows = {}
+                if getattr(self.model, "line_search_takes_row_bounds", False):       # a general NLP: the bounds of its rows come with the call
+                    ng = self.model.m - self.model.n
+                    rows = {k: np.broadcast_to(np.asarray(arg[k], float).reshape(-1, ng) if ng else np.zeros((1, 0)), (B, ng)) for k in ("lbg", "ubg")}
                 ls = self.model.line_search(p, self.result_["x"], box[0], box[1], localSystem.q, solution, info["y"], status=info.get("status"),
-                                            mu=self._mu, alpha0=self.alpha_, **self.line_search)
+                                            mu=self._mu, alpha0=self.alpha_, **self.line_search, **rows)
                 self.result_["f"] = ls["f"]; self.gmax = ls["gmax"]
                 self.alpha_taken = ls["alpha"]; self.accepted = ls["accepted"]; self.last_line_search = ls
                 self.step_max = ls["step_max"]
@@ -278,10 +283,12 @@ class DeviceSQPOptimizationSolver:
         # handle's forwarding.  Meant for per-frame references, whose N nx parameters push the full form off the on-chip kernels.
         self.presolve_fixed_rows = bool(options.get("presolve_fixed_rows", False))
         # extension (opt-in): a step length per instance by an l1-merit backtracking search starting at options["alpha"] -- one kernel
-        # (mpcqp_stage_linesearch) in place of the step + merit pair; see the module docstring.  It always honours the QP status.
+        # (mpcqp_stage_linesearch; mpcqp_nlp_linesearch with a general evaluator that has it) in place of the step + merit pair; see the module
+        # docstring.  It always honours the QP status.
         self.line_search = _line_search_options(options.get("line_search"))
-        if self.line_search is not None and evaluator is not None:
-            raise ValueError("line_search is limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has no merit line search")
+        if self.line_search is not None and evaluator is not None and not getattr(evaluator, "has_line_search", False):
+            raise ValueError("line_search: this general evaluator (evaluator=, mpcqp_nlp_*) has no merit line search -- its library was generated "
+                             "without mpcqp_general_linesearch, or the object is no general_eval.GeneralEvaluator")
         # extension (opt-in): one mpcqp_stage_convexify on P between the evaluation and the QP update; the touched-frame counts are
         # kept per iteration in `convexified`, a list of int tensors like admm_iterations
         if options.get("convexify") not in (None, False):
