@@ -605,6 +605,42 @@ typedef struct mpcqp_nlp_linesearch_args {
 } mpcqp_nlp_linesearch_args;
 int mpcqp_nlp_has_linesearch(const mpcqp_nlp *s);
 int mpcqp_nlp_linesearch(mpcqp_nlp *s, int batch, const mpcqp_nlp_linesearch_args *a, void *stream);
+/* The exact Hessian of the Lagrangian for a general NLP (opt-in).  The reference's QP takes hessian(f, w), the Hessian of the cost
+ * alone (src/sqp_solver/SQPOptimizationSolver.cpp:55-60), and so does mpcqp_nlp_eval; this entry departs from those lines, as mpcqp_stage_lagrangian
+ * does for the stage pattern.  With the rows c(w) = [p; x; g(w)], w = [p; x], and their multipliers y [m] -- what mpcqp_get returns and
+ * mpcqp_nlp_linesearch takes -- the Lagrangian is L = f + y'c, and since the rows p and x are linear its Hessian is that of f plus
+ *   C(w, y) = sum_i y[n + i] d2 g_i(w) / dw2     over the whole of w, parameter columns included, as P is.
+ * Called on the P mpcqp_nlp_eval just wrote at the same (p, x):
+ *   mode 0                   P <- P + C on the slots of C's structure.  With a workspace C [batch * nnzP] the curvature is written there first
+ *                            (its slots outside C's structure are not touched) and added by a second kernel; without one it is added to P
+ *                            directly.  Both give the same bits.
+ *   MPCQP_NLP_DOMINANT       the convexity safeguard: with R_c = sum_{r != c} |C_rc| and d_c = max(0, R_c - C_cc), P <- (P + C) + diag(d).
+ *                            C + diag(d) is diagonally dominant with a non-negative diagonal, hence positive semidefinite: P' is at least the
+ *                            Hessian of f whatever the multipliers are, d_c = 0 wherever C is already dominant, and y = 0 leaves P as it is.
+ *                            The rule is conservative -- it does not keep all of the curvature.  Needs the workspace.  shift [batch * n], when
+ *                            given, receives d_c for every column c with curvature of every instance that is read; nothing else is written to
+ *                            it, so zero it beforehand.
+ * A slot whose addend is zero keeps its bits.  status [batch], when given: an instance whose QP status is not MPCQP_SOLVED / _SOLVED_INACCURATE /
+ * _MAX_ITER_REACHED is neither read nor written (its y is NaN after an infeasible QP).  q, A, l, u are not arguments: the gradient, the merit and
+ * the fixed points stay exact.  Every entry has one writer and there are no atomics: the result is bitwise repeatable and does not depend on the
+ * batch size or the instance's position.  Asynchronous on `stream`; nothing is allocated, a captured graph replays it.  Needs a library generated
+ * from a model with exact_hessian=True (general_nlp.GeneralNLP): the structure of C is part of its pattern of P -- mpcqp_nlp_eval writes 0 to the
+ * added slots -- and it exports mpcqp_general_lagrangian.  A flagged model without curvature (linear constraints, ng = 0) makes the call a no-op.
+ * MPCQP_ERR_ARG for a null handle, a, x, y or P, a null p when np > 0, a null C with MPCQP_NLP_DOMINANT, any other mode, batch < 1;
+ * MPCQP_ERR_LIMIT (with the reason) for a library without the export.  The handle stays usable after either.
+ * mpcqp_nlp_has_exact_hessian: 1 when the handle's library carries the kernels, 0 otherwise or for a null handle. */
+#define MPCQP_NLP_DOMINANT 1
+typedef struct mpcqp_nlp_lagrangian_args {
+  const double *p, *x;                 /* [batch * np], [batch * nvar]: as mpcqp_nlp_eval             */
+  const double *y;                     /* [batch * m]: multiplier estimate, rows [p; x; g]           */
+  const int *status;                   /* [batch], optional                                          */
+  double *P;                           /* [batch * nnzP], in / out: as mpcqp_nlp_eval wrote it at the same (p, x) */
+  double *C;                           /* [batch * nnzP] workspace; optional with mode 0, required with MPCQP_NLP_DOMINANT */
+  int mode;                            /* 0 or MPCQP_NLP_DOMINANT                                    */
+  double *shift;                       /* [batch * n], optional out; written only with MPCQP_NLP_DOMINANT */
+} mpcqp_nlp_lagrangian_args;
+int mpcqp_nlp_has_exact_hessian(const mpcqp_nlp *s);
+int mpcqp_nlp_lagrangian(mpcqp_nlp *s, int batch, const mpcqp_nlp_lagrangian_args *a, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Structured stage form: the same QP, given by its stage blocks instead of CSC value arrays.

@@ -739,17 +739,24 @@ def _emit_body(tape, streaming=False):
 
 def _emit_streaming_body(tape):
     """the general evaluator's form of a body: an input is formed by the accessor `in(k)` where it is first used, an output goes to the
-    sink `out(r, value)` as soon as it is produced -- no array of the problem's length lives in the function"""
+    sink `out(r, value)` as soon as it is produced -- no array of the problem's length lives in the function.  A tape with plain_from (the
+    contracted gradient of general_nlp: inputs from there on are multipliers) takes those from a second accessor `mul(i)` as plain doubles, and
+    whatever depends on them and on constants alone stays a double next to T = Dual, as par and d do in the stage bodies"""
     outs_of = {}
     for r, o in enumerate(tape.outputs):
         outs_of.setdefault(o, []).append(r)
     ref = {}
     lines = []
+    plain_from = getattr(tape, "plain_from", tape.n_in)
+    plain = set()
 
     def use(i):
         if i not in ref:
             nd = tape.nodes[i]
-            if nd[0] == "in":
+            if nd[0] == "in" and nd[1] >= plain_from:
+                lines.append("    const double m%d = mul(%d);" % (nd[1] - plain_from, nd[1] - plain_from)); ref[i] = "m%d" % (nd[1] - plain_from)
+                plain.add(i)
+            elif nd[0] == "in":
                 lines.append("    const T x%d = in(%d);" % (nd[1], nd[1])); ref[i] = "x%d" % nd[1]
             else:
                 ref[i] = _lit(nd[1])
@@ -764,15 +771,17 @@ def _emit_streaming_body(tape):
             expr = "-%s" % args[0] if nd[0] == "neg" else "%s(%s)" % (_UNARY[nd[0]], args[0])
         else:
             expr = "%s %s %s" % (args[0], _BINARY[nd[0]], args[1])
-        lines.append("    const T w%d = %s;" % (i, expr)); ref[i] = "w%d" % i
+        if plain_from < tape.n_in and all(a in plain or tape.is_const(a) for a in nd[1:]):
+            plain.add(i)
+        lines.append("    const %s w%d = %s;" % ("double" if i in plain else "T", i, expr)); ref[i] = "w%d" % i
         for r in outs_of.get(i, ()):
-            lines.append("    out(%d, w%d);" % (r, i))
+            lines.append("    out(%d, %sw%d);" % (r, "T{} + " if i in plain else "", i))
     for r, o in enumerate(tape.outputs):
         nd = tape.nodes[o]
         if nd[0] == "const":
             lines.append("    out(%d, T{} + %s);" % (r, _lit(nd[1])))
         elif nd[0] == "in":
-            lines.append("    out(%d, %s);" % (r, use(o)))
+            lines.append("    out(%d, %s%s);" % (r, "T{} + " if nd[1] >= plain_from else "", use(o)))
     return "\n".join(lines)
 
 
@@ -1147,7 +1156,7 @@ def cache_dir():
 
 def _build(src_text, suffix, cmd_prefix):
     # the key covers everything the library is compiled from: the generated source, every header it includes and the command
-    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "stage_convexify.hpp", "general_kernels.hpp", "general_linesearch.hpp", "stage_models.hpp", "common.hpp"))
+    deps = "".join(open(os.path.join(CSRC, f)).read() for f in ("stage_kernels.hpp", "stage_convexify.hpp", "general_kernels.hpp", "general_linesearch.hpp", "general_lagrangian.hpp", "stage_models.hpp", "common.hpp"))
     deps += open(os.path.join(_HERE, "..", "include", "mpcqp.h")).read()
     key = hashlib.sha256((src_text + deps + " ".join(cmd_prefix)).encode()).hexdigest()[:20]
     base = os.path.join(cache_dir(), "user_%s_%s" % (suffix, key))
@@ -1227,9 +1236,10 @@ class TapeTooLarge(ValueError):
 
 
 def general_tape_size(model):
-    """operations (neither inputs nor constants) of the three bodies the general evaluator compiles"""
+    """operations (neither inputs nor constants) of the bodies the general evaluator compiles"""
     count = lambda t: sum(1 for i in t.live_nodes() if t.nodes[i][0] not in ("in", "const")) if t is not None else 0
-    return count(model._ftape) + count(model._gtape) + count(model._ctape)
+    # (a model built with exact_hessian=True also compiles the contracted gradient of its constraints, CG)
+    return count(model._ftape) + count(model._gtape) + count(model._ctape) + count(getattr(model, "_cgtape", None))
 
 
 def _ints(v, empty="-1"):
@@ -1254,6 +1264,14 @@ def emit_general(model, name="GnUser", cap=None):
     # colour of every input (-1: the variable carries no derivative): the seed of pass `pass` is colour == pass
     src += "  GN_TABLE int hcol[%d] = {%s};\n  GN_TABLE int jcol[%d] = {%s};\n" % (model.n, _ints(c["hcol"]), model.n, _ints(c["jcol"]))
     src += fn % ("F", body(model._ftape)) + fn % ("G", body(model._gtape)) + fn % ("C", body(model._ctape if model.ng else None))
+    if getattr(model, "exact_hessian", False):
+        # CG: out(r) = d(sum_i mul(i) g_i)/dw_r, the multipliers plain doubles (mpcqp_nlp_lagrangian); ccol, cslot: colours and slots of the
+        # curvature's structure in P's CSC; ccols, cptr, clist, cdiag: the walk of general_lagrangian.hpp over the columns with curvature
+        tab = lambda nm, v: "  GN_TABLE int %s[%d] = {%s};\n" % (nm, max(np.asarray(v).size, 1), _ints(v))
+        src += "  static constexpr int cp = %d, ncc = %d;\n" % (c["cp"], len(c["ccols"]))
+        src += "".join(tab(nm, c[nm]) for nm in ("ccol", "cslot", "ccols", "cptr", "clist", "cdiag"))
+        src += ("  template <class T, class In, class Mul, class Out> SM_HD static void CG(const In &in, const Mul &mul, const Out &out) {\n%s\n  }\n"
+                % body(model._cgtape if c["cp"] else None))
     src += "};\n"
     for nm, v in (("Pp", model.Pp), ("Pi", model.Pi), ("Ap", model.Ap), ("Ai", model.Ai), ("hslot", c["hslot"]), ("jslot", c["jslot"])):
         src += "static const int %s_%s[] = {%s};\n" % (name, nm, _ints(v))
@@ -1296,13 +1314,41 @@ int mpcqp_general_eval(const GnDev *gd, int batch, const double *p, const double
 int mpcqp_general_merit(int batch, const double *p, const double *x, const double *lbg, const double *ubg, double *f, double *gmax, void *stream) {
   return (int)general_launch_merit<GnUser>(batch, p, x, lbg, ubg, f, gmax, (hipStream_t)stream);
 }
-%(linesearch)s}
+%(linesearch)s%(lagrangian)s}
 '''
 
 # the optional export behind mpcqp_nlp_linesearch (found by dlsym: GnDev and GENERAL_ABI_VERSION are unchanged)
 _GENERAL_DEVICE_LINESEARCH = '''// the per-instance merit line search (mpcqp_nlp_linesearch)
 int mpcqp_general_linesearch(int batch, const mpcqp_nlp_linesearch_args *a, void *stream) {
   return (int)general_launch_linesearch<GnUser>(batch, *a, (hipStream_t)stream);
+}
+'''
+
+# the optional export behind mpcqp_nlp_lagrangian, only in the library of a model built with exact_hessian=True
+_GENERAL_DEVICE_LAGRANGIAN = '''// the exact Hessian of the Lagrangian (mpcqp_nlp_lagrangian)
+int mpcqp_general_lagrangian(int batch, const mpcqp_nlp_lagrangian_args *a, void *stream) {
+  return (int)general_launch_lagrangian<GnUser>(batch, *a, (hipStream_t)stream);
+}
+'''
+
+# the same on the host, appended to the host build of a model built with exact_hessian=True
+_GENERAL_HOST_LAGRANGIAN = '''
+#include "general_lagrangian.hpp"
+// GnSeededIn on the host, over p and x as the argument block carries them
+struct HSeededPX { const double *p, *x; const int *col; int pass;
+  Dual operator()(int k) const { return Dual{k < GnUser::np ? p[k] : x[k - GnUser::np], col[k] == pass ? 1.0 : 0.0}; } };
+extern "C" {
+// mpcqp_nlp_lagrangian for ONE instance on host arrays: the kernels' threads become a loop over the passes and one over the columns, with the same
+// functor text, the same tables and the walk of csrc/general_lagrangian.hpp
+void general_host_lagrangian(const mpcqp_nlp_lagrangian_args *a) {
+  if (a->status && !gn_ls_status_ok(a->status[0])) return;
+  if (GnUser::cp == 0) return;
+  for (int pass = 0; pass < GnUser::cp; pass++)
+    GnUser::CG<Dual>(HSeededPX{a->p, a->x, GnUser::ccol, pass}, GnMulIn{a->y + GnUser::n},
+                     GnCurvOut{a->C ? a->C : a->P, GnUser::cslot + pass * GnUser::n, a->C == nullptr});
+  if (a->C)
+    for (int ci = 0; ci < GnUser::ncc; ci++) gn_lag_apply_column<GnUser>(ci, a->C, a->P, a->mode == MPCQP_NLP_DOMINANT, a->shift);
+}
 }
 '''
 
@@ -1401,8 +1447,9 @@ void general_host_linesearch(const mpcqp_nlp_linesearch_args *a, double *phis, d
 
 def general_device_source(model, cap=None, line_search=True):
     """the translation unit of a general library; line_search=False leaves the export mpcqp_general_linesearch (and its kernel) out: the text of a
-    library generated before mpcqp_nlp_linesearch"""
-    return _GENERAL_DEVICE_TMPL % {"functor": emit_general(model, cap=cap), "linesearch": _GENERAL_DEVICE_LINESEARCH if line_search else ""}
+    library generated before mpcqp_nlp_linesearch.  A model built with exact_hessian=True adds the export mpcqp_general_lagrangian and its kernels"""
+    return _GENERAL_DEVICE_TMPL % {"functor": emit_general(model, cap=cap), "linesearch": _GENERAL_DEVICE_LINESEARCH if line_search else "",
+                                   "lagrangian": _GENERAL_DEVICE_LAGRANGIAN if getattr(model, "exact_hessian", False) else ""}
 
 
 def build_general_device_library(model, cap=None, line_search=True):
@@ -1412,5 +1459,9 @@ def build_general_device_library(model, cap=None, line_search=True):
     return _build(general_device_source(model, cap=cap, line_search=line_search), "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
 
 
+def general_host_source(model, cap=None):
+    return _GENERAL_HOST_TMPL % {"functor": emit_general(model, cap=cap)} + (_GENERAL_HOST_LAGRANGIAN if getattr(model, "exact_hessian", False) else "")
+
+
 def build_general_host_library(model, cap=None):
-    return _build(_GENERAL_HOST_TMPL % {"functor": emit_general(model, cap=cap)}, "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])
+    return _build(general_host_source(model, cap=cap), "host", ["g++", "-O2", "-std=c++17", "-ffp-contract=off"])

@@ -3,7 +3,7 @@
 // Replaces the construction and the per-iteration call of localSystemFunction_ for problems the stage pattern does not cover
 // (reference src/sqp_solver/SQPOptimizationSolver.cpp:47-77,100-120) and the update / objective of :171-181.  The kernels live in
 // general_kernels.hpp and are instantiated by the generated unit; this file loads it, checks its ABI version, uploads its tables once
-// and forwards the calls.  Nothing is allocated inside eval / merit / step / linesearch, so a captured graph replays them.
+// and forwards the calls.  Nothing is allocated inside eval / merit / step / linesearch / lagrangian, so a captured graph replays them.
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <cmath>
@@ -18,6 +18,7 @@ typedef int (*gn_eval_fn)(const GnDev *, int, const double *, const double *, co
                           double *, double *, double *, double *, double *, void *);
 typedef int (*gn_merit_fn)(int, const double *, const double *, const double *, const double *, double *, double *, void *);
 typedef int (*gn_linesearch_fn)(int, const mpcqp_nlp_linesearch_args *, void *);
+typedef int (*gn_lagrangian_fn)(int, const mpcqp_nlp_lagrangian_args *, void *);
 
 struct mpcqp_nlp {
   GnDev gd;
@@ -28,6 +29,7 @@ struct mpcqp_nlp {
   gn_eval_fn eval = nullptr;
   gn_merit_fn merit = nullptr;
   gn_linesearch_fn linesearch = nullptr;   // optional: a library generated before mpcqp_nlp_linesearch (or without it) does not export it
+  gn_lagrangian_fn lagrangian = nullptr;   // optional: only a library generated from a model with exact_hessian=True exports it
 };
 
 extern "C" {
@@ -56,6 +58,7 @@ int mpcqp_nlp_create(const char *library_path, int device, mpcqp_nlp **out) {
   mpcqp_nlp *s = new mpcqp_nlp();
   s->lib = lib; s->eval = ev; s->merit = me; s->device = dev;
   s->linesearch = (gn_linesearch_fn)dlsym(lib, "mpcqp_general_linesearch");
+  s->lagrangian = (gn_lagrangian_fn)dlsym(lib, "mpcqp_general_lagrangian");
   const int jp = passes - hp;
   s->Pp.resize(n + 1); s->Pi.resize(nnzP); s->Ap.resize(n + 1); s->Ai.resize(nnzA);
   std::vector<int> tab((size_t)(n + 1) + (size_t)hp * n + (size_t)jp * ng);
@@ -151,6 +154,22 @@ int mpcqp_nlp_linesearch(mpcqp_nlp *s, int batch, const mpcqp_nlp_linesearch_arg
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_general_linesearch (generated before this entry, or without it); regenerate it");
   MPCQP_HIPCHK(hipSetDevice(s->device));
   MPCQP_HIPCHK((hipError_t)s->linesearch(batch, a, stream));
+  return MPCQP_OK;
+}
+
+int mpcqp_nlp_has_exact_hessian(const mpcqp_nlp *s) { return s && s->lagrangian ? 1 : 0; }
+
+int mpcqp_nlp_lagrangian(mpcqp_nlp *s, int batch, const mpcqp_nlp_lagrangian_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "nlp handle is null");
+  if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if ((!a->p && s->gd.np > 0) || !a->x || !a->y || !a->P) return mpcqp_set_error(MPCQP_ERR_ARG, "p, x, y and P are required (p with np > 0)");
+  if (a->mode != 0 && a->mode != MPCQP_NLP_DOMINANT) return mpcqp_set_error(MPCQP_ERR_ARG, "mode must be 0 or MPCQP_NLP_DOMINANT");
+  if (a->mode == MPCQP_NLP_DOMINANT && !a->C) return mpcqp_set_error(MPCQP_ERR_ARG, "MPCQP_NLP_DOMINANT needs the workspace C");
+  if (!s->lagrangian)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_general_lagrangian: generate it from a model with exact_hessian=True");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  MPCQP_HIPCHK((hipError_t)s->lagrangian(batch, a, stream));
   return MPCQP_OK;
 }
 

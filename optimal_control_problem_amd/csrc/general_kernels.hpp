@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "stage_models.hpp"
 #include "general_linesearch.hpp"
+#include "general_lagrangian.hpp"
 
 #define GENERAL_ABI_VERSION 1
 
@@ -210,6 +211,39 @@ __global__ void __launch_bounds__(256) general_linesearch_kernel(int batch, int 
   }
 }
 
+// The exact Hessian of the Lagrangian (mpcqp_nlp_lagrangian; general_nlp.GeneralNLP.lagrangian_system is its NumPy statement, the shared parts are
+// general_lagrangian.hpp).  For a functor generated from a model with exact_hessian=True: CG is the reverse-derived gradient over w of the
+// contracted scalar sum_i mul(i) g_i(w), the multipliers plain values; ccol colours the columns of the curvature's structure and
+// cslot[pass * n + r] names the slot of entry (r, c) in P's CSC, as hcol / hslot do for the cost.  One thread per (instance, curvature pass), pass
+// fastest as in general_eval_kernel: the dual part of output r goes to its slot of the workspace C, or, without a workspace (mode 0 only), is
+// added to P there.  One writer per entry, no atomics, no LDS, no array in a thread.  An instance whose QP returned no point is neither read
+// nor written: its y is NaN.
+template <class M>
+__global__ void __launch_bounds__(256) general_curvature_kernel(int batch, mpcqp_nlp_lagrangian_args a) {
+  constexpr int n = M::n, np = M::np, nvar = M::nvar, ng = M::ng, cp = M::cp;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)batch * cp) return;
+  const int b = (int)(gid / cp), pass = (int)(gid - (long)b * cp);
+  if (a.status && !gn_ls_status_ok(a.status[b])) return;
+  const GnSeededIn<M, M::ccol> in{a.p + (long)b * np, a.x + (long)b * nvar, pass};
+  const GnMulIn mul{a.y + (long)b * (n + ng) + n};
+  const GnCurvOut out{(a.C ? a.C : a.P) + (long)b * M::nnzP, M::cslot + pass * n, a.C == nullptr};
+  M::template CG<Dual>(in, mul, out);
+}
+
+// P += C from the workspace, and the DOMINANT safeguard: one thread per (instance, column with curvature), the column walked by
+// gn_lag_apply_column in ascending slot order -- every slot of P has one reader and writer, the result does not depend on the batch
+template <class M>
+__global__ void __launch_bounds__(256) general_curvature_apply_kernel(int batch, mpcqp_nlp_lagrangian_args a) {
+  constexpr int ncc = M::ncc;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)batch * ncc) return;
+  const int b = (int)(gid / ncc), ci = (int)(gid - (long)b * ncc);
+  if (a.status && !gn_ls_status_ok(a.status[b])) return;
+  gn_lag_apply_column<M>(ci, a.C + (long)b * M::nnzP, a.P + (long)b * M::nnzP, a.mode == MPCQP_NLP_DOMINANT,
+                         a.shift ? a.shift + (long)b * M::n : nullptr);
+}
+
 template <class M>
 inline hipError_t general_launch_eval(const GnDev &gd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
                                       const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st) {
@@ -229,5 +263,14 @@ template <class M>
 inline hipError_t general_launch_linesearch(int batch, const mpcqp_nlp_linesearch_args &a, hipStream_t st) {
   const int W = gn_ls_group_width(a.candidates);
   general_linesearch_kernel<M><<<(unsigned)(((long)batch * W + 255) / 256), 256, 0, st>>>(batch, W, a);
+  return hipGetLastError();
+}
+// (cp = 0 -- linear constraints or none: nothing to add, nothing is launched)
+template <class M>
+inline hipError_t general_launch_lagrangian(int batch, const mpcqp_nlp_lagrangian_args &a, hipStream_t st) {
+  if constexpr (M::cp > 0) {
+    general_curvature_kernel<M><<<(unsigned)(((long)batch * M::cp + 255) / 256), 256, 0, st>>>(batch, a);
+    if (a.C) general_curvature_apply_kernel<M><<<(unsigned)(((long)batch * M::ncc + 255) / 256), 256, 0, st>>>(batch, a);
+  }
   return hipGetLastError();
 }

@@ -12,6 +12,7 @@ symmetric pattern for the Hessian; columns without an entry get no colour).  A p
 colour; the dual part of output row r is then exactly the entry (r, c) of the ONE column c of that colour that has row r: direct
 recovery.  slot[pass][r] names the CSC value slot of that entry (-1: none) in the order GeneralNLP.Pp / Pi / Ap / Ai define."""
 import ctypes as C
+from ctypes import byref as _byref      # (GeneralEvaluator.lagrangian has an argument named C, the workspace of the C entry)
 
 import numpy as np
 
@@ -65,7 +66,31 @@ def compress(model):
     jslot = np.full((jp, ng), -1, np.int32)
     if ng:
         jslot[:nj] = slot_table(jm, jcol, nj, model.Ap, first=1)
-    return dict(hcol=hcol, jcol=jcol, hp=hp, jp=jp, hslot=hslot, jslot=jslot, hcolours=nh, jcolours=nj)
+    c = dict(hcol=hcol, jcol=jcol, hp=hp, jp=jp, hslot=hslot, jslot=jslot, hcolours=nh, jcolours=nj)
+    if getattr(model, "exact_hessian", False):
+        c.update(compress_curvature(model))
+    return c
+
+
+def compress_curvature(model):
+    """the tables of mpcqp_nlp_lagrangian for a model built with exact_hessian=True: ccol / cp colour the columns of the curvature's structure cm
+    (cp = 0: no curvature, the call is a no-op); cslot[pass, r] is the slot of entry (r, c) in P's widened CSC, c the column of colour `pass`
+    with row r in cm, else -1.  For the apply kernel's walk over a column: ccols, the columns with curvature; cptr / clist, their curvature
+    slots in ascending order; cdiag, the slot of each one's diagonal entry"""
+    n = model.n
+    ccol, cp = colour_columns(model.cm)
+    rank = np.cumsum(model.hm, axis=0) - 1                 # position of row r among the entries of its column of P
+    cslot = np.full((cp, n), -1, np.int32)
+    ccols = np.nonzero(ccol >= 0)[0].astype(np.int32)
+    cptr = [0]; clist = []; cdiag = []
+    for j in ccols:
+        r = np.nonzero(model.cm[:, j])[0]
+        slots = int(model.Pp[j]) + rank[r, j]
+        cslot[ccol[j], r] = slots
+        clist += [int(v) for v in slots]; cptr.append(len(clist))
+        cdiag.append(int(model.Pp[j]) + int(rank[j, j]))
+    return dict(ccol=ccol, cp=cp, cslot=cslot, ccols=ccols, cptr=np.array(cptr, np.int32), clist=np.array(clist, np.int32),
+                cdiag=np.array(cdiag, np.int32))
 
 
 class LineSearchArgs(C.Structure):
@@ -73,6 +98,11 @@ class LineSearchArgs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("p", "x", "lbx", "ubx", "lbg", "ubg", "q", "dw", "y", "status", "mu", "alpha_out", "accepted", "step_max",
                                           "f_out", "gmax_out", "phi")] + \
                [(k, C.c_double) for k in ("alpha0", "beta", "c1", "mu_min", "mu_factor")] + [("candidates", C.c_int)]
+
+
+class LagrangianArgs(C.Structure):
+    """mpcqp_nlp_lagrangian_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("p", "x", "y", "status", "P", "C")] + [("mode", C.c_int), ("shift", C.c_void_p)]
 
 
 def _bind(L):
@@ -89,6 +119,8 @@ def _bind(L):
     L.mpcqp_nlp_step.argtypes = [vp, C.c_int, C.c_double, vp, vp, vp, vp, vp]
     L.mpcqp_nlp_has_linesearch.argtypes = [vp]
     L.mpcqp_nlp_linesearch.argtypes = [vp, C.c_int, C.POINTER(LineSearchArgs), vp]
+    L.mpcqp_nlp_has_exact_hessian.argtypes = [vp]
+    L.mpcqp_nlp_lagrangian.argtypes = [vp, C.c_int, C.POINTER(LagrangianArgs), vp]
     L._nlp_bound = True
     return L
 
@@ -112,7 +144,8 @@ def _check_int32(t, B, name):
 class GeneralEvaluator:
     """the surface of stage_eval.StageEvaluator the device SQP loop uses, for a general_nlp.GeneralNLP.  library: the generated
     gfx950 library (codegen.build_general_device_library; codegen.TapeTooLarge when the problem is refused).  line_search=False builds the
-    library without the line-search kernel (has_line_search is then False); ignored when `library` is given"""
+    library without the line-search kernel (has_line_search is then False); ignored when `library` is given.  A model built with
+    exact_hessian=True gives a library with the curvature kernels (has_exact_hessian, lagrangian)"""
 
     def __init__(self, model, device=-1, cap=None, library=None, line_search=True):
         from . import codegen
@@ -129,6 +162,7 @@ class GeneralEvaluator:
         _lib.check(L.mpcqp_nlp_pattern(self._h, self.Pp.ctypes.data, self.Pi.ctypes.data, self.Ap.ctypes.data, self.Ai.ctypes.data))
         self._bounds = None
         self.has_line_search = bool(L.mpcqp_nlp_has_linesearch(self._h))      # the library exports mpcqp_general_linesearch
+        self.has_exact_hessian = bool(L.mpcqp_nlp_has_exact_hessian(self._h))  # ... and mpcqp_general_lagrangian (a model with exact_hessian=True)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -215,3 +249,27 @@ class GeneralEvaluator:
         a.alpha0, a.beta, a.c1, a.mu_min, a.mu_factor, a.candidates = float(alpha0), float(beta), float(c1), float(mu_min), float(mu_factor), int(candidates)
         _lib.check(_lib.lib().mpcqp_nlp_linesearch(self._h, B, C.byref(a), stream))
         return out
+
+    MODES = {0: 0, 1: 1, "dominant": 1}    # mode 0; MPCQP_NLP_DOMINANT by its value or by the name the SQP option uses
+
+    def lagrangian(self, p, x, y, P, status=None, mode=0, C=None, shift=None, stream=None):
+        """P += C(w, y), the curvature of the constraints under the multipliers y [B, m], in place on the P of the last eval at the same (p, x)
+        (mpcqp_nlp_lagrangian; general_nlp.GeneralNLP.lagrangian_system is its host statement).  mode 0 adds C; "dominant" (MPCQP_NLP_DOMINANT)
+        adds the diagonal shift that keeps P at least the cost's Hessian, and needs the workspace C [B, nnzP].  shift [B, n], when given, receives
+        the shift of the columns with curvature of the instances that are read (zero it beforehand).  status (int32 [B]): instances whose QP
+        returned no point are neither read nor written.  Arrays are contiguous float64 CUDA tensors.  Returns P."""
+        B = x.shape[0]
+        if mode not in self.MODES:
+            raise ValueError("mode must be 0 or 'dominant' (MPCQP_NLP_DOMINANT)")
+        a = LagrangianArgs()
+        for name, t, w_ in (("p", p, self.np), ("x", x, self.nvar), ("y", y, self.m), ("P", P, self.nnzP)):
+            setattr(a, name, _check(t, (B, w_), name))
+        if C is not None:
+            a.C = _check(C, (B, self.nnzP), "C")
+        if shift is not None:
+            a.shift = _check(shift, (B, self.n), "shift")
+        if status is not None:
+            a.status = _check_int32(status, B, "status")
+        a.mode = self.MODES[mode]
+        _lib.check(_lib.lib().mpcqp_nlp_lagrangian(self._h, B, _byref(a), stream))
+        return P

@@ -44,6 +44,24 @@ def _trace(fn, n_in, what):
     return tape
 
 
+def _contracted_gradient(constraints, n, ng):
+    """gradient over w of the scalar lam' g(w): a tape with inputs [w (n); lam (ng)] and n outputs.  The multipliers carry no derivative
+    (plain_from = n): the generated body takes them as plain values"""
+    tape = codegen.Tape(n + ng)
+    w = codegen.TV(tape, [codegen.TS(tape, k) for k in range(n)])
+    out = [v.idx if isinstance(v, codegen.TS) else tape.const(v) for v in _flat(constraints(w))]
+    if len(out) != ng:
+        raise ValueError("the constraints returned %d values, then %d" % (ng, len(out)))
+    acc = tape.const(0.0)
+    for i, o in enumerate(out):
+        acc = tape.s_add(acc, tape.s_mul(n + i, o))
+    tape.outputs = [acc]
+    g = codegen.gradient_tape(tape)
+    g.outputs = g.outputs[:n]
+    g.plain_from = n
+    return g
+
+
 def _depends(tape):
     """[n_out, n_in] structural dependency of every output on every input (reachability on the tape)"""
     n = tape.n_in
@@ -67,7 +85,9 @@ class GeneralNLP:
 
     name = "general_nlp"
 
-    def __init__(self, nvar, npar, cost, constraints=None):
+    def __init__(self, nvar, npar, cost, constraints=None, exact_hessian=False):
+        """exact_hessian (opt-in): the structure of the constraints' curvature joins the pattern of P, so that lagrangian_system /
+        mpcqp_nlp_lagrangian can add it; without the flag the pattern, the generated text and every attribute are what they were"""
         self.nvar, self.np = int(nvar), int(npar)
         self.n = self.np + self.nvar
         self._ftape = _trace(lambda w: cost(w), self.n, "cost")
@@ -80,6 +100,18 @@ class GeneralNLP:
         self.m = self.n + self.ng
         jm = _depends(self._ctape) if self.ng else np.zeros((0, self.n), bool)
         self.am = np.vstack([np.eye(self.n, dtype=bool), jm])
+        if exact_hessian:
+            # the gradient over w of the contracted scalar sum_i lam_i g_i(w), the ng multipliers being extra tape inputs without a derivative
+            # (codegen._contracted_gradient does this per frame on the stage path); cm: the structure of its Hessian, valid for any multipliers,
+            # plus the diagonal entry of every column that has curvature -- the slot the DOMINANT safeguard writes its shift to
+            self.exact_hessian = True
+            self._cgtape = _contracted_gradient(constraints, self.n, self.ng) if self.ng else None
+            cm = codegen.hessian_mask(self._cgtape) if self.ng else np.zeros((self.n, self.n), bool)
+            cols = cm.any(axis=0)
+            cm[cols, cols] = True
+            self.cm = cm
+            self._ccols = np.nonzero(cols)[0]
+            self.hm = self.hm | cm
         self.Pp, self.Pi = _csc_from_dense_mask(self.hm)
         self.Ap, self.Ai = _csc_from_dense_mask(self.am)
         # columns that carry any derivative at all: the others are never perturbed
@@ -124,6 +156,62 @@ class GeneralNLP:
                 wc[:, k] = w[:, k]
         H = 0.5 * (H + H.transpose(0, 2, 1))
         return grad, H, gv, J
+
+    # -- the exact Hessian of the Lagrangian (include/mpcqp.h, mpcqp_nlp_lagrangian; csrc/general_kernels.hpp general_curvature_kernel) -------------
+    DOMINANT = 1                           # MPCQP_NLP_DOMINANT
+
+    def _need_exact(self):
+        if not getattr(self, "exact_hessian", False):
+            raise ValueError("this GeneralNLP was built without exact_hessian=True: the curvature's structure is not part of its pattern")
+
+    def constraint_curvature(self, p, x, y):
+        """C [B, n, n] = sum_i y[:, n + i] d2 g_i / dw2 at w = [p; x] (complex-step columns of the contracted gradient, symmetrised as
+        `derivatives` does); y [B, m] are multipliers of the rows [p; x; g]"""
+        self._need_exact()
+        x = np.asarray(x, float)
+        B = x.shape[0]
+        C = np.zeros((B, self.n, self.n))
+        if not len(self._ccols):
+            return C
+        h = 1e-30
+        w = np.concatenate([np.broadcast_to(np.asarray(p, float).reshape(-1, self.np) if self.np else np.zeros((1, 0)), (B, self.np)), x], axis=1)
+        wl = np.concatenate([w, np.asarray(y, float)[:, self.n:]], axis=1).astype(complex)
+        for k in self._ccols:
+            wl[:, k] += 1j * h
+            C[:, :, k] = self._eval_vec(self._cgtape, wl).imag / h
+            wl[:, k] = w[:, k]
+        return 0.5 * (C + C.transpose(0, 2, 1))
+
+    def lagrangian_system(self, p, x, y, P, status=None, mode=0):
+        """NumPy statement of mpcqp_nlp_lagrangian: (P', shift [B, n]) from P [B, nnzP] as local_system returned it at the same (p, x).
+        mode 0: P' = P + C on the curvature's slots.  mode DOMINANT: with R_c = sum_{r != c} |C_rc| and d_c = max(0, R_c - C_cc), the diagonal
+        slot of column c takes (P + C) + d_c -- C + diag(d) is diagonally dominant with a non-negative diagonal, hence positive semidefinite, so
+        P' is at least the cost's Hessian whatever the multipliers are.  A slot whose addend is zero keeps its bits.  An instance whose status
+        is not in STATUS_OK keeps every bit of P and gets shift = 0 (its y may be NaN)."""
+        self._need_exact()
+        if mode not in (0, self.DOMINANT):
+            raise ValueError("mode must be 0 or GeneralNLP.DOMINANT")
+        P = np.array(P, float)
+        B = P.shape[0]
+        ok = np.ones(B, bool) if status is None else np.isin(np.asarray(status), self.STATUS_OK)
+        shift = np.zeros((B, self.n))
+        if not len(self._ccols):
+            return P, shift
+        with np.errstate(all="ignore"):
+            C = self.constraint_curvature(p, x, np.where(ok[:, None], np.asarray(y, float), 0.0))
+            Cv = C.transpose(0, 2, 1)[:, self.hm.T]
+            new = np.where(Cv != 0.0, P + Cv, P)
+            if mode == self.DOMINANT:
+                dg = np.arange(self.n)
+                R = np.abs(C).sum(axis=1) - np.abs(C[:, dg, dg])
+                d = np.fmax(0.0, R - C[:, dg, dg])
+                d[:, ~self.cm.any(axis=0)] = 0.0
+                cols = np.repeat(np.arange(self.n), np.diff(self.Pp))
+                isdiag = np.asarray(self.Pi) == cols
+                dv = np.zeros_like(new); dv[:, isdiag] = d[:, cols[isdiag]]
+                new = np.where(dv > 0.0, new + dv, new)
+                shift = np.where(ok[:, None], d, 0.0)
+        return np.where(ok[:, None], new, P), shift
 
     # -- the per-instance merit line search (include/mpcqp.h, mpcqp_nlp_linesearch; csrc/general_kernels.hpp general_linesearch_kernel) ------
     STATUS_OK = (1, 2, 7)                  # MPCQP_SOLVED, _SOLVED_INACCURATE, _MAX_ITER_REACHED: the QP returned a point

@@ -303,6 +303,12 @@ class OptimalControlProblem:
         if not (ls is None or isinstance(ls, (bool, dict))):
             raise ValueError("SQP_settings.line_search: expected true, false or a map of candidates, beta, c1, mu_min, mu_factor")
         self.lineSearch_ = None if _line_search_options(ls) is None else (True if ls is True else dict(ls))
+        # extension (opt-in, no such key in the reference's YAML): SQP_settings.exact_hessian -- absent or false = the reference's hessian(f, w);
+        # true = the Hessian of the Lagrangian, "dominant" = the same with the diagonal-dominance safeguard (sqp.py).  General path only.
+        eh = s["SQP_settings"].get("exact_hessian")
+        if not (eh is None or isinstance(eh, bool) or eh == "dominant"):
+            raise ValueError("SQP_settings.exact_hessian: expected true, false or dominant")
+        self.exactHessian_ = eh if eh else None
         method = str(s["solve_method"])
         if method not in self.SOLVER_TYPES:
             raise ValueError("Unknown solver type: " + method)                       # :43-45
@@ -434,6 +440,12 @@ class OptimalControlProblem:
                    "verbose": self.solverSettings["verbose"]}
         if self.lineSearch_ is not None:
             options["line_search"] = self.lineSearch_        # to whichever of the three solvers below is built
+        if self.exactHessian_ is not None:
+            if not self.generalPath_:
+                raise ValueError("SQP_settings.exact_hessian: this problem is a stage pattern, and the facade does not build stage models with the "
+                                 "exact Hessian -- DESIGN 6.18 covers models.StageOCP with lcost and exact_hessian = True, not the stage facade; "
+                                 "the key serves problems on the general path")
+            options["exact_hessian"] = self.exactHessian_   # to whichever general solver is built below, host or device
         self.generalDeviceReason_ = None; self.generalLibrary_ = None
         if self.generalPath_ and self.generalDevice and self._qp_solver is None:
             from . import codegen
@@ -466,7 +478,7 @@ class OptimalControlProblem:
             raise RuntimeError("Cost function is empty")
         cost = lambda w: sum(_as_scalar(evaluate_expression(c, w[npar:], w[:npar])) for c in self.costs_)
         cons = lambda w: [evaluate_expression(c, w[npar:], w[:npar]) for c in self.constraints_]
-        model = GeneralNLP(nvar, npar, cost, cons)
+        model = GeneralNLP(nvar, npar, cost, cons, **({"exact_hessian": True} if self.exactHessian_ is not None else {}))
         if model.ng != sum(len(b) for b in self.constraintLowerBounds_):
             raise ValueError("SX used for constraints has different dimension!")
         self._row_order = list(range(len(self.constraints_)))

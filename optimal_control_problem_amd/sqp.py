@@ -23,7 +23,10 @@ Opt-in as well: options["exact_hessian"] = True adds the curvature of the constr
 Lagrangian instead of the reference's hessian(f, w) (:55-60; models.StageOCP.lagrangian_system states the rule, mpcqp_stage_lagrangian runs it on the
 device).  The loops keep a multiplier estimate lam [batch, m], zero at the start -- the first QP is the reference's -- and after each QP the instances
 whose QP returned a point take lam += alpha_b (y - lam), alpha_b the step length actually taken; setInitialGuess resets it.  With options["convexify"]
-the same call convexifies H_k + C_k.  For models with lcost that set exact_hessian = True.
+the same call convexifies H_k + C_k.  For models with lcost that set exact_hessian = True, and for a general NLP built with
+GeneralNLP(..., exact_hessian=True): there True adds the curvature of g over the whole of w and "dominant" adds it with the
+diagonal-dominance safeguard (general_nlp.GeneralNLP.lagrangian_system states the rule, mpcqp_nlp_lagrangian runs it on the device); `shift`
+holds the last iteration's diagonal shift.
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -77,14 +80,37 @@ def _convexify_options(value, model):
     return opts["mode"], eps
 
 
+def _is_general(model):
+    from .general_nlp import GeneralNLP
+    return isinstance(model, GeneralNLP)
+
+
 def _exact_hessian_option(value, model):
-    """options["exact_hessian"]: falsy = off; True needs a stage OCP with a stage cost that sets exact_hessian = True"""
+    """options["exact_hessian"]: falsy = off.  A stage OCP: True, and the model needs a stage cost that sets exact_hessian = True.  A general NLP
+    built with exact_hessian=True: True adds the curvature, "dominant" adds it with the diagonal-dominance safeguard"""
     if not value:
         return False
+    if _is_general(model):
+        if not getattr(model, "exact_hessian", False):
+            raise ValueError("exact_hessian on the general path needs a model built with GeneralNLP(..., exact_hessian=True): the flag puts the "
+                             "curvature's structure into the pattern of P and makes the generated library carry the kernels")
+        if value is not True and value != "dominant":
+            raise ValueError("exact_hessian: expected True or 'dominant' for a general NLP")
+        return True
+    if value == "dominant":
+        raise ValueError("exact_hessian = 'dominant' is the safeguard of the general path; a stage OCP convexifies its frame Hessians with "
+                         "options['convexify'] next to exact_hessian = True")
     if not (getattr(model, "general_cost", False) and getattr(model, "exact_hessian", False)):
         raise ValueError("exact_hessian needs a stage OCP with a stage cost (lcost) that sets exact_hessian = True: the flag puts the curvature's "
                          "structure into the pattern and makes the generated library carry the kernel")
     return True
+
+
+def _nlp_hessian_mode(value, model):
+    """None for a stage OCP (or the option off); for a general NLP the mode of mpcqp_nlp_lagrangian: 0 (True) or 1 ("dominant")"""
+    if not value or not _is_general(model):
+        return None
+    return 1 if value == "dominant" else 0
 
 
 class SQPOptimizationSolver:
@@ -124,6 +150,8 @@ class SQPOptimizationSolver:
         self.convexified = []
         # opt-in: the QP takes the Hessian of the Lagrangian under the multiplier estimate `lam` (models.StageOCP.lagrangian_system)
         self.exact_hessian = _exact_hessian_option(options.get("exact_hessian"), nlp)
+        self._nlp_mode = _nlp_hessian_mode(options.get("exact_hessian"), nlp)      # a general NLP: GeneralNLP.lagrangian_system, DESIGN 6.20
+        self.shift = None                                # ... and the last iteration's diagonal shift [batch, n]
         self.lam = np.zeros((self.batch, nlp.m)) if self.exact_hessian else None
         self.alpha_taken = None; self.accepted = None; self.gmax = None
         self.last_line_search = None                     # the NumPy statement's full result for the last iteration
@@ -159,7 +187,9 @@ class SQPOptimizationSolver:
         for i in range(self.stepNum_):
             t0 = time.perf_counter()
             localSystem = self.getLocalSystem(arg)
-            if self.exact_hessian:
+            if self._nlp_mode is not None:
+                localSystem.P, self.shift = self.model.lagrangian_system(p, self.result_["x"], self.lam, localSystem.P, None, self._nlp_mode)
+            elif self.exact_hessian:
                 mode, eps = self.convexify if self.convexify is not None else (None, 1e-6)
                 localSystem.P, touched, _ = self.model.lagrangian_system(p, self.result_["x"], self.lam, localSystem.P, None, mode, eps)
                 if self.convexify is not None:
@@ -301,11 +331,13 @@ class DeviceSQPOptimizationSolver:
         # extension (opt-in): one mpcqp_stage_lagrangian on P between the evaluation and the QP update, under the multiplier estimate
         # `lam`; with convexify its mode and eps go into that call in place of the separate mpcqp_stage_convexify
         if options.get("exact_hessian"):
-            if evaluator is not None:
-                raise ValueError("exact_hessian is limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has no constraint curvature kernel")
+            if evaluator is not None and not getattr(evaluator, "has_exact_hessian", False):
+                raise ValueError("exact_hessian: this general evaluator (evaluator=, mpcqp_nlp_*) has no constraint curvature kernel -- its library "
+                                 "was generated from a model without exact_hessian=True, or the object is no general_eval.GeneralEvaluator")
             if self.constant_matrices:
                 raise ValueError("exact_hessian does not combine with constant_matrices: the curvature changes P, which that option promises is constant")
         self.exact_hessian = _exact_hessian_option(options.get("exact_hessian"), nlp)
+        self._nlp_mode = _nlp_hessian_mode(options.get("exact_hessian"), nlp) if evaluator is not None else None
         self.alpha_taken = None; self.accepted = None
         self.iterations_done = 0
         self.step_max = None
@@ -328,6 +360,9 @@ class DeviceSQPOptimizationSolver:
         self.admm_iterations = []
         self._touched = torch.zeros(self.batch, dtype=torch.int32, device=self.dev) if self.convexify is not None else None
         self.lam = mk(self.ev.m) if self.exact_hessian else None      # the multiplier estimate, zero at the start: the first QP is the reference's
+        # a general evaluator: the workspace of mpcqp_nlp_lagrangian and, with "dominant", the last iteration's diagonal shift [batch, n]
+        self._curv = mk(self.ev.nnzP) if self._nlp_mode is not None else None
+        self.shift = mk(self.ev.n) if self._nlp_mode == 1 else None
         if self.exact_hessian and not self.ev.has_exact_hessian:
             raise ValueError("exact_hessian: the evaluator's library does not carry the kernel (a generated model with lcost and exact_hessian = True does)")
         self.f = None; self.gmax = None
@@ -395,7 +430,9 @@ class DeviceSQPOptimizationSolver:
         stream = torch.cuda.current_stream(self.dev).cuda_stream
         for i in range(self.stepNum_):
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
-            if self.exact_hessian:
+            if self._nlp_mode is not None:
+                ev.lagrangian(p, self.x, self.lam, self.ls["P"], mode=self._nlp_mode, C=self._curv, shift=self.shift, stream=stream)
+            elif self.exact_hessian:
                 mode, eps = self.convexify if self.convexify is not None else (None, 1e-6)
                 ev.lagrangian(p, self.x, self.lam, self.ls["P"], mode=mode, eps=eps, touched=self._touched, stream=stream)
                 if self.convexify is not None:
