@@ -847,7 +847,9 @@ def emit_functor(tape, name="SmUser"):
     return src
 
 
-# pf, pfpp: the launchers' PF template argument, written after SmUser or in full; pref: the export mpcqp_user_pref of a tracking library
+# The launchers, one per operation: (the handle's constants, batch, the argument block, ..., the rows, the stream).  stage_with_rows (stage_kernels.hpp)
+# picks the kernel instance that takes the rows from the functor's members, so the text is the same for every kind of data a model declares.
+# pf: the launchers' PF template argument, written after SmUser; pref: the export mpcqp_user_pref of a tracking library
 _DEVICE_TMPL = '''// generated by optimal_control_problem_amd/codegen.py -- do not edit
 #include "stage_kernels.hpp"
 
@@ -866,57 +868,40 @@ int mpcqp_user_cost(unsigned char *mask) {
   for (int i = 0; i < nl * nl; i++) mask[i] = SmUser_cost_mask[i];
   return 1;
 }
-int mpcqp_user_eval(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
-                    const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream) {
-  return (int)stage_launch_eval<SmUser%(pf)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream%(sdarg)s);
+int mpcqp_user_eval(const StageDev *sd, int batch, const StageEvalArgs *a, const StageRows *r, void *stream) {
+  return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_eval<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream, pp...); });
 }
-int mpcqp_user_merit(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
-  return (int)stage_launch_merit<SmUser%(pf)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream%(sdarg)s);
+int mpcqp_user_merit(const StageDev *sd, int batch, const StageMeritArgs *a, const StageRows *r, void *stream) {
+  return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_merit<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream, pp...); });
 }
 // the hand-over between two MPC ticks (mpcqp_stage_advance)
-int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream) {
-  return (int)stage_launch_advance<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream%(sdarg)s);
+int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, const StageRows *r, void *stream) {
+  return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_advance<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream, pp...); });
 }
 // the per-instance merit line search (mpcqp_stage_linesearch)
-int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
-  return (int)stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream%(sdarg)s);
+int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, const StageRows *r, void *stream) {
+  return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream, pp...); });
 }
 %(params)s%(link_cost)s%(sdata)s%(convexify)s%(exact)s}
 '''
 
-# a model with exact_hessian = True only: 1 and the structure of the constraint curvature over [s; u] (row-major f^2 bytes), and the launchers of
-# mpcqp_stage_lagrangian (slots: the handle's table of the curvature's slots; w: the convexification tables and scratch, used when a->mode != 0);
-# the _pp form of a library with parameters takes the rows, the _sd form of a library with stage data the rows of both.  A library without the
-# exports takes no constraint curvature
+# a model with exact_hessian = True only: 1 and the structure of the constraint curvature over [s; u] (row-major f^2 bytes), and the launcher of
+# mpcqp_stage_lagrangian (slots: the handle's table of the curvature's slots; w: the convexification tables and scratch, used when a->mode != 0).
+# A library without the exports takes no constraint curvature
 _DEVICE_EXACT_TMPL = '''int mpcqp_user_exact_hessian(unsigned char *mask) {
   constexpr int f = SmUser::nx + SmUser::nu;
   for (int i = 0; i < f * f; i++) mask[i] = SmUser_curv_mask[i];
   return 1;
 }
-int mpcqp_user_lagrangian(const StageDev *sd, int batch, const mpcqp_stage_lagrangian_args *a, const int *slots, const StageCvxBuf *w, void *stream) {
-  return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream%(sdarg)s);
+int mpcqp_user_lagrangian(const StageDev *sd, int batch, const mpcqp_stage_lagrangian_args *a, const int *slots, const StageCvxBuf *w, const StageRows *r, void *stream) {
+  return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_lagrangian<SmUser, %(cvx)s%(pf)s>(*sd, batch, *a, slots, w, (hipStream_t)stream, pp...); });
 }
 '''
-_DEVICE_EXACT_PP_TMPL = '''int mpcqp_user_lagrangian_pp(const StageDev *sd, int batch, const mpcqp_stage_lagrangian_args *a, const int *slots, const StageCvxBuf *w, void *stream,
-                             const double *theta) {
-  return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
-}
-'''
-_DEVICE_EXACT_SD_TMPL = '''int mpcqp_user_lagrangian_sd(const StageDev *sd, int batch, const mpcqp_stage_lagrangian_args *a, const int *slots, const StageCvxBuf *w, void *stream,
-                             const double *theta, const double *d) {
-%(th_lagrangian)s  return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream, StageData{d});
-}
-'''
-_DEVICE_EXACT_SD_THETA = "  if (theta) return (int)stage_launch_lagrangian<SmUser, %(pfpp)s, %(cvxpp)s>(*sd, batch, *a, slots, w, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n"
 
-# a model with convexify = True only: the launcher of mpcqp_stage_convexify (w: the handle's slot tables and scratch), and for a library with stage
-# data the form that takes the data rows.  A library without the export takes no convexification
-_DEVICE_CONVEXIFY_TMPL = '''int mpcqp_user_convexify(const StageDev *sd, int batch, const mpcqp_stage_convexify_args *a, const StageCvxBuf *w, void *stream) {
-  return (int)stage_launch_convexify<SmUser%(pf)s>(*sd, batch, *a, *w, (hipStream_t)stream%(sdarg)s);
-}
-'''
-_DEVICE_CONVEXIFY_SD_TMPL = '''int mpcqp_user_convexify_sd(const StageDev *sd, int batch, const mpcqp_stage_convexify_args *a, const StageCvxBuf *w, void *stream, const double *d) {
-  return (int)stage_launch_convexify<SmUser, %(pfpp)s>(*sd, batch, *a, *w, (hipStream_t)stream, StageData{d});
+# a model with convexify = True only: the launcher of mpcqp_stage_convexify (w: the handle's slot tables and scratch; lcost and lterm read no
+# parameters, so no instance takes them).  A library without the export takes no convexification
+_DEVICE_CONVEXIFY_TMPL = '''int mpcqp_user_convexify(const StageDev *sd, int batch, const mpcqp_stage_convexify_args *a, const StageCvxBuf *w, const StageRows *r, void *stream) {
+  return (int)stage_with_rows<SmUser, false>(*r, [&](auto... pp) { return stage_launch_convexify<SmUser%(pf)s>(*sd, batch, *a, *w, (hipStream_t)stream, pp...); });
 }
 '''
 
@@ -929,54 +914,15 @@ _DEVICE_LINK_COST_TMPL = '''int mpcqp_user_link_cost(unsigned char *mask) {
 }
 '''
 
-# a model with parameters (ntheta > 0) only: their count, their defaults (they become sd.par of the handle) and the per-instance-parameter
-# launchers (mpcqp_stage_set_instance_params; theta, plant: device rows [batch * SM_NPAR], null = the shared values)
+# a model with parameters (ntheta > 0) only: their count and their defaults (they become sd.par of the handle)
 _DEVICE_PARAMS_TMPL = '''int mpcqp_user_ntheta() { return SmUser::ntheta; }
 void mpcqp_user_theta0(double *par) { for (int i = 0; i < SmUser::ntheta; i++) par[i] = SmUser_theta0[i]; }
-int mpcqp_user_eval_pp(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
-                       const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream, const double *theta) {
-  return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
-}
-int mpcqp_user_merit_pp(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream, const double *theta) {
-  return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
-}
-int mpcqp_user_advance_pp(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream, const double *theta, const double *plant) {
-  return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant}%(sdarg)s);
-}
-int mpcqp_user_linesearch_pp(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream, const double *theta) {
-  return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr}%(sdarg)s);
-}
 '''
 
-# a model with stage data (nsd > 0) only: their count, their defaults and the launchers mpcqp_stage_* uses for such a library -- theta / plant: the
-# per-instance parameter rows (null; a library that also has ntheta > 0: null or the rows), d: the data rows [batch * horizon * nsd], null = the defaults.
-# Every instance of such a library carries a StageData; the plain and the _pp exports above pass a null one
+# a model with stage data (nsd > 0) only: their count and their defaults.  Every kernel instance of such a library carries a StageData
 _DEVICE_SDATA_TMPL = '''int mpcqp_user_nsd() { return SmUser::nsd; }
 void mpcqp_user_sdata0(double *d) { for (int i = 0; i < SmUser::nsd; i++) d[i] = SmUser_sdata0[i]; }
-int mpcqp_user_eval_sd(const StageDev *sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
-                       const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, void *stream, const double *theta,
-                       const double *d) {
-%(th_eval)s  return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageData{d});
-}
-int mpcqp_user_merit_sd(const StageDev *sd, int batch, const double *p, const double *x, double *f, double *gmax, void *stream, const double *theta,
-                        const double *d) {
-%(th_merit)s  return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageData{d});
-}
-int mpcqp_user_advance_sd(const StageDev *sd, int batch, const mpcqp_stage_advance_args *a, void *stream, const double *theta, const double *plant,
-                          const double *d) {
-%(th_advance)s  return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageData{d});
-}
-int mpcqp_user_linesearch_sd(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, void *stream, const double *theta, const double *d) {
-%(th_linesearch)s  return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageData{d});
-}
 '''
-# (the same launches with the parameter rows in front, in a library that has both)
-_DEVICE_SDATA_THETA = {
-    "th_eval": "  if (theta) return (int)stage_launch_eval<SmUser, %(pfpp)s>(*sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n",
-    "th_merit": "  if (theta) return (int)stage_launch_merit<SmUser, %(pfpp)s>(*sd, batch, p, x, f, gmax, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n",
-    "th_advance": "  if (theta || plant) return (int)stage_launch_advance<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, plant}, StageData{d});\n",
-    "th_linesearch": "  if (theta) return (int)stage_launch_linesearch<SmUser, %(pfpp)s>(*sd, batch, *a, (hipStream_t)stream, StageTheta{theta, nullptr}, StageData{d});\n",
-}
 
 _HOST_TMPL = '''// generated by optimal_control_problem_amd/codegen.py -- host build of the same functor, for checks without a GPU
 #include <cmath>
@@ -1174,24 +1120,13 @@ def device_source(tape):
     """the translation unit of a stage library.  Traced with per_frame_reference: SmUser::pref, the PF = true kernel instances only, and the
     export mpcqp_user_pref() by which mpcqp_stage_create_tracking / _create_user tell the two kinds apart; else the text it always was"""
     pf = getattr(tape, "pref", False)
-    nsd, nth = getattr(tape, "nsd", 0), getattr(tape, "ntheta", 0)
-    sub = {"pf": ", SmUser::pref" if pf else "", "pfpp": "SmUser::pref" if pf else "false",
-           "pref": "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\n" if pf else "",
-           "sdarg": ", StageData{nullptr}" if nsd else ""}      # (a library with stage data: every kernel instance takes a StageData)
-    sdata = ""
-    if nsd:
-        sdata = _DEVICE_SDATA_TMPL % dict(sub, **{k: (v % sub if nth else "") for k, v in _DEVICE_SDATA_THETA.items()})
-    cvx = ""
-    if getattr(tape, "convexify", False):
-        cvx = _DEVICE_CONVEXIFY_TMPL % sub + (_DEVICE_CONVEXIFY_SD_TMPL % sub if nsd else "")
-    exact = ""
-    if getattr(tape, "exact", None):
-        sub = dict(sub, cvxpp="true" if getattr(tape, "convexify", False) else "false")
-        exact = _DEVICE_EXACT_TMPL % sub + (_DEVICE_EXACT_PP_TMPL % sub if nth else "")
-        if nsd:
-            exact += _DEVICE_EXACT_SD_TMPL % dict(sub, th_lagrangian=_DEVICE_EXACT_SD_THETA % sub if nth else "")
-    return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL % sub if nth else "",
-                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "", sdata=sdata, convexify=cvx, exact=exact)
+    convexify = bool(getattr(tape, "convexify", False))
+    sub = {"pf": ", SmUser::pref" if pf else "", "pref": "int mpcqp_user_pref() { return SmUser::pref ? 1 : 0; }\n" if pf else "",
+           "cvx": "true" if convexify else "false"}
+    return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL if getattr(tape, "ntheta", 0) else "",
+                               link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "",
+                               sdata=_DEVICE_SDATA_TMPL if getattr(tape, "nsd", 0) else "", convexify=_DEVICE_CONVEXIFY_TMPL % sub if convexify else "",
+                               exact=_DEVICE_EXACT_TMPL % sub if getattr(tape, "exact", None) else "")
 
 
 def build_device_library(tape):

@@ -18,59 +18,30 @@
 #include "common.hpp"
 #include "stage_kernels.hpp"
 
-// The launchers a generated library exports (model == MPCQP_MODEL_USER).  advance and linesearch are optional: a library generated before
-// those entries has none.  The _pp four are the per-instance-parameter launchers of a library with ntheta > 0: the same arguments, then the
-// device rows ([batch * SM_NPAR]; advance takes the model rows and the plant rows, either may be null = the shared values).  The _sd four are the
-// launchers of a library with stage data (nsd > 0): the same arguments, then the parameter rows (null, or the rows of a library that also has
-// ntheta > 0) and the data rows ([batch * horizon * nsd], null = the defaults on every frame).
+// The launchers a generated library exports (model == MPCQP_MODEL_USER), one per operation: the handle's constants, the batch, the operation's
+// argument block (convexify: then the handle's tables and scratch; lagrangian: then the curvature's slot table and the convexification's tables and
+// scratch, null without a mode), the rows (StageRows) and the stream.  The library chooses the kernel instance from the rows (stage_with_rows).
+// eval and merit are required; the others are optional: a library generated before the entry, or from a model without the flag, has none.
 struct StageUserLib {
-  int (*eval)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *, const double *, double *,
-              double *, double *, double *, double *, void *) = nullptr;
-  int (*merit)(const StageDev *, int, const double *, const double *, double *, double *, void *) = nullptr;
-  int (*advance)(const StageDev *, int, const mpcqp_stage_advance_args *, void *) = nullptr;
-  int (*linesearch)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *) = nullptr;
-  int (*eval_pp)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *, const double *, double *,
-                 double *, double *, double *, double *, void *, const double *) = nullptr;
-  int (*merit_pp)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *) = nullptr;
-  int (*advance_pp)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *) = nullptr;
-  int (*linesearch_pp)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *) = nullptr;
-  int (*eval_sd)(const StageDev *, int, const double *, const double *, const double *, const double *, const double *, const double *, double *,
-                 double *, double *, double *, double *, void *, const double *, const double *) = nullptr;
-  int (*merit_sd)(const StageDev *, int, const double *, const double *, double *, double *, void *, const double *, const double *) = nullptr;
-  int (*advance_sd)(const StageDev *, int, const mpcqp_stage_advance_args *, void *, const double *, const double *, const double *) = nullptr;
-  int (*linesearch_sd)(const StageDev *, int, const mpcqp_stage_linesearch_args *, void *, const double *, const double *) = nullptr;
-  // optional, a library generated from a model with convexify = True (mpcqp_stage_convexify): the handle's tables and scratch, then the stream;
-  // the _sd form of a library with stage data takes the data rows last (lcost / lterm read no theta: there is no _pp form)
-  int (*convexify)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, void *) = nullptr;
-  int (*convexify_sd)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, void *, const double *) = nullptr;
-  // optional, a library generated from a model with exact_hessian = True (mpcqp_stage_lagrangian): the curvature's slot table, the convexification's
-  // tables and scratch (null when the library has none), then the stream; the _pp form takes the parameter rows, the _sd form the rows of both
-  int (*lagrangian)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, void *) = nullptr;
-  int (*lagrangian_pp)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, void *, const double *) = nullptr;
-  int (*lagrangian_sd)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, void *, const double *,
-                       const double *) = nullptr;
-  bool all_pp() const { return eval_pp && merit_pp && advance_pp && linesearch_pp; }
-  bool all_sd() const { return eval_sd && merit_sd && advance_sd && linesearch_sd; }
+  int (*eval)(const StageDev *, int, const StageEvalArgs *, const StageRows *, void *) = nullptr;
+  int (*merit)(const StageDev *, int, const StageMeritArgs *, const StageRows *, void *) = nullptr;
+  int (*advance)(const StageDev *, int, const mpcqp_stage_advance_args *, const StageRows *, void *) = nullptr;
+  int (*linesearch)(const StageDev *, int, const mpcqp_stage_linesearch_args *, const StageRows *, void *) = nullptr;
+  int (*convexify)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, const StageRows *, void *) = nullptr;
+  int (*lagrangian)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, const StageRows *, void *) = nullptr;
 };
 template <class Fn> static void stage_sym(void *lib, const char *name, Fn *&fn) { fn = (Fn *)dlsym(lib, name); }
 static StageUserLib stage_user_lib(void *lib) {
   StageUserLib u;
   stage_sym(lib, "mpcqp_user_eval", u.eval); stage_sym(lib, "mpcqp_user_merit", u.merit);
   stage_sym(lib, "mpcqp_user_advance", u.advance); stage_sym(lib, "mpcqp_user_linesearch", u.linesearch);
-  stage_sym(lib, "mpcqp_user_eval_pp", u.eval_pp); stage_sym(lib, "mpcqp_user_merit_pp", u.merit_pp);
-  stage_sym(lib, "mpcqp_user_advance_pp", u.advance_pp); stage_sym(lib, "mpcqp_user_linesearch_pp", u.linesearch_pp);
-  stage_sym(lib, "mpcqp_user_eval_sd", u.eval_sd); stage_sym(lib, "mpcqp_user_merit_sd", u.merit_sd);
-  stage_sym(lib, "mpcqp_user_advance_sd", u.advance_sd); stage_sym(lib, "mpcqp_user_linesearch_sd", u.linesearch_sd);
-  stage_sym(lib, "mpcqp_user_convexify", u.convexify); stage_sym(lib, "mpcqp_user_convexify_sd", u.convexify_sd);
-  stage_sym(lib, "mpcqp_user_lagrangian", u.lagrangian); stage_sym(lib, "mpcqp_user_lagrangian_pp", u.lagrangian_pp);
-  stage_sym(lib, "mpcqp_user_lagrangian_sd", u.lagrangian_sd);
+  stage_sym(lib, "mpcqp_user_convexify", u.convexify); stage_sym(lib, "mpcqp_user_lagrangian", u.lagrangian);
   return u;
 }
 
 // the zoo's PP instances (quadrotor, cart-pole) live in stage_eval_pp.hip, a translation unit of their own that compiles beside this one
-hipError_t mpcqp_launch_eval_pp(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx, const double *lbg,
-                                const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st, StageTheta th);
-hipError_t mpcqp_launch_merit_pp(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st, StageTheta th);
+hipError_t mpcqp_launch_eval_pp(const StageDev &sd, int batch, const StageEvalArgs &a, hipStream_t st, StageTheta th);
+hipError_t mpcqp_launch_merit_pp(const StageDev &sd, int batch, const StageMeritArgs &a, hipStream_t st, StageTheta th);
 hipError_t mpcqp_launch_advance_pp(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st, StageTheta th);
 hipError_t mpcqp_launch_linesearch_pp(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st, StageTheta th);
 
@@ -151,23 +122,27 @@ hipError_t mpcqp_launch_step(int batch, int nvar, int n, int np, double alpha, c
   return hipGetLastError();
 }
 
-// The common tail of the four entry points that launch a model's kernel, after their own argument checks: a launch may not be larger than a
-// stored parameter set (plant: advance reads the plant's set too) or than the stored stage data, then one of five launches -- a generated library or the
-// zoo, with the shared parameters or with per-instance rows; a library with stage data always through its _sd exports.  zoo(tag) launches the plain
-// zoo instance of StageTag tag; zoo_pp(th) calls the PP twin in stage_eval_pp.hip; user(), user_pp(th) and user_sd(th, d) call the library's exports.
-template <class Zoo, class ZooPP, class User, class UserPP, class UserSD>
-static int stage_launch(mpcqp_stage *s, int batch, bool plant, Zoo zoo, ZooPP zoo_pp, User user, UserPP user_pp, UserSD user_sd) {
-  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
-  if (plant) if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_PLANT, batch)) return rc;
+// The common tail of the six entry points that launch a model's kernel, after their own argument checks.  `rows` says which stored parameter sets
+// the operation reads (the stage data: every one): a launch may not be larger than a stored set it reads or than the stored stage data.  Then the
+// rows, and one of three launches: zoo(tag) launches the plain zoo instance of StageTag tag; zoo_pp(th) calls the PP twin in stage_eval_pp.hip;
+// user(rows) calls the library's export and answers an MPCQP code (stage_hipchk for a bare launcher).
+enum { STAGE_ROWS_THETA = 1, STAGE_ROWS_PLANT = 2 };
+static int stage_hipchk(int e) { MPCQP_HIPCHK((hipError_t)e); return MPCQP_OK; }
+template <class Zoo, class ZooPP, class User>
+static int stage_launch(mpcqp_stage *s, int batch, int rows, Zoo zoo, ZooPP zoo_pp, User user) {
+  if (rows & STAGE_ROWS_THETA) if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
+  if (rows & STAGE_ROWS_PLANT) if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_PLANT, batch)) return rc;
   if (s->sd_batch > 0 && batch > s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch is larger than the stored stage data (mpcqp_stage_set_stage_data)");
   MPCQP_HIPCHK(hipSetDevice(s->device));
-  const StageTheta th{s->theta(MPCQP_PARAMS_MODEL), plant ? s->theta(MPCQP_PARAMS_PLANT) : nullptr};
-  const bool pp = th.model || th.plant;
-  hipError_t e;
-  if (s->sd.model == MPCQP_MODEL_USER) e = (hipError_t)(s->nsd > 0 ? user_sd(th, s->sdata()) : pp ? user_pp(th) : user());
-  else e = pp ? zoo_pp(th) : stage_visit_zoo(s->sd.model, s->sd.pref != 0, zoo);
-  MPCQP_HIPCHK(e);
+  const StageRows r{rows & STAGE_ROWS_THETA ? s->theta(MPCQP_PARAMS_MODEL) : nullptr, rows & STAGE_ROWS_PLANT ? s->theta(MPCQP_PARAMS_PLANT) : nullptr, s->sdata()};
+  if (s->sd.model == MPCQP_MODEL_USER) return user(r);
+  MPCQP_HIPCHK(r.theta || r.plant ? zoo_pp(StageTheta{r.theta, r.plant}) : stage_visit_zoo(s->sd.model, s->sd.pref != 0, zoo));
   return MPCQP_OK;
+}
+// (convexify and lagrangian: generated libraries only, the entry point has refused the zoo)
+template <class User> static int stage_launch(mpcqp_stage *s, int batch, int rows, User user) {
+  auto none = [](auto) { return hipErrorInvalidValue; };
+  return stage_launch(s, batch, rows, none, none, user);
 }
 
 extern "C" {
@@ -339,28 +314,27 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   mpcqp_stage *s = new mpcqp_stage();
   s->user_lib = lib; s->user = user;
   mpcqp_stage_desc dd = *d; dd.model = MPCQP_MODEL_USER;
-  // optional exports of a library generated with parameters: their count, their defaults (which become sd.par: d->par stays ignored for a
-  // generated library) and the four PP launchers (StageUserLib).  A library without them -- every one generated before this entry -- has no parameters.
+  // optional exports of a library generated with parameters: their count and their defaults (which become sd.par: d->par stays ignored for a
+  // generated library).  A library without them has no parameters.
   {
     auto ntf = (int (*)())dlsym(lib, "mpcqp_user_ntheta");
     auto t0f = (void (*)(double *))dlsym(lib, "mpcqp_user_theta0");
     const int nt = ntf ? ntf() : 0;
-    if (nt < 0 || nt > SM_NPAR || (nt > 0 && !(t0f && user.all_pp()))) {
+    if (nt < 0 || nt > SM_NPAR || (nt > 0 && !t0f)) {
       mpcqp_stage_destroy(s);
-      return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares parameters but not 0..8 of them, or lacks mpcqp_user_theta0 or a _pp launcher");
+      return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares parameters but not 0..8 of them, or lacks mpcqp_user_theta0");
     }
     s->ntheta = nt;
     for (int i = 0; i < SM_NPAR; i++) dd.par[i] = 0.0;
     if (nt > 0) t0f(dd.par);
   }
-  // optional export of a library generated with stage data: how many values per frame its hfun / lcost / lterm read; such a library is always
-  // launched through its four _sd exports.  A library without it -- every one generated before this entry -- has none.
+  // optional export of a library generated with stage data: how many values per frame its hfun / lcost / lterm read.  A library without it has none.
   {
     auto nsf = (int (*)())dlsym(lib, "mpcqp_user_nsd");
     const int ns = nsf ? nsf() : 0;
-    if (ns < 0 || ns > SM_MAXSD || (ns > 0 && !user.all_sd())) {
+    if (ns < 0 || ns > SM_MAXSD) {
       mpcqp_stage_destroy(s);
-      return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares stage data but not 0..8 values per frame, or lacks an _sd launcher");
+      return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares stage data but not 0..8 values per frame");
     }
     s->nsd = ns;
   }
@@ -376,15 +350,15 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
                                    s->link_cost ? lmask.data() : nullptr)) { mpcqp_stage_destroy(s); return rc; }
   // optional export of a library generated with convexify = True: the launcher of mpcqp_stage_convexify.  Its cost mask is closed under the
   // fill-in of the correction, so every element the kernel adds has a slot in the pattern just built; the tables say which.
-  if (s->general_cost && user.convexify && (s->nsd == 0 || user.convexify_sd)) {
+  if (s->general_cost && user.convexify) {
     if (int rc = stage_build_convexify_tables(s, mask.data())) { mpcqp_stage_destroy(s); return rc; }
   }
   // optional exports of a library generated with exact_hessian = True: the structure of the constraint curvature over [s; u] -- part of the cost mask,
-  // so every element has a slot in the pattern just built -- and the launchers of mpcqp_stage_lagrangian, one for every kind of data the library takes
+  // so every element has a slot in the pattern just built -- and the launcher of mpcqp_stage_lagrangian
   {
     auto ef = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_exact_hessian");
     std::vector<unsigned char> cmask((size_t)(nx + nu) * (nx + nu));
-    if (s->general_cost && ef && ef(cmask.data()) && user.lagrangian && (s->ntheta == 0 || user.lagrangian_pp) && (s->nsd == 0 || user.lagrangian_sd)) {
+    if (s->general_cost && ef && ef(cmask.data()) && user.lagrangian) {
       if (int rc = stage_build_lagrangian_table(s, cmask.data())) { mpcqp_stage_destroy(s); return rc; }
     }
   }
@@ -539,26 +513,24 @@ int mpcqp_stage_eval(mpcqp_stage *s, int batch, const double *p, const double *x
   if (batch <= 0) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
   if (!p || !x || !lbx || !ubx || !lbg || !ubg || !P || !q || !A || !l || !u) return mpcqp_set_error(MPCQP_ERR_ARG, "null data pointer");
   const StageDev &sd = s->sd;
+  const StageEvalArgs a{p, x, lbx, ubx, lbg, ubg, P, q, A, l, u};
   hipStream_t st = (hipStream_t)stream;
-  return stage_launch(s, batch, false,
-      [&](auto t) { using T = decltype(t); return stage_launch_eval<typename T::M, T::PF>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st); },
-      [&](StageTheta th) { return mpcqp_launch_eval_pp(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st, th); },
-      [&] { return s->user.eval(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream); },
-      [&](StageTheta th) { return s->user.eval_pp(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th.model); },
-      [&](StageTheta th, const double *d) { return s->user.eval_sd(&sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, stream, th.model, d); });
+  return stage_launch(s, batch, STAGE_ROWS_THETA,
+      [&](auto t) { using T = decltype(t); return stage_launch_eval<typename T::M, T::PF>(sd, batch, a, st); },
+      [&](StageTheta th) { return mpcqp_launch_eval_pp(sd, batch, a, st, th); },
+      [&](const StageRows &r) { return stage_hipchk(s->user.eval(&sd, batch, &a, &r, stream)); });
 }
 
 int mpcqp_stage_merit(mpcqp_stage *s, int batch, const double *p, const double *x, double *f, double *gmax, void *stream) {
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   if (batch <= 0 || !p || !x) return mpcqp_set_error(MPCQP_ERR_ARG, "bad batch or null data pointer");
   const StageDev &sd = s->sd;
+  const StageMeritArgs a{p, x, f, gmax};
   hipStream_t st = (hipStream_t)stream;
-  return stage_launch(s, batch, false,
-      [&](auto t) { using T = decltype(t); return stage_launch_merit<typename T::M, T::PF>(sd, batch, p, x, f, gmax, st); },
-      [&](StageTheta th) { return mpcqp_launch_merit_pp(sd, batch, p, x, f, gmax, st, th); },
-      [&] { return s->user.merit(&sd, batch, p, x, f, gmax, stream); },
-      [&](StageTheta th) { return s->user.merit_pp(&sd, batch, p, x, f, gmax, stream, th.model); },
-      [&](StageTheta th, const double *d) { return s->user.merit_sd(&sd, batch, p, x, f, gmax, stream, th.model, d); });
+  return stage_launch(s, batch, STAGE_ROWS_THETA,
+      [&](auto t) { using T = decltype(t); return stage_launch_merit<typename T::M, T::PF>(sd, batch, a, st); },
+      [&](StageTheta th) { return mpcqp_launch_merit_pp(sd, batch, a, st, th); },
+      [&](const StageRows &r) { return stage_hipchk(s->user.merit(&sd, batch, &a, &r, stream)); });
 }
 
 int mpcqp_stage_step(mpcqp_stage *s, int batch, double alpha, const double *dw, double *x, double *step_max, const int *status, void *stream) {
@@ -593,12 +565,10 @@ int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_arg
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_advance (generated before this entry); regenerate it");
   const StageDev &sd = s->sd;
   hipStream_t st = (hipStream_t)stream;
-  return stage_launch(s, batch, true,
+  return stage_launch(s, batch, STAGE_ROWS_THETA | STAGE_ROWS_PLANT,
       [&](auto t) { using T = decltype(t); return stage_launch_advance<typename T::M, T::PF>(sd, batch, *a, st); },
       [&](StageTheta th) { return mpcqp_launch_advance_pp(sd, batch, *a, st, th); },
-      [&] { return s->user.advance(&sd, batch, a, stream); },
-      [&](StageTheta th) { return s->user.advance_pp(&sd, batch, a, stream, th.model, th.plant); },
-      [&](StageTheta th, const double *d) { return s->user.advance_sd(&sd, batch, a, stream, th.model, th.plant, d); });
+      [&](const StageRows &r) { return stage_hipchk(s->user.advance(&sd, batch, a, &r, stream)); });
 }
 
 int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesearch_args *a, void *stream) {
@@ -616,12 +586,10 @@ int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesear
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_linesearch (generated before this entry); regenerate it");
   const StageDev &sd = s->sd;
   hipStream_t st = (hipStream_t)stream;
-  return stage_launch(s, batch, false,
+  return stage_launch(s, batch, STAGE_ROWS_THETA,
       [&](auto t) { using T = decltype(t); return stage_launch_linesearch<typename T::M, T::PF>(sd, batch, *a, st); },
       [&](StageTheta th) { return mpcqp_launch_linesearch_pp(sd, batch, *a, st, th); },
-      [&] { return s->user.linesearch(&sd, batch, a, stream); },
-      [&](StageTheta th) { return s->user.linesearch_pp(&sd, batch, a, stream, th.model); },
-      [&](StageTheta th, const double *d) { return s->user.linesearch_sd(&sd, batch, a, stream, th.model, d); });
+      [&](const StageRows &r) { return stage_hipchk(s->user.linesearch(&sd, batch, a, &r, stream)); });
 }
 
 int mpcqp_stage_has_convexify(const mpcqp_stage *s) { return s && s->convexify ? 1 : 0; }
@@ -654,13 +622,11 @@ int mpcqp_stage_convexify(mpcqp_stage *s, int batch, const mpcqp_stage_convexify
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the built-in models have diagonal weights: there is nothing to convexify (a generated model with lcost and convexify = True has)");
   if (!s->convexify)
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_convexify: regenerate it from a model with a stage cost (lcost) and convexify = True");
-  if (s->sd_batch > 0 && batch > s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch is larger than the stored stage data (mpcqp_stage_set_stage_data)");
-  MPCQP_HIPCHK(hipSetDevice(s->device));
-  const StageDev &sd = s->sd;
-  StageCvxBuf w;
-  if (int rc = stage_convexify_buffers(s, batch, &w)) return rc;
-  MPCQP_HIPCHK((hipError_t)(s->nsd > 0 ? s->user.convexify_sd(&sd, batch, a, &w, stream, s->sdata()) : s->user.convexify(&sd, batch, a, &w, stream)));
-  return MPCQP_OK;
+  return stage_launch(s, batch, 0, [&](const StageRows &r) -> int {      // (lcost / lterm read no theta: the parameter rows are not looked at)
+    StageCvxBuf w;
+    if (int rc = stage_convexify_buffers(s, batch, &w)) return rc;
+    return stage_hipchk(s->user.convexify(&s->sd, batch, a, &w, &r, stream));
+  });
 }
 
 int mpcqp_stage_has_exact_hessian(const mpcqp_stage *s) { return s && s->exact ? 1 : 0; }
@@ -679,18 +645,11 @@ int mpcqp_stage_lagrangian(mpcqp_stage *s, int batch, const mpcqp_stage_lagrangi
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_lagrangian: regenerate it from a model with a stage cost (lcost) and exact_hessian = True");
   if (a->mode != 0 && !s->convexify)
     return mpcqp_set_error(MPCQP_ERR_LIMIT, "a mode needs the convexification: regenerate the library from a model that also sets convexify = True");
-  if (int rc = stage_theta_batch_ok(s, MPCQP_PARAMS_MODEL, batch)) return rc;
-  if (s->sd_batch > 0 && batch > s->sd_batch) return mpcqp_set_error(MPCQP_ERR_ARG, "batch is larger than the stored stage data (mpcqp_stage_set_stage_data)");
-  MPCQP_HIPCHK(hipSetDevice(s->device));
-  const StageDev &sd = s->sd;
-  StageCvxBuf w;
-  if (a->mode != 0) if (int rc = stage_convexify_buffers(s, batch, &w)) return rc;
-  const StageCvxBuf *wp = a->mode != 0 ? &w : nullptr;
-  const double *th = s->theta(MPCQP_PARAMS_MODEL);
-  MPCQP_HIPCHK((hipError_t)(s->nsd > 0 ? s->user.lagrangian_sd(&sd, batch, a, s->dlslots, wp, stream, th, s->sdata())
-                            : th     ? s->user.lagrangian_pp(&sd, batch, a, s->dlslots, wp, stream, th)
-                                     : s->user.lagrangian(&sd, batch, a, s->dlslots, wp, stream)));
-  return MPCQP_OK;
+  return stage_launch(s, batch, STAGE_ROWS_THETA, [&](const StageRows &r) -> int {
+    StageCvxBuf w;
+    if (a->mode != 0) if (int rc = stage_convexify_buffers(s, batch, &w)) return rc;
+    return stage_hipchk(s->user.lagrangian(&s->sd, batch, a, s->dlslots, a->mode != 0 ? &w : nullptr, &r, stream));
+  });
 }
 
 }  // extern "C"

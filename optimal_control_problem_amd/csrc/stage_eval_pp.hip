@@ -6,17 +6,13 @@
 #include "../../include/mpcqp.h"
 #include "stage_kernels.hpp"
 
-hipError_t mpcqp_launch_eval_pp(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx, const double *lbg,
-                                const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st, StageTheta th) {
-  // (an invalid value is not reached: mpcqp_stage_set_instance_params refuses a model without parameters)
-  return stage_visit_zoo<true>(sd.model, sd.pref, [&](auto t) {
-    using T = decltype(t);
-    return stage_launch_eval<typename T::M, T::PF>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, st, th);
-  });
+// (an invalid value is not reached: mpcqp_stage_set_instance_params refuses a model without parameters)
+hipError_t mpcqp_launch_eval_pp(const StageDev &sd, int batch, const StageEvalArgs &a, hipStream_t st, StageTheta th) {
+  return stage_visit_zoo<true>(sd.model, sd.pref, [&](auto t) { using T = decltype(t); return stage_launch_eval<typename T::M, T::PF>(sd, batch, a, st, th); });
 }
 
-hipError_t mpcqp_launch_merit_pp(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st, StageTheta th) {
-  return stage_visit_zoo<true>(sd.model, sd.pref, [&](auto t) { using T = decltype(t); return stage_launch_merit<typename T::M, T::PF>(sd, batch, p, x, f, gmax, st, th); });
+hipError_t mpcqp_launch_merit_pp(const StageDev &sd, int batch, const StageMeritArgs &a, hipStream_t st, StageTheta th) {
+  return stage_visit_zoo<true>(sd.model, sd.pref, [&](auto t) { using T = decltype(t); return stage_launch_merit<typename T::M, T::PF>(sd, batch, a, st, th); });
 }
 
 hipError_t mpcqp_launch_advance_pp(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st, StageTheta th) {

@@ -9,7 +9,7 @@
 #include "stage_convexify.hpp"
 #include "../../include/mpcqp.h"
 
-#define STAGE_ABI_VERSION 7
+#define STAGE_ABI_VERSION 8
 
 struct StageDev {
   int model, N, nx, nu, f, np, n, m, ng, nvar, nnzP, nnzA;   // ng = all general rows: (N-1)*nx dynamics rows, then N*nh path rows, then (N-1)*nk link rows
@@ -967,21 +967,37 @@ __global__ void __launch_bounds__(256) stage_convexify_sum_kernel(int batch, int
   if (any) P[(long)b * nnzP + slot] += acc;
 }
 
+// The rows a launch reads beside its arguments (device pointers; null = the shared values sd.par, the defaults M::sdata0): the per-instance
+// parameters of the controller's model and of the plant (only advance passes a plant row) and the stage data.  The one form in which the rows cross
+// from libmpcqp.so into a generated library: every launcher of the boundary is (const StageDev *, batch, its argument block, ..., const StageRows *, stream).
+struct StageRows { const double *theta, *plant, *sdata; };
+// the argument blocks of the two operations whose public entry points take loose pointers (mpcqp_stage_eval, mpcqp_stage_merit)
+struct StageEvalArgs { const double *p, *x, *lbx, *ubx, *lbg, *ubg; double *P, *q, *A, *l, *u; };
+struct StageMeritArgs { const double *p, *x; double *f, *gmax; };
+// fn(pack...) with the trailing pack of the kernel instance that takes these rows: a functor with stage data always ends in a StageData; a functor
+// with parameters gets a StageTheta in front when a parameter row is set (THETA: the operation has instances that read theta -- convexify has none).
+// A functor without the member compiles no instance with that element.
+template <class M, bool THETA, class Fn> inline hipError_t stage_with_rows(const StageRows &r, Fn fn) {
+  auto data = [&](auto... th) {
+    if constexpr (sm_nsd<M>::value > 0) return fn(th..., StageData{r.sdata}); else return fn(th...);
+  };
+  if constexpr (THETA && sm_ntheta<M>::value > 0) if (r.theta || r.plant) return data(StageTheta{r.theta, r.plant});
+  return data();
+}
+
 // launchers shared by the zoo dispatch and generated libraries
 // (PP: empty, or a StageTheta and / or a StageData behind the stream -- the per-instance-parameter and the stage-data instances)
 template <class M, bool PF = false, class... PP>
-inline hipError_t stage_launch_eval(const StageDev &sd, int batch, const double *p, const double *x, const double *lbx, const double *ubx,
-                                    const double *lbg, const double *ubg, double *P, double *q, double *A, double *l, double *u, hipStream_t st,
-                                    PP... pp) {
+inline hipError_t stage_launch_eval(const StageDev &sd, int batch, const StageEvalArgs &a, hipStream_t st, PP... pp) {
   constexpr int f = M::nx + M::nu;
   const int ppad = PF ? (sd.N * M::nx + f - 1) / f * f : f;
   const long threads = (long)batch * ((sm_has_coop<M>::value && (64 % f == 0) && M::nx <= f) ? ppad + f * sd.N : sd.n);
-  stage_eval_kernel<M, PF, PP...><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(sd, batch, p, x, lbx, ubx, lbg, ubg, P, q, A, l, u, pp...);
+  stage_eval_kernel<M, PF, PP...><<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(sd, batch, a.p, a.x, a.lbx, a.ubx, a.lbg, a.ubg, a.P, a.q, a.A, a.l, a.u, pp...);
   return hipGetLastError();
 }
 template <class M, bool PF = false, class... PP>
-inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const double *p, const double *x, double *f, double *gmax, hipStream_t st, PP... pp) {
-  stage_merit_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, p, x, f, gmax, pp...);
+inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const StageMeritArgs &a, hipStream_t st, PP... pp) {
+  stage_merit_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a.p, a.x, a.f, a.gmax, pp...);
   return hipGetLastError();
 }
 template <class M, bool PF = false, class... PP>
@@ -1011,7 +1027,7 @@ inline hipError_t stage_launch_convexify(const StageDev &sd, int batch, const mp
 // mpcqp_stage_lagrangian: the add kernel, then -- with a mode -- the convexify kernel with the StageExact element and its sum kernel on the updated P,
 // so that a frame the convexification does not touch holds the bits mode = 0 gives.  slots: the curvature's table; w: the convexification's (mode != 0)
 // (CVX: the library also carries the convexification -- without it only the add kernel is instantiated and a mode is an invalid value)
-template <class M, bool PF, bool CVX, class... PP>
+template <class M, bool CVX, bool PF = false, class... PP>
 inline hipError_t stage_launch_lagrangian(const StageDev &sd, int batch, const mpcqp_stage_lagrangian_args &a, const int *slots, const StageCvxBuf *w,
                                           hipStream_t st, PP... pp) {
   if constexpr (sm_has_exact<M>::value) {

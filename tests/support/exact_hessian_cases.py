@@ -11,8 +11,8 @@ EPS = 1e-6
 MODES = ("project", "mirror")
 B = 5
 STATUS = np.array([1, 2, 7, 3, 1], np.int32)      # instance 3: MPCQP_PRIMAL_INFEASIBLE, no point
-CASES = ("pend2", "pend3", "pend_theta", "pend_sd", "pend_pf", "nohfun", "klin", "llink", "cvx", "wide7")
-CONVEXIFY_CASES = ("pend2", "pend3", "pend_theta", "pend_sd", "pend_pf", "cvx", "wide7")
+CASES = ("pend2", "pend3", "pend_theta", "pend_sd", "pend_pf", "nohfun", "klin", "llink", "cvx", "wide7", "pend_theta_sd")
+CONVEXIFY_CASES = ("pend2", "pend3", "pend_theta", "pend_sd", "pend_pf", "cvx", "wide7", "pend_theta_sd")
 
 
 class Pendulum(models.StageOCP):
@@ -63,6 +63,14 @@ class PendulumSD(Pendulum):
         th, w, v = s[..., 0], s[..., 1], u[..., 0]
         e = th - self.sdata[0]
         return np.stack([e * e + self.sdata[1] * v * v + 0.3 * th * w, w * v + 0.2 * w * w], axis=-1)
+
+
+class PendulumThetaSD(PendulumTheta):
+    """both: the parameters of F and the stage data of the path constraint, every instance with rows of its own"""
+    name = "eh_pendulum_theta_sd"
+    nsd = 2
+    sdata = PendulumSD.sdata
+    hfun = PendulumSD.hfun
 
 
 class PendulumPF(Pendulum):
@@ -148,7 +156,7 @@ _MAKE = {
     "pend2": lambda: _pend(Pendulum, 2), "pend3": lambda: _pend(Pendulum, 3), "pend_theta": lambda: _pend(PendulumTheta, 3),
     "pend_sd": lambda: _pend(PendulumSD, 3), "pend_pf": lambda: _pend(PendulumPF, 3), "nohfun": lambda: _pend(NoPath, 3),
     "klin": lambda: _pend(LinearLink, 3), "llink": lambda: _pend(MovePenalty, 3), "cvx": lambda: _pend(Cvx, 4),
-    "wide7": lambda: Wide7(3, 0.05, Q=[1.0] * 7, R=[0.1] * 3),
+    "wide7": lambda: Wide7(3, 0.05, Q=[1.0] * 7, R=[0.1] * 3), "pend_theta_sd": lambda: _pend(PendulumThetaSD, 3),
 }
 
 
@@ -161,7 +169,7 @@ _CACHE = {}
 
 
 def case(name):
-    """model, p, x, y, status, bounds (theta rows for pend_theta, data rows d for pend_sd), the statement's local system `ls`, the cost's frame
+    """model, p, x, y, status, bounds (theta rows for the models with ntheta, data rows d for those with nsd), the statement's local system `ls`, the cost's frame
     Hessians `hess` [B, N, nl, nl], the curvature `C` [B, N, f, f] and the Frobenius norms `hnorm` [B, N] of H_k^L = H_k + C_k.  Computed once per case
     and left unchanged; callers copy what they change.  The model is left with nothing set."""
     if name in _CACHE:
@@ -181,9 +189,9 @@ def case(name):
         mu[4] = 0.0
         mu[4, :, 0] = 1.0                                   # instance 4: every frame stays positive
     theta = d = None
-    if name == "pend_theta":
+    if mdl.ntheta:
         theta = np.asarray(mdl.theta, float) * rng.uniform(0.6, 1.5, size=(B, 2))
-    if name == "pend_sd":
+    if mdl.nsd:
         d = np.asarray(mdl.sdata, float) + rng.uniform(-0.2, 0.4, size=(B, N, 2))
     lbx, ubx, lbg, ubg = mdl.stacked_bounds(X[:, 0, :])
     c = dict(name=name, model=mdl, p=p, x=x, y=y, status=STATUS.copy(), lbx=lbx, ubx=ubx, lbg=lbg, ubg=ubg, theta=theta, d=d)

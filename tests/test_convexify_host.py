@@ -14,6 +14,7 @@ import pytest
 
 from optimal_control_problem_amd import _lib, codegen, models
 from tests.support import convexify_cases as cc
+from tests.support import kernel_instances as ki
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -71,7 +72,7 @@ def test_generated_source_has_the_export_only_with_the_flag():
         src = codegen.device_source(plain)
         assert "convexify" not in src
         fs = codegen.device_source(flagged)
-        assert "mpcqp_user_convexify(" in fs and ("mpcqp_user_convexify_sd(" in fs) == (mdl.nsd > 0)
+        assert "mpcqp_user_convexify(" in fs and ("mpcqp_user_nsd" in fs) == ("static constexpr int nsd" in fs) == (mdl.nsd > 0)
         assert "_pp(" not in fs[fs.index("mpcqp_user_convexify"):]
         if np.array_equal(flagged.cost["mask"], plain.cost["mask"]):       # nothing but the export differs
             cut = fs.index("int mpcqp_user_convexify(")
@@ -266,8 +267,12 @@ def test_flagged_library_exports_the_launchers(built):
     nm = lambda so: subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
     for name, sd in (("bump3", False), ("bump_sd", True)):
         mdl = cc.case(name)["model"]
-        syms = nm(codegen.build_device_library(_tape(mdl, convexify=True)))
-        assert " T mpcqp_user_convexify\n" in syms and (" T mpcqp_user_convexify_sd\n" in syms) == sd
-        assert "mpcqp_user_convexify" not in nm(codegen.build_device_library(_tape(mdl)))
+        so = codegen.build_device_library(_tape(mdl, convexify=True))
+        assert " T mpcqp_user_convexify\n" in nm(so)
+        # the one launcher's instance takes the data rows in a library with stage data, and no instance takes them in a library without
+        got = {n for n in ki.kernel_instances(so) if n.startswith("stage_convexify_kernel<")}
+        assert got == {"stage_convexify_kernel<SmUser, false, StageData>" if sd else "stage_convexify_kernel<SmUser, false>"}, sorted(got)
+        plain = codegen.build_device_library(_tape(mdl))
+        assert "mpcqp_user_convexify" not in nm(plain) and not [n for n in ki.kernel_instances(plain) if "convexify" in n]
     syms = nm(os.path.join(ROOT, "optimal_control_problem_amd", "libmpcqp.so"))
     assert " T mpcqp_stage_convexify\n" in syms and " T mpcqp_stage_has_convexify\n" in syms

@@ -249,7 +249,7 @@ def _tape(mdl, **kw):
                          lcost=mdl.lcost, lterm=mdl.lterm, convexify=bool(mdl.convexify), **k, **kw)
 
 
-@pytest.mark.parametrize("name", ("pend3", "pend_theta", "pend_sd", "pend_pf", "nohfun", "klin", "llink"))
+@pytest.mark.parametrize("name", ("pend3", "pend_theta", "pend_sd", "pend_theta_sd", "pend_pf", "nohfun", "klin", "llink"))
 def test_generated_source_and_pattern_without_the_flag_are_unchanged(name):
     mdl = ec.case(name)["model"]
     twin = _twin(mdl)
@@ -260,7 +260,7 @@ def test_generated_source_and_pattern_without_the_flag_are_unchanged(name):
         assert word not in src, word
     flagged = _tape(mdl, exact_hessian=True)
     fs = codegen.device_source(flagged)
-    assert "mpcqp_user_lagrangian(" in fs and ("mpcqp_user_lagrangian_pp(" in fs) == (mdl.ntheta > 0) and ("mpcqp_user_lagrangian_sd(" in fs) == (mdl.nsd > 0)
+    assert "mpcqp_user_lagrangian(" in fs and ("mpcqp_user_ntheta" in fs) == (mdl.ntheta > 0) and ("mpcqp_user_nsd" in fs) == (mdl.nsd > 0)
     assert ("HG(" in fs) == (mdl.nh > 0) and "FG(" in fs
     assert np.array_equal(flagged.exact["mask"], mdl.curvature_mask) and np.array_equal(flagged.cost["mask"], mdl.cost_mask)
     # the unflagged model's pattern is the one it always had: cost mask without the curvature

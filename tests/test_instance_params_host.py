@@ -10,6 +10,7 @@ import pytest
 
 from optimal_control_problem_amd import _lib, codegen, models
 from tests.support import instance_params_cases as ipc
+from tests.support import kernel_instances as ki
 from tests.support import linesearch_cases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,12 +114,15 @@ def test_generated_functor_with_parameters_matches_numpy():
     m = ipc.param_pendulum()
     tape = codegen.trace(m.F, m.nx, m.nu, m.hfun, 1, m.h_lo, m.h_hi, kfun=m.kfun, nk=1, k_lo=m.k_lo, k_hi=m.k_hi, ntheta=2)
     src = codegen.device_source(tape)
-    for name in ("mpcqp_user_ntheta", "mpcqp_user_theta0", "mpcqp_user_eval_pp", "mpcqp_user_merit_pp", "mpcqp_user_advance_pp", "mpcqp_user_linesearch_pp",
-                 "static constexpr int ntheta = 2", "par[0]", "par[1]"):
+    for name in ("mpcqp_user_ntheta", "mpcqp_user_theta0", "static constexpr int ntheta = 2", "par[0]", "par[1]"):
         assert name in src, name
     q = ipc.plain_pendulum()
     plain = codegen.device_source(codegen.trace(q.F, q.nx, q.nu))
     assert "ntheta" not in plain and "_pp" not in plain and "StageTheta" not in plain
+    # the library with parameters carries the instances that take the rows beside the plain ones; the library without carries none
+    got = ki.kernel_instances(codegen.build_device_library(tape))
+    assert ki.four(False) | ki.four(False, "StageTheta") <= got and not [n for n in got if "StageData" in n], sorted(got)
+    assert not [n for n in ki.kernel_instances(codegen.build_device_library(codegen.trace(q.F, q.nx, q.nu))) if "StageTheta" in n or "StageData" in n]
     L = C.CDLL(codegen.build_host_library(tape))
     assert L.user_host_ntheta() == 2
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
