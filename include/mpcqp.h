@@ -386,6 +386,12 @@ int mpcqp_stage_has_cost(const mpcqp_stage *s);
  * takes no reference and no parameters; mpcqp_stage_merit and _linesearch include it, the stage_cost log of mpcqp_stage_advance (the k = 0 frame
  * term) does not.  0 for the zoo models and for a library without the export (every one generated before this entry). */
 int mpcqp_stage_has_link_cost(const mpcqp_stage *s);
+/* The number of residual rows nr when the library was generated with a Gauss-Newton frame cost f = sum_k |rcost(s_k, u_k, r)|^2 (the reference's
+ * addVectorCost, sum w_i e_i^2 without 1/2, with a nonlinear e; an optional terminal residual on the last frame): the library exports
+ * mpcqp_user_residual_cost, q is the exact gradient 2 J' r and P takes 2 J'J over [s_k; u_k; r] -- positive semidefinite by construction -- in
+ * place of the exact Hessian.  mpcqp_stage_has_cost is 1 for such a handle as well; mpcqp_stage_has_convexify and _has_exact_hessian are 0.
+ * 0 for the zoo models, for a scalar stage cost and for a library without the export (every one generated before this entry). */
+int mpcqp_stage_has_residual_cost(const mpcqp_stage *s);
 /* CSC sparsity of P (n x n, both triangles, as CasADi hands it to CuCaQP) and A = [I; dg/dw] (m x n): the arrays
  * mpcqp_create takes.  Pp, Ap: n + 1 entries; Pi: nnz(P); Ai: nnz(A).  Host pointers. */
 int mpcqp_stage_pattern(const mpcqp_stage *s, int *Pp, int *Pi, int *Ap, int *Ai);

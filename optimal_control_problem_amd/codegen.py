@@ -489,6 +489,91 @@ def trace_cost(lfun, nx, nu, nr, nsd=0, model=None):
     return tape, g
 
 
+NR_MAX = 32           # the most residual rows of a Gauss-Newton frame cost (models.StageOCP.rcost / rterm): a stated limit, like NTHETA_MAX
+
+
+def trace_residual(rfun, nx, nu, nr_ref, nsd=0, model=None):
+    """residual r(s, u, r) -> [..., n_out] on tracers (a list of components is accepted): the residual tape over the inputs [s; u; r](; d), d the
+    nsd stage-data values bound to model.sdata while rfun runs, as in trace_cost.  At most NR_MAX rows"""
+    nl = nx + nu + nr_ref
+    tape = Tape(nl + nsd)
+    mk = lambda a, b: TV(tape, [TS(tape, i) for i in range(a, b)])
+    with _bound_theta(model if nsd else None, mk(nl, nl + nsd), "sdata"):
+        out = rfun(mk(0, nx), mk(nx, nx + nu), mk(nx + nu, nl))
+    if isinstance(out, TS):
+        out = TV(tape, [out])
+    if isinstance(out, (list, tuple)):
+        out = TV(tape, [TS._lift(tape, v) for v in out])
+    if not isinstance(out, TV) or len(out) < 1:
+        raise ValueError("the residual must return its components [..., nr] (an array or a list)")
+    if len(out) > NR_MAX:
+        raise ValueError("at most %d residual rows are supported (nr = %d)" % (NR_MAX, len(out)))
+    tape.outputs = [TS._lift(tape, v).idx for v in out.items]
+    tape.n_out = len(tape.outputs)
+    tape.nx, tape.nu, tape.nr = nx, nu, nr_ref
+    if nsd:
+        tape.in_names = [("s", nx), ("u", nu), ("r", nr_ref), ("d", nsd)]
+        tape.plain_from = nl
+    return tape
+
+
+def _append_inputs(tape, k):
+    """the same tape with k more inputs behind its own (the node ids of everything else move up by k)"""
+    t = Tape(tape.n_in + k)
+    m = {i: i for i in range(tape.n_in)}
+    for i in range(tape.n_in, len(tape.nodes)):
+        nd = tape.nodes[i]
+        m[i] = t.const(nd[1]) if nd[0] == "const" else t._add((nd[0],) + tuple(m[a] for a in nd[1:]))
+    t.outputs = [m[o] for o in tape.outputs]
+    for a in ("nx", "nu", "nr"):
+        if hasattr(tape, a): setattr(t, a, getattr(tape, a))
+    return t
+
+
+def residual_tapes(rtape):
+    """What a Gauss-Newton frame cost f = sum_i r_i^2 needs next to its residual tape (trace_residual): dict with
+    L: the value tape sum_i r_i^2, i ascending from 0.0 (the order of Python's sum over the components);
+    G: its gradient tape over [s; u; r] (gradient_tape: 2 J' r);
+    RT: the transposed-Jacobian tape -- inputs [s; u; r](; d) and then n_out plain weights w, outputs J' w over [s; u; r]: gradient_tape of w' r with
+        w as inputs that carry no derivative;
+    mask: the structure of J'J | eye from the structural Jacobian (tangent_outputs): entry (a, b) is set when some row depends on both inputs."""
+    nl = rtape.nx + rtape.nu + rtape.nr
+    nsd = rtape.n_in - nl
+    n_out = len(rtape.outputs)
+    names = getattr(rtape, "in_names", None)
+    L = rtape.clone()
+    acc = L.const(0.0)
+    for o in rtape.outputs:
+        acc = L.binary("add", acc, L.binary("mul", o, o))
+    L.outputs = [acc]
+    G = gradient_tape(L)
+    G.outputs = G.outputs[:nl]
+    W = _append_inputs(rtape, n_out)
+    acc = W.const(0.0)
+    for i, o in enumerate(W.outputs):
+        acc = W.s_add(acc, W.s_mul(nl + nsd + i, o))
+    W.outputs = [acc]
+    RT = gradient_tape(W)
+    RT.outputs = RT.outputs[:nl]
+    RT.in_names = [("s", rtape.nx), ("u", rtape.nu), ("r", rtape.nr)] + ([("d", nsd)] if nsd else []) + [("w", n_out)]
+    RT.plain_from = nl
+    if names:
+        L.in_names = G.in_names = names
+        L.plain_from = G.plain_from = nl
+    J = np.zeros((n_out, nl), bool)
+    for k in range(nl):
+        t, d = tangent_outputs(rtape, k)
+        J[:, k] = [not (t.is_const(v) and t.nodes[v][1] == 0.0) for v in d]
+    Ji = J.astype(np.int64)
+    return dict(L=L, G=G, RT=RT, mask=((Ji.T @ Ji) > 0) | np.eye(nl, dtype=bool))
+
+
+GN_REFUSES_CONVEXIFY = ("convexify does not combine with a Gauss-Newton cost (rcost): 2 J'J is positive semidefinite by construction, there is nothing "
+                        "to convexify")
+GN_REFUSES_EXACT = ("exact_hessian does not combine with a Gauss-Newton cost (rcost): adding the constraints' curvature to a matrix that drops the "
+                    "cost's own is not covered")
+
+
 def _trace_link(kfun, nx, nu, nk):
     """kfun(s, u, s_next, u_next) -> [..., nk] on tracers over the inputs [s; u; s_next; u_next]"""
     tape = Tape(2 * (nx + nu))
@@ -584,7 +669,7 @@ def link_is_linear(link):
 
 
 def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False,
-          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None, convexify=False, exact_hessian=False):
+          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None, convexify=False, exact_hessian=False, rcost=None, rterm=None):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
@@ -608,9 +693,22 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     exact_hessian (models.StageOCP.exact_hessian; needs lcost, whose pattern has the off-diagonal slots): the functors FG and HG, the gradients over
     [s; u] of lam' F and mu' hfun (trace_curvature); the structure of their Hessians joins the [s; u] block of the cost's mask before the closure of
     convexify, and the library exports the launchers of mpcqp_stage_lagrangian.  A nonlinear kfun is refused: its curvature couples two frames.
+    Without it the library is the text it always was.
+    rcost(s, u, r) -> [..., nr] (and rterm -> [..., nrt] for the last frame; models.StageOCP.rcost): a Gauss-Newton frame cost
+    f = sum_k |rcost(s_k, u_k, r)|^2 in place of lcost / lterm.  tape.cost holds the value and gradient tapes derived from the residual tape
+    (residual_tapes) and the structure of J'J as the mask; tape.residual the residual tapes and their transposed-Jacobian tapes, which the functor
+    carries as R, RT (RTm, RTT: the terminal frame's).  The rules of lcost on theta and sdata hold; convexify and exact_hessian are refused.
     Without it the library is the text it always was."""
     ntheta = int(ntheta)
     nsd = int(nsd)
+    if rcost is not None and (lcost is not None or lterm is not None):
+        raise ValueError("rcost excludes lcost / lterm: the frame cost is either a scalar with its exact Hessian or a residual with the Gauss-Newton one")
+    if rterm is not None and rcost is None:
+        raise ValueError("a terminal residual (rterm) needs a stage residual (rcost)")
+    if rcost is not None and convexify:
+        raise ValueError(GN_REFUSES_CONVEXIFY)
+    if rcost is not None and exact_hessian:
+        raise ValueError(GN_REFUSES_EXACT)
     if nsd > NSD_MAX:
         raise ValueError("at most %d stage-data values are supported (nsd = %d)" % (NSD_MAX, nsd))
     if ntheta > NTHETA_MAX:
@@ -675,6 +773,19 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
             mask = closed_mask(mask)
             tape.convexify = True
         tape.cost = dict(L=L, G=G, LT=LT, GT=GT, mask=mask)
+    elif rcost is not None:
+        with _bound_theta(guarded, _ThetaGuard("rcost")):
+            R = trace_residual(rcost, nx, nu, nx, nsd, model)
+        d = residual_tapes(R)
+        mask = d["mask"]
+        Rm = dm = None
+        if rterm is not None:
+            with _bound_theta(guarded, _ThetaGuard("rterm")):
+                Rm = trace_residual(rterm, nx, nu, nx, nsd, model)
+            dm = residual_tapes(Rm)
+            mask = mask | dm["mask"]
+        tape.cost = dict(L=d["L"], G=d["G"], LT=dm["L"] if dm else None, GT=dm["G"] if dm else None, mask=mask)
+        tape.residual = dict(R=R, RT=d["RT"], Rm=Rm, RTT=dm["RT"] if dm else None, nr=R.n_out, nrt=Rm.n_out if Rm is not None else R.n_out)
     elif lterm is not None:
         raise ValueError("a terminal cost needs a stage cost")
     elif convexify:
@@ -811,6 +922,14 @@ def emit_functor(tape, name="SmUser"):
         # L: out[0] = l(s, u, r); LG: out[nx + nu + nx] = dl / d[s; u; r]; LT, LTG: the terminal frame's
         for fn, tp in (("L", cost["L"]), ("LG", cost["G"]), ("LT", cost["LT"] or cost["L"]), ("LTG", cost["GT"] or cost["G"])):
             src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *r, %sT *out) {\n%s\n  }\n" % (fn, dsig, _emit_body(tp))
+    res = getattr(tape, "residual", None)
+    if res:
+        # R: out[nr] = the residual; RT: out[nx + nu + nx] = J' w over [s; u; r], the weights w plain doubles like d; RTm, RTT: the terminal frame's
+        # (nrt rows).  L, LG above are sum r_i^2 and its gradient: the Hessian 2 J'J is formed from R and RT (sm_residual_column)
+        src += "  static constexpr int has_residual = 1, nr = %d, nrt = %d;\n" % (res["nr"], res["nrt"])
+        for fn, tp, wsig in (("R", res["R"], ""), ("RT", res["RT"], "const double *w, "), ("RTm", res["Rm"] or res["R"], ""),
+                             ("RTT", res["RTT"] or res["RT"], "const double *w, ")):
+            src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *r, %s%sT *out) {\n%s\n  }\n" % (fn, dsig, wsig, _emit_body(tp))
     if getattr(tape, "pref", False):
         src += "  static constexpr bool pref = true;\n"
     link_cost = getattr(tape, "link_cost", None)
@@ -882,7 +1001,7 @@ int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, const StageRows *r, void *stream) {
   return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream, pp...); });
 }
-%(params)s%(link_cost)s%(sdata)s%(convexify)s%(exact)s}
+%(params)s%(link_cost)s%(sdata)s%(convexify)s%(exact)s%(residual)s}
 '''
 
 # a model with exact_hessian = True only: 1 and the structure of the constraint curvature over [s; u] (row-major f^2 bytes), and the launcher of
@@ -902,6 +1021,28 @@ int mpcqp_user_lagrangian(const StageDev *sd, int batch, const mpcqp_stage_lagra
 # parameters, so no instance takes them).  A library without the export takes no convexification
 _DEVICE_CONVEXIFY_TMPL = '''int mpcqp_user_convexify(const StageDev *sd, int batch, const mpcqp_stage_convexify_args *a, const StageCvxBuf *w, const StageRows *r, void *stream) {
   return (int)stage_with_rows<SmUser, false>(*r, [&](auto... pp) { return stage_launch_convexify<SmUser%(pf)s>(*sd, batch, *a, *w, (hipStream_t)stream, pp...); });
+}
+'''
+
+# a model with a Gauss-Newton frame cost (rcost) only: the number of residual rows.  A library without the export has a scalar cost or diagonal weights
+_DEVICE_RESIDUAL_TMPL = '''int mpcqp_user_residual_cost() { return SmUser::nr; }
+'''
+
+# the host build of such a model: value by L / LT, every column of the gradient and of 2 J'J by the helper a device thread calls (sm_residual_column)
+_HOST_RESIDUAL_TMPL = '''template <class M> static void host_cost_gn(const double *s, const double *u, const double *r, const double *d, int term, double *val, double *grad, double *hess) {
+  constexpr int nx = M::nx, nu = M::nu, nl = 2 * nx + nu;
+  double v[1];
+  if (term) M::template LT<double>(s, u, r, %(d)sv); else M::template L<double>(s, u, r, %(d)sv);
+  val[0] = v[0];
+  for (int c = 0; c < nl; c++) {
+    Dual sd[nx], ud[nu], rd[nx], gd[nl];
+    for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
+    for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
+    for (int i = 0; i < nx; i++) rd[i] = {r[i], nx + nu + i == c ? 1.0 : 0.0};
+    sm_residual_column<M, %(sd)s>(term != 0, sd, ud, rd, d, gd);
+    for (int i = 0; i < nl; i++) hess[i * nl + c] = gd[i].d;
+    grad[c] = gd[c].v;
+  }
 }
 '''
 
@@ -929,7 +1070,7 @@ _HOST_TMPL = '''// generated by optimal_control_problem_amd/codegen.py -- host b
 #include "stage_models.hpp"
 
 %(functor)s
-// val [1], grad [nl], hess [nl * nl] row-major over [s; u; r], nl = 2 nx + nu; term != 0: the terminal frame's cost
+%(residual)s// val [1], grad [nl], hess [nl * nl] row-major over [s; u; r], nl = 2 nx + nu; term != 0: the terminal frame's cost
 template <class M> static void host_cost(const double *s, const double *u, const double *r, int term, double *val, double *grad, double *hess) {
   if constexpr (M::has_cost != 0) {
     constexpr int nx = M::nx, nu = M::nu, nl = 2 * nx + nu;
@@ -988,7 +1129,7 @@ void user_host_link(const double *s, const double *u, const double *sn, const do
 }
 %(link_cost)sint user_host_has_cost() { return SmUser::has_cost; }
 void user_host_cost(const double *s, const double *u, const double *r, int term, double *val, double *grad, double *hess) {
-  host_cost<SmUser>(s, u, r, term, val, grad, hess);
+  %(cost_call)s;
 }
 // out [nh], jac [nh * (nx + nu)] row-major
 void user_host_path(const double *s, const double *u, double *out, double *jac) {
@@ -1057,7 +1198,7 @@ template <class M> static void host_cost_d(const double *s, const double *u, con
 }
 extern "C" {
 void user_host_cost_d(const double *s, const double *u, const double *r, const double *d, int term, double *val, double *grad, double *hess) {
-  host_cost_d<SmUser>(s, u, r, d, term, val, grad, hess);
+  %(cost_d)s<SmUser>(s, u, r, d, term, val, grad, hess);
 }
 '''
 
@@ -1126,7 +1267,8 @@ def device_source(tape):
     return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL if getattr(tape, "ntheta", 0) else "",
                                link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "",
                                sdata=_DEVICE_SDATA_TMPL if getattr(tape, "nsd", 0) else "", convexify=_DEVICE_CONVEXIFY_TMPL % sub if convexify else "",
-                               exact=_DEVICE_EXACT_TMPL % sub if getattr(tape, "exact", None) else "")
+                               exact=_DEVICE_EXACT_TMPL % sub if getattr(tape, "exact", None) else "",
+                               residual=_DEVICE_RESIDUAL_TMPL if getattr(tape, "residual", None) else "")
 
 
 def build_device_library(tape):
@@ -1138,9 +1280,14 @@ def build_device_library(tape):
 def host_source(tape):
     """the translation unit of the host build (a functor with stage data: the exports without a data row use the defaults)"""
     nth, nsd = getattr(tape, "ntheta", 0), getattr(tape, "nsd", 0)
+    res = bool(getattr(tape, "residual", None))      # (a Gauss-Newton cost: user_host_cost and user_host_cost_d go through host_cost_gn)
     return _HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr",
                          "link_cost": _HOST_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "",
-                         "hd": "SmUser_sdata0, " if nsd else "", "sdata": _HOST_SDATA_TMPL if nsd else "", "exact": _host_exact(tape, nth, nsd)}
+                         "hd": "SmUser_sdata0, " if nsd else "", "exact": _host_exact(tape, nth, nsd),
+                         "sdata": _HOST_SDATA_TMPL % {"cost_d": "host_cost_gn" if res else "host_cost_d"} if nsd else "",
+                         "residual": _HOST_RESIDUAL_TMPL % {"d": "d, " if nsd else "", "sd": "true" if nsd else "false"} if res else "",
+                         "cost_call": ("host_cost_gn<SmUser>(s, u, r, %s, term, val, grad, hess)" % ("SmUser_sdata0" if nsd else "nullptr")) if res
+                                      else "host_cost<SmUser>(s, u, r, term, val, grad, hess)"}
 
 
 def _host_exact(tape, nth, nsd):

@@ -58,6 +58,7 @@ struct mpcqp_stage {
   StageUserLib user;
   bool general_cost = false;          // the library carries its own stage cost: Q, R and mpcqp_stage_set_weights do not apply
   bool link_cost = false;             // the library carries a link cost between consecutive frames (mpcqp_user_link_cost): P couples frame k to k + 1
+  int residual_rows = 0;              // the library's frame cost is a Gauss-Newton one (mpcqp_user_residual_cost): its residual rows nr; 0: none
   // per-instance parameters (mpcqp_stage_set_instance_params): set `which` is in force when th_batch[which] > 0
   int ntheta = 0;                     // entries of a row the model reads: 7 quadrotor, 4 cart-pole, 0 double integrator, mpcqp_user_ntheta of a library
   double *dth[2] = {nullptr, nullptr};
@@ -346,6 +347,12 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
   std::vector<unsigned char> lmask((size_t)4 * (nx + nu) * (nx + nu));
   auto lf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_link_cost");
   s->link_cost = lf && lf(lmask.data());
+  // optional export of a library generated with a Gauss-Newton frame cost (rcost): the number of its residual rows.  Nothing else differs for the
+  // handle: the library's eval kernel writes 2 J'J into the pattern of the cost mask
+  {
+    auto rf = (int (*)())dlsym(lib, "mpcqp_user_residual_cost");
+    s->residual_rows = s->general_cost && rf ? rf() : 0;
+  }
   if (int rc = stage_create_common(&dd, nx, nu, nh, h_lo, h_hi, s, s->general_cost ? mask.data() : nullptr, nk, k_lo, k_hi, pref,
                                    s->link_cost ? lmask.data() : nullptr)) { mpcqp_stage_destroy(s); return rc; }
   // optional export of a library generated with convexify = True: the launcher of mpcqp_stage_convexify.  Its cost mask is closed under the
@@ -499,6 +506,8 @@ int mpcqp_stage_dims(const mpcqp_stage *s, int *o) {
 int mpcqp_stage_has_cost(const mpcqp_stage *s) { return s && s->general_cost ? 1 : 0; }
 
 int mpcqp_stage_has_link_cost(const mpcqp_stage *s) { return s && s->link_cost ? 1 : 0; }
+
+int mpcqp_stage_has_residual_cost(const mpcqp_stage *s) { return s ? s->residual_rows : 0; }
 
 int mpcqp_stage_pattern(const mpcqp_stage *s, int *Pp, int *Pi, int *Ap, int *Ai) {
   if (!s || !Pp || !Pi || !Ap || !Ai) return mpcqp_set_error(MPCQP_ERR_ARG, "null argument");

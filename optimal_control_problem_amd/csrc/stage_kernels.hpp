@@ -69,6 +69,13 @@ template <class M, class T> __device__ __forceinline__ void stage_cost_grad(bool
   if constexpr (sm_nsd<M>::value > 0) { if (M::has_term && last) M::template LTG<T>(s, u, r, d, out); else M::template LG<T>(s, u, r, d, out); }
   else { if (M::has_term && last) M::template LTG<T>(s, u, r, out); else M::template LG<T>(s, u, r, out); }
 }
+// what stage_eval_kernel reads for the column that carries the seed: g[i].d = column c of the frame Hessian, g[c].v = the column's gradient entry.  A
+// functor with a scalar cost: the generated gradient on dual numbers (the exact Hessian); one with a residual (sm_has_residual): the Gauss-Newton
+// column 2 J' J_c and 2 J_c' r (sm_residual_column).  Each lane forms its own column: the mapping of threads to columns is that of the exact path
+template <class M> __device__ __forceinline__ void stage_cost_column(bool last, const Dual *s, const Dual *u, const Dual *r, const double *d, Dual *out) {
+  if constexpr (sm_has_residual<M>::value) sm_residual_column<M, (sm_nsd<M>::value > 0)>(last, s, u, r, d, out);
+  else stage_cost_grad<M, Dual>(last, s, u, r, d, out);
+}
 
 // the QP returned a point (solved, solved inaccurately, or stopped at the iteration limit): its dw, y may be used
 __device__ __forceinline__ bool stage_status_ok(int s) { return s == MPCQP_SOLVED || s == MPCQP_SOLVED_INACCURATE || s == MPCQP_MAX_ITER_REACHED; }
@@ -132,7 +139,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
         for (int a = 0; a < nx; a++) { s[a] = {fr[a], 0.0}; rr[a] = {rk[a], a == i ? 1.0 : 0.0}; }
 #pragma unroll
         for (int a = 0; a < nu; a++) uu[a] = {fr[nx + a], 0.0};
-        stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
+        stage_cost_column<M>(k == N - 1, s, uu, rr, dv, g);
         int e = 0;
         double gv = 0.0;
 #pragma unroll
@@ -173,7 +180,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
         for (int i = 0; i < nx; i++) s[i] = {fr[i], 0.0};
 #pragma unroll
         for (int i = 0; i < nu; i++) uu[i] = {fr[nx + i], 0.0};
-        stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
+        stage_cost_column<M>(k == N - 1, s, uu, rr, dv, g);
         double gv = 0.0;
 #pragma unroll
         for (int r = 0; r < nx; r++) { acc[r] += g[f + r].d; gv = r == j ? g[f + r].v : gv; }
@@ -233,7 +240,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
       Dual rr[nx], g[nl];
 #pragma unroll
       for (int i = 0; i < nx; i++) rr[i] = {pb[i], 0.0};
-      stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
+      stage_cost_column<M>(k == N - 1, s, uu, rr, dv, g);
 #pragma unroll
       for (int i = 0; i < nx; i++) if (mk[(f + i) * nl]) Pc[e++] = g[f + i].d;
       gv = 0.0; bbase = 0u;
@@ -304,7 +311,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
     Dual rr[nx], g[nl];
 #pragma unroll
     for (int i = 0; i < nx; i++) rr[i] = {pb[i], 0.0};
-    stage_cost_grad<M, Dual>(k == N - 1, s, uu, rr, dv, g);
+    stage_cost_column<M>(k == N - 1, s, uu, rr, dv, g);
     int e = 0;
     double gv = 0.0;
 #pragma unroll

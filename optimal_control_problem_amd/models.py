@@ -194,6 +194,14 @@ class StageOCP:
     # src/OptimalControlProblem.cpp:491-497) and its QP uses the exact Hessian (SQPOptimizationSolver.cpp:55-60); here the
     # callables are traced (codegen.trace_cost), the gradient is derived on the tape and the Hessian is its derivative.
     lcost = None; lterm = None
+    # optional Gauss-Newton frame cost, the third form: rcost(s, u, r) -> [..., nr] (an array or a list of components, like hfun),
+    # f = sum_k |rcost(s_k, u_k, r)|^2 -- no 1/2 and no weight vector, the convention of the docstring above (addVectorCost with a nonlinear e): the
+    # user scales the residuals -- and rterm -> [..., nrt] the same for the last frame only.  q is the exact gradient 2 J' r; P takes 2 J'J over
+    # [s_k; u_k; r], positive semidefinite by construction, in place of the exact Hessian of lcost.  It excludes lcost / lterm; it may read self.sdata
+    # and may not read self.theta, as lcost; general_cost stays True for such a model and gauss_newton is True; cost_mask is the structure of J'J.
+    # convexify and exact_hessian are refused.  At most NR_MAX rows each.
+    rcost = None; rterm = None
+    NR_MAX = 32
     # opt-in trajectory tracking: one reference state per frame, p = [r_0; ...; r_{N-1}] (np = N nx), and frame k's cost terms take r_k:
     # sum_k (s_k - r_k)' Q_k (s_k - r_k) + u_k' R_k u_k, or sum_k l(s_k, u_k, r_k).  The reference needs nothing special for it: setReference
     # takes an SX of any size (src/OptimalControlProblem.cpp:570-572), computeOptimalTrajectory checks the size only (:85-90) and the user
@@ -336,8 +344,30 @@ class StageOCP:
         self.ngd = (self.N - 1) * self.nx                 # dynamics rows
         self.ng = self.ngd + self.N * self.nh + (self.N - 1) * self.nk    # all general rows: dynamics, nh path rows per frame, nk link rows per stage
         self.m = self.n + self.ng
-        self.general_cost = self.lcost is not None
-        if self.general_cost:
+        self.gauss_newton = self.rcost is not None
+        self.general_cost = self.lcost is not None or self.gauss_newton
+        if self.gauss_newton:
+            from . import codegen
+            if self.lcost is not None or self.lterm is not None:
+                raise ValueError("rcost excludes lcost / lterm: the frame cost is either a scalar with its exact Hessian or a residual with the "
+                                 "Gauss-Newton one")
+            if self.convexify:
+                raise ValueError(codegen.GN_REFUSES_CONVEXIFY)
+            if self.exact_hessian:
+                raise ValueError(codegen.GN_REFUSES_EXACT)
+            self._rtape = codegen.trace_residual(self.rcost, self.nx, self.nu, self.nx, self.nsd, self)
+            d = codegen.residual_tapes(self._rtape)
+            self._ltape, self._gtape, mask = d["L"], d["G"], d["mask"]
+            self._rttape = self._lttape = self._gttape = None
+            if self.rterm is not None:
+                self._rttape = codegen.trace_residual(self.rterm, self.nx, self.nu, self.nx, self.nsd, self)
+                d = codegen.residual_tapes(self._rttape)
+                self._lttape, self._gttape, mask = d["L"], d["G"], mask | d["mask"]
+            self.nr, self.nrt = self._rtape.n_out, (self._rttape or self._rtape).n_out
+            self.cost_mask = mask
+        elif self.rterm is not None:
+            raise ValueError("a terminal residual (rterm) needs a stage residual (rcost)")
+        elif self.general_cost:
             from . import codegen
             dkw = {"nsd": self.nsd, "model": self} if self.nsd else {}
             self._ltape, self._gtape = codegen.trace_cost(self.lcost, self.nx, self.nu, self.nx, **dkw)
@@ -508,11 +538,34 @@ class StageOCP:
                 o[:, -1] = np.broadcast_to(np.asarray(v), shape)[:, -1]
         return out
 
+    @staticmethod
+    def _residual_jacobian(tape, inputs, nl):
+        """(r [B, n, nr], J [B, n, nr, nl]) of a residual tape on the frames of `inputs`: values directly, columns by complex-step differentiation"""
+        shape = np.shape(inputs[0]); eps = 1e-30
+        ev = lambda ins: np.stack([np.broadcast_to(np.asarray(o), shape) for o in tape.evaluate(ins)], axis=-1)
+        r = ev(inputs).astype(float)
+        J = np.zeros(shape + (len(tape.outputs), nl))
+        for c in range(nl):
+            ins = [np.asarray(v).astype(complex) for v in inputs]
+            ins[c] = ins[c] + 1j * eps
+            J[..., c] = ev(ins).imag / eps
+        return r, J
+
     def cost_derivatives(self, p, x):
         """(grad [B, N, nl], hess [B, N, nl, nl]) of the stage cost on every frame over [s; u; r]: gradient tape evaluated
-        directly, Hessian columns by complex-step differentiation of the gradient tape (exact to rounding)"""
+        directly, Hessian columns by complex-step differentiation of the gradient tape (exact to rounding).  A Gauss-Newton cost (rcost):
+        (2 J' r, 2 J'J), J the residual's Jacobian by complex-step differentiation of the residual tape"""
         inputs = self._cost_inputs(p, x)
         nl = len(inputs) - self.nsd; B, N = inputs[0].shape
+        if self.gauss_newton:
+            grad = np.zeros((B, N, nl)); hess = np.zeros((B, N, nl, nl))
+            for tape, sl in ((self._rtape, slice(0, N if self._rttape is None else N - 1)), (self._rttape, slice(N - 1, N))):
+                if tape is None:
+                    continue
+                r, J = self._residual_jacobian(tape, [v[:, sl] for v in inputs], nl)
+                grad[:, sl] = 2.0 * np.einsum("bkic,bki->bkc", J, r)
+                hess[:, sl] = 2.0 * np.einsum("bkia,bkic->bkac", J, J)
+            return grad, hess
         grad = np.stack(self._cost_eval(self._gtape, self._gttape, inputs), axis=-1)
         hess = np.zeros((B, N, nl, nl)); eps = 1e-30
         for c in range(nl):

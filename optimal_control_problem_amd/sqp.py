@@ -27,6 +27,8 @@ the same call convexifies H_k + C_k.  For models with lcost that set exact_hessi
 GeneralNLP(..., exact_hessian=True): there True adds the curvature of g over the whole of w and "dominant" adds it with the
 diagonal-dominance safeguard (general_nlp.GeneralNLP.lagrangian_system states the rule, mpcqp_nlp_lagrangian runs it on the device); `shift`
 holds the last iteration's diagonal shift.
+A stage OCP with a Gauss-Newton frame cost (models.StageOCP.rcost) needs no option: its local system carries 2 J'J and both loops run as
+they are; options["convexify"] and options["exact_hessian"] are refused for it with the model's reason.
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -59,6 +61,9 @@ def _convexify_options(value, model):
     if value is None or value is False:
         return None
     from .models import StageOCP
+    if getattr(model, "gauss_newton", False):      # a residual frame cost (rcost): the model decides, with its reason
+        from .codegen import GN_REFUSES_CONVEXIFY
+        raise ValueError(GN_REFUSES_CONVEXIFY)
     opts = {"mode": "project", "eps": 1e-6}
     if isinstance(value, str):
         opts["mode"] = value
@@ -90,6 +95,9 @@ def _exact_hessian_option(value, model):
     built with exact_hessian=True: True adds the curvature, "dominant" adds it with the diagonal-dominance safeguard"""
     if not value:
         return False
+    if getattr(model, "gauss_newton", False):      # a residual frame cost (rcost): the model decides, with its reason
+        from .codegen import GN_REFUSES_EXACT
+        raise ValueError(GN_REFUSES_EXACT)
     if _is_general(model):
         if not getattr(model, "exact_hessian", False):
             raise ValueError("exact_hessian on the general path needs a model built with GeneralNLP(..., exact_hessian=True): the flag puts the "

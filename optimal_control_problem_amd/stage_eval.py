@@ -70,6 +70,7 @@ def _bind(L):
     L.mpcqp_stage_dims.argtypes = [vp, vp]
     L.mpcqp_stage_has_cost.argtypes = [vp]
     L.mpcqp_stage_has_link_cost.argtypes = [vp]
+    L.mpcqp_stage_has_residual_cost.argtypes = [vp]
     L.mpcqp_stage_pattern.argtypes = [vp, vp, vp, vp, vp]
     L.mpcqp_stage_eval.argtypes = [vp, C.c_int] + [dp] * 11 + [vp]
     L.mpcqp_stage_merit.argtypes = [vp, C.c_int, dp, dp, dp, dp, vp]
@@ -101,6 +102,7 @@ def model_tape(model):
     general = bool(getattr(model, "general_cost", False))
     nk = int(getattr(model, "nk", 0))
     link_cost = bool(getattr(model, "link_cost", False))
+    gn = bool(getattr(model, "gauss_newton", False))      # a residual frame cost (rcost / rterm) in place of lcost / lterm
     h_lo, h_hi = model.path_bounds()
     # a model that declares parameters (ntheta, theta) keeps them as data of the generated functor.  The zoo classes, when they take this
     # path (a path / link constraint, a general cost), keep their constants in the code as before: no parameters on that handle
@@ -111,7 +113,8 @@ def model_tape(model):
     if nsd:
         pkw = dict(pkw, nsd=nsd, sdata0=model.sdata, model=model)
     return cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
-                    lcost=model.lcost if general else None, lterm=model.lterm if general else None,
+                    lcost=model.lcost if general and not gn else None, lterm=model.lterm if general and not gn else None,
+                    **({"rcost": model.rcost, "rterm": model.rterm} if gn else {}),
                     kfun=model.kfun if nk else None, nk=nk, k_lo=model.k_lo if nk else None, k_hi=model.k_hi if nk else None,
                     **({"per_frame_reference": True} if getattr(model, "per_frame_reference", False) else {}), **pkw,
                     **({"llink": model.llink} if link_cost else {}),
@@ -197,6 +200,8 @@ class StageEvaluator:
         self.ng = self.m - self.n
         self.general_cost = bool(L.mpcqp_stage_has_cost(self._h))
         self.link_cost = bool(L.mpcqp_stage_has_link_cost(self._h))      # a link cost between consecutive frames (models.StageOCP.llink)
+        self.nr = int(L.mpcqp_stage_has_residual_cost(self._h))          # residual rows of a Gauss-Newton frame cost (models.StageOCP.rcost); 0: none
+        self.gauss_newton = self.nr > 0
         self.param_count = int(L.mpcqp_stage_param_count(self._h))      # parameters per instance (mpcqp_stage_set_instance_params); 0: none
         self.nsd = int(L.mpcqp_stage_data_count(self._h))               # stage-data values per frame (mpcqp_stage_set_stage_data); 0: none
         self.has_convexify = bool(L.mpcqp_stage_has_convexify(self._h))  # the library carries the launcher of mpcqp_stage_convexify (model.convexify)
