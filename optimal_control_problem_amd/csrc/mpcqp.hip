@@ -126,41 +126,37 @@ static int dalloc(mpcqp_handle *h, T **p, size_t count) {
   return MPCQP_OK;
 }
 
-// the kernel instance a handle runs (instantiated in the k_*.hip units, kernel_table.hpp): waves per QP, register budget, factor location, and --
-// as its own instance so that the full-setup kernels carry no code for it -- the kept-workspace entry (mpcqp_update_vectors)
-static const void *res_kernel_of(const mpcqp_handle *h, bool reuse) {
-  const Selection &s = h->sel;
-  auto lds = [&](int nw, int minw) { return reuse ? mpcqp_kernel_res_lds_r1(nw, minw) : mpcqp_kernel_res_lds_r0(nw, minw); };
-  auto gb = [&](int nw, int minw, bool zyg) { return reuse ? mpcqp_kernel_res_gb_r1(nw, minw, zyg) : mpcqp_kernel_res_gb_r0(nw, minw, zyg); };
-  auto mono = [&](int nw) { return reuse ? mpcqp_kernel_oc_mono_r1(nw, s.oc_ng(), s.oc_nh(), s.tiles) : mpcqp_kernel_oc_mono_r0(nw, s.oc_ng(), s.oc_nh(), s.tiles); };
-  if (s.oc) return mono(s.oc8 ? 8 : 4);      // (eight waves: nullptr without an arrow head, such handles run the two-kernel form)
-  if (s.gblocks && s.waves == 2) return gb(2, 3, false);
-  if (s.gblocks && s.zyg) return gb(4, s.occ3 ? 3 : 2, true);
-  if (s.gblocks && s.occ3) return gb(4, 3, false);
-  if (s.gblocks) return gb(4, s.occ4 ? 4 : 2, false);
-  if (s.waves == 1) return lds(1, s.res1x ? 4 : 2);
-  if (s.waves == 8) return lds(8, 2);
-  if (s.waves == 2) return lds(2, 3);
-  if (s.res3 == 4) return lds(4, 4);
-  if (s.res3 == 3) return lds(4, 3);
-  return lds(4, s.wide ? 1 : 2);
+// the kernel instance a handle runs (instantiated in the k_*.hip units, kernel_table.hpp): which one is select.hpp's decision (kernel_id_of and its
+// siblings); here a KernelId only becomes a table pointer -- nullptr where no such instance is compiled
+static const void *kernel_of(const KernelId &k) {
+  switch (k.kind) {
+    case K_STREAM: return k.pd == 8 ? (const void *)mpcqp_admm_kernel<8> : k.pd == 4 ? (const void *)mpcqp_admm_kernel<4> : nullptr;
+    case K_LDS: return k.reuse ? mpcqp_kernel_res_lds_r1(k.nw, k.minw) : mpcqp_kernel_res_lds_r0(k.nw, k.minw);
+    case K_GB: return k.reuse ? mpcqp_kernel_res_gb_r1(k.nw, k.minw, k.zyg != 0) : mpcqp_kernel_res_gb_r0(k.nw, k.minw, k.zyg != 0);
+    case K_OC_MONO: return k.reuse ? mpcqp_kernel_oc_mono_r1(k.nw, k.ng, k.nh, k.tiles != 0) : mpcqp_kernel_oc_mono_r0(k.nw, k.ng, k.nh, k.tiles != 0);
+    case K_OC_SETUP: return mpcqp_kernel_oc_setup(k.nw, k.hub != 0, k.reuse != 0);
+    case K_OC_RESCALE: return mpcqp_kernel_oc_rescale(k.nw, k.hub != 0);
+    case K_OC_ADMM: return mpcqp_kernel_oc_admm(k.nw, k.ng, k.nh);
+    case K_OC_ADMM_RF: return mpcqp_kernel_oc_admm_rf(k.nw, k.ng, k.nh);
+    case K_OC_ADMM_P4: return mpcqp_kernel_oc_admm_p4(k.rf);
+    case K_OC_ADMM_TL: return mpcqp_kernel_oc_admm_tl(k.nw, k.ng, k.nh);
+  }
+  return nullptr;
 }
+// waves per QP, register budget, factor location, and -- as its own instance so that the full-setup kernels carry no code for it -- the kept-workspace
+// entry (mpcqp_update_vectors).  (On-chip: the single-kernel form; eight waves without an arrow head have none, such handles run the two-kernel form.)
+static const void *res_kernel_of(const mpcqp_handle *h, bool reuse) { return kernel_of(res_kernel_id_of(h->sel, reuse)); }
+static const void *stream_kernel_of(const mpcqp_handle *h) { return kernel_of(stream_kernel_id_of(h->sel)); }
 // the two kernels of the on-chip mode (kernel_oc_split.hpp): CuCaQP::initSolver and CuCaQP::solve
-static const void *oc_setup_of(const mpcqp_handle *h, bool reuse) { return mpcqp_kernel_oc_setup(h->sel.setup.nw, h->sel.ocplan.has_hub != 0, reuse); }
+static const void *oc_setup_of(const mpcqp_handle *h, bool reuse) { return kernel_of(oc_setup_kernel_id_of(h->sel, reuse)); }
 // ... and the kernel that takes the set-up's place after mpcqp_update_matrices (kernel_oc_rescale.hpp): in the set-up's launch shape
-static const void *oc_rescale_of(const mpcqp_handle *h) { return mpcqp_kernel_oc_rescale(h->sel.setup.nw, h->sel.ocplan.has_hub != 0); }
+static const void *oc_rescale_of(const mpcqp_handle *h) { return kernel_of(oc_rescale_kernel_id_of(h->sel)); }
 // which handles mpcqp_update_matrices takes: the two-kernel on-chip form without the tile experiment
 static bool takes_matrix_updates(const mpcqp_handle *h) {
   const Selection &s = h->sel;
   return s.waves > 0 && s.oc && s.split && !s.tiles && !s.vtiles && oc_rescale_of(h) != nullptr;
 }
-static const void *oc_admm_of(const mpcqp_handle *h, bool rf = false) {
-  const Selection &s = h->sel;
-  const int nw = s.oc8 ? 8 : 4, ng = s.oc_ng(), nh = s.oc_nh();
-  if (!s.oc8 && s.ocplan.pairs.size() > 1) return mpcqp_kernel_oc_admm_p4(rf ? 1 : 0);      // (four waves, two twisted pairs: its own instances)
-  if (s.vtiles && !rf) return mpcqp_kernel_oc_admm_tl(nw, ng, nh);      // (the last launch of a solve, rf, runs the ELL sweeps: the set-up writes both forms)
-  return rf ? mpcqp_kernel_oc_admm_rf(nw, ng, nh) : mpcqp_kernel_oc_admm(nw, ng, nh);
-}
+static const void *oc_admm_of(const mpcqp_handle *h, bool rf = false) { return kernel_of(oc_admm_kernel_id_of(h->sel, rf)); }
 // One solve of the two-kernel on-chip mode on stream s: set-up, iteration; then, for instances whose adaptive-rho step asked for a new factor
 // (kernel_oc_split.hpp: they leave the iteration kernel marked OC_PENDING), `resume_rounds` pairs of {re-factorisation, iteration} in which every other
 // workgroup returns at once, and a last pair whose iteration kernel re-factorises in place, so that any number of rho updates is served.
@@ -219,8 +215,10 @@ static int launch_batch(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipSt
     void *args[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&h->doc};
     HIPCHK(hipLaunchKernel(res_kernel_of(h, reuse), dim3(count), dim3(sl.waves * WAVE), args, (size_t)sl.lds, s));
   }
-  else if (sl.stream_pd8) hipLaunchKernelGGL(mpcqp_admm_kernel<8>, dim3(count), dim3(WAVE), (size_t)sl.lds, s, h->dp, h->st, io);
-  else hipLaunchKernelGGL(mpcqp_admm_kernel<4>, dim3(count), dim3(WAVE), (size_t)sl.lds, s, h->dp, h->st, io);
+  else {
+    void *args[] = {(void *)&h->dp, (void *)&h->st, (void *)&io};
+    HIPCHK(hipLaunchKernel(stream_kernel_of(h), dim3(count), dim3(WAVE), args, (size_t)sl.lds, s));
+  }
   HIPCHK(hipGetLastError());
   if (after_kernel) HIPCHK(hipEventRecord(after_kernel, s));
   if (h->m > 0) {
@@ -387,7 +385,7 @@ static int prepare_kernels(mpcqp_handle *h) {
     // maximum per function so that a later handle with a smaller footprint never lowers the limit under an earlier one
     static std::mutex mu; static std::map<std::pair<const void *, int>, long> limit;   // (function, device)
     const void *fns[5] = {res_kernel_of(h, false), res_kernel_of(h, true), nullptr, nullptr, nullptr};
-    if (s.waves == 0) fns[0] = fns[1] = s.stream_pd8 ? (const void *)mpcqp_admm_kernel<8> : (const void *)mpcqp_admm_kernel<4>;
+    if (s.waves == 0) fns[0] = fns[1] = stream_kernel_of(h);
     if (s.split) { fns[0] = oc_setup_of(h, false); fns[1] = oc_setup_of(h, true); fns[2] = oc_admm_of(h, false); fns[3] = oc_admm_of(h, true); fns[4] = oc_rescale_of(h); }
     std::lock_guard<std::mutex> lock(mu);
     for (int k = 0; k < 5; k++) {

@@ -465,6 +465,56 @@ inline void oc_launch_shape(const Ctx &c, Selection &s) {
 
 }  // namespace sel
 
+// Which compiled kernel instance a Selection launches: the one mapping from the policy's flags to the template arguments of the k_*.hip units
+// (kernel_table.hpp).  Host-only; mpcqp.hip turns a KernelId into a table pointer and does nothing else with the flags, and the tests read the
+// same mapping through tests/support/plan_interp.cpp (tests/support/instance_cases.py: the census of the instances and who reaches them).
+enum KernelKind { K_STREAM = 0, K_LDS, K_GB, K_OC_MONO, K_OC_SETUP, K_OC_ADMM, K_OC_ADMM_RF, K_OC_ADMM_P4, K_OC_ADMM_TL, K_OC_RESCALE };
+struct KernelId {
+  int kind = K_STREAM;
+  int nw = 0, minw = 0;       // waves per QP; K_LDS / K_GB: the register budget as waves per SIMD (4 = 128, 3 = 168, 2 = 256 VGPRs; 1 = the whole file)
+  int zyg = 0;                // K_GB: z, y in the slab
+  int ng = 0, nh = 0;         // on-chip instances: positions and hub blocks per wave in registers (nh = 0: the instance without hub blocks)
+  int hub = 0;                // K_OC_SETUP / K_OC_RESCALE: the instance for patterns with an arrow head
+  int pd = 0;                 // K_STREAM: factor blocks in flight (4 or 8)
+  int reuse = 0;              // the kept-workspace twin (_r1 units; K_OC_SETUP: its reuse instance)
+  int rf = 0;                 // K_OC_ADMM_P4: the instance that re-factorises in place (K_OC_ADMM_RF is a kind of its own)
+  int tiles = 0;              // K_OC_MONO: the tile experiment's instance
+};
+// the streaming kernel of a handle without resident waves
+inline KernelId stream_kernel_id_of(const Selection &s) { KernelId k; k.kind = K_STREAM; k.nw = 1; k.pd = s.stream_pd8 ? 8 : 4; return k; }
+// the single kernel of a resident handle: waves per QP, register budget, factor location, and the kept-workspace twin.  (On-chip: the single-kernel form's
+// lookup, which a two-kernel handle never launches; a plan without an arrow head asks with nh = 0, for which the eight-wave table has no instance.)
+inline KernelId res_kernel_id_of(const Selection &s, bool reuse) {
+  KernelId k; k.reuse = reuse ? 1 : 0;
+  auto lds = [&](int nw, int minw) { k.kind = K_LDS; k.nw = nw; k.minw = minw; return k; };
+  auto gb = [&](int nw, int minw, bool zyg) { k.kind = K_GB; k.nw = nw; k.minw = minw; k.zyg = zyg ? 1 : 0; return k; };
+  if (s.oc) { k.kind = K_OC_MONO; k.nw = s.oc8 ? 8 : 4; k.minw = 2; k.ng = s.oc_ng(); k.nh = s.oc_nh(); k.hub = s.ocplan.has_hub ? 1 : 0; k.tiles = s.tiles ? 1 : 0; return k; }
+  if (s.gblocks && s.waves == 2) return gb(2, 3, false);
+  if (s.gblocks && s.zyg) return gb(4, s.occ3 ? 3 : 2, true);
+  if (s.gblocks && s.occ3) return gb(4, 3, false);
+  if (s.gblocks) return gb(4, s.occ4 ? 4 : 2, false);
+  if (s.waves == 1) return lds(1, s.res1x ? 4 : 2);
+  if (s.waves == 8) return lds(8, 2);
+  if (s.waves == 2) return lds(2, 3);
+  if (s.res3 == 4) return lds(4, 4);
+  if (s.res3 == 3) return lds(4, 3);
+  return lds(4, s.wide ? 1 : 2);
+}
+// the kernels of the two-kernel on-chip form: the set-up (in its own launch shape), the kernel that takes its place after mpcqp_update_matrices, the iteration
+inline KernelId oc_setup_kernel_id_of(const Selection &s, bool reuse) { KernelId k; k.kind = K_OC_SETUP; k.nw = s.setup.nw; k.hub = s.ocplan.has_hub ? 1 : 0; k.reuse = reuse ? 1 : 0; return k; }
+inline KernelId oc_rescale_kernel_id_of(const Selection &s) { KernelId k; k.kind = K_OC_RESCALE; k.nw = s.setup.nw; k.hub = s.ocplan.has_hub ? 1 : 0; return k; }
+inline KernelId oc_admm_kernel_id_of(const Selection &s, bool rf) {
+  KernelId k; k.nw = s.oc8 ? 8 : 4; k.ng = s.oc_ng(); k.nh = s.oc_nh(); k.hub = s.ocplan.has_hub ? 1 : 0;
+  if (!s.oc8 && s.ocplan.pairs.size() > 1) { k.kind = K_OC_ADMM_P4; k.rf = rf ? 1 : 0; return k; }      // (four waves, two twisted pairs: its own instances)
+  if (s.vtiles && !rf) { k.kind = K_OC_ADMM_TL; return k; }      // (the last launch of a solve, rf, runs the ELL sweeps: the set-up writes both forms)
+  k.kind = rf ? K_OC_ADMM_RF : K_OC_ADMM;
+  return k;
+}
+// the iteration (or only) kernel of a handle; rf: the last launch of a two-kernel solve, which re-factorises in place
+inline KernelId kernel_id_of(const Selection &s, bool reuse, bool rf) {
+  return s.waves == 0 ? stream_kernel_id_of(s) : s.split ? oc_admm_kernel_id_of(s, rf) : res_kernel_id_of(s, reuse);
+}
+
 // The MPCQP_VERBOSE line of a two-kernel handle, up to what only the device knows (mpcqp.hip adds the resident workgroups)
 inline std::string setup_shape_text(const Selection &s) {
   const SetupShape &u = s.setup;

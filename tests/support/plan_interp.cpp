@@ -867,9 +867,38 @@ extern "C" int plan_oc_extras(int n, int m, const int *Pp, const int *Pi, const 
 // compute units.  forced_family: null = MPCQP_VARIANT or the rule.  Returns 0 and out[0..15] = mpcqp_plan_info, out[16..27] = mpcqp_oc_info,
 // out[28..39] = the set-up launch {waves, LDS bytes, stage doubles, a_lds, p_lds, ix16, zpad, ixo_a, ixo_p, two-kernel form, 0, 0}, out[40..47] =
 // {zyg, occ3, occ4, res1x, res3, wide, oc8 instance, waves whose chunks of A are assigned}; or the error code (1 = MPCQP_ERR_ARG, 5 = MPCQP_ERR_LIMIT).
-static std::string g_select_shape;
+static thread_local std::string g_select_shape;
+static int describe_selection(const Selection &s, int n, int m, int batch, long *out);
 extern "C" int plan_select(int n, int m, int batch, const int *Pp, const int *Pi, const int *Ap, const int *Ai, int cus, const char *forced_family, long *out) {
-  const Selection s = select_kernel(n, m, batch, Pp, Pi, Ap, Ai, cus, forced_family, Knobs::from_env());
+  return describe_selection(select_kernel(n, m, batch, Pp, Pi, Ap, Ai, cus, forced_family, Knobs::from_env()), n, m, batch, out);
+}
+// plan_select, and the kernel instances the handle would launch (csrc/select.hpp kernel_id_of and its siblings, the mapping mpcqp.hip itself goes through):
+// kid[12 r .. 12 r + 11] = {kind, nw, minw, zyg, ng, nh, hub, pd, reuse, rf, tiles, 1} of role r, all zero where the handle has no such kernel.  Roles:
+// 0 / 1 the iteration (or only) kernel without / with the kept-workspace entry, 2 the last launch of a two-kernel solve (re-factorises in place);
+// 3 / 4 the set-up kernel without / with the kept-workspace entry, 5 the kernel of mpcqp_update_matrices (two-kernel form only);
+// 6 the single-kernel lookup of a resident handle whatever its form (what res_kernel_of asks the table for);  7: {stream_pd8, split, 0, ...}.
+// knob_mask: occupancy knobs switched on besides those of the environment (bit 0 MPCQP_GB_OCC2, 1 MPCQP_GB_OCC3, 2 MPCQP_NO_ZYG, 3 MPCQP_NO_RES1X, 4 MPCQP_NO_RES3,
+// 5 MPCQP_PD4), so that a sweep can run on several threads without touching the environment.
+extern "C" int plan_select_kernels(int n, int m, int batch, const int *Pp, const int *Pi, const int *Ap, const int *Ai, int cus, const char *forced_family, int knob_mask,
+                                   long *out, long *kid) {
+  Knobs kn = Knobs::from_env();
+  kn.gb_occ2 |= (knob_mask & 1) != 0; kn.gb_occ3 |= (knob_mask & 2) != 0; kn.no_zyg |= (knob_mask & 4) != 0;
+  kn.no_res1x |= (knob_mask & 8) != 0; kn.no_res3 |= (knob_mask & 16) != 0; kn.pd4 |= (knob_mask & 32) != 0;
+  const Selection s = select_kernel(n, m, batch, Pp, Pi, Ap, Ai, cus, forced_family, kn);
+  const int rc = describe_selection(s, n, m, batch, out);
+  std::fill(kid, kid + 8 * 12, 0L);
+  if (rc) return rc;
+  auto put = [&](int role, const KernelId &k) {
+    const long v[12] = {k.kind, k.nw, k.minw, k.zyg, k.ng, k.nh, k.hub, k.pd, k.reuse, k.rf, k.tiles, 1};
+    std::copy(v, v + 12, kid + 12 * role);
+  };
+  put(0, kernel_id_of(s, false, false)); put(1, kernel_id_of(s, true, false));
+  if (s.waves > 0 && s.split) { put(2, kernel_id_of(s, false, true)); put(3, oc_setup_kernel_id_of(s, false)); put(4, oc_setup_kernel_id_of(s, true)); put(5, oc_rescale_kernel_id_of(s)); }
+  if (s.waves > 0) put(6, res_kernel_id_of(s, false));
+  kid[12 * 7] = s.stream_pd8; kid[12 * 7 + 1] = s.split;
+  return 0;
+}
+static int describe_selection(const Selection &s, int n, int m, int batch, long *out) {
   g_select_shape.clear();
   if (s.err) return s.err;
   plan_info_of(s, n, m, batch, out); oc_info_of(s, out + 16);

@@ -127,13 +127,14 @@ HARD_WORKLOADS = {"q20": ("quadrotor", 20, 8), "cp30": ("cartpole", 30, 6), "q50
 DUAL_INFEASIBLE, PRIMAL_INFEASIBLE = 1, 2          # the instances hard_stage_batch alters
 
 
-def hard_stage_batch(wid, dual=True):
+def hard_stage_batch(wid, dual=True, dual_q=-1.0):
     """-> (model, LocalSystem, meta) of HARD_WORKLOADS[wid] with
       * instance 2 primal infeasible: the second frame's first state boxed into [50, 60], which the pinned first frame cannot reach in one step;
       * instance 1 dual infeasible (dual=True): the last frame's last input -- which no dynamics row reads -- without curvature (its row and column of P
-        zero), with q = -1 and its only row of A (its box) unbounded: an unbounded direction of descent.
-    P is materialised per instance where the workload shares it; meta["dual_rows"]: the rows of A that were unbounded."""
-    name, N, B = HARD_WORKLOADS[wid]
+        zero), with q = dual_q = -1 and its only row of A (its box) unbounded: an unbounded direction of descent.
+    P is materialised per instance where the workload shares it; meta["dual_rows"]: the rows of A that were unbounded.
+    wid: an id of HARD_WORKLOADS, or any (workload, N, batch) with batch >= 3 (tests/support/instance_cases.py)."""
+    name, N, B = HARD_WORKLOADS[wid] if isinstance(wid, str) else wid
     mdl, ls, meta = models.make_workload(name, B, N=N)
     P = np.array(np.broadcast_to(ls.P, (B, len(ls.Pi)))); q, l, u = ls.q.copy(), ls.l.copy(), ls.u.copy()
     row = mdl.np + mdl.f
@@ -143,7 +144,7 @@ def hard_stage_batch(wid, dual=True):
         j = ls.n - 1
         cols = np.repeat(np.arange(ls.n), np.diff(ls.Pp))
         P[DUAL_INFEASIBLE, (cols == j) | (np.asarray(ls.Pi) == j)] = 0.0
-        q[DUAL_INFEASIBLE, j] = -1.0
+        q[DUAL_INFEASIBLE, j] = dual_q
         rows_of_j = np.asarray(ls.Ai[ls.Ap[j]:ls.Ap[j + 1]], int)
         l[DUAL_INFEASIBLE, rows_of_j] = -np.inf; u[DUAL_INFEASIBLE, rows_of_j] = np.inf
     hard = models.LocalSystem(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai, P, q, ls.A, l, u, ls.np)
@@ -195,15 +196,19 @@ def kept_q(ls):
     return ls.q * (1.0 + 0.1 * np.random.default_rng(17).standard_normal(ls.q.shape))
 
 
-def oracle_kept_solves(ls, q2, nthreads=8, **settings):
-    """-> (full solve, vectors-only solve with q2) of the oracle's kept workspaces (osqp_update_data_vec semantics)"""
+def oracle_kept_solves(ls, q2, nthreads=8, l2=None, u2=None, **settings):
+    """-> (full solve, vectors-only solve with q2 -- and the bounds l2, u2 where given, else the first solve's) of the oracle's kept workspaces
+    (osqp_update_data_vec semantics)"""
     from oracle import oracle as orc
     state = orc.State(orc.Pattern(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai), ls.batch, orc.default_settings(**settings))
-    return state.solve(ls.P, ls.q, ls.A, ls.l, ls.u, nthreads=nthreads), state.solve_vectors(q2, ls.l, ls.u, nthreads=nthreads)
+    return (state.solve(ls.P, ls.q, ls.A, ls.l, ls.u, nthreads=nthreads),
+            state.solve_vectors(q2, ls.l if l2 is None else l2, ls.u if u2 is None else u2, nthreads=nthreads))
 
 
-def oracle_kept_stable_mask(ls, q2, draws=3, nthreads=8, **settings):
+def oracle_kept_stable_mask(ls, q2, draws=3, nthreads=8, l2=None, u2=None, **settings):
     """oracle_stable_mask for the pair of solves of a kept workspace: -> (mask of the full solve, mask of the vectors-only solve)"""
+    if l2 is not None or u2 is not None:
+        settings = dict(settings, l2=l2, u2=u2)
     ref = oracle_kept_solves(ls, q2, nthreads, **settings)
     rng = np.random.default_rng(99)
     ok = [np.ones(ls.batch, bool), np.ones(ls.batch, bool)]
@@ -250,6 +255,14 @@ def random_qp(n, m, seed, density=0.3, infeasible=None):
     hm = np.ones((n, n), bool); am = np.ones((m, n), bool)
     Pp, Pi = models._csc_from_dense_mask(hm); Ap, Ai = models._csc_from_dense_mask(am)
     return models.LocalSystem(n, m, Pp, Pi, Ap, Ai, P.T[hm.T][None].copy(), q[None].copy(), A.T[am.T][None].copy(), l[None].copy(), u[None].copy())
+
+
+def fuzz_pattern_draw(c):
+    """(n, m, B, density) of pattern c of the randomised sweep's slice in tests/test_gpu_fuzz.py (the generator of tools/fuzz_gpu.py); sparse_batch(n, m, B, c, density)
+    is its batch"""
+    rng = np.random.default_rng(1000 + c)
+    n = int(rng.integers(2, 140)); m = int(rng.integers(1, 200)); B = int(rng.integers(1, 9))
+    return n, m, B, float(rng.choice([0.05, 0.15, 0.4, 1.0]))
 
 
 def sparse_batch(n, m, B, seed, dens):

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.support.problems import random_stage_ocp, sparse_batch
+from tests.support.problems import fuzz_pattern_draw, random_stage_ocp, sparse_batch
 
 pytestmark = pytest.mark.gpu
 
@@ -50,9 +50,7 @@ def test_random_patterns_every_family(built, monkeypatch):
     stats = {f: dict(solves=0, soft=0) for f in FAMILIES}
     worst = 0.0
     for c in range(NPAT):
-        rng = np.random.default_rng(1000 + c)
-        n = int(rng.integers(2, 140)); m = int(rng.integers(1, 200)); B = int(rng.integers(1, 9))
-        dens = float(rng.choice([0.05, 0.15, 0.4, 1.0]))
+        n, m, B, dens = fuzz_pattern_draw(c)
         ls = sparse_batch(n, m, B, c, dens)
         ref = orc.Pattern(ls.n, ls.m, ls.Pp, ls.Pi, ls.Ap, ls.Ai).solve(ls.P, ls.q, ls.A, ls.l, ls.u, orc.default_settings())
         fin = np.isfinite(ref["x"])
