@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_rescale_kernel(const De
   if (!(rho >= Q_RHO_MIN && rho <= Q_RHO_MAX)) rho = fmin(fmax(st.rho, Q_RHO_MIN), Q_RHO_MAX);
   cx.rho = uni(rho);
   // always a new factor, whatever the previous problem's verdict was: the matrices are new
-  const bool ok = factorize_res<NW, (HUB ? 2 : 1), false>(cx, &oc, L.octab, lds);
+  const bool ok = factorize_res<NW, (HUB ? 2 : 1), false, true>(cx, &oc, L.octab, lds);
   if (tid == 0) {
     io.status[b] = ok ? MPCQP_UNSOLVED : MPCQP_NON_CVX; io.iters[b] = 0;
     io.info[4L * b + 3] = cx.rho;

@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     bsync<NW>();
     cx.rho = uni(io.info[4L * b + 3]);
     cx.c = 1.0; cx.cinv = 1.0;
-    const bool okr = factorize_res<NW, (HUB ? 2 : 1), false>(cx, &oc, L.octab, lds);
+    const bool okr = factorize_res<NW, (HUB ? 2 : 1), false, true>(cx, &oc, L.octab, lds);
     if (tid == 0) io.status[b] = okr ? OC_PENDING : OC_PENDING_NONCVX;
     return;
   }
@@ -346,7 +346,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
   cx.rho = uni(reuse ? io.info[4L * b + 3] : fmin(fmax(io.rho0 && io.rho0[b] > 0.0 ? io.rho0[b] : st.rho, Q_RHO_MIN), Q_RHO_MAX));
   TS(2);
   bool ok = !(reuse && prev_status == MPCQP_NON_CVX);
-  if (ok && refactor) ok = factorize_res<NW, (HUB ? 2 : 1), false>(cx, &oc, L.octab, lds);
+  if (ok && refactor) ok = factorize_res<NW, (HUB ? 2 : 1), false, true>(cx, &oc, L.octab, lds);
   if (tid == 0) {
     io.status[b] = ok ? MPCQP_UNSOLVED : MPCQP_NON_CVX; io.iters[b] = 0;
     io.info[4L * b + 3] = cx.rho;

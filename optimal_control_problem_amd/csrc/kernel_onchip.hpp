@@ -31,19 +31,22 @@ struct DevTile {
 struct DevOc {
   int nbc, has_hub, junc, npw, nhr, nlds, ntab;
   int o_chainE, o_chainF, o_pos, o_fill, ghub_slot, ghub_src;
+  int su_path;          // set-up kernel, the factorisation's operands on chip: bit 0 the T tiles in LDS by parts, bit 1 the singleton rows from their list (plan.hpp oc_setup_tables;
+                        // MPCQP_NO_T_LDS=1 / MPCQP_NO_SING_LIST=1 clear them).  In the padding in front of the pointer: the struct's size and every other offset stay
   const int *a_assign;  // eight-wave instances: [8][32] row chunks of A per wave for the iteration's A sweep, balanced by load batches (-1: none); NULL = chunk wid + 8 k
   int npair, o_pair;   // twisted pairs of chains (plan.hpp OcPlan::pairs) and their records in tab: {LE, LF, oE, oF, junc, sLE, sLF, soE, soF, -, -, -}
   int nfill, o_s, o_dbl, ndbl, o_pp;   // LDS slots filled from the slab; the chains the solve walks; its double stages and their product blocks (plan.hpp oc_add_doubles)
   int at_poll, at_free;   // chunks of A' whose rows the iteration computes during the chain phase instead of before it (-1: none); see oc_solve
   int a_lds, p_lds; // the ELL values of A (and of P behind them) fit the LDS block slots: they stay there while the problem is scaled
   const int *tab;
-  const int *asm_rec;   // [8 nblk] assembly recipe per block {terms, diagonal block row or -1, a0, b0, a1, b1, a2, b2} (T tile ids of the first three terms)
+  const int *asm_rec;   // [8 nblk] assembly recipe per block {terms, diagonal block row or -1, a0, b0, a1, b1, a2, b2} (T tile ids of the first three terms); behind them the set-up kernel's tables (plan.hpp oc_setup_tables)
   DevTile tl;           // (the instances without tiles keep their argument layout)
   int resume;           // two-kernel form: this launch continues instances that left the iteration kernel for a re-factorisation (kernel_oc_split.hpp)
   int ixo_a, ixo_p;     // ... where those tables start, in 16-bit units from the LDS base (the z region; for shapes without staged values also the factorisation's scratch, idle until then)
   int ix16, zpad;       // set-up kernel (its own vector layout, kernel_oc_split.hpp oc_lds): 16-bit index tables of A (& 1) and P (& 2) in its z region of zpad doubles
   int no_ruiz_regs = 0; // set-up kernel, switch (MPCQP_NO_RUIZ_REGS=1): every wave reloads the Ruiz passes' fixed operands instead of keeping them in registers (in the struct's tail padding: same size)
 };
+static_assert(sizeof(DevOc) == 312 && offsetof(DevOc, a_assign) == 56, "DevOc is a kernel argument of every on-chip instance: its layout is part of their text");
 
 // LDS image of a 16x16 block: rows alternate between the two 32-bank halves in a pattern that also separates rows 4 apart, the four
 // 32-byte pieces of a row are rotated by the row pair, and the two 16-byte halves of a piece are swapped in the lower eight rows.  The

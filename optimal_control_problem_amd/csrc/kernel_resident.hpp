@@ -438,6 +438,16 @@ __device__ __forceinline__ d4 mfma_abt_l(const double *A, const double *B, d4 ac
   }
   return acc;
 }
+// ... on two tiles in the swizzled LDS image of the set-up kernel's assembly (plan.hpp t_lds_off)
+__device__ __forceinline__ d4 mfma_abt_tl(const double *A, const double *B, d4 acc, int lane) {
+  const int rr = lane & 15, kk = lane >> 4;
+#pragma unroll
+  for (int k0 = 0; k0 < BS; k0 += 4) {
+    const int o = t_lds_off(rr, k0 + kk);
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[o], B[o], acc, 0, 0, 0);
+  }
+  return acc;
+}
 
 // ---- solve-schedule executor -------------------------------------------------------------------------------
 // A lone wave issues roughly one instruction per 4-8 cycles, so the executor is written for instruction count:
@@ -609,7 +619,10 @@ __device__ __forceinline__ void tscatter_batch(const double *&vp, const int *&tp
 }
 // OCM: 0 the level loop below; 1 / 2 the on-chip topology without / with an arrow head: kernel_onchip.hpp's oc_ldl on the assembled blocks
 // TAIL: leave w = rho z - y behind (the set-up kernel of kernel_oc_split.hpp has no iterate yet: false)
-template <int NW, int OCM = 0, bool TAIL = true>
+// SU: the set-up and rescale kernels of the two-kernel form, whose LDS holds no factor: where the handle's tables say so (DevOc.su_path), the diagonal
+// term reads the singleton rows from their list, and the T tiles are scattered into LDS and multiplied from there, a part of the blocks at a time
+// (plan.hpp build_t_lds_plan, build_sing_list).  Same operands, same MFMAs, same order: the assembled blocks are bit for bit those of the slab path.
+template <int NW, int OCM = 0, bool TAIL = true, bool SU = false>
 __device__ __forceinline__ bool factorize_res(RCtx &cx, const DevOc *oc = nullptr, const int *octab = nullptr, double *scr = nullptr) {
   const DevPlan &pl = *cx.pl; const DevRes &rs = *cx.rs; double *ws = cx.ws;
   const int wid = cx.wid, lane = cx.lane, tid = wid * WAVE + lane; constexpr int NT = NW * WAVE;
@@ -621,8 +634,56 @@ __device__ __forceinline__ bool factorize_res(RCtx &cx, const DevOc *oc = nullpt
 #endif
   for (int i = tid; i < pl.mpad; i += NT) cx.W[i] = i < pl.m ? rho_of(lb[i], ub[i], cx.rho) : 0.0;
   // (the T tiles' structural zeros were written once, at creation: only the non-zeros are refreshed below)
+  [[maybe_unused]] const int *sut = nullptr, *suh = nullptr;      // the set-up kernel's tables and their header (plan.hpp oc_setup_tables)
+  [[maybe_unused]] bool t_lds = false, d_list = false;
+  // the image of part p: zeroed (its structural zeros and the zero tile in slot 0; a barrier later:) the part's entries of A times sqrt(rho_i), the product of tscatter_batch
+  [[maybe_unused]] auto t_zero = [&](const int p) {
+    const int nd = sut[suh[5] + 8 * p + 2];
+    int t0 = tid; asm volatile("" : "+v"(t0));      // (per call: addresses formed from tid once would stay in registers across the assembly loop, which has none to spare)
+    for (int k = t0; 2 * k < nd; k += NT) reinterpret_cast<d2 *>(scr)[k] = d2{0.0, 0.0};
+  };
+  [[maybe_unused]] auto t_scatter = [&](const int p) {
+    const int2 *sc = reinterpret_cast<const int2 *>(sut + sut[suh[5] + 8 * p + 3]);
+    const int cnt = sut[suh[5] + 8 * p + 4];
+    int k = tid; asm volatile("" : "+v"(k));
+    for (; k + 3 * NT < cnt; k += 4 * NT) {
+      int2 e[4]; double v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) e[u] = sc[k + u * NT];
+#pragma unroll
+      for (int u = 0; u < 4; u++) v[u] = valA[e[u].x];
+#pragma unroll
+      for (int u = 0; u < 4; u++) scr[(unsigned)e[u].y & 0xffffu] = v[u] * sqrt(cx.W[(unsigned)e[u].y >> 16]);
+    }
+    for (; k < cnt; k += NT) { const int2 e = sc[k]; scr[(unsigned)e.y & 0xffffu] = valA[e.x] * sqrt(cx.W[(unsigned)e.y >> 16]); }
+  };
+  if constexpr (SU) {
+    sut = oc->asm_rec; suh = sut + 8 * pl.nblk;
+    t_lds = OCM > 0 && (oc->su_path & 1); d_list = (oc->su_path & 2) != 0;
+    if (t_lds) t_zero(0);
+  }
   bsync<NW>();
-  {
+  if (SU && d_list) {
+    if constexpr (SU) {
+      // d_t from the list of column t's flagged entries of A' ([K][npad], K even, -1 = none), two at a time, in the order of the full pass below
+      const double sigma = cx.st->sigma;
+      const int K = suh[6], np = pl.npad;
+      const int *se = sut + suh[7], *sr = se + K * np;
+      for (int c = wid; c < pl.At.nchunks; c += NW) {
+        const int t = c * WAVE + lane;
+        if (t < np) {
+          double acc = 0.0;
+          for (int k = 0; k < K; k += 2) {
+            const int e0 = se[k * np + t], e1 = se[(k + 1) * np + t], r0 = sr[k * np + t], r1 = sr[(k + 1) * np + t];
+            const double v0 = valAt[max(e0, 0)], v1 = valAt[max(e1, 0)], w0 = cx.W[max(r0, 0)], w1 = cx.W[max(r1, 0)];
+            if (e0 >= 0) acc = __builtin_fma(w0 * v0, v0, acc);
+            if (e1 >= 0) acc = __builtin_fma(w1 * v1, v1, acc);
+          }
+          cx.R[t] = pl.perm[t] >= 0 ? sigma + acc : 1.0;
+        }
+      }
+    }
+  } else {
     // d_t = sigma + sum_i rho_i a_it^2 over the singleton rows of column t (the rest of A' rho A goes through the T tiles)
     const double sigma = cx.st->sigma;
     const DevEll &E = pl.At;
@@ -640,7 +701,9 @@ __device__ __forceinline__ bool factorize_res(RCtx &cx, const DevOc *oc = nullpt
       if (t < pl.npad) cx.R[t] = pl.perm[t] >= 0 ? sigma + acc : 1.0;
     }
   }
-  {
+  if (SU && t_lds) {
+    if constexpr (SU) t_scatter(0);
+  } else {
     const DevEll &E = pl.A;
     for (int c = wid; c < E.nchunks; c += NW) {
       const int i = c * WAVE + lane;
@@ -658,6 +721,11 @@ __device__ __forceinline__ bool factorize_res(RCtx &cx, const DevOc *oc = nullpt
   int *rec = nullptr;
   if constexpr (OCM > 0) {      // the assembly recipe of every block, one 32-byte record each, next to the factorisation's scratch blocks
     rec = reinterpret_cast<int *>(scr + OC_LDL_SCR * BLK);
+    if constexpr (SU) {
+      const int *src = oc->asm_rec;
+      if (t_lds) { rec = reinterpret_cast<int *>(scr + suh[1]); src = sut + suh[2]; }      // (tile ids as LDS slots; behind the images, where x was)
+      for (int k = tid; k < 8 * pl.nblk; k += NT) rec[k] = src[k];
+    } else
     for (int k = tid; k < 8 * pl.nblk; k += NT) rec[k] = oc->asm_rec[k];
   }
   bsync<NW>();
@@ -671,6 +739,66 @@ __device__ __forceinline__ bool factorize_res(RCtx &cx, const DevOc *oc = nullpt
     // loop used to wait for, block after block)
     // Every fetch is unconditional -- unused terms read the zero tile behind the T tiles, a block past the wave's last one is fetched again --
     // so the loop body is straight-line code and the compiler's wait counts stay exact (a conditional load makes it wait for everything)
+    if (SU && t_lds) {
+      if constexpr (SU) {
+        // The tiles in LDS, a part of the blocks at a time (part 0 was scattered above).  The P values stay two blocks ahead as below; a block's
+        // records and row pieces are read right before its MFMAs, into one register set -- an LDS round trip is a tenth of the slab's, and a second set's 48
+        // registers are what the scatter between two parts needs: with both the kernel passes 168 VGPRs and loses its third workgroup per CU.
+        // The row piece is two 16-byte halves of the swizzled row (plan.hpp t_lds_off).
+        auto rfl = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+        const int ol = t_lds_off(lane & 15, 4 * (lane >> 4));
+        auto lds_tile = [&](const int slot) {
+          const double *q = scr + slot * BLK;
+          const d2 lo = *reinterpret_cast<const d2 *>(q + ol), hi = *reinterpret_cast<const d2 *>(q + (ol ^ 2));
+          return d4{lo[0], lo[1], hi[0], hi[1]};
+        };
+        int pin[4];
+        auto fetch_pidx = [&](const int bb) {
+#pragma unroll
+          for (int g = 0; g < 4; g++) pin[g] = pl.asm_pidx[(long)bb * BLK + g * WAVE + lane];
+        };
+        auto gather = [&](double (&pv)[4], bool (&mk)[4]) {       // P values of the block whose indices sit in pin; then pin moves on
+#pragma unroll
+          for (int g = 0; g < 4; g++) { pv[g] = valP[max(pin[g], 0)]; mk[g] = pin[g] >= 0; }
+        };
+        auto finish = [&](const int bb, const double (&pv)[4], const bool (&mk)[4]) {
+          const int4 r0 = *reinterpret_cast<const int4 *>(rec + 8 * bb), r1 = *reinterpret_cast<const int4 *>(rec + 8 * bb + 4);
+          const int n = rfl(r0.x), J = rfl(r0.y);
+          d4 acc = {0, 0, 0, 0};
+          acc = oc_mm(lds_tile(rfl(r0.z)), lds_tile(rfl(r0.w)), acc);
+          if (n > 1) acc = oc_mm(lds_tile(rfl(r1.x)), lds_tile(rfl(r1.y)), acc);
+          if (n > 2) acc = oc_mm(lds_tile(rfl(r1.z)), lds_tile(rfl(r1.w)), acc);
+          if (n > 3) {
+            const int *ta = sut + suh[3], *tb = sut + suh[4];
+            for (int g = pl.asm_ptr[bb] + 3; g < pl.asm_ptr[bb + 1]; g++) acc = mfma_abt_tl(scr + ta[g] * BLK, scr + tb[g] * BLK, acc, lane);
+          }
+#pragma unroll
+          for (int g = 0; g < 4; g++) {
+            if (mk[g]) acc[g] += pv[g];
+            const int row = row0 + 4 * g;
+            if (J >= 0 && row == col) acc[g] += cx.R[J * BS + row];
+            cx.BL[(long)bb * BLK + row * BS + col] = acc[g];
+          }
+        };
+        const int parts = suh[0];
+        for (int p = 0; p < parts; p++) {
+          if (p > 0) { bsync<NW>(); t_zero(p); bsync<NW>(); t_scatter(p); bsync<NW>(); }
+          const int b1 = sut[suh[5] + 8 * p + 1], bw = sut[suh[5] + 8 * p] + wid;      // the part's end, the wave's first block
+          if (bw < b1) {
+            const int bl = bw + (b1 - 1 - bw) / NW * NW;                                // the wave's last block
+            double pv0[4], pv1[4]; bool m0[4], m1[4];
+            fetch_pidx(bw); gather(pv0, m0); fetch_pidx(min(bw + NW, bl));
+            for (int b = bw; b < b1; b += 2 * NW) {
+              const int c1 = min(b + NW, bl), c2 = min(b + 2 * NW, bl), c3 = min(b + 3 * NW, bl);     // (past the end: the last block once more, same result)
+              gather(pv1, m1); fetch_pidx(c2);
+              finish(b, pv0, m0);
+              gather(pv0, m0); fetch_pidx(c3);
+              finish(c1, pv1, m1);
+            }
+          }
+        }
+      }
+    } else {
     const int nblk = pl.nblk;
     auto rfl = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
     auto fetch_ops = [&](const int bb, d4 (&A)[3], d4 (&B)[3], int &n, int &J) {
@@ -719,6 +847,7 @@ __device__ __forceinline__ bool factorize_res(RCtx &cx, const DevOc *oc = nullpt
         fetch_ops(b2, A0, B0, n0, J0); gather(pv0, m0); fetch_pidx(b3, pin);
         finish(b1, A1, B1, n1, J1, pv1, m1);
       }
+    }
     }
   } else {
   for (int b = wid; b < pl.nblk; b += NW) {

@@ -1079,6 +1079,108 @@ inline std::vector<int> oc_asm_records(const Plan &pl) {
   }
   return r;
 }
+// ---- set-up kernel of the two-kernel on-chip form: the factorisation's operands on chip (kernel_resident.hpp factorize_res<..., SU = true>)
+// The T tiles of the assembly live in LDS instead of the slab, a PART of the blocks at a time: the blocks are split into consecutive parts such that
+// the tiles a part's blocks multiply (all terms, so the `n > 3` tail too), plus a zero tile in slot 0, fit the LDS that is idle during the assembly --
+// the block-slot region and x behind it, with the assembly records moved to their end (rho in w and d in r are live; oc_ldl's scratch is first used
+// behind the assembly's last barrier).  A tile used by blocks of two parts is scattered in both.
+// LDS image of a tile: element (r, c) -- r the variable, c the row of the 16-row group, as in the slab -- sits in row r with its 16-byte pairs XORed so
+// that the row-piece read of the assembly (lane l: row l & 15, columns 4 (l >> 4) ..., two ds_read_b128) finds every lane group of that instruction
+// ({0-3, 12-15, 20-27}, ...: each holds all sixteen rows once, at two neighbouring pieces) on sixteen different 16-byte slots of the 256-byte bank row.
+// Unswizzled, the 128-byte row stride puts a group on four slots: a four-way conflict on every read.
+constexpr int t_lds_off(int r, int c) { return r * BS + ((((c >> 1) ^ (r >> 1) ^ ((((r >> 1) + 2) >> 1) & 2)) << 1) | (c & 1)); }
+constexpr int T_LDS_MAX_PARTS = 8;      // more parts than this: every part re-scatters its shared tiles and costs three barriers -- the slab path
+struct TLdsPlan {
+  int parts = 0;                 // 0: does not apply, the T tiles go through the slab
+  long cap = 0;                  // doubles of LDS an image may take: the whole tiles below rec_off
+  int rec_off = 0;               // doubles from the LDS base: the assembly records (8 ints per block) in this mode
+  std::vector<int> blk0;         // [parts + 1] first block of each part
+  std::vector<int> image;        // [parts] doubles of the part's image (zero tile included)
+  std::vector<int> sc_ptr;       // [parts + 1] pairs of sc before each part's
+  std::vector<int> sc;           // pairs {ELL entry of A, row of A << 16 | double offset in the image}
+  std::vector<int> rec;          // [8 nblk] oc_asm_records with the tile ids as LDS slots of the block's part
+  std::vector<int> ta, tb;       // [terms] asm_a / asm_b as LDS slots (the tail of a block with more than three terms)
+  std::vector<std::vector<int>> tiles;   // [parts] tile id of every slot >= 1 (slot 0: the zero tile)
+};
+inline TLdsPlan build_t_lds_plan(const Plan &pl, long stage, int max_parts = T_LDS_MAX_PARTS) {
+  TLdsPlan tp;
+  const long rec_off = stage + pl.npad - 4L * pl.nblk;
+  if (pl.nT <= 0 || rec_off < 2L * BLK || (rec_off & 1) || pl.mpad > 65536 || rec_off > 65536) return tp;
+  const int cap_tiles = (int)(rec_off / BLK);
+  std::vector<int> blk0{0}, slot_of(pl.nT, -1);
+  std::vector<std::vector<int>> tiles(1);
+  std::vector<int> rec = oc_asm_records(pl), ta(pl.asm_a.size()), tb(pl.asm_b.size());
+  for (int b = 0; b < pl.nblk; b++) {
+    const int g0 = pl.asm_ptr[b], g1 = pl.asm_ptr[b + 1];
+    auto missing = [&]() { std::set<int> s; for (int g = g0; g < g1; g++) for (int t : {pl.asm_a[g], pl.asm_b[g]}) if (slot_of[t] < 0) s.insert(t); return s; };
+    std::set<int> add = missing();
+    if (1 + (int)tiles.back().size() + (int)add.size() > cap_tiles) {      // the next part starts at this block
+      if (blk0.back() == b) return tp;                                       // (one block's tiles alone do not fit)
+      for (int t : tiles.back()) slot_of[t] = -1;
+      blk0.push_back(b); tiles.emplace_back();
+      add = missing();
+      if (1 + (int)add.size() > cap_tiles) return tp;
+    }
+    for (int t : add) { tiles.back().push_back(t); slot_of[t] = (int)tiles.back().size(); }
+    for (int g = g0; g < g1; g++) { ta[g] = slot_of[pl.asm_a[g]]; tb[g] = slot_of[pl.asm_b[g]]; }
+    for (int k = 2; k < 8; k++) rec[8 * b + k] = 0;                          // (unused terms: the zero tile, slot 0)
+    for (int g = g0; g < std::min(g1, g0 + 3); g++) { rec[8 * b + 2 + 2 * (g - g0)] = ta[g]; rec[8 * b + 3 + 2 * (g - g0)] = tb[g]; }
+  }
+  blk0.push_back(pl.nblk);
+  const int parts = (int)tiles.size();
+  if (parts > max_parts) return tp;
+  tp.sc_ptr.assign(1, 0);
+  for (int p = 0; p < parts; p++) {
+    std::fill(slot_of.begin(), slot_of.end(), -1);
+    for (size_t k = 0; k < tiles[p].size(); k++) slot_of[tiles[p][k]] = (int)k + 1;
+    for (int c = 0; c < pl.A.nchunks; c++) for (int s = pl.A.chunk_off[c]; s < pl.A.chunk_off[c + 1]; s++) for (int lane = 0; lane < WAVE; lane++) {
+      const long e = (long)s * WAVE + lane;
+      const int tq = pl.tpos[e];
+      if (tq < 0 || slot_of[tq / BLK] < 0) continue;
+      const int off = slot_of[tq / BLK] * BLK + t_lds_off((tq % BLK) / BS, tq % BS);
+      tp.sc.push_back((int)e); tp.sc.push_back((int)(((unsigned)(c * WAVE + lane) << 16) | (unsigned)off));
+    }
+    tp.sc_ptr.push_back((int)tp.sc.size() / 2);
+    tp.image.push_back((1 + (int)tiles[p].size()) * BLK);
+  }
+  tp.parts = parts; tp.cap = (long)cap_tiles * BLK; tp.rec_off = (int)rec_off;
+  tp.blk0 = blk0; tp.rec = rec; tp.ta = ta; tp.tb = tb; tp.tiles = tiles;
+  return tp;
+}
+// The diagonal term d_t = sigma + sum rho_i a_it^2 runs over the singleton rows of column t: the flagged entries of A' in ELL layout, a handful among
+// all of A' and fixed by the pattern.  Per column position, in ascending slot order (the order of the full pass): [K][npad] ELL-A' entries and their
+// rows, -1 where a column has fewer; K = the largest count, rounded up to even (the kernel fetches two at a time).
+struct SingList { int K = 0; std::vector<int> ent, row; };
+inline SingList build_sing_list(const Plan &pl) {
+  SingList sl;
+  std::vector<std::vector<int>> of(pl.npad);
+  for (int t = 0; t < pl.npad && t < pl.At.nchunks * WAVE; t++)
+    for (int s = pl.At.chunk_off[t / WAVE]; s < pl.At.chunk_off[t / WAVE + 1]; s++) { const long e = (long)s * WAVE + t % WAVE; if (pl.At.flag[e]) of[t].push_back((int)e); }
+  for (const auto &v : of) sl.K = std::max(sl.K, (int)v.size());
+  sl.K = (sl.K + 1) / 2 * 2;
+  sl.ent.assign((size_t)sl.K * pl.npad, -1); sl.row.assign((size_t)sl.K * pl.npad, -1);
+  for (int t = 0; t < pl.npad; t++) for (size_t k = 0; k < of[t].size(); k++) { sl.ent[k * pl.npad + t] = of[t][k]; sl.row[k * pl.npad + t] = pl.At.idx[of[t][k]]; }
+  return sl;
+}
+// What the set-up kernel reads behind the 8 nblk ints of oc_asm_records, in the same device array (DevOc has no room for another pointer): 16 ints
+// {parts, rec_off, o_rec, o_ta, o_tb, o_part, K, o_sing, ...} -- offsets in ints from the array's start, even --, then the tables: per part 8 ints
+// {first block, end block, image doubles, o_sc, pairs, ...}.
+inline std::vector<int> oc_setup_tables(const Plan &pl, const TLdsPlan &tp, const SingList &sl) {
+  std::vector<int> r = oc_asm_records(pl);
+  const size_t h = r.size();
+  r.resize(h + 16, 0);
+  auto put = [&](const std::vector<int> &v) { if (r.size() & 1) r.push_back(0); const int o = (int)r.size(); r.insert(r.end(), v.begin(), v.end()); return o; };
+  r[h] = tp.parts; r[h + 1] = tp.rec_off; r[h + 6] = sl.K;
+  if (sl.K > 0) { const int o = put(sl.ent); put(sl.row); r[h + 7] = o; }      // ([K][npad] with K even: the rows start at an even offset too)
+  if (tp.parts > 0) {
+    const int o_rec = put(tp.rec), o_ta = put(tp.ta), o_tb = put(tp.tb), o_sc = put(tp.sc);
+    std::vector<int> pr((size_t)8 * tp.parts, 0);
+    for (int p = 0; p < tp.parts; p++) { int *q = &pr[8 * p]; q[0] = tp.blk0[p]; q[1] = tp.blk0[p + 1]; q[2] = tp.image[p]; q[3] = o_sc + 2 * tp.sc_ptr[p]; q[4] = tp.sc_ptr[p + 1] - tp.sc_ptr[p]; }
+    const int o_part = put(pr);
+    r[h + 2] = o_rec; r[h + 3] = o_ta; r[h + 4] = o_tb; r[h + 5] = o_part;
+  }
+  return r;
+}
 inline long oc_stage_doubles(const OcPlan &oc, const ResPlan &rp, const Plan &pl) {
   // block slots / temp tiles, or the factorisation's scratch: 8 hand-over blocks + the assembly records (4 doubles per block)
   return std::max((long)std::max(oc.nlds, rp.ntemp) * BLK, 8L * BLK + ((4L * pl.nblk + 15) / 16) * 16);   // (8: kernel_onchip.hpp OC_LDL_SCR)

@@ -65,6 +65,8 @@ struct Knobs {
   int resume_rounds = 1;      // MPCQP_RESUME_ROUNDS=<0..8>: {re-factorisation, iteration} pairs queued behind a solve before the last pair
   bool no_ix16 = false;       // MPCQP_NO_IX16: set-up kernel without 16-bit index tables in LDS
   bool no_ruiz_regs = false;  // MPCQP_NO_RUIZ_REGS=1: set-up kernel's Ruiz passes reload their fixed operands (indices, P's values) every pass instead of keeping them in registers
+  bool no_t_lds = false;      // MPCQP_NO_T_LDS=1: set-up kernel's assembly takes its T tiles through the slab instead of LDS, part by part (plan.hpp build_t_lds_plan)
+  bool no_sing_list = false;  // MPCQP_NO_SING_LIST=1: set-up kernel's diagonal term walks all of A' for its flagged entries instead of reading their list (plan.hpp build_sing_list)
   long setup_cap = LONG_MIN;  // MPCQP_SETUP_CAP=<bytes>: LDS the set-up kernel's shape is fitted to, instead of a half or a third of a CU (LONG_MIN: not set)
   bool no_abalance = false;   // MPCQP_NO_ABALANCE: eight-wave iteration kernel takes A's row chunks round-robin instead of balanced by load batches
   bool no_touch = false;      // MPCQP_NO_TOUCH: no L2 touch by the idle waves during the backward chains (on-chip kernels)
@@ -104,6 +106,8 @@ struct Knobs {
     if (const char *e = getenv("MPCQP_RESUME_ROUNDS")) k.resume_rounds = std::max(0, std::min(atoi(e), 8));
     k.no_ix16 = set("MPCQP_NO_IX16");
     k.no_ruiz_regs = one("MPCQP_NO_RUIZ_REGS") == 2;
+    k.no_t_lds = one("MPCQP_NO_T_LDS") == 2;
+    k.no_sing_list = one("MPCQP_NO_SING_LIST") == 2;
     if (const char *e = getenv("MPCQP_SETUP_CAP")) k.setup_cap = atol(e);
     k.no_abalance = set("MPCQP_NO_ABALANCE");
     k.no_touch = set("MPCQP_NO_TOUCH");
@@ -122,6 +126,7 @@ struct SetupShape {
   int nw = 0; long lds = 0, stage = 0;
   int a_lds = 0, p_lds = 0, ix16 = 0, zpad = 0, ixo_a = 0, ixo_p = 0;
   long vecs = 0, tabw = 0;      // (doubles of its vectors and tables: for the MPCQP_VERBOSE line)
+  int t_parts = 0, sing_k = 0;  // the factorisation's operands on chip: parts of the T tiles in LDS (0: through the slab), entries per column of the singleton list (0: the full pass)
 };
 
 // Everything the policy decides for one handle.
@@ -143,6 +148,7 @@ struct Selection {
   bool vtiles = false;          // ... in the two-kernel form, on the vector ALUs (kernel_oc_split.hpp; MPCQP_VTILES=1); mpcqp.hip clears it where the table has no such instance
   int resume_rounds = 1;        // two-kernel form: {re-factorisation, iteration} pairs queued behind a solve before the last pair (MPCQP_RESUME_ROUNDS)
   Plan plan; ResPlan rplan; OcPlan ocplan; TilePlan tplan; WsLayout wl;
+  TLdsPlan tlds; SingList sing; // two-kernel form: what the set-up kernel's factorisation reads on chip (plan.hpp; empty where a knob or the fit says no)
   long lds = 0;                 // dynamic LDS of the iteration (or only) kernel
   long stage = 0;               // on-chip mode: staging doubles of the iteration kernel (plan.hpp oc_stage_doubles) ...
   int a_lds = 0, p_lds = 0;     // ... and whether A's / A's and P's values fit them
@@ -446,6 +452,10 @@ inline void oc_launch_shape(const Ctx &c, Selection &s) {
   else { const Shape s3 = shape(cu / 3); if (s3.fits && (s3.a || !(sh.a && sh.p))) sh = s3; }
   su.a_lds = sh.a; su.p_lds = sh.p; su.ix16 = sh.ix16; su.zpad = sh.zpad; su.ixo_a = sh.ixo_a; su.ixo_p = sh.ixo_p;
   su.stage = sh.stage; su.nw = 4; su.lds = sh.bytes; su.vecs = vec + sh.zpad; su.tabw = tabw;
+  // the factorisation's operands on chip: fitted to the LDS this shape already asks for, never a reason to ask for more
+  if (!c.k.no_t_lds) s.tlds = build_t_lds_plan(pq, su.stage);
+  if (!c.k.no_sing_list) s.sing = build_sing_list(pq);
+  su.t_parts = s.tlds.parts; su.sing_k = s.sing.K;
   if (s.oc8 && !c.k.no_abalance) {
     // row chunks of A to waves by longest-processing-time over their load batches (a batch = one round trip to memory; plan.hpp ell_batches8)
     std::vector<int> assign(8 * 32, -1), load(8, 0), cnt(8, 0), order_(pq.A.nchunks);
