@@ -648,6 +648,40 @@ typedef struct mpcqp_nlp_lagrangian_args {
 int mpcqp_nlp_has_exact_hessian(const mpcqp_nlp *s);
 int mpcqp_nlp_lagrangian(mpcqp_nlp *s, int batch, const mpcqp_nlp_lagrangian_args *a, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * First-order optimality residuals of the NLP, per instance, one kernel for the batch (opt-in).  The reference's loop has no
+ * convergence test (src/sqp_solver/SQPOptimizationSolver.cpp:127-216: a fixed number of iterations; the ||dx|| < 1e-6 stop exists only when
+ * verbose, :183-197); these entries depart from those lines.  They read what an SQP iteration already holds on the device: the local system
+ * (q, A, l, u) mpcqp_stage_eval / mpcqp_nlp_eval just wrote at w = [p; x] -- q = grad f(w), A = d[p; x; g]/dw in the CSC value order of the
+ * handle's pattern, l = [p; lbx; lbg] - c(w), u = [p; ubx; ubg] - c(w) -- and multipliers y [m], rows [p; x; g], in the sign convention of
+ * mpcqp_get (P x + q + A'y = 0, y_i > 0 on an active upper bound).  With col0 = np (the parameter columns are skipped: their pinned rows
+ * absorb any value):
+ *   t_j    = sum_k A_kj y_k, the entries of column j added in storage order, each product and each sum rounded (no fused multiply-add)
+ *   stat   = max_{j >= col0} |q_j + t_j|                  scale = max_{j >= col0} max(|q_j|, |t_j|)
+ *   feas   = max_i max(l_i, -u_i, 0)                      (the distance of 0 from [l_i, u_i]: the violation of the NLP's own bounds at w)
+ *   compl  = max_i max( min(max(y_i, 0), max(u_i, 0)), min(max(-y_i, 0), max(-l_i, 0)) )
+ *            (the min form: no product with an infinite bound; a multiplier pushing on a bound that is +-inf or +-1e30 counts in full, an
+ *            equality row at a feasible point counts 0)
+ *   converged = stat <= tol_stat * max(1, scale)  and  feas <= tol_feas  and  compl <= tol_compl
+ * res[4 b ..] = {stat, feas, compl, scale}.  A NaN anywhere in the instance's q, A, l, u, y -- the parameter columns included -- or in a q_j + t_j
+ * makes all four NaN and converged 0: an instance whose last QP returned no point has a NaN y and never reads as converged.
+ * frozen [batch], when given: an instance with a nonzero entry is neither read nor written (its res and converged keep their bits).
+ * One lane group of 16, 32 or 64 lanes per instance, chosen from max(n - col0, m); a lane owns columns lane, lane + G, ... and then rows
+ * lane, lane + G, ...; the maxima are reduced by a fixed xor butterfly inside the group and one lane writes.  No atomics, no LDS: the result
+ * is bitwise repeatable and does not depend on the batch size or on the instance's position in the batch.  All pointers are device memory,
+ * instance-major and dense.  Asynchronous on `stream`; the handle keeps the pattern of A on the device from its creation, so a call allocates
+ * nothing, copies nothing, and a captured graph replays it.  Generated libraries take no part: every handle has the entry.
+ * MPCQP_ERR_ARG for a null handle, batch <= 0, a null argument block, a null q, A, l, u, y or res, or a tolerance that is negative or NaN. */
+typedef struct mpcqp_kkt_args {
+  const double *q, *A, *l, *u, *y;     /* [batch * n | nnzA | m | m | m]                              */
+  double *res;                         /* [batch * 4]: stat, feas, compl, scale                      */
+  int *converged;                      /* [batch], optional                                          */
+  const int *frozen;                   /* [batch], optional: nonzero = neither read nor written      */
+  double tol_stat, tol_feas, tol_compl;
+} mpcqp_kkt_args;
+int mpcqp_stage_kkt(mpcqp_stage *s, int batch, const mpcqp_kkt_args *a, void *stream);
+int mpcqp_nlp_kkt(mpcqp_nlp *s, int batch, const mpcqp_kkt_args *a, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Structured stage form: the same QP, given by its stage blocks instead of CSC value arrays.
  *

@@ -8,7 +8,11 @@
 // only under `verbose` (:183-197) -- the loop ends after the first iteration in which every instance moved by less than t
 // (max-norm of alpha * dx, mpcqp_stage_step's step_max).  Opt-in as well: setLineSearch(candidates, beta, c1) replaces the one alpha of :171-177
 // by a step length per instance from an l1-merit backtracking search that starts at alpha (mpcqp_stage_linesearch, one kernel in place of
-// the step; the penalty persists across iterations and calls); alphaTaken() reports the last iteration's step lengths.  Header-only; needs the HIP runtime for the device buffers (hipMalloc / hipMemcpy).
+// the step; the penalty persists across iterations and calls); alphaTaken() reports the last iteration's step lengths.  Opt-in as well:
+// setKktTolerance(stat, feas, compl) adds the per-instance stop on the NLP's optimality residuals (mpcqp_stage_kkt): in every iteration but
+// the first of a call, between the evaluation and the QP, the residuals are taken with the multipliers of the previous QP; an instance that meets the
+// tolerances is frozen for the rest of the call (its x is not stepped), and the loop ends before the QP once every instance is; converged(),
+// convergedAt() and kktResiduals() report on the last call.  Header-only; needs the HIP runtime for the device buffers (hipMalloc / hipMemcpy).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -43,6 +47,8 @@ class StageSQP {
   ~StageSQP() {
     for (double *p : bufs_) (void)hipFree(p);
     if (status_) (void)hipFree(status_);
+    if (conv_) (void)hipFree(conv_);
+    if (masked_) (void)hipFree(masked_);
     if (qp_) mpcqp_destroy(qp_);
     if (ocp_) mpcqp_stage_destroy(ocp_);
   }
@@ -96,12 +102,31 @@ class StageSQP {
   void setLineSearch(int candidates, double beta = 0.5, double c1 = 1e-4) {
     if (candidates < 0 || candidates > MPCQP_LINESEARCH_MAX_CANDIDATES) throw std::invalid_argument("candidates must be in 0..8");
     lsCandidates_ = candidates; lsBeta_ = beta; lsC1_ = c1;
-    if (candidates > 0 && !y_) {
+    if (candidates > 0 && !mu_) {
       const size_t B = batch_;
-      y_ = dalloc(B * m()); mu_ = dalloc(B); alphaOut_ = dalloc(B);
+      needDuals();
+      mu_ = dalloc(B); alphaOut_ = dalloc(B);
       hip(hipMemset(mu_, 0, B * sizeof(double)));
-      hip(hipMalloc(&status_, B * sizeof(int)));
     }
+  }
+  // option kkt_tol (default off: all three 0): the per-instance stop on stat <= tol_stat max(1, scale), feas <= tol_feas, compl <= tol_compl
+  void setKktTolerance(double stat, double feas, double compl_) {
+    if (!(stat >= 0.0) || !(feas >= 0.0) || !(compl_ >= 0.0)) throw std::invalid_argument("the tolerances must not be negative or NaN");
+    kktTol_[0] = stat; kktTol_[1] = feas; kktTol_[2] = compl_;
+    kkt_ = stat > 0.0 || feas > 0.0 || compl_ > 0.0;
+    if (kkt_ && !kktRes_) {
+      const size_t B = batch_;
+      needDuals();
+      kktRes_ = dalloc(B * 4);
+      hip(hipMalloc(&conv_, B * sizeof(int))); hip(hipMalloc(&masked_, B * sizeof(int)));
+    }
+  }
+  const std::vector<int> &converged() const { return converged_; }          // per instance, 0 / 1, of the last call
+  const std::vector<int> &convergedAt() const { return convergedAt_; }      // the iteration index of the check that froze the instance, -1 if never
+  std::vector<double> kktResiduals() const {                                // [batch * 4] = stat, feas, compl, scale of the last check (empty: none ran)
+    std::vector<double> r;
+    if (kktRes_ && checked_) { r.resize((size_t)batch_ * 4); hip(hipMemcpy(r.data(), kktRes_, r.size() * sizeof(double), hipMemcpyDeviceToHost)); }
+    return r;
   }
   const std::vector<double> &alphaTaken() const { return alphaTaken_; }      // per instance, last iteration (empty without the line search)
   int iterationsDone() const { return iterationsDone_; }
@@ -111,8 +136,21 @@ class StageSQP {
     need(arg.lbx.size(), B * nvar(), "lbx"); need(arg.ubx.size(), B * nvar(), "ubx");
     need(arg.lbg.size(), B * ng(), "lbg"); need(arg.ubg.size(), B * ng(), "ubg"); need(arg.p.size(), B * np(), "p");
     up(lbx_, arg.lbx); up(ubx_, arg.ubx); up(lbg_, arg.lbg); up(ubg_, arg.ubg); up(p_, arg.p);
+    if (kkt_) { hip(hipMemset(conv_, 0, B * sizeof(int))); converged_.assign(B, 0); convergedAt_.assign(B, -1); checked_ = false; }
+    iterationsDone_ = 0;
     for (int i = 0; i < stepNum_; i++) {
       check(mpcqp_stage_eval(ocp_, batch_, p_, x_, lbx_, ubx_, lbg_, ubg_, dP_, dq_, dA_, dl_, du_, nullptr), "mpcqp_stage_eval");
+      if (kkt_ && i >= 1) {                                         // the verdicts of the earlier checks are the frozen mask of this one
+        mpcqp_kkt_args k = {};
+        k.q = dq_; k.A = dA_; k.l = dl_; k.u = du_; k.y = y_; k.res = kktRes_; k.converged = conv_; k.frozen = conv_;
+        k.tol_stat = kktTol_[0]; k.tol_feas = kktTol_[1]; k.tol_compl = kktTol_[2];
+        check(mpcqp_stage_kkt(ocp_, batch_, &k, nullptr), "mpcqp_stage_kkt");
+        hip(hipMemcpy(converged_.data(), conv_, B * sizeof(int), hipMemcpyDeviceToHost));      // one vector back to the host per iteration
+        checked_ = true;
+        bool all = true;
+        for (size_t b = 0; b < B; b++) { if (converged_[b] && convergedAt_[b] < 0) convergedAt_[b] = i; all = all && converged_[b] != 0; }
+        if (all) break;
+      }
       int rc = MPCQP_ERR_LIMIT;
       if (keepScaling_ && scaled_) {
         rc = mpcqp_update_matrices(qp_, dP_, nnzP(), dq_, n(), dA_, nnzA(), dl_, m(), du_, m(), MPCQP_MEM_DEVICE);
@@ -126,14 +164,25 @@ class StageSQP {
       check(mpcqp_solve(qp_, nullptr), "mpcqp_solve");
       if (lsCandidates_ > 0) {
         check(mpcqp_get(qp_, dw_, y_, nullptr, status_, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
+        if (kkt_) {                                                 // a frozen instance reads as one whose QP returned no point
+          hostStatus_.resize(B);
+          hip(hipMemcpy(hostStatus_.data(), status_, B * sizeof(int), hipMemcpyDeviceToHost));
+          for (size_t b = 0; b < B; b++) if (converged_[b]) hostStatus_[b] = 0;
+          hip(hipMemcpy(masked_, hostStatus_.data(), B * sizeof(int), hipMemcpyHostToDevice));
+        }
         mpcqp_stage_linesearch_args ls = {};
-        ls.p = p_; ls.x = x_; ls.lbx = lbx_; ls.ubx = ubx_; ls.q = dq_; ls.dw = dw_; ls.y = y_; ls.status = status_; ls.mu = mu_;
+        ls.p = p_; ls.x = x_; ls.lbx = lbx_; ls.ubx = ubx_; ls.q = dq_; ls.dw = dw_; ls.y = y_; ls.status = kkt_ ? masked_ : status_; ls.mu = mu_;
         ls.alpha_out = alphaOut_; ls.step_max = tol_ > 0.0 ? g_ : nullptr;
         ls.alpha0 = alpha_; ls.beta = lsBeta_; ls.c1 = lsC1_; ls.mu_min = 1.0; ls.mu_factor = 1.1; ls.candidates = lsCandidates_;
         check(mpcqp_stage_linesearch(ocp_, batch_, &ls, nullptr), "mpcqp_stage_linesearch");
       } else {
-        check(mpcqp_get(qp_, dw_, nullptr, nullptr, nullptr, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
-        check(mpcqp_stage_step(ocp_, batch_, alpha_, dw_, x_, tol_ > 0.0 ? g_ : nullptr, nullptr, nullptr), "mpcqp_stage_step");
+        check(mpcqp_get(qp_, dw_, kkt_ ? y_ : nullptr, nullptr, nullptr, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
+        if (kkt_) {                                                 // every live instance steps as the reference does; a frozen one keeps its x
+          hostStatus_.resize(B);
+          for (size_t b = 0; b < B; b++) hostStatus_[b] = converged_[b] ? 0 : MPCQP_SOLVED;
+          hip(hipMemcpy(masked_, hostStatus_.data(), B * sizeof(int), hipMemcpyHostToDevice));
+        }
+        check(mpcqp_stage_step(ocp_, batch_, alpha_, dw_, x_, tol_ > 0.0 ? g_ : nullptr, kkt_ ? masked_ : nullptr, nullptr), "mpcqp_stage_step");
       }
       iterationsDone_ = i + 1;
       if (tol_ > 0.0) {                                           // one vector of step norms back to the host per iteration
@@ -164,6 +213,12 @@ class StageSQP {
   static void need(size_t got, size_t want, const char *name) {
     if (got != want) throw std::invalid_argument(std::string(name) + " 的维度不对: expected " + std::to_string(want) + ", got " + std::to_string(got));
   }
+  // the multipliers and statuses of the QP on the device (the line search and the optimality residuals read them)
+  void needDuals() {
+    if (y_) return;
+    y_ = dalloc((size_t)batch_ * m());
+    hip(hipMalloc(&status_, (size_t)batch_ * sizeof(int)));
+  }
   double *dalloc(size_t count) { double *p = nullptr; hip(hipMalloc(&p, (count ? count : 1) * sizeof(double))); bufs_.push_back(p); return p; }
   void up(double *dst, const std::vector<double> &src) { if (!src.empty()) hip(hipMemcpy(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice)); }
 
@@ -173,6 +228,9 @@ class StageSQP {
   int lsCandidates_ = 0; double lsBeta_ = 0.5, lsC1_ = 1e-4;      // line search: 0 candidates = off
   double *y_ = nullptr, *mu_ = nullptr, *alphaOut_ = nullptr; int *status_ = nullptr;
   std::vector<double> alphaTaken_;
+  bool kkt_ = false, checked_ = false; double kktTol_[3] = {0.0, 0.0, 0.0};   // optimality residuals: all tolerances 0 = off
+  double *kktRes_ = nullptr; int *conv_ = nullptr, *masked_ = nullptr;
+  std::vector<int> converged_, convergedAt_, hostStatus_;
   int dims_[8] = {0};
   mpcqp_stage *ocp_ = nullptr; mpcqp_handle *qp_ = nullptr;
   double *x_ = nullptr, *dP_ = nullptr, *dq_ = nullptr, *dA_ = nullptr, *dl_ = nullptr, *du_ = nullptr, *dw_ = nullptr, *f_ = nullptr, *g_ = nullptr;

@@ -25,6 +25,7 @@ struct mpcqp_nlp {
   int device = 0;
   std::vector<int> Pp, Pi, Ap, Ai;
   int *dtab = nullptr;               // one device allocation: Ap, hslot, jslot
+  int *dkkt = nullptr;               // Ap and Ai on the device for mpcqp_nlp_kkt
   void *lib = nullptr;
   gn_eval_fn eval = nullptr;
   gn_merit_fn merit = nullptr;
@@ -76,6 +77,7 @@ int mpcqp_nlp_create(const char *library_path, int device, mpcqp_nlp **out) {
       hipMemcpy(s->dtab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
     mpcqp_nlp_destroy(s); return mpcqp_set_error(MPCQP_ERR_HIP, "upload of the evaluator's tables failed");
   }
+  if (int rc = mpcqp_kkt_upload(n, m, np, s->Ap, s->Ai, &s->dkkt)) { mpcqp_nlp_destroy(s); return rc; }
   GnDev &gd = s->gd;
   gd.n = n; gd.np = np; gd.nvar = nvar; gd.ng = ng; gd.m = m; gd.nnzP = nnzP; gd.nnzA = nnzA; gd.hp = hp; gd.jp = jp;
   gd.Ap = s->dtab; gd.hslot = s->dtab + n + 1; gd.jslot = gd.hslot + (size_t)hp * n;
@@ -86,6 +88,7 @@ int mpcqp_nlp_create(const char *library_path, int device, mpcqp_nlp **out) {
 void mpcqp_nlp_destroy(mpcqp_nlp *s) {
   if (!s) return;
   if (s->dtab) { (void)hipSetDevice(s->device); (void)hipFree(s->dtab); }
+  if (s->dkkt) { (void)hipSetDevice(s->device); (void)hipFree(s->dkkt); }
   if (s->lib) dlclose(s->lib);
   delete s;
 }
@@ -171,6 +174,12 @@ int mpcqp_nlp_lagrangian(mpcqp_nlp *s, int batch, const mpcqp_nlp_lagrangian_arg
   MPCQP_HIPCHK(hipSetDevice(s->device));
   MPCQP_HIPCHK((hipError_t)s->lagrangian(batch, a, stream));
   return MPCQP_OK;
+}
+
+// the optimality residuals at the system mpcqp_nlp_eval just wrote (kkt.hip; the library takes no part)
+int mpcqp_nlp_kkt(mpcqp_nlp *s, int batch, const mpcqp_kkt_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "nlp handle is null");
+  return mpcqp_kkt_run(s->device, s->gd.n, s->gd.m, s->gd.np, s->gd.nnzA, s->dkkt, batch, a, stream);
 }
 
 }  // extern "C"

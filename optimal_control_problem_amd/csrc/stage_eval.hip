@@ -79,6 +79,7 @@ struct mpcqp_stage {
   // library that exports the launchers
   bool exact = false;
   int *dlslots = nullptr;
+  int *dkkt = nullptr;                // Ap and Ai on the device for mpcqp_stage_kkt
 };
 
 // a launch may not be larger than a stored parameter set
@@ -203,6 +204,7 @@ static int stage_create_common(const mpcqp_stage_desc *d, int nx, int nu, int nh
   if (hipMemcpy(s->dPp, s->Pp.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(s->dAp, s->Ap.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
     return mpcqp_set_error(MPCQP_ERR_HIP, "upload of the column pointers failed");
+  if (int rc = mpcqp_kkt_upload(sd.n, sd.m, sd.np, s->Ap, s->Ai, &s->dkkt)) return rc;
   sd.Pp = s->dPp; sd.Ap = s->dAp; sd.Qk = nullptr; sd.Rk = nullptr; sd.hmask = nullptr; sd.h_lok = nullptr; sd.h_hik = nullptr;
   if (cost_mask) {
     const size_t mb = (size_t)(sd.f + sd.nx) * (sd.f + sd.nx);
@@ -396,6 +398,7 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   if (s->dslots) (void)hipFree(s->dslots);
   if (s->dcvx) (void)hipFree(s->dcvx);
   if (s->dlslots) (void)hipFree(s->dlslots);
+  if (s->dkkt) (void)hipFree(s->dkkt);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -659,6 +662,12 @@ int mpcqp_stage_lagrangian(mpcqp_stage *s, int batch, const mpcqp_stage_lagrangi
     if (a->mode != 0) if (int rc = stage_convexify_buffers(s, batch, &w)) return rc;
     return stage_hipchk(s->user.lagrangian(&s->sd, batch, a, s->dlslots, a->mode != 0 ? &w : nullptr, &r, stream));
   });
+}
+
+// the optimality residuals at the system mpcqp_stage_eval just wrote (kkt.hip; no model code takes part, so a generated library needs no export)
+int mpcqp_stage_kkt(mpcqp_stage *s, int batch, const mpcqp_kkt_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  return mpcqp_kkt_run(s->device, s->sd.n, s->sd.m, s->sd.np, s->sd.nnzA, s->dkkt, batch, a, stream);
 }
 
 }  // extern "C"

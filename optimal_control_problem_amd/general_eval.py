@@ -121,6 +121,7 @@ def _bind(L):
     L.mpcqp_nlp_linesearch.argtypes = [vp, C.c_int, C.POINTER(LineSearchArgs), vp]
     L.mpcqp_nlp_has_exact_hessian.argtypes = [vp]
     L.mpcqp_nlp_lagrangian.argtypes = [vp, C.c_int, C.POINTER(LagrangianArgs), vp]
+    L.mpcqp_nlp_kkt.argtypes = [vp, C.c_int, vp, vp]
     L._nlp_bound = True
     return L
 
@@ -273,3 +274,11 @@ class GeneralEvaluator:
         a.mode = self.MODES[mode]
         _lib.check(_lib.lib().mpcqp_nlp_lagrangian(self._h, B, _byref(a), stream))
         return P
+
+    def kkt(self, ls, y, tol=1e-3, out=None, frozen=None, stream=None):
+        """the optimality residuals of every instance in one kernel (mpcqp_nlp_kkt; general_nlp.GeneralNLP.kkt_residuals is its host statement):
+        ls the dict eval just wrote at the iterate, y [B, m] the multipliers of the last QP.  tol: a number or {stat, feas, compl}.  Returns
+        (res [B, 4] = stat, feas, compl, scale; converged [B] int32), device tensors (`out`: such a pair to write into); frozen (int32 [B],
+        optional): an instance with a nonzero entry is neither read nor written."""
+        from .kkt import device_kkt
+        return device_kkt(_lib.lib().mpcqp_nlp_kkt, self, ls, y, tol, out, frozen, stream)

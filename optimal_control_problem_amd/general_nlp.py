@@ -294,6 +294,13 @@ class GeneralNLP:
         return {"x": x, "alpha": alpha, "accepted": acc, "step_max": np.where(moved, np.abs(step).max(axis=1), 0.0), "f": cost[rows, sel],
                 "gmax": gmx[rows, sel], "phi": np.stack([phis[:, 0], phis[rows, sel]], axis=1), "mu": mub, "D": D, "alphas": alphas, "phis": phis}
 
+    # -- the optimality residuals (include/mpcqp.h, mpcqp_nlp_kkt; csrc/kkt_kernels.hpp) ---------------------------------------------------
+    def kkt_residuals(self, ls, y, tol=1e-3):
+        """Host statement of mpcqp_nlp_kkt: (res [B, 4] = stat, feas, compl, scale; converged [B]) of the local system `ls` (what local_system
+        returned at the iterate) under the multipliers y [B, m]; kkt.kkt_residuals states the measure"""
+        from .kkt import kkt_residuals
+        return kkt_residuals(self.Ap, self.Ai, ls.q, ls.A, ls.l, ls.u, y, self.np, tol)
+
     def local_system(self, p, x, lbx, ubx, lbg, ubg):
         """reference SQPOptimizationSolver.cpp:47-77,100-120: P = Hessian of f wrt w, q = gradient, A = [I; dg/dw], bounds shifted by the
         current [p; x; g]"""

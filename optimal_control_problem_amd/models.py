@@ -92,6 +92,11 @@ class DenseNLP:
             u[b] = np.concatenate([p[b], ubx[b], ubg[b]]) - c
         return LocalSystem(self.n, self.m, self.Pp, self.Pi, self.Ap, self.Ai, P, q, A, l, u, self.np)
 
+    def kkt_residuals(self, ls, y, tol=1e-3):
+        """the optimality residuals of the local system `ls` under the multipliers y (kkt.kkt_residuals states the measure)"""
+        from .kkt import kkt_residuals
+        return kkt_residuals(self.Ap, self.Ai, ls.q, ls.A, ls.l, ls.u, y, self.np, tol)
+
 
 def reference_test_cases():
     """The 8 NLPs of the reference's test/test.cpp (cases 1-8), as (model, arg, expected-or-None).
@@ -1071,6 +1076,13 @@ class StageOCP:
         rows = np.arange(B)
         return {"x": x, "alpha": alpha, "accepted": acc, "step_max": np.where(moved, np.abs(step).max(axis=1), 0.0), "f": cost[rows, sel],
                 "gmax": gmx[rows, sel], "phi": np.stack([phis[:, 0], phis[rows, sel]], axis=1), "mu": mub, "D": D, "alphas": alphas, "phis": phis}
+
+    # -- the optimality residuals (include/mpcqp.h, mpcqp_stage_kkt; csrc/kkt_kernels.hpp) -------------------------------------------------
+    def kkt_residuals(self, ls, y, tol=1e-3):
+        """Host statement of mpcqp_stage_kkt: (res [B, 4] = stat, feas, compl, scale; converged [B]) of the local system `ls` (what local_system
+        returned at the iterate: its q, A, l, u) under the multipliers y [B, m]; kkt.kkt_residuals states the measure"""
+        from .kkt import kkt_residuals
+        return kkt_residuals(self.Ap, self.Ai, ls.q, ls.A, ls.l, ls.u, y, self.np, tol)
 
 
 class DoubleIntegrator(StageOCP):

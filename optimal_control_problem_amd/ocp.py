@@ -309,6 +309,13 @@ class OptimalControlProblem:
         if not (eh is None or isinstance(eh, bool) or eh == "dominant"):
             raise ValueError("SQP_settings.exact_hessian: expected true, false or dominant")
         self.exactHessian_ = eh if eh else None
+        # extension (opt-in, no such key in the reference's YAML): SQP_settings.kkt_tol -- absent, false or 0 = the reference's fixed step_num; a number,
+        # or a map {stat, feas, compl} = the per-instance stop on the NLP's optimality residuals (sqp.py).  Checked here.
+        from .kkt import kkt_tolerances
+        kt = s["SQP_settings"].get("kkt_tol")
+        if not (kt is None or kt is False or (isinstance(kt, (int, float)) and not isinstance(kt, bool)) or isinstance(kt, dict)):
+            raise ValueError("SQP_settings.kkt_tol: expected a number or a map of stat, feas, compl")
+        self.kktTol_ = None if kkt_tolerances(kt) is None else (dict(kt) if isinstance(kt, dict) else float(kt))
         method = str(s["solve_method"])
         if method not in self.SOLVER_TYPES:
             raise ValueError("Unknown solver type: " + method)                       # :43-45
@@ -440,6 +447,8 @@ class OptimalControlProblem:
                    "verbose": self.solverSettings["verbose"]}
         if self.lineSearch_ is not None:
             options["line_search"] = self.lineSearch_        # to whichever of the three solvers below is built
+        if self.kktTol_ is not None:
+            options["kkt_tol"] = self.kktTol_                # to whichever of the three solvers below is built
         if self.exactHessian_ is not None:
             if not self.generalPath_:
                 raise ValueError("SQP_settings.exact_hessian: this problem is a stage pattern, and the facade does not build stage models with the "

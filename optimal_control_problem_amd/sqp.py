@@ -27,6 +27,14 @@ the same call convexifies H_k + C_k.  For models with lcost that set exact_hessi
 GeneralNLP(..., exact_hessian=True): there True adds the curvature of g over the whole of w and "dominant" adds it with the
 diagonal-dominance safeguard (general_nlp.GeneralNLP.lagrangian_system states the rule, mpcqp_nlp_lagrangian runs it on the device); `shift`
 holds the last iteration's diagonal shift.
+Opt-in as well: options["kkt_tol"] = t, or {"stat":, "feas":, "compl":}, adds a per-instance stop on the NLP's first-order optimality residuals
+(kkt.kkt_residuals states the measure, mpcqp_stage_kkt / mpcqp_nlp_kkt run it on the device).  In iteration i >= 1 of a call, after the
+evaluation and before the QP, the residuals are taken at the current iterate with the multipliers of QP i - 1; iteration 0 is never checked (its
+bounds and p may be new, its multipliers stale), so every call solves at least one QP.  An instance that meets the tolerances is frozen for the rest
+of the call: its x is not stepped, its lam not updated, later checks skip it.  When every instance is frozen the loop ends before the QP.
+`converged` [batch], `converged_at` [batch] (the iteration index, -1 if never), `kkt_history` (one [batch, 4] = stat, feas, compl, scale per check,
+frozen rows keeping the values they converged with) and `iterations_done` (the QPs solved) report on the last call; kkt(arg) checks the returned
+point on demand.  Either of sqp_tol and kkt_tol stops the loop.
 A stage OCP with a Gauss-Newton frame cost (models.StageOCP.rcost) needs no option: its local system carries 2 J'J and both loops run as
 they are; options["convexify"] and options["exact_hessian"] are refused for it with the model's reason.
 
@@ -39,6 +47,7 @@ import numpy as np
 
 from . import _lib
 from .cucaqp import CuCaQP
+from .kkt import kkt_tolerances
 
 
 def _line_search_options(value):
@@ -147,6 +156,11 @@ class SQPOptimizationSolver:
         # and carry each instance's adapted rho into its next QP, as a kept OSQP workspace would (with warm_start_admm)
         self.carry_rho = bool(options.get("carry_rho", False))
         self.sqp_tol = float(options.get("sqp_tol", 0.0) or 0.0)
+        # opt-in: the per-instance stop on the NLP's optimality residuals (module docstring)
+        self.kkt_tol = kkt_tolerances(options.get("kkt_tol"))
+        if self.kkt_tol is not None and not hasattr(nlp, "kkt_residuals"):
+            raise ValueError("kkt_tol needs a model that states its optimality residuals (kkt_residuals)")
+        self.converged = np.zeros(self.batch, bool); self.converged_at = np.full(self.batch, -1, np.int64); self.kkt_history = []
         # extension, as in the device loop: an instance whose QP returned no point keeps its iterate (the reference adds the NaN solution, :171-177)
         self.skip_failed_steps = bool(options.get("skip_failed_steps", False))
         self.line_search = _line_search_options(options.get("line_search"))
@@ -192,9 +206,22 @@ class SQPOptimizationSolver:
         B = self.batch
         pSize = self.model.np
         p = np.broadcast_to(np.asarray(arg.get("p", np.zeros(0)), float).reshape(-1, pSize) if pSize else np.zeros((1, 0)), (B, pSize))
+        frozen = np.zeros(B, bool)                       # kkt_tol: the instances that converged earlier in this call
+        self.converged = frozen; self.converged_at = np.full(B, -1, np.int64); self.kkt_history = []
+        self.iterations_done = 0
         for i in range(self.stepNum_):
             t0 = time.perf_counter()
             localSystem = self.getLocalSystem(arg)
+            if self.kkt_tol is not None and i >= 1:
+                res, conv = self.model.kkt_residuals(localSystem, self._last_y(), self.kkt_tol)
+                if self.kkt_history:                     # a frozen instance is not looked at again: it keeps what it converged with
+                    res = np.where(frozen[:, None], self.kkt_history[-1], res)
+                self.kkt_history.append(res)
+                self.converged_at = np.where(conv & ~frozen, i, self.converged_at)
+                frozen = frozen | conv
+                self.converged = frozen
+                if frozen.all():
+                    break
             if self._nlp_mode is not None:
                 localSystem.P, self.shift = self.model.lagrangian_system(p, self.result_["x"], self.lam, localSystem.P, None, self._nlp_mode)
             elif self.exact_hessian:
@@ -244,7 +271,10 @@ class SQPOptimizationSolver:
                 if getattr(self.model, "line_search_takes_row_bounds", False):       # a general NLP: the bounds of its rows come with the call
                     ng = self.model.m - self.model.n
                     rows = {k: np.broadcast_to(np.asarray(arg[k], float).reshape(-1, ng) if ng else np.zeros((1, 0)), (B, ng)) for k in ("lbg", "ubg")}
-                ls = self.model.line_search(p, self.result_["x"], box[0], box[1], localSystem.q, solution, info["y"], status=info.get("status"),
+                status = info.get("status")
+                if frozen.any():                         # a frozen instance keeps x and mu like one whose QP returned no point
+                    status = np.where(frozen, 0, np.ones(B, np.int64) if status is None else np.asarray(status))
+                ls = self.model.line_search(p, self.result_["x"], box[0], box[1], localSystem.q, solution, info["y"], status=status,
                                             mu=self._mu, alpha0=self.alpha_, **self.line_search, **rows)
                 self.result_["f"] = ls["f"]; self.gmax = ls["gmax"]
                 self.alpha_taken = ls["alpha"]; self.accepted = ls["accepted"]; self.last_line_search = ls
@@ -253,14 +283,18 @@ class SQPOptimizationSolver:
                 step = self.alpha_ * solution[:, pSize:]
                 if self.skip_failed_steps and self.last_qp_info is not None and "status" in self.last_qp_info:
                     step = np.where(np.isin(np.asarray(self.last_qp_info["status"]), (1, 2, 7))[:, None], step, 0.0)
-                self.result_["x"] = self.result_["x"] + step
+                if frozen.any():
+                    step = np.where(frozen[:, None], 0.0, step)
+                    self.result_["x"] = np.where(frozen[:, None], self.result_["x"], self.result_["x"] + step)
+                else:
+                    self.result_["x"] = self.result_["x"] + step
                 self.result_["f"] = self.model.objective(p, self.result_["x"])
                 self.step_max = np.abs(step).max(axis=1)
             if self.exact_hessian:
                 info = self.last_qp_info
                 if info is None or "y" not in info:
                     raise ValueError("exact_hessian needs a QP backend that reports its multipliers (getInfo()['y'])")
-                got = np.isin(np.asarray(info["status"]), (1, 2, 7)) if "status" in info else np.ones(B, bool)
+                got = (np.isin(np.asarray(info["status"]), (1, 2, 7)) if "status" in info else np.ones(B, bool)) & ~frozen
                 a = self.alpha_taken[:, None] if self.line_search is not None else self.alpha_
                 with np.errstate(invalid="ignore"):
                     self.lam = np.where(got[:, None], self.lam + a * (np.asarray(info["y"], float) - self.lam), self.lam)
@@ -273,6 +307,20 @@ class SQPOptimizationSolver:
             if self.sqp_tol > 0.0 and _all_finite_steps_below(self.step_max, self.sqp_tol):
                 break
         return {"x": self.result_["x"].copy(), "f": self.result_["f"].copy()}
+
+    def _last_y(self):
+        info = self.last_qp_info
+        if info is None or "y" not in info:
+            raise ValueError("kkt needs the multipliers of a QP: a backend that reports them (getInfo()['y']) and one solved QP")
+        return np.asarray(info["y"], float).reshape(self.batch, -1)
+
+    def kkt(self, arg, tol=None):
+        """the optimality residuals of the current iterate under the multipliers of the last QP: one evaluation plus the NumPy statement.
+        tol: as options["kkt_tol"] (default: the option's, else 1e-3).  Returns {"res": [batch, 4] = stat, feas, compl, scale, "converged": [batch]}."""
+        if not hasattr(self.model, "kkt_residuals"):
+            raise ValueError("this model states no optimality residuals (kkt_residuals)")
+        res, conv = self.model.kkt_residuals(self.getLocalSystem(arg), self._last_y(), (tol if tol is not None else self.kkt_tol) or 1e-3)
+        return {"res": res, "converged": conv}
 
 
 def _all_finite_steps_below(step_max, tol):
@@ -311,6 +359,10 @@ class DeviceSQPOptimizationSolver:
         # A handle that does not take such updates (MPCQP_ERR_LIMIT) goes on with full set-ups.
         self.keep_scaling = bool(options.get("keep_scaling", False))
         self.sqp_tol = float(options.get("sqp_tol", 0.0) or 0.0)      # opt-in convergence stop, see the module docstring
+        # extension (opt-in): the per-instance stop on the NLP's optimality residuals -- one mpcqp_stage_kkt / mpcqp_nlp_kkt between the evaluation and
+        # the QP of every iteration but the first, one scalar back to the host (module docstring)
+        self.kkt_tol = kkt_tolerances(options.get("kkt_tol"))
+        self.converged = None; self.converged_at = None; self.kkt_history = []
         # extension: OSQP's `polishing` on every QP of the loop (mpcqp_set_polish); the reference leaves it off (:80-85), and so does the default
         self.polish_qp = bool(options.get("polish_qp", False))
         # extension (opt-in): the QP handle comes from mpcqp_create_presolved -- every singleton row of A with l = u in the first local system (the
@@ -376,6 +428,12 @@ class DeviceSQPOptimizationSolver:
         self.f = None; self.gmax = None
         self._have_start = False                         # like last_qp_info of the host loop: survives across calls
         self._start_clean = False                        # set by mpc.ClosedLoopMPC: mpcqp_stage_advance already zeroed the failed instances' start
+        if self.kkt_tol is not None and not hasattr(self.ev, "kkt"):
+            raise ValueError("kkt_tol: this evaluator has no optimality-residual kernel (stage_eval.StageEvaluator and general_eval.GeneralEvaluator have)")
+        # kkt_tol: the residuals, the verdicts (= the frozen mask: a frozen row is not written again) and the masked status of the step
+        if self.kkt_tol is not None:
+            self._kkt_res = mk(4); self._kkt_conv = torch.zeros(self.batch, dtype=torch.int32, device=self.dev)
+            self._live = torch.ones(self.batch, dtype=torch.int32, device=self.dev)
         if self.line_search is not None:
             self.mu = torch.zeros(self.batch, dtype=torch.float64, device=self.dev)      # the penalty, monotone across iterations and calls
             self._ls_out = {k: torch.zeros(self.batch, dtype=torch.float64, device=self.dev) for k in ("alpha", "step_max", "f", "gmax")}
@@ -436,8 +494,22 @@ class DeviceSQPOptimizationSolver:
         lbx = self._dev(arg["lbx"], ev.nvar); ubx = self._dev(arg["ubx"], ev.nvar)
         lbg = self._dev(arg["lbg"], ev.ng); ubg = self._dev(arg["ubg"], ev.ng)
         stream = torch.cuda.current_stream(self.dev).cuda_stream
+        kkt = self.kkt_tol is not None
+        if kkt:
+            self._kkt_conv.zero_(); self.kkt_history = []
+            self.converged_at = torch.full((self.batch,), -1, dtype=torch.int32, device=self.dev)
+            self.converged = self._kkt_conv.bool()
+        self.iterations_done = 0
         for i in range(self.stepNum_):
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
+            if kkt and i >= 1:
+                # the verdicts of the earlier checks are the frozen mask of this one: a frozen row is neither read nor written
+                ev.kkt(self.ls, self.y, self.kkt_tol, out=(self._kkt_res, self._kkt_conv), frozen=self._kkt_conv, stream=stream)
+                self.kkt_history.append(self._kkt_res.clone())
+                self.converged = self._kkt_conv != 0
+                self.converged_at = torch.where(self.converged & (self.converged_at < 0), torch.full_like(self.converged_at, i), self.converged_at)
+                if int(self._kkt_conv.min()) != 0:       # one scalar back to the host per iteration: every instance is frozen
+                    break
             if self._nlp_mode is not None:
                 ev.lagrangian(p, self.x, self.lam, self.ls["P"], mode=self._nlp_mode, C=self._curv, shift=self.shift, stream=stream)
             elif self.exact_hessian:
@@ -484,17 +556,22 @@ class DeviceSQPOptimizationSolver:
             self.qp.get_device(x=self.dw, y=self.y, status=self.status, iters=self.iters, info=self.info)
             self._have_start = True
             self._start_clean = False
+            status = self.status
+            masked = kkt and i >= 1                      # (nothing is frozen in iteration 0: it runs the launches of a loop without the option)
+            if masked:   # a frozen instance reads as one whose QP returned no point (0 is no status of a point); the reported status stays
+                status = torch.where(self.converged, torch.zeros_like(self.status), self.status if (self.skip_failed_steps or self.line_search is not None) else self._live)
             if self.line_search is not None:
-                ls = ev.line_search(p, self.x, lbx, ubx, self.ls["q"], self.dw, self.y, status=self.status, mu=self.mu, alpha0=self.alpha_,
+                ls = ev.line_search(p, self.x, lbx, ubx, self.ls["q"], self.dw, self.y, status=status, mu=self.mu, alpha0=self.alpha_,
                                     out=self._ls_out, stream=stream, **self.line_search)
                 step, self.f, self.gmax = ls["step_max"], ls["f"], ls["gmax"]
                 self.alpha_taken, self.accepted = ls["alpha"], ls["accepted"]
             else:
-                step = ev.step(self.alpha_, self.dw, self.x, stream=stream, status=self.status if self.skip_failed_steps else None)
+                step = ev.step(self.alpha_, self.dw, self.x, stream=stream, status=status if (self.skip_failed_steps or masked) else None)
                 self.f, self.gmax = ev.merit(p, self.x, stream=stream)
             if self.exact_hessian:
                 # lam += alpha_b (y - lam) where the QP returned a point (its y is NaN elsewhere); elementwise torch, no kernel
-                got = ((self.status == 1) | (self.status == 2) | (self.status == 7)).unsqueeze(1)
+                got = (self.status == 1) | (self.status == 2) | (self.status == 7)
+                got = (got & ~self.converged if kkt else got).unsqueeze(1)
                 a = self.alpha_taken.unsqueeze(1) if self.line_search is not None else self.alpha_
                 self.lam.copy_(torch.where(got, self.lam + a * (self.y - self.lam), self.lam))
             self.admm_iterations.append(self.iters.clone())
@@ -513,6 +590,22 @@ class DeviceSQPOptimizationSolver:
         if not to_host:
             return {"x": self.x, "f": self.f}
         return {"x": self.x.cpu().numpy(), "f": self.f.cpu().numpy()}
+
+    def kkt(self, arg, tol=None):
+        """the optimality residuals of the current iterate -- the point getOptimalSolution returned -- under the multipliers of the last QP: one
+        evaluation plus one mpcqp_stage_kkt / mpcqp_nlp_kkt.  tol: as options["kkt_tol"] (default: the option's, else 1e-3).  Returns
+        {"res": [batch, 4] = stat, feas, compl, scale, "converged": [batch] bool}, device tensors of their own."""
+        import torch
+        if not self._have_start:
+            raise ValueError("kkt needs the multipliers of a QP: call getOptimalSolution first")
+        ev = self.ev
+        p = self._dev(arg.get("p", np.zeros(ev.np)), ev.np)
+        lbx = self._dev(arg["lbx"], ev.nvar); ubx = self._dev(arg["ubx"], ev.nvar)
+        lbg = self._dev(arg["lbg"], ev.ng); ubg = self._dev(arg["ubg"], ev.ng)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
+        res, conv = ev.kkt(self.ls, self.y, (tol if tol is not None else self.kkt_tol) or 1e-3, stream=stream)
+        return {"res": res, "converged": conv != 0}
 
     def close(self):
         if self.qp is not None:

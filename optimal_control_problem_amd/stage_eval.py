@@ -81,6 +81,7 @@ def _bind(L):
     L.mpcqp_stage_convexify.argtypes = [vp, C.c_int, C.POINTER(ConvexifyArgs), vp]
     L.mpcqp_stage_has_exact_hessian.argtypes = [vp]
     L.mpcqp_stage_lagrangian.argtypes = [vp, C.c_int, C.POINTER(LagrangianArgs), vp]
+    L.mpcqp_stage_kkt.argtypes = [vp, C.c_int, vp, vp]
     L._stage_bound = True
     return L
 
@@ -414,3 +415,11 @@ class StageEvaluator:
             a.lam_min = _check(lam_min, (B, self.horizon), "lam_min")
         _lib.check(_lib.lib().mpcqp_stage_lagrangian(self._h, B, C.byref(a), stream))
         return P
+
+    def kkt(self, ls, y, tol=1e-3, out=None, frozen=None, stream=None):
+        """the optimality residuals of every instance in one kernel (mpcqp_stage_kkt; models.StageOCP.kkt_residuals is its host statement): ls the
+        dict eval just wrote at the iterate, y [B, m] the multipliers of the last QP.  tol: a number or {stat, feas, compl}.  Returns
+        (res [B, 4] = stat, feas, compl, scale; converged [B] int32), device tensors (`out`: such a pair to write into); frozen (int32 [B],
+        optional): an instance with a nonzero entry is neither read nor written."""
+        from .kkt import device_kkt
+        return device_kkt(_lib.lib().mpcqp_stage_kkt, self, ls, y, tol, out, frozen, stream)
