@@ -200,6 +200,31 @@ int mpcqp_solve_host(mpcqp_handle *h, const double *P, long strideP, const doubl
  * same plants); a stale hint is harmless.  No reference counterpart (the reference solves one QP at a time). */
 int mpcqp_set_dispatch_hint(mpcqp_handle *h, int enable);
 
+/* Solve a subset of the batch (opt-in; a handle that never sets a skip array launches exactly what it launched before).  skip [batch]: a nonzero
+ * entry (any value) leaves that instance out of the following mpcqp_solve calls -- the polarity of mpcqp_kkt_args.frozen, so the verdict array of
+ * mpcqp_stage_kkt / mpcqp_nlp_kkt can be passed as it is.  NULL clears the skip array.  MPCQP_MEM_DEVICE: the pointer is borrowed and every following
+ * mpcqp_solve reads it on its stream, so the contents may change between solves (and between replays of a captured solve) without another call;
+ * MPCQP_MEM_HOST: the array is copied into a buffer of the handle.  Everything the feature needs is allocated here, never inside mpcqp_solve, which
+ * stays capturable in a HIP graph.  No value comes back to the host.
+ * A skipped instance: none of its inputs is read (P, q, A, l, u, x0, y0, rho0), its bounds are not validated, and nothing of it is written -- x, y, z,
+ * status, iters, info, polish_status, polish_info and its slab of the workspace (factor, D, E, c, rho, parked factor) keep their bits; on a handle
+ * that never solved it they are whatever the buffers held.  An active instance gets, bit for bit, the result of the same solve without a skip array.
+ * How: one small kernel ahead of the solve compacts the dispatch order -- the hint's order where there is one, else the identity -- to the active
+ * instances, in that order, followed by -1 up to batch entries; the grids stay as they are and a workgroup whose entry is negative returns at once
+ * (the ticket loop of the eight-wave iteration kernel ends at the first negative entry).  Reduced handles forward the array to the handle that runs.
+ * Kept workspaces, tracked per handle (not per instance):
+ *   - after a full set-up (mpcqp_update + mpcqp_solve) under a skip array, mpcqp_update_vectors and mpcqp_update_matrices answer MPCQP_ERR_STATE
+ *     until a full set-up without one has run: a skipped instance would reuse a factor or a scaling of other matrices;
+ *   - after an mpcqp_update_matrices solve under a skip array, mpcqp_update_vectors answers MPCQP_ERR_STATE (a skipped instance's factor is of
+ *     older matrices) until an mpcqp_update_matrices solve or a full set-up without one; mpcqp_update_matrices still works (D, E, c are those of
+ *     the unskipped full set-up);
+ *   - an mpcqp_update_vectors solve under a skip array leaves everything valid: a skipped instance's factor, rho and parked state are not touched.
+ * mpcqp_solve_host with a skip array set answers MPCQP_ERR_STATE.  No reference counterpart (the reference solves one QP at a time). */
+int mpcqp_set_skip(mpcqp_handle *h, const int *skip, int mem);
+/* The compacted dispatch list of the last mpcqp_solve (list [batch]: the active instances in dispatch order, then -1), for tests of the compaction
+ * kernel; waits for the solve.  MPCQP_ERR_STATE when the last solve ran without a skip array (or none ran). */
+int mpcqp_debug_skip_list(mpcqp_handle *h, int *list, int mem);
+
 /* Replaces CuCaQP::getSolution / getSolutionAsDM (CuCaQP.cpp:213-224), and additionally surfaces what the
  * reference drops: duals y, row activities z, per-QP status, iteration count and
  * info[4] = {objective, primal residual, dual residual, final rho}.  Any output pointer may be NULL.

@@ -40,6 +40,15 @@ def _ptr_stride(a, width, batch, name):
     return ptr, width, mem, keep
 
 
+def skip_list(skip, order=None):
+    """The dispatch list of a solve under a skip array, as mpcqp_skip_list_kernel builds it (include/mpcqp.h mpcqp_set_skip): `base` is `order`, or the
+    identity when there is none; the list is base[skip[base] == 0] -- stable: it keeps the base order -- followed by -1 up to batch entries."""
+    skip = np.asarray(skip)
+    base = np.arange(len(skip), dtype=np.int32) if order is None else np.asarray(order, dtype=np.int32)
+    act = base[skip[base] == 0]
+    return np.concatenate([act, np.full(len(skip) - len(act), -1, dtype=np.int32)]).astype(np.int32)
+
+
 class BatchQP:
     def __init__(self, n, m, batch, Pp, Pi, Ap, Ai, settings=None, fixed_rows=None, tuned=False, presolve_bounds=None, **kw):
         """fixed_rows: opt-in reduced form (mpcqp_create_reduced) -- singleton rows of A with l = u in every instance, whose
@@ -72,6 +81,14 @@ class BatchQP:
             fr = np.ascontiguousarray(fixed_rows, dtype=np.int32)
             _lib.check(L.mpcqp_create_reduced(self.n, self.m, self.batch, self.Pp.ctypes.data, self.Pi.ctypes.data,
                                               self.Ap.ctypes.data, self.Ai.ctypes.data, len(fr), fr.ctypes.data, C.byref(self.settings), C.byref(self._h)))
+        # the device the handle lives on (settings.device, -1 = the one current at creation): what a borrowed tensor is checked against (set_skip)
+        self._device_index = int(self.settings.device)
+        if self._device_index < 0:
+            try:
+                import torch
+                self._device_index = int(torch.cuda.current_device())
+            except ImportError:
+                self._device_index = 0
 
     @property
     def nnzP(self):
@@ -117,6 +134,35 @@ class BatchQP:
     def set_dispatch_hint(self, enable=True):
         """longest-first dispatch order from the previous solve's iteration counts (on by default; changes no result)"""
         _lib.check(_lib.lib().mpcqp_set_dispatch_hint(self._h, 1 if enable else 0))
+
+    def set_skip(self, skip):
+        """Leave instances out of the following solves (mpcqp_set_skip): skip [batch], nonzero = skipped -- nothing of such an instance is read or
+        written, the active ones get the bits of an unskipped solve.  A CUDA int32 tensor is borrowed and read by every following solve on its
+        stream (its contents may change between solves); a NumPy array is copied; None clears."""
+        if skip is None:
+            self._keep_skip = None
+            _lib.check(_lib.lib().mpcqp_set_skip(self._h, None, _lib.MEM_HOST))
+            return
+        if _is_torch(skip) and skip.is_cuda:
+            import torch
+            if skip.dtype != torch.int32 or not skip.is_contiguous() or tuple(skip.shape) != (self.batch,):
+                raise ValueError("skip: expected a contiguous int32 tensor of %d values" % self.batch)
+            if skip.device.index != self._device_index:      # (borrowed: the kernels of this handle dereference the pointer on the handle's device)
+                raise ValueError("skip: the tensor lives on cuda:%s, the handle on cuda:%d" % (skip.device.index, self._device_index))
+            self._keep_skip = skip
+            _lib.check(_lib.lib().mpcqp_set_skip(self._h, skip.data_ptr(), _lib.MEM_DEVICE))
+            return
+        a = np.ascontiguousarray(skip.numpy() if _is_torch(skip) else skip, dtype=np.int32)
+        if a.shape != (self.batch,):
+            raise ValueError("skip: expected %d values, one per instance" % self.batch)
+        self._keep_skip = a
+        _lib.check(_lib.lib().mpcqp_set_skip(self._h, a.ctypes.data, _lib.MEM_HOST))
+
+    def debug_skip_list(self):
+        """the dispatch list of the last solve under a skip array (mpcqp_debug_skip_list): active instances in dispatch order, then -1"""
+        a = np.empty(self.batch, dtype=np.int32)
+        _lib.check(_lib.lib().mpcqp_debug_skip_list(self._h, a.ctypes.data, _lib.MEM_HOST))
+        return a
 
     def keep_workspace(self, enable=True):
         """keep scaling, factorisation and rho across solves so that update_vectors() can skip the setup"""

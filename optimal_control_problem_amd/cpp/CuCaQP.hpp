@@ -68,6 +68,11 @@ class CuCaQP {
   // and every instance's rho, scales the new data with them and re-factorises (mpcqp_update_matrices = OSQP's osqp_update_data_mat, what OsqpEigen makes
   // of the reference's CuCaQP.cpp:106-116,129-140).  A handle that answers MPCQP_ERR_LIMIT runs the full set-up instead, silently.
   void setKeepScaling(bool keep) { keepScaling_ = keep; }
+  // extension: leave instances out of the following solves (mpcqp_set_skip): skip [batch], nonzero = skipped; nullptr solves the whole batch again.
+  // A skipped instance's entries of getSolutionVector() / getStatus() / getIterations() are those of its last solve on this handle.
+  // Kept workspace: after a set-up under a skip array the skipped instances hold no factor or scaling of the current matrices, so mpcqp_update_vectors /
+  // mpcqp_update_matrices answer MPCQP_ERR_STATE (include/mpcqp.h); a solve() after update*() then runs the full set-up instead, as for MPCQP_ERR_LIMIT.
+  void setSkip(const int *skip) { if (skip) skip_.assign(skip, skip + batch_); else skip_.clear(); }
   int getPolishStatus() const { return polishStatus_.empty() ? MPCQP_POLISH_NOT_PERFORMED : polishStatus_[0]; }
   const std::vector<int> &getPolishStatusVector() const { return polishStatus_; }
 
@@ -171,13 +176,17 @@ class CuCaQP {
     // (updateLowerBound / updateUpperBound on a presolved handle: bounds that pin another set of rows need a new handle, as in initSolver)
     if (presolve_ && vectorsOnly_ && pinnedRows() != fixedRows_ && !initSolver()) return false;
     int rc = MPCQP_OK;
-    if (vectorsOnly_ && kept_ && solvedOnce_ && !matricesDirty_)
+    if (vectorsOnly_ && kept_ && solvedOnce_ && !matricesDirty_) {
       rc = mpcqp_update_vectors(handle_, q_.data(), numOfVariables_, l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
+      if (rc == MPCQP_ERR_STATE && skipUsed_)      // (an earlier set-up ran under a skip array: the full set-up, which repairs the slabs of the instances it solves)
+        rc = mpcqp_update(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
+                          l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
+    }
     else if (matricesDirty_ && keepScaling_ && kept_ && solvedOnce_ && !noMatrixUpdates_) {
       rc = mpcqp_update_matrices(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
                                  l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
-      if (rc == MPCQP_ERR_LIMIT) {      // (this handle's kernel family has no such entry: the full set-up from now on)
-        noMatrixUpdates_ = true;
+      if (rc == MPCQP_ERR_LIMIT || (rc == MPCQP_ERR_STATE && skipUsed_)) {      // (this handle's kernel family has no such entry: the full set-up from now on; or an earlier set-up ran under a skip array: the full set-up this time)
+        if (rc == MPCQP_ERR_LIMIT) noMatrixUpdates_ = true;
         rc = mpcqp_update(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
                           l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
       }
@@ -186,6 +195,8 @@ class CuCaQP {
       rc = mpcqp_update(handle_, Pv_.data(), (long)Pi_.size(), q_.data(), numOfVariables_, Av_.data(), (long)Ai_.size(),
                         l_.data(), numOfConstraints_, u_.data(), numOfConstraints_, MPCQP_MEM_HOST);
     vectorsOnly_ = matricesDirty_ = false;
+    if (rc == MPCQP_OK) rc = mpcqp_set_skip(handle_, skip_.empty() ? nullptr : skip_.data(), MPCQP_MEM_HOST);
+    skipUsed_ = skipUsed_ || !skip_.empty();
     if (rc == MPCQP_OK) rc = mpcqp_solve(handle_, nullptr);
     solvedOnce_ = rc == MPCQP_OK;
     solution_.resize((size_t)batch_ * numOfVariables_); status_.resize(batch_); iters_.resize(batch_);
@@ -337,6 +348,7 @@ class CuCaQP {
   bool isInitialized_ = false, verbose_ = false, patternChanged_ = true, dirty_ = false;
   bool kept_ = false, vectorsOnly_ = false, matricesDirty_ = false, solvedOnce_ = false, presolve_ = false, polish_ = false, polishOn_ = false;
   bool keepScaling_ = false, noMatrixUpdates_ = false;
+  std::vector<int> skip_; bool skipUsed_ = false;      // (skipUsed_: some solve of this object ran under a skip array)
   int nfixed_ = 0;
   mpcqp_settings settings_;
   mpcqp_handle *handle_ = nullptr;

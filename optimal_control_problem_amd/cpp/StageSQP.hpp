@@ -121,6 +121,14 @@ class StageSQP {
       hip(hipMalloc(&conv_, B * sizeof(int))); hip(hipMalloc(&masked_, B * sizeof(int)));
     }
   }
+  // option skip_converged_qps (default off; with the KKT stop): from iteration 1 on the verdict array is the QP handle's skip array (mpcqp_set_skip), so
+  // a frozen instance's QP is neither set up nor iterated; x, converged() and convergedAt() are bit for bit those of the loop without it
+  // While the stop is switched off again (setKktTolerance(0, 0, 0)) the option stays set and does nothing: every iteration solves the whole batch.
+  void setSkipConvergedQPs(bool on) {
+    if (on && !kkt_) throw std::invalid_argument("setSkipConvergedQPs skips the QPs of the instances the KKT stop has frozen: call setKktTolerance first");
+    skipConverged_ = on;
+    if (!on) check(mpcqp_set_skip(qp_, nullptr, MPCQP_MEM_DEVICE), "mpcqp_set_skip");
+  }
   const std::vector<int> &converged() const { return converged_; }          // per instance, 0 / 1, of the last call
   const std::vector<int> &convergedAt() const { return convergedAt_; }      // the iteration index of the check that froze the instance, -1 if never
   std::vector<double> kktResiduals() const {                                // [batch * 4] = stat, feas, compl, scale of the last check (empty: none ran)
@@ -161,6 +169,8 @@ class StageSQP {
         check(mpcqp_update(qp_, dP_, nnzP(), dq_, n(), dA_, nnzA(), dl_, m(), du_, m(), MPCQP_MEM_DEVICE), "mpcqp_update");
         scaled_ = true;
       }
+      // (iteration 0, and every iteration once the KKT stop has been switched off again: the whole batch -- the verdicts of an earlier call must not linger on the handle)
+      if (skipConverged_) check(mpcqp_set_skip(qp_, kkt_ && i >= 1 ? conv_ : nullptr, MPCQP_MEM_DEVICE), "mpcqp_set_skip");
       check(mpcqp_solve(qp_, nullptr), "mpcqp_solve");
       if (lsCandidates_ > 0) {
         check(mpcqp_get(qp_, dw_, y_, nullptr, status_, nullptr, nullptr, MPCQP_MEM_DEVICE), "mpcqp_get");
@@ -228,6 +238,7 @@ class StageSQP {
   int lsCandidates_ = 0; double lsBeta_ = 0.5, lsC1_ = 1e-4;      // line search: 0 candidates = off
   double *y_ = nullptr, *mu_ = nullptr, *alphaOut_ = nullptr; int *status_ = nullptr;
   std::vector<double> alphaTaken_;
+  bool skipConverged_ = false;
   bool kkt_ = false, checked_ = false; double kktTol_[3] = {0.0, 0.0, 0.0};   // optimality residuals: all tolerances 0 = off
   double *kktRes_ = nullptr; int *conv_ = nullptr, *masked_ = nullptr;
   std::vector<int> converged_, convergedAt_, hostStatus_;

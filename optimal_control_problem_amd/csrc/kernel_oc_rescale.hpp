@@ -15,6 +15,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_rescale_kernel(const De
   constexpr int NT = NW * WAVE;
   const int lane = threadIdx.x & 63;
   const int b = __builtin_amdgcn_readfirstlane(io.order ? io.order[blockIdx.x] : (int)blockIdx.x);
+  if (b < 0) return;      // (mpcqp_set_skip: the dispatch list ends in -1 entries; the whole workgroup leaves, nothing of any instance is touched)
   int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (NW == 4) wid = oc_wave_role4(lds, wid, lane, io.no_remap);
   const int tid = wid * WAVE + lane;

@@ -103,6 +103,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
   constexpr int NT = NW * WAVE;
   const int lane = threadIdx.x & 63;
   const int b = __builtin_amdgcn_readfirstlane(io.order ? io.order[blockIdx.x] : (int)blockIdx.x);
+  if (b < 0) return;      // (mpcqp_set_skip: the dispatch list ends in -1 entries; the whole workgroup leaves, nothing of any instance is touched)
   int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (NW == 4) wid = oc_wave_role4(lds, wid, lane, io.no_remap);
   const int tid = wid * WAVE + lane;
@@ -692,7 +693,9 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_admm_kernel(const DevPl
   int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (NW == 4) wid = oc_wave_role4(lds, wid, lane, io.no_remap);
   if constexpr (NW != 8) {      // (the four-wave instances, two workgroups per CU, keep a grid of one workgroup per instance: measured below)
-    oc_admm_one<NW, OCG, OCH, RF, TL, PAIRS>(pl, rs, st, io, oc, lds, __builtin_amdgcn_readfirstlane(io.order ? io.order[blockIdx.x] : (int)blockIdx.x), wid, lane);
+    const int b1 = __builtin_amdgcn_readfirstlane(io.order ? io.order[blockIdx.x] : (int)blockIdx.x);
+    if (b1 < 0) return;      // (mpcqp_set_skip: a -1 entry of the dispatch list)
+    oc_admm_one<NW, OCG, OCH, RF, TL, PAIRS>(pl, rs, st, io, oc, lds, b1, wid, lane);
     return;
   }
   const OcLds<NW> L = oc_lds<NW>(lds, pl, rs, oc);
@@ -710,7 +713,7 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_admm_kernel(const DevPl
         base = __builtin_amdgcn_readfirstlane(b0);
         const int t = base + (int)threadIdx.x;
         int st_ = 0;
-        if (t < io.count) st_ = io.status[io.order ? io.order[t] : t];
+        if (t < io.count) { const int bt = io.order ? io.order[t] : t; if (bt >= 0) st_ = io.status[bt]; }      // (a -1 entry, mpcqp_set_skip, reads as status 0)
         mask = __ballot(st_ == OC_PENDING || st_ == OC_PENDING_NONCVX);
       }
       if (threadIdx.x == 0) {
@@ -722,11 +725,13 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_admm_kernel(const DevPl
     bsync<NW>();
     const int t = __builtin_amdgcn_readfirstlane(*ticket);
     if (t >= io.count) break;
+    const int bq = __builtin_amdgcn_readfirstlane(io.order ? io.order[t] : t);
+    if (bq < 0) break;      // (mpcqp_set_skip: the active instances stand first in the dispatch list, every later entry is -1 too)
     // (lane and wave index made opaque per instance: everything derived from them is computed again for each instance, as in a fresh workgroup -- hoisted out of
     // this loop it stays live across the whole body: 240 B of scratch in an instance that had none)
     int lane_q = lane, wid_q = wid;
     asm volatile("" : "+v"(lane_q), "+s"(wid_q));
-    oc_admm_one<NW, OCG, OCH, RF, TL, PAIRS>(pl, rs, st, io, oc, lds, __builtin_amdgcn_readfirstlane(io.order ? io.order[t] : t), wid_q, lane_q);
+    oc_admm_one<NW, OCG, OCH, RF, TL, PAIRS>(pl, rs, st, io, oc, lds, bq, wid_q, lane_q);
     bsync<NW>();      // (LDS is this instance's until every wave is through with it -- and the ticket until every wave has read it)
   }
 }

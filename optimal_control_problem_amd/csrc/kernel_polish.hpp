@@ -101,6 +101,7 @@ __global__ void __launch_bounds__(WAVE) mpcqp_polish_kernel(const DevPlan pl, co
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int n = pl.n, m = pl.m, npad = pl.npad, mpad = pl.mpad;
+  if (po.skip && po.skip[b] != 0) return;      // (mpcqp_set_skip: polish_status / polish_info of a skipped instance keep their bits)
   if (po.status[b] != MPCQP_SOLVED) {      // (as osqp_solve: only a solved problem is polished)
     if (lane == 0) {
       po.pstatus[b] = MPCQP_POLISH_NOT_PERFORMED;

@@ -7,6 +7,7 @@ template <int PD>
 __global__ void __launch_bounds__(WAVE) mpcqp_admm_kernel(const DevPlan pl, const mpcqp_settings st, const DevIO io) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int b = io.order ? io.order[blockIdx.x] : blockIdx.x, lane = threadIdx.x;
+  if (b < 0) return;      // (mpcqp_set_skip: the dispatch list ends in -1 entries; the whole workgroup leaves, nothing of any instance is touched)
   Ctx cx;
   cx.pl = &pl; cx.st = &st;
   cx.X = lds; cx.Q = cx.X + pl.npad; cx.R = cx.Q + pl.npad;

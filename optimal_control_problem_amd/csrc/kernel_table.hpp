@@ -30,6 +30,7 @@ struct DevPolish {
   double *fac; long fac_stride;
   int *pstatus; double *pinfo;              // MPCQP_POLISH_* and {objective, primal residual, dual residual, active rows} of the candidate
   double delta; int refine;
+  const int *skip;                          // mpcqp_set_skip: per instance of the slice, nonzero = leave it as it is (NULL = none)
 };
 MPCQP_HIDDEN size_t mpcqp_polish_lds(const DevPlan &pl);           // dynamic LDS of one workgroup, bytes
 MPCQP_HIDDEN long mpcqp_polish_fac_doubles(const DevPlan &pl);     // scratch of one instance, doubles

@@ -21,9 +21,10 @@ extern "C" __global__ void __launch_bounds__(WAVE) mpcqp_blockops_kernel(const d
 // iterations and NaN in x, y, z and the residuals (rho, info[3], is left for a kept workspace).  One wave per instance.
 extern "C" __global__ void __launch_bounds__(256) mpcqp_validate_kernel(int batch, int n, int m, const double *__restrict__ l, long sl,
                                                                           const double *__restrict__ u, long su, double *x, double *y, double *z,
-                                                                          int *status, int *iters, double *info) {
+                                                                          int *status, int *iters, double *info, const int *__restrict__ skip) {
   const int lane = threadIdx.x & (WAVE - 1), b = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
   if (b >= batch) return;
+  if (skip && skip[b] != 0) return;      // (mpcqp_set_skip: a skipped instance's bounds are not read, its outputs keep their bits)
   const double *lb = l + (long)b * sl, *ub = u + (long)b * su;
   int crossed = 0;
   for (int i = lane; i < m; i += WAVE) crossed |= lb[i] > ub[i];
@@ -49,4 +50,29 @@ __global__ void __launch_bounds__(1024) mpcqp_order_kernel(const int *__restrict
   if (tid == 0) { int acc = 0; for (int k = NB - 1; k >= 0; k--) { const int c = start[k]; start[k] = acc; acc += c; } }
   __syncthreads();
   for (int i = tid; i < batch; i += blockDim.x) order[atomicAdd(&start[min(max(iters[i], 0) / unit, NB - 1)], 1)] = i;
+}
+
+// The dispatch list of a solve under a skip array (mpcqp_set_skip): base[skip[base] == 0] -- base = the hint's order, or the identity -- followed by -1 up
+// to batch entries; stable, so the hint's longest-first order survives among the active instances.  One workgroup of sixteen waves; per pass of 1024
+// slots a lane's place is the running offset + the totals of the waves below its own (through LDS) + the active lanes below it in its wave (ballot).
+// No atomics: the list is exactly the statement's.  The pass count is uniform and both barriers are inside the loop.
+__global__ void __launch_bounds__(1024) mpcqp_skip_list_kernel(const int *__restrict__ skip, const int *__restrict__ base, int *__restrict__ list, int batch) {
+  __shared__ int wtot[16];
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid / WAVE;
+  int off = 0;
+  for (int i0 = 0; i0 < batch; i0 += 1024) {
+    const int i = i0 + tid;
+    int b = -1;
+    if (i < batch) b = base ? base[i] : i;
+    const bool act = b >= 0 && b < batch && skip[b] == 0;
+    const unsigned long long mask = __ballot(act);
+    if (lane == 0) wtot[w] = __popcll(mask);
+    __syncthreads();
+    int below = 0, total = 0;
+    for (int k = 0; k < 16; k++) { const int c = wtot[k]; below += k < w ? c : 0; total += c; }
+    if (act) list[off + below + __popcll(mask & ((1ull << lane) - 1ull))] = b;
+    off += total;
+    __syncthreads();
+  }
+  for (int i = off + tid; i < batch; i += 1024) list[i] = -1;
 }

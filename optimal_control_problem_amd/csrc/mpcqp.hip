@@ -87,7 +87,19 @@ struct mpcqp_handle {
   bool polish = false, polish_timed = false; double pol_delta = 1e-6; int pol_refine = 3;
   double *pfac = nullptr; long pfac_stride = 0; int *opstatus = nullptr; double *opinfo = nullptr;
   hipEvent_t evp0 = nullptr, evp1 = nullptr;
+  // a subset of the batch (mpcqp_set_skip): the array the following solves read (borrowed, or dskip), the dispatch list the compaction kernel writes
+  // ahead of every such solve (allocated when an array is first set: nothing is allocated inside a solve), whether the last solve wrote one, and what
+  // the skipped instances' slabs may lack: skip_full = a full set-up ran under a skip array (their scaling and factor), skip_mat = an
+  // mpcqp_update_matrices solve did (their factor)
+  const int *skip = nullptr; int *dskip = nullptr, *skip_list = nullptr; bool skip_listed = false, skip_full = false, skip_mat = false;
 };
+// what a solve under the handle's skip array (or without one) leaves for the kept-workspace entries; mode = DevIO.reuse of the solve
+static void note_skip_state(mpcqp_handle *h, int mode) {
+  const bool sk = h->skip != nullptr;
+  if (mode == 0) { h->skip_full = sk; h->skip_mat = false; }
+  else if (mode == 2) h->skip_mat = sk;
+  h->skip_listed = sk;
+}
 
 int mpcqp_order_after_last_solve(mpcqp_handle *h, hipStream_t s) {
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
@@ -205,7 +217,7 @@ static int launch_oc_split(mpcqp_handle *h, DevIO &io, int count, bool reuse, hi
 }
 // `count` instances on stream s through the handle's kernel(s), then the check of what they wrote; every per-instance pointer of io is at the first of them
 // (the kernels index by blockIdx).  Events, where given: after the set-up kernel of the two-kernel form, after the last kernel of the solve.
-static int launch_batch(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipStream_t s, hipEvent_t after_setup, hipEvent_t after_kernel, int qslot) {
+static int launch_batch(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipStream_t s, hipEvent_t after_setup, hipEvent_t after_kernel, int qslot, const int *skip = nullptr) {
   const Selection &sl = h->sel;
   if (sl.waves > 0 && sl.split) {     // CuCaQP::initSolver, then CuCaQP::solve
     int rc = launch_oc_split(h, io, count, reuse, s, after_setup, qslot);
@@ -223,7 +235,7 @@ static int launch_batch(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipSt
   if (after_kernel) HIPCHK(hipEventRecord(after_kernel, s));
   if (h->m > 0) {
     hipLaunchKernelGGL(mpcqp_validate_kernel, dim3((count + 3) / 4), dim3(256), 0, s, count, h->n, h->m, io.l, io.sl, io.u, io.su, io.x, io.y, io.z,
-                       io.status, io.iters, io.info);
+                       io.status, io.iters, io.info, skip);
     HIPCHK(hipGetLastError());
   }
   if (h->polish) {      // OSQP's polish() behind osqp_solve's loop: on the final status (the validation above included), ahead of anything that reads the outputs
@@ -231,7 +243,7 @@ static int launch_batch(mpcqp_handle *h, DevIO &io, int count, bool reuse, hipSt
     DevPolish po;
     po.q = io.q; po.sq = io.sq; po.x = io.x; po.y = io.y; po.z = io.z; po.status = io.status; po.info = io.info; po.ws = io.ws; po.cscale = io.cscale;
     po.fac = h->pfac + b0 * h->pfac_stride; po.fac_stride = h->pfac_stride; po.pstatus = h->opstatus + b0; po.pinfo = h->opinfo + 4 * b0;
-    po.delta = h->pol_delta; po.refine = h->pol_refine;
+    po.delta = h->pol_delta; po.refine = h->pol_refine; po.skip = skip;
     const bool timed = after_kernel != nullptr;
     if (timed) HIPCHK(hipEventRecord(h->evp0, s));
     if (int rc = mpcqp_polish_launch(h->dp, h->st, po, count, s)) return rc;
@@ -636,7 +648,7 @@ static int solve_reduced(mpcqp_handle *h, hipStream_t s) {
   const bool vectors = h->reuse_next, matrices = h->rescale_next;
   // the presolve overwrites the reduced arrays the previous solve of this handle read: if that one ran on another stream, wait for it
   if (h->solved && h->last_stream != s) { HIPCHK(hipEventRecord(h->ev0r, h->last_stream)); HIPCHK(hipStreamWaitEvent(s, h->ev0r, 0)); }
-  hipLaunchKernelGGL(mpcqp_presolve_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io, vectors ? 1 : 0);
+  hipLaunchKernelGGL(mpcqp_presolve_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io, vectors ? 1 : 0, h->skip);
   HIPCHK(hipGetLastError());
   int rc;
   if (vectors) rc = mpcqp_update_vectors(in, d.qr, d.nr, d.lr, d.mr, d.ur, d.mr, MPCQP_MEM_DEVICE);
@@ -645,7 +657,7 @@ static int solve_reduced(mpcqp_handle *h, hipStream_t s) {
   if (rc) return rc;
   if (h->st.warm_start && h->io.x0 && h->io.y0) {
     if (!h->rx0) return fail(MPCQP_ERR_STATE, "warm start on a reduced handle: settings.warm_start must be set when the handle is created");
-    hipLaunchKernelGGL(mpcqp_red_gather_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io.x0, h->io.y0, h->rx0, h->ry0);
+    hipLaunchKernelGGL(mpcqp_red_gather_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io.x0, h->io.y0, h->rx0, h->ry0, h->skip);
     HIPCHK(hipGetLastError());
     if ((rc = mpcqp_warm_start(in, h->rx0, h->ry0, MPCQP_MEM_DEVICE))) return rc;
   }
@@ -653,8 +665,9 @@ static int solve_reduced(mpcqp_handle *h, hipStream_t s) {
   const bool pol = in->polish && h->opinfo;      // (the inner handle's polish outcome comes back with the objective's constant, like info[0])
   hipLaunchKernelGGL(mpcqp_postsolve_kernel, dim3(h->batch), dim3(256), 0, s, d, h->io, in->ox, in->oy, in->oz, in->ostatus, in->oiters, in->oinfo,
                      pol ? in->opstatus : (const int *)nullptr, pol ? in->opinfo : (const double *)nullptr,
-                     h->ox, h->oy, h->oz, h->ostatus, h->oiters, h->oinfo, h->opstatus, h->opinfo);
+                     h->ox, h->oy, h->oz, h->ostatus, h->oiters, h->oinfo, h->opstatus, h->opinfo, h->skip);
   HIPCHK(hipGetLastError());
+  note_skip_state(h, vectors ? 1 : matrices ? 2 : 0);
   h->last_stream = s; h->solved = true; h->have_factor = h->keep; h->reuse_next = false; h->rescale_next = false;
   return MPCQP_OK;
 }
@@ -713,6 +726,9 @@ int mpcqp_update_matrices(mpcqp_handle *h, const double *P, long sP, const doubl
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
   if (!h->keep || !h->have_factor)
     return fail(MPCQP_ERR_STATE, "mpcqp_update_matrices needs mpcqp_keep_workspace(h, 1) and a completed mpcqp_update + mpcqp_solve before it");
+  if (h->skip_full)
+    return fail(MPCQP_ERR_STATE, "mpcqp_update_matrices: the last full set-up ran under a skip array (mpcqp_set_skip), so the skipped instances hold no scaling "
+                                 "of this handle's data; run mpcqp_update + mpcqp_solve without a skip array first");
   if (!takes_matrix_updates(h->inner ? h->inner : h))
     return fail(MPCQP_ERR_LIMIT, "mpcqp_update_matrices: this handle does not run the two-kernel on-chip form (use mpcqp_update)");
   if (int rc = set_problem_data(h, P, sP, q, sq, A, sA, l, sl, u, su, mem)) return rc;
@@ -759,6 +775,12 @@ int mpcqp_update_vectors(mpcqp_handle *h, const double *q, long sq, const double
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
   if (!h->keep || !h->have_factor)
     return fail(MPCQP_ERR_STATE, "mpcqp_update_vectors needs mpcqp_keep_workspace(h, 1) and a completed mpcqp_update + mpcqp_solve before it");
+  if (h->skip_full)
+    return fail(MPCQP_ERR_STATE, "mpcqp_update_vectors: the last full set-up ran under a skip array (mpcqp_set_skip), so the skipped instances hold no factor "
+                                 "of this handle's matrices; run mpcqp_update + mpcqp_solve without a skip array first");
+  if (h->skip_mat && !(h->rescale_next && !h->rescale_done))
+    return fail(MPCQP_ERR_STATE, "mpcqp_update_vectors: the last mpcqp_update_matrices solve ran under a skip array (mpcqp_set_skip), so the skipped instances' "
+                                 "factors are of older matrices; run an mpcqp_update_matrices or mpcqp_update solve without a skip array first");
   if (!q || (h->m > 0 && (!l || !u))) return fail(MPCQP_ERR_ARG, "null data pointer");
   if (sq < 0 || sl < 0 || su < 0 || (sq && sq < h->n) || (sl && sl < h->m) || (su && su < h->m)) return fail(MPCQP_ERR_ARG, "dimension mismatch: stride shorter than the array");
   HIPCHK(hipSetDevice(h->device));
@@ -791,6 +813,40 @@ int mpcqp_set_rho(mpcqp_handle *h, const double *rho0, int mem) {
   return MPCQP_OK;
 }
 
+int mpcqp_set_skip(mpcqp_handle *h, const int *skip, int mem) {
+  if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+  if (!skip) { h->skip = nullptr; return h->inner ? mpcqp_set_skip(h->inner, nullptr, mem) : MPCQP_OK; }
+  if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
+  HIPCHK(hipSetDevice(h->device));
+  int rc;
+  if (mem == MPCQP_MEM_HOST) {
+    if (!h->dskip) { if ((rc = dalloc(h, &h->dskip, (size_t)h->batch))) return rc; }
+    if (h->solved) HIPCHK(hipStreamSynchronize(h->last_stream));      // (a solve in flight may still read the buffer)
+    HIPCHK(hipMemcpy(h->dskip, skip, (size_t)h->batch * sizeof(int), hipMemcpyHostToDevice));
+    skip = h->dskip;
+  }
+  if (h->inner) {      // the handle that runs reads the same array (this handle's copy of a host array)
+    if ((rc = mpcqp_set_skip(h->inner, skip, MPCQP_MEM_DEVICE))) return rc;
+    h->skip = skip;
+    return MPCQP_OK;
+  }
+  if (!h->skip_list) { if ((rc = dalloc(h, &h->skip_list, (size_t)h->batch))) return rc; }
+  if (!h->ev_guard) HIPCHK(hipEventCreateWithFlags(&h->ev_guard, hipEventDisableTiming));
+  h->skip = skip;
+  return MPCQP_OK;
+}
+
+int mpcqp_debug_skip_list(mpcqp_handle *h, int *list, int mem) {
+  if (!h || !list) return fail(MPCQP_ERR_ARG, "null pointer");
+  if (h->inner) return mpcqp_debug_skip_list(h->inner, list, mem);
+  if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
+  if (!h->solved || !h->skip_listed) return fail(MPCQP_ERR_STATE, "the last solve of this handle ran without a skip array (mpcqp_set_skip), or none has been issued");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->last_stream));
+  HIPCHK(hipMemcpy(list, h->skip_list, (size_t)h->batch * sizeof(int), mem == MPCQP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+  return MPCQP_OK;
+}
+
 int mpcqp_solve(mpcqp_handle *h, void *stream) {
   if (!h) return fail(MPCQP_ERR_ARG, "null handle");
   if (!h->have_data) return fail(MPCQP_ERR_STATE, "Solver not initialized. Call mpcqp_update() first.");
@@ -801,8 +857,16 @@ int mpcqp_solve(mpcqp_handle *h, void *stream) {
   io.reuse = h->rescale_next ? 2 : h->reuse_next ? 1 : 0;
   io.order = (h->lpt && h->order_cur >= 0) ? h->order[h->order_cur] : nullptr;
   if (io.order && h->last_stream != s) HIPCHK(hipStreamWaitEvent(s, h->ev_order, 0));    // the hint was written on another stream
+  if (h->skip) {
+    // the dispatch list of this solve: the hint's order (or the identity) without the skipped instances, then -1 (kernels_util.hpp); the list of the
+    // solve before may still be read on another stream
+    if (h->solved && h->last_stream != s) { HIPCHK(hipEventRecord(h->ev_guard, h->last_stream)); HIPCHK(hipStreamWaitEvent(s, h->ev_guard, 0)); }
+    hipLaunchKernelGGL(mpcqp_skip_list_kernel, dim3(1), dim3(1024), 0, s, h->skip, io.order, h->skip_list, h->batch);
+    HIPCHK(hipGetLastError());
+    io.order = h->skip_list;
+  }
   HIPCHK(hipEventRecord(h->ev0, s));
-  if (int rc = launch_batch(h, io, h->batch, io.reuse != 0, s, h->ev_mid, h->ev1, 0)) return rc;
+  if (int rc = launch_batch(h, io, h->batch, io.reuse != 0, s, h->ev_mid, h->ev1, 0, h->skip)) return rc;
   if (h->lpt && h->batch > 1) {   // order of the next solve from this solve's iteration counts
     const int nxt = h->order_cur == 0 ? 1 : 0;
     hipLaunchKernelGGL(mpcqp_order_kernel, dim3(1), dim3(1024), 0, s, (const int *)h->oiters, h->order[nxt], h->batch, std::max(1, h->st.check_termination));
@@ -810,6 +874,7 @@ int mpcqp_solve(mpcqp_handle *h, void *stream) {
     HIPCHK(hipEventRecord(h->ev_order, s));
     h->order_cur = nxt;
   }
+  note_skip_state(h, io.reuse);
   h->last_stream = s; h->solved = true; h->have_factor = h->keep; h->rescale_done = h->rescale_next;
   return MPCQP_OK;
 }
@@ -834,6 +899,7 @@ int mpcqp_solve_host(mpcqp_handle *h, const double *P, long sP, const double *q,
   if (!q || (h->sel.plan.nnzP_in > 0 && !P) || (h->sel.plan.nnzA_in > 0 && !A) || (h->m > 0 && (!l || !u))) return fail(MPCQP_ERR_ARG, "null data pointer");
   const long wP = h->sel.plan.nnzP_in, wA = h->sel.plan.nnzA_in, n = h->n, m = h->m;
   if (h->inner) return fail(MPCQP_ERR_STATE, "mpcqp_solve_host is not available on a reduced handle");
+  if (h->skip) return fail(MPCQP_ERR_STATE, "mpcqp_solve_host solves the whole batch: clear the skip array first (mpcqp_set_skip(h, NULL, 0))");
   if ((sP && sP != wP) || sq != n || (sA && sA != wA) || (m > 0 && (sl != m || su != m)))
     return fail(MPCQP_ERR_ARG, "dimension mismatch: mpcqp_solve_host takes dense instance-major arrays (stride = width; 0 shares P or A)");
   HIPCHK(hipSetDevice(h->device));
@@ -883,6 +949,7 @@ int mpcqp_solve_host(mpcqp_handle *h, const double *P, long sP, const double *q,
   for (int i = 0; i < ns; i++) HIPCHK(hipStreamSynchronize(h->pipe[i]));
   h->io.P = io.P; h->io.sP = io.sP; h->io.q = io.q; h->io.sq = io.sq; h->io.A = io.A; h->io.sA = io.sA; h->io.l = io.l; h->io.sl = io.sl; h->io.u = io.u; h->io.su = io.su;
   h->have_data = true; h->reuse_next = false; h->rescale_next = false; h->solved = true; h->have_factor = h->keep; h->last_stream = nullptr; h->order_cur = -1;
+  note_skip_state(h, 0);
   return MPCQP_OK;
 }
 

@@ -90,8 +90,9 @@ struct DevRed {
 };
 
 // one workgroup per instance.  vectors_only: P, A values of the reduced pattern are in place already (kept workspace)
-__global__ void __launch_bounds__(256) mpcqp_presolve_kernel(const DevRed rd, const DevIO io, int vectors_only) {
+__global__ void __launch_bounds__(256) mpcqp_presolve_kernel(const DevRed rd, const DevIO io, int vectors_only, const int *__restrict__ skip) {
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (skip && skip[b] != 0) return;      // (mpcqp_set_skip: the whole workgroup; the instance's reduced data keep their bits, the inner handle skips it too)
   const double *P = io.P + (long)b * io.sP, *A = io.A + (long)b * io.sA, *q = io.q + (long)b * io.sq, *l = io.l + (long)b * io.sl, *u = io.u + (long)b * io.su;
   double *xf = rd.xfix + (long)b * rd.nfix;
   __shared__ int bad;
@@ -133,8 +134,9 @@ __global__ void __launch_bounds__(256) mpcqp_presolve_kernel(const DevRed rd, co
 // variables contribute,  q_f'x_f + 1/2 x_f'P_ff x_f,  summed per thread over its eliminated variables and then over the threads in a fixed tree.
 __global__ void __launch_bounds__(256) mpcqp_postsolve_kernel(const DevRed rd, const DevIO io, const double *xr, const double *yr, const double *zr, const int *str,
                                                               const int *itr, const double *infr, const int *pstr, const double *pinr, double *x, double *y,
-                                                              double *z, int *status, int *iters, double *info, int *pst, double *pin) {
+                                                              double *z, int *status, int *iters, double *info, int *pst, double *pin, const int *__restrict__ skip) {
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (skip && skip[b] != 0) return;
   const double *P = io.P + (long)b * io.sP, *A = io.A + (long)b * io.sA, *q = io.q + (long)b * io.sq, *l = io.l + (long)b * io.sl;
   const double *xf = rd.xfix + (long)b * rd.nfix;
   const bool refused = rd.bad[b] != 0;
@@ -185,8 +187,9 @@ __global__ void __launch_bounds__(256) mpcqp_postsolve_kernel(const DevRed rd, c
 }
 
 // warm start of a reduced handle: the caller's x0 [n], y0 [m] restricted to the free variables / kept rows
-__global__ void __launch_bounds__(256) mpcqp_red_gather_kernel(const DevRed rd, const double *x0, const double *y0, double *xr, double *yr) {
+__global__ void __launch_bounds__(256) mpcqp_red_gather_kernel(const DevRed rd, const double *x0, const double *y0, double *xr, double *yr, const int *__restrict__ skip) {
   const int b = blockIdx.x, tid = threadIdx.x;
+  if (skip && skip[b] != 0) return;
   for (int jr = tid; jr < rd.nr; jr += 256) xr[(long)b * rd.nr + jr] = x0[(long)b * rd.n + rd.free_var[jr]];
   for (int ir = tid; ir < rd.mr; ir += 256) yr[(long)b * rd.mr + ir] = y0[(long)b * rd.m + rd.kept_row[ir]];
 }

@@ -38,6 +38,8 @@ class CuCaQP:
         self._result = None
         self._start = None
         self._rho0 = None
+        self._skip = None
+        self._skip_used = False                # some solve of this object may have run under a skip array
         self._kept = False
         self._polish = self._polish_applied = False
         self._vectors_dirty = self._matrices_dirty = self._solved_once = False
@@ -93,6 +95,16 @@ class CuCaQP:
         """extension: per-instance starting rho for the next solves (a kept OSQP workspace carries its adapted rho over);
         None returns to the configured rho"""
         self._rho0 = None if rho0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(rho0, np.float64), (self.batch,)))
+
+    def setSkip(self, skip):
+        """extension: leave instances out of the following solves (mpcqp_set_skip): skip [batch], nonzero = skipped; None solves the whole batch
+        again.  A skipped instance's rows of getSolution() / getDual() / getStatus() ... are those of its last solve on this handle.
+        Kept workspace: after a set-up under a skip array the skipped instances hold no factor or scaling of the current matrices, so the library refuses
+        the vectors-only and the keep-scaling update (MPCQP_ERR_STATE, include/mpcqp.h); a solve() after update*() then runs the full set-up instead."""
+        self._skip = None if skip is None else np.ascontiguousarray(skip, dtype=np.int32).reshape(self.batch)
+        self._skip_used = self._skip_used or self._skip is not None
+        if self._qp is not None:
+            self._qp.set_skip(self._skip)
 
     def setKeepScaling(self, keep):
         """extension (off by default): a solve() after updateHessianMatrix / updateLinearConstraintsMatrix keeps the scaling D, E, c of the last
@@ -289,6 +301,8 @@ class CuCaQP:
             if self._start is not None:
                 self._qp.warm_start(self._start[0], self._start[1])
             self._qp.set_rho(self._rho0)
+            if self._skip is not None:                     # (a cleared array was cleared on the handle by setSkip; a new handle has none)
+                self._qp.set_skip(self._skip)
         except (_lib.MpcqpError, ValueError) as e:
             return _err("Failed to initialize solver. (%s)" % e)
         self.isInitialized_ = True
@@ -302,14 +316,20 @@ class CuCaQP:
         try:
             data = (self._P[2], self.gradient, self._A[2], self.lowerBound, self.upperBound)
             if self._vectors_dirty and self._kept and self._solved_once and not self._matrices_dirty:
-                self._qp.update_vectors(self.gradient, self.lowerBound, self.upperBound)
+                try:
+                    self._qp.update_vectors(self.gradient, self.lowerBound, self.upperBound)
+                except _lib.MpcqpError as e:
+                    if e.code != _lib.ERR_STATE or not self._skip_used:
+                        raise
+                    self._qp.update(*data)                  # (an earlier set-up ran under a skip array: the full set-up repairs what it solves)
             elif self._matrices_dirty and self._keep_scaling and self._kept and self._solved_once and not self._no_matrix_updates:
                 try:
                     self._qp.update_matrices(*data)
                 except _lib.MpcqpError as e:
-                    if e.code != _lib.ERR_LIMIT:
-                        raise
-                    self._no_matrix_updates = True          # (this handle's kernel family has no such entry: the full set-up from now on)
+                    if e.code == _lib.ERR_LIMIT:
+                        self._no_matrix_updates = True      # (this handle's kernel family has no such entry: the full set-up from now on)
+                    elif e.code != _lib.ERR_STATE or not self._skip_used:
+                        raise                               # (ERR_STATE behind a skip array: an earlier set-up ran under one -- the full set-up this time)
                     self._qp.update(*data)
             elif self._vectors_dirty or self._matrices_dirty:
                 self._qp.update(*data)

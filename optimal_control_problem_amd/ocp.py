@@ -15,7 +15,7 @@ batched local-system evaluator (models.StageOCP) that plays the role of the CasA
 import numpy as np
 
 from . import models
-from .sqp import DeviceSQPOptimizationSolver, SQPOptimizationSolver
+from .sqp import SKIP_NEEDS_KKT, DeviceSQPOptimizationSolver, SQPOptimizationSolver
 
 
 # ---------------------------------------------------------------------------------------------------- expressions
@@ -316,6 +316,14 @@ class OptimalControlProblem:
         if not (kt is None or kt is False or (isinstance(kt, (int, float)) and not isinstance(kt, bool)) or isinstance(kt, dict)):
             raise ValueError("SQP_settings.kkt_tol: expected a number or a map of stat, feas, compl")
         self.kktTol_ = None if kkt_tolerances(kt) is None else (dict(kt) if isinstance(kt, dict) else float(kt))
+        # extension (opt-in, no such key in the reference's YAML): SQP_settings.skip_converged_qps -- true = an instance that kkt_tol froze is left out
+        # of the later QP launches of the call (sqp.py).  Needs kkt_tol; checked here.
+        sk = s["SQP_settings"].get("skip_converged_qps")
+        if not (sk is None or isinstance(sk, bool)):
+            raise ValueError("SQP_settings.skip_converged_qps: expected true or false")
+        if sk and self.kktTol_ is None:
+            raise ValueError(SKIP_NEEDS_KKT.replace('options["skip_converged_qps"]', "SQP_settings.skip_converged_qps").replace('options["kkt_tol"]', "SQP_settings.kkt_tol"))
+        self.skipConvergedQPs_ = bool(sk)
         method = str(s["solve_method"])
         if method not in self.SOLVER_TYPES:
             raise ValueError("Unknown solver type: " + method)                       # :43-45
@@ -449,6 +457,8 @@ class OptimalControlProblem:
             options["line_search"] = self.lineSearch_        # to whichever of the three solvers below is built
         if self.kktTol_ is not None:
             options["kkt_tol"] = self.kktTol_                # to whichever of the three solvers below is built
+        if self.skipConvergedQPs_:
+            options["skip_converged_qps"] = True
         if self.exactHessian_ is not None:
             if not self.generalPath_:
                 raise ValueError("SQP_settings.exact_hessian: this problem is a stage pattern, and the facade does not build stage models with the "

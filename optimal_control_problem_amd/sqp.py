@@ -35,6 +35,13 @@ of the call: its x is not stepped, its lam not updated, later checks skip it.  W
 `converged` [batch], `converged_at` [batch] (the iteration index, -1 if never), `kkt_history` (one [batch, 4] = stat, feas, compl, scale per check,
 frozen rows keeping the values they converged with) and `iterations_done` (the QPs solved) report on the last call; kkt(arg) checks the returned
 point on demand.  Either of sqp_tol and kkt_tol stops the loop.
+Opt-in as well, with kkt_tol: options["skip_converged_qps"] = True leaves the frozen instances out of the QP launches too (mpcqp_set_skip with the
+verdicts as they are): from iteration 1 on a frozen instance's QP is neither set up nor iterated.  x, f, converged, converged_at and
+kkt_history are bit for bit those of the loop without the option -- a frozen instance is not stepped either way, and the active instances' QPs are
+the same QPs.  What differs is what the call leaves behind: admm_iterations[i][b] is 0 for an instance skipped in iteration i, and dw, y, status, iters and
+info -- rho included -- (host loop: the rows of last_qp_info) of a frozen instance are those of its last solved QP, not of a QP at the frozen point.  A LATER
+call that carries such state (warm_start_admm, carry_rho, keep_scaling, ClosedLoopMPC's hand-over, kkt(arg)) therefore starts from other values than after a call
+without the option, and agrees with it to the QPs' tolerance, not bit for bit.
 A stage OCP with a Gauss-Newton frame cost (models.StageOCP.rcost) needs no option: its local system carries 2 J'J and both loops run as
 they are; options["convexify"] and options["exact_hessian"] are refused for it with the model's reason.
 
@@ -48,6 +55,17 @@ import numpy as np
 from . import _lib
 from .cucaqp import CuCaQP
 from .kkt import kkt_tolerances
+
+
+SKIP_NEEDS_KKT = ('options["skip_converged_qps"] leaves out the QPs of the instances that options["kkt_tol"] has frozen: without kkt_tol no '
+                  "instance is ever frozen, so there is nothing it could skip -- set kkt_tol as well")
+
+
+def _skip_option(options, kkt_tol):
+    on = bool(options.get("skip_converged_qps", False))
+    if on and kkt_tol is None:
+        raise ValueError(SKIP_NEEDS_KKT)
+    return on
 
 
 def _line_search_options(value):
@@ -150,6 +168,7 @@ class SQPOptimizationSolver:
         self.result_ = {"x": np.zeros((self.batch, nvar)), "f": np.zeros(self.batch)}
         self.timings = {"local_system_ms": 0.0, "qp_ms": 0.0}
         self.last_qp_info = None
+        self._last_solution = None
         # extension (BASELINE config 4): warm-start each QP's ADMM from the previous SQP
         # iteration's solution.  Off by default: the reference cold-starts every QP (CuCaQP.cpp:271-288).
         self.warm_start_admm = bool(options.get("warm_start_admm", False))
@@ -161,6 +180,9 @@ class SQPOptimizationSolver:
         if self.kkt_tol is not None and not hasattr(nlp, "kkt_residuals"):
             raise ValueError("kkt_tol needs a model that states its optimality residuals (kkt_residuals)")
         self.converged = np.zeros(self.batch, bool); self.converged_at = np.full(self.batch, -1, np.int64); self.kkt_history = []
+        # opt-in, with kkt_tol: a frozen instance's QP is skipped (qpSolver_.setSkip where the backend has it) and its rows of the solution and of
+        # last_qp_info stay those of its last solved QP (module docstring)
+        self.skip_converged_qps = _skip_option(options, self.kkt_tol)
         # extension, as in the device loop: an instance whose QP returned no point keeps its iterate (the reference adds the NaN solution, :171-177)
         self.skip_failed_steps = bool(options.get("skip_failed_steps", False))
         self.line_search = _line_search_options(options.get("line_search"))
@@ -209,6 +231,9 @@ class SQPOptimizationSolver:
         frozen = np.zeros(B, bool)                       # kkt_tol: the instances that converged earlier in this call
         self.converged = frozen; self.converged_at = np.full(B, -1, np.int64); self.kkt_history = []
         self.iterations_done = 0
+        skipping = self.skip_converged_qps
+        if skipping and hasattr(self.qpSolver_, "setSkip"):
+            self.qpSolver_.setSkip(None)
         for i in range(self.stepNum_):
             t0 = time.perf_counter()
             localSystem = self.getLocalSystem(arg)
@@ -249,6 +274,9 @@ class SQPOptimizationSolver:
                     self.qpSolver_.setPrimalDualStart((1.0 - self.alpha_) * info["x"], info["y"])
                     if self.carry_rho and hasattr(self.qpSolver_, "setRhoStart"):
                         self.qpSolver_.setRhoStart(info["rho"])
+            if skipping and hasattr(self.qpSolver_, "setSkip"):
+                self.qpSolver_.setSkip(frozen.astype(np.int32) if frozen.any() else None)
+            prev_solution, prev_info = (self._last_solution, self.last_qp_info) if skipping and frozen.any() else (None, None)
             self.qpSolver_.initSolver()
             self.qpSolver_.solve()
             t2 = time.perf_counter()
@@ -256,8 +284,16 @@ class SQPOptimizationSolver:
             self.timings["qp_ms"] += (t2 - t1) * 1e3
             solution = np.asarray(self.qpSolver_.getSolutionAsDM(), float).reshape(B, -1)
             self.last_qp_info = getattr(self.qpSolver_, "getInfo", lambda: None)()
+            if prev_solution is not None:                # skip_converged_qps: a frozen instance reports its last solved QP, whatever the backend left there
+                solution = np.where(frozen[:, None], prev_solution, solution)
+                if self.last_qp_info is not None and prev_info is not None:
+                    keep = lambda new, old: np.where(frozen.reshape((B,) + (1,) * (np.ndim(new) - 1)), old, new)
+                    self.last_qp_info = {k: keep(v, prev_info[k]) if k in prev_info and np.ndim(v) >= 1 and np.shape(v)[0] == B else v
+                                         for k, v in self.last_qp_info.items()}
+            self._last_solution = solution
             if self.last_qp_info is not None and "iters" in self.last_qp_info:
-                self.admm_iterations.append(np.asarray(self.last_qp_info["iters"]).copy())
+                it = np.asarray(self.last_qp_info["iters"]).copy()
+                self.admm_iterations.append(np.where(frozen, 0, it).astype(it.dtype) if prev_solution is not None else it)
             oldRes = self.result_["x"].copy()
             if self.line_search is not None:
                 info = self.last_qp_info
@@ -363,6 +399,9 @@ class DeviceSQPOptimizationSolver:
         # the QP of every iteration but the first, one scalar back to the host (module docstring)
         self.kkt_tol = kkt_tolerances(options.get("kkt_tol"))
         self.converged = None; self.converged_at = None; self.kkt_history = []
+        # extension (opt-in, with kkt_tol): the verdict tensor is the QP handle's skip array from iteration 1 on (mpcqp_set_skip, borrowed: the check
+        # writes it on the stream the solve reads it on) -- a frozen instance's QP is neither set up nor iterated (module docstring)
+        self.skip_converged_qps = _skip_option(options, self.kkt_tol)
         # extension: OSQP's `polishing` on every QP of the loop (mpcqp_set_polish); the reference leaves it off (:80-85), and so does the default
         self.polish_qp = bool(options.get("polish_qp", False))
         # extension (opt-in): the QP handle comes from mpcqp_create_presolved -- every singleton row of A with l = u in the first local system (the
@@ -500,6 +539,9 @@ class DeviceSQPOptimizationSolver:
             self.converged_at = torch.full((self.batch,), -1, dtype=torch.int32, device=self.dev)
             self.converged = self._kkt_conv.bool()
         self.iterations_done = 0
+        skipping = self.skip_converged_qps
+        if skipping and self.qp is not None:
+            self.qp.set_skip(None)                       # iteration 0 solves the whole batch: nothing is frozen yet
         for i in range(self.stepNum_):
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
             if kkt and i >= 1:
@@ -523,6 +565,8 @@ class DeviceSQPOptimizationSolver:
             if self.qp is None:                          # presolve_fixed_rows: the fixed rows are read off this first system's bounds
                 torch.cuda.current_stream(self.dev).synchronize()
                 self._create_qp((self.ls["l"], self.ls["u"]))
+                if skipping:
+                    self.qp.set_skip(None)
             if self.constant_matrices and self._kept:
                 self.qp.update_vectors(self.ls["q"], self.ls["l"], self.ls["u"])
             elif self.keep_scaling and self._scaled:
@@ -552,6 +596,8 @@ class DeviceSQPOptimizationSolver:
                     self.dw.zero_(); self.y.zero_()
                     self.qp.set_rho(None)
                 self.qp.warm_start(self.dw, self.y)
+            if skipping and i >= 1:
+                self.qp.set_skip(self._kkt_conv)         # the check above has written it on this stream
             self.qp.solve(stream)
             self.qp.get_device(x=self.dw, y=self.y, status=self.status, iters=self.iters, info=self.info)
             self._have_start = True
@@ -574,7 +620,7 @@ class DeviceSQPOptimizationSolver:
                 got = (got & ~self.converged if kkt else got).unsqueeze(1)
                 a = self.alpha_taken.unsqueeze(1) if self.line_search is not None else self.alpha_
                 self.lam.copy_(torch.where(got, self.lam + a * (self.y - self.lam), self.lam))
-            self.admm_iterations.append(self.iters.clone())
+            self.admm_iterations.append(torch.where(self.converged, torch.zeros_like(self.iters), self.iters) if skipping and masked else self.iters.clone())
             self.iterations_done = i + 1
             self.step_max = step
             if self.verbose_:
