@@ -470,6 +470,39 @@ typedef struct mpcqp_stage_advance_args {
   int tail;                            /* MPCQP_TAIL_*                                               */
 } mpcqp_stage_advance_args;
 int mpcqp_stage_advance(mpcqp_stage *s, int batch, const mpcqp_stage_advance_args *a, void *stream);
+/* A dynamically feasible trajectory from a first frame and a sequence of inputs, one kernel for the batch (opt-in: the reference starts its SQP loop
+ * at x = 0, SQPOptimizationSolver.cpp:88-91, and has no such step).  Linearised about a trajectory with s_{k+1} = F(s_k, u_k) the dynamics rows of
+ * the local system are satisfied by dx = 0, so the first QP can only be infeasible through the boxes.  Per instance b, with
+ * X_k = [s_k; u_k] the frames, f = nx + nu, and clip(v, lo, hi) = (v < lo ? lo : v), then (v > hi ? hi : v), elementwise against the same entries of
+ * lbx / ubx (the identity without the pair; a NaN passes through):
+ *   first frame  X_0 = clip(x_in[0:f]): a first frame pinned through lbx = ubx comes out as pinned, bit for bit
+ *   inputs       u_k = clip(u_in_k) for k >= 1, u_in_k being x_in's own input of frame k (MPCQP_ROLLOUT_INPUTS_ITERATE) or u_0
+ *                (MPCQP_ROLLOUT_INPUTS_HOLD); the states of x_in's frames k >= 1 are not read
+ *   states       s_{k+1} = F(s_k, u_k), k = 0 .. N - 2, by the handle's own discrete map under the instance's stored model parameter row
+ *                (MPCQP_PARAMS_MODEL) where one is set, as the rollout tail of mpcqp_stage_advance; stage data and references take no part; states
+ *                are not clipped
+ *   divergence   step k fails when an entry of s_k, u_k or F(s_k, u_k) is not finite: diverged[b] = the first such k, and every later state
+ *                holds s_k (the inputs are still written); -1 when no step fails.  No state is written that F did not produce from finite data,
+ *                but for a non-finite X_0 the caller handed in, which is held and reported as diverged[b] = 0
+ *   box_viol[b]  max over all nvar entries of max(lbx - x_out, x_out - ubx, 0): 0 without the pair, an infinite bound contributes 0; with
+ *                lbx <= ubx only the states of the frames k >= 1 can contribute
+ *   frozen       an instance with frozen[b] != 0 is neither read nor written: its rows of x_out, diverged and box_viol keep what they held
+ * One thread per instance, one writer per element, no atomics: bitwise repeatable, independent of the batch size and of the instance's position, and
+ * the same in place (x_out == x_in) and out of place.  All pointers are device memory.  Asynchronous on `stream`; nothing is allocated, so a
+ * captured graph replays it.  MPCQP_ERR_ARG for a null s, a, x_in or x_out, only one of lbx / ubx, an unknown `inputs`, batch < 1 or a batch larger
+ * than the stored parameter rows; MPCQP_ERR_LIMIT for a generated library from before this entry (it does not export mpcqp_user_rollout;
+ * regenerate it). */
+#define MPCQP_ROLLOUT_INPUTS_ITERATE 0   /* u_k = the inputs of x_in's frame k                      */
+#define MPCQP_ROLLOUT_INPUTS_HOLD    1   /* u_k = u_0 for every k                                   */
+typedef struct mpcqp_stage_rollout_args {
+  const double *x_in;  double *x_out;    /* [batch * nvar]; x_out may be x_in (in place)             */
+  const double *lbx, *ubx;               /* [batch * nvar], optional pair: the box to project onto   */
+  const int *frozen;                     /* [batch], optional: nonzero = neither read nor written    */
+  int *diverged;                         /* [batch], optional                                        */
+  double *box_viol;                      /* [batch], optional                                        */
+  int inputs;                            /* MPCQP_ROLLOUT_INPUTS_*                                   */
+} mpcqp_stage_rollout_args;
+int mpcqp_stage_rollout(mpcqp_stage *s, int batch, const mpcqp_stage_rollout_args *a, void *stream);
 /* Per-instance step length by an l1-merit backtracking search, one kernel for the batch (opt-in; replaces one mpcqp_stage_step + mpcqp_stage_merit
  * pair).  The reference takes result.x += alpha * solution[pSize:] with one alpha for every iteration (SQPOptimizationSolver.cpp:171-177: no
  * line search, no merit function); this entry departs from those lines.  Per instance b, with dx = dw[np:] and ok = (status == NULL or status[b] is

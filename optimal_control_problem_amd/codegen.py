@@ -1004,6 +1004,16 @@ int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_lines
 %(params)s%(link_cost)s%(sdata)s%(convexify)s%(exact)s%(residual)s}
 '''
 
+# the launcher of mpcqp_stage_rollout (one kernel instance for both kinds of reference: F reads none), a block of its own that library_source puts
+# behind the translation unit of device_source: the text of device_source stays, byte for byte, what it was before this entry.  A library without
+# the export -- every one generated before this entry, and library_source(tape, rollout=False) for the tests of that case -- answers MPCQP_ERR_LIMIT there
+_DEVICE_ROLLOUT_TMPL = '''
+// the dynamically feasible start (mpcqp_stage_rollout)
+extern "C" int mpcqp_user_rollout(const StageDev *sd, int batch, const mpcqp_stage_rollout_args *a, const StageRows *r, void *stream) {
+  return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_rollout<SmUser>(*sd, batch, *a, (hipStream_t)stream, pp...); });
+}
+'''
+
 # a model with exact_hessian = True only: 1 and the structure of the constraint curvature over [s; u] (row-major f^2 bytes), and the launcher of
 # mpcqp_stage_lagrangian (slots: the handle's table of the curvature's slots; w: the convexification tables and scratch, used when a->mode != 0).
 # A library without the exports takes no constraint curvature
@@ -1258,7 +1268,7 @@ def _build(src_text, suffix, cmd_prefix):
 
 
 def device_source(tape):
-    """the translation unit of a stage library.  Traced with per_frame_reference: SmUser::pref, the PF = true kernel instances only, and the
+    """the translation unit of a stage library but for the launcher library_source appends.  Traced with per_frame_reference: SmUser::pref, the PF = true kernel instances only, and the
     export mpcqp_user_pref() by which mpcqp_stage_create_tracking / _create_user tell the two kinds apart; else the text it always was"""
     pf = getattr(tape, "pref", False)
     convexify = bool(getattr(tape, "convexify", False))
@@ -1271,10 +1281,17 @@ def device_source(tape):
                                residual=_DEVICE_RESIDUAL_TMPL if getattr(tape, "residual", None) else "")
 
 
-def build_device_library(tape):
-    """gfx950 shared library for mpcqp_stage_create_user / _create_tracking (hipcc cross-compiles without a GPU); cached by content"""
+def library_source(tape, rollout=True):
+    """what build_device_library compiles: device_source(tape) and, behind it, the launcher mpcqp_user_rollout.  rollout=False (tests only) leaves
+    the launcher and its kernel out: the text of a library generated before mpcqp_stage_rollout"""
+    return device_source(tape) + (_DEVICE_ROLLOUT_TMPL if rollout else "")
+
+
+def build_device_library(tape, rollout=True):
+    """gfx950 shared library for mpcqp_stage_create_user / _create_tracking (hipcc cross-compiles without a GPU); cached by content.
+    rollout=False (tests only): without the launcher of mpcqp_stage_rollout, which then answers MPCQP_ERR_LIMIT."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    return _build(device_source(tape), "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
+    return _build(library_source(tape, rollout=rollout), "dev", [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950"])
 
 
 def host_source(tape):

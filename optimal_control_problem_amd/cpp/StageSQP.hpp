@@ -12,7 +12,8 @@
 // setKktTolerance(stat, feas, compl) adds the per-instance stop on the NLP's optimality residuals (mpcqp_stage_kkt): in every iteration but
 // the first of a call, between the evaluation and the QP, the residuals are taken with the multipliers of the previous QP; an instance that meets the
 // tolerances is frozen for the rest of the call (its x is not stepped), and the loop ends before the QP once every instance is; converged(),
-// convergedAt() and kktResiduals() report on the last call.  Header-only; needs the HIP runtime for the device buffers (hipMalloc / hipMemcpy).
+// convergedAt() and kktResiduals() report on the last call.  Opt-in as well: setInitialGuessMode(GUESS_ROLLOUT / GUESS_RESHOOT) makes a fresh iterate
+// dynamically feasible before the first evaluation (mpcqp_stage_rollout).  Header-only; needs the HIP runtime for the device buffers (hipMalloc / hipMemcpy).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -49,6 +50,7 @@ class StageSQP {
     if (status_) (void)hipFree(status_);
     if (conv_) (void)hipFree(conv_);
     if (masked_) (void)hipFree(masked_);
+    if (rollDiv_) (void)hipFree(rollDiv_);
     if (qp_) mpcqp_destroy(qp_);
     if (ocp_) mpcqp_stage_destroy(ocp_);
   }
@@ -89,7 +91,19 @@ class StageSQP {
     need(x.size(), (size_t)batch_ * nvar(), "x");
     hip(hipMemcpy(x_, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice));
     if (mu_) hip(hipMemset(mu_, 0, (size_t)batch_ * sizeof(double)));
+    fresh_ = true;
   }
+  // option initial_guess (default GUESS_NONE: the stored iterate as it is): a fresh iterate -- after construction or setInitialGuess -- is made
+  // dynamically feasible by one mpcqp_stage_rollout in place, in the first getOptimalSolution, with that call's lbx / ubx:
+  // GUESS_ROLLOUT holds u_0, GUESS_RESHOOT keeps the iterate's own inputs.  Later calls continue from the stored iterate.
+  enum { GUESS_NONE = 0, GUESS_ROLLOUT = 1, GUESS_RESHOOT = 2 };
+  void setInitialGuessMode(int mode) {
+    if (mode != GUESS_NONE && mode != GUESS_ROLLOUT && mode != GUESS_RESHOOT) throw std::invalid_argument("mode must be GUESS_NONE, GUESS_ROLLOUT or GUESS_RESHOOT");
+    guessMode_ = mode;
+    if (mode != GUESS_NONE && !rollViol_) { rollViol_ = dalloc(batch_); hip(hipMalloc(&rollDiv_, (size_t)batch_ * sizeof(int))); }
+  }
+  const std::vector<int> &rolloutDiverged() const { return rolloutDiverged_; }         // per instance: the first failed step, -1 if none (empty: no rollout ran)
+  const std::vector<double> &rolloutBoxViolation() const { return rolloutBoxViol_; }  // per instance: max violation of lbx / ubx by the rolled-out states
 
   // option polish_qp (default off, as the reference leaves OSQP's `polishing` off, :80-85): every QP of the loop is polished (mpcqp_set_polish)
   void setPolishQP(bool on) { check(mpcqp_set_polish(qp_, on ? 1 : 0, 0.0, -1), "mpcqp_set_polish"); }
@@ -146,6 +160,16 @@ class StageSQP {
     up(lbx_, arg.lbx); up(ubx_, arg.ubx); up(lbg_, arg.lbg); up(ubg_, arg.ubg); up(p_, arg.p);
     if (kkt_) { hip(hipMemset(conv_, 0, B * sizeof(int))); converged_.assign(B, 0); convergedAt_.assign(B, -1); checked_ = false; }
     iterationsDone_ = 0;
+    if (guessMode_ != GUESS_NONE && fresh_) {
+      mpcqp_stage_rollout_args r = {};
+      r.x_in = x_; r.x_out = x_; r.lbx = lbx_; r.ubx = ubx_; r.diverged = rollDiv_; r.box_viol = rollViol_;
+      r.inputs = guessMode_ == GUESS_ROLLOUT ? MPCQP_ROLLOUT_INPUTS_HOLD : MPCQP_ROLLOUT_INPUTS_ITERATE;
+      check(mpcqp_stage_rollout(ocp_, batch_, &r, nullptr), "mpcqp_stage_rollout");
+      rolloutDiverged_.resize(B); rolloutBoxViol_.resize(B);
+      hip(hipMemcpy(rolloutDiverged_.data(), rollDiv_, B * sizeof(int), hipMemcpyDeviceToHost));
+      hip(hipMemcpy(rolloutBoxViol_.data(), rollViol_, B * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    fresh_ = false;
     for (int i = 0; i < stepNum_; i++) {
       check(mpcqp_stage_eval(ocp_, batch_, p_, x_, lbx_, ubx_, lbg_, ubg_, dP_, dq_, dA_, dl_, du_, nullptr), "mpcqp_stage_eval");
       if (kkt_ && i >= 1) {                                         // the verdicts of the earlier checks are the frozen mask of this one
@@ -239,6 +263,9 @@ class StageSQP {
   double *y_ = nullptr, *mu_ = nullptr, *alphaOut_ = nullptr; int *status_ = nullptr;
   std::vector<double> alphaTaken_;
   bool skipConverged_ = false;
+  int guessMode_ = GUESS_NONE; bool fresh_ = true;               // initial_guess: applied once to a fresh iterate
+  double *rollViol_ = nullptr; int *rollDiv_ = nullptr;
+  std::vector<int> rolloutDiverged_; std::vector<double> rolloutBoxViol_;
   bool kkt_ = false, checked_ = false; double kktTol_[3] = {0.0, 0.0, 0.0};   // optimality residuals: all tolerances 0 = off
   double *kktRes_ = nullptr; int *conv_ = nullptr, *masked_ = nullptr;
   std::vector<int> converged_, convergedAt_, hostStatus_;

@@ -27,6 +27,7 @@ struct StageUserLib {
   int (*merit)(const StageDev *, int, const StageMeritArgs *, const StageRows *, void *) = nullptr;
   int (*advance)(const StageDev *, int, const mpcqp_stage_advance_args *, const StageRows *, void *) = nullptr;
   int (*linesearch)(const StageDev *, int, const mpcqp_stage_linesearch_args *, const StageRows *, void *) = nullptr;
+  int (*rollout)(const StageDev *, int, const mpcqp_stage_rollout_args *, const StageRows *, void *) = nullptr;
   int (*convexify)(const StageDev *, int, const mpcqp_stage_convexify_args *, const StageCvxBuf *, const StageRows *, void *) = nullptr;
   int (*lagrangian)(const StageDev *, int, const mpcqp_stage_lagrangian_args *, const int *, const StageCvxBuf *, const StageRows *, void *) = nullptr;
 };
@@ -36,6 +37,7 @@ static StageUserLib stage_user_lib(void *lib) {
   stage_sym(lib, "mpcqp_user_eval", u.eval); stage_sym(lib, "mpcqp_user_merit", u.merit);
   stage_sym(lib, "mpcqp_user_advance", u.advance); stage_sym(lib, "mpcqp_user_linesearch", u.linesearch);
   stage_sym(lib, "mpcqp_user_convexify", u.convexify); stage_sym(lib, "mpcqp_user_lagrangian", u.lagrangian);
+  stage_sym(lib, "mpcqp_user_rollout", u.rollout);
   return u;
 }
 
@@ -44,6 +46,7 @@ hipError_t mpcqp_launch_eval_pp(const StageDev &sd, int batch, const StageEvalAr
 hipError_t mpcqp_launch_merit_pp(const StageDev &sd, int batch, const StageMeritArgs &a, hipStream_t st, StageTheta th);
 hipError_t mpcqp_launch_advance_pp(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st, StageTheta th);
 hipError_t mpcqp_launch_linesearch_pp(const StageDev &sd, int batch, const mpcqp_stage_linesearch_args &a, hipStream_t st, StageTheta th);
+hipError_t mpcqp_launch_rollout_pp(const StageDev &sd, int batch, const mpcqp_stage_rollout_args &a, hipStream_t st, StageTheta th);
 
 struct mpcqp_stage {
   mpcqp_stage_desc desc;
@@ -602,6 +605,24 @@ int mpcqp_stage_linesearch(mpcqp_stage *s, int batch, const mpcqp_stage_linesear
       [&](auto t) { using T = decltype(t); return stage_launch_linesearch<typename T::M, T::PF>(sd, batch, *a, st); },
       [&](StageTheta th) { return mpcqp_launch_linesearch_pp(sd, batch, *a, st, th); },
       [&](const StageRows &r) { return stage_hipchk(s->user.linesearch(&sd, batch, a, &r, stream)); });
+}
+
+int mpcqp_stage_rollout(mpcqp_stage *s, int batch, const mpcqp_stage_rollout_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (!a->x_in || !a->x_out) return mpcqp_set_error(MPCQP_ERR_ARG, "x_in and x_out are required");
+  if ((a->lbx == nullptr) != (a->ubx == nullptr)) return mpcqp_set_error(MPCQP_ERR_ARG, "give both lbx and ubx or neither");
+  if (a->inputs != MPCQP_ROLLOUT_INPUTS_ITERATE && a->inputs != MPCQP_ROLLOUT_INPUTS_HOLD)
+    return mpcqp_set_error(MPCQP_ERR_ARG, "inputs must be MPCQP_ROLLOUT_INPUTS_ITERATE or MPCQP_ROLLOUT_INPUTS_HOLD");
+  if (s->sd.model == MPCQP_MODEL_USER && !s->user.rollout)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library does not export mpcqp_user_rollout (generated before this entry); regenerate it");
+  const StageDev &sd = s->sd;
+  hipStream_t st = (hipStream_t)stream;
+  return stage_launch(s, batch, STAGE_ROWS_THETA,
+      [&](auto t) { using T = decltype(t); return stage_launch_rollout<typename T::M>(sd, batch, *a, st); },
+      [&](StageTheta th) { return mpcqp_launch_rollout_pp(sd, batch, *a, st, th); },
+      [&](const StageRows &r) { return stage_hipchk(s->user.rollout(&sd, batch, a, &r, stream)); });
 }
 
 int mpcqp_stage_has_convexify(const mpcqp_stage *s) { return s && s->convexify ? 1 : 0; }

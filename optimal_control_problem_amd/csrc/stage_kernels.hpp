@@ -595,6 +595,75 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
   }
 }
 
+// A dynamically feasible trajectory (mpcqp_stage_rollout): X_0 and the inputs projected onto the box, the states by the chain s_{k+1} = F(s_k, u_k).
+// The chain of N - 1 dependent runs of F<double> is serial, so the parallelism is across instances: one thread per instance, 64-thread workgroups
+// (a batch of 8192 is 128 workgroups).  A thread reads frame k's input before it writes frame k and touches its own instance only, so the launch
+// may run in place; the state lives in registers between the frames.  No PF twin: F reads no reference.  No LDS, no atomics, one writer per element.
+__device__ __forceinline__ double stage_clip(double v, const double *lo, const double *hi, long i) {
+  if (lo) { const double l = lo[i], h = hi[i]; v = v < l ? l : v; v = v > h ? h : v; }
+  return v;
+}
+__device__ __forceinline__ double stage_box_viol(double acc, double v, const double *lo, const double *hi, long i) {
+  return lo ? fmax(acc, fmax(lo[i] - v, v - hi[i])) : acc;
+}
+template <class M, class... PP>
+__global__ void __launch_bounds__(64) stage_rollout_kernel(StageDev sd, int batch, mpcqp_stage_rollout_args a, PP... pp) {
+  constexpr int nx = M::nx, nu = M::nu, f = nx + nu;
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= batch) return;
+  if (a.frozen && a.frozen[b] != 0) return;
+  const int N = sd.N;
+  const long base = (long)b * sd.nvar;
+  const double *xi = a.x_in + base;
+  double *xo = a.x_out + base;
+  const double *lo = a.lbx ? a.lbx + base : nullptr, *hi = a.lbx ? a.ubx + base : nullptr;
+  const bool hold = a.inputs == MPCQP_ROLLOUT_INPUTS_HOLD;
+  constexpr int NT = sm_ntheta<M>::value > 0 ? sm_ntheta<M>::value : 1;
+  double th[NT];
+  {
+    const double *row = stage_theta(pp...).model;      // (null without a PP element: the shared values, which stay in scalar registers)
+#pragma unroll
+    for (int i = 0; i < NT; i++) th[i] = row ? row[(long)b * SM_NPAR + i] : sd.par[i];
+  }
+  double s[nx], uu[nu], u0[nu], sn[nx];
+  double viol = 0.0;
+  bool fin = true;
+#pragma unroll
+  for (int i = 0; i < nx; i++) { s[i] = stage_clip(xi[i], lo, hi, i); fin = fin && isfinite(s[i]); }
+#pragma unroll
+  for (int i = 0; i < nu; i++) { uu[i] = u0[i] = stage_clip(xi[nx + i], lo, hi, nx + i); }
+#pragma unroll
+  for (int i = 0; i < nx; i++) { xo[i] = s[i]; viol = stage_box_viol(viol, s[i], lo, hi, i); }
+#pragma unroll
+  for (int i = 0; i < nu; i++) { xo[nx + i] = uu[i]; viol = stage_box_viol(viol, uu[i], lo, hi, nx + i); }
+  int div = -1;
+  for (int k = 0; k < N - 1; k++) {
+    if (div < 0) {
+      bool ok = fin;
+#pragma unroll
+      for (int i = 0; i < nu; i++) ok = ok && isfinite(uu[i]);
+      M::template F<double>(th, sd.dt, s, uu, sn);
+#pragma unroll
+      for (int i = 0; i < nx; i++) ok = ok && isfinite(sn[i]);
+      if (ok) {
+#pragma unroll
+        for (int i = 0; i < nx; i++) s[i] = sn[i];
+      } else {
+        div = k;
+      }
+    }
+    const long o = (long)(k + 1) * f;
+#pragma unroll
+    for (int i = 0; i < nu; i++) uu[i] = stage_clip(hold ? u0[i] : xi[o + nx + i], lo, hi, o + nx + i);
+#pragma unroll
+    for (int i = 0; i < nx; i++) { xo[o + i] = s[i]; viol = stage_box_viol(viol, s[i], lo, hi, o + i); }
+#pragma unroll
+    for (int i = 0; i < nu; i++) { xo[o + nx + i] = uu[i]; viol = stage_box_viol(viol, uu[i], lo, hi, o + nx + i); }
+  }
+  if (a.diverged) a.diverged[b] = div;
+  if (a.box_viol) a.box_viol[b] = viol;
+}
+
 // per-candidate accumulators of the line search: the candidate is known at run time only, the registers are addressed statically (an unrolled
 // select written as a compile-time recursion: a loop over j, even one that is unrolled later, is turned back into a dynamically indexed array
 // by the optimiser, and that array goes to scratch)
@@ -1010,6 +1079,12 @@ inline hipError_t stage_launch_merit(const StageDev &sd, int batch, const StageM
 template <class M, bool PF = false, class... PP>
 inline hipError_t stage_launch_advance(const StageDev &sd, int batch, const mpcqp_stage_advance_args &a, hipStream_t st, PP... pp) {
   stage_advance_kernel<M, PF, PP...><<<(unsigned)((batch + 3) / 4), 256, 0, st>>>(sd, batch, a, pp...);
+  return hipGetLastError();
+}
+// (one thread per instance in 64-thread workgroups; the same instance serves both kinds of reference)
+template <class M, class... PP>
+inline hipError_t stage_launch_rollout(const StageDev &sd, int batch, const mpcqp_stage_rollout_args &a, hipStream_t st, PP... pp) {
+  stage_rollout_kernel<M, PP...><<<(unsigned)((batch + 63) / 64), 64, 0, st>>>(sd, batch, a, pp...);
   return hipGetLastError();
 }
 template <class M, bool PF = false, class... PP>

@@ -983,6 +983,62 @@ class StageOCP:
                 out["stage_cost"] = c
         return out
 
+    # -- the dynamically feasible start (include/mpcqp.h, mpcqp_stage_rollout; csrc/stage_kernels.hpp stage_rollout_kernel) ----------
+    ROLLOUT_INPUTS = ("iterate", "hold")
+
+    def rollout(self, x, lbx=None, ubx=None, inputs="iterate", frozen=None):
+        """Host statement of mpcqp_stage_rollout: x [B, nvar] -> dict with `x` (the first frame and the inputs clipped to lbx / ubx, the states
+        s_{k+1} = F(s_k, u_k)), `diverged` [B] (the first step k at which s_k, u_k or F(s_k, u_k) is not finite -- every later state holds s_k --
+        or -1) and `box_viol` [B] (max over all entries of max(lbx - x, x - ubx, 0)).  inputs: "iterate" keeps x's own inputs, "hold" repeats
+        u_0; the states of x's frames k >= 1 are not read.  clip is (v < lo ? lo : v), then (v > hi ? hi : v): a NaN passes through.  frozen [B]:
+        an instance with a nonzero entry keeps its row of x and reports -1 and 0 (the device leaves its entries as they were).  The map uses
+        the per-instance model rows of set_instance_params where they are set."""
+        if inputs not in self.ROLLOUT_INPUTS:
+            raise ValueError("inputs must be 'iterate' or 'hold'")
+        if (lbx is None) != (ubx is None):
+            raise ValueError("give both lbx and ubx or neither")
+        x = np.asarray(x, float)
+        B, N, nx, f = x.shape[0], self.N, self.nx, self.f
+        if self._theta_rows is not None:
+            sl = lambda v, i: None if v is None else np.asarray(v, float).reshape(B, -1)[i]
+            one = self._each_instance(self._theta_rows, B, lambda i: self.rollout(x[i], sl(lbx, i), sl(ubx, i), inputs,
+                                                                                  None if frozen is None else np.asarray(frozen).reshape(B)[i]))
+            return {k: np.concatenate([o[k] for o in one]) for k in one[0]}
+        X = x.reshape(B, N, f)
+        box = lbx is not None
+        if box:
+            Lo = np.asarray(lbx, float).reshape(B, N, f); Hi = np.asarray(ubx, float).reshape(B, N, f)
+
+        def clip(v, k, cols):
+            if not box:
+                return v
+            lo, hi = Lo[:, k, cols], Hi[:, k, cols]
+            v = np.where(v < lo, lo, v)
+            return np.where(v > hi, hi, v)
+
+        fr, st, un = slice(0, f), slice(0, nx), slice(nx, f)
+        out = np.empty_like(X)
+        out[:, 0] = clip(X[:, 0], 0, fr)
+        s, u0 = out[:, 0, :nx].copy(), out[:, 0, nx:].copy()
+        div = np.full(B, -1, np.int64)
+        with np.errstate(all="ignore"):
+            for k in range(N - 1):
+                u = out[:, k, nx:]
+                sn = np.asarray(self.F(s, u), float)
+                bad = (div < 0) & ~(np.isfinite(s).all(axis=1) & np.isfinite(u).all(axis=1) & np.isfinite(sn).all(axis=1))
+                div = np.where(bad, k, div)
+                s = np.where((div < 0)[:, None], sn, s)
+                out[:, k + 1, :nx] = s
+                out[:, k + 1, nx:] = clip(u0 if inputs == "hold" else X[:, k + 1, nx:], k + 1, un)
+            viol = np.zeros(B)
+            if box:
+                viol = np.fmax.reduce(np.fmax(Lo - out, out - Hi).reshape(B, -1), axis=1, initial=0.0)
+        out = out.reshape(B, -1)
+        if frozen is not None:
+            fz = np.asarray(frozen).reshape(B) != 0
+            out = np.where(fz[:, None], x, out); div = np.where(fz, -1, div); viol = np.where(fz, 0.0, viol)
+        return {"x": out, "diverged": div.astype(np.int32), "box_viol": viol}
+
     # -- the per-instance merit line search (include/mpcqp.h, mpcqp_stage_linesearch; csrc/stage_kernels.hpp stage_linesearch_kernel) ----------
     LINE_SEARCH_DEFAULTS = {"candidates": 4, "beta": 0.5, "c1": 1e-4, "mu_min": 1.0, "mu_factor": 1.1}
 

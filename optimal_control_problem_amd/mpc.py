@@ -40,18 +40,30 @@ class ClosedLoopMPC:
         self.ticks = 0
         self._ready = False
         self._has_data = False
+        self.rollout_diverged = None; self.rollout_box_viol = None
 
     def reset(self, frame0, reference=None, x0=None):
         """frame0 [B, f] (or [f]): the measured state and the input being applied, pinned as the first frame.  reference: p, [B, nx] -- or
-        [B, N nx] / [B, N, nx] for a per_frame_reference model -- zero when omitted.  x0: the iterate to start from; zero like the reference's."""
+        [B, N nx] / [B, N, nx] for a per_frame_reference model -- zero when omitted.  x0: the iterate to start from; zero like the reference's.
+        x0 = "rollout": the trajectory of the pinned first frame under its input held (one mpcqp_stage_rollout on the bounds just written, so the
+        first tick linearises about a dynamically feasible trajectory); x0 = "reshoot": the same with zero inputs clipped to the box.
+        rollout_diverged / rollout_box_viol (device tensors) report the outcome."""
         import torch
         m, B = self.model, self.batch
+        shoot = {"rollout": "hold", "reshoot": "iterate"}.get(x0) if isinstance(x0, str) else None
+        if isinstance(x0, str) and shoot is None:
+            raise ValueError("x0: expected an iterate, None, 'rollout' or 'reshoot'")
+        if shoot is not None:
+            x0 = None
         f0 = np.broadcast_to(np.asarray(frame0, float).reshape(-1, m.f), (B, m.f))
         for t, v in zip((self.lbx, self.ubx, self.lbg, self.ubg), m.stacked_bounds(f0)):
             t.copy_(torch.as_tensor(v, dtype=torch.float64))
         ref = np.zeros((B, m.np)) if reference is None else np.broadcast_to(np.asarray(reference, float).reshape(-1, m.np), (B, m.np))
         self.p.copy_(torch.as_tensor(np.array(ref), dtype=torch.float64))
         self.sol.setInitialGuess(np.zeros(self.ev.nvar) if x0 is None else x0)
+        if shoot is not None:      # the bounds are written: the first frame of the zero iterate is clipped onto the pinned one
+            r = self.ev.rollout(self.sol.x, lbx=self.lbx, ubx=self.ubx, inputs=shoot, stream=torch.cuda.current_stream(self.dev).cuda_stream)
+            self.rollout_diverged, self.rollout_box_viol = r["diverged"], r["box_viol"]
         self.ticks = 0
         self._ready = True
 

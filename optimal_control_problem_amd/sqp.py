@@ -42,6 +42,11 @@ the same QPs.  What differs is what the call leaves behind: admm_iterations[i][b
 info -- rho included -- (host loop: the rows of last_qp_info) of a frozen instance are those of its last solved QP, not of a QP at the frozen point.  A LATER
 call that carries such state (warm_start_admm, carry_rho, keep_scaling, ClosedLoopMPC's hand-over, kkt(arg)) therefore starts from other values than after a call
 without the option, and agrees with it to the QPs' tolerance, not bit for bit.
+Opt-in as well: options["initial_guess"] = "rollout" or "reshoot" makes a fresh iterate dynamically feasible before the first evaluation (models.StageOCP.rollout
+states the rule, mpcqp_stage_rollout runs it on the device): the first frame and the inputs are clipped to the call's lbx / ubx and the states
+become s_{k+1} = F(s_k, u_k), with u_k = u_0 ("rollout") or the stored iterate's own inputs ("reshoot": for a caller whose guess holds inputs only).  Applied once
+to a fresh iterate -- in the first getOptimalSolution after construction or after setInitialGuess; later calls continue from the stored iterate.
+`rollout_diverged` and `rollout_box_viol` report the outcome; an instance whose chain left the finite numbers takes the held trajectory.  Stage OCPs only.
 A stage OCP with a Gauss-Newton frame cost (models.StageOCP.rcost) needs no option: its local system carries 2 J'J and both loops run as
 they are; options["convexify"] and options["exact_hessian"] are refused for it with the model's reason.
 
@@ -66,6 +71,23 @@ def _skip_option(options, kkt_tol):
     if on and kkt_tol is None:
         raise ValueError(SKIP_NEEDS_KKT)
     return on
+
+
+ROLLOUT_NEEDS_DYNAMICS = ('options["initial_guess"] shoots the start through the stage dynamics s_{k+1} = F(s_k, u_k): the general path (a '
+                          "general_nlp.GeneralNLP, an evaluator= of mpcqp_nlp_*) has no notion of dynamics, frames or inputs, so there is nothing "
+                          "to roll out -- build the start yourself and hand it to setInitialGuess")
+
+
+def _initial_guess_option(value, model, evaluator=None):
+    """options["initial_guess"]: None = the stored iterate as it is; "rollout" = hold u_0; "reshoot" = keep the guess's inputs.  Returns None or the
+    `inputs` of models.StageOCP.rollout / mpcqp_stage_rollout."""
+    if value is None:
+        return None
+    if value not in ("rollout", "reshoot"):
+        raise ValueError("initial_guess: expected None, 'rollout' or 'reshoot'")
+    if (evaluator is not None and not hasattr(evaluator, "rollout")) or _is_general(model) or not hasattr(model, "rollout"):
+        raise ValueError(ROLLOUT_NEEDS_DYNAMICS)
+    return "hold" if value == "rollout" else "iterate"
 
 
 def _line_search_options(value):
@@ -203,6 +225,11 @@ class SQPOptimizationSolver:
         self.iterations_done = 0
         self.step_max = None
         self.admm_iterations = []
+        # opt-in: a fresh iterate (construction, setInitialGuess) is shot through the dynamics once, in the first getOptimalSolution, with that
+        # call's lbx / ubx (models.StageOCP.rollout); rollout_diverged / rollout_box_viol report the outcome
+        self.initial_guess = _initial_guess_option(options.get("initial_guess"), nlp)
+        self._fresh = True
+        self.rollout_diverged = None; self.rollout_box_viol = None
 
     def setVerbose(self, verbose):
         self.verbose_ = bool(verbose)
@@ -215,6 +242,7 @@ class SQPOptimizationSolver:
             self.lam = np.zeros_like(self.lam)
         self.result_["x"] = np.array(np.broadcast_to(np.asarray(x, float).reshape(-1, self.result_["x"].shape[1]), self.result_["x"].shape))
         self.last_qp_info = None
+        self._fresh = True
 
     def getLocalSystem(self, arg):
         B = self.batch
@@ -234,6 +262,12 @@ class SQPOptimizationSolver:
         skipping = self.skip_converged_qps
         if skipping and hasattr(self.qpSolver_, "setSkip"):
             self.qpSolver_.setSkip(None)
+        if self.initial_guess is not None and self._fresh:
+            nvar = self.model.n - pSize
+            box = [np.broadcast_to(np.asarray(arg[k], float).reshape(-1, nvar), (B, nvar)) for k in ("lbx", "ubx")]
+            r = self.model.rollout(self.result_["x"], box[0], box[1], inputs=self.initial_guess)
+            self.result_["x"] = r["x"]; self.rollout_diverged = r["diverged"]; self.rollout_box_viol = r["box_viol"]
+        self._fresh = False
         for i in range(self.stepNum_):
             t0 = time.perf_counter()
             localSystem = self.getLocalSystem(arg)
@@ -438,6 +472,11 @@ class DeviceSQPOptimizationSolver:
         self.exact_hessian = _exact_hessian_option(options.get("exact_hessian"), nlp)
         self._nlp_mode = _nlp_hessian_mode(options.get("exact_hessian"), nlp) if evaluator is not None else None
         self.alpha_taken = None; self.accepted = None
+        # extension (opt-in): a fresh iterate (construction, setInitialGuess) is shot through the dynamics once, by one mpcqp_stage_rollout in place
+        # in the first getOptimalSolution, with that call's lbx / ubx; without the option not a launch more
+        self.initial_guess = _initial_guess_option(options.get("initial_guess"), nlp, evaluator)
+        self._fresh = True
+        self.rollout_diverged = None; self.rollout_box_viol = None
         self.iterations_done = 0
         self.step_max = None
         self._kept = False
@@ -492,6 +531,7 @@ class DeviceSQPOptimizationSolver:
         """extension: the reference ignores arg["x0"] and starts from zero (:88-91); this overwrites the stored iterate"""
         self.x.copy_(self._dev(x, self.ev.nvar))
         self._have_start = False
+        self._fresh = True
         if self.line_search is not None:
             self.mu.zero_()
         if self.exact_hessian:
@@ -542,6 +582,12 @@ class DeviceSQPOptimizationSolver:
         skipping = self.skip_converged_qps
         if skipping and self.qp is not None:
             self.qp.set_skip(None)                       # iteration 0 solves the whole batch: nothing is frozen yet
+        if self.initial_guess is not None and self._fresh:
+            if self.rollout_diverged is None:
+                self.rollout_diverged = torch.full((self.batch,), -1, dtype=torch.int32, device=self.dev)
+                self.rollout_box_viol = torch.zeros(self.batch, dtype=torch.float64, device=self.dev)
+            ev.rollout(self.x, lbx=lbx, ubx=ubx, inputs=self.initial_guess, diverged=self.rollout_diverged, box_viol=self.rollout_box_viol, stream=stream)
+        self._fresh = False
         for i in range(self.stepNum_):
             ev.eval(p, self.x, lbx, ubx, lbg, ubg, out=self.ls, stream=stream)
             if kkt and i >= 1:

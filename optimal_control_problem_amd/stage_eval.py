@@ -25,6 +25,10 @@ class AdvanceArgs(C.Structure):
 
 
 TAILS = {"repeat": 0, "rollout": 1}
+
+
+RolloutArgs = _lib.RolloutArgs            # mpcqp_stage_rollout_args
+ROLLOUT_INPUTS = {"iterate": _lib.ROLLOUT_INPUTS_ITERATE, "hold": _lib.ROLLOUT_INPUTS_HOLD}
 NPAR = 8                                  # MPCQP_STAGE_NPAR: the width of a parameter row
 PARAMS_MODEL, PARAMS_PLANT = 0, 1         # MPCQP_PARAMS_*
 
@@ -76,6 +80,7 @@ def _bind(L):
     L.mpcqp_stage_merit.argtypes = [vp, C.c_int, dp, dp, dp, dp, vp]
     L.mpcqp_stage_step.argtypes = [vp, C.c_int, C.c_double, dp, dp, dp, vp, vp]
     L.mpcqp_stage_advance.argtypes = [vp, C.c_int, C.POINTER(AdvanceArgs), vp]
+    L.mpcqp_stage_rollout.argtypes = [vp, C.c_int, C.POINTER(RolloutArgs), vp]
     L.mpcqp_stage_linesearch.argtypes = [vp, C.c_int, C.POINTER(LineSearchArgs), vp]
     L.mpcqp_stage_has_convexify.argtypes = [vp]
     L.mpcqp_stage_convexify.argtypes = [vp, C.c_int, C.POINTER(ConvexifyArgs), vp]
@@ -348,6 +353,34 @@ class StageEvaluator:
         if status is not None:
             a.status = _check_int32(status, B, "status")
         _lib.check(_lib.lib().mpcqp_stage_advance(self._h, B, C.byref(a), stream))
+
+    def rollout(self, x_in, x_out=None, lbx=None, ubx=None, inputs="iterate", frozen=None, diverged=None, box_viol=None, stream=None):
+        """a dynamically feasible trajectory in one kernel (mpcqp_stage_rollout; models.StageOCP.rollout is its host statement): the first frame and
+        the inputs of x_in projected onto the box lbx / ubx (both or neither), the states by s_{k+1} = F(s_k, u_k) under the stored model rows.
+        inputs: "iterate" keeps x_in's own inputs, "hold" repeats u_0.  x_out None: in place.  frozen (int32 [B], optional): an instance with a
+        nonzero entry is neither read nor written.  Returns {"x", "diverged" (int32 [B]), "box_viol" [B]}, device tensors (`diverged`, `box_viol`:
+        tensors to write into).  Arrays are contiguous float64 CUDA tensors."""
+        import torch
+        if inputs not in ROLLOUT_INPUTS:
+            raise ValueError("inputs must be 'iterate' or 'hold'")
+        B = x_in.shape[0]
+        if x_out is None:
+            x_out = x_in
+        if diverged is None:
+            diverged = torch.full((B,), -1, dtype=torch.int32, device=x_in.device)
+        if box_viol is None:
+            box_viol = torch.zeros(B, dtype=torch.float64, device=x_in.device)
+        a = RolloutArgs()
+        a.inputs = ROLLOUT_INPUTS[inputs]
+        for name, t in (("x_in", x_in), ("x_out", x_out), ("lbx", lbx), ("ubx", ubx)):
+            if t is not None:
+                setattr(a, name, _check(t, (B, self.nvar), name))
+        a.box_viol = _check(box_viol, (B,), "box_viol")
+        a.diverged = _check_int32(diverged, B, "diverged")
+        if frozen is not None:
+            a.frozen = _check_int32(frozen, B, "frozen")
+        _lib.check(_lib.lib().mpcqp_stage_rollout(self._h, B, C.byref(a), stream))
+        return {"x": x_out, "diverged": diverged, "box_viol": box_viol}
 
     def line_search(self, p, x, lbx, ubx, q, dw, y, status=None, mu=None, alpha0=1.0, candidates=4, beta=0.5, c1=1e-4, mu_min=1.0, mu_factor=1.1,
                     out=None, phi=None, stream=None):
