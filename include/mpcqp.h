@@ -399,6 +399,15 @@ int mpcqp_stage_set_instance_params(mpcqp_stage *s, int which, int batch, const 
 int mpcqp_stage_data_count(const mpcqp_stage *s);
 int mpcqp_stage_set_stage_data(mpcqp_stage *s, int batch, const double *d, int mem);
 int mpcqp_stage_shift_data(mpcqp_stage *s, int batch, const double *d_new /* [batch * nsd], device, may be NULL */, void *stream);
+/* Transition data: the stage data in the dynamics (opt-in).  A library generated from a model that also sets transition_data reads
+ * d[0..k-1] inside F / cdyn, kfun and llink as well: a step length per frame (a non-uniform time grid), a previewed disturbance, a schedule.  The
+ * functions of the transition k -> k + 1 take row k of the instance.  mpcqp_stage_eval, _merit, _linesearch, _rollout and _lagrangian use the rows of
+ * the stored set; mpcqp_stage_advance takes row 0 for the plant step and row horizon - 1 for the rollout tail, both as they stand before
+ * mpcqp_stage_shift_data, which stays a separate call after it.  The rows stay data: pattern and sizes are those of the same model with the numbers
+ * written as constants.
+ * mpcqp_stage_has_transition_data: 1 for such a library, 0 for every other handle (the zoo, a library generated without the flag or before this
+ * entry) and for a null handle. */
+int mpcqp_stage_has_transition_data(const mpcqp_stage *s);
 /* dims[8] = {nx, nu, np, n, m, nnz(P), nnz(A), horizon * (nx + nu)} */
 int mpcqp_stage_dims(const mpcqp_stage *s, int *dims8);
 /* 1 when the evaluator was generated with its own stage cost (mpcqp_stage_create_user above), 0 for diagonal tracking weights */

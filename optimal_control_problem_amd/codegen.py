@@ -439,11 +439,18 @@ class _bound_theta:
 
 def _trace_fn(fn, nx, nu, n_out, what, ntheta=0, model=None, nsd=0):
     """ntheta > 0: that many extra tape inputs behind [s; u], bound to model.theta while fn runs (the plant parameters: par[i] in the emitted code).
-    nsd > 0 (hfun): that many extra inputs behind [s; u], bound to model.sdata (the frame's stage data: d[i] in the emitted code)"""
+    nsd > 0 (hfun; F of a model with transition_data): that many extra inputs behind [s; u] (behind the parameters, where both are given), bound to
+    model.sdata (the frame's stage data: d[i] in the emitted code)"""
     tape = Tape(nx + nu + ntheta + nsd)
     s = TV(tape, [TS(tape, i) for i in range(nx)])
     u = TV(tape, [TS(tape, nx + i) for i in range(nu)])
-    if nsd:
+    if nsd and ntheta:      # (F of a model with transition_data: the parameter row, then the frame's data row)
+        with _bound_theta(model, TV(tape, [TS(tape, nx + nu + i) for i in range(ntheta)])), \
+                _bound_theta(model, TV(tape, [TS(tape, nx + nu + ntheta + i) for i in range(nsd)]), "sdata"):
+            out = fn(s, u)
+        tape.in_names = [("s", nx), ("u", nu), ("par", ntheta), ("d", nsd)]
+        tape.plain_from = nx + nu
+    elif nsd:
         with _bound_theta(model, TV(tape, [TS(tape, nx + nu + i) for i in range(nsd)]), "sdata"):
             out = fn(s, u)
         tape.in_names = [("s", nx), ("u", nu), ("d", nsd)]
@@ -574,12 +581,14 @@ GN_REFUSES_EXACT = ("exact_hessian does not combine with a Gauss-Newton cost (rc
                     "cost's own is not covered")
 
 
-def _trace_link(kfun, nx, nu, nk):
-    """kfun(s, u, s_next, u_next) -> [..., nk] on tracers over the inputs [s; u; s_next; u_next]"""
-    tape = Tape(2 * (nx + nu))
+def _trace_link(kfun, nx, nu, nk, nsd=0, model=None):
+    """kfun(s, u, s_next, u_next) -> [..., nk] on tracers over the inputs [s; u; s_next; u_next].  nsd > 0 (a model with transition_data): that many
+    extra inputs behind them, bound to model.sdata while kfun runs (the data row of the pair's first frame), without a derivative"""
+    tape = Tape(2 * (nx + nu) + nsd)
     mk = lambda a, b: TV(tape, [TS(tape, i) for i in range(a, b)])
     f = nx + nu
-    out = kfun(mk(0, nx), mk(nx, f), mk(f, f + nx), mk(f + nx, 2 * f))
+    with _bound_theta(model if nsd else None, mk(2 * f, 2 * f + nsd), "sdata"):
+        out = kfun(mk(0, nx), mk(nx, f), mk(f, f + nx), mk(f + nx, 2 * f))
     if isinstance(out, TS):
         out = TV(tape, [out])
     if isinstance(out, (list, tuple)):
@@ -589,15 +598,21 @@ def _trace_link(kfun, nx, nu, nk):
     tape.outputs = [TS._lift(tape, v).idx for v in out.items]
     tape.nx, tape.nu = nx, nu
     tape.in_names = [("s", nx), ("u", nu), ("sn", nx), ("un", nu)]
+    if nsd:
+        tape.in_names.append(("d", nsd))
+        tape.plain_from = 2 * f
     return tape
 
 
-def trace_link_cost(llink, nx, nu):
-    """link cost llink(s, u, s_next, u_next) -> scalar on tracers; returns (value tape, gradient tape) over the inputs [s; u; s_next; u_next]"""
-    tape = Tape(2 * (nx + nu))
+def trace_link_cost(llink, nx, nu, nsd=0, model=None):
+    """link cost llink(s, u, s_next, u_next) -> scalar on tracers; returns (value tape, gradient tape) over the inputs [s; u; s_next; u_next].
+    nsd > 0 (a model with transition_data): that many extra inputs behind them, bound to model.sdata while llink runs (the data row of the pair's
+    first frame); the gradient keeps the [s; u; s_next; u_next] block only"""
+    tape = Tape(2 * (nx + nu) + nsd)
     mk = lambda a, b: TV(tape, [TS(tape, i) for i in range(a, b)])
     f = nx + nu
-    out = llink(mk(0, nx), mk(nx, f), mk(f, f + nx), mk(f + nx, 2 * f))
+    with _bound_theta(model if nsd else None, mk(2 * f, 2 * f + nsd), "sdata"):
+        out = llink(mk(0, nx), mk(nx, f), mk(f, f + nx), mk(f + nx, 2 * f))
     if isinstance(out, TV) and len(out) == 1:
         out = out.items[0]
     if isinstance(out, (int, float, np.integer, np.floating)):
@@ -608,20 +623,23 @@ def trace_link_cost(llink, nx, nu):
     tape.nx, tape.nu = nx, nu
     tape.in_names = [("s", nx), ("u", nu), ("sn", nx), ("un", nu)]
     g = gradient_tape(tape)
+    if nsd:
+        g.outputs = g.outputs[:2 * f]
+        tape.in_names.append(("d", nsd))
+        tape.plain_from = g.plain_from = 2 * f
     g.in_names = tape.in_names
     return tape, g
 
 
-def _contracted_gradient(fn, nx, nu, n_out, mult, what, model=None, attr=None, nattr=0, attr_name=None):
+def _contracted_gradient(fn, nx, nu, n_out, mult, what, model=None, ntheta=0, nsd=0):
     """gradient over [s; u] of the scalar mult' fn(s, u), the multipliers `mult` (n_out of them) being extra tape inputs without a derivative, like
-    theta and sdata: inputs [s; u; par (nattr, attr = "theta")?; mult; d (nattr, attr = "sdata")?] -> outputs [f]"""
+    theta and sdata: inputs [s; u; par (ntheta)?; mult; d (nsd)?] -> outputs [f]"""
     f = nx + nu
-    lead = nattr if attr == "theta" else 0
-    tape = Tape(f + nattr + n_out)
+    tape = Tape(f + ntheta + n_out + nsd)
     mk = lambda a, b: TV(tape, [TS(tape, i) for i in range(a, b)])
-    m0 = f + lead
-    d0 = f if attr == "theta" else m0 + n_out
-    with _bound_theta(model if nattr else None, mk(d0, d0 + nattr), attr or "theta"):
+    m0 = f + ntheta
+    d0 = m0 + n_out
+    with _bound_theta(model if ntheta else None, mk(f, f + ntheta)), _bound_theta(model if nsd else None, mk(d0, d0 + nsd), "sdata"):
         out = fn(mk(0, nx), mk(nx, f))
     if isinstance(out, TS):
         out = TV(tape, [out])
@@ -636,40 +654,48 @@ def _contracted_gradient(fn, nx, nu, n_out, mult, what, model=None, attr=None, n
     tape.nx, tape.nu = nx, nu
     g = gradient_tape(tape)
     g.outputs = g.outputs[:f]
-    g.in_names = [("s", nx), ("u", nu)] + ([("par", nattr)] if lead else []) + [(mult, n_out)] + ([(attr_name, nattr)] if nattr and not lead else [])
+    g.in_names = [("s", nx), ("u", nu)] + ([("par", ntheta)] if ntheta else []) + [(mult, n_out)] + ([("d", nsd)] if nsd else [])
     g.plain_from = f
     return g
 
 
-def trace_curvature(F, nx, nu, hfun=None, nh=0, ntheta=0, nsd=0, model=None):
+def trace_curvature(F, nx, nu, hfun=None, nh=0, ntheta=0, nsd=0, model=None, transition_data=False):
     """The constraint curvature of the exact Lagrangian Hessian (models.StageOCP.exact_hessian): the gradient tapes over [s; u] of the
     contracted scalars lam' F(s, u) (inputs [s; u; par; lam]) and mu' hfun(s, u) (inputs [s; u; mu; d]) and the structure of their Hessians, valid
-    for any multipliers.  Returns dict(FG, HG (None without a path constraint), mask [f, f])."""
+    for any multipliers.  transition_data: F reads the frame's stage data too (inputs [s; u; par; lam; d]).
+    Returns dict(FG, HG (None without a path constraint), mask [f, f])."""
     guarded = model if ntheta else None
     unread = model if nsd else None
-    with _bound_theta(unread, _SdataGuard("F"), "sdata"):
-        FG = _contracted_gradient(F, nx, nu, nx, "lam", "F must return the next state", model, "theta" if ntheta else None, ntheta)
+    if transition_data and nsd:
+        FG = _contracted_gradient(F, nx, nu, nx, "lam", "F must return the next state", model, ntheta, nsd)
+    else:
+        with _bound_theta(unread, _SdataGuard("F"), "sdata"):
+            FG = _contracted_gradient(F, nx, nu, nx, "lam", "F must return the next state", model, ntheta)
     mask = hessian_mask(FG)
     HG = None
     if hfun is not None and nh:
         with _bound_theta(guarded, _ThetaGuard("hfun")):
-            HG = _contracted_gradient(hfun, nx, nu, nh, "mu", "hfun must return the path-constraint values", model, "sdata" if nsd else None, nsd, "d")
+            HG = _contracted_gradient(hfun, nx, nu, nh, "mu", "hfun must return the path-constraint values", model, 0, nsd)
         mask = mask | hessian_mask(HG)
     return dict(FG=FG, HG=HG, mask=mask)
 
 
 def link_is_linear(link):
     """no output of the link-constraint tape has a second derivative (a rate limit and the like)"""
+    nv = 2 * (link.nx + link.nu)      # (stage data behind the two frames carry no derivative)
     for o in link.outputs:
         t = link.clone()
         t.outputs = [o]
-        if hessian_mask(gradient_tape(t)).any():
+        g = gradient_tape(t)
+        g.outputs = g.outputs[:nv]
+        if hessian_mask(g).any():
             return False
     return True
 
 
 def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=None, kfun=None, nk=0, k_lo=None, k_hi=None, per_frame_reference=False,
-          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None, convexify=False, exact_hessian=False, rcost=None, rterm=None):
+          ntheta=0, theta0=None, model=None, llink=None, nsd=0, sdata0=None, convexify=False, exact_hessian=False, rcost=None, rterm=None,
+          transition_data=False):
     """Run F (and the optional per-stage path constraint hfun) once on tracers.  F(s, u) -> s_next with s [..., nx],
     u [..., nu] (the contract of models.StageOCP.F); hfun(s, u) -> [..., nh] with bounds h_lo <= hfun <= h_hi.
     lcost(s, u, r) -> scalar: a general stage cost summed over the frames (r = the reference parameter, size nx), replacing
@@ -687,7 +713,7 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     nsd = k (<= 8), sdata0 = the k default values: the model reads its stage data as self.sdata[i] inside hfun, lcost and lterm (a cost that does
     is a method of the model); while those are traced, self.sdata holds k extra tape inputs, emitted as d[i] -- data of the launch
     (mpcqp_stage_set_stage_data gives every frame of every instance its own row), without a derivative: the gradient and the Hessian's structure
-    are over [s; u; r] as before.  F / cdyn, kfun and llink take none: reading self.sdata there raises a ValueError.
+    are over [s; u; r] as before.  F / cdyn, kfun and llink take none: reading self.sdata there raises a ValueError (unless transition_data, below).
     convexify (models.StageOCP.convexify; needs lcost): the cost's mask becomes its component closure (closed_mask) and the library exports
     mpcqp_user_convexify, the launcher of mpcqp_stage_convexify.  Without it the library is the text it always was.
     exact_hessian (models.StageOCP.exact_hessian; needs lcost, whose pattern has the off-diagonal slots): the functors FG and HG, the gradients over
@@ -698,9 +724,16 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     f = sum_k |rcost(s_k, u_k, r)|^2 in place of lcost / lterm.  tape.cost holds the value and gradient tapes derived from the residual tape
     (residual_tapes) and the structure of J'J as the mask; tape.residual the residual tapes and their transposed-Jacobian tapes, which the functor
     carries as R, RT (RTm, RTT: the terminal frame's).  The rules of lcost on theta and sdata hold; convexify and exact_hessian are refused.
-    Without it the library is the text it always was."""
+    Without it the library is the text it always was.
+    transition_data (models.StageOCP.transition_data; needs nsd): F / cdyn, kfun and llink read self.sdata[i] as well -- the row of the
+    transition's first frame, k for the step k -> k + 1 -- instead of being refused: F is traced with nsd inputs behind [s; u; theta], kfun and llink
+    with nsd inputs behind their two frames, the gradient tapes keep their outputs over the variables.  The functor declares tdata = 1 and every
+    transition function it has takes d.  Without it the library is the text it always was."""
     ntheta = int(ntheta)
     nsd = int(nsd)
+    tdata = bool(transition_data)
+    if tdata and not nsd:
+        raise ValueError("transition_data needs stage data (nsd > 0): it lets F / cdyn, kfun and llink read self.sdata")
     if rcost is not None and (lcost is not None or lterm is not None):
         raise ValueError("rcost excludes lcost / lterm: the frame cost is either a scalar with its exact Hessian or a residual with the Gauss-Newton one")
     if rterm is not None and rcost is None:
@@ -728,9 +761,14 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
         sdata0 = np.asarray(model.sdata if sdata0 is None else sdata0, float).ravel()
         if sdata0.size != nsd:
             raise ValueError("sdata0 must hold nsd = %d values" % nsd)
-    unread = model if nsd else None           # whose sdata F, kfun and llink may not read
-    with _bound_theta(unread, _SdataGuard("F"), "sdata"):
-        tape = _trace_fn(F, nx, nu, nx, "F must return the next state", ntheta, model)
+    unread = model if nsd and not tdata else None           # whose sdata F, kfun and llink may not read
+    tnsd = nsd if tdata else 0                # the data inputs of the transition functions
+    if tdata:
+        tape = _trace_fn(F, nx, nu, nx, "F must return the next state", ntheta, model, nsd=nsd)
+        tape.tdata = True
+    else:
+        with _bound_theta(unread, _SdataGuard("F"), "sdata"):
+            tape = _trace_fn(F, nx, nu, nx, "F must return the next state", ntheta, model)
     if nsd:
         tape.nsd = nsd
         tape.sdata0 = [float(v) for v in sdata0]
@@ -749,7 +787,7 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     tape.link = None
     if tape.nk:
         with _bound_theta(guarded, _ThetaGuard("kfun")), _bound_theta(unread, _SdataGuard("kfun"), "sdata"):
-            tape.link = _trace_link(kfun, nx, nu, tape.nk)
+            tape.link = _trace_link(kfun, nx, nu, tape.nk, tnsd, model)
         tape.k_lo = [float(v) for v in np.broadcast_to(np.asarray(k_lo, float), (tape.nk,))]
         tape.k_hi = [float(v) for v in np.broadcast_to(np.asarray(k_hi, float), (tape.nk,))]
     tape.cost = None
@@ -767,7 +805,7 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
             if tape.nk and not link_is_linear(tape.link):
                 raise ValueError("exact_hessian does not cover a nonlinear link constraint (kfun): its curvature couples two frames; a linear kfun "
                                  "(rate limits) is fine")
-            tape.exact = trace_curvature(F, nx, nu, hfun if tape.nh else None, tape.nh, ntheta, nsd, model)
+            tape.exact = trace_curvature(F, nx, nu, hfun if tape.nh else None, tape.nh, ntheta, nsd, model, **({"transition_data": True} if tdata else {}))
             mask[:nx + nu, :nx + nu] |= tape.exact["mask"]
         if convexify:
             mask = closed_mask(mask)
@@ -795,7 +833,7 @@ def trace(F, nx, nu, hfun=None, nh=0, h_lo=None, h_hi=None, lcost=None, lterm=No
     tape.link_cost = None
     if llink is not None:
         with _bound_theta(guarded, _ThetaGuard("llink")), _bound_theta(unread, _SdataGuard("llink"), "sdata"):
-            LK, LKG = trace_link_cost(llink, nx, nu)
+            LK, LKG = trace_link_cost(llink, nx, nu, tnsd, model)
         tape.link_cost = dict(L=LK, G=LKG, mask=hessian_mask(LKG))
     return tape
 
@@ -910,13 +948,15 @@ def emit_functor(tape, name="SmUser"):
     nth = getattr(tape, "ntheta", 0)
     nsd = getattr(tape, "nsd", 0)
     dsig = "const double *d, " if nsd else ""      # (nsd > 0: H, L, LG, LT, LTG take the frame's stage-data row d behind their inputs)
+    tsig = "const double *d, " if getattr(tape, "tdata", False) else ""      # (transition_data: so do F, K, LK, LKG and FG, the row of the first frame)
     # (ntheta > 0: the plant parameters are par[i] in F's body -- data of the launch, sd.par or the instance's row)
     fmt = ("struct %s {\n  static constexpr int nx = %d, nu = %d, nh = %d, nk = %d, has_cost = %d, has_term = %d;\n"
            + ("  static constexpr int ntheta = %d;\n" % nth if nth else "")
-           + ("  static constexpr int nsd = %d;\n  static constexpr double sdata0[%d] = {%s};\n" % (nsd, nsd, ", ".join(_lit(v) for v in tape.sdata0)) if nsd else "") +
-           "  template <class T> SM_HD static void F(const double *" + ("par" if nth else "") + ", double, const T *s, const T *u, T *out) {\n%s\n  }\n"
+           + ("  static constexpr int nsd = %d;\n  static constexpr double sdata0[%d] = {%s};\n" % (nsd, nsd, ", ".join(_lit(v) for v in tape.sdata0)) if nsd else "")
+           + ("  static constexpr int tdata = 1;\n" if tsig else "") +
+           "  template <class T> SM_HD static void F(const double *" + ("par" if nth else "") + ", double, const T *s, const T *u, " + tsig + "T *out) {\n%s\n  }\n"
            "  template <class T> SM_HD static void H(const T *s, const T *u, " + dsig + "T *out) {\n%s\n  }\n"
-           "  template <class T> SM_HD static void K(const T *s, const T *u, const T *sn, const T *un, T *out) {\n%s\n  }\n")
+           "  template <class T> SM_HD static void K(const T *s, const T *u, const T *sn, const T *un, " + tsig + "T *out) {\n%s\n  }\n")
     src = fmt % (name, tape.nx, tape.nu, nh, nk, 1 if cost else 0, 1 if cost and cost["LT"] is not None else 0, _emit_body(tape), hbody, kbody)
     if cost:
         # L: out[0] = l(s, u, r); LG: out[nx + nu + nx] = dl / d[s; u; r]; LT, LTG: the terminal frame's
@@ -937,14 +977,14 @@ def emit_functor(tape, name="SmUser"):
         # LK: out[0] = llink(s, u, sn, un); LKG: out[2 f] = its gradient over [s; u; sn; un]; lmask: the structure of its Hessian, row-major (2 f)^2
         src += "  static constexpr int has_link_cost = 1;\n"
         for fn, tp in (("LK", link_cost["L"]), ("LKG", link_cost["G"])):
-            src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *sn, const T *un, T *out) {\n%s\n  }\n" % (fn, _emit_body(tp))
+            src += "  template <class T> SM_HD static void %s(const T *s, const T *u, const T *sn, const T *un, %sT *out) {\n%s\n  }\n" % (fn, tsig, _emit_body(tp))
         lm = link_cost["mask"]
         src += "  static constexpr unsigned char lmask[%d] = {%s};\n" % (lm.size, ", ".join(str(int(v)) for v in lm.ravel()))
     exact = getattr(tape, "exact", None)
     if exact:
         # FG: out[f] = d(lam' F)/d[s; u]; HG: out[f] = d(mu' H)/d[s; u] -- the multipliers are plain doubles like par and d (mpcqp_stage_lagrangian)
         src += "  static constexpr int has_exact = 1;\n"
-        src += ("  template <class T> SM_HD static void FG(const double *" + ("par" if nth else "") + ", double, const T *s, const T *u, const double *lam, T *out) {\n%s\n  }\n"
+        src += ("  template <class T> SM_HD static void FG(const double *" + ("par" if nth else "") + ", double, const T *s, const T *u, const double *lam, " + tsig + "T *out) {\n%s\n  }\n"
                 % _emit_body(exact["FG"]))
         if exact["HG"] is not None:
             src += "  template <class T> SM_HD static void HG(const T *s, const T *u, const double *mu, %sT *out) {\n%s\n  }\n" % (dsig, _emit_body(exact["HG"]))
@@ -1001,7 +1041,7 @@ int mpcqp_user_advance(const StageDev *sd, int batch, const mpcqp_stage_advance_
 int mpcqp_user_linesearch(const StageDev *sd, int batch, const mpcqp_stage_linesearch_args *a, const StageRows *r, void *stream) {
   return (int)stage_with_rows<SmUser, true>(*r, [&](auto... pp) { return stage_launch_linesearch<SmUser%(pf)s>(*sd, batch, *a, (hipStream_t)stream, pp...); });
 }
-%(params)s%(link_cost)s%(sdata)s%(convexify)s%(exact)s%(residual)s}
+%(params)s%(link_cost)s%(sdata)s%(tdata)s%(convexify)s%(exact)s%(residual)s}
 '''
 
 # the launcher of mpcqp_stage_rollout (one kernel instance for both kinds of reference: F reads none), a block of its own that library_source puts
@@ -1075,6 +1115,11 @@ _DEVICE_SDATA_TMPL = '''int mpcqp_user_nsd() { return SmUser::nsd; }
 void mpcqp_user_sdata0(double *d) { for (int i = 0; i < SmUser::nsd; i++) d[i] = SmUser_sdata0[i]; }
 '''
 
+# a model with transition_data = True only: its F, K, LK, LKG and FG take the data row of the transition's first frame.  A library without the export --
+# every one generated before this entry -- reads stage data in hfun and the frame costs only
+_DEVICE_TDATA_TMPL = '''int mpcqp_user_transition_data() { return SmUser::tdata; }
+'''
+
 _HOST_TMPL = '''// generated by optimal_control_problem_amd/codegen.py -- host build of the same functor, for checks without a GPU
 #include <cmath>
 #include "stage_models.hpp"
@@ -1106,7 +1151,7 @@ void user_host_eval(const double *s, const double *u, double *out, double *jac) 
     Dual sd[nx], ud[nu], od[nx];
     for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
     for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
-    SmUser::F<Dual>(%(theta0)s, 0.0, sd, ud, od);
+    SmUser::F<Dual>(%(theta0)s, 0.0, sd, ud, %(td)sod);
     for (int r = 0; r < nx; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
   }
 }
@@ -1118,7 +1163,7 @@ void user_host_eval_theta(const double *theta, const double *s, const double *u,
     Dual sd[nx], ud[nu], od[nx];
     for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
     for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
-    SmUser::F<Dual>(theta, 0.0, sd, ud, od);
+    SmUser::F<Dual>(theta, 0.0, sd, ud, %(td)sod);
     for (int r = 0; r < nx; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
   }
 }
@@ -1132,7 +1177,7 @@ void user_host_link(const double *s, const double *u, const double *sn, const do
       Dual sd[nx], ud[nu], snd[nx], und[nu], od[nk];
       for (int i = 0; i < nx; i++) { sd[i] = {s[i], i == c ? 1.0 : 0.0}; snd[i] = {sn[i], f + i == c ? 1.0 : 0.0}; }
       for (int i = 0; i < nu; i++) { ud[i] = {u[i], nx + i == c ? 1.0 : 0.0}; und[i] = {un[i], f + nx + i == c ? 1.0 : 0.0}; }
-      SmUser::K<Dual>(sd, ud, snd, und, od);
+      SmUser::K<Dual>(sd, ud, snd, und, %(td)sod);
       for (int r = 0; r < nk; r++) { jac[r * 2 * f + c] = od[r].d; out[r] = od[r].v; }
     }
   }
@@ -1152,7 +1197,7 @@ void user_host_path(const double *s, const double *u, double *out, double *jac) 
     for (int r = 0; r < nh; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
   }
 }
-%(sdata)s%(exact)s}
+%(sdata)s%(tdata)s%(exact)s}
 '''
 
 # a functor with exact_hessian only: C [f * f] row-major = -sum_i lam_i d2F_i + sum_i mu_i d2h_i over [s; u], column c by one pass of FG (dyn != 0) and
@@ -1165,7 +1210,7 @@ _HOST_EXACT_TMPL = '''void user_host_curvature(const double *theta, const double
     for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
     for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
     for (int r = 0; r < f; r++) { gf[r] = {0.0, 0.0}; gh[r] = {0.0, 0.0}; }
-    if (dyn) SmUser::FG<Dual>(%(th)s, 0.0, sd, ud, lam, gf);
+    if (dyn) SmUser::FG<Dual>(%(th)s, 0.0, sd, ud, lam, %(fd)sgf);
 %(hg)s    for (int r = 0; r < f; r++) {
       double v = 0.0;
       if (dyn) v = -gf[r].d;
@@ -1216,12 +1261,52 @@ void user_host_cost_d(const double *s, const double *u, const double *r, const d
 # val [1], grad [2 f], hess [(2 f)^2] row-major over [s; u; s_next; u_next]: the gradient on duals, one direction per pass (what a device thread does)
 _HOST_LINK_COST_TMPL = '''void user_host_link_cost(const double *s, const double *u, const double *sn, const double *un, double *val, double *grad, double *hess) {
   constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu;
-  SmUser::LK<double>(s, u, sn, un, val);
+  SmUser::LK<double>(s, u, sn, un, %(td)sval);
   for (int c = 0; c < 2 * f; c++) {
     Dual sd[nx], ud[nu], snd[nx], und[nu], gd[2 * f];
     for (int i = 0; i < nx; i++) { sd[i] = {s[i], i == c ? 1.0 : 0.0}; snd[i] = {sn[i], f + i == c ? 1.0 : 0.0}; }
     for (int i = 0; i < nu; i++) { ud[i] = {u[i], nx + i == c ? 1.0 : 0.0}; und[i] = {un[i], f + nx + i == c ? 1.0 : 0.0}; }
-    SmUser::LKG<Dual>(sd, ud, snd, und, gd);
+    SmUser::LKG<Dual>(sd, ud, snd, und, %(td)sgd);
+    for (int i = 0; i < 2 * f; i++) { hess[i * 2 * f + c] = gd[i].d; grad[i] = gd[i].v; }
+  }
+}
+'''
+
+# a functor with transition_data only: the dynamics with their Jacobian, the link rows and the link cost with a data row d [nsd] given (the exports
+# above use the defaults); theta [ntheta] may be null = the defaults.  user_host_curvature takes its row already
+_HOST_TDATA_TMPL = '''int user_host_transition_data() { return SmUser::tdata; }
+void user_host_eval_d(const double *theta, const double *s, const double *u, const double *d, double *out, double *jac) {
+  constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu;
+  for (int c = 0; c < f; c++) {
+    Dual sd[nx], ud[nu], od[nx];
+    for (int i = 0; i < nx; i++) sd[i] = {s[i], i == c ? 1.0 : 0.0};
+    for (int i = 0; i < nu; i++) ud[i] = {u[i], nx + i == c ? 1.0 : 0.0};
+    SmUser::F<Dual>(%(th)s, 0.0, sd, ud, d, od);
+    for (int r = 0; r < nx; r++) { jac[r * f + c] = od[r].d; out[r] = od[r].v; }
+  }
+}
+void user_host_link_d(const double *s, const double *u, const double *sn, const double *un, const double *d, double *out, double *jac) {
+  constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu, nk = SmUser::nk;
+  if constexpr (nk > 0) {
+    for (int c = 0; c < 2 * f; c++) {
+      Dual sd[nx], ud[nu], snd[nx], und[nu], od[nk];
+      for (int i = 0; i < nx; i++) { sd[i] = {s[i], i == c ? 1.0 : 0.0}; snd[i] = {sn[i], f + i == c ? 1.0 : 0.0}; }
+      for (int i = 0; i < nu; i++) { ud[i] = {u[i], nx + i == c ? 1.0 : 0.0}; und[i] = {un[i], f + nx + i == c ? 1.0 : 0.0}; }
+      SmUser::K<Dual>(sd, ud, snd, und, d, od);
+      for (int r = 0; r < nk; r++) { jac[r * 2 * f + c] = od[r].d; out[r] = od[r].v; }
+    }
+  }
+}
+%(link_cost)s'''
+
+_HOST_TDATA_LINK_COST_TMPL = '''void user_host_link_cost_d(const double *s, const double *u, const double *sn, const double *un, const double *d, double *val, double *grad, double *hess) {
+  constexpr int nx = SmUser::nx, nu = SmUser::nu, f = nx + nu;
+  SmUser::LK<double>(s, u, sn, un, d, val);
+  for (int c = 0; c < 2 * f; c++) {
+    Dual sd[nx], ud[nu], snd[nx], und[nu], gd[2 * f];
+    for (int i = 0; i < nx; i++) { sd[i] = {s[i], i == c ? 1.0 : 0.0}; snd[i] = {sn[i], f + i == c ? 1.0 : 0.0}; }
+    for (int i = 0; i < nu; i++) { ud[i] = {u[i], nx + i == c ? 1.0 : 0.0}; und[i] = {un[i], f + nx + i == c ? 1.0 : 0.0}; }
+    SmUser::LKG<Dual>(sd, ud, snd, und, d, gd);
     for (int i = 0; i < 2 * f; i++) { hess[i * 2 * f + c] = gd[i].d; grad[i] = gd[i].v; }
   }
 }
@@ -1276,7 +1361,8 @@ def device_source(tape):
            "cvx": "true" if convexify else "false"}
     return _DEVICE_TMPL % dict(sub, functor=emit_functor(tape), params=_DEVICE_PARAMS_TMPL if getattr(tape, "ntheta", 0) else "",
                                link_cost=_DEVICE_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "",
-                               sdata=_DEVICE_SDATA_TMPL if getattr(tape, "nsd", 0) else "", convexify=_DEVICE_CONVEXIFY_TMPL % sub if convexify else "",
+                               sdata=_DEVICE_SDATA_TMPL if getattr(tape, "nsd", 0) else "",
+                               tdata=_DEVICE_TDATA_TMPL if getattr(tape, "tdata", False) else "", convexify=_DEVICE_CONVEXIFY_TMPL % sub if convexify else "",
                                exact=_DEVICE_EXACT_TMPL % sub if getattr(tape, "exact", None) else "",
                                residual=_DEVICE_RESIDUAL_TMPL if getattr(tape, "residual", None) else "")
 
@@ -1298,8 +1384,13 @@ def host_source(tape):
     """the translation unit of the host build (a functor with stage data: the exports without a data row use the defaults)"""
     nth, nsd = getattr(tape, "ntheta", 0), getattr(tape, "nsd", 0)
     res = bool(getattr(tape, "residual", None))      # (a Gauss-Newton cost: user_host_cost and user_host_cost_d go through host_cost_gn)
-    return _HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr",
-                         "link_cost": _HOST_LINK_COST_TMPL if getattr(tape, "link_cost", None) else "",
+    tdata = bool(getattr(tape, "tdata", False))      # (transition_data: the forms without a row hand the defaults to F, K, LK, LKG; the _d forms take one)
+    td = {"td": "SmUser_sdata0, " if tdata else ""}
+    link_cost = bool(getattr(tape, "link_cost", None))
+    return _HOST_TMPL % {"functor": emit_functor(tape), "ntheta": nth, "theta0": "SmUser_theta0" if nth else "nullptr", "td": td["td"],
+                         "link_cost": _HOST_LINK_COST_TMPL % td if link_cost else "",
+                         "tdata": _HOST_TDATA_TMPL % {"th": "theta ? theta : SmUser_theta0" if nth else "nullptr",
+                                                      "link_cost": _HOST_TDATA_LINK_COST_TMPL if link_cost else ""} if tdata else "",
                          "hd": "SmUser_sdata0, " if nsd else "", "exact": _host_exact(tape, nth, nsd),
                          "sdata": _HOST_SDATA_TMPL % {"cost_d": "host_cost_gn" if res else "host_cost_d"} if nsd else "",
                          "residual": _HOST_RESIDUAL_TMPL % {"d": "d, " if nsd else "", "sd": "true" if nsd else "false"} if res else "",
@@ -1314,7 +1405,8 @@ def _host_exact(tape, nth, nsd):
     hg = ""
     if exact["HG"] is not None:
         hg = "    SmUser::HG<Dual>(sd, ud, mu, %sgh);\n" % ("d ? d : SmUser_sdata0, " if nsd else "")
-    return _HOST_EXACT_TMPL % {"th": "theta ? theta : SmUser_theta0" if nth else "nullptr", "hg": hg}
+    return _HOST_EXACT_TMPL % {"th": "theta ? theta : SmUser_theta0" if nth else "nullptr", "hg": hg,
+                               "fd": "d ? d : SmUser_sdata0, " if getattr(tape, "tdata", False) else ""}
 
 
 def build_host_library(tape):

@@ -71,6 +71,7 @@ struct mpcqp_stage {
   int nsd = 0;                        // values per frame the library's hfun / lcost / lterm read (mpcqp_user_nsd); 0: the zoo, a library without
   double *dsd[2] = {nullptr, nullptr};
   int sd_cur = 0, sd_batch = 0, sd_cap = 0;
+  bool tdata = false;                 // the library's F, kfun and llink read the stage data too (mpcqp_user_transition_data)
   const double *sdata() const { return sd_batch > 0 ? dsd[sd_cur] : nullptr; }
   // convexification (mpcqp_stage_convexify): the slot tables of the frame term, built with the handle of a library that exports the launcher, and
   // the scratch of the launch ([cvx_cap * N * nx * nx] doubles, then [cvx_cap * N] flags), sized on first use like the stage-data buffers
@@ -343,6 +344,9 @@ static int stage_create_library(const mpcqp_stage_desc *d, const char *library_p
       return mpcqp_set_error(MPCQP_ERR_LIMIT, "the library declares stage data but not 0..8 values per frame");
     }
     s->nsd = ns;
+    // optional export of a library generated with transition_data: the rows reach F, kfun and llink as well.  A library without it reports 0.
+    auto tdf = (int (*)())dlsym(lib, "mpcqp_user_transition_data");
+    s->tdata = ns > 0 && tdf && tdf() != 0;
   }
   std::vector<unsigned char> mask((size_t)(2 * nx + nu) * (2 * nx + nu));
   auto cf = (int (*)(unsigned char *))dlsym(lib, "mpcqp_user_cost");
@@ -464,6 +468,7 @@ int mpcqp_stage_set_instance_params(mpcqp_stage *s, int which, int batch, const 
 }
 
 int mpcqp_stage_data_count(const mpcqp_stage *s) { return s ? s->nsd : 0; }
+int mpcqp_stage_has_transition_data(const mpcqp_stage *s) { return s && s->tdata ? 1 : 0; }
 
 int mpcqp_stage_set_stage_data(mpcqp_stage *s, int batch, const double *d, int mem) {
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");

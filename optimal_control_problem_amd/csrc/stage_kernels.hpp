@@ -85,6 +85,26 @@ template <class M, class T> __device__ __forceinline__ void stage_cost_value(boo
   else { if (M::has_term && last) M::template LT<T>(s, u, r, out); else M::template L<T>(s, u, r, out); }
 }
 
+// Transition data (models.StageOCP.transition_data): a generated functor that declares tdata = 1 takes the stage-data row of the
+// transition's first frame -- row k for the step k -> k + 1 -- behind the inputs of F, K, LK, LKG and FG as well.  One trait decides for all five; the
+// zoo and every functor generated without the flag declare nothing and keep their signatures and their code.
+template <class M, class = void> struct sm_tdata : std::false_type {};
+template <class M> struct sm_tdata<M, std::void_t<decltype(M::tdata)>> : std::bool_constant<M::tdata != 0> {};
+template <class M, class T> __device__ __forceinline__ void stage_dyn(const double *par, double dt, const T *s, const T *u, const double *d, T *out) {
+  if constexpr (sm_tdata<M>::value) M::template F<T>(par, dt, s, u, d, out); else M::template F<T>(par, dt, s, u, out);
+}
+template <class M, class T> __device__ __forceinline__ void stage_link(const T *s, const T *u, const T *sn, const T *un, const double *d, T *out) {
+  if constexpr (sm_tdata<M>::value) M::template K<T>(s, u, sn, un, d, out); else M::template K<T>(s, u, sn, un, out);
+}
+template <class M, class T> __device__ __forceinline__ void stage_link_cost(const T *s, const T *u, const T *sn, const T *un, const double *d, T *out) {
+  if constexpr (sm_tdata<M>::value) M::template LK<T>(s, u, sn, un, d, out); else M::template LK<T>(s, u, sn, un, out);
+}
+template <class M, class T> __device__ __forceinline__ void stage_link_cost_grad(const T *s, const T *u, const T *sn, const T *un, const double *d, T *out) {
+  if constexpr (sm_tdata<M>::value) M::template LKG<T>(s, u, sn, un, d, out); else M::template LKG<T>(s, u, sn, un, out);
+}
+// the second row the eval kernel needs: row k - 1 for the pair (k - 1, k), compiled in only for a functor that has a link constraint or a link cost
+template <class M> inline constexpr bool sm_tdata_pair = sm_tdata<M>::value && (M::nk > 0 || sm_has_link_cost<M>::value);
+
 // PF (per-frame references, StageDev::pref): the parameter block holds one reference state per frame.  Parameter column j = k nx + i is thread j of
 // its instance, as before; the cooperative mapping pads the N nx parameter slots up to a multiple of f, so that every frame's f lanes still start
 // at a multiple of f (threads per instance ceil(N nx / f) f + N f).  Adjacent lanes still own adjacent columns: the store streams stay contiguous.
@@ -216,6 +236,9 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
   // SD: the f lanes of a frame read the same row, once, into registers: hfun and the frame cost below take it from there
   double dv[sm_nsd_regs<M>];
   stage_load_data<M>(dv, b, N, k, pp...);
+  // transition data: F, K and LKG of the pair (k, k + 1) take dv; K and LKG of the pair (k - 1, k) take row k - 1, a second load skipped at k = 0
+  [[maybe_unused]] double dvp[sm_nsd_regs<M>];
+  if constexpr (sm_tdata_pair<M>) { if (k >= 1) stage_load_data<M>(dvp, b, N, k - 1, pp...); }
   Dual s[nx], uu[nu];
 #pragma unroll
   for (int i = 0; i < nx; i++) s[i] = {fr[i], i == c ? 1.0 : 0.0};
@@ -269,7 +292,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
       for (int i = 0; i < nx; i++) os[i] = {pf[i], 0.0};
 #pragma unroll
       for (int i = 0; i < nu; i++) ou[i] = {pf[nx + i], 0.0};
-      M::template LKG<Dual>(os, ou, s, uu, g2);
+      stage_link_cost_grad<M, Dual>(os, ou, s, uu, dvp, g2);
       double ga = 0.0;
 #pragma unroll
       for (int r = 0; r < f; r++) if ((bprev >> r) & 1u) Pc[e++] = g2[r].d;
@@ -283,7 +306,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
       for (int i = 0; i < nx; i++) os[i] = {nf[i], 0.0};
 #pragma unroll
       for (int i = 0; i < nu; i++) ou[i] = {nf[nx + i], 0.0};
-      M::template LKG<Dual>(s, uu, os, ou, g2);
+      stage_link_cost_grad<M, Dual>(s, uu, os, ou, dv, g2);
       double gb = 0.0;
 #pragma unroll
       for (int r = 0; r < f; r++) gb = r == c ? g2[r].v : gb;
@@ -334,7 +357,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
   if (k >= 1 && c < nx) Ac[a++] = 1.0;
   if (k < N - 1) {
     Dual out[nx];
-    if constexpr (COOP) M::Fc(par, sd.dt, s, uu, out, c); else M::template F<Dual>(par, sd.dt, s, uu, out);
+    if constexpr (COOP) M::Fc(par, sd.dt, s, uu, out, c); else stage_dyn<M, Dual>(par, sd.dt, s, uu, dv, out);
 #pragma unroll
     for (int r = 0; r < nx; r++) Ac[a + r] = -out[r].d;
     a += nx;
@@ -375,7 +398,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
       for (int i = 0; i < nx; i++) os[i] = {pf[i], 0.0};
 #pragma unroll
       for (int i = 0; i < nu; i++) ou[i] = {pf[nx + i], 0.0};
-      M::template K<Dual>(os, ou, s, uu, kv);
+      stage_link<M, Dual>(os, ou, s, uu, dvp, kv);
 #pragma unroll
       for (int r = 0; r < nk; r++) Ac[a + r] = kv[r].d;
       a += nk;
@@ -386,7 +409,7 @@ __global__ void __launch_bounds__(256) stage_eval_kernel(StageDev sd, int batch,
       for (int i = 0; i < nx; i++) os[i] = {nf[i], 0.0};
 #pragma unroll
       for (int i = 0; i < nu; i++) ou[i] = {nf[nx + i], 0.0};
-      M::template K<Dual>(s, uu, os, ou, kv);
+      stage_link<M, Dual>(s, uu, os, ou, dv, kv);
 #pragma unroll
       for (int r = 0; r < nk; r++) Ac[a + r] = kv[r].d;
       for (int r0 = c; r0 < nk; r0 += f) {
@@ -442,13 +465,13 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
         for (int i = 0; i < nx; i++) ns[i] = fr[f + i];
 #pragma unroll
         for (int i = 0; i < nu; i++) nun[i] = fr[f + nx + i];
-        M::template LK<double>(s, uu, ns, nun, lk);
+        stage_link_cost<M, double>(s, uu, ns, nun, dv, lk);
         cost += lk[0];
       }
     }
     if (k < sd.N - 1) {
       double out[nx];
-      M::template F<double>(par, sd.dt, s, uu, out);
+      stage_dyn<M, double>(par, sd.dt, s, uu, dv, out);
 #pragma unroll
       for (int i = 0; i < nx; i++) gmax = fmax(gmax, fabs(fr[f + i] - out[i]));
     }
@@ -468,7 +491,7 @@ __global__ void __launch_bounds__(256) stage_merit_kernel(StageDev sd, int batch
         for (int i = 0; i < nx; i++) ns[i] = fr[f + i];
 #pragma unroll
         for (int i = 0; i < nu; i++) nun[i] = fr[f + nx + i];
-        M::template K<double>(s, uu, ns, nun, kv);
+        stage_link<M, double>(s, uu, ns, nun, dv, kv);
 #pragma unroll
         for (int i = 0; i < M::nk; i++) gmax = fmax(gmax, fmax(sd.k_lo[i] - kv[i], kv[i] - sd.k_hi[i]));
       }
@@ -515,6 +538,9 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
     for (int i = 0; i < nx; i++) s[i] = fr[i];
 #pragma unroll
     for (int i = 0; i < nu; i++) uu[i] = fr[nx + i];
+    // transition data: the plant step takes row 0, the rollout tail row N - 1 -- the rows stored before the shift (mpcqp_stage_shift_data comes after)
+    [[maybe_unused]] double dt_[sm_nsd_regs<M>];
+    if constexpr (sm_tdata<M>::value) stage_load_data<M>(dt_, b, N, lane == 0 ? 0 : N - 1, pp...);
     if constexpr (stage_has<StageTheta, PP...>) {
       // PP: the plant step (lane 0) takes the plant row, or the model row when no plant set is stored; the rollout tail (lane 1) the model
       // row; a set that is not stored stands for sd.par.  Values, not addresses, are selected: sd.par stays in its scalar registers
@@ -524,9 +550,9 @@ __global__ void __launch_bounds__(256) stage_advance_kernel(StageDev sd, int bat
       double th[NT];
 #pragma unroll
       for (int i = 0; i < NT; i++) th[i] = row ? row[(long)b * SM_NPAR + i] : sd.par[i];
-      if (lane == 0 ? a.s_meas == nullptr : rollout) M::template F<double>(th, sd.dt, s, uu, Fo);
+      if (lane == 0 ? a.s_meas == nullptr : rollout) stage_dyn<M, double>(th, sd.dt, s, uu, dt_, Fo);
     } else {
-      if (lane == 0 ? a.s_meas == nullptr : rollout) M::template F<double>(sd.par, sd.dt, s, uu, Fo);
+      if (lane == 0 ? a.s_meas == nullptr : rollout) stage_dyn<M, double>(sd.par, sd.dt, s, uu, dt_, Fo);
     }
     if (lane == 0 && a.stage_cost) {
       // the k = 0 term of stage_merit_kernel's objective, in its order of operations
@@ -642,7 +668,10 @@ __global__ void __launch_bounds__(64) stage_rollout_kernel(StageDev sd, int batc
       bool ok = fin;
 #pragma unroll
       for (int i = 0; i < nu; i++) ok = ok && isfinite(uu[i]);
-      M::template F<double>(th, sd.dt, s, uu, sn);
+      // transition data: step k takes row k of the instance -- nsd loads per step, N nsd doubles apart between lanes
+      [[maybe_unused]] double dv[sm_nsd_regs<M>];
+      if constexpr (sm_tdata<M>::value) stage_load_data<M>(dv, b, N, k, pp...);
+      stage_dyn<M, double>(th, sd.dt, s, uu, dv, sn);
 #pragma unroll
       for (int i = 0; i < nx; i++) ok = ok && isfinite(sn[i]);
       if (ok) {
@@ -737,13 +766,13 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
         for (int i = 0; i < nx; i++) { ns[i] = fr[f + i]; if (c > 0) ns[i] += ac * dfr[f + i]; }
 #pragma unroll
         for (int i = 0; i < nu; i++) { nun[i] = fr[f + nx + i]; if (c > 0) nun[i] += ac * dfr[f + nx + i]; }
-        M::template LK<double>(s, uu, ns, nun, lk);
+        stage_link_cost<M, double>(s, uu, ns, nun, dv, lk);
         lc += lk[0];
       }
     }
     if (k < N - 1) {
       double out[nx];
-      M::template F<double>(par, sd.dt, s, uu, out);
+      stage_dyn<M, double>(par, sd.dt, s, uu, dv, out);
 #pragma unroll
       for (int i = 0; i < nx; i++) {
         double sn = fr[f + i];
@@ -769,7 +798,7 @@ __global__ void __launch_bounds__(256) stage_linesearch_kernel(StageDev sd, int 
         for (int i = 0; i < nx; i++) { ns[i] = fr[f + i]; if (c > 0) ns[i] += ac * dfr[f + i]; }
 #pragma unroll
         for (int i = 0; i < nu; i++) { nun[i] = fr[f + nx + i]; if (c > 0) nun[i] += ac * dfr[f + nx + i]; }
-        M::template K<double>(s, uu, ns, nun, kv);
+        stage_link<M, double>(s, uu, ns, nun, dv, kv);
 #pragma unroll
         for (int i = 0; i < M::nk; i++) {
           lv += fmax(sd.k_lo[i] - kv[i], 0.0) + fmax(kv[i] - sd.k_hi[i], 0.0);
@@ -882,7 +911,7 @@ template <class M> __device__ __forceinline__ void stage_curvature_column(const 
 #pragma unroll
     for (int i = 0; i < nx; i++) lam[i] = yd[i];
     Dual g[f];
-    M::template FG<Dual>(par, sd.dt, s, uu, lam, g);
+    if constexpr (sm_tdata<M>::value) M::template FG<Dual>(par, sd.dt, s, uu, lam, dv, g); else M::template FG<Dual>(par, sd.dt, s, uu, lam, g);
 #pragma unroll
     for (int r = 0; r < f; r++) cv[r] = -g[r].d;
   }

@@ -177,13 +177,13 @@ class StageOCP:
             for c in range(w):
                 pert = [v.copy() if i == a else v for i, v in enumerate(args)]
                 pert[a][..., c] += 1j * eps
-                out[..., :, col] = np.asarray(self.kfun(*pert)).imag / eps
+                out[..., :, col] = np.asarray(self._kfun(*pert)).imag / eps
                 col += 1
         return out
 
     def link_values(self, x):
         s, u = self.frames(x)
-        return np.asarray(self.kfun(s[:, :-1], u[:, :-1], s[:, 1:], u[:, 1:])).reshape(x.shape[0], -1)
+        return np.asarray(self._kfun(s[:, :-1], u[:, :-1], s[:, 1:], u[:, 1:])).reshape(x.shape[0], -1)
 
     def path_bounds(self):
         """([N, nh], [N, nh]) bounds of the path constraint per frame"""
@@ -233,6 +233,11 @@ class StageOCP:
     nsd = 0; sdata = None
     NSD_MAX = 8
     _sdata_rows = None
+    # opt-in transition data: a model with nsd > 0 sets transition_data = True and F / cdyn, kfun and llink read self.sdata[i] as well --
+    # a step length per frame (a non-uniform time grid), a previewed disturbance, a schedule.  The functions of the transition k -> k + 1 take row k;
+    # row N-1 is read by hfun, the costs and the rollout tail of advance.  The rows stay data: no column, row, entry or derivative comes with them.
+    # Without the flag the three stay refused and nothing changes.
+    transition_data = False
 
     # opt-in convexification of the frame term: a model with lcost sets convexify = True when its cost is not convex everywhere (a
     # Gaussian bump, an inverse-distance potential, a cosine swing-up term).  The QP otherwise takes the exact, indefinite Hessian and comes back
@@ -253,7 +258,9 @@ class StageOCP:
         """Host statement of mpcqp_stage_set_stage_data.  d [B, N, nsd]: frame k of instance b takes row d[b, k] in hfun, lcost and lterm -- in
         path_values, dh, constraints, objective, cost_derivatives, local_system, violation, line_search and the stage_cost of advance (d[b, 0]).
         None returns to the defaults self.sdata on every frame.  A call with more instances than rows is a ValueError, a smaller batch uses the
-        first rows.  With nothing set every method returns the bits it always did."""
+        first rows.  With nothing set every method returns the bits it always did.  A model with transition_data: F, kfun and llink of the transition
+        k -> k + 1 take row d[b, k] as well -- in constraints, dF, dk, the link cost, rollout (row k at step k), advance (row 0 for the plant step, row
+        N-1 for the rollout tail) and constraint_curvature."""
         if d is not None:
             if self.nsd == 0:
                 raise ValueError("this model has no stage data (nsd = 0)")
@@ -289,6 +296,28 @@ class StageOCP:
             return self.hfun(s, u)
         finally:
             self.sdata = saved
+
+    def _with_rows(self, rows, fn, *args):
+        """fn(*args) with self.sdata[i] = column i of `rows` ([B, n, nsd] for frames [B, n, .], [B, nsd] for one frame per instance)"""
+        saved = self.sdata
+        try:
+            self.sdata = np.moveaxis(rows, -1, 0)
+            return fn(*args)
+        finally:
+            self.sdata = saved
+
+    def _F(self, s, u, rows=None):
+        """F on the first frames of the transitions, s [B, n, nx] = frames 0 .. n-1 (rows: their data, [B, n, nsd]; default: the rows in force), or
+        on one frame per instance, s [B, nx], with rows [B, nsd].  A model without transition_data: F as it is"""
+        if not self.transition_data:
+            return self.F(s, u)
+        return self._with_rows(self._stage_data(s.shape[0])[:, :s.shape[1]] if rows is None else rows, self.F, s, u)
+
+    def _kfun(self, s, u, sn, un, rows=None):
+        """kfun on the pairs (k, k + 1), k = 0 .. n-1, with the rows of the first frames (a model with transition_data; else kfun as it is)"""
+        if not self.transition_data:
+            return self.kfun(s, u, sn, un)
+        return self._with_rows(self._stage_data(s.shape[0])[:, :s.shape[1]] if rows is None else rows, self.kfun, s, u, sn, un)
 
     def set_instance_params(self, theta=None, plant=None):
         """Host statement of mpcqp_stage_set_instance_params.  theta [B, ntheta]: instance b's parameters, what local_system, objective,
@@ -336,6 +365,8 @@ class StageOCP:
             raise ValueError("a model may declare at most %d stage-data values (nsd = %d)" % (self.NSD_MAX, self.nsd))
         if self.nsd and np.size(self.sdata) != self.nsd:
             raise ValueError("sdata must hold the nsd = %d default values" % self.nsd)
+        if self.transition_data and not self.nsd:
+            raise ValueError("transition_data needs stage data (nsd > 0): it lets F / cdyn, kfun and llink read self.sdata")
         # diagonal weights, the same for every frame ([nx], [nu]) or one row per frame ([N, nx], [N, nu]: terminal costs,
         # ramps) -- addVectorCost is called per step in the reference (readme.md:121-128), so weights may differ by step
         self.Q = np.asarray(Q, float); self.R = np.asarray(R, float)
@@ -391,7 +422,8 @@ class StageOCP:
         self.link_cost = self.llink is not None
         if self.link_cost:
             from . import codegen
-            self._lktape, self._lkgtape = codegen.trace_link_cost(self.llink, self.nx, self.nu)
+            tkw = {"nsd": self.nsd, "model": self} if self.transition_data else {}
+            self._lktape, self._lkgtape = codegen.trace_link_cost(self.llink, self.nx, self.nu, **tkw)
             self.lmask = codegen.hessian_mask(self._lkgtape)      # exact structure of M over [s; u; s_next; u_next]: no diagonal forced in
         self._build_pattern()
         if self.general_cost:
@@ -622,12 +654,14 @@ class StageOCP:
     def _trace_curvature(self, codegen):
         """the gradient tapes of lam' F and mu' hfun over [s; u] (codegen.trace_curvature, what the generated library compiles) and the structure of
         their Hessians, which joins the [s; u] block of cost_mask"""
-        if self.nk and not codegen.link_is_linear(codegen._trace_link(self.kfun, self.nx, self.nu, self.nk)):
+        tkw = {"nsd": self.nsd, "model": self} if self.transition_data else {}
+        if self.nk and not codegen.link_is_linear(codegen._trace_link(self.kfun, self.nx, self.nu, self.nk, **tkw)):
             raise ValueError("exact_hessian does not cover a nonlinear link constraint (kfun): its curvature couples two frames; a linear kfun "
                              "(rate limits) is fine")
         # (the zoo classes on the generated path keep their constants in the code: no parameter inputs, as in stage_eval.StageEvaluator)
         self._curv_ntheta = 0 if isinstance(self, (Quadrotor, CartPole)) else int(self.ntheta)
-        t = codegen.trace_curvature(self.F, self.nx, self.nu, self.hfun if self.nh else None, self.nh, self._curv_ntheta, self.nsd, self)
+        t = codegen.trace_curvature(self.F, self.nx, self.nu, self.hfun if self.nh else None, self.nh, self._curv_ntheta, self.nsd, self,
+                                    **({"transition_data": True} if self.transition_data else {}))
         self._fgtape, self._hgtape, self.curvature_mask = t["FG"], t["HG"], t["mask"]
         self.cost_mask[:self.f, :self.f] |= self.curvature_mask
 
@@ -662,7 +696,8 @@ class StageOCP:
                 raise ValueError("batch %d is larger than the stored per-instance parameters (%d rows)" % (B, rows.shape[0]))
             rows = np.broadcast_to(np.asarray(self.theta, float), (B, self._curv_ntheta)) if rows is None else rows[:B]
             par = [np.broadcast_to(rows[:, i:i + 1], (B, N)) for i in range(self._curv_ntheta)]
-        C = -self._tape_hessian(self._fgtape, frame + par + [lam[..., i] for i in range(nx)], f)
+        tdata = [self._stage_data(B)[..., i] for i in range(self.nsd)] if self.transition_data else []      # (frame k under row k)
+        C = -self._tape_hessian(self._fgtape, frame + par + [lam[..., i] for i in range(nx)] + tdata, f)
         C[:, N - 1] = 0.0                                       # the last frame has no dynamics row
         if nh:
             mu = y[:, n + self.ngd:n + self.ngd + N * nh].reshape(B, N, nh)
@@ -738,17 +773,18 @@ class StageOCP:
         return s + (h / 6.0) * (k1 + 2 * k2 + 2 * k3 + k4)
 
     def dF(self, s, u):
-        """[..., nx, f] Jacobian of F wrt [s; u] by complex-step differentiation (exact to rounding)."""
+        """[..., nx, f] Jacobian of F wrt [s; u] by complex-step differentiation (exact to rounding); a model with transition_data: s, u are the
+        frames 0 .. n-1 [B, n, .], each under its own row"""
         eps = 1e-30
         out = np.empty(s.shape[:-1] + (self.nx, self.f))
         sc = s.astype(complex); uc = u.astype(complex)
         for c in range(self.f):
             if c < self.nx:
                 sp = sc.copy(); sp[..., c] += 1j * eps
-                out[..., :, c] = self.F(sp, uc).imag / eps
+                out[..., :, c] = self._F(sp, uc).imag / eps
             else:
                 up = uc.copy(); up[..., c - self.nx] += 1j * eps
-                out[..., :, c] = self.F(sc, up).imag / eps
+                out[..., :, c] = self._F(sc, up).imag / eps
         return out
 
     # -- evaluation ------------------------------------------------------------------------------
@@ -775,8 +811,12 @@ class StageOCP:
 
     def _link_cost_inputs(self, x):
         s, u = self.frames(x)
-        return ([s[:, :-1, i] for i in range(self.nx)] + [u[:, :-1, i] for i in range(self.nu)]
-                + [s[:, 1:, i] for i in range(self.nx)] + [u[:, 1:, i] for i in range(self.nu)])
+        ins = ([s[:, :-1, i] for i in range(self.nx)] + [u[:, :-1, i] for i in range(self.nu)]
+               + [s[:, 1:, i] for i in range(self.nx)] + [u[:, 1:, i] for i in range(self.nu)])
+        if self.transition_data:       # the rows of the pairs' first frames behind the two frames: inputs of the tapes without a derivative
+            d = self._stage_data(x.shape[0])[:, :-1]
+            ins += [d[..., i] for i in range(self.nsd)]
+        return ins
 
     def link_cost_values(self, x):
         """[B, N-1]: llink(s_k, u_k, s_{k+1}, u_{k+1}) on every stage"""
@@ -787,7 +827,7 @@ class StageOCP:
         """(grad [B, N-1, 2 f], hess [B, N-1, 2 f, 2 f]) of the link cost on every stage over [s_k; u_k; s_{k+1}; u_{k+1}]: gradient tape evaluated
         directly, Hessian columns by complex-step differentiation of the gradient tape (exact to rounding), like cost_derivatives"""
         ins = self._link_cost_inputs(x)
-        n2 = len(ins); shape = ins[0].shape
+        n2 = 2 * self.f; shape = ins[0].shape
         ev = lambda v: np.stack([np.broadcast_to(np.asarray(o), shape) for o in self._lkgtape.evaluate(v)], axis=-1)
         grad = ev(ins).astype(float)
         hess = np.zeros(shape + (n2, n2)); eps = 1e-30
@@ -816,7 +856,7 @@ class StageOCP:
         if self._theta_rows is not None:
             return np.concatenate(self._each_instance(self._theta_rows, x.shape[0], lambda i: self.constraints(x[i])))
         s, u = self.frames(x)
-        return (s[:, 1:, :] - self.F(s[:, :-1, :], u[:, :-1, :])).reshape(x.shape[0], -1)
+        return (s[:, 1:, :] - self._F(s[:, :-1, :], u[:, :-1, :])).reshape(x.shape[0], -1)
 
     def path_values(self, x):
         s, u = self.frames(x)
@@ -866,7 +906,7 @@ class StageOCP:
         A[:, self._A_id] = 1.0
         A[:, self._A_next[1:].ravel()] = 1.0
         A[:, self._A_blk.ravel()] = -J.reshape(B, -1)
-        g = (s[:, 1:, :] - self.F(s[:, :-1, :], u[:, :-1, :])).reshape(B, -1)
+        g = (s[:, 1:, :] - self._F(s[:, :-1, :], u[:, :-1, :])).reshape(B, -1)
         if self.nh:
             A[:, self._A_h.ravel()] = self.dh(s, u).reshape(B, -1)
             g = np.concatenate([g, np.asarray(self._hfun(s, u)).reshape(B, -1)], axis=1)
@@ -941,7 +981,7 @@ class StageOCP:
         if s_meas is not None:
             sp = np.array(s_meas, float).reshape(B, nx)
         else:
-            sp = np.asarray(self.F(X[:, 0, :nx], X[:, 0, nx:]), float)
+            sp = np.asarray(self._F(X[:, 0, :nx], X[:, 0, nx:], self._stage_data(B)[:, 0] if self.transition_data else None), float)
             if w is not None:
                 sp = sp + np.asarray(w, float).reshape(B, nx)
         up = np.where(ok[:, None], X[:, 1, nx:], X[:, 0, nx:])
@@ -950,7 +990,7 @@ class StageOCP:
         Xo[:, 1:N - 1] = X[:, 2:]
         Xo[:, N - 1] = X[:, N - 1]
         if tail == "rollout":
-            Xo[:, N - 1, :nx] = self.F(X[:, N - 1, :nx], X[:, N - 1, nx:])
+            Xo[:, N - 1, :nx] = self._F(X[:, N - 1, :nx], X[:, N - 1, nx:], self._stage_data(B)[:, N - 1] if self.transition_data else None)
         out = {"x": Xo.reshape(B, -1), "lbx": np.array(lbx, float), "ubx": np.array(ubx, float), "applied": X[:, 0].copy()}
         out["lbx"][:, :f] = Xo[:, 0]; out["ubx"][:, :f] = Xo[:, 0]
         if self.pref and p is not None:
@@ -1021,10 +1061,11 @@ class StageOCP:
         out[:, 0] = clip(X[:, 0], 0, fr)
         s, u0 = out[:, 0, :nx].copy(), out[:, 0, nx:].copy()
         div = np.full(B, -1, np.int64)
+        D = self._stage_data(B) if self.transition_data else None      # step k takes row k
         with np.errstate(all="ignore"):
             for k in range(N - 1):
                 u = out[:, k, nx:]
-                sn = np.asarray(self.F(s, u), float)
+                sn = np.asarray(self._F(s, u, D[:, k] if D is not None else None), float)
                 bad = (div < 0) & ~(np.isfinite(s).all(axis=1) & np.isfinite(u).all(axis=1) & np.isfinite(sn).all(axis=1))
                 div = np.where(bad, k, div)
                 s = np.where((div < 0)[:, None], sn, s)
@@ -1242,6 +1283,57 @@ class CartPole(StageOCP):
         thdd = (self.grav * sn - cs * tmp) / (self.length * (4.0 / 3.0 - self.mp * cs * cs / tot))
         xdd = tmp - self.mp * self.length * thdd * cs / tot
         return np.stack([xd, thd, xdd, thdd], axis=-1)
+
+    def frame_bounds(self):
+        return np.array([-2.4, -INF, -INF, -INF, -20.0]), np.array([2.4, INF, INF, INF, 20.0])
+
+
+class GridCartPole(StageOCP):
+    """The cart-pole on a non-uniform time grid h_k = h0 g^k (transition_data): fine steps near now, coarse steps far out.  The frame's
+    stage data d = [h_k] is the step of the transition k -> k + 1: in the model's own RK4, in the rate limit |u_{k+1} - u_k| / h_k <= rate (kfun)
+    and in the move penalty move (u_{k+1} - u_k)^2 / h_k (llink).  The diagonal weights of frame k are scaled by h_k / h0, so that the sum
+    approximates the same integral on every grid.  growth = 1 is the uniform grid; grid_rows gives the rows set_stage_data takes."""
+    nx = 4; nu = 1; name = "grid_cartpole"
+    mc = 1.0; mp = 0.1; length = 0.5; grav = 9.81
+    nsd = 1; sdata = np.array([0.02]); transition_data = True
+    nk = 1; rate = 400.0; k_lo = [-400.0]; k_hi = [400.0]
+    move = 1e-5
+
+    def __init__(self, N=20, h0=0.02, growth=1.0):
+        self.h0, self.growth = float(h0), float(growth)
+        self.steps = self.h0 * self.growth ** np.arange(int(N))
+        self.sdata = np.array([self.h0])
+        w = (self.steps / self.h0)[:, None]
+        super().__init__(N, h0, w * np.array([1.0, 10.0, 0.1, 0.1]), w * np.array([0.01]))
+
+    def grid_rows(self, batch):
+        """[batch, N, 1]: frame k's step length h_k, the same grid for every instance"""
+        return np.tile(self.steps[None, :, None], (int(batch), 1, 1))
+
+    def _rate(self, th, xd, thd, force):
+        sn, cs = np.sin(th), np.cos(th)
+        tot = self.mc + self.mp
+        tmp = (force + self.mp * self.length * thd * thd * sn) / tot
+        thdd = (self.grav * sn - cs * tmp) / (self.length * (4.0 / 3.0 - self.mp * cs * cs / tot))
+        return xd, thd, tmp - self.mp * self.length * thdd * cs / tot, thdd
+
+    def F(self, s, u):
+        """RK4 over the frame's own step h = self.sdata[0], component by component (h has the shape of a component)"""
+        h = self.sdata[0]
+        y = [s[..., i] for i in range(4)]
+        force = u[..., 0]
+        k1 = self._rate(y[1], y[2], y[3], force)
+        k2 = self._rate(*[y[i] + 0.5 * h * k1[i] for i in (1, 2, 3)], force)
+        k3 = self._rate(*[y[i] + 0.5 * h * k2[i] for i in (1, 2, 3)], force)
+        k4 = self._rate(*[y[i] + h * k3[i] for i in (1, 2, 3)], force)
+        return np.stack([y[i] + (h / 6.0) * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]) for i in range(4)], axis=-1)
+
+    def kfun(self, s, u, sn, un):
+        return np.stack([(un[..., 0] - u[..., 0]) / self.sdata[0]], axis=-1)
+
+    def llink(self, s, u, sn, un):
+        d = un[..., 0] - u[..., 0]
+        return self.move * d * d / self.sdata[0]
 
     def frame_bounds(self):
         return np.array([-2.4, -INF, -INF, -INF, -20.0]), np.array([2.4, INF, INF, INF, 20.0])

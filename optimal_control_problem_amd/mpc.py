@@ -15,10 +15,12 @@ from .sqp import DeviceSQPOptimizationSolver
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, options=None, batch=1, tail="rollout", shift=True, device=-1, codegen=None):
+    def __init__(self, model, options=None, batch=1, tail="rollout", shift=True, device=-1, codegen=None, shift_data=True):
         """model: a models.StageOCP (zoo, generated or per_frame_reference).  options: those of DeviceSQPOptimizationSolver, passed through
         (warm_start_admm, carry_rho, constant_matrices, keep_scaling, presolve_fixed_rows, ...); max_iter defaults to 1 SQP iteration per
-        tick and alpha to 1 (real-time iteration), skip_failed_steps to True (an infeasible QP keeps its iterate and holds the input)."""
+        tick and alpha to 1 (real-time iteration), skip_failed_steps to True (an infeasible QP keeps its iterate and holds the input).
+        shift_data=False: a tick does not shift the stored stage data -- rows that belong to horizon positions, not to world time (the step
+        lengths of a non-uniform time grid, models.StageOCP.transition_data); tick's d_new is then a ValueError."""
         import torch
         if tail not in ("repeat", "rollout"):
             raise ValueError("tail must be 'repeat' or 'rollout'")
@@ -27,7 +29,7 @@ class ClosedLoopMPC:
             raise ValueError("exact_hessian is not available in ClosedLoopMPC: the multiplier estimate would need its own shift in advance, and "
                              "running a tick with unshifted multipliers would be silently wrong")
         opts.setdefault("max_iter", 1); opts.setdefault("alpha", 1.0); opts.setdefault("skip_failed_steps", True)
-        self.model, self.batch, self.tail, self.shift = model, int(batch), tail, bool(shift)
+        self.model, self.batch, self.tail, self.shift, self.shift_data = model, int(batch), tail, bool(shift), bool(shift_data)
         self.sol = DeviceSQPOptimizationSolver(model, opts, batch=self.batch, device=device, codegen=codegen)
         self.ev, self.dev = self.sol.ev, self.sol.dev
         ev = self.ev
@@ -102,6 +104,8 @@ class ClosedLoopMPC:
         set only; omitted: the last row repeats); the set shifts with shift=False as well, like the references.  Returns device tensors, overwritten by the next tick:
         applied [B, f] (the frame that was applied), status, iters [B] of the tick's last QP, stage_cost [B] (the k = 0 cost term)."""
         import torch
+        if d_new is not None and not self.shift_data:
+            raise ValueError("d_new with shift_data=False: the stored rows belong to horizon positions and do not move")
         if not self._ready:
             raise RuntimeError("call reset(frame0, reference) first")
         sol, ev = self.sol, self.ev
@@ -117,7 +121,7 @@ class ClosedLoopMPC:
                    tail=self.tail, p=None if pf else self.p, p_in=self.p if pf else None, p_out=self._p2, r_new=self._arr(r_new, ev.nx) if pf else None,
                    dw_in=sol.dw if moved else None, dw_out=self._dw2 if moved else None, y_in=sol.y if moved else None,
                    y_out=self._y2 if moved else None, applied=self.applied, stage_cost=self.stage_cost, stream=stream)
-        if self._has_data:       # after advance, whose stage_cost log still took d_0
+        if self._has_data and self.shift_data:       # after advance, whose stage_cost log and plant step still took d_0
             ev.shift_stage_data(self._arr(d_new, ev.nsd), stream=stream)
         if pf:
             self.p, self._p2 = self._p2, self.p

@@ -71,6 +71,7 @@ def _bind(L):
     L.mpcqp_stage_data_count.argtypes = [vp]
     L.mpcqp_stage_set_stage_data.argtypes = [vp, C.c_int, dp, C.c_int]
     L.mpcqp_stage_shift_data.argtypes = [vp, C.c_int, dp, vp]
+    L.mpcqp_stage_has_transition_data.argtypes = [vp]
     L.mpcqp_stage_dims.argtypes = [vp, vp]
     L.mpcqp_stage_has_cost.argtypes = [vp]
     L.mpcqp_stage_has_link_cost.argtypes = [vp]
@@ -118,6 +119,9 @@ def model_tape(model):
     nsd = int(getattr(model, "nsd", 0))
     if nsd:
         pkw = dict(pkw, nsd=nsd, sdata0=model.sdata, model=model)
+    # ... and with transition_data = True in F / cdyn, kfun and llink as well
+    if getattr(model, "transition_data", False):
+        pkw = dict(pkw, transition_data=True)
     return cg.trace(model.F, model.nx, model.nu, model.hfun if model.nh else None, model.nh, h_lo[0] if model.nh else None, h_hi[0] if model.nh else None,
                     lcost=model.lcost if general and not gn else None, lterm=model.lterm if general and not gn else None,
                     **({"rcost": model.rcost, "rterm": model.rterm} if gn else {}),
@@ -210,6 +214,7 @@ class StageEvaluator:
         self.gauss_newton = self.nr > 0
         self.param_count = int(L.mpcqp_stage_param_count(self._h))      # parameters per instance (mpcqp_stage_set_instance_params); 0: none
         self.nsd = int(L.mpcqp_stage_data_count(self._h))               # stage-data values per frame (mpcqp_stage_set_stage_data); 0: none
+        self.transition_data = bool(L.mpcqp_stage_has_transition_data(self._h))      # F, kfun and llink read the rows too (model.transition_data)
         self.has_convexify = bool(L.mpcqp_stage_has_convexify(self._h))  # the library carries the launcher of mpcqp_stage_convexify (model.convexify)
         self.has_exact_hessian = bool(L.mpcqp_stage_has_exact_hessian(self._h))  # ... and the launchers of mpcqp_stage_lagrangian (model.exact_hessian)
         self.horizon = int(d.horizon)
