@@ -749,6 +749,77 @@ typedef struct mpcqp_kkt_args {
 int mpcqp_stage_kkt(mpcqp_stage *s, int batch, const mpcqp_kkt_args *a, void *stream);
 int mpcqp_nlp_kkt(mpcqp_nlp *s, int batch, const mpcqp_kkt_args *a, void *stream);
 
+/* Time-varying LQR feedback gains along the plan, one backward Riccati sweep per instance in one kernel (opt-in; the reference hands the plant
+ * X_0 only and has no such step), and the feedback law u = u_k + K_k (s - s_k) applied in a second one (DESIGN 6.29;
+ * models.StageOCP.riccati_gains and StageOCP.feedback are the host statements).  The gains are those of the equality-constrained tangent problem
+ * of the local system mpcqp_stage_eval wrote (and mpcqp_stage_convexify / mpcqp_stage_lagrangian may have made positive definite):
+ * inequalities enter only through the clamp.  Per instance b of a handle with N frames, f = nx + nu:
+ *   H_k [f x f]      frame k's block of P: rows and columns np + k f + (0 .. f-1).  Both triangles are stored and each entry is read from its
+ *                    own slot; an entry outside the pattern is 0
+ *   [A_k B_k]        [nx x f], MINUS the dynamics block of A: rows n + k nx + r, columns np + k f + c, k = 0 .. N-2 (mpcqp_stage_eval writes
+ *                    -dF there); an entry outside the pattern is 0
+ *   not read         the reference columns and rows, the path rows, the link rows (nk > 0 is accepted, the rows are ignored like the path
+ *                    rows), q, l, u
+ * Backwards from k = N-1, with Q = [Q_ss Q_su; Q_us Q_uu] split at nx and acc(...) a sum in ascending index order from 0:
+ *   Q          k = N-1: Q = H_{N-1} as read.  k < N-1: T = V_{k+1} [A_k B_k], then for r <= c
+ *              Q[r][c] = Q[c][r] = H_k[r][c] + acc_j [A_k B_k][j][r] T[j][c]: the upper triangle is formed once and mirrored, so Q is
+ *              symmetric bit for bit (the lower triangle of H_k is then not used)
+ *   clamp      optional, needs x, lbx, ubx together: input i of frame k is clamped when x - lbx <= clamp_tol or ubx - x <= clamp_tol at entry
+ *              k f + nx + i (a NaN there compares false: not clamped); a pinned first frame is therefore always clamped.  Row and column i of
+ *              Q_uu become the unit vector and row i of Q_us becomes 0 -- the control-limited DDP rule: row i of K_k is 0 and the input does
+ *              not enter V_k
+ *   reg        added to the diagonal of Q_uu, free inputs only (>= 0, default 0)
+ *   Cholesky   Q_uu = U' U from the upper triangle of Q_uu, by rows, together with the forward solve Y = U'^-1 Q_us: for jj = 0 .. nu-1
+ *              d = Q_uu[jj][jj] - acc_t U[t][jj]^2 (t < jj);  the frame FAILS when !(d > thr), thr = MPCQP_RICCATI_PIVOT * max(1, max_i |Q_uu[i][i]|)
+ *              (the diagonal after clamp and reg, a NaN entry skipped by the max; a non-finite pivot fails);  U[jj][jj] = sqrt(d);
+ *              M[jj][c] = (M[jj][c] - acc_t U[t][jj] M[t][c]) / U[jj][jj] for the columns c > jj of Q_uu (giving U) and every column of Q_us (giving Y)
+ *   gain       K_k = -U^-1 Y [nu x nx] by back substitution: z_i = (Y[i][j] - acc_t U[i][t] z_t (t = i+1 .. nu-1)) / U[i][i], K_k[i][j] = -z_i
+ *   value      V_k[r][c] = V_k[c][r] = Q_ss[r][c] - acc_i Y[i][r] Y[i][c] for r <= c: symmetric bit for bit
+ *   failure    failed[b] = the frame whose pivot failed (the first one met, walking backwards), -1 if none.  K_j and V_j for every j <= failed[b]
+ *              are written as zeros -- a zero gain is the open-loop plan, the safe answer; the frames above keep what was computed
+ *   frozen     an instance with frozen[b] != 0 is neither read nor written
+ * The device runs the same operations with fused multiply-adds, so it agrees with the statement to rounding, not bit for bit.  One lane group of
+ * 16 (f <= 16) or 32 lanes per instance, lanes own columns, the tiles V, Q, [A B], T in LDS; one writer per element, no atomics: bitwise repeatable
+ * and independent of the batch size and of the instance's position.  The handle builds two slot tables from its own pattern on the first call
+ * and frees them in mpcqp_stage_destroy: a first call while `stream` is capturing answers MPCQP_ERR_STATE (call once before the capture); after
+ * that nothing is allocated and a captured graph replays the launch.  No model code takes part, so a generated library needs no export.
+ * MPCQP_ERR_ARG for a null s, a, P, A or K, a partial clamp triple, a negative (or NaN) clamp_tol or reg, batch < 1; MPCQP_ERR_LIMIT (with the
+ * reason) for a handle with a link cost (mpcqp_stage_has_link_cost): its P couples neighbouring frames, and a sweep that dropped those blocks
+ * would be silently wrong. */
+#define MPCQP_RICCATI_PIVOT 1e-12
+typedef struct mpcqp_stage_riccati_args {
+  const double *P, *A;          /* [batch * nnzP], [batch * nnzA] on the handle's pattern      */
+  const double *x, *lbx, *ubx;  /* [batch * nvar], all three or none: the clamp                */
+  double clamp_tol, reg;
+  const int *frozen;            /* [batch], optional: nonzero = neither read nor written       */
+  double *K;                    /* [batch * N * nu * nx], (k, i, j) row-major, required        */
+  double *V;                    /* [batch * N * nx * nx], optional                             */
+  int *failed;                  /* [batch], optional                                           */
+} mpcqp_stage_riccati_args;
+int mpcqp_stage_riccati(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_args *a, void *stream);
+/* The feedback law at one frame, one thread per (instance, input): with row(v, stride) = v + b * stride,
+ *   acc = acc_j K[b][k][i][j] * (s[j] - s_nom[j])     (each product and each sum rounded, no fused multiply-add: bitwise the host statement)
+ *   u   = clip(u_nom[i] + acc), clip the two selects of mpcqp_stage_rollout against lo[i] / hi[i] (the identity without the pair)
+ *   x_out[b * nvar + nx + i] = u, and the same entry of lbx[b] and ubx[b] when that pair is given -- the corrected input is what the next tick
+ *   sees pinned;  du[b * nu + i] = u - u_nom[i] when given.
+ * s, s_nom, u_nom, lo, hi are pointers with row strides (in doubles), so a caller points them into its trajectory buffers and bound arrays without
+ * copies; they may lie inside x_out, lbx, ubx as long as no entry that is written (nx .. f-1 of each row) is also read through another name.
+ * k is one frame for the launch.  An instance whose sweep failed at a frame >= k has a zero gain there and gets clip(u_nom).  Nothing is
+ * allocated: a captured graph replays it.  MPCQP_ERR_ARG for a null s, a, K, s, s_nom, u_nom or x_out, only one of lo / hi or of lbx / ubx,
+ * batch < 1, k outside 0 .. N-1. */
+typedef struct mpcqp_stage_feedback_args {
+  const double *K;              /* [batch * N * nu * nx], what mpcqp_stage_riccati wrote        */
+  int k;                        /* the frame whose gain is applied                             */
+  const double *s, *s_nom, *u_nom;                 /* rows of nx, nx, nu doubles               */
+  long s_stride, s_nom_stride, u_nom_stride;       /* distance between two instances' rows     */
+  const double *lo, *hi;        /* rows of nu doubles, optional pair                           */
+  long lo_stride, hi_stride;
+  double *x_out;                /* [batch * nvar]: entries nx .. f-1 of each row are written    */
+  double *lbx, *ubx;            /* [batch * nvar], optional pair: the same entries              */
+  double *du;                   /* [batch * nu], optional                                      */
+} mpcqp_stage_feedback_args;
+int mpcqp_stage_feedback(mpcqp_stage *s, int batch, const mpcqp_stage_feedback_args *a, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Structured stage form: the same QP, given by its stage blocks instead of CSC value arrays.
  *

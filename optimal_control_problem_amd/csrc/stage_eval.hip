@@ -17,6 +17,7 @@
 #include "../../include/mpcqp.h"
 #include "common.hpp"
 #include "stage_kernels.hpp"
+#include "stage_riccati.hpp"
 
 // The launchers a generated library exports (model == MPCQP_MODEL_USER), one per operation: the handle's constants, the batch, the operation's
 // argument block (convexify: then the handle's tables and scratch; lagrangian: then the curvature's slot table and the convexification's tables and
@@ -84,6 +85,7 @@ struct mpcqp_stage {
   bool exact = false;
   int *dlslots = nullptr;
   int *dkkt = nullptr;                // Ap and Ai on the device for mpcqp_stage_kkt
+  int *dric = nullptr;                // the slot tables of mpcqp_stage_riccati, [N f f] of P then [(N - 1) nx f] of A, built by its first call
 };
 
 // a launch may not be larger than a stored parameter set
@@ -406,6 +408,7 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   if (s->dcvx) (void)hipFree(s->dcvx);
   if (s->dlslots) (void)hipFree(s->dlslots);
   if (s->dkkt) (void)hipFree(s->dkkt);
+  if (s->dric) (void)hipFree(s->dric);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -694,6 +697,76 @@ int mpcqp_stage_lagrangian(mpcqp_stage *s, int batch, const mpcqp_stage_lagrangi
 int mpcqp_stage_kkt(mpcqp_stage *s, int batch, const mpcqp_kkt_args *a, void *stream) {
   if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
   return mpcqp_kkt_run(s->device, s->sd.n, s->sd.m, s->sd.np, s->sd.nnzA, s->dkkt, batch, a, stream);
+}
+
+// Slot tables of mpcqp_stage_riccati (StageRicTab): H_k[r][c] sits in column np + k f + c, row np + k f + r of P, -[A_k B_k][r][c] in column
+// np + k f + c, row n + k nx + r of A; both are found in the pattern itself, -1 where it has no such entry.
+static int stage_build_riccati_tables(mpcqp_stage *s) {
+  const StageDev &sd = s->sd;
+  const int f = sd.f, nx = sd.nx, N = sd.N;
+  const size_t np_ = (size_t)N * f * f;
+  std::vector<int> tab(np_ + (size_t)(N - 1) * nx * f, -1);
+  auto find = [](const std::vector<int> &cp, const std::vector<int> &ri, int row, int col) {
+    for (int e = cp[col]; e < cp[col + 1]; e++) if (ri[e] == row) return e;
+    return -1;
+  };
+  for (int k = 0; k < N; k++)
+    for (int r = 0; r < f; r++)
+      for (int c = 0; c < f; c++) tab[((size_t)k * f + r) * f + c] = find(s->Pp, s->Pi, sd.np + k * f + r, sd.np + k * f + c);
+  for (int k = 0; k < N - 1; k++)
+    for (int r = 0; r < nx; r++)
+      for (int c = 0; c < f; c++) tab[np_ + ((size_t)k * nx + r) * f + c] = find(s->Ap, s->Ai, sd.n + k * nx + r, sd.np + k * f + c);
+  int *d = nullptr;
+  if (hipMalloc(&d, tab.size() * sizeof(int)) != hipSuccess) return mpcqp_set_error(MPCQP_ERR_HIP, "hipMalloc of the Riccati slot tables failed");
+  if (hipMemcpy(d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return mpcqp_set_error(MPCQP_ERR_HIP, "upload of the Riccati slot tables failed");
+  }
+  s->dric = d;
+  return MPCQP_OK;
+}
+
+// the feedback gains along the plan (stage_riccati.hpp; no model code takes part, so a generated library needs no export)
+int mpcqp_stage_riccati(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (!a->P || !a->A || !a->K) return mpcqp_set_error(MPCQP_ERR_ARG, "P, A and K are required");
+  if (!((a->x && a->lbx && a->ubx) || (!a->x && !a->lbx && !a->ubx))) return mpcqp_set_error(MPCQP_ERR_ARG, "the clamp needs x, lbx and ubx: give all three or none");
+  if (!(a->clamp_tol >= 0.0) || !(a->reg >= 0.0)) return mpcqp_set_error(MPCQP_ERR_ARG, "clamp_tol and reg must not be negative");
+  if (s->link_cost)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "this handle has a link cost: its P couples neighbouring frames, and a Riccati sweep over the frame blocks alone would drop those terms");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (!s->dric) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    MPCQP_HIPCHK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+      return mpcqp_set_error(MPCQP_ERR_STATE, "the first mpcqp_stage_riccati of a handle builds its slot tables and may not run while the stream is capturing: call it once before the capture");
+    if (int rc = stage_build_riccati_tables(s)) return rc;
+  }
+  const StageDev &sd = s->sd;
+  const StageRicTab tab{s->dric, s->dric + (size_t)sd.N * sd.f * sd.f};
+  const hipError_t e = sd.f <= 8 ? stage_launch_riccati<16, 8>(sd, batch, *a, tab, st)
+                     : sd.f <= 16 ? stage_launch_riccati<16, 16>(sd, batch, *a, tab, st) : stage_launch_riccati<32, 24>(sd, batch, *a, tab, st);
+  MPCQP_HIPCHK(e);
+  return MPCQP_OK;
+}
+
+int mpcqp_stage_feedback(mpcqp_stage *s, int batch, const mpcqp_stage_feedback_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (!a->K || !a->s || !a->s_nom || !a->u_nom || !a->x_out) return mpcqp_set_error(MPCQP_ERR_ARG, "K, s, s_nom, u_nom and x_out are required");
+  if ((a->lo == nullptr) != (a->hi == nullptr) || (a->lbx == nullptr) != (a->ubx == nullptr))
+    return mpcqp_set_error(MPCQP_ERR_ARG, "give both lo and hi (lbx and ubx) or neither");
+  const StageDev &sd = s->sd;
+  if (a->k < 0 || a->k >= sd.N) return mpcqp_set_error(MPCQP_ERR_ARG, "k must be a frame of the horizon, 0 .. N - 1");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  const long tot = (long)batch * sd.nu;
+  stage_feedback_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, (hipStream_t)stream>>>(batch, sd.N, sd.nx, sd.nu, sd.nvar, *a);
+  MPCQP_HIPCHK(hipGetLastError());
+  return MPCQP_OK;
 }
 
 }  // extern "C"

@@ -1080,6 +1080,148 @@ class StageOCP:
             out = np.where(fz[:, None], x, out); div = np.where(fz, -1, div); viol = np.where(fz, 0.0, viol)
         return {"x": out, "diverged": div.astype(np.int32), "box_viol": viol}
 
+    # -- the feedback gains along the plan (include/mpcqp.h, mpcqp_stage_riccati / mpcqp_stage_feedback; csrc/stage_riccati.hpp) ----------
+    RICCATI_PIVOT = 1e-12      # MPCQP_RICCATI_PIVOT
+
+    def _riccati_slots(self):
+        """(pslot [N, f, f], aslot [N - 1, nx, f]): the slot of P that holds H_k[r][c] and the slot of A that holds -[A_k B_k][r][c]; -1 where the
+        pattern has no such entry (the tables the handle builds on the device)"""
+        if getattr(self, "_ric_slots", None) is None:
+            N, f, npp = self.N, self.f, self.np
+            pslot = np.full((N, f, f), -1, np.int64)
+            for k in range(N):
+                for c in range(f):
+                    col = npp + k * f + c
+                    for e in range(self.Pp[col], self.Pp[col + 1]):
+                        r = int(self.Pi[e]) - npp - k * f
+                        if 0 <= r < f:
+                            pslot[k, r, c] = e
+            self._ric_slots = (pslot, self._A_blk.copy())
+        return self._ric_slots
+
+    def riccati_gains(self, P, A, x=None, lbx=None, ubx=None, clamp_tol=0.0, reg=0.0, frozen=None):
+        """Host statement of mpcqp_stage_riccati (include/mpcqp.h has the rule in full): the time-varying LQR gains of the equality-constrained
+        tangent problem of a local system, P [B, nnzP] and A [B, nnzA] on this model's pattern.  x, lbx, ubx [B, nvar] (all three or none): an
+        input within clamp_tol of a bound is clamped -- its row of K_k is 0 and it does not enter V_k.  reg >= 0 is added to the diagonal of
+        Q_uu (free inputs).  Returns dict K [B, N, nu, nx], V [B, N, nx, nx], failed [B] (the frame whose pivot failed, -1: none; K and V are
+        zero at and below it).  frozen [B]: an instance with a nonzero entry reports zeros and -1 (the device leaves its entries as they were).
+        Sums run in ascending index order from 0, as in the header."""
+        if self.link_cost:
+            raise ValueError("riccati_gains: this model has a link cost: its P couples neighbouring frames, and a sweep over the frame blocks alone "
+                             "would drop those terms")
+        if len({x is None, lbx is None, ubx is None}) != 1:
+            raise ValueError("the clamp needs x, lbx and ubx: give all three or none")
+        if not (clamp_tol >= 0.0) or not (reg >= 0.0):
+            raise ValueError("clamp_tol and reg must not be negative")
+        P = np.asarray(P, float); A = np.asarray(A, float)
+        B, N, nx, nu, f = P.shape[0], self.N, self.nx, self.nu, self.f
+        if P.shape != (B, len(self.Pi)) or A.shape != (B, len(self.Ai)):
+            raise ValueError("P, A: expected shapes [B, %d] and [B, %d] (dimension mismatch)" % (len(self.Pi), len(self.Ai)))
+        pslot, aslot = self._riccati_slots()
+        Pz = np.concatenate([P, np.zeros((B, 1))], axis=1)      # slot -1 reads the appended zero
+        clamp = x is not None
+        if clamp:
+            X, LB, UB = [np.asarray(v, float).reshape(B, N, f)[:, :, nx:] for v in (x, lbx, ubx)]
+        K = np.zeros((B, N, nu, nx)); Vout = np.zeros((B, N, nx, nx)); failed = np.full(B, -1, np.int64)
+        alive = np.ones(B, bool) if frozen is None else np.asarray(frozen).reshape(B) == 0
+        V = np.zeros((B, nx, nx))
+        iu, ju = np.triu_indices(f)
+        ix, jx = np.triu_indices(nx)
+        dg = np.arange(nu)
+
+        def mirrored(M, i, j):
+            out = np.empty_like(M)
+            out[:, i, j] = M[:, i, j]; out[:, j, i] = M[:, i, j]
+            return out
+
+        with np.errstate(all="ignore"):
+            for k in range(N - 1, -1, -1):
+                Q = Pz[:, pslot[k]]
+                if k < N - 1:
+                    AB = -A[:, aslot[k]]
+                    T = np.zeros((B, nx, f))
+                    for j in range(nx):
+                        T = T + V[:, :, j, None] * AB[:, j, None, :]
+                    acc = np.zeros((B, f, f))
+                    for j in range(nx):
+                        acc = acc + AB[:, j, :, None] * T[:, j, None, :]
+                    Q = mirrored(Q + acc, iu, ju)
+                Qss = Q[:, :nx, :nx]
+                M = Q[:, nx:, :].copy()      # the input rows [Q_us Q_uu]: they become [Y U]
+                if clamp:
+                    cm = (X[:, k] - LB[:, k] <= clamp_tol) | (UB[:, k] - X[:, k] <= clamp_tol)
+                    M[:, :, :nx] = np.where(cm[:, :, None], 0.0, M[:, :, :nx])
+                    M[:, :, nx:] = np.where(cm[:, :, None] | cm[:, None, :], np.eye(nu), M[:, :, nx:])
+                else:
+                    cm = np.zeros((B, nu), bool)
+                M[:, dg, nx + dg] = M[:, dg, nx + dg] + np.where(cm, 0.0, reg)
+                dmax = np.ones(B)
+                for i in range(nu):
+                    v = np.abs(M[:, i, nx + i])
+                    dmax = np.where(v > dmax, v, dmax)
+                thr = self.RICCATI_PIVOT * dmax
+                bad = np.zeros(B, bool)
+                ud = np.zeros((B, nu))
+                for jj in range(nu):
+                    acc = np.zeros(B)
+                    for t in range(jj):
+                        acc = acc + M[:, t, nx + jj] * M[:, t, nx + jj]
+                    d = M[:, jj, nx + jj] - acc
+                    bad |= ~(d > thr)
+                    ud[:, jj] = np.sqrt(d)
+                    s = np.zeros((B, f))
+                    for t in range(jj):
+                        s = s + M[:, t, nx + jj, None] * M[:, t, :]
+                    new = (M[:, jj, :] - s) / ud[:, jj, None]
+                    cols = list(range(nx)) + list(range(nx + jj + 1, f))
+                    M[:, jj, cols] = new[:, cols]
+                Y = M[:, :, :nx]
+                Z = np.zeros((B, nu, nx))
+                for i in range(nu - 1, -1, -1):
+                    s = np.zeros((B, nx))
+                    for t in range(i + 1, nu):
+                        s = s + M[:, i, nx + t, None] * Z[:, t, :]
+                    Z[:, i, :] = (Y[:, i, :] - s) / ud[:, i, None]
+                acc = np.zeros((B, nx, nx))
+                for i in range(nu):
+                    acc = acc + Y[:, i, :, None] * Y[:, i, None, :]
+                Vn = mirrored(Qss - acc, ix, jx)
+                failed = np.where(alive & (failed < 0) & bad, k, failed)
+                ok = alive & (failed < 0)
+                K[ok, k] = -Z[ok]; Vout[ok, k] = Vn[ok]
+                V = np.where(ok[:, None, None], Vn, 0.0)
+        return {"K": K, "V": Vout, "failed": failed.astype(np.int32)}
+
+    def feedback(self, K, k, s, s_nom, u_nom, lo=None, hi=None, x=None, lbx=None, ubx=None):
+        """Host statement of mpcqp_stage_feedback: u = clip(u_nom + K[:, k] (s - s_nom)) with the sum over the state entries in ascending order,
+        every product and sum rounded; clip is the two selects of `rollout` against lo / hi [B, nu] (both or neither).  Returns dict u, du = u - u_nom
+        [B, nu], and -- for each of x, lbx, ubx [B, nvar] that is given -- a copy with u written into the input entries of the first frame."""
+        if (lo is None) != (hi is None):
+            raise ValueError("give both lo and hi or neither")
+        if (lbx is None) != (ubx is None):
+            raise ValueError("give both lbx and ubx or neither")
+        k = int(k)
+        if not 0 <= k < self.N:
+            raise ValueError("k must be a frame of the horizon, 0 .. N - 1")
+        K = np.asarray(K, float).reshape(-1, self.N, self.nu, self.nx)
+        B, nx, nu = K.shape[0], self.nx, self.nu
+        s = np.asarray(s, float).reshape(B, nx); s_nom = np.asarray(s_nom, float).reshape(B, nx); u_nom = np.asarray(u_nom, float).reshape(B, nu)
+        acc = np.zeros((B, nu))
+        for j in range(nx):
+            acc = acc + K[:, k, :, j] * (s[:, j] - s_nom[:, j])[:, None]
+        u = u_nom + acc
+        if lo is not None:
+            lo = np.asarray(lo, float).reshape(B, nu); hi = np.asarray(hi, float).reshape(B, nu)
+            u = np.where(u < lo, lo, u)
+            u = np.where(u > hi, hi, u)
+        out = {"u": u, "du": u - u_nom}
+        for name, v in (("x", x), ("lbx", lbx), ("ubx", ubx)):
+            if v is not None:
+                c = np.array(v, float).reshape(B, self.nvar)
+                c[:, nx:nx + nu] = u
+                out[name] = c
+        return out
+
     # -- the per-instance merit line search (include/mpcqp.h, mpcqp_stage_linesearch; csrc/stage_kernels.hpp stage_linesearch_kernel) ----------
     LINE_SEARCH_DEFAULTS = {"candidates": 4, "beta": 0.5, "c1": 1e-4, "mu_min": 1.0, "mu_factor": 1.1}
 

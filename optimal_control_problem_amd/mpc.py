@@ -15,13 +15,30 @@ from .sqp import DeviceSQPOptimizationSolver
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, options=None, batch=1, tail="rollout", shift=True, device=-1, codegen=None, shift_data=True):
+    def __init__(self, model, options=None, batch=1, tail="rollout", shift=True, device=-1, codegen=None, shift_data=True, feedback=None):
         """model: a models.StageOCP (zoo, generated or per_frame_reference).  options: those of DeviceSQPOptimizationSolver, passed through
         (warm_start_admm, carry_rho, constant_matrices, keep_scaling, presolve_fixed_rows, ...); max_iter defaults to 1 SQP iteration per
         tick and alpha to 1 (real-time iteration), skip_failed_steps to True (an infeasible QP keeps its iterate and holds the input).
         shift_data=False: a tick does not shift the stored stage data -- rows that belong to horizon positions, not to world time (the step
-        lengths of a non-uniform time grid, models.StageOCP.transition_data); tick's d_new is then a ValueError."""
+        lengths of a non-uniform time grid, models.StageOCP.transition_data); tick's d_new is then a ValueError.
+        feedback=True or {"clamp_tol": ..., "reg": ...}: every tick also computes the time-varying LQR gains around its plan (one
+        mpcqp_stage_riccati on the tick's local system; K, gain_failed) and hold() becomes available -- a plant step without a solve that tracks
+        the plan with u = u_k + K_k (s - s_k).  Without the option a tick is what it was, not a launch more."""
         import torch
+        if feedback is not None and feedback is not True and not isinstance(feedback, dict):
+            raise ValueError("feedback: expected None, True or a dict with clamp_tol and / or reg")
+        fb = {} if feedback is True else feedback
+        if fb is not None:
+            unknown = set(fb) - {"clamp_tol", "reg"}
+            if unknown:
+                raise ValueError("feedback: unknown keys %s (clamp_tol and reg are the options)" % sorted(unknown))
+            if not (float(fb.get("clamp_tol", 0.0)) >= 0.0) or not (float(fb.get("reg", 0.0)) >= 0.0):
+                raise ValueError("feedback: clamp_tol and reg must not be negative")
+            if getattr(model, "link_cost", False):
+                raise ValueError("feedback: this model has a link cost: its Hessian couples neighbouring frames, and the Riccati sweep over the frame "
+                                 "blocks alone would drop those terms")
+            fb = {"clamp_tol": float(fb.get("clamp_tol", 0.0)), "reg": float(fb.get("reg", 0.0))}
+        self.feedback = fb
         if tail not in ("repeat", "rollout"):
             raise ValueError("tail must be 'repeat' or 'rollout'")
         opts = dict(options or {})
@@ -43,6 +60,13 @@ class ClosedLoopMPC:
         self._ready = False
         self._has_data = False
         self.rollout_diverged = None; self.rollout_box_viol = None
+        # feedback: the gains of the last tick's plan, the frame that failed per instance, the inputs' correction of the last hold, the holds since
+        self.age = 0
+        if self.feedback is not None:
+            self.K = mk(B, ev.horizon, ev.nu, ev.nx)
+            self.gain_failed = torch.full((B,), -1, dtype=torch.int32, device=self.dev)
+            self.du = mk(B, ev.nu)
+            self.plan = mk(B, ev.nvar)
 
     def reset(self, frame0, reference=None, x0=None):
         """frame0 [B, f] (or [f]): the measured state and the input being applied, pinned as the first frame.  reference: p, [B, nx] -- or
@@ -67,6 +91,8 @@ class ClosedLoopMPC:
             r = self.ev.rollout(self.sol.x, lbx=self.lbx, ubx=self.ubx, inputs=shoot, stream=torch.cuda.current_stream(self.dev).cuda_stream)
             self.rollout_diverged, self.rollout_box_viol = r["diverged"], r["box_viol"]
         self.ticks = 0
+        self.age = 0
+        self._solved = False
         self._ready = True
 
     def set_instance_params(self, model=None, plant=None):
@@ -115,6 +141,11 @@ class ClosedLoopMPC:
             raise ValueError("d_new needs a stored set of stage data (set_stage_data)")
         sol.getOptimalSolution({"p": self.p, "lbx": self.lbx, "ubx": self.ubx, "lbg": self.lbg, "ubg": self.ubg}, to_host=False)
         stream = torch.cuda.current_stream(self.dev).cuda_stream
+        if self.feedback is not None:      # the gains around this tick's plan, from the system the solve just used; the clamp reads the new iterate
+            ev.riccati(sol.ls, x=sol.x, lbx=self.lbx, ubx=self.ubx, K=self.K, V=False, failed=self.gain_failed, stream=stream, **self.feedback)
+            self.plan.copy_(sol.x)
+        self.age = 0
+        self._solved = True
         pf = ev.per_frame_reference
         moved = self.shift and sol.warm_start_admm
         ev.advance(sol.x, self._x2, self.lbx, self.ubx, status=sol.status, s_meas=self._arr(measured, ev.nx), w=self._arr(disturbance, ev.nx),
@@ -133,6 +164,53 @@ class ClosedLoopMPC:
                 sol._start_clean = True          # advance left zeros where the QP failed: no NaN to wash out of the start
         self.ticks += 1
         return {"applied": self.applied, "status": sol.status, "iters": sol.iters, "stage_cost": self.stage_cost}
+
+    def hold(self, measured=None, disturbance=None, r_new=None, d_new=None):
+        """a plant step without a solve (feedback= only): the hand-over of tick with every instance taking its plan's next input, then one
+        mpcqp_stage_feedback launch that corrects the new first frame's input to u = clip(u_1 + K_k (s - s_1)), k = age + 1, age the holds since the
+        last tick: s the new first-frame state, (s_1, u_1) frame 1 of the trajectory before the shift, the clip frame 1's input box in lbx / ubx.
+        The corrected input is pinned in lbx / ubx like the rest of the first frame.  An instance whose sweep failed at a frame >= k has a zero
+        gain there and keeps the plan's input.  Arguments and the data shift as in tick.  Returns device tensors applied [B, f], du [B, nu] (the
+        correction), stage_cost [B]."""
+        import torch
+        if self.feedback is None:
+            raise ValueError("hold needs the feedback gains: create the controller with feedback=True")
+        if not self.shift:
+            raise ValueError("hold with shift=False: the plan does not move between ticks, so there is no next frame to track")
+        if not self._ready or not self._solved:
+            raise RuntimeError("hold follows a tick: call reset(frame0, reference) and tick() first")
+        sol, ev = self.sol, self.ev
+        k = self.age + 1
+        if k > ev.horizon - 2:
+            raise ValueError("hold: the plan is exhausted (%d holds since the last tick on a horizon of %d frames): tick() again" % (self.age, ev.horizon))
+        if d_new is not None and not self.shift_data:
+            raise ValueError("d_new with shift_data=False: the stored rows belong to horizon positions and do not move")
+        if r_new is not None and not ev.per_frame_reference:
+            raise ValueError("r_new belongs to per_frame_reference models")
+        if d_new is not None and not self._has_data:
+            raise ValueError("d_new needs a stored set of stage data (set_stage_data)")
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        pf = ev.per_frame_reference
+        moved = sol.warm_start_admm
+        nx, f = ev.nx, ev.nx + ev.nu
+        ev.advance(sol.x, self._x2, self.lbx, self.ubx, status=None, s_meas=self._arr(measured, ev.nx), w=self._arr(disturbance, ev.nx),
+                   tail=self.tail, p=None if pf else self.p, p_in=self.p if pf else None, p_out=self._p2, r_new=self._arr(r_new, ev.nx) if pf else None,
+                   dw_in=sol.dw if moved else None, dw_out=self._dw2 if moved else None, y_in=sol.y if moved else None,
+                   y_out=self._y2 if moved else None, applied=self.applied, stage_cost=self.stage_cost, stream=stream)
+        # advance wrote the first f entries of lbx / ubx only: frame 1 still carries the frame box
+        ev.feedback(self.K, k, self._x2[:, :nx], sol.x[:, f:f + nx], sol.x[:, f + nx:2 * f], self._x2, lo=self.lbx[:, f + nx:2 * f],
+                    hi=self.ubx[:, f + nx:2 * f], lbx=self.lbx, ubx=self.ubx, du=self.du, stream=stream)
+        if self._has_data and self.shift_data:
+            ev.shift_stage_data(self._arr(d_new, ev.nsd), stream=stream)
+        if pf:
+            self.p, self._p2 = self._p2, self.p
+        sol.x, self._x2 = self._x2, sol.x
+        if moved:
+            sol.dw, self._dw2 = self._dw2, sol.dw
+            sol.y, self._y2 = self._y2, sol.y
+            sol._start_clean = True
+        self.age += 1
+        return {"applied": self.applied, "du": self.du, "stage_cost": self.stage_cost}
 
     def close(self):
         self.sol.close()

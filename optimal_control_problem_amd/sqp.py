@@ -683,6 +683,24 @@ class DeviceSQPOptimizationSolver:
             return {"x": self.x, "f": self.f}
         return {"x": self.x.cpu().numpy(), "f": self.f.cpu().numpy()}
 
+    def feedbackGains(self, arg=None, **kw):
+        """extension: the time-varying LQR feedback gains u = u_k + K_k (s - s_k) around the plan, from the last evaluated local system (self.ls,
+        after convexify / lagrangian when those options are on): one StageEvaluator.riccati launch.  arg: the dict of getOptimalSolution; when it
+        carries lbx and ubx, inputs of the current iterate within clamp_tol of a bound get a zero gain.  kw: clamp_tol, reg, frozen, K, V, failed
+        as in StageEvaluator.riccati.  Returns {"K": [batch, N, nu, nx], "V": [batch, N, nx, nx], "failed": [batch] int32}, device tensors.
+        Stage OCPs only."""
+        import torch
+        if not hasattr(self.ev, "riccati"):
+            raise ValueError("feedback gains are limited to stage OCPs: a general evaluator (evaluator=, mpcqp_nlp_*) has no frames, dynamics blocks "
+                             "or inputs to sweep over")
+        if not self._have_start:
+            raise RuntimeError("feedbackGains needs an evaluated local system: call getOptimalSolution first")
+        ev = self.ev
+        clamp = {}
+        if arg is not None and "lbx" in arg and "ubx" in arg:
+            clamp = {"x": self.x, "lbx": self._dev(arg["lbx"], ev.nvar), "ubx": self._dev(arg["ubx"], ev.nvar)}
+        return ev.riccati(self.ls, stream=torch.cuda.current_stream(self.dev).cuda_stream, **clamp, **kw)
+
     def kkt(self, arg, tol=None):
         """the optimality residuals of the current iterate -- the point getOptimalSolution returned -- under the multipliers of the last QP: one
         evaluation plus one mpcqp_stage_kkt / mpcqp_nlp_kkt.  tol: as options["kkt_tol"] (default: the option's, else 1e-3).  Returns

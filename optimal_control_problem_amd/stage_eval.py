@@ -54,6 +54,25 @@ class LagrangianArgs(C.Structure):
                [(k, C.c_void_p) for k in ("touched", "lam_min")]
 
 
+class RiccatiArgs(C.Structure):
+    """mpcqp_stage_riccati_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("P", "A", "x", "lbx", "ubx")] + [("clamp_tol", C.c_double), ("reg", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("frozen", "K", "V", "failed")]
+
+
+class FeedbackArgs(C.Structure):
+    """mpcqp_stage_feedback_args (include/mpcqp.h)"""
+    _fields_ = [("K", C.c_void_p), ("k", C.c_int)] + [(k, C.c_void_p) for k in ("s", "s_nom", "u_nom")] + \
+               [(k, C.c_long) for k in ("s_stride", "s_nom_stride", "u_nom_stride")] + [("lo", C.c_void_p), ("hi", C.c_void_p)] + \
+               [("lo_stride", C.c_long), ("hi_stride", C.c_long)] + [(k, C.c_void_p) for k in ("x_out", "lbx", "ubx", "du")]
+
+
+def riccati_groups_per_block(f):
+    """instances one workgroup of the Riccati sweep holds (csrc/stage_riccati.hpp, stage_ric<W, FM>::G): 16 groups of 16 lanes for f <= 8, 4 for
+    f <= 16, else 2 groups of 32"""
+    return 16 if f <= 8 else 4 if f <= 16 else 2
+
+
 def _bind(L):
     if getattr(L, "_stage_bound", False):
         return L
@@ -88,6 +107,8 @@ def _bind(L):
     L.mpcqp_stage_has_exact_hessian.argtypes = [vp]
     L.mpcqp_stage_lagrangian.argtypes = [vp, C.c_int, C.POINTER(LagrangianArgs), vp]
     L.mpcqp_stage_kkt.argtypes = [vp, C.c_int, vp, vp]
+    L.mpcqp_stage_riccati.argtypes = [vp, C.c_int, C.POINTER(RiccatiArgs), vp]
+    L.mpcqp_stage_feedback.argtypes = [vp, C.c_int, C.POINTER(FeedbackArgs), vp]
     L._stage_bound = True
     return L
 
@@ -461,3 +482,83 @@ class StageEvaluator:
         optional): an instance with a nonzero entry is neither read nor written."""
         from .kkt import device_kkt
         return device_kkt(_lib.lib().mpcqp_stage_kkt, self, ls, y, tol, out, frozen, stream)
+
+    def riccati(self, ls_or_P, A=None, x=None, lbx=None, ubx=None, clamp_tol=0.0, reg=0.0, frozen=None, K=None, V=None, failed=None, stream=None):
+        """the time-varying LQR feedback gains along the plan, one backward Riccati sweep per instance in one kernel (mpcqp_stage_riccati;
+        models.StageOCP.riccati_gains is its host statement).  ls_or_P: the dict eval wrote (P and A are taken from it) or P [B, nnzP] with
+        A [B, nnzA].  x, lbx, ubx [B, nvar], all three or none: inputs within clamp_tol of a bound get a zero row of K.  frozen (int32 [B]): an
+        instance with a nonzero entry is neither read nor written.  Returns dict K [B, horizon, nu, nx], V [B, horizon, nx, nx], failed (int32
+        [B]), device tensors (K, V, failed: tensors to write into; V=False: the value matrices are not written and "V" is None).  The first call of a handle builds its slot tables and may not run under
+        stream capture.  Arrays are contiguous float64 CUDA tensors."""
+        import torch
+        if isinstance(ls_or_P, dict):
+            if A is not None:
+                raise ValueError("give the local system's dict, or P and A, not both")
+            P, A = ls_or_P["P"], ls_or_P["A"]
+        else:
+            P = ls_or_P
+        if A is None:
+            raise ValueError("A is required with P")
+        if len({x is None, lbx is None, ubx is None}) != 1:
+            raise ValueError("the clamp needs x, lbx and ubx: give all three or none")
+        if not isinstance(P, torch.Tensor) or P.dim() != 2:
+            raise ValueError("P: expected a contiguous float64 CUDA tensor of shape (B, %d)" % self.nnzP)
+        B, N = P.shape[0], self.horizon
+        a = RiccatiArgs()
+        a.P, a.A = _check(P, (B, self.nnzP), "P"), _check(A, (B, self.nnzA), "A")
+        for name, t in (("x", x), ("lbx", lbx), ("ubx", ubx)):
+            if t is not None:
+                setattr(a, name, _check(t, (B, self.nvar), name))
+        a.clamp_tol, a.reg = float(clamp_tol), float(reg)
+        if K is None:
+            K = torch.zeros((B, N, self.nu, self.nx), dtype=torch.float64, device=P.device)
+        if V is None:
+            V = torch.zeros((B, N, self.nx, self.nx), dtype=torch.float64, device=P.device)
+        elif V is False:                                 # the value matrices are not wanted: two thirds of the sweep's stores
+            V = None
+        if failed is None:
+            failed = torch.full((B,), -1, dtype=torch.int32, device=P.device)
+        a.K = _check(K, (B, N, self.nu, self.nx), "K")
+        if V is not None:
+            a.V = _check(V, (B, N, self.nx, self.nx), "V")
+        a.failed = _check_int32(failed, B, "failed")
+        if frozen is not None:
+            a.frozen = _check_int32(frozen, B, "frozen")
+        _lib.check(_lib.lib().mpcqp_stage_riccati(self._h, B, C.byref(a), stream))
+        return {"K": K, "V": V, "failed": failed}
+
+    @staticmethod
+    def _rows(t, w, B, name):
+        """pointer and row stride of a [B, w] float64 CUDA view whose rows are contiguous (a slice of a trajectory or bound array)"""
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and tuple(t.shape) == (B, w) and t.stride(1) == 1):
+            raise ValueError("%s: expected a float64 CUDA tensor of shape (%d, %d) with contiguous rows" % (name, B, w))
+        return t.data_ptr(), int(t.stride(0))
+
+    def feedback(self, K, k, s, s_nom, u_nom, x_out, lo=None, hi=None, lbx=None, ubx=None, du=None, stream=None):
+        """u = clip(u_nom + K[:, k] (s - s_nom)) in one kernel (mpcqp_stage_feedback; models.StageOCP.feedback is its host statement, bit for
+        bit).  s, s_nom [B, nx], u_nom, lo, hi [B, nu] may be views with contiguous rows (slices of a trajectory or of lbx / ubx: no copies).
+        The result goes to the input entries of the first frame of x_out [B, nvar], to the same entries of lbx / ubx when that pair is given, and
+        u - u_nom to du [B, nu] when given.  Returns x_out."""
+        import torch
+        if (lo is None) != (hi is None):
+            raise ValueError("give both lo and hi or neither")
+        if (lbx is None) != (ubx is None):
+            raise ValueError("give both lbx and ubx or neither")
+        B, N = x_out.shape[0], self.horizon
+        a = FeedbackArgs()
+        a.K = _check(K, (B, N, self.nu, self.nx), "K")
+        a.k = int(k)
+        a.s, a.s_stride = self._rows(s, self.nx, B, "s")
+        a.s_nom, a.s_nom_stride = self._rows(s_nom, self.nx, B, "s_nom")
+        a.u_nom, a.u_nom_stride = self._rows(u_nom, self.nu, B, "u_nom")
+        if lo is not None:
+            a.lo, a.lo_stride = self._rows(lo, self.nu, B, "lo")
+            a.hi, a.hi_stride = self._rows(hi, self.nu, B, "hi")
+        a.x_out = _check(x_out, (B, self.nvar), "x_out")
+        if lbx is not None:
+            a.lbx, a.ubx = _check(lbx, (B, self.nvar), "lbx"), _check(ubx, (B, self.nvar), "ubx")
+        if du is not None:
+            a.du = _check(du, (B, self.nu), "du")
+        _lib.check(_lib.lib().mpcqp_stage_feedback(self._h, B, C.byref(a), stream))
+        return x_out
