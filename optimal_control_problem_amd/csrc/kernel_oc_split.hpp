@@ -22,6 +22,17 @@
 // Part of the kernel translation units (included through kernels_all.hpp, in order; not a stand-alone header).
 #pragma once
 
+// set-up kernel, batched load and write-out phases: entries of A per thread in the load phase's first batch, trips of q and of l / u per
+// batch, slots of each of two chunks of A' per batch.  Sized by the registers the phase has (the kernel's count is the factorisation's), not by eight.
+constexpr int SU_GA = 16, SU_QB = 2, SU_AT = 8, SU_TB = 4;
+static_assert(SU_GA <= 32 && RUIZ_REG_CHUNKS_P <= SU_QB, "q of the wave's register columns comes from the load phase's first batch");
+// element k of an array as base + 32-bit byte offset (one address register per access where a 64-bit index costs two, held from the load to the store), and
+// the index of a masked batch: past the end, the last element.  Every array here is a QP's or a pattern's: far below 4 GB.
+template <class T> __device__ __forceinline__ T *su_at(T *p, const unsigned k) {
+  using C = std::conditional_t<std::is_const_v<T>, const char, char>;
+  return reinterpret_cast<T *>(reinterpret_cast<C *>(p) + k * (unsigned)sizeof(T));
+}
+__device__ __forceinline__ unsigned su_clamp(const long e, const long entries) { return (unsigned)min(e, entries - 1); }
 constexpr int OC_PENDING = 100, OC_PENDING_NONCVX = 101;      // DevIO.status between the launches of one mpcqp_solve (never seen by the caller)
 // LDS carve-up shared by both kernels (the same as the single kernel's on-chip mode, so that one footprint -- plan.hpp lds_bytes_oc -- serves both)
 template <int NW>
@@ -166,6 +177,8 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     // (the staged values through pointers whose memory the compiler KNOWS: `a_lds ? lds : valA` is a pointer to either, every access through it a
     // flat load that takes both memory paths and waits for both counters -- the whole scaling phase ran on those; one copy of the phase per case)
     const bool a_lds = oc.a_lds, p_lds = oc.p_lds;
+    // (the kept-workspace instances keep the text they had)
+    [[maybe_unused]] const bool batch = !REUSE && (oc.su_path & 4);
     // rg: the instances whose passes keep their fixed operands in registers (kernel_resident.hpp rz_*): A's indices with the LDS offsets of its staged
     // values, P's values and indices, q of the wave's columns.  Decided per wave and per structure from the chunk offsets; a wave whose list does not
     // fit walks that structure as before (and P then goes through the slab first, for every wave).
@@ -177,11 +190,20 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     bool ra = false, rp = false, p_slab = true;      // this wave's A / P from registers; P's unscaled values are needed in the slab
     if constexpr (RG) {
       const bool on = !oc.no_ruiz_regs && pl.A.entries <= 65536 && npad <= 65536 && mpad <= 65536;
+      if (batch) {      // (the chunk offsets in the lanes of two registers: one round trip for the six lists)
+        const int offA = pl.A.chunk_off[min(lane, pl.A.nchunks)], offP = pl.P.chunk_off[min(lane, pl.P.nchunks)];
+        LA = rz_list_lanes<NW, RZ_KA, RZ_CAPA>(offA, pl.A.nchunks, firstA); LP = rz_list_lanes<NW, RZ_KP, RZ_CAPP>(offP, pl.P.nchunks, wid);
+        ra = on && LA.fits; rp = on && LP.fits;
+        bool every = on;
+        for (int w = 0; w < NW; w++) every = every && rz_list_lanes<NW, RZ_KP, RZ_CAPP>(offP, pl.P.nchunks, w).fits;
+        p_slab = !every;
+      } else {
       LA = rz_list<NW, RZ_KA, RZ_CAPA>(pl.A.chunk_off, pl.A.nchunks, firstA); LP = rz_list<NW, RZ_KP, RZ_CAPP>(pl.P.chunk_off, pl.P.nchunks, wid);
       ra = on && LA.fits; rp = on && LP.fits;
       bool every = on;
       for (int w = 0; w < NW; w++) every = every && rz_list<NW, RZ_KP, RZ_CAPP>(pl.P.chunk_off, pl.P.nchunks, w).fits;
       p_slab = !every;
+      }
     }
     // (eight source indices, then the eight values they point at, in flight at a time: one element per trip was two dependent round trips to memory each)
     auto gather8 = [&](const int *__restrict__ src, const double *__restrict__ in, double *dst, const long entries) __attribute__((always_inline)) {
@@ -197,22 +219,110 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
       }
       for (; e < entries; e += NT) { const int sr = src[e]; dst[e] = sr >= 0 ? in[sr] : 0.0; }
     };
-    gather8(pl.A.src, inA, sA, pl.A.entries);
-    if (p_slab) gather8(pl.P.src, inP, sP, pl.P.entries);
-    // (the ten passes gather through these: a read from LDS instead of a round trip to the L2 in front of every batch)
-    if constexpr (sizeof(*iA) == 2) { for (long e = tid; e < pl.A.entries; e += NT) iA[e] = (unsigned short)pl.A.idx[e]; }
-    if constexpr (sizeof(*iP) == 2) { for (long e = tid; e < pl.P.entries; e += NT) iP[e] = (unsigned short)pl.P.idx[e]; }
-    for (int t = tid; t < npad; t += NT) { if (pl.perm[t] < 0) Qs[t] = 0.0; cx.R[t] = 1.0; cx.X[t] = 0.0; }      // (q in place in the slab: one workgroup writes it, padding here)
-    for (int i = tid; i < mpad; i += NT) cx.W[i] = 1.0;
-    bsync<NW>();
-    for (int j = tid; j < n; j += NT) Qs[pl.pos[j]] = inq[j];
-    bsync<NW>();
-    if constexpr (RG) {
-      if (ra) rz_fill_a(LA, iA, lane, aR);
-      if (rp) {
-        rz_fill_p(LP, iP, pl.P.src, inP, lane, pV, pI);
+    if (batch) {
+      if constexpr (!REUSE) {
+        // ---- the load phase in two stages for the whole workgroup: every load from the pattern's tables that this thread needs, then every
+        // gather from the caller's arrays they point at, then what waits for them.  Masked batches: a slot past the end takes the array's last element -- load,
+        // gather and store alike, so it writes the value its owner writes and nothing needs a branch.
+        constexpr int GA = SU_GA, QB = SU_QB;
+        constexpr bool FA = RG && sizeof(*iA) == 4, FP = RG && sizeof(*iP) == 4;      // lists whose indices come from the pattern's tables (not from the 16-bit copies in LDS, filled below)
+        const long nA = pl.A.entries;
+        int srA[GA], pm[QB]; double vA[GA], qv[QB];
+        [[maybe_unused]] unsigned ai[RZ_CAPA], pix[RZ_CAPP]; [[maybe_unused]] int psr[RZ_CAPP];
+        // (a batch of G entries per thread through their source indices, from entry e0 on)
+        auto gatherm = [&](auto g_, const int *__restrict__ src, const double *__restrict__ in, double *dst, const long entries, const long e0) __attribute__((always_inline)) {
+          constexpr int G = decltype(g_)::value;
+          for (long base = e0; base < entries; base += (long)G * NT) {
+            int sr[G]; double v[G];
 #pragma unroll
-        for (int q = 0; q < RZ_KP; q++) { const int t = (wid + q * NW) * WAVE + lane; qs[q] = (q < LP.nk && t < npad) ? Qs[t] : 0.0; }
+            for (int u = 0; u < G; u++) sr[u] = *su_at(src, su_clamp(base + tid + (long)u * NT, entries));
+#pragma unroll
+            for (int u = 0; u < G; u++) v[u] = *su_at(in, (unsigned)max(sr[u], 0));
+#pragma unroll
+            for (int u = 0; u < G; u++) *su_at(dst, su_clamp(base + tid + (long)u * NT, entries)) = sr[u] >= 0 ? v[u] : 0.0;
+          }
+        };
+        // stage one.  The lists' tables first: the loads come back in order, so by the time A's source indices are here the lists' registers are packed -- no wait
+        // of their own, and the indices are out of the way (two to a register, or folded into aR) before the values take their registers
+        if constexpr (FA) { if (ra) rz_fill_a_tab(LA, iA, lane, aR, ai); }
+        if constexpr (FP) { if (rp) rz_fill_p_tab(LP, iP, pl.P.src, lane, psr, pix); }
+#pragma unroll
+        for (int u = 0; u < GA; u++) srA[u] = *su_at(pl.A.src, su_clamp((long)tid + (long)u * NT, nA));
+#pragma unroll
+        for (int k = 0; k < QB; k++) pm[k] = pl.perm[min(tid + k * NT, npad - 1)];
+        if constexpr (FA) { if (ra) rz_fill_a_pack(aR, ai); }
+        if constexpr (FP) { if (rp) rz_fill_p_pack(pix, pI); }
+        // stage two (q by its owner: thread t loads q of position t, writes it to the slab and keeps it), and what waits for it; P's values for the registers
+        // behind A's (both batches in flight at once cost the kernel its third workgroup per CU)
+        // (a gather's address as a 32-bit byte offset from the instance's base -- an index below 2^29 --, "not padding" as a bit of one register: the source index
+        // does not stay live beside the value)
+        unsigned okA = 0;
+        int tid_st = tid; asm volatile("" : "+v"(tid_st));      // (the stores' offsets formed again when they are due: shared with the loads' they stay live beside the values)
+#pragma unroll
+        for (int u = 0; u < GA; u++) { okA |= (srA[u] >= 0 ? 1u : 0u) << u; vA[u] = *su_at(inA, (unsigned)max(srA[u], 0)); }
+#pragma unroll
+        for (int k = 0; k < QB; k++) qv[k] = inq[max(pm[k], 0)];
+#pragma unroll
+        for (int u = 0; u < GA; u++) *su_at(sA, su_clamp((long)tid_st + (long)u * NT, nA)) = ((okA >> u) & 1u) ? vA[u] : 0.0;
+#pragma unroll
+        for (int k = 0; k < QB; k++) {
+          const int t = min(tid + k * NT, npad - 1);
+          qv[k] = pm[k] >= 0 ? qv[k] : 0.0;
+          Qs[t] = qv[k]; cx.R[t] = 1.0; cx.X[t] = 0.0;
+        }
+        if constexpr (FP) { if (rp) rz_fill_p_val(inP, psr, pV); }
+        // what one batch does not hold (long horizons), P where it goes through the slab or LDS, the 16-bit index tables
+        gatherm(std::integral_constant<int, GA>{}, pl.A.src, inA, sA, nA, (long)GA * NT);
+        for (int t0 = QB * NT; t0 < npad; t0 += QB * NT) {
+          int pm2[QB]; double q2[QB];
+#pragma unroll
+          for (int k = 0; k < QB; k++) pm2[k] = pl.perm[min(t0 + tid + k * NT, npad - 1)];
+#pragma unroll
+          for (int k = 0; k < QB; k++) q2[k] = inq[max(pm2[k], 0)];
+#pragma unroll
+          for (int k = 0; k < QB; k++) { const int t = min(t0 + tid + k * NT, npad - 1); Qs[t] = pm2[k] >= 0 ? q2[k] : 0.0; cx.R[t] = 1.0; cx.X[t] = 0.0; }
+        }
+        if (p_slab) gatherm(std::integral_constant<int, GA>{}, pl.P.src, inP, sP, pl.P.entries, 0L);
+        auto fill16 = [&](auto *dst, const int *__restrict__ idx, const long entries) __attribute__((always_inline)) {
+          for (long base = 0; base < entries; base += 8L * NT) {
+            int ix[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) ix[u] = *su_at(idx, su_clamp(base + tid + (long)u * NT, entries));
+#pragma unroll
+            for (int u = 0; u < 8; u++) *su_at(dst, su_clamp(base + tid + (long)u * NT, entries)) = (unsigned short)ix[u];
+          }
+        };
+        if constexpr (sizeof(*iA) == 2) fill16(iA, pl.A.idx, nA);
+        if constexpr (sizeof(*iP) == 2) fill16(iP, pl.P.idx, pl.P.entries);
+        for (int i = tid; i < mpad; i += NT) cx.W[i] = 1.0;
+        bsync<NW>();      // (one barrier: R, X, W, the staged values and the index tables; q of a position is only ever read by the thread that wrote it)
+        if constexpr (RG) {
+          if constexpr (!FA) { if (ra) rz_fill_a(LA, iA, lane, aR); }
+          if (rp) {
+            if constexpr (!FP) rz_fill_p(LP, iP, pl.P.src, inP, lane, pV, pI);
+#pragma unroll
+            for (int q = 0; q < RZ_KP; q++) { const int t = (wid + q * NW) * WAVE + lane; qs[q] = (q < LP.nk && t < npad) ? qv[q] : 0.0; }
+          }
+        }
+      }
+    } else {
+      gather8(pl.A.src, inA, sA, pl.A.entries);
+      if (p_slab) gather8(pl.P.src, inP, sP, pl.P.entries);
+      // (the ten passes gather through these: a read from LDS instead of a round trip to the L2 in front of every batch)
+      if constexpr (sizeof(*iA) == 2) { for (long e = tid; e < pl.A.entries; e += NT) iA[e] = (unsigned short)pl.A.idx[e]; }
+      if constexpr (sizeof(*iP) == 2) { for (long e = tid; e < pl.P.entries; e += NT) iP[e] = (unsigned short)pl.P.idx[e]; }
+      for (int t = tid; t < npad; t += NT) { if (pl.perm[t] < 0) Qs[t] = 0.0; cx.R[t] = 1.0; cx.X[t] = 0.0; }      // (q in place in the slab: one workgroup writes it, padding here)
+      for (int i = tid; i < mpad; i += NT) cx.W[i] = 1.0;
+      bsync<NW>();
+      for (int j = tid; j < n; j += NT) Qs[pl.pos[j]] = inq[j];
+      bsync<NW>();
+      if constexpr (RG) {
+        if (ra) rz_fill_a(LA, iA, lane, aR);
+        if (rp) {
+          rz_fill_p(LP, iP, pl.P.src, inP, lane, pV, pI);
+  #pragma unroll
+          for (int q = 0; q < RZ_KP; q++) { const int t = (wid + q * NW) * WAVE + lane; qs[q] = (q < LP.nk && t < npad) ? Qs[t] : 0.0; }
+        }
       }
     }
     TS(0);
@@ -294,6 +404,45 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
       const int i = ch * WAVE + lane; const double ei = i < mpad ? cx.W[i] : 0.0;
       ell_map_chunk<false>(sA, pl.A.idx, nullptr, pl.A.idx, valA, cx.coA[ch], cx.coA[ch + 1], lane, [&](double v, int j) { return v * (ei * cx.R[j]); });
     }
+    if (batch) {
+      if constexpr (!REUSE) {
+        // A' two chunks of the wave at a time, SU_AT slots of each per batch: keys and indices first, then the values -- from the staged copy of A through the
+        // host's map (plan.hpp build_at_map; sA is read-only here) where the shape has one, else from the caller's array as before -- then the products
+        const bool staged = oc.a_lds && (oc.su_path & 8);
+        const unsigned short *amap = reinterpret_cast<const unsigned short *>(oc.asm_rec + oc.asm_rec[8 * pl.nblk + 8]);
+        auto at_pair = [&](auto st_, const int ch0) __attribute__((always_inline)) {
+          constexpr bool ST = decltype(st_)::value; constexpr int U = SU_AT;
+          const int ch1 = ch0 + NW; const bool two = ch1 < pl.At.nchunks;
+          const int a0 = __builtin_amdgcn_readfirstlane(cx.coAt[ch0]), na = __builtin_amdgcn_readfirstlane(cx.coAt[ch0 + 1]) - a0;
+          const int b0 = two ? __builtin_amdgcn_readfirstlane(cx.coAt[ch1]) : a0, nb = two ? __builtin_amdgcn_readfirstlane(cx.coAt[ch1 + 1]) - b0 : 0;
+          const int t0 = ch0 * WAVE + lane, t1 = ch1 * WAVE + lane;
+          const double dj0 = t0 < npad ? cx.R[t0] : 0.0, dj1 = (two && t1 < npad) ? cx.R[t1] : 0.0;
+          const int last = (int)pl.A.entries - 1;
+          for (int s = 0; s < max(na, nb); s += U) {
+            int key[2 * U], ix[2 * U]; double v[2 * U];
+#pragma unroll
+            for (int u = 0; u < 2 * U; u++) {
+              const int sl = s + (u % U), n_ = u < U ? na : nb;
+              const long e = (long)((u < U ? a0 : b0) + (sl < n_ ? sl : 0)) * WAVE + lane;
+              key[u] = ST ? (int)amap[e] : pl.At.src[e]; ix[u] = pl.At.idx[e];
+            }
+#pragma unroll
+            for (int u = 0; u < 2 * U; u++) v[u] = ST ? sA[min(key[u], last)] : inA[max(key[u], 0)];
+#pragma unroll
+            for (int u = 0; u < 2 * U; u++) {
+              const int sl = s + (u % U), n_ = u < U ? na : nb;
+              const double vv = (ST ? key[u] != (int)AT_MAP_NONE : key[u] >= 0) ? v[u] : 0.0;
+              if (sl < n_) valAt[(long)((u < U ? a0 : b0) + sl) * WAVE + lane] = vv * ((u < U ? dj0 : dj1) * cx.W[ix[u]]);
+            }
+          }
+        };
+        for (int ch = wid; ch < pl.At.nchunks; ch += 2 * NW) { if (staged) at_pair(std::true_type{}, ch); else at_pair(std::false_type{}, ch); }
+        if (!(RG && rp)) for (int ch = wid; ch < pl.At.nchunks; ch += NW) {
+          const int t = ch * WAVE + lane; const double dj = t < npad ? cx.R[t] : 0.0;
+          ell_map_chunk<false>(sP, pl.P.idx, nullptr, pl.P.idx, valP, cx.coP[ch], cx.coP[ch + 1], lane, [&](double v, int k) { return v * (c * dj * cx.R[k]); });
+        }
+      }
+    } else
     for (int ch = wid; ch < pl.At.nchunks; ch += NW) {
       const int t = ch * WAVE + lane; const double dj = t < npad ? cx.R[t] : 0.0;
       ell_map_chunk<true>(valAt, pl.At.src, inA, pl.At.idx, valAt, cx.coAt[ch], cx.coAt[ch + 1], lane, [&](double v, int i) { return v * (dj * cx.W[i]); });
@@ -324,6 +473,22 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
     }
     bsync<NW>();
     for (int t = tid; t < npad; t += NT) { Qs[t] *= c * cx.R[t]; Dg[t] = cx.R[t]; }
+    if (batch) {
+      if constexpr (!REUSE) {
+        // (the bounds of up to SU_TB trips in flight together: a trip each was a cold round trip each)
+        constexpr int TB = SU_TB;
+        for (int i0 = 0; i0 < mpad; i0 += TB * NT) {
+          double lo[TB], up[TB], ee[TB];
+#pragma unroll
+          for (int k = 0; k < TB; k++) { const int i = i0 + tid + k * NT, ic = min(i, m - 1); lo[k] = inl[ic]; up[k] = inu[ic]; ee[k] = cx.W[min(i, mpad - 1)]; }
+#pragma unroll
+          for (int k = 0; k < TB; k++) {
+            const int i = i0 + tid + k * NT; const double ei = ee[k];
+            if (i < mpad) { Eg[i] = ei; lb[i] = i < m ? ei * fmax(lo[k], -Q_INFTY) : 0.0; ub[i] = i < m ? ei * fmin(up[k], Q_INFTY) : 0.0; }
+          }
+        }
+      }
+    } else
     for (int i = tid; i < mpad; i += NT) {
       const double ei = cx.W[i];
       Eg[i] = ei;

@@ -32,7 +32,8 @@ struct DevOc {
   int nbc, has_hub, junc, npw, nhr, nlds, ntab;
   int o_chainE, o_chainF, o_pos, o_fill, ghub_slot, ghub_src;
   int su_path;          // set-up kernel, the factorisation's operands on chip: bit 0 the T tiles in LDS by parts, bit 1 the singleton rows from their list (plan.hpp oc_setup_tables;
-                        // MPCQP_NO_T_LDS=1 / MPCQP_NO_SING_LIST=1 clear them).  In the padding in front of the pointer: the struct's size and every other offset stay
+                        // MPCQP_NO_T_LDS=1 / MPCQP_NO_SING_LIST=1 clear them); bit 2 its load and write-out phases in batched stages, bit 3 A' written out from the staged copy of
+                        // A through the map behind the set-up tables (kernel_oc_split.hpp scale_phase; MPCQP_NO_SETUP_BATCH=1 clears both).  In the padding in front of the pointer: the struct's size and every other offset stay
   const int *a_assign;  // eight-wave instances: [8][32] row chunks of A per wave for the iteration's A sweep, balanced by load batches (-1: none); NULL = chunk wid + 8 k
   int npair, o_pair;   // twisted pairs of chains (plan.hpp OcPlan::pairs) and their records in tab: {LE, LF, oE, oF, junc, sLE, sLF, soE, soF, -, -, -}
   int nfill, o_s, o_dbl, ndbl, o_pp;   // LDS slots filled from the slab; the chains the solve walks; its double stages and their product blocks (plan.hpp oc_add_doubles)

@@ -227,6 +227,21 @@ __device__ __forceinline__ RzList<K> rz_list(const int *__restrict__ chunk_off, 
   L.fits = first + K * NW >= nchunks && L.tot <= CAP;
   return L;
 }
+// ... from the chunk offsets in the lanes of one register (lane l: chunk_off[min(l, nchunks)]; a list's chunks lie below first + K NW < 64): rz_list reads each
+// offset from memory and waits for it, two dependent round trips per chunk and six lists per wave (set-up kernel's batched load phase)
+template <int NW, int K, int CAP>
+__device__ __forceinline__ RzList<K> rz_list_lanes(const int offs, const int nchunks, const int first) {
+  static_assert((K + 1) * NW < WAVE, "a list's chunk offsets in one register");
+  RzList<K> L; L.nk = 0; L.tot = 0;
+  auto one = [&](const int q, int &s0, int &end) {
+    const int ch = first + q * NW; const bool in = q < K && ch < nchunks;
+    const int a = in ? __builtin_amdgcn_readlane(offs, ch) : 0, b = in ? __builtin_amdgcn_readlane(offs, ch + 1) : 0;
+    s0 = a; L.tot += b - a; end = L.tot; L.nk += in;
+  };
+  one(0, L.s0, L.e0); one(1, L.s1, L.e1); one(2, L.s2, L.e2);
+  L.fits = first + K * NW >= nchunks && L.tot <= CAP;
+  return L;
+}
 // walking a list slot by slot: register slot u belongs to chunk k, which covers register slots [beg, beg + w) and starts at ELL slot s0
 struct RzWalk { int k, beg, w, s0; };
 template <int K>
@@ -289,6 +304,50 @@ __device__ __forceinline__ void rz_fill_p(const RzList<RZ_KP> &L, const IT *__re
 #pragma unroll
     for (int j = 0; j < RZ_U; j += 2) pI[(g * RZ_U + j) >> 1] = ix[j] | (ix[j + 1] << 16);
   }
+}
+// The two fills in steps, for the set-up kernel's batched load phase: every table load of a list at once (_tab), what waits for them
+// later (_pack), P's gathers at once (_val) -- where the fills above take a batch of RZ_U at a time, each a round trip (P: two).  Same registers, same contents.
+template <class IT>
+__device__ __forceinline__ void rz_fill_a_tab(const RzList<RZ_KA> &L, const IT *__restrict__ idx, const int lane, unsigned (&aR)[RZ_CAPA], unsigned (&ai)[RZ_CAPA]) {
+  RzWalk wk = rz_walk0(L);
+  int r0 = wk.w > 0 ? lane % wk.w : 0;
+#pragma unroll
+  for (int u = 0; u < RZ_CAPA; u++) {
+    aR[u] = (unsigned)lane; ai[u] = 0;
+    if (u < L.tot) {
+      if (rz_step(L, wk, u)) r0 = lane % wk.w;
+      int su = u - wk.beg + r0; su -= su >= wk.w ? wk.w : 0;
+      const int e = (wk.s0 + su) * WAVE + lane;
+      aR[u] = (unsigned)e; ai[u] = (unsigned)idx[e];
+    }
+  }
+}
+__device__ __forceinline__ void rz_fill_a_pack(unsigned (&aR)[RZ_CAPA], const unsigned (&ai)[RZ_CAPA]) {
+#pragma unroll
+  for (int u = 0; u < RZ_CAPA; u++) aR[u] |= ai[u] << 16;
+}
+template <class IT>
+__device__ __forceinline__ void rz_fill_p_tab(const RzList<RZ_KP> &L, const IT *__restrict__ idx, const int *__restrict__ src, const int lane, int (&sr)[RZ_CAPP], unsigned (&ix)[RZ_CAPP]) {
+  RzWalk wk = rz_walk0(L);
+#pragma unroll
+  for (int u = 0; u < RZ_CAPP; u++) {
+    sr[u] = -1; ix[u] = 0;
+    if (u < L.tot) {
+      rz_step(L, wk, u);
+      const int e = (wk.s0 + u - wk.beg) * WAVE + lane;
+      sr[u] = src[e]; ix[u] = (unsigned)idx[e];
+    }
+  }
+}
+__device__ __forceinline__ void rz_fill_p_pack(const unsigned (&ix)[RZ_CAPP], unsigned (&pI)[RZ_CAPP / 2]) {
+#pragma unroll
+  for (int u = 0; u < RZ_CAPP; u += 2) pI[u >> 1] = ix[u] | (ix[u + 1] << 16);
+}
+__device__ __forceinline__ void rz_fill_p_val(const double *__restrict__ in, const int (&sr)[RZ_CAPP], double (&pV)[RZ_CAPP]) {
+#pragma unroll
+  for (int u = 0; u < RZ_CAPP; u++) pV[u] = in[max(sr[u], 0)];
+#pragma unroll
+  for (int u = 0; u < RZ_CAPP; u++) pV[u] = sr[u] >= 0 ? pV[u] : 0.0;
 }
 // ell_chunk_rc over the wave's chunks of A: row norms into W in place (E, read by its own lane only), column atomics as there.  The maxima do not care
 // about the order; the products are the same.

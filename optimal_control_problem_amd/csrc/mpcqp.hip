@@ -352,14 +352,14 @@ static int upload_onchip(mpcqp_handle *h, int cus) {
   d.a_lds = s.a_lds; d.p_lds = s.p_lds;
   if (s.vtiles && !mpcqp_kernel_oc_admm_tl(s.waves, s.oc_ng(), s.oc_nh())) s.vtiles = false;      // (the table has the tile instance for two of the shapes only)
   UP(upload(h, o.tab, &d.tab));
-  UP(upload(h, oc_setup_tables(pl, s.tlds, s.sing), &d.asm_rec));
+  UP(upload(h, oc_setup_tables(pl, s.tlds, s.sing, s.at_map), &d.asm_rec));
   if (s.tiles || s.vtiles) UP(upload_tiles(h));
   // (after the tables are uploaded: the set-up kernel's copies of the arguments)
   const SetupShape &su = s.setup; DevRes &ds = h->dres_setup; DevOc &dd = h->doc_setup;
   ds = dr; dd = d;
   dd.a_lds = su.a_lds; dd.p_lds = su.p_lds; dd.ix16 = su.ix16; dd.zpad = su.zpad; dd.ixo_a = su.ixo_a; dd.ixo_p = su.ixo_p;
   dd.no_ruiz_regs = h->knobs.no_ruiz_regs ? 1 : 0;
-  dd.su_path = (s.split && su.t_parts > 0 ? 1 : 0) | (s.split && su.sing_k > 0 ? 2 : 0);
+  dd.su_path = setup_path_bits(s);
   ds.stage = su.stage;
   if (!s.split) return MPCQP_OK;
   if (s.oc8 && !s.vtiles && !s.a_assign.empty()) UP(upload(h, s.a_assign, &d.a_assign));

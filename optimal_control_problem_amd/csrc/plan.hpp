@@ -1162,10 +1162,28 @@ inline SingList build_sing_list(const Plan &pl) {
   for (int t = 0; t < pl.npad; t++) for (size_t k = 0; k < of[t].size(); k++) { sl.ent[k * pl.npad + t] = of[t][k]; sl.row[k * pl.npad + t] = pl.At.idx[of[t][k]]; }
   return sl;
 }
+// A' from the staged copy of A (set-up kernel's write-out): per ELL entry of A' the ELL entry of A with the same source index, 16 bits
+// each (AT_MAP_NONE: padding).  Both layouts hold every non-zero of the caller's A once; empty where A has 65,535 entries or more, or a source is missing.
+constexpr unsigned short AT_MAP_NONE = 0xffffu;
+inline std::vector<unsigned short> build_at_map(const Plan &pl) {
+  if (pl.A.entries() >= (long)AT_MAP_NONE) return {};
+  int nnz = 0;
+  for (int s : pl.A.src) nnz = std::max(nnz, s + 1);
+  std::vector<int> of(nnz, -1);
+  for (size_t e = 0; e < pl.A.src.size(); e++) if (pl.A.src[e] >= 0) of[pl.A.src[e]] = (int)e;
+  std::vector<unsigned short> map(pl.At.src.size(), AT_MAP_NONE);
+  for (size_t e = 0; e < pl.At.src.size(); e++) {
+    const int s = pl.At.src[e];
+    if (s < 0) continue;
+    if (s >= nnz || of[s] < 0) return {};
+    map[e] = (unsigned short)of[s];
+  }
+  return map;
+}
 // What the set-up kernel reads behind the 8 nblk ints of oc_asm_records, in the same device array (DevOc has no room for another pointer): 16 ints
-// {parts, rec_off, o_rec, o_ta, o_tb, o_part, K, o_sing, ...} -- offsets in ints from the array's start, even --, then the tables: per part 8 ints
-// {first block, end block, image doubles, o_sc, pairs, ...}.
-inline std::vector<int> oc_setup_tables(const Plan &pl, const TLdsPlan &tp, const SingList &sl) {
+// {parts, rec_off, o_rec, o_ta, o_tb, o_part, K, o_sing, o_atmap, ...} -- offsets in ints from the array's start, even --, then the tables: per part 8 ints
+// {first block, end block, image doubles, o_sc, pairs, ...}; the A' -> A map (build_at_map, two entries to an int, 0 = none) stands last.
+inline std::vector<int> oc_setup_tables(const Plan &pl, const TLdsPlan &tp, const SingList &sl, const std::vector<unsigned short> &at_map = {}) {
   std::vector<int> r = oc_asm_records(pl);
   const size_t h = r.size();
   r.resize(h + 16, 0);
@@ -1178,6 +1196,11 @@ inline std::vector<int> oc_setup_tables(const Plan &pl, const TLdsPlan &tp, cons
     for (int p = 0; p < tp.parts; p++) { int *q = &pr[8 * p]; q[0] = tp.blk0[p]; q[1] = tp.blk0[p + 1]; q[2] = tp.image[p]; q[3] = o_sc + 2 * tp.sc_ptr[p]; q[4] = tp.sc_ptr[p + 1] - tp.sc_ptr[p]; }
     const int o_part = put(pr);
     r[h + 2] = o_rec; r[h + 3] = o_ta; r[h + 4] = o_tb; r[h + 5] = o_part;
+  }
+  if (!at_map.empty()) {
+    std::vector<int> packed((at_map.size() + 1) / 2, 0);
+    for (size_t e = 0; e < at_map.size(); e++) packed[e / 2] |= (int)((unsigned)at_map[e] << (16 * (e & 1)));
+    r[h + 8] = put(packed);
   }
   return r;
 }

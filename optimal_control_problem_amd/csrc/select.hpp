@@ -67,6 +67,7 @@ struct Knobs {
   bool no_ruiz_regs = false;  // MPCQP_NO_RUIZ_REGS=1: set-up kernel's Ruiz passes reload their fixed operands (indices, P's values) every pass instead of keeping them in registers
   bool no_t_lds = false;      // MPCQP_NO_T_LDS=1: set-up kernel's assembly takes its T tiles through the slab instead of LDS, part by part (plan.hpp build_t_lds_plan)
   bool no_sing_list = false;  // MPCQP_NO_SING_LIST=1: set-up kernel's diagonal term walks all of A' for its flagged entries instead of reading their list (plan.hpp build_sing_list)
+  bool no_setup_batch = false; // MPCQP_NO_SETUP_BATCH=1: set-up kernel's load and write-out phases one round trip at a time, as before DESIGN.md 3.13 (no batched stages, q through the slab, A' from the caller's array)
   long setup_cap = LONG_MIN;  // MPCQP_SETUP_CAP=<bytes>: LDS the set-up kernel's shape is fitted to, instead of a half or a third of a CU (LONG_MIN: not set)
   bool no_abalance = false;   // MPCQP_NO_ABALANCE: eight-wave iteration kernel takes A's row chunks round-robin instead of balanced by load batches
   bool no_touch = false;      // MPCQP_NO_TOUCH: no L2 touch by the idle waves during the backward chains (on-chip kernels)
@@ -108,6 +109,7 @@ struct Knobs {
     k.no_ruiz_regs = one("MPCQP_NO_RUIZ_REGS") == 2;
     k.no_t_lds = one("MPCQP_NO_T_LDS") == 2;
     k.no_sing_list = one("MPCQP_NO_SING_LIST") == 2;
+    k.no_setup_batch = one("MPCQP_NO_SETUP_BATCH") == 2;
     if (const char *e = getenv("MPCQP_SETUP_CAP")) k.setup_cap = atol(e);
     k.no_abalance = set("MPCQP_NO_ABALANCE");
     k.no_touch = set("MPCQP_NO_TOUCH");
@@ -126,6 +128,7 @@ struct SetupShape {
   int nw = 0; long lds = 0, stage = 0;
   int a_lds = 0, p_lds = 0, ix16 = 0, zpad = 0, ixo_a = 0, ixo_p = 0;
   long vecs = 0, tabw = 0;      // (doubles of its vectors and tables: for the MPCQP_VERBOSE line)
+  int batch = 0, at_map = 0;    // load and write-out phases in batched stages; A' written out from the staged copy of A through Selection::at_map
   int t_parts = 0, sing_k = 0;  // the factorisation's operands on chip: parts of the T tiles in LDS (0: through the slab), entries per column of the singleton list (0: the full pass)
 };
 
@@ -148,6 +151,7 @@ struct Selection {
   bool vtiles = false;          // ... in the two-kernel form, on the vector ALUs (kernel_oc_split.hpp; MPCQP_VTILES=1); mpcqp.hip clears it where the table has no such instance
   int resume_rounds = 1;        // two-kernel form: {re-factorisation, iteration} pairs queued behind a solve before the last pair (MPCQP_RESUME_ROUNDS)
   Plan plan; ResPlan rplan; OcPlan ocplan; TilePlan tplan; WsLayout wl;
+  std::vector<unsigned short> at_map;  // two-kernel form, A staged: ELL entry of A per ELL entry of A' (plan.hpp build_at_map; empty where it does not apply)
   TLdsPlan tlds; SingList sing; // two-kernel form: what the set-up kernel's factorisation reads on chip (plan.hpp; empty where a knob or the fit says no)
   long lds = 0;                 // dynamic LDS of the iteration (or only) kernel
   long stage = 0;               // on-chip mode: staging doubles of the iteration kernel (plan.hpp oc_stage_doubles) ...
@@ -456,6 +460,9 @@ inline void oc_launch_shape(const Ctx &c, Selection &s) {
   if (!c.k.no_t_lds) s.tlds = build_t_lds_plan(pq, su.stage);
   if (!c.k.no_sing_list) s.sing = build_sing_list(pq);
   su.t_parts = s.tlds.parts; su.sing_k = s.sing.K;
+  su.batch = (c.k.no_setup_batch || pq.m <= 0 || pq.A.entries() <= 0 || pq.P.entries() <= 0) ? 0 : 1;      // (its masked loads clamp their addresses into the arrays: none may be empty)
+  if (su.batch && su.a_lds) s.at_map = build_at_map(pq);
+  su.at_map = s.at_map.empty() ? 0 : 1;
   if (s.oc8 && !c.k.no_abalance) {
     // row chunks of A to waves by longest-processing-time over their load batches (a batch = one round trip to memory; plan.hpp ell_batches8)
     std::vector<int> assign(8 * 32, -1), load(8, 0), cnt(8, 0), order_(pq.A.nchunks);
@@ -525,6 +532,11 @@ inline KernelId kernel_id_of(const Selection &s, bool reuse, bool rf) {
   return s.waves == 0 ? stream_kernel_id_of(s) : s.split ? oc_admm_kernel_id_of(s, rf) : res_kernel_id_of(s, reuse);
 }
 
+// DevOc.su_path of a two-kernel handle's set-up kernel (kernel_onchip.hpp): which of its on-chip and batched paths this handle takes
+inline int setup_path_bits(const Selection &s) {
+  const SetupShape &u = s.setup;
+  return !s.split ? 0 : (u.t_parts > 0 ? 1 : 0) | (u.sing_k > 0 ? 2 : 0) | (u.batch ? 4 : 0) | (u.at_map ? 8 : 0);
+}
 // The MPCQP_VERBOSE line of a two-kernel handle, up to what only the device knows (mpcqp.hip adds the resident workgroups)
 inline std::string setup_shape_text(const Selection &s) {
   const SetupShape &u = s.setup;
