@@ -225,6 +225,25 @@ int mpcqp_set_skip(mpcqp_handle *h, const int *skip, int mem);
  * kernel; waits for the solve.  MPCQP_ERR_STATE when the last solve ran without a skip array (or none ran). */
 int mpcqp_debug_skip_list(mpcqp_handle *h, int *list, int mem);
 
+/* Soft constraint rows.  With weights set, the following solves minimise
+ *     1/2 x'Px + q'x + sum_i [ w1_i d_i + 1/2 w2_i d_i^2 ],   d_i = dist((Ax)_i, [l_i, u_i]),
+ * with no new variables and the same P, A, pattern, row classes, rho and factorisation: only the z update of the ADMM changes, from the projection onto
+ * [l, u] to the proximal map of the penalty (past a bound by max(0, (rho_i d - w1) / (rho_i + w2)) in the scaled problem).  w1, w2 [m] per instance, >= 0;
+ * stride 0 = one array shared by the batch; w2 = NULL means zeros; a row with w1_i >= 1e30 (the library's infinity, as for bounds) is hard, and a handle whose
+ * rows are all hard returns the bits of the plain solve.  w1 = NULL clears the setting: the plain kernels run again.  Device arrays are borrowed and read by
+ * every following solve on its stream (like the skip array); host arrays are copied.  The set call allocates what the solves need (nothing is allocated inside
+ * mpcqp_solve: a soft solve stays capturable in a graph).
+ * Outputs: z is the minimiser's row activity and may lie outside [l, u] on soft rows (the penalty can be read off it); y_i is a subgradient of the penalty at
+ * z_i: 0 inside, |y_i| <= w1_i on a bound, +-(w1_i + w2_i d_i) outside; info[0] stays 1/2 x'Px + q'x.  The primal-infeasibility certificate treats a soft row
+ * like a row with both bounds infinite; the dual-infeasibility certificate still counts it as bounded, so a problem that is unbounded only through soft rows with
+ * w2 = 0 (and singular P) ends on the iteration limit.
+ * Only the two-kernel on-chip form has soft twins of its iteration kernel: every other family, and the tile experiment, answers MPCQP_ERR_LIMIT (the precedent
+ * of mpcqp_update_matrices), and so do reduced and presolved handles.  Polishing and soft rows exclude each other -- the active-set guess assumes hard bounds:
+ * whichever of mpcqp_set_polish / mpcqp_set_soft_rows comes second answers MPCQP_ERR_STATE.  mpcqp_solve_host with soft rows set answers MPCQP_ERR_STATE.
+ * Kept workspaces (mpcqp_update_vectors, mpcqp_update_matrices), warm starts, mpcqp_set_rho, the dispatch hint and mpcqp_set_skip work as before.
+ * No reference counterpart (OSQP has hard rows only; the reference models slack as extra inputs). */
+int mpcqp_set_soft_rows(mpcqp_handle *h, const double *w1, long stride1, const double *w2, long stride2, int mem);
+
 /* Replaces CuCaQP::getSolution / getSolutionAsDM (CuCaQP.cpp:213-224), and additionally surfaces what the
  * reference drops: duals y, row activities z, per-QP status, iteration count and
  * info[4] = {objective, primal residual, dual residual, final rho}.  Any output pointer may be NULL.

@@ -16,7 +16,7 @@ STATUS = {1: "solved", 2: "solved_inaccurate", 3: "primal_infeasible", 4: "prima
 # OSQP's status_polish (mpcqp_get_polish)
 POLISH_LINSYS_ERROR, POLISH_FAILED, POLISH_NOT_PERFORMED, POLISH_SUCCESS = -2, -1, 0, 1
 
-EXPORTS = ["mpcqp_default_settings", "mpcqp_create", "mpcqp_create_tuned", "mpcqp_create_reduced", "mpcqp_create_presolved", "mpcqp_update", "mpcqp_warm_start", "mpcqp_keep_workspace", "mpcqp_update_vectors", "mpcqp_update_matrices", "mpcqp_set_rho", "mpcqp_set_dispatch_hint", "mpcqp_set_skip", "mpcqp_debug_skip_list", "mpcqp_solve", "mpcqp_solve_host",
+EXPORTS = ["mpcqp_default_settings", "mpcqp_create", "mpcqp_create_tuned", "mpcqp_create_reduced", "mpcqp_create_presolved", "mpcqp_update", "mpcqp_warm_start", "mpcqp_keep_workspace", "mpcqp_update_vectors", "mpcqp_update_matrices", "mpcqp_set_rho", "mpcqp_set_dispatch_hint", "mpcqp_set_skip", "mpcqp_debug_skip_list", "mpcqp_set_soft_rows", "mpcqp_solve", "mpcqp_solve_host",
            "mpcqp_get", "mpcqp_set_polish", "mpcqp_get_polish", "mpcqp_last_polish_ms", "mpcqp_sync", "mpcqp_destroy", "mpcqp_strerror", "mpcqp_last_kernel_ms", "mpcqp_last_phase_ms",
            "mpcqp_plan_info", "mpcqp_oc_info", "mpcqp_debug_scaling", "mpcqp_debug_blockops",
            "mpcqp_stage_default", "mpcqp_stage_create", "mpcqp_stage_create_user", "mpcqp_stage_create_tracking", "mpcqp_stage_destroy", "mpcqp_stage_set_weights", "mpcqp_stage_set_path_bounds", "mpcqp_stage_param_count", "mpcqp_stage_set_instance_params", "mpcqp_stage_data_count", "mpcqp_stage_set_stage_data", "mpcqp_stage_shift_data", "mpcqp_stage_has_transition_data", "mpcqp_stage_dims", "mpcqp_stage_has_cost", "mpcqp_stage_has_link_cost", "mpcqp_stage_has_residual_cost", "mpcqp_stage_pattern",
@@ -90,6 +90,7 @@ def lib():
         L.mpcqp_set_dispatch_hint.argtypes = [vp, C.c_int]
         L.mpcqp_set_skip.argtypes = [vp, vp, C.c_int]
         L.mpcqp_debug_skip_list.argtypes = [vp, vp, C.c_int]
+        L.mpcqp_set_soft_rows.argtypes = [vp, dp, lg, dp, lg, C.c_int]
         L.mpcqp_update_vectors.argtypes = [vp, dp, lg, dp, lg, dp, lg, C.c_int]
         L.mpcqp_update_matrices.argtypes = [vp, dp, lg, dp, lg, dp, lg, dp, lg, dp, lg, C.c_int]
         L.mpcqp_solve.argtypes = [vp, vp]

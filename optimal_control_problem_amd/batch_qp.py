@@ -3,7 +3,9 @@
 Accepts NumPy arrays (host memory, copied by the library like CuCaQP copies into its members,
 reference include/optimal_control_problem/sqp_solver/CuCaQP.h:83-87) or torch CUDA tensors (device
 memory, borrowed; torch is only the allocator/stream provider here)."""
+import contextlib
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -49,9 +51,67 @@ def skip_list(skip, order=None):
     return np.concatenate([act, np.full(len(skip) - len(act), -1, dtype=np.int32)]).astype(np.int32)
 
 
+SOFT_INFTY = 1e30      # a row whose l1 weight reaches the library's infinity is hard (include/mpcqp.h mpcqp_set_soft_rows)
+
+
+def soft_prox(v, l, u, rho, w1, w2):
+    """The z update of the ADMM with soft rows (include/mpcqp.h mpcqp_set_soft_rows), stated in NumPy: the proximal map at v, with weight rho, of the penalty
+    w1 d + w2 d^2 / 2 on d = dist(z, [l, u]).  Inside the box it is v; past a bound it is the bound plus max(0, (rho d(v) - w1) / (rho + w2)); a row with
+    w1 >= 1e30 is hard.  Written as a select on the clipped value -- "where the step is positive add it, else keep the clip" -- so that a hard row has the
+    bits of min(max(v, l), u) (-0.0 + 0.0 would flip a sign bit).  Element-wise; every argument broadcasts."""
+    v, l, u, rho, w1, w2 = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64) for a in (v, l, u, rho, w1, w2)))
+    zc = np.minimum(np.maximum(v, l), u)
+    above = v > u
+    d = np.where(above, v - u, l - v)
+    with np.errstate(over="ignore", invalid="ignore"):
+        step = (rho * d - w1) / (rho + w2)
+    take = (w1 < SOFT_INFTY) & (step > 0.0)
+    return np.where(take, np.where(above, zc + step, zc - step), zc)
+
+
+@contextlib.contextmanager
+def _family_in_environment(family):
+    """MPCQP_VARIANT = family while a handle is created (the library reads its switches once, at create); None: the environment as it is"""
+    if family is None:
+        yield
+        return
+    saved = os.environ.get("MPCQP_VARIANT")
+    os.environ["MPCQP_VARIANT"] = family
+    try:
+        yield
+    finally:
+        if saved is None:
+            del os.environ["MPCQP_VARIANT"]
+        else:
+            os.environ["MPCQP_VARIANT"] = saved
+
+
+def with_soft_rows(make, w1, w2=None):
+    """A handle that takes soft rows: make(family) -> BatchQP is tried with the library's own choice of kernel family first, then -- where that handle answers
+    ERR_LIMIT and the environment names no family -- with the two-kernel on-chip forms "oc4" and "oc8" by name.  Returns the handle with the weights set;
+    raises the last MpcqpError where the pattern admits neither."""
+    last = None
+    for family in (None, "oc4", "oc8"):
+        if family is not None and os.environ.get("MPCQP_VARIANT"):
+            break
+        qp = None
+        try:
+            qp = make(family)
+            qp.set_soft_rows(w1, w2)
+            return qp
+        except _lib.MpcqpError as e:
+            if qp is not None:
+                qp.close()
+            if e.code != _lib.ERR_LIMIT:
+                raise
+            last = e
+    raise last
+
+
 class BatchQP:
-    def __init__(self, n, m, batch, Pp, Pi, Ap, Ai, settings=None, fixed_rows=None, tuned=False, presolve_bounds=None, **kw):
-        """fixed_rows: opt-in reduced form (mpcqp_create_reduced) -- singleton rows of A with l = u in every instance, whose
+    def __init__(self, n, m, batch, Pp, Pi, Ap, Ai, settings=None, fixed_rows=None, tuned=False, presolve_bounds=None, family=None, **kw):
+        """family: the kernel family by name ("oc4", "oc8", ...: what MPCQP_VARIANT names), None = the library's choice.
+        fixed_rows: opt-in reduced form (mpcqp_create_reduced) -- singleton rows of A with l = u in every instance, whose
         variables are substituted before the solve; None (default) = the full form, what the reference's OSQP solves.
         presolve_bounds = (l, u): the same with the rows FOUND from the first update's bounds (mpcqp_create_presolved); self.nfixed says how many.
         tuned: opt-in mpcqp_create_tuned -- the kernel family chosen by measurement on this pattern instead of by rule"""
@@ -66,21 +126,22 @@ class BatchQP:
         L = _lib.lib()
         self.nfixed = 0
         self.polish = False
-        if presolve_bounds is not None:
-            lp, ls_, lmem, lk = _ptr_stride(presolve_bounds[0], self.m, self.batch, "l"); up, us_, umem, uk = _ptr_stride(presolve_bounds[1], self.m, self.batch, "u")
-            if lmem != umem:
-                raise ValueError("l and u must live in the same memory space")
-            nf = C.c_int(0)
-            _lib.check(L.mpcqp_create_presolved(self.n, self.m, self.batch, self.Pp.ctypes.data, self.Pi.ctypes.data, self.Ap.ctypes.data, self.Ai.ctypes.data,
-                                                lp, ls_, up, us_, lmem, C.byref(self.settings), C.byref(self._h), C.byref(nf)))
-            self.nfixed = int(nf.value)
-        elif fixed_rows is None:
-            _lib.check((L.mpcqp_create_tuned if tuned else L.mpcqp_create)(self.n, self.m, self.batch, self.Pp.ctypes.data, self.Pi.ctypes.data,
-                                      self.Ap.ctypes.data, self.Ai.ctypes.data, C.byref(self.settings), C.byref(self._h)))
-        else:
-            fr = np.ascontiguousarray(fixed_rows, dtype=np.int32)
-            _lib.check(L.mpcqp_create_reduced(self.n, self.m, self.batch, self.Pp.ctypes.data, self.Pi.ctypes.data,
-                                              self.Ap.ctypes.data, self.Ai.ctypes.data, len(fr), fr.ctypes.data, C.byref(self.settings), C.byref(self._h)))
+        with _family_in_environment(family):
+            if presolve_bounds is not None:
+                lp, ls_, lmem, lk = _ptr_stride(presolve_bounds[0], self.m, self.batch, "l"); up, us_, umem, uk = _ptr_stride(presolve_bounds[1], self.m, self.batch, "u")
+                if lmem != umem:
+                    raise ValueError("l and u must live in the same memory space")
+                nf = C.c_int(0)
+                _lib.check(L.mpcqp_create_presolved(self.n, self.m, self.batch, self.Pp.ctypes.data, self.Pi.ctypes.data, self.Ap.ctypes.data, self.Ai.ctypes.data,
+                                                    lp, ls_, up, us_, lmem, C.byref(self.settings), C.byref(self._h), C.byref(nf)))
+                self.nfixed = int(nf.value)
+            elif fixed_rows is None:
+                _lib.check((L.mpcqp_create_tuned if tuned else L.mpcqp_create)(self.n, self.m, self.batch, self.Pp.ctypes.data, self.Pi.ctypes.data,
+                                          self.Ap.ctypes.data, self.Ai.ctypes.data, C.byref(self.settings), C.byref(self._h)))
+            else:
+                fr = np.ascontiguousarray(fixed_rows, dtype=np.int32)
+                _lib.check(L.mpcqp_create_reduced(self.n, self.m, self.batch, self.Pp.ctypes.data, self.Pi.ctypes.data,
+                                                  self.Ap.ctypes.data, self.Ai.ctypes.data, len(fr), fr.ctypes.data, C.byref(self.settings), C.byref(self._h)))
         # the device the handle lives on (settings.device, -1 = the one current at creation): what a borrowed tensor is checked against (set_skip)
         self._device_index = int(self.settings.device)
         if self._device_index < 0:
@@ -157,6 +218,26 @@ class BatchQP:
             raise ValueError("skip: expected %d values, one per instance" % self.batch)
         self._keep_skip = a
         _lib.check(_lib.lib().mpcqp_set_skip(self._h, a.ctypes.data, _lib.MEM_HOST))
+
+    def set_soft_rows(self, w1, w2=None):
+        """Soft constraint rows (mpcqp_set_soft_rows): the following solves add w1_i d_i + w2_i d_i^2 / 2 on d_i = dist((Ax)_i, [l_i, u_i]) to the objective
+        instead of enforcing the row.  w1, w2: [m] shared by the batch or [batch, m], >= 0; w2 None = zeros; a row with w1 >= 1e30 stays hard; w1 None
+        clears the setting.  CUDA tensors are borrowed and read by every following solve; NumPy arrays are copied.  Only handles of the two-kernel
+        on-chip form take soft rows (MpcqpError with code ERR_LIMIT otherwise; create with MPCQP_VARIANT=oc4 / oc8 or tuned=True where the pattern
+        admits it); together with set_polish() the second of the two calls raises with ERR_STATE."""
+        if w1 is None:
+            self._keep_soft = None
+            _lib.check(_lib.lib().mpcqp_set_soft_rows(self._h, None, 0, None, 0, _lib.MEM_HOST))
+            return
+        p1, s1, mem1, k1 = _ptr_stride(w1, self.m, self.batch, "w1")
+        p2, s2, mem2, k2 = _ptr_stride(w2, self.m, self.batch, "w2")
+        if mem2 is not None and mem2 != mem1:
+            raise ValueError("w1 and w2 must live in the same memory space")
+        for k, name in ((k1, "w1"), (k2, "w2")):
+            if _is_torch(k) and k.is_cuda and k.device.index != self._device_index:      # (borrowed: the kernels dereference the pointer on the handle's device)
+                raise ValueError("%s: the tensor lives on cuda:%s, the handle on cuda:%d" % (name, k.device.index, self._device_index))
+        self._keep_soft = (k1, k2)
+        _lib.check(_lib.lib().mpcqp_set_soft_rows(self._h, p1, s1, p2, s2, mem1))
 
     def debug_skip_list(self):
         """the dispatch list of the last solve under a skip array (mpcqp_debug_skip_list): active instances in dispatch order, then -1"""

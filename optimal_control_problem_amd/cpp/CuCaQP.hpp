@@ -73,6 +73,15 @@ class CuCaQP {
   // Kept workspace: after a set-up under a skip array the skipped instances hold no factor or scaling of the current matrices, so mpcqp_update_vectors /
   // mpcqp_update_matrices answer MPCQP_ERR_STATE (include/mpcqp.h); a solve() after update*() then runs the full set-up instead, as for MPCQP_ERR_LIMIT.
   void setSkip(const int *skip) { if (skip) skip_.assign(skip, skip + batch_); else skip_.clear(); }
+  // extension: soft constraint rows (mpcqp_set_soft_rows): w1, w2 [numOfConstraints] shared by the batch, >= 0 -- the following solves add w1_i d_i +
+  // w2_i d_i^2 / 2 on the distance d_i of (Ax)_i to [l_i, u_i] instead of enforcing row i; w1_i >= 1e30 keeps row i hard, w2 = nullptr means zeros,
+  // w1 = nullptr clears.  solve() returns false where the handle refuses them: a kernel family other than the two-kernel on-chip form, a presolved
+  // handle (MPCQP_ERR_LIMIT), or together with setPolish(true) (MPCQP_ERR_STATE).
+  void setSoftRows(const double *w1, const double *w2 = nullptr) {
+    if (!w1) { soft1_.clear(); soft2_.clear(); return; }
+    soft1_.assign(w1, w1 + numOfConstraints_);
+    if (w2) soft2_.assign(w2, w2 + numOfConstraints_); else soft2_.clear();
+  }
   int getPolishStatus() const { return polishStatus_.empty() ? MPCQP_POLISH_NOT_PERFORMED : polishStatus_[0]; }
   const std::vector<int> &getPolishStatusVector() const { return polishStatus_; }
 
@@ -197,6 +206,10 @@ class CuCaQP {
     vectorsOnly_ = matricesDirty_ = false;
     if (rc == MPCQP_OK) rc = mpcqp_set_skip(handle_, skip_.empty() ? nullptr : skip_.data(), MPCQP_MEM_HOST);
     skipUsed_ = skipUsed_ || !skip_.empty();
+    if (rc == MPCQP_OK && (!soft1_.empty() || softOn_)) {
+      rc = mpcqp_set_soft_rows(handle_, soft1_.empty() ? nullptr : soft1_.data(), 0, soft2_.empty() ? nullptr : soft2_.data(), 0, MPCQP_MEM_HOST);
+      softOn_ = rc == MPCQP_OK && !soft1_.empty();
+    }
     if (rc == MPCQP_OK) rc = mpcqp_solve(handle_, nullptr);
     solvedOnce_ = rc == MPCQP_OK;
     solution_.resize((size_t)batch_ * numOfVariables_); status_.resize(batch_); iters_.resize(batch_);
@@ -337,7 +350,7 @@ class CuCaQP {
     vectorsOnly_ = false; matricesDirty_ = true;
     return true;
   }
-  void clearSolver() { if (handle_) { mpcqp_destroy(handle_); handle_ = nullptr; } isInitialized_ = false; }
+  void clearSolver() { if (handle_) { mpcqp_destroy(handle_); handle_ = nullptr; } isInitialized_ = false; softOn_ = false; }
   bool updateVector(bool stored) {
     if (!isInitialized_) { std::cerr << "Error: Solver not initialized. Call initSolver() first." << std::endl; return false; }   // CuCaQP.cpp:118-121
     if (stored) vectorsOnly_ = true;
@@ -348,6 +361,7 @@ class CuCaQP {
   bool isInitialized_ = false, verbose_ = false, patternChanged_ = true, dirty_ = false;
   bool kept_ = false, vectorsOnly_ = false, matricesDirty_ = false, solvedOnce_ = false, presolve_ = false, polish_ = false, polishOn_ = false;
   bool keepScaling_ = false, noMatrixUpdates_ = false;
+  std::vector<double> soft1_, soft2_; bool softOn_ = false;      // (softOn_: the handle has soft rows set)
   std::vector<int> skip_; bool skipUsed_ = false;      // (skipUsed_: some solve of this object ran under a skip array)
   int nfixed_ = 0;
   mpcqp_settings settings_;

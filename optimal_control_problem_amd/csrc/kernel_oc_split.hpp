@@ -34,6 +34,24 @@ template <class T> __device__ __forceinline__ T *su_at(T *p, const unsigned k) {
 }
 __device__ __forceinline__ unsigned su_clamp(const long e, const long entries) { return (unsigned)min(e, entries - 1); }
 constexpr int OC_PENDING = 100, OC_PENDING_NONCVX = 101;      // DevIO.status between the launches of one mpcqp_solve (never seen by the caller)
+// Soft rows (mpcqp_set_soft_rows): the extra argument of the soft twins of the iteration kernel -- no other kernel's argument block knows of it.
+// w1, w2: the caller's weights per row (stride 0: shared by the batch; w2 null: zeros), in the caller's units.  buf: 2 ms doubles per instance, the handle's:
+// the weights as the scaled iteration sees them, w1 c / E_i in the first ms, w2 c / E_i^2 behind them; a hard row (w1 >= 1e30) holds Q_INFTY and 0.  Written by
+// the instance's own workgroup at the head of every launch (E and c are the set-up kernel's, in the slab and in DevIO.cscale by then), one thread per element.
+struct DevSoft {
+  const double *w1, *w2; long s1, s2;
+  double *buf; int ms;      // ms: rows per instance in buf, mpad rounded up to whole chunks of A's sweep (the sweep fetches a chunk's 64 lanes unmasked, like l and u)
+};
+// The z update of a soft row: the proximal map of w1 d + w2 d^2 / 2, d = dist(z, [lo, up]), at v with weight rh -- past the bound by (rh d(v) - w1) / (rh + w2)
+// where that is positive.  A select on the clipped value, so that a hard row (and a row inside its box) keeps the bits of fmin(fmax(v, lo), up).
+__device__ __forceinline__ double oc_soft_prox(const double v, const double lo, const double up, const double rh, const double s1, const double s2) {
+  const double zc = fmin(fmax(v, lo), up);
+  const bool above = v > up;
+  const double d = above ? v - up : lo - v;
+  const double step = __builtin_fma(rh, d, -s1) / (rh + s2);
+  const bool take = s1 < Q_INFTY && step > 0.0;
+  return take ? (above ? zc + step : zc - step) : zc;
+}
 // LDS carve-up shared by both kernels (the same as the single kernel's on-chip mode, so that one footprint -- plan.hpp lds_bytes_oc -- serves both)
 template <int NW>
 struct OcLds {
@@ -534,8 +552,11 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_setup_kernel(const DevP
 // RF = 1: an adaptive-rho step re-factorises in place (the last launch of a solve); RF = 0: the instance leaves for the set-up kernel's resume mode
 // TL: the two sweeps of the iteration on dense tiles of A + remainder ELL layouts (experiment; below)
 // One instance; called once per workgroup (a grid of `count` workgroups) or, with DevIO.queue set, again and again by a resident workgroup that draws tickets.
-template <int NW, int OCG, int OCH, int RF, bool TL, bool PAIRS>
-__device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs, const mpcqp_settings &st, const DevIO &io, const DevOc &oc, double *lds, const int b, const int wid, const int lane) {
+// SOFT: the soft-row twin (mpcqp_set_soft_rows): the z update is oc_soft_prox, the primal-infeasibility certificate skips the soft rows; sf = its weights
+template <int NW, int OCG, int OCH, int RF, bool TL, bool PAIRS, bool SOFT = false>
+__device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs, const mpcqp_settings &st, const DevIO &io, const DevOc &oc, double *lds, const int b, const int wid, const int lane,
+                                            [[maybe_unused]] const DevSoft *sf = nullptr) {
+  static_assert(!(SOFT && TL), "the tile experiment has no soft twin");
   constexpr int NT = NW * WAVE;
   [[maybe_unused]] constexpr int OCU = NW == 4 ? 16 : 8;      // ELL slots in flight per lane (eight waves split the chunks further and hold more resident blocks)
   constexpr bool HUB = OCH > 0;
@@ -570,6 +591,22 @@ __device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs,
   } else {
     for (int t = tid; t < npad; t += NT) { cx.Q[t] = Qs[t]; cx.X[t] = 0.0; }
     for (int i = tid; i < mpad; i += NT) { cx.Z[i] = 0.0; cx.Y[i] = 0.0; }
+  }
+  [[maybe_unused]] const double *sw1 = nullptr, *sw2 = nullptr;
+  if constexpr (SOFT) {
+    // the caller's weights under the equilibration (zbar = E z, cost scaled by c): w1 c / E_i, w2 c / E_i^2; hard and padding rows: infinity, 0.  ms >= 64 A.nchunks:
+    // the sweep below reads a whole chunk's lanes
+    double *sb = sf->buf + (long)b * 2 * sf->ms;
+    const double *w1 = sf->w1 + (long)b * sf->s1, *w2 = sf->w2 ? sf->w2 + (long)b * sf->s2 : nullptr;
+    for (int i = tid; i < sf->ms; i += NT) {
+      double a1 = Q_INFTY, a2 = 0.0;
+      if (i < m) {
+        const double w = w1[i];
+        if (w < Q_INFTY) { const double ei = 1.0 / Eg[i]; a1 = c * w * ei; a2 = w2 ? c * w2[i] * ei * ei : 0.0; }
+      }
+      sb[i] = a1; sb[sf->ms + i] = a2;
+    }
+    sw1 = sb; sw2 = sb + sf->ms;
   }
   bsync<NW>();
   if (!resume && st.warm_start && io.x0 && io.y0) {
@@ -735,6 +772,8 @@ __device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs,
           const int i = ch * WAVE + lane, k = LPT ? kq : (ch - wid) / NW;
           const double lo = lb[i], up = ub[i];
           const double zo = i < mpad ? cx.Z[i] : 0.0, yo = i < mpad ? cx.Y[i] : 0.0;
+          [[maybe_unused]] double s1 = 0.0, s2 = 0.0;
+          if constexpr (SOFT) { s1 = sw1[i]; s2 = sw2[i]; }
           double zt;
           if constexpr (TL) {
             // the tiles with a row in this chunk, as they lie (one 32-byte row piece per lane), four in flight; a tile sum reaches its row's owner through w,
@@ -766,7 +805,9 @@ __device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs,
             const double rh = loose ? Q_RHO_MIN : (eq ? rho_eq : rho_in), rinv = loose ? ri_min : (eq ? ri_eq : ri_in);
             // (every fused multiply-add written out, in the form the single kernel's build has: a * b + c * d may be contracted either way round)
             const double zr = __builtin_fma(alpha, zt, (1.0 - alpha) * zo);
-            const double zn = fmin(fmax(__builtin_fma(rinv, yo, zr), lo), up);
+            double zn;
+            if constexpr (SOFT) zn = oc_soft_prox(__builtin_fma(rinv, yo, zr), lo, up, rh, s1, s2);
+            else zn = fmin(fmax(__builtin_fma(rinv, yo, zr), lo), up);
             const double dz = zr - zn, yn = __builtin_fma(rh, dz, yo);
             cx.Z[i] = zn; cx.Y[i] = yn; cx.W[i] = __builtin_fma(rh, zn, -yn);
             const double dy = rh * dz;
@@ -787,7 +828,7 @@ __device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs,
       iter_done = iter;
       if (__builtin_expect(can_check, 0)) {     // (rare paths are marked cold: their register pressure must not cost the hot loop its registers)
         update_info_res<NW, true>(cx, in);
-        status = check_termination_res<NW>(cx, in, 0);
+        status = check_termination_res<NW, SOFT>(cx, in, 0, sw1);
         TS(7);
         if (status != MPCQP_UNSOLVED) break;
       }
@@ -818,8 +859,8 @@ __device__ __forceinline__ void oc_admm_one(const DevPlan &pl, const DevRes &rs,
     }
     if (iter > st.max_iter) iter_done = st.max_iter;
     if (status == MPCQP_UNSOLVED) {
-      if (!can_check) { update_info_res<NW, true>(cx, in); status = check_termination_res<NW>(cx, in, 0); }
-      if (status == MPCQP_UNSOLVED) { status = check_termination_res<NW>(cx, in, 1); if (status == MPCQP_UNSOLVED) status = MPCQP_MAX_ITER_REACHED; }
+      if (!can_check) { update_info_res<NW, true>(cx, in); status = check_termination_res<NW, SOFT>(cx, in, 0, sw1); }
+      if (status == MPCQP_UNSOLVED) { status = check_termination_res<NW, SOFT>(cx, in, 1, sw1); if (status == MPCQP_UNSOLVED) status = MPCQP_MAX_ITER_REACHED; }
     }
   }
   const bool bad = status == MPCQP_PRIMAL_INFEASIBLE || status == MPCQP_PRIMAL_INFEASIBLE_INACCURATE ||
@@ -897,6 +938,57 @@ __global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_admm_kernel(const DevPl
     int lane_q = lane, wid_q = wid;
     asm volatile("" : "+v"(lane_q), "+s"(wid_q));
     oc_admm_one<NW, OCG, OCH, RF, TL, PAIRS>(pl, rs, st, io, oc, lds, bq, wid_q, lane_q);
+    bsync<NW>();      // (LDS is this instance's until every wave is through with it -- and the ticket until every wave has read it)
+  }
+}
+// The soft-row twin (mpcqp_set_soft_rows): the same launch -- the text above, kept apart so that the plain kernel's does not change -- with one more argument,
+// the weights.  Instantiated in units of its own (k_oc_admm_soft*.hip); a handle that never sets soft rows never launches one.
+template <int NW, int OCG, int OCH, int RF, bool PAIRS = false>
+__global__ void __launch_bounds__(NW * WAVE, 2) mpcqp_oc_admm_soft_kernel(const DevPlan pl, const DevRes rs, const mpcqp_settings st, const DevIO io, const DevOc oc, const DevSoft sf) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x & 63;
+  int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if constexpr (NW == 4) wid = oc_wave_role4(lds, wid, lane, io.no_remap);
+  if constexpr (NW != 8) {      // (the four-wave instances, two workgroups per CU, keep a grid of one workgroup per instance: measured below)
+    const int b1 = __builtin_amdgcn_readfirstlane(io.order ? io.order[blockIdx.x] : (int)blockIdx.x);
+    if (b1 < 0) return;      // (mpcqp_set_skip: a -1 entry of the dispatch list)
+    oc_admm_one<NW, OCG, OCH, RF, false, PAIRS, true>(pl, rs, st, io, oc, lds, b1, wid, lane, &sf);
+    return;
+  }
+  const OcLds<NW> L = oc_lds<NW>(lds, pl, rs, oc);
+  int *ticket = reinterpret_cast<int *>(L.RED + 16 * NW);      // (the spare words in front of the chain tables)
+  if (threadIdx.x == 0) { ticket[1] = 0; ticket[2] = 0; ticket[3] = 0; }
+  for (;;) {
+    if (!oc.resume) { if (threadIdx.x == 0) *ticket = atomicAdd(io.queue, 1); }
+    else if (threadIdx.x < WAVE) {
+      // a resume launch serves the few instances that left the launch before: tickets are drawn 64 at a time, the wave looks at their status words together
+      // and keeps the waiting ones as a bit mask (one ticket and one barrier pair per instance made an all-idle launch of 8192 cost 0.1 - 0.2 ms)
+      int base = ticket[1]; unsigned long long mask = ((unsigned long long)(unsigned)ticket[3] << 32) | (unsigned)ticket[2];
+      while (mask == 0ull && base < io.count) {
+        int b0 = 0;
+        if (threadIdx.x == 0) b0 = atomicAdd(io.queue, WAVE);
+        base = __builtin_amdgcn_readfirstlane(b0);
+        const int t = base + (int)threadIdx.x;
+        int st_ = 0;
+        if (t < io.count) { const int bt = io.order ? io.order[t] : t; if (bt >= 0) st_ = io.status[bt]; }      // (a -1 entry, mpcqp_set_skip, reads as status 0)
+        mask = __ballot(st_ == OC_PENDING || st_ == OC_PENDING_NONCVX);
+      }
+      if (threadIdx.x == 0) {
+        if (mask == 0ull) *ticket = io.count;
+        else { *ticket = base + __builtin_ctzll(mask); mask &= mask - 1; }
+        ticket[1] = base; ticket[2] = (int)(unsigned)(mask & 0xffffffffull); ticket[3] = (int)(unsigned)(mask >> 32);
+      }
+    }
+    bsync<NW>();
+    const int t = __builtin_amdgcn_readfirstlane(*ticket);
+    if (t >= io.count) break;
+    const int bq = __builtin_amdgcn_readfirstlane(io.order ? io.order[t] : t);
+    if (bq < 0) break;      // (mpcqp_set_skip: the active instances stand first in the dispatch list, every later entry is -1 too)
+    // (lane and wave index made opaque per instance: everything derived from them is computed again for each instance, as in a fresh workgroup -- hoisted out of
+    // this loop it stays live across the whole body: 240 B of scratch in an instance that had none)
+    int lane_q = lane, wid_q = wid;
+    asm volatile("" : "+v"(lane_q), "+s"(wid_q));
+    oc_admm_one<NW, OCG, OCH, RF, false, PAIRS, true>(pl, rs, st, io, oc, lds, bq, wid_q, lane_q, &sf);
     bsync<NW>();      // (LDS is this instance's until every wave is through with it -- and the ticket until every wave has read it)
   }
 }

@@ -1043,8 +1043,10 @@ __device__ __forceinline__ void update_info_res(RCtx &cx, Info &in) {
   in.obj = uni(cx.st->scaling ? cx.cinv * v[14] : v[14]);
 }
 
-template <int NW>
-__device__ __forceinline__ bool primal_infeasible_res(RCtx &cx, double eps) {
+// SOFT (the soft-row twins of the two-kernel form's iteration kernel, kernel_oc_split.hpp): sw1 = the instance's scaled l1 weights; a row whose weight is below
+// the library's infinity has no bounded domain, and its entry of the certificate is that of a row with both bounds infinite
+template <int NW, bool SOFT = false>
+__device__ __forceinline__ bool primal_infeasible_res(RCtx &cx, double eps, [[maybe_unused]] const double *sw1 = nullptr) {
   const DevPlan &pl = *cx.pl; double *ws = cx.ws; const int wid = cx.wid, lane = cx.lane, tid = wid * WAVE + lane; constexpr int NT = NW * WAVE;
   const double *lb = ws + pl.o_l, *ub = ws + pl.o_u, *Eg = ws + pl.o_E, *Dg = ws + pl.o_D, *dy = ws + pl.o_dy;
   double v[2] = {0.0, 0.0};   // 0 nrm (max) 1 lhs (sum)
@@ -1055,6 +1057,7 @@ __device__ __forceinline__ bool primal_infeasible_res(RCtx &cx, double eps) {
       const double lo = lb[i], up = ub[i];
       if (up > Q_INFTY * Q_MIN_SCALING) { if (lo < -Q_INFTY * Q_MIN_SCALING) x = 0.0; else x = fmin(x, 0.0); }
       else if (lo < -Q_INFTY * Q_MIN_SCALING) x = fmax(x, 0.0);
+      if constexpr (SOFT) { if (sw1[i] < Q_INFTY) x = 0.0; }
       v[0] = fmax(v[0], fabs(cx.unscale ? Eg[i] * x : x));
       v[1] += up * fmax(x, 0.0) + lo * fmin(x, 0.0);
     }
@@ -1111,8 +1114,8 @@ __device__ __forceinline__ bool dual_infeasible_res(RCtx &cx, double eps) {
   return res;
 }
 
-template <int NW>
-__device__ __forceinline__ int check_termination_res(RCtx &cx, Info &in, int approximate) {
+template <int NW, bool SOFT = false>
+__device__ __forceinline__ int check_termination_res(RCtx &cx, Info &in, int approximate, [[maybe_unused]] const double *sw1 = nullptr) {
   const mpcqp_settings &st = *cx.st;
   double eps_abs = st.eps_abs, eps_rel = st.eps_rel, epi = st.eps_prim_inf, edi = st.eps_dual_inf;
   if (in.prim_res > Q_INFTY || in.dual_res > Q_INFTY || in.prim_res != in.prim_res || in.dual_res != in.dual_res) { in.obj = NAN; return MPCQP_NON_CVX; }
@@ -1121,7 +1124,9 @@ __device__ __forceinline__ int check_termination_res(RCtx &cx, Info &in, int app
   if (cx.pl->m == 0) pc = true;
   else {
     const double eps_prim = eps_abs + eps_rel * fmax(in.nz, in.nax);
-    if (in.prim_res < eps_prim) pc = true; else pic = primal_infeasible_res<NW>(cx, epi);
+    if (in.prim_res < eps_prim) pc = true;
+    else if constexpr (SOFT) pic = primal_infeasible_res<NW, true>(cx, epi, sw1);
+    else pic = primal_infeasible_res<NW>(cx, epi);
   }
   {
     double mx = fmax(in.nq, fmax(in.naty, in.npx));

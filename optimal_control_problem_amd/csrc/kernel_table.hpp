@@ -20,6 +20,10 @@ MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm(int nw, int ng, int nh);        //
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_rf(int nw, int ng, int nh);
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_p4(int rf);                      // four waves, two twisted pairs of chains (dissected order)
 MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_tl(int nw, int ng, int nh);     // sweeps on dense tiles of A (experiment, MPCQP_VTILES=1)     // re-factorises in place (the last launch of a solve)
+// mpcqp_oc_admm_soft_kernel: the soft-row twins of the three iteration tables above (mpcqp_set_soft_rows; k_oc_admm_soft*.hip); the tile experiment has none
+MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_soft(int nw, int ng, int nh);
+MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_soft_rf(int nw, int ng, int nh);
+MPCQP_HIDDEN const void *mpcqp_kernel_oc_admm_soft_p4(int rf);
 
 // kernel_polish.hpp (k_polish.hip): OSQP's polishing as a post-solve kernel, one wavefront per instance of a slice.  Per-instance pointers stand at the
 // slice's first instance (the kernel indexes by blockIdx); `fac` is the polish factor's own scratch (Lf, Lb, T of one instance: fac_stride doubles)

@@ -92,6 +92,9 @@ struct mpcqp_handle {
   // the skipped instances' slabs may lack: skip_full = a full set-up ran under a skip array (their scaling and factor), skip_mat = an
   // mpcqp_update_matrices solve did (their factor)
   const int *skip = nullptr; int *dskip = nullptr, *skip_list = nullptr; bool skip_listed = false, skip_full = false, skip_mat = false;
+  // soft rows (mpcqp_set_soft_rows): the argument of the soft twins of the iteration kernel -- the weights as they stand (borrowed, or the handle's copies dsw1 /
+  // dsw2 of host arrays) and the per-instance buffer of scaled weights, allocated by the first set call; soft = the following solves launch the twins
+  bool soft = false; DevSoft dsoft = {nullptr, nullptr, 0, 0, nullptr, 0}; double *dsw1 = nullptr, *dsw2 = nullptr;
 };
 // what a solve under the handle's skip array (or without one) leaves for the kept-workspace entries; mode = DevIO.reuse of the solve
 static void note_skip_state(mpcqp_handle *h, int mode) {
@@ -148,9 +151,9 @@ static const void *kernel_of(const KernelId &k) {
     case K_OC_MONO: return k.reuse ? mpcqp_kernel_oc_mono_r1(k.nw, k.ng, k.nh, k.tiles != 0) : mpcqp_kernel_oc_mono_r0(k.nw, k.ng, k.nh, k.tiles != 0);
     case K_OC_SETUP: return mpcqp_kernel_oc_setup(k.nw, k.hub != 0, k.reuse != 0);
     case K_OC_RESCALE: return mpcqp_kernel_oc_rescale(k.nw, k.hub != 0);
-    case K_OC_ADMM: return mpcqp_kernel_oc_admm(k.nw, k.ng, k.nh);
-    case K_OC_ADMM_RF: return mpcqp_kernel_oc_admm_rf(k.nw, k.ng, k.nh);
-    case K_OC_ADMM_P4: return mpcqp_kernel_oc_admm_p4(k.rf);
+    case K_OC_ADMM: return k.soft ? mpcqp_kernel_oc_admm_soft(k.nw, k.ng, k.nh) : mpcqp_kernel_oc_admm(k.nw, k.ng, k.nh);
+    case K_OC_ADMM_RF: return k.soft ? mpcqp_kernel_oc_admm_soft_rf(k.nw, k.ng, k.nh) : mpcqp_kernel_oc_admm_rf(k.nw, k.ng, k.nh);
+    case K_OC_ADMM_P4: return k.soft ? mpcqp_kernel_oc_admm_soft_p4(k.rf) : mpcqp_kernel_oc_admm_p4(k.rf);
     case K_OC_ADMM_TL: return mpcqp_kernel_oc_admm_tl(k.nw, k.ng, k.nh);
   }
   return nullptr;
@@ -168,7 +171,9 @@ static bool takes_matrix_updates(const mpcqp_handle *h) {
   const Selection &s = h->sel;
   return s.waves > 0 && s.oc && s.split && !s.tiles && !s.vtiles && oc_rescale_of(h) != nullptr;
 }
-static const void *oc_admm_of(const mpcqp_handle *h, bool rf = false) { return kernel_of(oc_admm_kernel_id_of(h->sel, rf)); }
+static const void *oc_admm_of(const mpcqp_handle *h, bool rf = false) { return kernel_of(oc_admm_kernel_id_of(h->sel, rf, h->soft)); }
+// the soft-row twins of a handle's iteration kernels (whether or not soft rows are set)
+static const void *oc_admm_soft_of(const mpcqp_handle *h, bool rf) { return kernel_of(oc_admm_kernel_id_of(h->sel, rf, true)); }
 // One solve of the two-kernel on-chip mode on stream s: set-up, iteration; then, for instances whose adaptive-rho step asked for a new factor
 // (kernel_oc_split.hpp: they leave the iteration kernel marked OC_PENDING), `resume_rounds` pairs of {re-factorisation, iteration} in which every other
 // workgroup returns at once, and a last pair whose iteration kernel re-factorises in place, so that any number of rho updates is served.
@@ -198,8 +203,9 @@ static int launch_oc_split(mpcqp_handle *h, DevIO &io, int count, bool reuse, hi
   DevOc docr = doc0; docr.resume = 1;
   DevOc docs0 = h->doc_setup; docs0.resume = 0;
   DevOc docsr = docs0; docsr.resume = 1;
-  void *args[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&doc0};
-  void *argr[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&docr};
+  // (the sixth entry is the soft twins' own argument: hipLaunchKernel reads as many entries as the kernel has parameters, five for every other kernel)
+  void *args[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&doc0, (void *)&h->dsoft};
+  void *argr[] = {(void *)&h->dp, (void *)&h->dres, (void *)&h->st, (void *)&io, (void *)&docr, (void *)&h->dsoft};
   void *sargs[] = {(void *)&h->dp, (void *)&h->dres_setup, (void *)&h->st, (void *)&io, (void *)&docs0};
   void *sargr[] = {(void *)&h->dp, (void *)&h->dres_setup, (void *)&h->st, (void *)&io, (void *)&docsr};
   HIPCHK(hipLaunchKernel(io.reuse == 2 ? oc_rescale_of(h) : oc_setup_of(h, reuse), grid, block_s, sargs, lds_setup, s));      // (DevIO.reuse 2: new matrices on the kept scaling)
@@ -397,11 +403,12 @@ static int prepare_kernels(mpcqp_handle *h) {
     // MaxDynamicSharedMemorySize is a property of the kernel function, shared by every handle that launches it: keep a running
     // maximum per function so that a later handle with a smaller footprint never lowers the limit under an earlier one
     static std::mutex mu; static std::map<std::pair<const void *, int>, long> limit;   // (function, device)
-    const void *fns[5] = {res_kernel_of(h, false), res_kernel_of(h, true), nullptr, nullptr, nullptr};
+    const void *fns[7] = {res_kernel_of(h, false), res_kernel_of(h, true), nullptr, nullptr, nullptr, nullptr, nullptr};
     if (s.waves == 0) fns[0] = fns[1] = stream_kernel_of(h);
     if (s.split) { fns[0] = oc_setup_of(h, false); fns[1] = oc_setup_of(h, true); fns[2] = oc_admm_of(h, false); fns[3] = oc_admm_of(h, true); fns[4] = oc_rescale_of(h); }
+    if (takes_soft_rows(s)) { fns[5] = oc_admm_soft_of(h, false); fns[6] = oc_admm_soft_of(h, true); }      // (the twins a later mpcqp_set_soft_rows switches to: the limit is set here, once)
     std::lock_guard<std::mutex> lock(mu);
-    for (int k = 0; k < 5; k++) {
+    for (int k = 0; k < 7; k++) {
       const void *fn = fns[k];
       if (!fn) continue;
       const long want_lds = (s.split && (k < 2 || k == 4)) ? s.setup.lds : s.lds;
@@ -836,6 +843,42 @@ int mpcqp_set_skip(mpcqp_handle *h, const int *skip, int mem) {
   return MPCQP_OK;
 }
 
+int mpcqp_set_soft_rows(mpcqp_handle *h, const double *w1, long stride1, const double *w2, long stride2, int mem) {
+  if (!h) return fail(MPCQP_ERR_ARG, "null handle");
+  if (!w1) { h->soft = false; return MPCQP_OK; }      // (the buffers stay the handle's: a later set call reuses them)
+  if (h->inner) return fail(MPCQP_ERR_LIMIT, "mpcqp_set_soft_rows: a reduced or presolved handle does not take soft rows (its rows are not the caller's)");
+  if (!takes_soft_rows(h->sel) || !oc_admm_soft_of(h, false) || !oc_admm_soft_of(h, true))
+    return fail(MPCQP_ERR_LIMIT, "mpcqp_set_soft_rows: this handle does not run the two-kernel on-chip form (MPCQP_VARIANT=oc4 / oc8 at create names it, where the pattern admits it)");
+  if (h->polish) return fail(MPCQP_ERR_STATE, "mpcqp_set_soft_rows: polishing is on (mpcqp_set_polish); its active-set guess assumes hard bounds");
+  if (mem != MPCQP_MEM_HOST && mem != MPCQP_MEM_DEVICE) return fail(MPCQP_ERR_ARG, "mem must be MPCQP_MEM_HOST or MPCQP_MEM_DEVICE");
+  const long m = h->m;
+  if (m <= 0) return fail(MPCQP_ERR_ARG, "mpcqp_set_soft_rows: the QP has no rows");
+  if (stride1 < 0 || stride2 < 0 || (stride1 && stride1 < m) || (w2 && stride2 && stride2 < m)) return fail(MPCQP_ERR_ARG, "stride smaller than the array it strides (dimension mismatch)");
+  HIPCHK(hipSetDevice(h->device));
+  int rc;
+  const size_t B = h->batch;
+  if (!h->dsoft.buf) {
+    const Plan &pl = h->sel.plan;
+    h->dsoft.ms = std::max((pl.mpad + WAVE - 1) / WAVE, pl.A.nchunks) * WAVE;
+    if ((rc = dalloc(h, &h->dsoft.buf, B * 2 * (size_t)h->dsoft.ms))) return rc;
+  }
+  if (mem == MPCQP_MEM_HOST) {
+    if (h->solved) HIPCHK(hipStreamSynchronize(h->last_stream));      // (a solve in flight may still read the copies)
+    auto bad = [&](const double *w, long st_) {      // (host arrays are checked: weights are >= 0 and not NaN)
+      for (long k = 0; w && k < (st_ ? (long)B : 1L); k++) for (long i = 0; i < m; i++) if (!(w[k * st_ + i] >= 0.0)) return true;
+      return false;
+    };
+    if (bad(w1, stride1) || bad(w2, stride2)) return fail(MPCQP_ERR_ARG, "mpcqp_set_soft_rows: a weight is negative or NaN");
+    if ((rc = stage(h, &h->dsw1, w1, stride1, m, &h->dsoft.w1, &h->dsoft.s1))) return rc;
+    if (w2) { if ((rc = stage(h, &h->dsw2, w2, stride2, m, &h->dsoft.w2, &h->dsoft.s2))) return rc; }
+    else { h->dsoft.w2 = nullptr; h->dsoft.s2 = 0; }
+  } else {
+    h->dsoft.w1 = w1; h->dsoft.s1 = stride1; h->dsoft.w2 = w2; h->dsoft.s2 = w2 ? stride2 : 0;
+  }
+  h->soft = true;
+  return MPCQP_OK;
+}
+
 int mpcqp_debug_skip_list(mpcqp_handle *h, int *list, int mem) {
   if (!h || !list) return fail(MPCQP_ERR_ARG, "null pointer");
   if (h->inner) return mpcqp_debug_skip_list(h->inner, list, mem);
@@ -900,6 +943,7 @@ int mpcqp_solve_host(mpcqp_handle *h, const double *P, long sP, const double *q,
   const long wP = h->sel.plan.nnzP_in, wA = h->sel.plan.nnzA_in, n = h->n, m = h->m;
   if (h->inner) return fail(MPCQP_ERR_STATE, "mpcqp_solve_host is not available on a reduced handle");
   if (h->skip) return fail(MPCQP_ERR_STATE, "mpcqp_solve_host solves the whole batch: clear the skip array first (mpcqp_set_skip(h, NULL, 0))");
+  if (h->soft) return fail(MPCQP_ERR_STATE, "mpcqp_solve_host does not take soft rows: clear them first (mpcqp_set_soft_rows(h, NULL, 0, NULL, 0, 0)) or use mpcqp_update + mpcqp_solve");
   if ((sP && sP != wP) || sq != n || (sA && sA != wA) || (m > 0 && (sl != m || su != m)))
     return fail(MPCQP_ERR_ARG, "dimension mismatch: mpcqp_solve_host takes dense instance-major arrays (stride = width; 0 shares P or A)");
   HIPCHK(hipSetDevice(h->device));
@@ -1034,6 +1078,7 @@ int mpcqp_set_polish(mpcqp_handle *h, int enable, double delta, int refine_iter)
     return rc;
   }
   if (!enable) { h->polish = false; h->polish_timed = false; return MPCQP_OK; }
+  if (h->soft) return fail(MPCQP_ERR_STATE, "mpcqp_set_polish: the handle has soft rows set (mpcqp_set_soft_rows); the polish's active-set guess assumes hard bounds");
   HIPCHK(hipSetDevice(h->device));
   if (!h->pfac) {
     if (int rc = mpcqp_polish_prepare(h->dp, h->device)) return rc;

@@ -496,6 +496,7 @@ struct KernelId {
   int reuse = 0;              // the kept-workspace twin (_r1 units; K_OC_SETUP: its reuse instance)
   int rf = 0;                 // K_OC_ADMM_P4: the instance that re-factorises in place (K_OC_ADMM_RF is a kind of its own)
   int tiles = 0;              // K_OC_MONO: the tile experiment's instance
+  int soft = 0;               // K_OC_ADMM / K_OC_ADMM_RF / K_OC_ADMM_P4: the soft-row twin (mpcqp_set_soft_rows; k_oc_admm_soft*.hip)
 };
 // the streaming kernel of a handle without resident waves
 inline KernelId stream_kernel_id_of(const Selection &s) { KernelId k; k.kind = K_STREAM; k.nw = 1; k.pd = s.stream_pd8 ? 8 : 4; return k; }
@@ -520,17 +521,21 @@ inline KernelId res_kernel_id_of(const Selection &s, bool reuse) {
 // the kernels of the two-kernel on-chip form: the set-up (in its own launch shape), the kernel that takes its place after mpcqp_update_matrices, the iteration
 inline KernelId oc_setup_kernel_id_of(const Selection &s, bool reuse) { KernelId k; k.kind = K_OC_SETUP; k.nw = s.setup.nw; k.hub = s.ocplan.has_hub ? 1 : 0; k.reuse = reuse ? 1 : 0; return k; }
 inline KernelId oc_rescale_kernel_id_of(const Selection &s) { KernelId k; k.kind = K_OC_RESCALE; k.nw = s.setup.nw; k.hub = s.ocplan.has_hub ? 1 : 0; return k; }
-inline KernelId oc_admm_kernel_id_of(const Selection &s, bool rf) {
+// soft: the handle has soft rows set -- the twin of the same shape; the tile experiment has none (mpcqp_set_soft_rows refuses such a handle)
+inline KernelId oc_admm_kernel_id_of(const Selection &s, bool rf, bool soft = false) {
   KernelId k; k.nw = s.oc8 ? 8 : 4; k.ng = s.oc_ng(); k.nh = s.oc_nh(); k.hub = s.ocplan.has_hub ? 1 : 0;
-  if (!s.oc8 && s.ocplan.pairs.size() > 1) { k.kind = K_OC_ADMM_P4; k.rf = rf ? 1 : 0; return k; }      // (four waves, two twisted pairs: its own instances)
+  if (!s.oc8 && s.ocplan.pairs.size() > 1) { k.kind = K_OC_ADMM_P4; k.rf = rf ? 1 : 0; k.soft = soft ? 1 : 0; return k; }      // (four waves, two twisted pairs: its own instances)
   if (s.vtiles && !rf) { k.kind = K_OC_ADMM_TL; return k; }      // (the last launch of a solve, rf, runs the ELL sweeps: the set-up writes both forms)
-  k.kind = rf ? K_OC_ADMM_RF : K_OC_ADMM;
+  k.kind = rf ? K_OC_ADMM_RF : K_OC_ADMM; k.soft = soft ? 1 : 0;
   return k;
 }
-// the iteration (or only) kernel of a handle; rf: the last launch of a two-kernel solve, which re-factorises in place
-inline KernelId kernel_id_of(const Selection &s, bool reuse, bool rf) {
-  return s.waves == 0 ? stream_kernel_id_of(s) : s.split ? oc_admm_kernel_id_of(s, rf) : res_kernel_id_of(s, reuse);
+// the iteration (or only) kernel of a handle; rf: the last launch of a two-kernel solve, which re-factorises in place; soft: with soft rows set (two-kernel form
+// only: every other family's id keeps soft = 0, and mpcqp_set_soft_rows answers MPCQP_ERR_LIMIT there)
+inline KernelId kernel_id_of(const Selection &s, bool reuse, bool rf, bool soft = false) {
+  return s.waves == 0 ? stream_kernel_id_of(s) : s.split ? oc_admm_kernel_id_of(s, rf, soft) : res_kernel_id_of(s, reuse);
 }
+// which handles take soft rows: the two-kernel on-chip form without the tile experiment
+inline bool takes_soft_rows(const Selection &s) { return s.waves > 0 && s.oc && s.split && !s.tiles && !s.vtiles; }
 
 // DevOc.su_path of a two-kernel handle's set-up kernel (kernel_onchip.hpp): which of its on-chip and batched paths this handle takes
 inline int setup_path_bits(const Selection &s) {

@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 from . import _lib
-from .batch_qp import BatchQP
+from .batch_qp import BatchQP, with_soft_rows
 
 
 def _err(msg):
@@ -39,6 +39,7 @@ class CuCaQP:
         self._start = None
         self._rho0 = None
         self._skip = None
+        self._soft = None                      # (w1, w2) of setSoftRows
         self._skip_used = False                # some solve of this object may have run under a skip array
         self._kept = False
         self._polish = self._polish_applied = False
@@ -105,6 +106,26 @@ class CuCaQP:
         self._skip_used = self._skip_used or self._skip is not None
         if self._qp is not None:
             self._qp.set_skip(self._skip)
+
+    def setSoftRows(self, w1, w2=None):
+        """extension: soft constraint rows (mpcqp_set_soft_rows): w1, w2 [numOfConstraints] shared by the batch or [batch, numOfConstraints], >= 0 -- the
+        following solves add w1_i d_i + w2_i d_i^2 / 2 on the distance d_i of (Ax)_i to [l_i, u_i] instead of enforcing row i; w1_i >= 1e30 keeps row i
+        hard, w2 None means zeros, w1 None clears.  Kept across setSystem / initSolver.  Returns False where the handle refuses them -- a kernel family
+        other than the two-kernel on-chip form, a presolved handle, or together with setPolish(True); initSolver() then fails the same way."""
+        if w1 is None:
+            self._soft = None
+        else:
+            self._soft = (np.ascontiguousarray(w1, dtype=np.float64), None if w2 is None else np.ascontiguousarray(w2, dtype=np.float64))
+        if self._qp is not None:
+            try:
+                self._qp.set_soft_rows(*(self._soft or (None,)))
+            except (_lib.MpcqpError, ValueError) as e:
+                if getattr(e, "code", None) == _lib.ERR_LIMIT and not self._presolve:
+                    # (this handle's kernel family has no soft twin: the next initSolver() creates one that has, where the pattern admits it)
+                    self._qp.close(); self._qp = None; self._pattern_key = None; self._clear_solver()
+                    return True
+                return _err("Failed to set soft rows. (%s)" % e)
+        return True
 
     def setKeepScaling(self, keep):
         """extension (off by default): a solve() after updateHessianMatrix / updateLinearConstraintsMatrix keeps the scaling D, E, c of the last
@@ -284,8 +305,10 @@ class CuCaQP:
                 if self._presolve:
                     kw["presolve_bounds"] = (self.lowerBound, self.upperBound)
                 self._fixed_rows = key[-1]
-                self._qp = BatchQP(self.numOfVariables_, self.numOfConstraints_, self.batch, self._P[0], self._P[1],
-                                   self._A[0], self._A[1], device=self._device, **kw)
+                make = lambda family: BatchQP(self.numOfVariables_, self.numOfConstraints_, self.batch, self._P[0], self._P[1],
+                                              self._A[0], self._A[1], device=self._device, family=family, **kw)
+                # (soft rows: where the library's own choice of kernel family has no soft twin, the two-kernel on-chip forms are asked for by name)
+                self._qp = with_soft_rows(make, *self._soft) if self._soft is not None and not self._presolve else make(None)
                 self._pattern_key = key
                 self._kept = False
                 self._no_matrix_updates = False
@@ -303,6 +326,8 @@ class CuCaQP:
             self._qp.set_rho(self._rho0)
             if self._skip is not None:                     # (a cleared array was cleared on the handle by setSkip; a new handle has none)
                 self._qp.set_skip(self._skip)
+            if self._soft is not None:                     # (likewise)
+                self._qp.set_soft_rows(*self._soft)
         except (_lib.MpcqpError, ValueError) as e:
             return _err("Failed to initialize solver. (%s)" % e)
         self.isInitialized_ = True

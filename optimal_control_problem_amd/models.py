@@ -939,6 +939,32 @@ class StageOCP:
             lbg[:, self.ngd + self.N * self.nh:] = lo.ravel(); ubg[:, self.ngd + self.N * self.nh:] = hi.ravel()
         return lbx, ubx, lbg, ubg
 
+    # -- soft constraint rows of the stacked QP (include/mpcqp.h, mpcqp_set_soft_rows) ----------
+    SOFT_HARD = 1e30      # the l1 weight of a hard row: the library's infinity
+
+    def soft_rows(self, state=None, input=None, path=None, link=None):
+        """(w1, w2) over the m = n + ng rows of the stacked QP, where local_system puts them: the box rows of the states / inputs of frames 1 .. N-1, the
+        nh path rows of every frame, the nk link rows of every stage.  Each argument is a pair (w1, w2) of l1 / quadratic weights, scalars or one value per
+        component (nx, nu, nh, nk); None = hard.  The parameter rows, the pinned first frame and the dynamics rows are always hard.  The weights belong to
+        horizon positions: a receding horizon does not shift them."""
+        N, nx, nu, f, npp = self.N, self.nx, self.nu, self.f, self.np
+        w1 = np.full(self.m, self.SOFT_HARD); w2 = np.zeros(self.m)
+
+        def put(arg, rows, width, name):
+            if arg is None or width == 0:
+                return
+            a1, a2 = (np.broadcast_to(np.asarray(a, dtype=np.float64), (width,)) for a in arg)
+            if (a1 < 0).any() or (a2 < 0).any():
+                raise ValueError("soft_rows: %s weights must be >= 0" % name)
+            w1[rows] = a1; w2[rows] = a2            # (rows: [count, width])
+
+        k = np.arange(1, N)[:, None]
+        put(state, npp + k * f + np.arange(nx)[None, :], nx, "state")
+        put(input, npp + k * f + nx + np.arange(nu)[None, :], nu, "input")
+        put(path, self.n + self.ngd + np.arange(N)[:, None] * self.nh + np.arange(self.nh)[None, :], self.nh, "path")
+        put(link, self.n + self.ngd + N * self.nh + np.arange(N - 1)[:, None] * self.nk + np.arange(self.nk)[None, :], self.nk, "link")
+        return w1, w2
+
     # -- the hand-over between two MPC ticks (include/mpcqp.h, mpcqp_stage_advance; csrc/stage_kernels.hpp stage_advance_kernel) ----------
     STATUS_OK = (1, 2, 7)      # solved, solved_inaccurate, max_iter_reached: the QP returned a point (what mpcqp_stage_step takes too)
 

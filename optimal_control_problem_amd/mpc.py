@@ -15,7 +15,7 @@ from .sqp import DeviceSQPOptimizationSolver
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, options=None, batch=1, tail="rollout", shift=True, device=-1, codegen=None, shift_data=True, feedback=None):
+    def __init__(self, model, options=None, batch=1, tail="rollout", shift=True, device=-1, codegen=None, shift_data=True, feedback=None, soft_rows=None):
         """model: a models.StageOCP (zoo, generated or per_frame_reference).  options: those of DeviceSQPOptimizationSolver, passed through
         (warm_start_admm, carry_rho, constant_matrices, keep_scaling, presolve_fixed_rows, ...); max_iter defaults to 1 SQP iteration per
         tick and alpha to 1 (real-time iteration), skip_failed_steps to True (an infeasible QP keeps its iterate and holds the input).
@@ -23,7 +23,9 @@ class ClosedLoopMPC:
         lengths of a non-uniform time grid, models.StageOCP.transition_data); tick's d_new is then a ValueError.
         feedback=True or {"clamp_tol": ..., "reg": ...}: every tick also computes the time-varying LQR gains around its plan (one
         mpcqp_stage_riccati on the tick's local system; K, gain_failed) and hold() becomes available -- a plant step without a solve that tracks
-        the plan with u = u_k + K_k (s - s_k).  Without the option a tick is what it was, not a launch more."""
+        the plan with u = u_k + K_k (s - s_k).  Without the option a tick is what it was, not a launch more.
+        soft_rows: options["soft_rows"] of the loop (a dict for models.StageOCP.soft_rows, or (w1, w2) over the rows): a measured state outside its
+        box no longer makes the tick's QP infeasible.  The weights belong to horizon positions and are not shifted."""
         import torch
         if feedback is not None and feedback is not True and not isinstance(feedback, dict):
             raise ValueError("feedback: expected None, True or a dict with clamp_tol and / or reg")
@@ -42,6 +44,10 @@ class ClosedLoopMPC:
         if tail not in ("repeat", "rollout"):
             raise ValueError("tail must be 'repeat' or 'rollout'")
         opts = dict(options or {})
+        if soft_rows is not None:
+            if opts.get("soft_rows") is not None:
+                raise ValueError('soft_rows: given both as an argument and as options["soft_rows"]')
+            opts["soft_rows"] = soft_rows
         if opts.get("exact_hessian"):
             raise ValueError("exact_hessian is not available in ClosedLoopMPC: the multiplier estimate would need its own shift in advance, and "
                              "running a tick with unshifted multipliers would be silently wrong")

@@ -42,6 +42,11 @@ the same QPs.  What differs is what the call leaves behind: admm_iterations[i][b
 info -- rho included -- (host loop: the rows of last_qp_info) of a frozen instance are those of its last solved QP, not of a QP at the frozen point.  A LATER
 call that carries such state (warm_start_admm, carry_rho, keep_scaling, ClosedLoopMPC's hand-over, kkt(arg)) therefore starts from other values than after a call
 without the option, and agrees with it to the QPs' tolerance, not bit for bit.
+Opt-in as well: options["soft_rows"] = {"state": (w1, w2), "input": ..., "path": ..., "link": ...} (models.StageOCP.soft_rows) or a pair (w1, w2) of arrays over the rows of
+the QP makes those rows of every QP soft: w1 d + w2 d^2 / 2 on the distance d of the row's activity to its bounds instead of the bounds themselves (mpcqp_set_soft_rows; DESIGN
+3.14).  A measured state outside its box then no longer makes the QP infeasible.  The parameter rows, the pinned first frame and the dynamics stay hard; the weights belong to
+horizon positions.  Refused next to line_search, kkt_tol, exact_hessian and presolve_fixed_rows, whose merit, residuals and multipliers would need the penalty.
+
 Opt-in as well: options["initial_guess"] = "rollout" or "reshoot" makes a fresh iterate dynamically feasible before the first evaluation (models.StageOCP.rollout
 states the rule, mpcqp_stage_rollout runs it on the device): the first frame and the inputs are clipped to the call's lbx / ubx and the states
 become s_{k+1} = F(s_k, u_k), with u_k = u_0 ("rollout") or the stored iterate's own inputs ("reshoot": for a caller whose guess holds inputs only).  Applied once
@@ -88,6 +93,42 @@ def _initial_guess_option(value, model, evaluator=None):
     if (evaluator is not None and not hasattr(evaluator, "rollout")) or _is_general(model) or not hasattr(model, "rollout"):
         raise ValueError(ROLLOUT_NEEDS_DYNAMICS)
     return "hold" if value == "rollout" else "iterate"
+
+
+SOFT_ROWS_REFUSED = {
+    "line_search": 'options["soft_rows"] does not combine with options["line_search"]: the l1 merit counts a soft row\'s violation as infeasibility at weight mu, '
+                   'not at the row\'s own penalty, so its descent test would reject the steps the penalised QP asks for',
+    "kkt_tol": 'options["soft_rows"] does not combine with options["kkt_tol"]: the feasibility and complementarity residuals hold z to [l, u] and y to the '
+               'normal cone of the box; with soft rows y is a subgradient of the penalty and the residuals would need it',
+    "exact_hessian": 'options["soft_rows"] does not combine with options["exact_hessian"]: the multiplier estimate that weighs the constraint curvature is '
+                     'bounded by the penalty weights on soft rows, which the Lagrangian Hessian does not know of',
+    "presolve_fixed_rows": 'options["soft_rows"] does not combine with options["presolve_fixed_rows"]: a presolved handle answers MPCQP_ERR_LIMIT to '
+                           'mpcqp_set_soft_rows (its rows are not the caller\'s)',
+}
+
+
+def _soft_rows_option(options, model):
+    """options["soft_rows"]: None = every row hard.  A dict {state, input, path, link} of (w1, w2) pairs for models.StageOCP.soft_rows, or a pair (w1, w2) of
+    arrays over the m rows of the QP.  Returns None or (w1, w2) [m]; the weights belong to horizon positions.  Refused, with the reason, next to line_search,
+    kkt_tol, exact_hessian and presolve_fixed_rows: their merit, residuals and multipliers would need the penalty."""
+    value = options.get("soft_rows")
+    if value is None:
+        return None
+    for key, why in SOFT_ROWS_REFUSED.items():
+        if options.get(key):
+            raise ValueError(why)
+    if isinstance(value, dict):
+        if not hasattr(model, "soft_rows"):
+            raise ValueError('options["soft_rows"] as a dict names the rows of a stage OCP (models.StageOCP.soft_rows): pass (w1, w2) over the rows for this model')
+        w1, w2 = model.soft_rows(**value)
+    else:
+        w1, w2 = value
+        w1 = np.ascontiguousarray(w1, dtype=np.float64); w2 = np.zeros_like(w1) if w2 is None else np.ascontiguousarray(w2, dtype=np.float64)
+    if w1.shape != (model.m,) or w2.shape != (model.m,):
+        raise ValueError('options["soft_rows"]: expected %d weights, one per row of the QP' % model.m)
+    if (w1 < 0).any() or (w2 < 0).any() or np.isnan(w1).any() or np.isnan(w2).any():
+        raise ValueError('options["soft_rows"]: weights must be >= 0')
+    return w1, w2
 
 
 def _line_search_options(value):
@@ -207,6 +248,12 @@ class SQPOptimizationSolver:
         self.skip_converged_qps = _skip_option(options, self.kkt_tol)
         # extension, as in the device loop: an instance whose QP returned no point keeps its iterate (the reference adds the NaN solution, :171-177)
         self.skip_failed_steps = bool(options.get("skip_failed_steps", False))
+        # opt-in: soft constraint rows in every QP of the loop (qpSolver_.setSoftRows; include/mpcqp.h mpcqp_set_soft_rows)
+        self.soft_rows = _soft_rows_option(options, nlp)
+        if self.soft_rows is not None:
+            if not hasattr(self.qpSolver_, "setSoftRows"):
+                raise ValueError('options["soft_rows"]: this QP backend has no setSoftRows')
+            self.qpSolver_.setSoftRows(*self.soft_rows)
         self.line_search = _line_search_options(options.get("line_search"))
         if self.line_search is not None and not hasattr(nlp, "line_search"):
             raise ValueError("line_search needs a stage OCP (models.StageOCP) or a general NLP (general_nlp.GeneralNLP): this model states no merit line search")
@@ -445,6 +492,11 @@ class DeviceSQPOptimizationSolver:
         # breaks it comes back MPCQP_UNSOLVED / NaN (include/mpcqp.h).  Warm start, carried rho, keep_scaling and polish_qp go through the reduced
         # handle's forwarding.  Meant for per-frame references, whose N nx parameters push the full form off the on-chip kernels.
         self.presolve_fixed_rows = bool(options.get("presolve_fixed_rows", False))
+        # extension (opt-in): soft constraint rows in every QP of the loop (mpcqp_set_soft_rows): the weights live on the device and are
+        # borrowed by the handle, which is created on a kernel family that has soft twins (batch_qp.with_soft_rows)
+        self.soft_rows = _soft_rows_option(options, nlp)
+        if self.soft_rows is not None and self.polish_qp:
+            raise ValueError('options["soft_rows"] does not combine with options["polish_qp"]: the polish\'s active-set guess assumes hard bounds (MPCQP_ERR_STATE)')
         # extension (opt-in): a step length per instance by an l1-merit backtracking search starting at options["alpha"] -- one kernel
         # (mpcqp_stage_linesearch; mpcqp_nlp_linesearch with a general evaluator that has it) in place of the step + merit pair; see the module
         # docstring.  It always honours the QP status.
@@ -518,10 +570,17 @@ class DeviceSQPOptimizationSolver:
             self._ls_out["accepted"] = torch.zeros(self.batch, dtype=torch.int32, device=self.dev)
 
     def _create_qp(self, presolve_bounds):
-        from .batch_qp import BatchQP
+        import torch
+        from .batch_qp import BatchQP, with_soft_rows
         # reference SQPOptimizationSolver.cpp:80-85
-        self.qp = BatchQP(self.ev.n, self.ev.m, self.batch, self.ev.Pp, self.ev.Pi, self.ev.Ap, self.ev.Ai, presolve_bounds=presolve_bounds,
-                          eps_abs=1e-3, eps_rel=1e-3, max_iter=10000, warm_start=1 if self.warm_start_admm else 0, device=self._device)
+        make = lambda family: BatchQP(self.ev.n, self.ev.m, self.batch, self.ev.Pp, self.ev.Pi, self.ev.Ap, self.ev.Ai, presolve_bounds=presolve_bounds, family=family,
+                                      eps_abs=1e-3, eps_rel=1e-3, max_iter=10000, warm_start=1 if self.warm_start_admm else 0, device=self._device)
+        if self.soft_rows is not None:
+            dev = torch.device("cuda", torch.cuda.current_device() if self._device < 0 else self._device)
+            self._soft_dev = tuple(torch.as_tensor(w, dtype=torch.float64, device=dev).contiguous() for w in self.soft_rows)
+            self.qp = with_soft_rows(make, *self._soft_dev)
+        else:
+            self.qp = make(None)
         if self.constant_matrices or self.keep_scaling:
             self.qp.keep_workspace(True)
         if self.polish_qp:
