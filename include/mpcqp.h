@@ -816,6 +816,62 @@ typedef struct mpcqp_stage_riccati_args {
   int *failed;                  /* [batch], optional                                           */
 } mpcqp_stage_riccati_args;
 int mpcqp_stage_riccati(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_args *a, void *stream);
+/* The direct solve of the stage QP where no inequality is active (opt-in; models.StageOCP.direct_qp is the host statement).  The
+ * QP  min 1/2 w'P w + q'w  s.t.  l <= A w <= u  of a local system is, with every inequality slack, the equality-constrained tangent problem:
+ * one Riccati recursion with its affine terms solves that exactly.  The entry solves it per instance, tests the result against every inequality
+ * row, and reports in direct[b] whether the result IS the QP's solution; only the instances it does not accept need mpcqp_solve (direct > 0 is
+ * the array mpcqp_set_skip takes).  H_k, [A_k B_k] and acc(...) are those of mpcqp_stage_riccati above; w = [dp; d_0 .. d_{N-1}], d_k = [ds_k; du_k],
+ * variable c of frame k is column and identity row j = np + k f + c; q_k = q[np + k f ..]; dynamics row n + k nx + r reads
+ * ds_{k+1}[r] - ([A_k B_k] d_k)[r] and its entry on ds_{k+1} is taken as 1 (not read); path rows n + (N-1) nx + k nh + r, link rows behind them.
+ *   eligible   read from l, u alone.  All of: l_j == u_j == 0 on every parameter row; l == u on every state row of frame 0 (ds_0 = l there);
+ *              every input row of frame 0 either pinned (l == u: du = l) or free, no NaN in its l, u; on every identity row of the frames
+ *              k >= 1 no NaN in l, u and not l == u; l == u on every dynamics row (b_k = l there).  A NaN compares unequal.  Otherwise
+ *              direct[b] = -1 and nothing else is written.
+ *   backwards  k = N-1 .. 0.  Q as in mpcqp_stage_riccati.  g [f]: k = N-1: g = q_k.  k < N-1: h[j] = acc_i V_{k+1}[j][i] b_k[i] + v_{k+1}[j], then
+ *              g[c] = q_k[c] + acc_j [A_k B_k][j][c] h[j].
+ *              k = 0 only, the pins (P the pinned inputs, in ascending order): a free input i gets g_u[i] += acc_{p in P} Q_uu[p][i] l_p; a pinned
+ *              input p gets g_u[p] = -l_p, row p of Q_us = 0, row and column p of Q_uu = the unit vector.  There is no clamp in the frames k >= 1.
+ *              reg (>= 0) is added to the diagonal of Q_uu, free inputs only.
+ *              Cholesky and pivot test as in mpcqp_stage_riccati, with g_u as one more column: y0[jj] = (g_u[jj] - acc_t U[t][jj] y0[t]) / U[jj][jj].
+ *              A failed pivot at any frame ends the instance: direct[b] = -2, nothing else is written.
+ *              K_k as there; kappa_k: z_i = (y0[i] - acc_t U[i][t] z_t (t = i+1 .. nu-1)) / U[i][i], kappa_k[i] = -z_i.
+ *              k >= 1: V_k as there, v_k[r] = g_s[r] - acc_i Y[i][r] y0[i].
+ *   forwards   ds_0 = l.  du_k[i] = acc_j K_k[i][j] ds_k[j] + kappa_k[i] (a pinned input of frame 0: l, exactly);
+ *              ds_{k+1}[r] = acc_c [A_k B_k][r][c] d_k[c] + b_k[r].
+ *   adjoint    k = N-1 .. 0, in the convention of mpcqp_get (P w + q + A'y = 0):  e[c] = acc_r H_k[r][c] d_k[r] + q_k[c] (column c of H_k: P
+ *              stores both triangles),  t[c] = acc_r [A_k B_k][r][c] y_k[r] (0 at k = N-1),  val[c] = t[c] - e[c].  k >= 1: the multiplier of
+ *              dynamics row n + (k-1) nx + c is y_{k-1}[c] = val[c], c < nx: the state columns are stationary by construction, the input columns
+ *              by the gain.  k = 0: a pinned identity row j = np + c (every state, the pinned inputs) closes its own column, y_j = val[c].
+ *              A parameter row j closes its column too: y_j = -(acc_e P_e w_row(e) + q_j) over the entries of column j of P in rows >= np, in
+ *              storage order (dp = 0: the entries in the parameter rows are not read).  Every other row -- the identity rows of free
+ *              variables, the path rows, the link rows -- gets 0.
+ *   z          z_j = w_j on the identity rows, z = l on the dynamics rows (A w there, up to rounding), and on a path or link row the entries of
+ *              the row times w in ascending column order (a link row: frame k, then frame k + 1; a structural zero is skipped).
+ *   accepted   direct[b] = 1 iff l_i - feas_tol <= z_i <= u_i + feas_tol on every identity row of a free variable, every path row and every link
+ *              row (a NaN compares false and rejects); otherwise direct[b] = 0.  Only an accepted instance has w, y, z written; a rejected,
+ *              ineligible or failed one writes direct[b] alone, and a frozen one (frozen[b] != 0) is neither read nor written, direct[b] included.
+ * Why accepted means optimal: positive pivots make the objective strictly convex on the set the equalities (pins, dynamics) leave, so (w, y) is
+ * that set's unique minimiser with its multipliers; a minimiser over a set that also lies in a subset of it minimises over the subset, and zero
+ * multipliers on the slack inequalities complete the KKT conditions of the QP.  This needs no P >= 0 on the whole space: the entry can accept an
+ * instance mpcqp_solve would report as MPCQP_NON_CVX, and its answer is then the minimiser the tangent problem does have.
+ * The device runs the same operations with fused multiply-adds: it agrees with the statement to rounding.  stage_direct_kernel uses the size
+ * classes, lane groups and tiles of the gain sweep plus six vectors per group; K_k, kappa_k and d_k go through a workspace the handle owns
+ * (batch N (nu (nx + 1) + f) doubles, grown when a larger batch arrives); forward and adjoint passes run in the same kernel by the same group.  One
+ * writer per element, no atomics: bitwise repeatable, independent of the batch size and of the instance's position.  The first call builds the
+ * slot tables (those of mpcqp_stage_riccati included), and the first call at a batch allocates the workspace: either while `stream` is capturing
+ * answers MPCQP_ERR_STATE (call once before the capture); after that nothing is allocated and a captured graph replays the launch.
+ * MPCQP_ERR_ARG for a null s, a, P, q, A, l, u, w, y or direct, a negative (or NaN) feas_tol or reg, batch < 1; MPCQP_ERR_LIMIT (with the reason)
+ * for a handle with a link cost, as mpcqp_stage_riccati answers. */
+typedef struct mpcqp_stage_riccati_solve_args {
+  const double *P, *q, *A, *l, *u;   /* [batch * nnzP | n | nnzA | m | m], the local system          */
+  double feas_tol, reg;
+  const int *frozen;            /* [batch], optional: nonzero = neither read nor written       */
+  double *w;                    /* [batch * n], required                                       */
+  double *y;                    /* [batch * m], required                                       */
+  double *z;                    /* [batch * m], optional                                       */
+  int *direct;                  /* [batch], required: 1 accepted, 0 rejected, -1 ineligible, -2 a pivot failed */
+} mpcqp_stage_riccati_solve_args;
+int mpcqp_stage_riccati_solve(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_solve_args *a, void *stream);
 /* The feedback law at one frame, one thread per (instance, input): with row(v, stride) = v + b * stride,
  *   acc = acc_j K[b][k][i][j] * (s[j] - s_nom[j])     (each product and each sum rounded, no fused multiply-add: bitwise the host statement)
  *   u   = clip(u_nom[i] + acc), clip the two selects of mpcqp_stage_rollout against lo[i] / hi[i] (the identity without the pair)

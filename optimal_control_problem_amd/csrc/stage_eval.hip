@@ -86,6 +86,12 @@ struct mpcqp_stage {
   int *dlslots = nullptr;
   int *dkkt = nullptr;                // Ap and Ai on the device for mpcqp_stage_kkt
   int *dric = nullptr;                // the slot tables of mpcqp_stage_riccati, [N f f] of P then [(N - 1) nx f] of A, built by its first call
+  // the direct solve (mpcqp_stage_riccati_solve): its own slot tables (StageDirTab, built by its first call; dir_off: where each one starts) and
+  // the workspace of the launch, sized on first use like the convexification's
+  int *ddir = nullptr;
+  size_t dir_off[5] = {0, 0, 0, 0, 0};
+  double *ddws = nullptr;
+  int dir_cap = 0;
 };
 
 // a launch may not be larger than a stored parameter set
@@ -409,6 +415,8 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   if (s->dlslots) (void)hipFree(s->dlslots);
   if (s->dkkt) (void)hipFree(s->dkkt);
   if (s->dric) (void)hipFree(s->dric);
+  if (s->ddir) (void)hipFree(s->ddir);
+  if (s->ddws) (void)hipFree(s->ddws);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -749,6 +757,81 @@ int mpcqp_stage_riccati(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_arg
   const StageRicTab tab{s->dric, s->dric + (size_t)sd.N * sd.f * sd.f};
   const hipError_t e = sd.f <= 8 ? stage_launch_riccati<16, 8>(sd, batch, *a, tab, st)
                      : sd.f <= 16 ? stage_launch_riccati<16, 16>(sd, batch, *a, tab, st) : stage_launch_riccati<32, 24>(sd, batch, *a, tab, st);
+  MPCQP_HIPCHK(e);
+  return MPCQP_OK;
+}
+
+// Slot tables of mpcqp_stage_riccati_solve on top of the sweep's (StageDirTab): the path rows' and the link rows' entries of A per frame, and the
+// parameter columns of P below the parameter rows; all found in the pattern itself.
+static int stage_build_direct_tables(mpcqp_stage *s) {
+  const StageDev &sd = s->sd;
+  const int f = sd.f, nx = sd.nx, N = sd.N, nh = sd.nh, nk = sd.nk, np = sd.np;
+  const int rowh = sd.n + (N - 1) * nx, rowk = rowh + N * nh;
+  auto find = [&](int row, int col) {
+    for (int e = s->Ap[col]; e < s->Ap[col + 1]; e++) if (s->Ai[e] == row) return e;
+    return -1;
+  };
+  std::vector<int> hs((size_t)N * nh * f, -1), k0((size_t)(N - 1) * nk * f, -1), k1((size_t)(N - 1) * nk * f, -1), pcp(np + 1, 0), pcs, pcr;
+  for (int k = 0; k < N; k++)
+    for (int r = 0; r < nh; r++)
+      for (int c = 0; c < f; c++) hs[((size_t)k * nh + r) * f + c] = find(rowh + k * nh + r, np + k * f + c);
+  for (int k = 0; k < N - 1; k++)
+    for (int r = 0; r < nk; r++)
+      for (int c = 0; c < f; c++) {
+        k0[((size_t)k * nk + r) * f + c] = find(rowk + k * nk + r, np + k * f + c);
+        k1[((size_t)k * nk + r) * f + c] = find(rowk + k * nk + r, np + (k + 1) * f + c);
+      }
+  for (int j = 0; j < np; j++) {
+    for (int e = s->Pp[j]; e < s->Pp[j + 1]; e++)
+      if (s->Pi[e] >= np && s->Pi[e] < sd.n) { pcs.push_back(e); pcr.push_back(s->Pi[e] - np); }
+    pcp[j + 1] = (int)pcs.size();
+  }
+  std::vector<int> tab;
+  const std::vector<int> *parts[6] = {&hs, &k0, &k1, &pcp, &pcs, &pcr};
+  for (int i = 0; i < 6; i++) { if (i >= 1) s->dir_off[i - 1] = tab.size(); tab.insert(tab.end(), parts[i]->begin(), parts[i]->end()); }
+  tab.push_back(0);      // (never empty)
+  int *d = nullptr;
+  if (hipMalloc(&d, tab.size() * sizeof(int)) != hipSuccess) return mpcqp_set_error(MPCQP_ERR_HIP, "hipMalloc of the direct solve's slot tables failed");
+  if (hipMemcpy(d, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    return mpcqp_set_error(MPCQP_ERR_HIP, "upload of the direct solve's slot tables failed");
+  }
+  s->ddir = d;
+  return MPCQP_OK;
+}
+
+// the direct solve of the stage QP (stage_riccati.hpp; no model code takes part, so a generated library needs no export)
+int mpcqp_stage_riccati_solve(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_solve_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (!a->P || !a->q || !a->A || !a->l || !a->u) return mpcqp_set_error(MPCQP_ERR_ARG, "P, q, A, l and u are required");
+  if (!a->w || !a->y || !a->direct) return mpcqp_set_error(MPCQP_ERR_ARG, "w, y and direct are required");
+  if (!(a->feas_tol >= 0.0) || !(a->reg >= 0.0)) return mpcqp_set_error(MPCQP_ERR_ARG, "feas_tol and reg must not be negative");
+  if (s->link_cost)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "this handle has a link cost: its P couples neighbouring frames, and a Riccati recursion over the frame blocks alone would drop those terms");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  const StageDev &sd = s->sd;
+  if (!s->dric || !s->ddir || batch > s->dir_cap) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    MPCQP_HIPCHK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+      return mpcqp_set_error(MPCQP_ERR_STATE, "the first mpcqp_stage_riccati_solve of a handle (and the first at a larger batch) builds its slot tables and its workspace and may not run while the stream is capturing: call it once before the capture");
+    if (!s->dric) if (int rc = stage_build_riccati_tables(s)) return rc;
+    if (!s->ddir) if (int rc = stage_build_direct_tables(s)) return rc;
+    if (batch > s->dir_cap) {
+      double *nb = nullptr;
+      MPCQP_HIPCHK(hipMalloc(&nb, (size_t)batch * sd.N * ((size_t)sd.nu * (sd.nx + 1) + sd.f) * sizeof(double)));
+      MPCQP_HIPCHK(hipDeviceSynchronize());       // a launch that uses the old workspace may still be queued
+      if (s->ddws) (void)hipFree(s->ddws);
+      s->ddws = nb; s->dir_cap = batch;
+    }
+  }
+  const StageDirTab tab{s->dric, s->dric + (size_t)sd.N * sd.f * sd.f, s->ddir, s->ddir + s->dir_off[0], s->ddir + s->dir_off[1],
+                        s->ddir + s->dir_off[2], s->ddir + s->dir_off[3], s->ddir + s->dir_off[4]};
+  const hipError_t e = sd.f <= 8 ? stage_launch_direct<16, 8>(sd, batch, *a, tab, s->ddws, st)
+                     : sd.f <= 16 ? stage_launch_direct<16, 16>(sd, batch, *a, tab, s->ddws, st) : stage_launch_direct<32, 24>(sd, batch, *a, tab, s->ddws, st);
   MPCQP_HIPCHK(e);
   return MPCQP_OK;
 }

@@ -1218,6 +1218,209 @@ class StageOCP:
                 V = np.where(ok[:, None, None], Vn, 0.0)
         return {"K": K, "V": Vout, "failed": failed.astype(np.int32)}
 
+    # -- the direct solve of the stage QP (include/mpcqp.h, mpcqp_stage_riccati_solve; csrc/stage_riccati.hpp stage_direct_kernel) ----------
+    def _direct_slots(self):
+        """(hslot [N, nh, f], k0slot, k1slot [N - 1, nk, f], pcols): the slots of A that hold the path and link rows' entries per frame and, per
+        parameter column, its entries of P below the parameter rows as (slots, rows - np) -- the tables the handle builds on the device"""
+        if getattr(self, "_dir_slots", None) is None:
+            npp, n = self.np, self.n
+            pcols = []
+            for j in range(npp):
+                e = np.arange(self.Pp[j], self.Pp[j + 1])
+                rows = self.Pi[e].astype(np.int64)
+                keep = (rows >= npp) & (rows < n)
+                pcols.append((e[keep], rows[keep] - npp))
+            self._dir_slots = (self._A_h.copy(), self._A_k0.copy(), self._A_k1.copy(), pcols)
+        return self._dir_slots
+
+    def direct_qp(self, P, q, A, l, u, feas_tol=0.0, reg=0.0, frozen=None):
+        """Host statement of mpcqp_stage_riccati_solve (include/mpcqp.h has the rule in full): the local QP solved as its equality-constrained
+        tangent problem by one Riccati recursion with affine terms, then tested against every inequality row.  P [B, nnzP], q [B, n], A [B, nnzA],
+        l, u [B, m] on this model's pattern.  Returns (w [B, n], y [B, m], z [B, m], direct [B] int32): direct 1 = accepted, the result is the QP's
+        solution with its multipliers; 0 = some inequality is violated by more than feas_tol; -1 = not eligible (read from l, u); -2 = a pivot failed.
+        Rows of w, y, z of an instance that is not accepted are NaN (the device leaves them as they were); a frozen instance reports direct 0 here
+        (the device does not write it).  Sums run in ascending index order from 0, as in the header."""
+        if self.link_cost:
+            raise ValueError("direct_qp: this model has a link cost: its P couples neighbouring frames, and a Riccati recursion over the frame blocks "
+                             "alone would drop those terms")
+        if not (feas_tol >= 0.0) or not (reg >= 0.0):
+            raise ValueError("feas_tol and reg must not be negative")
+        P = np.asarray(P, float); A = np.asarray(A, float); q = np.asarray(q, float); l = np.asarray(l, float); u = np.asarray(u, float)
+        B, N, nx, nu, f, npp, n, m, nh, nk = P.shape[0], self.N, self.nx, self.nu, self.f, self.np, self.n, self.m, self.nh, self.nk
+        if P.shape != (B, len(self.Pi)) or A.shape != (B, len(self.Ai)) or q.shape != (B, n) or l.shape != (B, m) or u.shape != (B, m):
+            raise ValueError("P, q, A, l, u: expected shapes [B, %d], [B, %d], [B, %d], [B, %d], [B, %d] (dimension mismatch)"
+                             % (len(self.Pi), n, len(self.Ai), m, m))
+        pslot, aslot = self._riccati_slots()
+        hslot, k0slot, k1slot, pcols = self._direct_slots()
+        alive = np.ones(B, bool) if frozen is None else np.asarray(frozen).reshape(B) == 0
+        Pz = np.concatenate([P, np.zeros((B, 1))], axis=1)      # slot -1 reads the appended zero
+        lf = l[:, npp:n].reshape(B, N, f); uf = u[:, npp:n].reshape(B, N, f)
+        ld = l[:, n:n + self.ngd].reshape(B, N - 1, nx); ud = u[:, n:n + self.ngd].reshape(B, N - 1, nx)
+        qf = q[:, npp:n].reshape(B, N, f)
+        with np.errstate(all="ignore"):
+            el = ((l[:, :npp] == 0.0) & (u[:, :npp] == 0.0)).all(axis=1)
+            el &= (lf[:, 0, :nx] == uf[:, 0, :nx]).all(axis=1)
+            el &= (~np.isnan(lf[:, 0, nx:]) & ~np.isnan(uf[:, 0, nx:])).all(axis=1)
+            el &= (~np.isnan(lf[:, 1:]) & ~np.isnan(uf[:, 1:]) & ~(lf[:, 1:] == uf[:, 1:])).all(axis=(1, 2))
+            el &= (ld == ud).all(axis=(1, 2))
+            pin = lf[:, 0, nx:] == uf[:, 0, nx:]                 # [B, nu]
+            pval = lf[:, 0, nx:]
+            iu, ju = np.triu_indices(f)
+            ix, jx = np.triu_indices(nx)
+            dg = np.arange(nu)
+
+            def mirrored(M, i, j):
+                out = np.empty_like(M)
+                out[:, i, j] = M[:, i, j]; out[:, j, i] = M[:, i, j]
+                return out
+
+            H = [Pz[:, pslot[k]] for k in range(N)]
+            ABs = [-A[:, aslot[k]] for k in range(N - 1)]
+            Kk = np.zeros((B, N, nu, nx)); kap = np.zeros((B, N, nu))
+            V = np.zeros((B, nx, nx)); v = np.zeros((B, nx))
+            bad = np.zeros(B, bool)
+            for k in range(N - 1, -1, -1):
+                Q = H[k]
+                g = qf[:, k].copy()
+                if k < N - 1:
+                    AB = ABs[k]
+                    T = np.zeros((B, nx, f))
+                    for j in range(nx):
+                        T = T + V[:, :, j, None] * AB[:, j, None, :]
+                    acc = np.zeros((B, f, f))
+                    for j in range(nx):
+                        acc = acc + AB[:, j, :, None] * T[:, j, None, :]
+                    Q = mirrored(Q + acc, iu, ju)
+                    h = np.zeros((B, nx))
+                    for i in range(nx):
+                        h = h + V[:, :, i] * ld[:, k, i, None]
+                    h = h + v
+                    acc = np.zeros((B, f))
+                    for j in range(nx):
+                        acc = acc + AB[:, j, :] * h[:, j, None]
+                    g = g + acc
+                Qss = Q[:, :nx, :nx]
+                M = Q[:, nx:, :].copy()      # the input rows [Q_us Q_uu]: they become [Y U]
+                gu = g[:, nx:].copy()
+                if k == 0:
+                    acc = np.zeros((B, nu))
+                    for p_ in range(nu):     # Q_uu[p][i] l_p over the pinned inputs p
+                        acc = acc + np.where(pin[:, p_, None], M[:, p_, nx:] * pval[:, p_, None], 0.0)
+                    gu = np.where(pin, -pval, np.where(pin.any(axis=1)[:, None], gu + acc, gu))
+                    M[:, :, :nx] = np.where(pin[:, :, None], 0.0, M[:, :, :nx])
+                    M[:, :, nx:] = np.where(pin[:, :, None] | pin[:, None, :], np.eye(nu), M[:, :, nx:])
+                    cm = pin
+                else:
+                    cm = np.zeros((B, nu), bool)
+                M[:, dg, nx + dg] = M[:, dg, nx + dg] + np.where(cm, 0.0, reg)
+                dmax = np.ones(B)
+                for i in range(nu):
+                    vv = np.abs(M[:, i, nx + i])
+                    dmax = np.where(vv > dmax, vv, dmax)
+                thr = self.RICCATI_PIVOT * dmax
+                ud_ = np.zeros((B, nu)); y0 = np.zeros((B, nu))
+                for jj in range(nu):
+                    acc = np.zeros(B)
+                    for t in range(jj):
+                        acc = acc + M[:, t, nx + jj] * M[:, t, nx + jj]
+                    d = M[:, jj, nx + jj] - acc
+                    bad |= ~(d > thr)
+                    ud_[:, jj] = np.sqrt(d)
+                    s = np.zeros((B, f)); s0 = np.zeros(B)
+                    for t in range(jj):
+                        s = s + M[:, t, nx + jj, None] * M[:, t, :]
+                        s0 = s0 + M[:, t, nx + jj] * y0[:, t]
+                    new = (M[:, jj, :] - s) / ud_[:, jj, None]
+                    cols = list(range(nx)) + list(range(nx + jj + 1, f))
+                    M[:, jj, cols] = new[:, cols]
+                    y0[:, jj] = (gu[:, jj] - s0) / ud_[:, jj]
+                Y = M[:, :, :nx]
+                Z = np.zeros((B, nu, nx)); z0 = np.zeros((B, nu))
+                for i in range(nu - 1, -1, -1):
+                    s = np.zeros((B, nx)); s0 = np.zeros(B)
+                    for t in range(i + 1, nu):
+                        s = s + M[:, i, nx + t, None] * Z[:, t, :]
+                        s0 = s0 + M[:, i, nx + t] * z0[:, t]
+                    Z[:, i, :] = (Y[:, i, :] - s) / ud_[:, i, None]
+                    z0[:, i] = (y0[:, i] - s0) / ud_[:, i]
+                Kk[:, k] = -Z; kap[:, k] = -z0
+                if k > 0:
+                    acc = np.zeros((B, nx, nx)); acc0 = np.zeros((B, nx))
+                    for i in range(nu):
+                        acc = acc + Y[:, i, :, None] * Y[:, i, None, :]
+                        acc0 = acc0 + Y[:, i, :] * y0[:, i, None]
+                    V = mirrored(Qss - acc, ix, jx)
+                    v = g[:, :nx] - acc0
+            # forwards
+            d = np.zeros((B, N, f))
+            ds = lf[:, 0, :nx].copy()
+            for k in range(N):
+                acc = np.zeros((B, nu))
+                for j in range(nx):
+                    acc = acc + Kk[:, k, :, j] * ds[:, j, None]
+                du = acc + kap[:, k]
+                if k == 0:
+                    du = np.where(pin, pval, du)
+                d[:, k, :nx] = ds; d[:, k, nx:] = du
+                if k < N - 1:
+                    acc = np.zeros((B, nx))
+                    for c in range(f):
+                        acc = acc + ABs[k][:, :, c] * d[:, k, c, None]
+                    ds = acc + ld[:, k]
+            # the adjoint recursion
+            w = np.zeros((B, n)); y = np.zeros((B, m)); z = np.zeros((B, m))
+            w[:, npp:] = d.reshape(B, -1)
+            lam = np.zeros((B, nx))
+            for k in range(N - 1, -1, -1):
+                e = np.zeros((B, f))
+                for r in range(f):
+                    e = e + H[k][:, r, :] * d[:, k, r, None]
+                e = e + qf[:, k]
+                t = np.zeros((B, f))
+                if k < N - 1:
+                    for r in range(nx):
+                        t = t + ABs[k][:, r, :] * lam[:, r, None]
+                val = t - e
+                if k >= 1:
+                    lam = val[:, :nx]
+                    y[:, n + (k - 1) * nx:n + k * nx] = lam
+                else:
+                    y[:, npp:npp + nx] = val[:, :nx]
+                    y[:, npp + nx:npp + f] = np.where(pin, val[:, nx:], 0.0)
+            for j in range(npp):
+                slots, rows = pcols[j]
+                acc = np.zeros(B)
+                for e_, r_ in zip(slots, rows):
+                    acc = acc + P[:, e_] * w[:, npp + r_]
+                y[:, j] = -(acc + q[:, j])
+            # z and the test
+            z[:, :n] = w
+            z[:, n:n + self.ngd] = l[:, n:n + self.ngd]
+
+            def row(slots, dk, acc):
+                for c in range(f):
+                    if slots[c] >= 0:
+                        acc = acc + A[:, slots[c]] * dk[:, c]
+                return acc
+            rowh = n + self.ngd; rowk = rowh + N * nh
+            for k in range(N):
+                for r in range(nh):
+                    z[:, rowh + k * nh + r] = row(hslot[k, r], d[:, k], np.zeros(B))
+                if k < N - 1:
+                    for r in range(nk):
+                        z[:, rowk + k * nk + r] = row(k1slot[k, r], d[:, k + 1], row(k0slot[k, r], d[:, k], np.zeros(B)))
+            inside = (l - feas_tol <= z) & (z <= u + feas_tol)
+            tested = np.ones((B, m), bool)
+            tested[:, :npp + nx] = False
+            tested[:, npp + nx:npp + f] = ~pin
+            tested[:, n:n + self.ngd] = False
+            acc_ok = (inside | ~tested).all(axis=1)
+        direct = np.where(~el, -1, np.where(bad, -2, np.where(acc_ok, 1, 0)))
+        direct = np.where(alive, direct, 0).astype(np.int32)
+        out = direct != 1
+        w[out] = np.nan; y[out] = np.nan; z[out] = np.nan
+        return w, y, z, direct
+
     def feedback(self, K, k, s, s_nom, u_nom, lo=None, hi=None, x=None, lbx=None, ubx=None):
         """Host statement of mpcqp_stage_feedback: u = clip(u_nom + K[:, k] (s - s_nom)) with the sum over the state entries in ascending order,
         every product and sum rounded; clip is the two selects of `rollout` against lo / hi [B, nu] (both or neither).  Returns dict u, du = u - u_nom

@@ -19,6 +19,8 @@ class ClosedLoopMPC:
         """model: a models.StageOCP (zoo, generated or per_frame_reference).  options: those of DeviceSQPOptimizationSolver, passed through
         (warm_start_admm, carry_rho, constant_matrices, keep_scaling, presolve_fixed_rows, ...); max_iter defaults to 1 SQP iteration per
         tick and alpha to 1 (real-time iteration), skip_failed_steps to True (an infeasible QP keeps its iterate and holds the input).
+        options["direct_qp"]: a tick's QP is first solved directly where no inequality is active; the hand-over takes the merged
+        dw, y and status, and sol.direct_history holds the verdicts per tick.
         shift_data=False: a tick does not shift the stored stage data -- rows that belong to horizon positions, not to world time (the step
         lengths of a non-uniform time grid, models.StageOCP.transition_data); tick's d_new is then a ValueError.
         feedback=True or {"clamp_tol": ..., "reg": ...}: every tick also computes the time-varying LQR gains around its plan (one

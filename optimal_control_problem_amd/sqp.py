@@ -54,6 +54,13 @@ to a fresh iterate -- in the first getOptimalSolution after construction or afte
 `rollout_diverged` and `rollout_box_viol` report the outcome; an instance whose chain left the finite numbers takes the held trajectory.  Stage OCPs only.
 A stage OCP with a Gauss-Newton frame cost (models.StageOCP.rcost) needs no option: its local system carries 2 J'J and both loops run as
 they are; options["convexify"] and options["exact_hessian"] are refused for it with the model's reason.
+Opt-in as well: options["direct_qp"] = True or {"feas_tol":, "reg":} solves every QP first as its equality-constrained tangent problem -- one Riccati
+recursion with affine terms, then the step forwards and the multipliers backwards (models.StageOCP.direct_qp states the rule, mpcqp_stage_riccati_solve
+runs it on the device after P is final) -- and tests the result against every inequality row.  An instance that passes is solved: it takes
+the exact step and multipliers, status 1 and 0 ADMM iterations, and is left out of the QP launch (mpcqp_set_skip; host loop: setSkip where the backend
+has it); the others go through the QP solver as ever.  `direct_history` holds the verdicts (1 accepted, 0 rejected, -1 not eligible, -2 a pivot failed),
+one array per iteration; an instance that kkt_tol has frozen is not looked at, reports 0 and takes nothing.  Stage OCPs without a link cost only; refused with the reason next to constant_matrices, keep_scaling, carry_rho, soft_rows
+and presolve_fixed_rows.  The direct solve needs positive pivots on the equality set, not P >= 0: it can accept an instance the ADMM would call non-convex.
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -129,6 +136,47 @@ def _soft_rows_option(options, model):
     if (w1 < 0).any() or (w2 < 0).any() or np.isnan(w1).any() or np.isnan(w2).any():
         raise ValueError('options["soft_rows"]: weights must be >= 0')
     return w1, w2
+
+
+DIRECT_QP_REFUSES = {
+    "constant_matrices": 'options["direct_qp"] does not combine with options["constant_matrices"]: an accepted instance is left out of the QP launch '
+                         '(mpcqp_set_skip), and a full set-up under a skip array invalidates the kept workspace that option lives on',
+    "keep_scaling": 'options["direct_qp"] does not combine with options["keep_scaling"]: an accepted instance is left out of the QP launch '
+                    '(mpcqp_set_skip), and a full set-up under a skip array invalidates the kept workspace that option lives on',
+    "carry_rho": 'options["direct_qp"] does not combine with options["carry_rho"]: the info of an instance that is left out of the QP launch is not '
+                 'written, so there is no adapted rho to carry',
+    "soft_rows": 'options["direct_qp"] does not combine with options["soft_rows"]: the direct solve tests the rows\' bounds as hard ones and knows no penalty',
+    "presolve_fixed_rows": 'options["direct_qp"] does not combine with options["presolve_fixed_rows"]: the direct solve reads and writes the rows of the '
+                           'full form, a presolved handle has its own',
+}
+DIRECT_QP_NEEDS_STAGE = ('options["direct_qp"] is limited to stage OCPs (models.StageOCP): the direct solve is a Riccati recursion over frames and dynamics '
+                         'blocks, which a general NLP (evaluator=, mpcqp_nlp_*) does not have')
+DIRECT_QP_LINK_COST = ('options["direct_qp"]: this model has a link cost: its P couples neighbouring frames, and a Riccati recursion over the frame blocks '
+                       'alone would drop those terms')
+
+
+def _direct_qp_option(options, model, evaluator=None):
+    """options["direct_qp"]: None / False = off.  True or a dict {feas_tol, reg} -> (feas_tol, reg), both >= 0, default 0"""
+    value = options.get("direct_qp")
+    if value is None or value is False:
+        return None
+    if value is not True and not isinstance(value, dict):
+        raise ValueError("direct_qp: expected True or a dict with feas_tol and / or reg")
+    d = {} if value is True else value
+    unknown = set(d) - {"feas_tol", "reg"}
+    if unknown:
+        raise ValueError("direct_qp: unknown keys %s (feas_tol and reg are the options)" % sorted(unknown))
+    feas_tol, reg = float(d.get("feas_tol", 0.0)), float(d.get("reg", 0.0))
+    if not (feas_tol >= 0.0) or not (reg >= 0.0):
+        raise ValueError("direct_qp: feas_tol and reg must not be negative")
+    if evaluator is not None or _is_general(model) or not hasattr(model, "direct_qp"):
+        raise ValueError(DIRECT_QP_NEEDS_STAGE)
+    if getattr(model, "link_cost", False):
+        raise ValueError(DIRECT_QP_LINK_COST)
+    for key, why in DIRECT_QP_REFUSES.items():
+        if options.get(key) not in (None, False):
+            raise ValueError(why)
+    return feas_tol, reg
 
 
 def _line_search_options(value):
@@ -254,6 +302,11 @@ class SQPOptimizationSolver:
             if not hasattr(self.qpSolver_, "setSoftRows"):
                 raise ValueError('options["soft_rows"]: this QP backend has no setSoftRows')
             self.qpSolver_.setSoftRows(*self.soft_rows)
+        # opt-in: every QP is first solved as its equality-constrained tangent problem (models.StageOCP.direct_qp); the instances whose
+        # result passes every inequality row take it, exact multipliers included, and are left out of the backend's solve where it has setSkip.
+        # direct_history holds the verdicts, one int32 array per iteration
+        self.direct_qp = _direct_qp_option(options, nlp)
+        self.direct_history = []
         self.line_search = _line_search_options(options.get("line_search"))
         if self.line_search is not None and not hasattr(nlp, "line_search"):
             raise ValueError("line_search needs a stage OCP (models.StageOCP) or a general NLP (general_nlp.GeneralNLP): this model states no merit line search")
@@ -355,8 +408,15 @@ class SQPOptimizationSolver:
                     self.qpSolver_.setPrimalDualStart((1.0 - self.alpha_) * info["x"], info["y"])
                     if self.carry_rho and hasattr(self.qpSolver_, "setRhoStart"):
                         self.qpSolver_.setRhoStart(info["rho"])
-            if skipping and hasattr(self.qpSolver_, "setSkip"):
-                self.qpSolver_.setSkip(frozen.astype(np.int32) if frozen.any() else None)
+            taken = None
+            if self.direct_qp is not None:
+                dq = self.model.direct_qp(localSystem.P, localSystem.q, localSystem.A, localSystem.l, localSystem.u, self.direct_qp[0], self.direct_qp[1],
+                                          frozen=frozen.astype(np.int32))
+                taken = dq[3] > 0
+                self.direct_history.append(dq[3].copy())
+            if hasattr(self.qpSolver_, "setSkip") and (skipping or taken is not None):
+                left_out = (frozen if skipping else np.zeros(B, bool)) | (taken if taken is not None else False)
+                self.qpSolver_.setSkip(left_out.astype(np.int32) if left_out.any() else None)
             prev_solution, prev_info = (self._last_solution, self.last_qp_info) if skipping and frozen.any() else (None, None)
             self.qpSolver_.initSolver()
             self.qpSolver_.solve()
@@ -365,6 +425,17 @@ class SQPOptimizationSolver:
             self.timings["qp_ms"] += (t2 - t1) * 1e3
             solution = np.asarray(self.qpSolver_.getSolutionAsDM(), float).reshape(B, -1)
             self.last_qp_info = getattr(self.qpSolver_, "getInfo", lambda: None)()
+            if taken is not None and taken.any():        # an accepted instance reports the direct solve: exact step and multipliers, solved, 0 iterations
+                solution = np.where(taken[:, None], dq[0], solution)
+                if self.last_qp_info is not None:
+                    info = dict(self.last_qp_info)
+                    for key, val in (("x", dq[0]), ("y", dq[1]), ("z", dq[2])):
+                        if key in info:
+                            info[key] = np.where(taken[:, None], val, np.asarray(info[key], float).reshape(B, -1))
+                    for key, val in (("status", 1), ("iters", 0)):
+                        if key in info:
+                            info[key] = np.where(taken, val, np.asarray(info[key])).astype(np.asarray(info[key]).dtype)
+                    self.last_qp_info = info
             if prev_solution is not None:                # skip_converged_qps: a frozen instance reports its last solved QP, whatever the backend left there
                 solution = np.where(frozen[:, None], prev_solution, solution)
                 if self.last_qp_info is not None and prev_info is not None:
@@ -497,6 +568,12 @@ class DeviceSQPOptimizationSolver:
         self.soft_rows = _soft_rows_option(options, nlp)
         if self.soft_rows is not None and self.polish_qp:
             raise ValueError('options["soft_rows"] does not combine with options["polish_qp"]: the polish\'s active-set guess assumes hard bounds (MPCQP_ERR_STATE)')
+        # extension (opt-in): one mpcqp_stage_riccati_solve between the final P and the QP update: the QP solved as its equality-
+        # constrained tangent problem and tested against every inequality row.  The instances it accepts are the QP handle's skip array for this
+        # iteration (ORed with the kkt verdicts under skip_converged_qps) and take the direct w, y with status 1 and 0 iterations; the others go
+        # through the ADMM as ever.  Nothing comes back to the host; direct_history holds one cloned verdict tensor per iteration.
+        self.direct_qp = _direct_qp_option(options, nlp, evaluator)
+        self.direct_history = []
         # extension (opt-in): a step length per instance by an l1-merit backtracking search starting at options["alpha"] -- one kernel
         # (mpcqp_stage_linesearch; mpcqp_nlp_linesearch with a general evaluator that has it) in place of the step + merit pair; see the module
         # docstring.  It always honours the QP status.
@@ -568,6 +645,10 @@ class DeviceSQPOptimizationSolver:
             self.mu = torch.zeros(self.batch, dtype=torch.float64, device=self.dev)      # the penalty, monotone across iterations and calls
             self._ls_out = {k: torch.zeros(self.batch, dtype=torch.float64, device=self.dev) for k in ("alpha", "step_max", "f", "gmax")}
             self._ls_out["accepted"] = torch.zeros(self.batch, dtype=torch.int32, device=self.dev)
+        if self.direct_qp is not None:
+            # the staging of the direct solve (z is not wanted) and the persistent skip mask the QP handle borrows
+            self._dq = {"w": mk(self.ev.n), "y": mk(self.ev.m), "z": None, "direct": torch.zeros(self.batch, dtype=torch.int32, device=self.dev)}
+            self._dq_skip = torch.zeros(self.batch, dtype=torch.int32, device=self.dev)
 
     def _create_qp(self, presolve_bounds):
         import torch
@@ -667,6 +748,15 @@ class DeviceSQPOptimizationSolver:
             elif self.convexify is not None:
                 ev.convexify(p, self.x, self.ls["P"], self.convexify[0], self.convexify[1], touched=self._touched, stream=stream)
                 self.convexified.append(self._touched.clone())
+            direct = self.direct_qp is not None
+            if direct:       # P is final: solve directly, test, and leave the accepted instances out of the QP launch
+                ev.riccati_solve(self.ls, self.direct_qp[0], self.direct_qp[1], frozen=self._kkt_conv if kkt and i >= 1 else None, out=self._dq,
+                                 stream=stream)
+                if kkt and i >= 1:       # the kernel leaves a frozen instance's slot alone: it reports 0, as in the host loop, and takes nothing
+                    self._dq["direct"].copy_(torch.where(self._kkt_conv != 0, torch.zeros_like(self._dq["direct"]), self._dq["direct"]))
+                taken = self._dq["direct"] > 0
+                self._dq_skip.copy_(taken | (self._kkt_conv != 0) if skipping and i >= 1 else taken)
+                self.direct_history.append(self._dq["direct"].clone())
             if self.qp is None:                          # presolve_fixed_rows: the fixed rows are read off this first system's bounds
                 torch.cuda.current_stream(self.dev).synchronize()
                 self._create_qp((self.ls["l"], self.ls["u"]))
@@ -701,10 +791,17 @@ class DeviceSQPOptimizationSolver:
                     self.dw.zero_(); self.y.zero_()
                     self.qp.set_rho(None)
                 self.qp.warm_start(self.dw, self.y)
-            if skipping and i >= 1:
+            if direct:
+                self.qp.set_skip(self._dq_skip)          # written above on this stream
+            elif skipping and i >= 1:
                 self.qp.set_skip(self._kkt_conv)         # the check above has written it on this stream
             self.qp.solve(stream)
             self.qp.get_device(x=self.dw, y=self.y, status=self.status, iters=self.iters, info=self.info)
+            if direct:       # torch.where selects: whatever the handle holds for an instance it never solved does not leak through
+                rows = taken.unsqueeze(1)
+                self.dw.copy_(torch.where(rows, self._dq["w"], self.dw)); self.y.copy_(torch.where(rows, self._dq["y"], self.y))
+                self.status.copy_(torch.where(taken, torch.ones_like(self.status), self.status))
+                self.iters.copy_(torch.where(taken, torch.zeros_like(self.iters), self.iters))
             self._have_start = True
             self._start_clean = False
             status = self.status

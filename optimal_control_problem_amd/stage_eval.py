@@ -60,6 +60,12 @@ class RiccatiArgs(C.Structure):
                [(k, C.c_void_p) for k in ("frozen", "K", "V", "failed")]
 
 
+class RiccatiSolveArgs(C.Structure):
+    """mpcqp_stage_riccati_solve_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("P", "q", "A", "l", "u")] + [("feas_tol", C.c_double), ("reg", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("frozen", "w", "y", "z", "direct")]
+
+
 class FeedbackArgs(C.Structure):
     """mpcqp_stage_feedback_args (include/mpcqp.h)"""
     _fields_ = [("K", C.c_void_p), ("k", C.c_int)] + [(k, C.c_void_p) for k in ("s", "s_nom", "u_nom")] + \
@@ -108,6 +114,7 @@ def _bind(L):
     L.mpcqp_stage_lagrangian.argtypes = [vp, C.c_int, C.POINTER(LagrangianArgs), vp]
     L.mpcqp_stage_kkt.argtypes = [vp, C.c_int, vp, vp]
     L.mpcqp_stage_riccati.argtypes = [vp, C.c_int, C.POINTER(RiccatiArgs), vp]
+    L.mpcqp_stage_riccati_solve.argtypes = [vp, C.c_int, C.POINTER(RiccatiSolveArgs), vp]
     L.mpcqp_stage_feedback.argtypes = [vp, C.c_int, C.POINTER(FeedbackArgs), vp]
     L._stage_bound = True
     return L
@@ -526,6 +533,37 @@ class StageEvaluator:
             a.frozen = _check_int32(frozen, B, "frozen")
         _lib.check(_lib.lib().mpcqp_stage_riccati(self._h, B, C.byref(a), stream))
         return {"K": K, "V": V, "failed": failed}
+
+    def riccati_solve(self, ls, feas_tol=0.0, reg=0.0, frozen=None, out=None, stream=None):
+        """the local QP solved directly where no inequality is active, one kernel (mpcqp_stage_riccati_solve; models.StageOCP.direct_qp is its
+        host statement): the equality-constrained tangent problem by a Riccati recursion with its affine terms, the step forwards, the
+        multipliers backwards, and the test of every inequality row.  ls: the dict eval wrote (P, q, A, l, u).  Returns dict w [B, n], y [B, m],
+        z [B, m], direct (int32 [B]: 1 accepted -- w, y, z are the QP's solution; 0 rejected, -1 not eligible, -2 a pivot failed -- w, y, z keep
+        what they held), device tensors; `out`: such a dict to write into (w, y, direct required; z may be absent or None: not written).  frozen
+        (int32 [B]): an instance with a nonzero entry is neither read nor written.  direct > 0 is the array BatchQP.set_skip takes.  The first call
+        of a handle (and the first at a larger batch) builds tables and a workspace and may not run under stream capture."""
+        import torch
+        P = ls["P"]
+        if not isinstance(P, torch.Tensor) or P.dim() != 2:
+            raise ValueError("P: expected a contiguous float64 CUDA tensor of shape (B, %d)" % self.nnzP)
+        if not (feas_tol >= 0.0) or not (reg >= 0.0):
+            raise ValueError("feas_tol and reg must not be negative")
+        B = P.shape[0]
+        a = RiccatiSolveArgs()
+        a.P, a.q, a.A = _check(P, (B, self.nnzP), "P"), _check(ls["q"], (B, self.n), "q"), _check(ls["A"], (B, self.nnzA), "A")
+        a.l, a.u = _check(ls["l"], (B, self.m), "l"), _check(ls["u"], (B, self.m), "u")
+        a.feas_tol, a.reg = float(feas_tol), float(reg)
+        if out is None:
+            out = {"w": torch.zeros((B, self.n), dtype=torch.float64, device=P.device), "y": torch.zeros((B, self.m), dtype=torch.float64, device=P.device),
+                   "z": torch.zeros((B, self.m), dtype=torch.float64, device=P.device), "direct": torch.zeros((B,), dtype=torch.int32, device=P.device)}
+        a.w, a.y = _check(out["w"], (B, self.n), "w"), _check(out["y"], (B, self.m), "y")
+        if out.get("z") is not None:
+            a.z = _check(out["z"], (B, self.m), "z")
+        a.direct = _check_int32(out["direct"], B, "direct")
+        if frozen is not None:
+            a.frozen = _check_int32(frozen, B, "frozen")
+        _lib.check(_lib.lib().mpcqp_stage_riccati_solve(self._h, B, C.byref(a), stream))
+        return out
 
     @staticmethod
     def _rows(t, w, B, name):
