@@ -872,6 +872,61 @@ typedef struct mpcqp_stage_riccati_solve_args {
   int *direct;                  /* [batch], required: 1 accepted, 0 rejected, -1 ineligible, -2 a pivot failed */
 } mpcqp_stage_riccati_solve_args;
 int mpcqp_stage_riccati_solve(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_solve_args *a, void *stream);
+/* The direct solve with active input bounds (opt-in; models.StageOCP.direct_qp_active is the host statement): the entry above, then
+ * up to `rounds` primal-dual active-set rounds over the INPUT box rows, all in one kernel.  An input held at its bound is a pinned input, and the
+ * recursion absorbs a pin at no cost; state bounds, path rows and link rows are still only tested.  Notation, eligibility, reg, frozen, z and the
+ * pivot test are those of mpcqp_stage_riccati_solve.  The set S holds inputs (k, i) of any frame, each at its lower or its upper bound; the
+ * inputs of frame 0 that the bounds pin (l == u) stay pinned, are not part of S, and their entries of act_in / act_out are neither read nor written.
+ *   round 0    the entry above with S empty, operation for operation.  A failed pivot: direct[b] = -2.  An instance accepted here has that entry's
+ *              bits in w, y, z, direct[b] = 1 and rounds_used[b] = 0.
+ *   hopeless   after the forward pass of any round: some identity row of a state of a frame k >= 1, some path row or some link row has
+ *              !(l_i - feas_tol <= z_i <= u_i + feas_tol) (a NaN counts).  No set over the inputs repairs those rows here: direct[b] = 0 at once.
+ *   violation  a free input (not pinned, not in S) with du < l - feas_tol violates its lower bound, else with du > u + feas_tol its upper bound.
+ *   round 1's set   every violating input, held at the bound it violates; and every entry of act_in (when given) -1 / +1 whose input does not
+ *              violate, is not pinned and whose named bound is finite, held at that bound (an infinite bound cannot be held: the entry is ignored;
+ *              where guess and violation disagree the violation decides).
+ *   a round with S   the three passes of the entry above with the pin rule of frame 0 applied at every frame: the held set C of frame k is S's
+ *              inputs of that frame (and, k = 0, the pins), c_p the bound input p is held at (the pins: l).  After Q and g are formed, with Q as
+ *              it stands before any of it is rewritten and p in ascending order: a free input i gets g_u[i] += acc_{p in C} Q_uu[p][i] c_p;
+ *              for k >= 1 a state column j gets g_s[j] += acc_{p in C} Q_us[p][j] c_p (this enters v_k.  Frame 0 has no v_0, so the entry above
+ *              could leave the state columns out, and frame 0 still does); a held input p gets g_u[p] = -c_p, row p of Q_us = 0, row and column p
+ *              of Q_uu = the unit vector; reg is added on free inputs only.  Forwards a held input takes c_p exactly.  Adjoint: the identity row of
+ *              a held input closes its own column, y_j = val[c], as the pinned rows of frame 0 do.  A failed pivot in a round >= 1 rejects
+ *              (direct[b] = 0): with positive pivots in round 0 it can only be rounding.
+ *   test       primal as above: every identity row of a free variable, every path row, every link row within feas_tol.  Dual, in the sign
+ *              convention of mpcqp_get: a row held at its upper bound needs y_j >= -dual_tol, one held at its lower bound y_j <= dual_tol (a NaN
+ *              fails).  Both hold: direct[b] = 1, w, y, z are written, rounds_used[b] = the round.
+ *   update     test failed, not hopeless, rounds remain: every violating input joins S at the bound it violates, every held input whose
+ *              multiplier fails the dual test leaves S.  After round `rounds` the instance is rejected: direct[b] = 0.
+ *   act_out    the last set formed, i.e. the set of the last round the instance ran (round 0: empty), -1 / +1 / 0 per input, for accepted and
+ *              rejected instances alike: the next tick's guess.  rounds_used[b] = that round.  An ineligible (-1), failed (-2) or frozen instance
+ *              writes neither.  act_out may be act_in: an entry is read in round 0 and written at the end by the same thread.
+ * Why accepted means optimal: the argument of the entry above (a minimiser over a set that lies in a subset) does not carry over -- a held bound
+ * makes the round's feasible set SMALLER than the QP's.  What carries it is round 0: its positive pivots make the objective strictly convex on
+ * the set the pins and the dynamics leave, and the QP's feasible set lies in that set, so the QP has at most one KKT point and a KKT point is its
+ * minimiser.  A round's point with the primal and the dual test passed IS a KKT point of the QP: stationary by construction, feasible, zero
+ * multipliers on slack rows, the right sign on held ones.
+ * stage_direct_active_kernel uses the size classes, lane groups and tiles of stage_direct_kernel; its workspace (the handle's, grown with the
+ * batch: batch N (nu (nx + 1) + 2 f + 1) doubles) also holds val and the set words of the round at work and of the next.  The loop over rounds is
+ * uniform over the block; one writer per element, no atomics: bitwise repeatable, independent of the batch size and of the instance's position.
+ * Capture rules as above (the first call, and the first at a larger batch, answer MPCQP_ERR_STATE under capture).  MPCQP_ERR_ARG and
+ * MPCQP_ERR_LIMIT as above, MPCQP_ERR_ARG also for rounds outside 1 .. MPCQP_ACTIVE_MAX_ROUNDS and a negative (or NaN) dual_tol. */
+#define MPCQP_ACTIVE_MAX_ROUNDS 8
+typedef struct mpcqp_stage_riccati_solve_active_args {
+  const double *P, *q, *A, *l, *u;   /* [batch * nnzP | n | nnzA | m | m], the local system          */
+  double feas_tol, reg;
+  const int *frozen;            /* [batch], optional: nonzero = neither read nor written       */
+  double *w;                    /* [batch * n], required                                       */
+  double *y;                    /* [batch * m], required                                       */
+  double *z;                    /* [batch * m], optional                                       */
+  int *direct;                  /* [batch], required: 1 accepted, 0 rejected, -1 ineligible, -2 a pivot failed in round 0 */
+  int rounds;                   /* 1 .. MPCQP_ACTIVE_MAX_ROUNDS: the rounds after round 0      */
+  double dual_tol;              /* >= 0                                                        */
+  const int *act_in;            /* [batch * N * nu], optional: the guess, -1 / 0 / +1          */
+  int *act_out;                 /* [batch * N * nu], optional; may alias act_in                */
+  int *rounds_used;             /* [batch], optional                                           */
+} mpcqp_stage_riccati_solve_active_args;
+int mpcqp_stage_riccati_solve_active(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_solve_active_args *a, void *stream);
 /* The feedback law at one frame, one thread per (instance, input): with row(v, stride) = v + b * stride,
  *   acc = acc_j K[b][k][i][j] * (s[j] - s_nom[j])     (each product and each sum rounded, no fused multiply-add: bitwise the host statement)
  *   u   = clip(u_nom[i] + acc), clip the two selects of mpcqp_stage_rollout against lo[i] / hi[i] (the identity without the pair)

@@ -1421,6 +1421,243 @@ class StageOCP:
         w[out] = np.nan; y[out] = np.nan; z[out] = np.nan
         return w, y, z, direct
 
+    # -- the direct solve with held input bounds (include/mpcqp.h, mpcqp_stage_riccati_solve_active; csrc/stage_riccati_active.hpp) -------------
+    def _direct_active_round(self, P, q, A, l, u, reg, hold, cval):
+        """one round of the rule: the three passes of direct_qp with the inputs of hold [B, N, nu] (the pins of frame 0 included) fixed at
+        cval [B, N, nu].  Returns (d [B, N, f], y [B, m], z [B, m], bad [B]).  With no input held beyond the pins the operations are direct_qp's."""
+        B, N, nx, nu, f, npp, n, m, nh, nk = P.shape[0], self.N, self.nx, self.nu, self.f, self.np, self.n, self.m, self.nh, self.nk
+        pslot, aslot = self._riccati_slots()
+        hslot, k0slot, k1slot, pcols = self._direct_slots()
+        Pz = np.concatenate([P, np.zeros((B, 1))], axis=1)
+        lf = l[:, npp:n].reshape(B, N, f)
+        ld = l[:, n:n + self.ngd].reshape(B, N - 1, nx)
+        qf = q[:, npp:n].reshape(B, N, f)
+        iu, ju = np.triu_indices(f)
+        ix, jx = np.triu_indices(nx)
+        dg = np.arange(nu)
+
+        def mirrored(M, i, j):
+            out = np.empty_like(M)
+            out[:, i, j] = M[:, i, j]; out[:, j, i] = M[:, i, j]
+            return out
+
+        H = [Pz[:, pslot[k]] for k in range(N)]
+        ABs = [-A[:, aslot[k]] for k in range(N - 1)]
+        Kk = np.zeros((B, N, nu, nx)); kap = np.zeros((B, N, nu))
+        V = np.zeros((B, nx, nx)); v = np.zeros((B, nx))
+        bad = np.zeros(B, bool)
+        for k in range(N - 1, -1, -1):
+            Q = H[k]
+            g = qf[:, k].copy()
+            if k < N - 1:
+                AB = ABs[k]
+                T = np.zeros((B, nx, f))
+                for j in range(nx):
+                    T = T + V[:, :, j, None] * AB[:, j, None, :]
+                acc = np.zeros((B, f, f))
+                for j in range(nx):
+                    acc = acc + AB[:, j, :, None] * T[:, j, None, :]
+                Q = mirrored(Q + acc, iu, ju)
+                h = np.zeros((B, nx))
+                for i in range(nx):
+                    h = h + V[:, :, i] * ld[:, k, i, None]
+                h = h + v
+                acc = np.zeros((B, f))
+                for j in range(nx):
+                    acc = acc + AB[:, j, :] * h[:, j, None]
+                g = g + acc
+            Qss = Q[:, :nx, :nx]
+            M = Q[:, nx:, :].copy()
+            cm = hold[:, k]; cv = cval[:, k]
+            anyc = cm.any(axis=1)[:, None]
+            acc = np.zeros((B, f))
+            for p_ in range(nu):         # Q[p][c] c_p over the held inputs p, every column c
+                acc = acc + np.where(cm[:, p_, None], M[:, p_, :] * cv[:, p_, None], 0.0)
+            gu = np.where(cm, -cv, np.where(anyc, g[:, nx:] + acc[:, nx:], g[:, nx:]))
+            gs = np.where(anyc, g[:, :nx] + acc[:, :nx], g[:, :nx]) if k > 0 else g[:, :nx]
+            M[:, :, :nx] = np.where(cm[:, :, None], 0.0, M[:, :, :nx])
+            M[:, :, nx:] = np.where(cm[:, :, None] | cm[:, None, :], np.eye(nu), M[:, :, nx:])
+            M[:, dg, nx + dg] = M[:, dg, nx + dg] + np.where(cm, 0.0, reg)
+            dmax = np.ones(B)
+            for i in range(nu):
+                vv = np.abs(M[:, i, nx + i])
+                dmax = np.where(vv > dmax, vv, dmax)
+            thr = self.RICCATI_PIVOT * dmax
+            ud_ = np.zeros((B, nu)); y0 = np.zeros((B, nu))
+            for jj in range(nu):
+                acc = np.zeros(B)
+                for t in range(jj):
+                    acc = acc + M[:, t, nx + jj] * M[:, t, nx + jj]
+                d = M[:, jj, nx + jj] - acc
+                bad |= ~(d > thr)
+                ud_[:, jj] = np.sqrt(d)
+                s = np.zeros((B, f)); s0 = np.zeros(B)
+                for t in range(jj):
+                    s = s + M[:, t, nx + jj, None] * M[:, t, :]
+                    s0 = s0 + M[:, t, nx + jj] * y0[:, t]
+                new = (M[:, jj, :] - s) / ud_[:, jj, None]
+                cols = list(range(nx)) + list(range(nx + jj + 1, f))
+                M[:, jj, cols] = new[:, cols]
+                y0[:, jj] = (gu[:, jj] - s0) / ud_[:, jj]
+            Y = M[:, :, :nx]
+            Z = np.zeros((B, nu, nx)); z0 = np.zeros((B, nu))
+            for i in range(nu - 1, -1, -1):
+                s = np.zeros((B, nx)); s0 = np.zeros(B)
+                for t in range(i + 1, nu):
+                    s = s + M[:, i, nx + t, None] * Z[:, t, :]
+                    s0 = s0 + M[:, i, nx + t] * z0[:, t]
+                Z[:, i, :] = (Y[:, i, :] - s) / ud_[:, i, None]
+                z0[:, i] = (y0[:, i] - s0) / ud_[:, i]
+            Kk[:, k] = -Z; kap[:, k] = -z0
+            if k > 0:
+                acc = np.zeros((B, nx, nx)); acc0 = np.zeros((B, nx))
+                for i in range(nu):
+                    acc = acc + Y[:, i, :, None] * Y[:, i, None, :]
+                    acc0 = acc0 + Y[:, i, :] * y0[:, i, None]
+                V = mirrored(Qss - acc, ix, jx)
+                v = gs - acc0
+        d = np.zeros((B, N, f))
+        ds = lf[:, 0, :nx].copy()
+        for k in range(N):
+            acc = np.zeros((B, nu))
+            for j in range(nx):
+                acc = acc + Kk[:, k, :, j] * ds[:, j, None]
+            du = np.where(hold[:, k], cval[:, k], acc + kap[:, k])
+            d[:, k, :nx] = ds; d[:, k, nx:] = du
+            if k < N - 1:
+                acc = np.zeros((B, nx))
+                for c in range(f):
+                    acc = acc + ABs[k][:, :, c] * d[:, k, c, None]
+                ds = acc + ld[:, k]
+        w = np.zeros((B, n)); y = np.zeros((B, m)); z = np.zeros((B, m))
+        w[:, npp:] = d.reshape(B, -1)
+        lam = np.zeros((B, nx))
+        for k in range(N - 1, -1, -1):
+            e = np.zeros((B, f))
+            for r in range(f):
+                e = e + H[k][:, r, :] * d[:, k, r, None]
+            e = e + qf[:, k]
+            t = np.zeros((B, f))
+            if k < N - 1:
+                for r in range(nx):
+                    t = t + ABs[k][:, r, :] * lam[:, r, None]
+            val = t - e
+            o = npp + k * f
+            if k >= 1:
+                lam = val[:, :nx]
+                y[:, n + (k - 1) * nx:n + k * nx] = lam
+            else:
+                y[:, o:o + nx] = val[:, :nx]
+            y[:, o + nx:o + f] = np.where(hold[:, k], val[:, nx:], 0.0)
+        for j in range(npp):
+            slots, rows = pcols[j]
+            acc = np.zeros(B)
+            for e_, r_ in zip(slots, rows):
+                acc = acc + P[:, e_] * w[:, npp + r_]
+            y[:, j] = -(acc + q[:, j])
+        z[:, :n] = w
+        z[:, n:n + self.ngd] = l[:, n:n + self.ngd]
+
+        def row(slots, dk, acc):
+            for c in range(f):
+                if slots[c] >= 0:
+                    acc = acc + A[:, slots[c]] * dk[:, c]
+            return acc
+        rowh = n + self.ngd; rowk = rowh + N * nh
+        for k in range(N):
+            for r in range(nh):
+                z[:, rowh + k * nh + r] = row(hslot[k, r], d[:, k], np.zeros(B))
+            if k < N - 1:
+                for r in range(nk):
+                    z[:, rowk + k * nk + r] = row(k1slot[k, r], d[:, k + 1], row(k0slot[k, r], d[:, k], np.zeros(B)))
+        return d, w, y, z, bad
+
+    def direct_qp_active(self, P, q, A, l, u, feas_tol=0.0, reg=0.0, rounds=4, dual_tol=0.0, act=None, frozen=None):
+        """Host statement of mpcqp_stage_riccati_solve_active (include/mpcqp.h has the rule in full): direct_qp, then up to `rounds` primal-dual
+        active-set rounds over the input box rows, every round one Riccati solve with the held inputs fixed at their bounds.  act [B, N, nu]
+        (optional): the guess, -1 held at the lower bound, +1 at the upper bound, 0 free.  Returns (w [B, n], y [B, m], z [B, m], direct [B] int32,
+        act [B, N, nu] int32, rounds_used [B] int32).  direct as direct_qp; rows of w, y, z of an instance that is not accepted are NaN.  act and
+        rounds_used of an ineligible, failed or frozen instance are what came in (zeros without a guess) and -1: the device does not write them."""
+        if self.link_cost:
+            raise ValueError("direct_qp_active: this model has a link cost: its P couples neighbouring frames, and a Riccati recursion over the frame "
+                             "blocks alone would drop those terms")
+        if not (feas_tol >= 0.0) or not (reg >= 0.0) or not (dual_tol >= 0.0):
+            raise ValueError("feas_tol, reg and dual_tol must not be negative")
+        if int(rounds) != rounds or not 1 <= rounds <= 8:
+            raise ValueError("rounds: expected 1 .. 8")
+        P = np.asarray(P, float); A = np.asarray(A, float); q = np.asarray(q, float); l = np.asarray(l, float); u = np.asarray(u, float)
+        B, N, nx, nu, f, npp, n, m, nh, nk = P.shape[0], self.N, self.nx, self.nu, self.f, self.np, self.n, self.m, self.nh, self.nk
+        if P.shape != (B, len(self.Pi)) or A.shape != (B, len(self.Ai)) or q.shape != (B, n) or l.shape != (B, m) or u.shape != (B, m):
+            raise ValueError("P, q, A, l, u: expected shapes [B, %d], [B, %d], [B, %d], [B, %d], [B, %d] (dimension mismatch)"
+                             % (len(self.Pi), n, len(self.Ai), m, m))
+        guess = np.zeros((B, N, nu), np.int32) if act is None else np.array(act, np.int32).reshape(B, N, nu)
+        alive = np.ones(B, bool) if frozen is None else np.asarray(frozen).reshape(B) == 0
+        lf = l[:, npp:n].reshape(B, N, f); uf = u[:, npp:n].reshape(B, N, f)
+        ld = l[:, n:n + self.ngd].reshape(B, N - 1, nx); ud = u[:, n:n + self.ngd].reshape(B, N - 1, nx)
+        with np.errstate(all="ignore"):
+            el = ((l[:, :npp] == 0.0) & (u[:, :npp] == 0.0)).all(axis=1)
+            el &= (lf[:, 0, :nx] == uf[:, 0, :nx]).all(axis=1)
+            el &= (~np.isnan(lf[:, 0, nx:]) & ~np.isnan(uf[:, 0, nx:])).all(axis=1)
+            el &= (~np.isnan(lf[:, 1:]) & ~np.isnan(uf[:, 1:]) & ~(lf[:, 1:] == uf[:, 1:])).all(axis=(1, 2))
+            el &= (ld == ud).all(axis=(1, 2))
+            pin = np.zeros((B, N, nu), bool)
+            pin[:, 0] = lf[:, 0, nx:] == uf[:, 0, nx:]
+            lu, uu = lf[:, :, nx:], uf[:, :, nx:]                  # the inputs' bounds [B, N, nu]
+            # the rows no set over the inputs repairs: the states of the frames k >= 1, the path rows, the link rows
+            hard = np.zeros((B, m), bool)
+            for k in range(1, N):
+                hard[:, npp + k * f:npp + k * f + nx] = True
+            hard[:, n + self.ngd:] = True
+            lo = np.zeros((B, N, nu), bool); hi = np.zeros((B, N, nu), bool)          # the set S
+            w = np.full((B, n), np.nan); y = np.full((B, m), np.nan); z = np.full((B, m), np.nan)
+            direct = np.zeros(B, np.int32)
+            used = np.full(B, -1, np.int32)
+            open_ = alive & el
+            for r in range(rounds + 1):
+                if not open_.any():
+                    break
+                hold = pin | lo | hi
+                cval = np.where(hi, uu, lu)
+                d, wr, yr, zr, bad = self._direct_active_round(P, q, A, l, u, reg, hold, cval)
+                if r == 0:
+                    direct[open_ & bad] = -2
+                    open_ = open_ & ~bad
+                else:
+                    used[open_ & bad] = r
+                    open_ = open_ & ~bad
+                inside = (l - feas_tol <= zr) & (zr <= u + feas_tol)
+                hopeless = ~(inside | ~hard).all(axis=1)
+                du = d[:, :, nx:]
+                free = ~hold
+                vlo = free & (du < lu - feas_tol)
+                vhi = free & ~vlo & (du > uu + feas_tol)
+                primal = ((lu - feas_tol <= du) & (du <= uu + feas_tol) | ~free).all(axis=(1, 2))
+                yu = np.stack([yr[:, npp + k * f + nx:npp + (k + 1) * f] for k in range(N)], axis=1)
+                rel = (hi & ~(yu >= -dual_tol)) | (lo & ~(yu <= dual_tol))
+                dual = ~rel.any(axis=(1, 2))
+                used[open_ & hopeless] = r
+                open_ = open_ & ~hopeless
+                take = open_ & primal & dual
+                w[take] = wr[take]; y[take] = yr[take]; z[take] = zr[take]
+                direct[take] = 1; used[take] = r
+                open_ = open_ & ~take
+                if r == rounds:
+                    used[open_] = r
+                    break
+                # the next round's set, for the instances still open
+                up = open_[:, None, None]
+                if r == 0:
+                    can_lo = ~pin & np.isfinite(lu) & (guess < 0)
+                    can_hi = ~pin & np.isfinite(uu) & (guess > 0)
+                    nlo = vlo | (can_lo & ~vhi); nhi = vhi | (can_hi & ~vlo)
+                else:
+                    nlo = (lo | vlo) & ~rel; nhi = (hi | vhi) & ~rel
+                lo = np.where(up, nlo, lo); hi = np.where(up, nhi, hi)
+        done = alive & el & (direct != -2)
+        act_out = np.where(done[:, None, None] & ~pin, hi.astype(np.int32) - lo.astype(np.int32), guess).astype(np.int32)
+        direct = np.where(alive, np.where(~el, -1, direct), 0).astype(np.int32)
+        return w, y, z, direct, act_out, used
+
     def feedback(self, K, k, s, s_nom, u_nom, lo=None, hi=None, x=None, lbx=None, ubx=None):
         """Host statement of mpcqp_stage_feedback: u = clip(u_nom + K[:, k] (s - s_nom)) with the sum over the state entries in ascending order,
         every product and sum rounded; clip is the two selects of `rollout` against lo / hi [B, nu] (both or neither).  Returns dict u, du = u - u_nom

@@ -20,7 +20,8 @@ class ClosedLoopMPC:
         (warm_start_admm, carry_rho, constant_matrices, keep_scaling, presolve_fixed_rows, ...); max_iter defaults to 1 SQP iteration per
         tick and alpha to 1 (real-time iteration), skip_failed_steps to True (an infeasible QP keeps its iterate and holds the input).
         options["direct_qp"]: a tick's QP is first solved directly where no inequality is active; the hand-over takes the merged
-        dw, y and status, and sol.direct_history holds the verdicts per tick.
+        dw, y and status, and sol.direct_history holds the verdicts per tick.  With its "active_set" key the set of held inputs a tick
+        ends with (sol.act) is shifted by one frame with the plan -- a device slice copy, the last frame repeats -- and is the next tick's guess.
         shift_data=False: a tick does not shift the stored stage data -- rows that belong to horizon positions, not to world time (the step
         lengths of a non-uniform time grid, models.StageOCP.transition_data); tick's d_new is then a ValueError.
         feedback=True or {"clamp_tol": ..., "reg": ...}: every tick also computes the time-varying LQR gains around its plan (one
@@ -64,6 +65,7 @@ class ClosedLoopMPC:
         self.p = mk(B, ev.np); self._p2 = mk(B, ev.np) if ev.per_frame_reference else None
         self.lbx = mk(B, ev.nvar); self.ubx = mk(B, ev.nvar); self.lbg = mk(B, ev.ng); self.ubg = mk(B, ev.ng)
         self.applied = mk(B, ev.nx + ev.nu); self.stage_cost = mk(B)
+        self._act2 = torch.zeros_like(self.sol.act) if self.sol.direct_active is not None else None
         self.ticks = 0
         self._ready = False
         self._has_data = False
@@ -98,6 +100,8 @@ class ClosedLoopMPC:
         if shoot is not None:      # the bounds are written: the first frame of the zero iterate is clipped onto the pinned one
             r = self.ev.rollout(self.sol.x, lbx=self.lbx, ubx=self.ubx, inputs=shoot, stream=torch.cuda.current_stream(self.dev).cuda_stream)
             self.rollout_diverged, self.rollout_box_viol = r["diverged"], r["box_viol"]
+        if self.sol.direct_active is not None:
+            self.sol.act.zero_()      # no guess from an earlier run
         self.ticks = 0
         self.age = 0
         self._solved = False
@@ -164,6 +168,10 @@ class ClosedLoopMPC:
             ev.shift_stage_data(self._arr(d_new, ev.nsd), stream=stream)
         if pf:
             self.p, self._p2 = self._p2, self.p
+        if self.shift and sol.direct_active is not None:      # the held set moves with the plan: frame k + 1's entries to frame k, the last frame repeats
+            self._act2[:, :-1].copy_(sol.act[:, 1:]); self._act2[:, -1].copy_(sol.act[:, -1])
+            sol.act, self._act2 = self._act2, sol.act
+            sol._dq["act"] = sol.act
         if self.shift:
             sol.x, self._x2 = self._x2, sol.x
             if moved:

@@ -61,6 +61,11 @@ the exact step and multipliers, status 1 and 0 ADMM iterations, and is left out 
 has it); the others go through the QP solver as ever.  `direct_history` holds the verdicts (1 accepted, 0 rejected, -1 not eligible, -2 a pivot failed),
 one array per iteration; an instance that kkt_tol has frozen is not looked at, reports 0 and takes nothing.  Stage OCPs without a link cost only; refused with the reason next to constant_matrices, keep_scaling, carry_rho, soft_rows
 and presolve_fixed_rows.  The direct solve needs positive pivots on the equality set, not P >= 0: it can accept an instance the ADMM would call non-convex.
+With {"active_set": True, "rounds": 4, "dual_tol": 0.0} in that dict the direct solve also runs up to `rounds` (1 .. 8) primal-dual active-set rounds over the
+input box rows (models.StageOCP.direct_qp_active, mpcqp_stage_riccati_solve_active): an input that violates its bound is held there, a held
+one whose multiplier has the wrong sign is released, and an instance is accepted when a round's point meets the QP's KKT conditions.  State bounds, path
+rows and link rows are still only tested.  The set a call ends with is the next call's guess (`act` on the device loop); `direct_rounds_history` sits
+beside `direct_history`.  Without the key nothing changes.
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -163,9 +168,9 @@ def _direct_qp_option(options, model, evaluator=None):
     if value is not True and not isinstance(value, dict):
         raise ValueError("direct_qp: expected True or a dict with feas_tol and / or reg")
     d = {} if value is True else value
-    unknown = set(d) - {"feas_tol", "reg"}
+    unknown = set(d) - {"feas_tol", "reg", "active_set", "rounds", "dual_tol"}
     if unknown:
-        raise ValueError("direct_qp: unknown keys %s (feas_tol and reg are the options)" % sorted(unknown))
+        raise ValueError("direct_qp: unknown keys %s (feas_tol, reg, active_set, rounds and dual_tol are the options)" % sorted(unknown))
     feas_tol, reg = float(d.get("feas_tol", 0.0)), float(d.get("reg", 0.0))
     if not (feas_tol >= 0.0) or not (reg >= 0.0):
         raise ValueError("direct_qp: feas_tol and reg must not be negative")
@@ -177,6 +182,26 @@ def _direct_qp_option(options, model, evaluator=None):
         if options.get(key) not in (None, False):
             raise ValueError(why)
     return feas_tol, reg
+
+
+def _direct_active_option(options):
+    """the active-set keys of options["direct_qp"]: None without "active_set": True, else (rounds, dual_tol) -- rounds 1 .. 8, default
+    4; dual_tol >= 0, default 0.  Called behind _direct_qp_option, whose refusals apply unchanged."""
+    value = options.get("direct_qp")
+    if not isinstance(value, dict):
+        return None
+    if value.get("active_set") not in (None, False, True):
+        raise ValueError("direct_qp: active_set: expected True or False")
+    if not value.get("active_set"):
+        if "rounds" in value or "dual_tol" in value:
+            raise ValueError('direct_qp: rounds and dual_tol belong to "active_set": True')
+        return None
+    rounds, dual_tol = value.get("rounds", 4), float(value.get("dual_tol", 0.0))
+    if isinstance(rounds, bool) or int(rounds) != rounds or not 1 <= rounds <= _lib.ACTIVE_MAX_ROUNDS:
+        raise ValueError("direct_qp: rounds: expected 1 .. %d" % _lib.ACTIVE_MAX_ROUNDS)
+    if not (dual_tol >= 0.0):
+        raise ValueError("direct_qp: dual_tol must not be negative")
+    return int(rounds), dual_tol
 
 
 def _line_search_options(value):
@@ -307,6 +332,10 @@ class SQPOptimizationSolver:
         # direct_history holds the verdicts, one int32 array per iteration
         self.direct_qp = _direct_qp_option(options, nlp)
         self.direct_history = []
+        # "active_set": True: models.StageOCP.direct_qp_active in its place; the set it ends with is the next iteration's guess
+        self.direct_active = _direct_active_option(options) if self.direct_qp is not None else None
+        self.direct_rounds_history = []
+        self._act = None
         self.line_search = _line_search_options(options.get("line_search"))
         if self.line_search is not None and not hasattr(nlp, "line_search"):
             raise ValueError("line_search needs a stage OCP (models.StageOCP) or a general NLP (general_nlp.GeneralNLP): this model states no merit line search")
@@ -409,7 +438,14 @@ class SQPOptimizationSolver:
                     if self.carry_rho and hasattr(self.qpSolver_, "setRhoStart"):
                         self.qpSolver_.setRhoStart(info["rho"])
             taken = None
-            if self.direct_qp is not None:
+            if self.direct_active is not None:
+                dq = self.model.direct_qp_active(localSystem.P, localSystem.q, localSystem.A, localSystem.l, localSystem.u, self.direct_qp[0], self.direct_qp[1],
+                                                 rounds=self.direct_active[0], dual_tol=self.direct_active[1], act=self._act, frozen=frozen.astype(np.int32))
+                self._act = dq[4]
+                self.direct_rounds_history.append(dq[5].copy())
+                taken = dq[3] > 0
+                self.direct_history.append(dq[3].copy())
+            elif self.direct_qp is not None:
                 dq = self.model.direct_qp(localSystem.P, localSystem.q, localSystem.A, localSystem.l, localSystem.u, self.direct_qp[0], self.direct_qp[1],
                                           frozen=frozen.astype(np.int32))
                 taken = dq[3] > 0
@@ -574,6 +610,11 @@ class DeviceSQPOptimizationSolver:
         # through the ADMM as ever.  Nothing comes back to the host; direct_history holds one cloned verdict tensor per iteration.
         self.direct_qp = _direct_qp_option(options, nlp, evaluator)
         self.direct_history = []
+        # "active_set": True: mpcqp_stage_riccati_solve_active in its place.  `act` [batch, N, nu] is the set the last call ended with and
+        # the next call's guess (read and written in place; mpc.ClosedLoopMPC shifts it by a frame between ticks); direct_rounds_history sits beside
+        # direct_history.  Without the key the entry above is called and nothing else changes.
+        self.direct_active = _direct_active_option(options) if self.direct_qp is not None else None
+        self.direct_rounds_history = []
         # extension (opt-in): a step length per instance by an l1-merit backtracking search starting at options["alpha"] -- one kernel
         # (mpcqp_stage_linesearch; mpcqp_nlp_linesearch with a general evaluator that has it) in place of the step + merit pair; see the module
         # docstring.  It always honours the QP status.
@@ -649,6 +690,10 @@ class DeviceSQPOptimizationSolver:
             # the staging of the direct solve (z is not wanted) and the persistent skip mask the QP handle borrows
             self._dq = {"w": mk(self.ev.n), "y": mk(self.ev.m), "z": None, "direct": torch.zeros(self.batch, dtype=torch.int32, device=self.dev)}
             self._dq_skip = torch.zeros(self.batch, dtype=torch.int32, device=self.dev)
+            if self.direct_active is not None:
+                self.act = torch.zeros((self.batch, self.ev.horizon, self.ev.nu), dtype=torch.int32, device=self.dev)
+                self._dq["act"] = self.act
+                self._dq["rounds_used"] = torch.full((self.batch,), -1, dtype=torch.int32, device=self.dev)
 
     def _create_qp(self, presolve_bounds):
         import torch
@@ -750,8 +795,14 @@ class DeviceSQPOptimizationSolver:
                 self.convexified.append(self._touched.clone())
             direct = self.direct_qp is not None
             if direct:       # P is final: solve directly, test, and leave the accepted instances out of the QP launch
-                ev.riccati_solve(self.ls, self.direct_qp[0], self.direct_qp[1], frozen=self._kkt_conv if kkt and i >= 1 else None, out=self._dq,
-                                 stream=stream)
+                if self.direct_active is not None:
+                    self._dq["rounds_used"].fill_(-1)        # (an ineligible, failed or frozen instance writes none)
+                    ev.riccati_solve_active(self.ls, self.direct_qp[0], self.direct_qp[1], rounds=self.direct_active[0], dual_tol=self.direct_active[1],
+                                            act_in=self.act, frozen=self._kkt_conv if kkt and i >= 1 else None, out=self._dq, stream=stream)
+                    self.direct_rounds_history.append(self._dq["rounds_used"].clone())
+                else:
+                    ev.riccati_solve(self.ls, self.direct_qp[0], self.direct_qp[1], frozen=self._kkt_conv if kkt and i >= 1 else None, out=self._dq,
+                                     stream=stream)
                 if kkt and i >= 1:       # the kernel leaves a frozen instance's slot alone: it reports 0, as in the host loop, and takes nothing
                     self._dq["direct"].copy_(torch.where(self._kkt_conv != 0, torch.zeros_like(self._dq["direct"]), self._dq["direct"]))
                 taken = self._dq["direct"] > 0

@@ -115,6 +115,7 @@ def _bind(L):
     L.mpcqp_stage_kkt.argtypes = [vp, C.c_int, vp, vp]
     L.mpcqp_stage_riccati.argtypes = [vp, C.c_int, C.POINTER(RiccatiArgs), vp]
     L.mpcqp_stage_riccati_solve.argtypes = [vp, C.c_int, C.POINTER(RiccatiSolveArgs), vp]
+    L.mpcqp_stage_riccati_solve_active.argtypes = [vp, C.c_int, C.POINTER(_lib.RiccatiSolveActiveArgs), vp]
     L.mpcqp_stage_feedback.argtypes = [vp, C.c_int, C.POINTER(FeedbackArgs), vp]
     L._stage_bound = True
     return L
@@ -563,6 +564,50 @@ class StageEvaluator:
         if frozen is not None:
             a.frozen = _check_int32(frozen, B, "frozen")
         _lib.check(_lib.lib().mpcqp_stage_riccati_solve(self._h, B, C.byref(a), stream))
+        return out
+
+    def riccati_solve_active(self, ls, feas_tol=0.0, reg=0.0, rounds=4, dual_tol=0.0, act_in=None, frozen=None, out=None, stream=None):
+        """riccati_solve with active-set rounds over the input box rows, one kernel (mpcqp_stage_riccati_solve_active;
+        models.StageOCP.direct_qp_active is its host statement): round 0 is riccati_solve, then up to `rounds` (1 .. 8) rounds hold the inputs
+        that violate their bounds there and release the held ones whose multiplier has the wrong sign (beyond dual_tol).  act_in (int32
+        [B, N, nu], optional): the guess, -1 / 0 / +1.  Returns riccati_solve's dict plus act (int32 [B, N, nu], the last set formed: the next
+        guess) and rounds_used (int32 [B]); `out` may hold them (act may be the tensor given as act_in).  An ineligible, failed or frozen
+        instance has neither written.  The first call of a handle (and the first at a larger batch) may not run under stream capture."""
+        import torch
+        P = ls["P"]
+        if not isinstance(P, torch.Tensor) or P.dim() != 2:
+            raise ValueError("P: expected a contiguous float64 CUDA tensor of shape (B, %d)" % self.nnzP)
+        if not (feas_tol >= 0.0) or not (reg >= 0.0) or not (dual_tol >= 0.0):
+            raise ValueError("feas_tol, reg and dual_tol must not be negative")
+        if int(rounds) != rounds or not 1 <= rounds <= _lib.ACTIVE_MAX_ROUNDS:
+            raise ValueError("rounds: expected 1 .. %d" % _lib.ACTIVE_MAX_ROUNDS)
+        B, N = P.shape[0], self.horizon
+
+        def ints(t, name):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (B, N, self.nu)):
+                raise ValueError("%s: expected a contiguous int32 CUDA tensor of shape (%d, %d, %d)" % (name, B, N, self.nu))
+            return t.data_ptr()
+        a = _lib.RiccatiSolveActiveArgs()
+        a.P, a.q, a.A = _check(P, (B, self.nnzP), "P"), _check(ls["q"], (B, self.n), "q"), _check(ls["A"], (B, self.nnzA), "A")
+        a.l, a.u = _check(ls["l"], (B, self.m), "l"), _check(ls["u"], (B, self.m), "u")
+        a.feas_tol, a.reg, a.rounds, a.dual_tol = float(feas_tol), float(reg), int(rounds), float(dual_tol)
+        if out is None:
+            out = {"w": torch.zeros((B, self.n), dtype=torch.float64, device=P.device), "y": torch.zeros((B, self.m), dtype=torch.float64, device=P.device),
+                   "z": torch.zeros((B, self.m), dtype=torch.float64, device=P.device), "direct": torch.zeros((B,), dtype=torch.int32, device=P.device)}
+        if out.get("act") is None:
+            out["act"] = torch.zeros((B, N, self.nu), dtype=torch.int32, device=P.device)
+        if out.get("rounds_used") is None:
+            out["rounds_used"] = torch.full((B,), -1, dtype=torch.int32, device=P.device)
+        a.w, a.y = _check(out["w"], (B, self.n), "w"), _check(out["y"], (B, self.m), "y")
+        if out.get("z") is not None:
+            a.z = _check(out["z"], (B, self.m), "z")
+        a.direct = _check_int32(out["direct"], B, "direct")
+        a.act_out, a.rounds_used = ints(out["act"], "act"), _check_int32(out["rounds_used"], B, "rounds_used")
+        if act_in is not None:
+            a.act_in = ints(act_in, "act_in")
+        if frozen is not None:
+            a.frozen = _check_int32(frozen, B, "frozen")
+        _lib.check(_lib.lib().mpcqp_stage_riccati_solve_active(self._h, B, C.byref(a), stream))
         return out
 
     @staticmethod
