@@ -927,6 +927,79 @@ typedef struct mpcqp_stage_riccati_solve_active_args {
   int *rounds_used;             /* [batch], optional                                           */
 } mpcqp_stage_riccati_solve_active_args;
 int mpcqp_stage_riccati_solve_active(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_solve_active_args *a, void *stream);
+/* The interior-point direct solve (opt-in; models.StageOCP.direct_qp_ipm is the host statement): mpcqp_stage_riccati_solve as
+ * iteration 0, then up to `iters` iterations of a primal-dual interior-point method over the box rows of the free variables -- STATES and inputs,
+ * either side, any frame -- all in one kernel.  A bound on a state cannot be pinned; it can be barriered: a log-barrier on a box row adds a
+ * positive term to the diagonal of H_k and a term to q_k and changes nothing else, so an iteration is the backward and the forward pass of the
+ * entry above on modified data.  Notation, eligibility (-1), reg, frozen, z, the pivot test and the capture rules are those of
+ * mpcqp_stage_riccati_solve.
+ *   barriered rows   every identity row of a free variable: states and inputs of the frames k >= 1, the inputs of frame 0 that are not pinned.
+ *              Each finite side has a slack t > 0 and a multiplier lambda > 0 of its own; an infinite side has neither.  Path rows and link rows
+ *              are NOT barriered: they are tested at a candidate, and a violation there rejects the instance.
+ *   inside     w is inside when every barriered row has l_j - feas_tol <= w_j <= u_j + feas_tol (a NaN fails): the test of the entry above.
+ *   iteration 0  the entry above, operation for operation: w0.  A failed pivot: direct[b] = -2.  w0 inside: w0 is a candidate with no
+ *              multipliers; path and link rows within feas_tol: direct[b] = 1 with that entry's bits in w, y, z, iters_used[b] = 0; else
+ *              direct[b] = 0, iters_used[b] = 0.  w0 satisfies the dynamics and the pins exactly, and every later iterate is an affine
+ *              combination of such points: the dynamics rows never carry a residual, z = l there as before.
+ *   start      w0 not inside: per finite side t = max(w0 - l, MPCQP_IPM_T0) resp. max(u - w0, MPCQP_IPM_T0) (the slack where it is larger,
+ *              else T0), lambda = MPCQP_IPM_MU0 / t.
+ *   mu         the mean of lambda t over all finite sides: per column the frames in ascending order (lower side, then upper side), then the
+ *              columns by the butterfly of the lane group (v + v[lane ^ o], o = W / 2 .. 1; W = 16 for f <= 16, else 32), divided by the count.
+ *   sigma      1 when the last iterate was a candidate whose stationarity was too large (re-centre: mu is not driven further); else
+ *              MPCQP_IPM_SIGMA when the last alpha >= MPCQP_IPM_ALPHA_SHORT (also in iteration 1), else MPCQP_IPM_SIGMA_SHORT.
+ *   target     s = max(sigma mu, MPCQP_IPM_TARGET * comp_tol): the loop never drives mu below what the stop test asks for (rounding, below).
+ *   iteration  with that s and r = lambda / t per side: a lower side of column c adds r to H_k[c][c] and -((s / t + lambda) + r l) to
+ *              q_k[c]; an upper side adds r and +((s / t + lambda) - r u); both sides of a column are summed before they are added.  The
+ *              backward and the forward pass of the entry above on this data (reg and the pins of frame 0 as there) give w+.  dw = w+ - w;
+ *              lower side dt = dw + ((w - l) - t), upper side dt = ((u - w) - t) - dw; dlambda = (s / t - lambda) - r dt.
+ *              alpha = min(1, MPCQP_IPM_FRAC * min over all t and lambda with a negative direction of -v / dv); w, t, lambda += alpha times
+ *              their directions.  A failed pivot, or an alpha that is not in (0, 1] (a NaN), rejects: direct[b] = 0 (with positive pivots in
+ *              iteration 0 this can only be rounding).
+ *   candidate  the new w is inside, max lambda t <= comp_tol and mu <= comp_tol (a NaN fails).  Then the adjoint pass of the entry above runs
+ *              at w with y_j = lambda_U - lambda_L (the sign convention of mpcqp_get) on the barriered rows: val = [A_k B_k]' lam_k -
+ *              (H_k w_k + q_k) - y; the state columns give the dynamics multipliers lam_{k-1}, frame 0's pinned rows close their own columns,
+ *              and stat = max |val - reg w| over the barriered INPUT columns is what the iterate leaves of the stationarity condition of the QP the
+ *              passes solve, reg on the free inputs' diagonal included (the gain closes
+ *              these columns exactly only after a full step).  Path and link rows are tested at w: a violation rejects, direct[b] = 0.
+ *              stat <= stat_tol: direct[b] = 1, w, y, z written.  Else the loop goes on (sigma = 1).
+ *   the end    after `iters` iterations an open instance is rejected: direct[b] = 0, iters_used[b] = iters.
+ *   iters_used, res   the last iteration the instance ran; res[3 b ..] = the largest violation of a barriered row, max lambda t (0 in iteration
+ *              0) and stat (NaN when the exit point was not a candidate), all at the exit point -- for accepted and rejected instances alike.  An
+ *              ineligible (-1), failed (-2) or frozen instance writes neither; a rejected instance writes nothing else.
+ * What accepted means: unlike the two entries above, an accepted point of an iteration >= 1 is an APPROXIMATE KKT point of the QP: primal
+ * feasible within feas_tol (exactly on the dynamics and the pins), multipliers of the right sign, lambda t <= comp_tol on every side, stationary
+ * within stat_tol.  Iteration 0's positive pivots make the objective strictly convex on the set the pins and the dynamics leave, so the QP has one
+ * KKT point: the accepted point is close to the minimiser and cannot be near a different stationary point.  How close depends on comp_tol, on
+ * the smallest active multiplier and on the conditioning (DESIGN 6.32 has measured distances).  Rounding: lambda carries an error of about
+ * eps * (lambda / t) * |w|, and t = mu / lambda on an active row: stat cannot be driven below about 1e-16 lambda^2 / mu, which is why the target
+ * stops at MPCQP_IPM_TARGET * comp_tol and why a comp_tol below 1e-8 is out of reach in double precision (DESIGN 6.32 has the measurements).
+ * stage_direct_ipm_kernel uses the size classes, lane groups and tiles of stage_direct_kernel; its workspace (the handle's, grown with the batch:
+ * batch N (nu (nx + 1) + 7 f) doubles) holds the gains, w, dw, val, t_L, t_U, lambda_L, lambda_U.  The loop over the iterations is uniform over
+ * the block; one writer per element, no atomics: bitwise repeatable, independent of the batch size and of the instance's position.  No state is
+ * kept between calls.  MPCQP_ERR_ARG and MPCQP_ERR_LIMIT as above, MPCQP_ERR_ARG also for iters outside 1 .. MPCQP_IPM_MAX_ITERS and a negative
+ * (or NaN) comp_tol or stat_tol. */
+#define MPCQP_IPM_MAX_ITERS 50
+#define MPCQP_IPM_T0 0.1
+#define MPCQP_IPM_MU0 1.0
+#define MPCQP_IPM_FRAC 0.995
+#define MPCQP_IPM_SIGMA 0.1
+#define MPCQP_IPM_SIGMA_SHORT 0.5
+#define MPCQP_IPM_ALPHA_SHORT 0.5
+#define MPCQP_IPM_TARGET 0.5
+typedef struct mpcqp_stage_riccati_solve_ipm_args {
+  const double *P, *q, *A, *l, *u;   /* [batch * nnzP | n | nnzA | m | m], the local system          */
+  double feas_tol, reg;
+  const int *frozen;            /* [batch], optional: nonzero = neither read nor written       */
+  double *w;                    /* [batch * n], required                                       */
+  double *y;                    /* [batch * m], required                                       */
+  double *z;                    /* [batch * m], optional                                       */
+  int *direct;                  /* [batch], required: 1 accepted, 0 rejected, -1 ineligible, -2 a pivot failed in iteration 0 */
+  int iters;                    /* 1 .. MPCQP_IPM_MAX_ITERS: the iterations after iteration 0  */
+  double comp_tol, stat_tol;    /* >= 0                                                        */
+  int *iters_used;              /* [batch], optional                                           */
+  double *res;                  /* [batch * 3], optional                                       */
+} mpcqp_stage_riccati_solve_ipm_args;
+int mpcqp_stage_riccati_solve_ipm(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_solve_ipm_args *a, void *stream);
 /* The feedback law at one frame, one thread per (instance, input): with row(v, stride) = v + b * stride,
  *   acc = acc_j K[b][k][i][j] * (s[j] - s_nom[j])     (each product and each sum rounded, no fused multiply-add: bitwise the host statement)
  *   u   = clip(u_nom[i] + acc), clip the two selects of mpcqp_stage_rollout against lo[i] / hi[i] (the identity without the pair)

@@ -20,7 +20,7 @@ EXPORTS = ["mpcqp_default_settings", "mpcqp_create", "mpcqp_create_tuned", "mpcq
            "mpcqp_get", "mpcqp_set_polish", "mpcqp_get_polish", "mpcqp_last_polish_ms", "mpcqp_sync", "mpcqp_destroy", "mpcqp_strerror", "mpcqp_last_kernel_ms", "mpcqp_last_phase_ms",
            "mpcqp_plan_info", "mpcqp_oc_info", "mpcqp_debug_scaling", "mpcqp_debug_blockops",
            "mpcqp_stage_default", "mpcqp_stage_create", "mpcqp_stage_create_user", "mpcqp_stage_create_tracking", "mpcqp_stage_destroy", "mpcqp_stage_set_weights", "mpcqp_stage_set_path_bounds", "mpcqp_stage_param_count", "mpcqp_stage_set_instance_params", "mpcqp_stage_data_count", "mpcqp_stage_set_stage_data", "mpcqp_stage_shift_data", "mpcqp_stage_has_transition_data", "mpcqp_stage_dims", "mpcqp_stage_has_cost", "mpcqp_stage_has_link_cost", "mpcqp_stage_has_residual_cost", "mpcqp_stage_pattern",
-           "mpcqp_stage_eval", "mpcqp_stage_merit", "mpcqp_stage_step", "mpcqp_stage_advance", "mpcqp_stage_rollout", "mpcqp_stage_linesearch", "mpcqp_stage_has_convexify", "mpcqp_stage_convexify", "mpcqp_stage_has_exact_hessian", "mpcqp_stage_lagrangian", "mpcqp_stage_kkt", "mpcqp_stage_riccati", "mpcqp_stage_riccati_solve", "mpcqp_stage_riccati_solve_active", "mpcqp_stage_feedback",
+           "mpcqp_stage_eval", "mpcqp_stage_merit", "mpcqp_stage_step", "mpcqp_stage_advance", "mpcqp_stage_rollout", "mpcqp_stage_linesearch", "mpcqp_stage_has_convexify", "mpcqp_stage_convexify", "mpcqp_stage_has_exact_hessian", "mpcqp_stage_lagrangian", "mpcqp_stage_kkt", "mpcqp_stage_riccati", "mpcqp_stage_riccati_solve", "mpcqp_stage_riccati_solve_active", "mpcqp_stage_riccati_solve_ipm", "mpcqp_stage_feedback",
            "mpcqp_nlp_create", "mpcqp_nlp_destroy", "mpcqp_nlp_dims", "mpcqp_nlp_pattern", "mpcqp_nlp_eval", "mpcqp_nlp_merit", "mpcqp_nlp_step", "mpcqp_nlp_has_linesearch", "mpcqp_nlp_linesearch",
            "mpcqp_nlp_has_exact_hessian", "mpcqp_nlp_lagrangian", "mpcqp_nlp_kkt",
            "mpcqp_stageqp_pattern", "mpcqp_stageqp_create", "mpcqp_stageqp_handle", "mpcqp_stageqp_update", "mpcqp_stageqp_destroy"]
@@ -52,6 +52,16 @@ class RiccatiSolveActiveArgs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("P", "q", "A", "l", "u")] + [("feas_tol", C.c_double), ("reg", C.c_double)] + \
                [(k, C.c_void_p) for k in ("frozen", "w", "y", "z", "direct")] + [("rounds", C.c_int), ("dual_tol", C.c_double)] + \
                [(k, C.c_void_p) for k in ("act_in", "act_out", "rounds_used")]
+
+
+IPM_MAX_ITERS = 50         # MPCQP_IPM_MAX_ITERS
+
+
+class RiccatiSolveIpmArgs(C.Structure):
+    """mpcqp_stage_riccati_solve_ipm_args (include/mpcqp.h)"""
+    _fields_ = [(k, C.c_void_p) for k in ("P", "q", "A", "l", "u")] + [("feas_tol", C.c_double), ("reg", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("frozen", "w", "y", "z", "direct")] + [("iters", C.c_int), ("comp_tol", C.c_double), ("stat_tol", C.c_double)] + \
+               [(k, C.c_void_p) for k in ("iters_used", "res")]
 
 
 class MpcqpError(RuntimeError):

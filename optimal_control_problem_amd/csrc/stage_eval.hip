@@ -19,6 +19,7 @@
 #include "stage_kernels.hpp"
 #include "stage_riccati.hpp"
 #include "stage_riccati_active.hpp"
+#include "stage_riccati_ipm.hpp"
 
 // The launchers a generated library exports (model == MPCQP_MODEL_USER), one per operation: the handle's constants, the batch, the operation's
 // argument block (convexify: then the handle's tables and scratch; lagrangian: then the curvature's slot table and the convexification's tables and
@@ -96,6 +97,9 @@ struct mpcqp_stage {
   // the workspace of mpcqp_stage_riccati_solve_active (stage_riccati_active.hpp: the one above plus val and the set words), grown the same way
   double *dactws = nullptr;
   int act_cap = 0;
+  // the workspace of mpcqp_stage_riccati_solve_ipm (stage_riccati_ipm.hpp: the gains, the iterate, its step, val, slacks and multipliers)
+  double *dipmws = nullptr;
+  int ipm_cap = 0;
 };
 
 // a launch may not be larger than a stored parameter set
@@ -422,6 +426,7 @@ void mpcqp_stage_destroy(mpcqp_stage *s) {
   if (s->ddir) (void)hipFree(s->ddir);
   if (s->ddws) (void)hipFree(s->ddws);
   if (s->dactws) (void)hipFree(s->dactws);
+  if (s->dipmws) (void)hipFree(s->dipmws);
   if (s->user_lib) dlclose(s->user_lib);
   delete s;
 }
@@ -875,6 +880,45 @@ int mpcqp_stage_riccati_solve_active(mpcqp_stage *s, int batch, const mpcqp_stag
   const hipError_t e = sd.f <= 8 ? stage_launch_direct_active<16, 8>(sd, batch, *a, tab, s->dactws, st)
                      : sd.f <= 16 ? stage_launch_direct_active<16, 16>(sd, batch, *a, tab, s->dactws, st)
                                   : stage_launch_direct_active<32, 24>(sd, batch, *a, tab, s->dactws, st);
+  MPCQP_HIPCHK(e);
+  return MPCQP_OK;
+}
+
+// the interior-point direct solve (stage_riccati_ipm.hpp): the tables of mpcqp_stage_riccati_solve, a workspace of its own
+int mpcqp_stage_riccati_solve_ipm(mpcqp_stage *s, int batch, const mpcqp_stage_riccati_solve_ipm_args *a, void *stream) {
+  if (!s) return mpcqp_set_error(MPCQP_ERR_ARG, "stage handle is null");
+  if (batch < 1) return mpcqp_set_error(MPCQP_ERR_ARG, "batch must be positive");
+  if (!a) return mpcqp_set_error(MPCQP_ERR_ARG, "the argument block is null");
+  if (!a->P || !a->q || !a->A || !a->l || !a->u) return mpcqp_set_error(MPCQP_ERR_ARG, "P, q, A, l and u are required");
+  if (!a->w || !a->y || !a->direct) return mpcqp_set_error(MPCQP_ERR_ARG, "w, y and direct are required");
+  if (!(a->feas_tol >= 0.0) || !(a->reg >= 0.0) || !(a->comp_tol >= 0.0) || !(a->stat_tol >= 0.0))
+    return mpcqp_set_error(MPCQP_ERR_ARG, "feas_tol, reg, comp_tol and stat_tol must not be negative");
+  if (a->iters < 1 || a->iters > MPCQP_IPM_MAX_ITERS) return mpcqp_set_error(MPCQP_ERR_ARG, "iters must be 1 .. 50");
+  if (s->link_cost)
+    return mpcqp_set_error(MPCQP_ERR_LIMIT, "this handle has a link cost: its P couples neighbouring frames, and a Riccati recursion over the frame blocks alone would drop those terms");
+  MPCQP_HIPCHK(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  const StageDev &sd = s->sd;
+  if (!s->dric || !s->ddir || batch > s->ipm_cap) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    MPCQP_HIPCHK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+      return mpcqp_set_error(MPCQP_ERR_STATE, "the first mpcqp_stage_riccati_solve_ipm of a handle (and the first at a larger batch) builds its slot tables and its workspace and may not run while the stream is capturing: call it once before the capture");
+    if (!s->dric) if (int rc = stage_build_riccati_tables(s)) return rc;
+    if (!s->ddir) if (int rc = stage_build_direct_tables(s)) return rc;
+    if (batch > s->ipm_cap) {
+      double *nb = nullptr;
+      MPCQP_HIPCHK(hipMalloc(&nb, (size_t)batch * stage_ipm_ws_doubles(sd) * sizeof(double)));
+      MPCQP_HIPCHK(hipDeviceSynchronize());       // a launch that uses the old workspace may still be queued
+      if (s->dipmws) (void)hipFree(s->dipmws);
+      s->dipmws = nb; s->ipm_cap = batch;
+    }
+  }
+  const StageDirTab tab{s->dric, s->dric + (size_t)sd.N * sd.f * sd.f, s->ddir, s->ddir + s->dir_off[0], s->ddir + s->dir_off[1],
+                        s->ddir + s->dir_off[2], s->ddir + s->dir_off[3], s->ddir + s->dir_off[4]};
+  const hipError_t e = sd.f <= 8 ? stage_launch_direct_ipm<16, 8>(sd, batch, *a, tab, s->dipmws, st)
+                     : sd.f <= 16 ? stage_launch_direct_ipm<16, 16>(sd, batch, *a, tab, s->dipmws, st)
+                                  : stage_launch_direct_ipm<32, 24>(sd, batch, *a, tab, s->dipmws, st);
   MPCQP_HIPCHK(e);
   return MPCQP_OK;
 }

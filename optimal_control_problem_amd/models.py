@@ -1422,13 +1422,15 @@ class StageOCP:
         return w, y, z, direct
 
     # -- the direct solve with held input bounds (include/mpcqp.h, mpcqp_stage_riccati_solve_active; csrc/stage_riccati_active.hpp) -------------
-    def _direct_active_round(self, P, q, A, l, u, reg, hold, cval):
+    def _direct_active_round(self, P, q, A, l, u, reg, hold, cval, hadd=None, qadd=None):
         """one round of the rule: the three passes of direct_qp with the inputs of hold [B, N, nu] (the pins of frame 0 included) fixed at
-        cval [B, N, nu].  Returns (d [B, N, f], y [B, m], z [B, m], bad [B]).  With no input held beyond the pins the operations are direct_qp's."""
+        cval [B, N, nu].  Returns (d [B, N, f], y [B, m], z [B, m], bad [B]).  With no input held beyond the pins the operations are direct_qp's.
+        hadd, qadd [B, N, f] (direct_qp_ipm's barrier terms): added to the diagonal of H_k and to q_k for the backward pass alone; the adjoint pass
+        keeps the QP's own H_k and q_k."""
         B, N, nx, nu, f, npp, n, m, nh, nk = P.shape[0], self.N, self.nx, self.nu, self.f, self.np, self.n, self.m, self.nh, self.nk
         pslot, aslot = self._riccati_slots()
         hslot, k0slot, k1slot, pcols = self._direct_slots()
-        Pz = np.concatenate([P, np.zeros((B, 1))], axis=1)
+        Pz = np.concatenate([P, np.zeros((B, 1), P.dtype)], axis=1)
         lf = l[:, npp:n].reshape(B, N, f)
         ld = l[:, n:n + self.ngd].reshape(B, N - 1, nx)
         qf = q[:, npp:n].reshape(B, N, f)
@@ -1443,26 +1445,30 @@ class StageOCP:
 
         H = [Pz[:, pslot[k]] for k in range(N)]
         ABs = [-A[:, aslot[k]] for k in range(N - 1)]
-        Kk = np.zeros((B, N, nu, nx)); kap = np.zeros((B, N, nu))
-        V = np.zeros((B, nx, nx)); v = np.zeros((B, nx))
+        Kk = np.zeros((B, N, nu, nx), P.dtype); kap = np.zeros((B, N, nu), P.dtype)
+        V = np.zeros((B, nx, nx), P.dtype); v = np.zeros((B, nx), P.dtype)
         bad = np.zeros(B, bool)
         for k in range(N - 1, -1, -1):
             Q = H[k]
             g = qf[:, k].copy()
+            if hadd is not None:
+                Q = Q.copy()
+                Q[:, np.arange(f), np.arange(f)] = Q[:, np.arange(f), np.arange(f)] + hadd[:, k]
+                g = g + qadd[:, k]
             if k < N - 1:
                 AB = ABs[k]
-                T = np.zeros((B, nx, f))
+                T = np.zeros((B, nx, f), P.dtype)
                 for j in range(nx):
                     T = T + V[:, :, j, None] * AB[:, j, None, :]
-                acc = np.zeros((B, f, f))
+                acc = np.zeros((B, f, f), P.dtype)
                 for j in range(nx):
                     acc = acc + AB[:, j, :, None] * T[:, j, None, :]
                 Q = mirrored(Q + acc, iu, ju)
-                h = np.zeros((B, nx))
+                h = np.zeros((B, nx), P.dtype)
                 for i in range(nx):
                     h = h + V[:, :, i] * ld[:, k, i, None]
                 h = h + v
-                acc = np.zeros((B, f))
+                acc = np.zeros((B, f), P.dtype)
                 for j in range(nx):
                     acc = acc + AB[:, j, :] * h[:, j, None]
                 g = g + acc
@@ -1470,7 +1476,7 @@ class StageOCP:
             M = Q[:, nx:, :].copy()
             cm = hold[:, k]; cv = cval[:, k]
             anyc = cm.any(axis=1)[:, None]
-            acc = np.zeros((B, f))
+            acc = np.zeros((B, f), P.dtype)
             for p_ in range(nu):         # Q[p][c] c_p over the held inputs p, every column c
                 acc = acc + np.where(cm[:, p_, None], M[:, p_, :] * cv[:, p_, None], 0.0)
             gu = np.where(cm, -cv, np.where(anyc, g[:, nx:] + acc[:, nx:], g[:, nx:]))
@@ -1483,15 +1489,15 @@ class StageOCP:
                 vv = np.abs(M[:, i, nx + i])
                 dmax = np.where(vv > dmax, vv, dmax)
             thr = self.RICCATI_PIVOT * dmax
-            ud_ = np.zeros((B, nu)); y0 = np.zeros((B, nu))
+            ud_ = np.zeros((B, nu), P.dtype); y0 = np.zeros((B, nu), P.dtype)
             for jj in range(nu):
-                acc = np.zeros(B)
+                acc = np.zeros(B, P.dtype)
                 for t in range(jj):
                     acc = acc + M[:, t, nx + jj] * M[:, t, nx + jj]
                 d = M[:, jj, nx + jj] - acc
                 bad |= ~(d > thr)
                 ud_[:, jj] = np.sqrt(d)
-                s = np.zeros((B, f)); s0 = np.zeros(B)
+                s = np.zeros((B, f), P.dtype); s0 = np.zeros(B, P.dtype)
                 for t in range(jj):
                     s = s + M[:, t, nx + jj, None] * M[:, t, :]
                     s0 = s0 + M[:, t, nx + jj] * y0[:, t]
@@ -1500,9 +1506,9 @@ class StageOCP:
                 M[:, jj, cols] = new[:, cols]
                 y0[:, jj] = (gu[:, jj] - s0) / ud_[:, jj]
             Y = M[:, :, :nx]
-            Z = np.zeros((B, nu, nx)); z0 = np.zeros((B, nu))
+            Z = np.zeros((B, nu, nx), P.dtype); z0 = np.zeros((B, nu), P.dtype)
             for i in range(nu - 1, -1, -1):
-                s = np.zeros((B, nx)); s0 = np.zeros(B)
+                s = np.zeros((B, nx), P.dtype); s0 = np.zeros(B, P.dtype)
                 for t in range(i + 1, nu):
                     s = s + M[:, i, nx + t, None] * Z[:, t, :]
                     s0 = s0 + M[:, i, nx + t] * z0[:, t]
@@ -1510,34 +1516,34 @@ class StageOCP:
                 z0[:, i] = (y0[:, i] - s0) / ud_[:, i]
             Kk[:, k] = -Z; kap[:, k] = -z0
             if k > 0:
-                acc = np.zeros((B, nx, nx)); acc0 = np.zeros((B, nx))
+                acc = np.zeros((B, nx, nx), P.dtype); acc0 = np.zeros((B, nx), P.dtype)
                 for i in range(nu):
                     acc = acc + Y[:, i, :, None] * Y[:, i, None, :]
                     acc0 = acc0 + Y[:, i, :] * y0[:, i, None]
                 V = mirrored(Qss - acc, ix, jx)
                 v = gs - acc0
-        d = np.zeros((B, N, f))
+        d = np.zeros((B, N, f), P.dtype)
         ds = lf[:, 0, :nx].copy()
         for k in range(N):
-            acc = np.zeros((B, nu))
+            acc = np.zeros((B, nu), P.dtype)
             for j in range(nx):
                 acc = acc + Kk[:, k, :, j] * ds[:, j, None]
             du = np.where(hold[:, k], cval[:, k], acc + kap[:, k])
             d[:, k, :nx] = ds; d[:, k, nx:] = du
             if k < N - 1:
-                acc = np.zeros((B, nx))
+                acc = np.zeros((B, nx), P.dtype)
                 for c in range(f):
                     acc = acc + ABs[k][:, :, c] * d[:, k, c, None]
                 ds = acc + ld[:, k]
-        w = np.zeros((B, n)); y = np.zeros((B, m)); z = np.zeros((B, m))
+        w = np.zeros((B, n), P.dtype); y = np.zeros((B, m), P.dtype); z = np.zeros((B, m), P.dtype)
         w[:, npp:] = d.reshape(B, -1)
-        lam = np.zeros((B, nx))
+        lam = np.zeros((B, nx), P.dtype)
         for k in range(N - 1, -1, -1):
-            e = np.zeros((B, f))
+            e = np.zeros((B, f), P.dtype)
             for r in range(f):
                 e = e + H[k][:, r, :] * d[:, k, r, None]
             e = e + qf[:, k]
-            t = np.zeros((B, f))
+            t = np.zeros((B, f), P.dtype)
             if k < N - 1:
                 for r in range(nx):
                     t = t + ABs[k][:, r, :] * lam[:, r, None]
@@ -1551,7 +1557,7 @@ class StageOCP:
             y[:, o + nx:o + f] = np.where(hold[:, k], val[:, nx:], 0.0)
         for j in range(npp):
             slots, rows = pcols[j]
-            acc = np.zeros(B)
+            acc = np.zeros(B, P.dtype)
             for e_, r_ in zip(slots, rows):
                 acc = acc + P[:, e_] * w[:, npp + r_]
             y[:, j] = -(acc + q[:, j])
@@ -1566,10 +1572,10 @@ class StageOCP:
         rowh = n + self.ngd; rowk = rowh + N * nh
         for k in range(N):
             for r in range(nh):
-                z[:, rowh + k * nh + r] = row(hslot[k, r], d[:, k], np.zeros(B))
+                z[:, rowh + k * nh + r] = row(hslot[k, r], d[:, k], np.zeros(B, P.dtype))
             if k < N - 1:
                 for r in range(nk):
-                    z[:, rowk + k * nk + r] = row(k1slot[k, r], d[:, k + 1], row(k0slot[k, r], d[:, k], np.zeros(B)))
+                    z[:, rowk + k * nk + r] = row(k1slot[k, r], d[:, k + 1], row(k0slot[k, r], d[:, k], np.zeros(B, P.dtype)))
         return d, w, y, z, bad
 
     def direct_qp_active(self, P, q, A, l, u, feas_tol=0.0, reg=0.0, rounds=4, dual_tol=0.0, act=None, frozen=None):
@@ -1657,6 +1663,226 @@ class StageOCP:
         act_out = np.where(done[:, None, None] & ~pin, hi.astype(np.int32) - lo.astype(np.int32), guess).astype(np.int32)
         direct = np.where(alive, np.where(~el, -1, direct), 0).astype(np.int32)
         return w, y, z, direct, act_out, used
+
+    # -- the interior-point direct solve (include/mpcqp.h, mpcqp_stage_riccati_solve_ipm; csrc/stage_riccati_ipm.hpp) ----------------------------
+    IPM_MAX_ITERS = 50         # MPCQP_IPM_MAX_ITERS
+    IPM_T0 = 0.1               # MPCQP_IPM_T0
+    IPM_MU0 = 1.0              # MPCQP_IPM_MU0
+    IPM_FRAC = 0.995           # MPCQP_IPM_FRAC
+    IPM_SIGMA = 0.1            # MPCQP_IPM_SIGMA
+    IPM_SIGMA_SHORT = 0.5      # MPCQP_IPM_SIGMA_SHORT
+    IPM_ALPHA_SHORT = 0.5      # MPCQP_IPM_ALPHA_SHORT
+    IPM_TARGET = 0.5           # MPCQP_IPM_TARGET
+
+    def _direct_ipm_adjoint(self, P, q, A, w, yid):
+        """the adjoint pass at the point w [B, n] with yid [B, N, f] on the identity rows: val_k = [A_k B_k]' lam_k - (H_k d_k + q_k) - yid_k, the
+        state columns of a frame k >= 1 give lam_{k-1}.  Returns val [B, N, f] (frame 0 and the state columns: multipliers; the input columns of
+        the frames k >= 1 and the free inputs of frame 0: what is left of the stationarity condition)."""
+        B, N, nx, f, npp, n = P.shape[0], self.N, self.nx, self.f, self.np, self.n
+        pslot, aslot = self._riccati_slots()
+        Pz = np.concatenate([P, np.zeros((B, 1), P.dtype)], axis=1)
+        qf = q[:, npp:n].reshape(B, N, f)
+        d = w[:, npp:n].reshape(B, N, f)
+        out = np.zeros((B, N, f), P.dtype)
+        lam = np.zeros((B, nx), P.dtype)
+        for k in range(N - 1, -1, -1):
+            Hk = Pz[:, pslot[k]]
+            e = np.zeros((B, f), P.dtype)
+            for r in range(f):
+                e = e + Hk[:, r, :] * d[:, k, r, None]
+            e = e + qf[:, k]
+            t = np.zeros((B, f), P.dtype)
+            if k < N - 1:
+                ABk = -A[:, aslot[k]]
+                for r in range(nx):
+                    t = t + ABk[:, r, :] * lam[:, r, None]
+            val = (t - e) - yid[:, k]
+            out[:, k] = val
+            lam = val[:, :nx]
+        return out
+
+    def direct_qp_ipm(self, P, q, A, l, u, feas_tol=1e-9, reg=0.0, iters=30, comp_tol=1e-6, stat_tol=1e-5, frozen=None, trace=None, dtype=float):
+        """Host statement of mpcqp_stage_riccati_solve_ipm (include/mpcqp.h has the rule in full): direct_qp as iteration 0, then up to `iters`
+        iterations of a primal-dual interior-point method on the box rows of the free variables (states and inputs), every iteration one backward
+        and one forward pass of the direct solve on H_k + diag(lambda / t) and a shifted q_k.  Returns (w [B, n], y [B, m], z [B, m], direct [B]
+        int32, iters_used [B] int32, res [B, 3]): direct as direct_qp; an accepted point meets the QP's KKT conditions within (feas_tol, comp_tol,
+        stat_tol); res = (primal violation of the barriered rows, max lambda t, stationarity left on the free input columns; NaN where the exit
+        point was not a candidate).  Rows of w, y, z of an instance that is not accepted are NaN; iters_used and res of an ineligible, failed or
+        frozen instance are -1 and NaN (the device does not write them).  trace (a list, optional) receives one dict of the decision margins per
+        iteration (tests); dtype=np.longdouble carries the same iteration out in extended precision (the rounding sensitivity of the statement)."""
+        if self.link_cost:
+            raise ValueError("direct_qp_ipm: this model has a link cost: its P couples neighbouring frames, and a Riccati recursion over the frame "
+                             "blocks alone would drop those terms")
+        if not (feas_tol >= 0.0) or not (reg >= 0.0) or not (comp_tol >= 0.0) or not (stat_tol >= 0.0):
+            raise ValueError("feas_tol, reg, comp_tol and stat_tol must not be negative")
+        if isinstance(iters, bool) or int(iters) != iters or not 1 <= iters <= self.IPM_MAX_ITERS:
+            raise ValueError("iters: expected 1 .. %d" % self.IPM_MAX_ITERS)
+        P = np.asarray(P, dtype); A = np.asarray(A, dtype); q = np.asarray(q, dtype); l = np.asarray(l, dtype); u = np.asarray(u, dtype)
+        B, N, nx, nu, f, npp, n, m = P.shape[0], self.N, self.nx, self.nu, self.f, self.np, self.n, self.m
+        if P.shape != (B, len(self.Pi)) or A.shape != (B, len(self.Ai)) or q.shape != (B, n) or l.shape != (B, m) or u.shape != (B, m):
+            raise ValueError("P, q, A, l, u: expected shapes [B, %d], [B, %d], [B, %d], [B, %d], [B, %d] (dimension mismatch)"
+                             % (len(self.Pi), n, len(self.Ai), m, m))
+        alive = np.ones(B, bool) if frozen is None else np.asarray(frozen).reshape(B) == 0
+        lf = l[:, npp:n].reshape(B, N, f); uf = u[:, npp:n].reshape(B, N, f)
+        ld = l[:, n:n + self.ngd].reshape(B, N - 1, nx); ud = u[:, n:n + self.ngd].reshape(B, N - 1, nx)
+        W = 16 if f <= 16 else 32                              # the lane group of the size class: the order of the sums across the columns
+        lanes = np.arange(W)
+
+        def across(v, op):                                     # [B, f] -> [B]: the butterfly of the group (v + v[lane ^ o], o = W / 2 .. 1)
+            t = np.zeros((B, W), P.dtype) if op is np.add else np.full((B, W), -np.inf if op is np.fmax else np.inf, P.dtype)
+            t[:, :f] = v
+            o = W // 2
+            while o >= 1:
+                t = op(t, t[:, lanes ^ o]); o //= 2
+            return t[:, 0]
+
+        with np.errstate(all="ignore"):
+            el = ((l[:, :npp] == 0.0) & (u[:, :npp] == 0.0)).all(axis=1)
+            el &= (lf[:, 0, :nx] == uf[:, 0, :nx]).all(axis=1)
+            el &= (~np.isnan(lf[:, 0, nx:]) & ~np.isnan(uf[:, 0, nx:])).all(axis=1)
+            el &= (~np.isnan(lf[:, 1:]) & ~np.isnan(uf[:, 1:]) & ~(lf[:, 1:] == uf[:, 1:])).all(axis=(1, 2))
+            el &= (ld == ud).all(axis=(1, 2))
+            pin = np.zeros((B, N, nu), bool)
+            pin[:, 0] = lf[:, 0, nx:] == uf[:, 0, nx:]
+            cval = lf[:, :, nx:]
+            bar = np.ones((B, N, f), bool)                     # the barriered columns: every identity row of a free variable
+            bar[:, 0, :nx] = False; bar[:, 0, nx:] = ~pin[:, 0]
+            mL = bar & (lf > -np.inf); mU = bar & (uf < np.inf)
+            lz = np.where(mL, lf, 0.0); uz = np.where(mU, uf, 0.0)
+            cnt = (mL.sum(axis=(1, 2)) + mU.sum(axis=(1, 2))).astype(P.dtype)
+            rowh = n + self.ngd
+
+            def box_ok(d):
+                return ((lf - feas_tol <= d) & (d <= uf + feas_tol) | ~bar).all(axis=(1, 2))
+
+            def rows_ok(z):
+                return ((l[:, rowh:] - feas_tol <= z[:, rowh:]) & (z[:, rowh:] <= u[:, rowh:] + feas_tol)).all(axis=1)
+
+            def viol(d):                                       # per column the frames in ascending order, then across the columns
+                v = np.zeros((B, f), P.dtype)
+                for k in range(N):
+                    a = np.where(mL[:, k], lz[:, k] - d[:, k], 0.0); b_ = np.where(mU[:, k], d[:, k] - uz[:, k], 0.0)
+                    v = np.where(a > v, a, v); v = np.where(b_ > v, b_, v)
+                return across(v, np.fmax)
+
+            def mu_comp(tL, tU, lL, lU):
+                s = np.zeros((B, f), P.dtype); c = np.zeros((B, f), P.dtype)
+                for k in range(N):
+                    a = np.where(mL[:, k], lL[:, k] * tL[:, k], 0.0); b_ = np.where(mU[:, k], lU[:, k] * tU[:, k], 0.0)
+                    s = s + a; s = s + b_
+                    c = np.where(a > c, a, c); c = np.where(b_ > c, b_, c)
+                return across(s, np.add) / cnt, across(c, np.fmax)
+
+            w = np.full((B, n), np.nan, P.dtype); y = np.full((B, m), np.nan, P.dtype); z = np.full((B, m), np.nan, P.dtype)
+            direct = np.zeros(B, np.int32)
+            used = np.full(B, -1, np.int32)
+            res = np.full((B, 3), np.nan, P.dtype)
+            # ---- iteration 0: direct_qp
+            d, wr, yr, zr, bad = self._direct_active_round(P, q, A, l, u, reg, pin, cval)
+            open_ = alive & el
+            direct[open_ & bad] = -2
+            open_ = open_ & ~bad
+            bok, rok = box_ok(d), rows_ok(zr)
+            stat0 = self._direct_ipm_adjoint(P, q, A, wr, np.zeros((B, N, f), P.dtype))
+            stat0 = across(np.max(np.where(bar & (np.arange(f) >= nx), np.abs(stat0 - reg * d), 0.0), axis=1), np.fmax)
+            pv = viol(d)
+            res[open_, 0] = pv[open_]; res[open_, 1] = 0.0
+            used[open_] = 0
+            take = open_ & bok & rok
+            w[take] = wr[take]; y[take] = yr[take]; z[take] = zr[take]; direct[take] = 1; res[take, 2] = stat0[take]
+            res[open_ & bok & ~rok, 2] = stat0[open_ & bok & ~rok]
+            open_ = open_ & ~bok
+            # ---- the start
+            sl = d - lz; su = uz - d
+            tL = np.where(mL, np.where(sl > self.IPM_T0, sl, self.IPM_T0), 1.0); tU = np.where(mU, np.where(su > self.IPM_T0, su, self.IPM_T0), 1.0)
+            lL = np.where(mL, self.IPM_MU0 / tL, 0.0); lU = np.where(mU, self.IPM_MU0 / tU, 0.0)
+            mu, _ = mu_comp(tL, tU, lL, lU)
+            alpha = np.ones(B, P.dtype)
+            recentre = np.zeros(B, bool)                       # the last iterate was a candidate whose stationarity was too large
+            for it in range(1, int(iters) + 1):
+                if not open_.any():
+                    break
+                sigma = np.where(recentre, 1.0, np.where(alpha >= self.IPM_ALPHA_SHORT, self.IPM_SIGMA, self.IPM_SIGMA_SHORT))
+                sm = sigma * mu
+                sm = np.where(sm > self.IPM_TARGET * comp_tol, sm, self.IPM_TARGET * comp_tol)[:, None, None]
+                rL = lL / tL; rU = lU / tU
+                hadd = np.where(mL, rL, 0.0) + np.where(mU, rU, 0.0)
+                qadd = np.where(mL, -((sm / tL + lL) + rL * lz), 0.0) + np.where(mU, (sm / tU + lU) - rU * uz, 0.0)
+                dn, _, _, _, bad = self._direct_active_round(P, q, A, l, u, reg, pin, cval, hadd=hadd, qadd=qadd)
+                dw = dn - d
+                dtL = dw + ((d - lz) - tL); dtU = ((uz - d) - tU) - dw
+                dlL = (sm / tL - lL) - rL * dtL; dlU = (sm / tU - lU) - rU * dtU
+                amin = np.full((B, f), np.inf, P.dtype)
+                for k in range(N):
+                    for msk, v, dv in ((mL, tL, dtL), (mL, lL, dlL), (mU, tU, dtU), (mU, lU, dlU)):
+                        r_ = np.where(msk[:, k] & (dv[:, k] < 0.0), -v[:, k] / dv[:, k], np.inf)
+                        amin = np.where(r_ < amin, r_, amin)
+                amin = across(amin, np.fmin) * self.IPM_FRAC
+                alpha_n = np.where(amin < 1.0, amin, 1.0)
+                lost = open_ & (bad | ~((alpha_n > 0.0) & (alpha_n <= 1.0)))
+                used[lost] = it
+                open_ = open_ & ~lost
+                up = open_[:, None, None]
+                a3 = alpha_n[:, None, None]
+                d = np.where(up, d + a3 * dw, d)
+                tL = np.where(up & mL, tL + a3 * dtL, tL); tU = np.where(up & mU, tU + a3 * dtU, tU)
+                lL = np.where(up & mL, lL + a3 * dlL, lL); lU = np.where(up & mU, lU + a3 * dlU, lU)
+                alpha = np.where(open_, alpha_n, alpha)
+                mun, comp = mu_comp(tL, tU, lL, lU)
+                mu = np.where(open_, mun, mu)
+                pv = viol(d)
+                res[open_, 0] = pv[open_]; res[open_, 1] = comp[open_]; res[open_, 2] = np.nan
+                used[open_] = it
+                cand = open_ & box_ok(d) & (comp <= comp_tol) & (mu <= comp_tol)
+                recentre = cand
+                if trace is not None:
+                    trace.append(dict(it=it, open=open_.copy(), alpha=alpha_n.copy(), mu=mu.copy(), comp=comp.copy(), pv=pv.copy(), cand=cand.copy(),
+                                      d=d.copy(), stat=np.full(B, np.nan)))
+                if cand.any():
+                    wc = np.zeros((B, n), P.dtype); wc[:, npp:] = d.reshape(B, -1)
+                    yid = lU - lL
+                    val = self._direct_ipm_adjoint(P, q, A, wc, yid)
+                    stat = across(np.max(np.where(bar & (np.arange(f) >= nx), np.abs(val - reg * d), 0.0), axis=1), np.fmax)
+                    if trace is not None:
+                        trace[-1]["stat"] = np.where(cand, stat, np.nan)
+                    yc = np.zeros((B, m), P.dtype); zc = np.zeros((B, m), P.dtype)
+                    yc[:, npp:n] = np.where(bar, yid, val).reshape(B, -1)
+                    for k in range(1, N):
+                        yc[:, n + (k - 1) * nx:n + k * nx] = val[:, k, :nx]
+                    hslot, k0slot, k1slot, pcols = self._direct_slots()
+                    for j in range(npp):
+                        slots, rws = pcols[j]
+                        acc = np.zeros(B, P.dtype)
+                        for e_, r_ in zip(slots, rws):
+                            acc = acc + P[:, e_] * wc[:, npp + r_]
+                        yc[:, j] = -(acc + q[:, j])
+                    zc[:, :n] = wc
+                    zc[:, n:rowh] = l[:, n:rowh]
+
+                    def row(slots, dk, acc):
+                        for c in range(f):
+                            if slots[c] >= 0:
+                                acc = acc + A[:, slots[c]] * dk[:, c]
+                        return acc
+                    rowk = rowh + N * self.nh
+                    for k in range(N):
+                        for r in range(self.nh):
+                            zc[:, rowh + k * self.nh + r] = row(hslot[k, r], d[:, k], np.zeros(B, P.dtype))
+                        if k < N - 1:
+                            for r in range(self.nk):
+                                zc[:, rowk + k * self.nk + r] = row(k1slot[k, r], d[:, k + 1], row(k0slot[k, r], d[:, k], np.zeros(B, P.dtype)))
+                    res[cand, 2] = stat[cand]
+                    rok = rows_ok(zc)
+                    if trace is not None:
+                        trace[-1]["z"] = zc.copy()
+                    open_ = open_ & ~(cand & ~rok)
+                    take = cand & rok & (stat <= stat_tol)
+                    w[take] = wc[take]; y[take] = yc[take]; z[take] = zc[take]; direct[take] = 1
+                    open_ = open_ & ~take
+        direct = np.where(alive, np.where(~el, -1, direct), 0).astype(np.int32)
+        gone = ~alive | (direct < 0)
+        used[gone] = -1; res[gone] = np.nan
+        return w, y, z, direct, used, res
 
     def feedback(self, K, k, s, s_nom, u_nom, lo=None, hi=None, x=None, lbx=None, ubx=None):
         """Host statement of mpcqp_stage_feedback: u = clip(u_nom + K[:, k] (s - s_nom)) with the sum over the state entries in ascending order,

@@ -22,6 +22,8 @@ class ClosedLoopMPC:
         options["direct_qp"]: a tick's QP is first solved directly where no inequality is active; the hand-over takes the merged
         dw, y and status, and sol.direct_history holds the verdicts per tick.  With its "active_set" key the set of held inputs a tick
         ends with (sol.act) is shifted by one frame with the plan -- a device slice copy, the last frame repeats -- and is the next tick's guess.
+        With its "interior_point" key the QPs whose plans ride state bounds are solved directly as well; nothing is carried between ticks,
+        and sol.direct_iters_history holds the iteration counts per tick.
         shift_data=False: a tick does not shift the stored stage data -- rows that belong to horizon positions, not to world time (the step
         lengths of a non-uniform time grid, models.StageOCP.transition_data); tick's d_new is then a ValueError.
         feedback=True or {"clamp_tol": ..., "reg": ...}: every tick also computes the time-varying LQR gains around its plan (one

@@ -66,6 +66,11 @@ input box rows (models.StageOCP.direct_qp_active, mpcqp_stage_riccati_solve_acti
 one whose multiplier has the wrong sign is released, and an instance is accepted when a round's point meets the QP's KKT conditions.  State bounds, path
 rows and link rows are still only tested.  The set a call ends with is the next call's guess (`act` on the device loop); `direct_rounds_history` sits
 beside `direct_history`.  Without the key nothing changes.
+With {"interior_point": True, "iters": 30, "comp_tol": 1e-6, "stat_tol": 1e-5} instead, the direct solve is followed by up to `iters` (1 .. 50) iterations of a
+primal-dual interior-point method over the box rows of the free variables, states included (models.StageOCP.direct_qp_ipm, mpcqp_stage_riccati_solve_ipm;
+DESIGN 6.32): a barrier term sits on the diagonal of H_k and in q_k alone, so an iteration is one backward and one forward pass of the direct solve.  An
+accepted point meets the QP's KKT conditions within (feas_tol, comp_tol, stat_tol); feas_tol defaults to 1e-9 here.  Path rows and link rows are still only
+tested.  `direct_iters_history` sits beside `direct_history`; nothing is carried from one QP to the next.  Refused together with "active_set".
 
 The model supplies what CasADi's generated localSystemFunction_ supplies in the reference
 (optimal_control_problem_amd.models).  The QP backend is any object with the CuCaQP interface.
@@ -168,10 +173,12 @@ def _direct_qp_option(options, model, evaluator=None):
     if value is not True and not isinstance(value, dict):
         raise ValueError("direct_qp: expected True or a dict with feas_tol and / or reg")
     d = {} if value is True else value
-    unknown = set(d) - {"feas_tol", "reg", "active_set", "rounds", "dual_tol"}
+    unknown = set(d) - {"feas_tol", "reg", "active_set", "rounds", "dual_tol", "interior_point", "iters", "comp_tol", "stat_tol"}
     if unknown:
-        raise ValueError("direct_qp: unknown keys %s (feas_tol, reg, active_set, rounds and dual_tol are the options)" % sorted(unknown))
-    feas_tol, reg = float(d.get("feas_tol", 0.0)), float(d.get("reg", 0.0))
+        raise ValueError("direct_qp: unknown keys %s (feas_tol, reg, active_set, rounds, dual_tol, interior_point, iters, comp_tol and stat_tol are "
+                         "the options)" % sorted(unknown))
+    # (with "interior_point": True an absent feas_tol is 1e-9: at 0 a rounding error of one ulp in w - l would reject)
+    feas_tol, reg = float(d.get("feas_tol", 1e-9 if d.get("interior_point") is True else 0.0)), float(d.get("reg", 0.0))
     if not (feas_tol >= 0.0) or not (reg >= 0.0):
         raise ValueError("direct_qp: feas_tol and reg must not be negative")
     if evaluator is not None or _is_general(model) or not hasattr(model, "direct_qp"):
@@ -202,6 +209,32 @@ def _direct_active_option(options):
     if not (dual_tol >= 0.0):
         raise ValueError("direct_qp: dual_tol must not be negative")
     return int(rounds), dual_tol
+
+
+IPM_KEYS = ("iters", "comp_tol", "stat_tol")
+
+
+def _direct_ipm_option(options):
+    """the interior-point keys of options["direct_qp"]: None without "interior_point": True, else (iters, comp_tol, stat_tol) -- iters
+    1 .. 50, default 30; comp_tol >= 0, default 1e-6; stat_tol >= 0, default 1e-5.  Called behind _direct_qp_option, whose refusals apply unchanged."""
+    value = options.get("direct_qp")
+    if not isinstance(value, dict):
+        return None
+    if value.get("interior_point") is not None and not isinstance(value.get("interior_point"), bool):      # (1 is not True: one predicate with _direct_qp_option)
+        raise ValueError("direct_qp: interior_point: expected True or False")
+    if not value.get("interior_point"):
+        if any(k in value for k in IPM_KEYS):
+            raise ValueError('direct_qp: iters, comp_tol and stat_tol belong to "interior_point": True')
+        return None
+    if value.get("active_set"):
+        raise ValueError('direct_qp: "interior_point" does not combine with "active_set": the interior-point iterations treat the input bounds '
+                         'themselves, and a held set has no meaning for them')
+    iters, comp_tol, stat_tol = value.get("iters", 30), float(value.get("comp_tol", 1e-6)), float(value.get("stat_tol", 1e-5))
+    if isinstance(iters, bool) or int(iters) != iters or not 1 <= iters <= _lib.IPM_MAX_ITERS:
+        raise ValueError("direct_qp: iters: expected 1 .. %d" % _lib.IPM_MAX_ITERS)
+    if not (comp_tol >= 0.0) or not (stat_tol >= 0.0):
+        raise ValueError("direct_qp: comp_tol and stat_tol must not be negative")
+    return int(iters), comp_tol, stat_tol
 
 
 def _line_search_options(value):
@@ -336,6 +369,9 @@ class SQPOptimizationSolver:
         self.direct_active = _direct_active_option(options) if self.direct_qp is not None else None
         self.direct_rounds_history = []
         self._act = None
+        # "interior_point": True: models.StageOCP.direct_qp_ipm in its place; nothing is carried from one QP to the next
+        self.direct_ipm = _direct_ipm_option(options) if self.direct_qp is not None else None
+        self.direct_iters_history = []
         self.line_search = _line_search_options(options.get("line_search"))
         if self.line_search is not None and not hasattr(nlp, "line_search"):
             raise ValueError("line_search needs a stage OCP (models.StageOCP) or a general NLP (general_nlp.GeneralNLP): this model states no merit line search")
@@ -438,7 +474,13 @@ class SQPOptimizationSolver:
                     if self.carry_rho and hasattr(self.qpSolver_, "setRhoStart"):
                         self.qpSolver_.setRhoStart(info["rho"])
             taken = None
-            if self.direct_active is not None:
+            if self.direct_ipm is not None:
+                dq = self.model.direct_qp_ipm(localSystem.P, localSystem.q, localSystem.A, localSystem.l, localSystem.u, self.direct_qp[0], self.direct_qp[1],
+                                              iters=self.direct_ipm[0], comp_tol=self.direct_ipm[1], stat_tol=self.direct_ipm[2], frozen=frozen.astype(np.int32))
+                self.direct_iters_history.append(dq[4].copy())
+                taken = dq[3] > 0
+                self.direct_history.append(dq[3].copy())
+            elif self.direct_active is not None:
                 dq = self.model.direct_qp_active(localSystem.P, localSystem.q, localSystem.A, localSystem.l, localSystem.u, self.direct_qp[0], self.direct_qp[1],
                                                  rounds=self.direct_active[0], dual_tol=self.direct_active[1], act=self._act, frozen=frozen.astype(np.int32))
                 self._act = dq[4]
@@ -615,6 +657,10 @@ class DeviceSQPOptimizationSolver:
         # direct_history.  Without the key the entry above is called and nothing else changes.
         self.direct_active = _direct_active_option(options) if self.direct_qp is not None else None
         self.direct_rounds_history = []
+        # "interior_point": True: mpcqp_stage_riccati_solve_ipm in its place; direct_iters_history sits beside direct_history.  No
+        # state is carried between calls.
+        self.direct_ipm = _direct_ipm_option(options) if self.direct_qp is not None else None
+        self.direct_iters_history = []
         # extension (opt-in): a step length per instance by an l1-merit backtracking search starting at options["alpha"] -- one kernel
         # (mpcqp_stage_linesearch; mpcqp_nlp_linesearch with a general evaluator that has it) in place of the step + merit pair; see the module
         # docstring.  It always honours the QP status.
@@ -694,6 +740,9 @@ class DeviceSQPOptimizationSolver:
                 self.act = torch.zeros((self.batch, self.ev.horizon, self.ev.nu), dtype=torch.int32, device=self.dev)
                 self._dq["act"] = self.act
                 self._dq["rounds_used"] = torch.full((self.batch,), -1, dtype=torch.int32, device=self.dev)
+            if self.direct_ipm is not None:
+                self._dq["iters_used"] = torch.full((self.batch,), -1, dtype=torch.int32, device=self.dev)
+                self._dq["res"] = torch.full((self.batch, 3), float("nan"), dtype=torch.float64, device=self.dev)
 
     def _create_qp(self, presolve_bounds):
         import torch
@@ -795,7 +844,12 @@ class DeviceSQPOptimizationSolver:
                 self.convexified.append(self._touched.clone())
             direct = self.direct_qp is not None
             if direct:       # P is final: solve directly, test, and leave the accepted instances out of the QP launch
-                if self.direct_active is not None:
+                if self.direct_ipm is not None:
+                    self._dq["iters_used"].fill_(-1)         # (an ineligible, failed or frozen instance writes none)
+                    ev.riccati_solve_ipm(self.ls, self.direct_qp[0], self.direct_qp[1], iters=self.direct_ipm[0], comp_tol=self.direct_ipm[1],
+                                         stat_tol=self.direct_ipm[2], frozen=self._kkt_conv if kkt and i >= 1 else None, out=self._dq, stream=stream)
+                    self.direct_iters_history.append(self._dq["iters_used"].clone())
+                elif self.direct_active is not None:
                     self._dq["rounds_used"].fill_(-1)        # (an ineligible, failed or frozen instance writes none)
                     ev.riccati_solve_active(self.ls, self.direct_qp[0], self.direct_qp[1], rounds=self.direct_active[0], dual_tol=self.direct_active[1],
                                             act_in=self.act, frozen=self._kkt_conv if kkt and i >= 1 else None, out=self._dq, stream=stream)

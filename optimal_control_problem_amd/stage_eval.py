@@ -116,6 +116,7 @@ def _bind(L):
     L.mpcqp_stage_riccati.argtypes = [vp, C.c_int, C.POINTER(RiccatiArgs), vp]
     L.mpcqp_stage_riccati_solve.argtypes = [vp, C.c_int, C.POINTER(RiccatiSolveArgs), vp]
     L.mpcqp_stage_riccati_solve_active.argtypes = [vp, C.c_int, C.POINTER(_lib.RiccatiSolveActiveArgs), vp]
+    L.mpcqp_stage_riccati_solve_ipm.argtypes = [vp, C.c_int, C.POINTER(_lib.RiccatiSolveIpmArgs), vp]
     L.mpcqp_stage_feedback.argtypes = [vp, C.c_int, C.POINTER(FeedbackArgs), vp]
     L._stage_bound = True
     return L
@@ -608,6 +609,43 @@ class StageEvaluator:
         if frozen is not None:
             a.frozen = _check_int32(frozen, B, "frozen")
         _lib.check(_lib.lib().mpcqp_stage_riccati_solve_active(self._h, B, C.byref(a), stream))
+        return out
+
+    def riccati_solve_ipm(self, ls, feas_tol=1e-9, reg=0.0, iters=30, comp_tol=1e-6, stat_tol=1e-5, frozen=None, out=None, stream=None):
+        """riccati_solve with interior-point iterations over the box rows of the free variables, states included, one kernel
+        (mpcqp_stage_riccati_solve_ipm; models.StageOCP.direct_qp_ipm is its host statement): iteration 0 is riccati_solve, then up to `iters`
+        (1 .. 50) primal-dual iterations, each one backward and one forward pass on barrier-modified data.  An accepted point meets the QP's KKT
+        conditions within (feas_tol, comp_tol, stat_tol).  Returns riccati_solve's dict plus iters_used (int32 [B]) and res (float64 [B, 3]: primal
+        violation, max lambda t, stationarity at the exit point); `out` may hold them.  An ineligible, failed or frozen instance has neither
+        written.  The first call of a handle (and the first at a larger batch) may not run under stream capture."""
+        import torch
+        P = ls["P"]
+        if not isinstance(P, torch.Tensor) or P.dim() != 2:
+            raise ValueError("P: expected a contiguous float64 CUDA tensor of shape (B, %d)" % self.nnzP)
+        if not (feas_tol >= 0.0) or not (reg >= 0.0) or not (comp_tol >= 0.0) or not (stat_tol >= 0.0):
+            raise ValueError("feas_tol, reg, comp_tol and stat_tol must not be negative")
+        if isinstance(iters, bool) or int(iters) != iters or not 1 <= iters <= _lib.IPM_MAX_ITERS:
+            raise ValueError("iters: expected 1 .. %d" % _lib.IPM_MAX_ITERS)
+        B = P.shape[0]
+        a = _lib.RiccatiSolveIpmArgs()
+        a.P, a.q, a.A = _check(P, (B, self.nnzP), "P"), _check(ls["q"], (B, self.n), "q"), _check(ls["A"], (B, self.nnzA), "A")
+        a.l, a.u = _check(ls["l"], (B, self.m), "l"), _check(ls["u"], (B, self.m), "u")
+        a.feas_tol, a.reg, a.iters, a.comp_tol, a.stat_tol = float(feas_tol), float(reg), int(iters), float(comp_tol), float(stat_tol)
+        if out is None:
+            out = {"w": torch.zeros((B, self.n), dtype=torch.float64, device=P.device), "y": torch.zeros((B, self.m), dtype=torch.float64, device=P.device),
+                   "z": torch.zeros((B, self.m), dtype=torch.float64, device=P.device), "direct": torch.zeros((B,), dtype=torch.int32, device=P.device)}
+        if out.get("iters_used") is None:
+            out["iters_used"] = torch.full((B,), -1, dtype=torch.int32, device=P.device)
+        if out.get("res") is None:
+            out["res"] = torch.full((B, 3), float("nan"), dtype=torch.float64, device=P.device)
+        a.w, a.y = _check(out["w"], (B, self.n), "w"), _check(out["y"], (B, self.m), "y")
+        if out.get("z") is not None:
+            a.z = _check(out["z"], (B, self.m), "z")
+        a.direct = _check_int32(out["direct"], B, "direct")
+        a.iters_used, a.res = _check_int32(out["iters_used"], B, "iters_used"), _check(out["res"], (B, 3), "res")
+        if frozen is not None:
+            a.frozen = _check_int32(frozen, B, "frozen")
+        _lib.check(_lib.lib().mpcqp_stage_riccati_solve_ipm(self._h, B, C.byref(a), stream))
         return out
 
     @staticmethod
